@@ -2,7 +2,13 @@
 """bench.py -- ms per Levenberg-Marquardt iteration of the MI355X bundle-adjustment backend.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--scale S]
-                  [--mode selfcal|ba] [--variant sparse|iterative] [--no-cpu-baseline]
+                  [--mode selfcal|ba] [--variant sparse|iterative] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-other-variants] [--no-other-workloads]]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last step (--dump-outputs) and prints the line.
+--full adds everything else behind the timed region: the per-stage table and the rooflines (HIP events on two stages inside
+the timed region, the other stages over a few further iterations), the other Schur variants, the CPU baseline and the
+short runs of the other BASELINE.json configurations.
 
 A "step" is one LM iteration on a synthetic BA problem of the named BASELINE.json shape
 (--workload sphere2500 runs the SE3 pose-graph path of BASELINE configs[1] instead):
@@ -31,6 +37,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md): 8 TB/s
+DUMP_MAX_ROWS = 1 << 20    # --dump-outputs: a larger array is written as a seeded sample of this many rows
+DUMP_MAX_BYTES = 64 << 20
 
 
 def parse():
@@ -43,9 +51,11 @@ def parse():
     ap.add_argument("--mode", default="selfcal", choices=["selfcal", "ba"])
     ap.add_argument("--variant", default="sparse", choices=["sparse", "iterative", "implicit"])
     ap.add_argument("--cg", default="", help="max_iter,tol of the PCG variants (default: the reference's 200,1e-6 / implicit 500,1e-9)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-variants", action="store_true", help="skip the Iterative / matrix-free runs that follow the timed region of a Sparse run")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the short runs of the other BASELINE.json configurations that follow the headline's timed region")
+    ap.add_argument("--full", action="store_true", help="also the stage table, rooflines, other variants, CPU baseline and other workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-other-variants", action="store_true", help="--full: skip the Iterative / matrix-free runs that follow the timed region of a Sparse run")
+    ap.add_argument("--no-other-workloads", action="store_true", help="--full: skip the short runs of the other BASELINE.json configurations that follow the headline's timed region")
     ap.add_argument("--comm", choices=("auto", "rccl", "shm"), default="auto", help="N > 1: the library's transport (auto: RCCL, host shared memory if RCCL cannot be initialised)")
     ap.add_argument("--opt", action="append", default=[], help="implementation switch name=value (apexgpu_set_option), repeatable")
     ap.add_argument("--cpu-sample-scale", type=float, default=0.0, help="0: full size when the reference's dense S fits (<= 2300 cameras), else a ~1000-camera sample")
@@ -72,6 +82,26 @@ def lm_step(s, state):
         state["nu"] *= 2.0
         s.discard_step()
     state["hist"].append((state["cost"], rho))
+
+
+def dump_outputs(folder, arrays):
+    """--dump-outputs: one float64 DIR/<name>.npy per array.  An array of more than DUMP_MAX_ROWS rows is written as the
+    rows of a fixed seeded sample (the same rows for the same shape in every run), their row numbers beside it as
+    <name>_rows.npy; the whole stays under DUMP_MAX_BYTES."""
+    files = {}
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim > 0 and a.shape[0] > DUMP_MAX_ROWS:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_MAX_ROWS, replace=False))
+            files[name + "_rows"] = rows.astype(np.float64)
+            a = a[rows]
+        files[name] = np.ascontiguousarray(a)
+    total = sum(a.nbytes for a in files.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(folder, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(folder, name + ".npy"), a)
 
 
 def usable_cores():
@@ -210,8 +240,10 @@ def factor_roofline(info, f_ms, note=None):
     return out
 
 
-def run_pose_graph(args, torch, dist, world, pg_dev, dev, steps, warmup, scale=1.0, workload="sphere2500", cpu_base=True, timing_barrier=True):
-    """One pose-graph measurement (the body of bench_pose_graph; also a line of `other_workloads`)."""
+def run_pose_graph(args, torch, dist, world, pg_dev, dev, steps, warmup, scale=1.0, workload="sphere2500", cpu_base=True, timing_barrier=True,
+                   full=True, dump=None):
+    """One pose-graph measurement (the body of bench_pose_graph; also a line of `other_workloads`).  full=False: the timed
+    region alone, without the stage table, the roofline and the CPU baseline; dump: folder of --dump-outputs."""
     import apex_solver_amd as pkg
     from apex_solver_amd.pose_graph import GpuSparseCholeskySolver, PoseGraphProblem
 
@@ -225,7 +257,7 @@ def run_pose_graph(args, torch, dist, world, pg_dev, dev, steps, warmup, scale=1
     s = GpuSparseCholeskySolver(dev).initialize_structure(prob)
     s.set_parameters(d.poses)
     info = s.info()
-    st8 = dict(lam=1e-3, nu=2.0, cost=s.compute_cost(), accepted=0)
+    st8 = dict(lam=1e-3, nu=2.0, cost=s.compute_cost(), accepted=0, hist=[])
     initial_cost = st8["cost"]
 
     def step():
@@ -240,6 +272,7 @@ def run_pose_graph(args, torch, dist, world, pg_dev, dev, steps, warmup, scale=1
             st8["cost"] = nc; s.commit_step(); st8["accepted"] += 1
         else:
             st8["lam"] = min(st8["lam"] * st8["nu"], 1e12); st8["nu"] *= 2.0; s.discard_step()
+        st8["hist"].append((st8["cost"], rho))
 
     for _ in range(warmup):
         step()
@@ -250,9 +283,10 @@ def run_pose_graph(args, torch, dist, world, pg_dev, dev, steps, warmup, scale=1
             dist.barrier()
         torch.cuda.synchronize()
 
-    # (inside the timed region the factorisation alone is timed -- this workload's roofline; the other stages over a few
-    # iterations behind it: see main())
-    s.enable_stage_timing(2 << pkg.capi.PG_STAGE_NAMES.index("factor")); s.reset_stage_times()
+    # (--full: inside the timed region the factorisation alone is timed -- this workload's roofline; the other stages over a
+    # few iterations behind it: see main())
+    if full:
+        s.enable_stage_timing(2 << pkg.capi.PG_STAGE_NAMES.index("factor")); s.reset_stage_times()
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
@@ -263,10 +297,23 @@ def run_pose_graph(args, torch, dist, world, pg_dev, dev, steps, warmup, scale=1
         t = torch.tensor([elapsed], dtype=torch.float64, device=pg_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    stages_timed = s.stage_times()
     ms = elapsed * 1e3 / steps
-    f_ms = stages_timed["factor"][0] / max(stages_timed["factor"][1], 1)
     cost_region, accepted_region = st8["cost"], st8["accepted"]
+    if dump:
+        poses = s.get_parameters()
+        if rank == 0:
+            dump_outputs(dump, {"poses": poses, "lm_history": st8["hist"][warmup:warmup + steps]})
+    out = {"metric": "ms per LM iter (Jacobian+JtJ+Cholesky)", "value": ms, "unit": "ms", "n_gpus": world, "steps": steps,
+           "warmup": warmup, "ms_per_step": ms, "higher_is_better": False, "scaling": "weak", "vs_baseline": None,
+           "dtype": "f64", "data": data_kind,
+           "config": {"workload": f"{d.name} {data_kind} SE3 pose graph ({d.n_v} vertices / {d.n_e} edges)" + (f" from {data_src}" if data_src else ""), "tile_rows": info["tile_rows"],
+                      "tiles": info["tiles"], "etree_levels": info["etree_levels"], "parallelism": f"replicas x{world}"},
+           "initial_cost": initial_cost, "final_cost": cost_region, "accepted_steps": accepted_region}
+    if not full:
+        s.close()
+        return out
+    stages_timed = s.stage_times()
+    f_ms = stages_timed["factor"][0] / max(stages_timed["factor"][1], 1)
     stage_steps = max(2, min(5, steps))
     s.enable_stage_timing(True); s.reset_stage_times()
     for _ in range(stage_steps):
@@ -275,14 +322,8 @@ def run_pose_graph(args, torch, dist, world, pg_dev, dev, steps, warmup, scale=1
     stages = s.stage_times()
     per_step = {k: v[0] / stage_steps for k, v in stages.items()}
     per_step["factor"] = stages_timed["factor"][0] / steps
-    out = {"metric": "ms per LM iter (Jacobian+JtJ+Cholesky)", "value": ms, "unit": "ms", "n_gpus": world, "steps": steps,
-           "warmup": warmup, "ms_per_step": ms, "higher_is_better": False, "scaling": "weak", "vs_baseline": None,
-           "dtype": "f64", "data": data_kind,
-           "config": {"workload": f"{d.name} {data_kind} SE3 pose graph ({d.n_v} vertices / {d.n_e} edges)" + (f" from {data_src}" if data_src else ""), "tile_rows": info["tile_rows"],
-                      "tiles": info["tiles"], "etree_levels": info["etree_levels"], "parallelism": f"replicas x{world}"},
-           "roofline": factor_roofline(info, f_ms, "17-68 dependent levels: latency-bound at this size"),
-           "stages_ms_per_step": per_step,
-           "initial_cost": initial_cost, "final_cost": cost_region, "accepted_steps": accepted_region}
+    out["roofline"] = factor_roofline(info, f_ms, "17-68 dependent levels: latency-bound at this size")
+    out["stages_ms_per_step"] = per_step
     if rank == 0 and world == 1 and cpu_base:
         try:
             from oracle import pg_oracle as po
@@ -316,7 +357,7 @@ def bench_pose_graph(args):
         import torch.distributed as dist
         dev, pg_dev = process_group(torch, local_rank)
     out = run_pose_graph(args, torch, dist if world > 1 else None, world, pg_dev, dev, args.steps, args.warmup, args.scale, args.workload,
-                         cpu_base=not args.no_cpu_baseline)
+                         cpu_base=not args.no_cpu_baseline, full=args.full, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(out))
     if world > 1:
@@ -529,14 +570,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # Inside the timed region only the two stages with a roofline of their own are timed (HIP events on the solver's stream around
+    # --full: inside the timed region only the two stages with a roofline of their own are timed (HIP events on the solver's stream around
     # k_schur_pairs_r, the graded kernel, and around the factorisation: roofline.avg_launch_ms and factor.avg_factor_ms are measured
     # live, over these very steps); the eighteen events per iteration of the full stage table cost the stream ~0.1 ms per
     # iteration (round 5: 12.88 against 12.69 ms, three pairs of runs), so the other stages are timed over `stage_steps` further
     # iterations right behind the timed region (a later LM state: `stage_sum_ms` beside `value` says how far the table is off).
     sc_stage, fa_stage = pkg.capi.STAGE_NAMES.index("schur_scatter"), pkg.capi.STAGE_NAMES.index("factor")
-    s.enable_stage_timing((2 << sc_stage) | ((2 << fa_stage) if args.variant == "sparse" else 0))
-    s.reset_stage_times()
+    if args.full:
+        s.enable_stage_timing((2 << sc_stage) | ((2 << fa_stage) if args.variant == "sparse" else 0))
+        s.reset_stage_times()
     accepted_before = state["accepted"]
     barrier()
     t0 = time.perf_counter()
@@ -548,10 +590,46 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=pg_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    stages_timed = s.stage_times()
     ms_per_step = elapsed * 1e3 / args.steps
     accepted_in_region = state["accepted"] - accepted_before
     final_cost_region = state["cost"]
+    if args.dump_outputs:   # (on every rank: the points of the other ranks' landmark ranges are gathered)
+        poses, intr, points = s.get_parameters()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"poses": poses, "intrinsics": intr, "points": points,
+                                             "lm_history": state["hist"][args.warmup:args.warmup + args.steps]})
+    dc = 9 if args.mode == "selfcal" else 6
+    form = info.get("schur_form", 3)
+    st = s.setup_times()
+    out = {
+        "metric": "ms per LM iter (Jacobian+Schur+solve)", "value": ms_per_step, "unit": "ms", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": False,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": data_kind,
+        "config": {"workload": f"{d.name} {data_kind} ({d.n_cam} cameras / {d.n_pt} landmarks / {d.n_obs} observations)" + (f" from {data_src}" if data_src else ""),
+                   "optimization_type": args.mode, "camera_dof": dc, "schur_variant": args.variant, "huber": 1.0,
+                   "s_tile_rows": info["tile_rows"], "s_tiles": info["tiles"], "s_tiles_touched": info["touched_tiles"],
+                   "etree_levels": info["etree_levels"], "border_cameras": st["hub_cameras"], "schur_form": form, "setup_s": setup_s,
+                   "host_cache_bytes": int(pkg.capi.load().apexgpu_host_cache_bytes()), **s.variant_info(), **({"transport": comm_kind} if world > 1 else {}), "parallelism": f"landmark-shard x{world}" + (f", landmarks and Cholesky distributed by elimination subtree ({info['dist_top_columns']} shared top tile columns, tree_sharded={info.get('tree_sharded')})" if info.get("dist_top_columns") else "")},
+        "setup_s": setup_s, "setup_by_phase_s": {k: st[k] for k in ("order", "lists", "tile_plan", "schur_lists", "uploads", "total")},
+        # the whole of setup_s by piece: handle creation (the process's first HIP call = runtime start-up), the host-side
+        # argument arrays, apexgpu_set_structure (= setup_by_phase_s.total + its argument checks), the parameter upload
+        "setup_wall_s": dict(getattr(s, "setup_wall", {})),
+        "initial_cost": initial_cost, "final_cost": final_cost_region, "accepted_steps": accepted_in_region,
+        "accepted_steps_incl_warmup": state["accepted"],
+        "obs_per_s": d.n_obs / (ms_per_step * 1e-3),
+    }
+    if args.variant != "sparse":
+        out["pcg_iterations_per_step"] = state["pcg"][args.warmup:args.warmup + args.steps]
+    if not args.full:
+        s.close()
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: the stage table, the rooflines, the other variants, the CPU baseline and the other workloads ------------
+    stages_timed = s.stage_times()
     stage_steps = max(2, min(5, args.steps))
     saved_params, saved_state = s.get_parameters(), {k: (list(v) if isinstance(v, list) else v) for k, v in state.items()}
     s.enable_stage_timing(True)
@@ -569,8 +647,6 @@ def main():
     state.clear(); state.update(saved_state)
 
     # ---- roofline of the graded Schur-reduction kernel, per launch -------------------------------------------------------
-    dc = 9 if args.mode == "selfcal" else 6
-    form = info.get("schur_form", 3)
     kernel = "k_schur_pairs_r"   # (form 4: the queued layout of the pair list, 3: one running block per wave)
     record_form = True
     n_obs_local = info["local_obs"]
@@ -583,7 +659,6 @@ def main():
                  + 96.0 * d.n_pt                # Hll^-1 and g_l per landmark
                  + tile_bytes * info["touched_tiles"]  # S tiles that receive contributions
                  + 8.0 * dc * d.n_cam)          # g_red
-    st = s.setup_times()
     pair_list_bytes = 16.0 * st["pair_slots"]   # the sorted pair list the default form streams (an index, like cam/pt idx)
     sc_ms, sc_n = stages["schur_scatter"]
     sc_avg = sc_ms / max(sc_n, 1)
@@ -639,15 +714,7 @@ def main():
     if fac:   # (scalars the driver's record keeps: the factorisation against ITS roof, the fp64 MFMA peak)
         roofline["factor_ms"] = fac["avg_factor_ms"]
         roofline["factor_mfma_frac"] = fac["frac"]
-    out = {
-        "metric": "ms per LM iter (Jacobian+Schur+solve)", "value": ms_per_step, "unit": "ms", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": False,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": data_kind,
-        "config": {"workload": f"{d.name} {data_kind} ({d.n_cam} cameras / {d.n_pt} landmarks / {d.n_obs} observations)" + (f" from {data_src}" if data_src else ""),
-                   "optimization_type": args.mode, "camera_dof": dc, "schur_variant": args.variant, "huber": 1.0,
-                   "s_tile_rows": info["tile_rows"], "s_tiles": info["tiles"], "s_tiles_touched": info["touched_tiles"],
-                   "etree_levels": info["etree_levels"], "border_cameras": st["hub_cameras"], "schur_form": form, "setup_s": setup_s,
-                   "host_cache_bytes": int(pkg.capi.load().apexgpu_host_cache_bytes()), **s.variant_info(), **({"transport": comm_kind} if world > 1 else {}), "parallelism": f"landmark-shard x{world}" + (f", landmarks and Cholesky distributed by elimination subtree ({info['dist_top_columns']} shared top tile columns, tree_sharded={info.get('tree_sharded')})" if info.get("dist_top_columns") else "")},
+    out.update({
         "roofline": roofline,
         # the stage that is half the step, against ITS roof (fp64 MFMA); only where a factorisation ran
         **({"factor": fac} if fac else {}),
@@ -656,17 +723,8 @@ def main():
         "stage_sum_ms": sum(per_step.values()),
         "stages_measured": f"schur_scatter (the graded kernel) and factor: HIP events inside the timed region, {args.steps} iterations; the other stages: {stage_steps} "
                            "further iterations right behind it with every stage event on (the full table costs the stream ~0.1 ms per iteration)",
-        "setup_s": setup_s, "setup_by_phase_s": {k: st[k] for k in ("order", "lists", "tile_plan", "schur_lists", "uploads", "total")},
-        # the whole of setup_s by piece: handle creation (the process's first HIP call = runtime start-up), the host-side
-        # argument arrays, apexgpu_set_structure (= setup_by_phase_s.total + its argument checks), the parameter upload
-        "setup_wall_s": dict(getattr(s, "setup_wall", {})),
-        "initial_cost": initial_cost, "final_cost": final_cost_region, "accepted_steps": accepted_in_region,
-        "accepted_steps_incl_warmup": state["accepted"],
-        "obs_per_s": d.n_obs / (ms_per_step * 1e-3),
-    }
-    if args.variant != "sparse":
-        out["pcg_iterations_per_step"] = state["pcg"][args.warmup:args.warmup + args.steps]
-    elif world == 1 and not args.no_other_variants:
+    })
+    if args.variant == "sparse" and world == 1 and not args.no_other_variants:
         # OUTSIDE the timed region, same handle, same problem, the optimisation simply goes on: the reference's BA default
         # (SchurVariant::Iterative, 200 Jacobi-PCG iterations at 1e-6 on the explicit S: levenberg_marquardt.rs:519-530 -- what
         # every BASELINE.md row was published with) and the matrix-free IterativeSchurSolver at ITS defaults (500 / 1e-9,

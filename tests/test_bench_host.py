@@ -70,3 +70,29 @@ def test_usable_cores_respects_affinity_and_quota():
 
     n = bench.usable_cores()
     assert 1 <= n <= len(os.sched_getaffinity(0))
+
+
+def test_dump_outputs_samples_large_arrays_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs on the host side: float64 files, a seeded sample (the same rows every time) of an array longer than
+    DUMP_MAX_ROWS with its row numbers beside it, and a refusal beyond the byte budget."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 100)
+    big = np.arange(3000, dtype=np.float64).reshape(1000, 3)
+    small = np.ones((7, 7), dtype=np.float32)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), {"big": big, "small": small, "hist": [(1.0, 0.5), (0.5, 0.25)]})
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(a) == ["big", "big_rows", "hist", "small"]
+    assert all(v.dtype == np.float64 for v in a.values())
+    rows = a["big_rows"].astype(np.int64)
+    assert rows.shape == (100,) and np.all(np.diff(rows) > 0) and np.array_equal(a["big"], big[rows])
+    assert np.array_equal(a["small"], small) and a["hist"].shape == (2, 2)
+    assert np.array_equal(np.load(tmp_path / "b" / "big_rows.npy"), a["big_rows"])
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1000)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "c"), {"big": big})
+    assert not (tmp_path / "c").exists()

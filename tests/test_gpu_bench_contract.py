@@ -1,16 +1,22 @@
-"""bench.py's one-line JSON contract (metric / value / roofline / cpu_baseline ...) on a small workload."""
+"""bench.py's one-line JSON contract on a small workload: the plain line (metric / value / ms_per_step ...) and its outputs
+(--dump-outputs), and the --full line (roofline / cpu_baseline ...)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+import apex_solver_amd as pkg
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-REQUIRED = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-            "dtype", "data", "config", "roofline", "cpu_baseline")
+PLAIN = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+         "dtype", "data", "config")
+REQUIRED = PLAIN + ("roofline", "cpu_baseline")
+FULL_ONLY = ("roofline", "cpu_baseline", "factor", "stages_ms_per_step", "other_variants", "fallback_implicit", "other_workloads")
 
 
 def run(*args):
@@ -22,7 +28,7 @@ def run(*args):
 
 
 def test_ba_line():
-    out = run("--workload", "ladybug-49", "--steps", "3", "--warmup", "1")
+    out = run("--workload", "ladybug-49", "--steps", "3", "--warmup", "1", "--full")
     for k in REQUIRED:
         assert k in out, k
     assert out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup"] == 1 and out["higher_is_better"] is False
@@ -44,10 +50,38 @@ def test_ba_line():
 
 
 def test_pose_graph_line():
-    out = run("--workload", "sphere2500", "--scale", "0.04", "--steps", "3", "--warmup", "1")
+    out = run("--workload", "sphere2500", "--scale", "0.04", "--steps", "3", "--warmup", "1", "--full")
     for k in REQUIRED:
         assert k in out, k
     assert out["roofline"]["bound"] == "mfma" and out["scaling"] == "weak" and out["final_cost"] < out["initial_cost"]
+
+
+def test_plain_ba_line_and_its_outputs(tmp_path):
+    """A plain run carries the headline and nothing that --full adds; --dump-outputs writes the parameters after the last timed
+    step (float64), and a second run with the same arguments starts from the same inputs: its line agrees on the costs."""
+    out = run("--workload", "ladybug-49", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / "a"))
+    for k in PLAIN:
+        assert k in out, k
+    for k in FULL_ONLY:
+        assert k not in out, k
+    assert out["steps"] == 4 and out["warmup"] == 1 and out["value"] == pytest.approx(out["ms_per_step"]) and out["value"] > 0
+    assert out["final_cost"] < out["initial_cost"]
+    d = pkg.synthetic.make_named("ladybug-49")
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("poses", "intrinsics", "points", "lm_history")}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["poses"].shape == (d.n_cam, 7) and a["intrinsics"].shape == (d.n_cam, 3) and a["points"].shape == (d.n_pt, 3)
+    assert a["lm_history"].shape == (4, 2) and a["lm_history"][-1, 0] == out["final_cost"]
+    assert not np.array_equal(a["points"], d.points)   # the steps moved the landmarks
+    again = run("--workload", "ladybug-49", "--steps", "4", "--warmup", "1")
+    assert again["initial_cost"] == out["initial_cost"]
+    assert again["final_cost"] == pytest.approx(out["final_cost"], rel=1e-6)
+
+
+def test_plain_pose_graph_outputs(tmp_path):
+    out = run("--workload", "sphere2500", "--scale", "0.04", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert "roofline" not in out and "cpu_baseline" not in out and out["ms_per_step"] > 0
+    poses, hist = np.load(tmp_path / "poses.npy"), np.load(tmp_path / "lm_history.npy")
+    assert poses.dtype == np.float64 and poses.shape[1] == 7 and hist.shape == (3, 2) and hist[-1, 0] == out["final_cost"]
 
 
 def test_two_ranks_fall_back_to_shared_memory_when_rccl_refuses():

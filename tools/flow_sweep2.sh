@@ -3,7 +3,7 @@ export APEX_SYNTH_CACHE=/tmp/apex_synth_cache
 O=gpurun_out; T=${1:-r04}
 run() {
   w=$1; shift; st=$1; shift
-  python3 bench.py --workload $w --steps $st --warmup 3 --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
+  python3 bench.py --full --workload $w --steps $st --warmup 3 --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
 import json,sys
 try:
     b=json.loads(sys.stdin.read().strip().splitlines()[-1]); st=b.get('stages_ms_per_step',{})

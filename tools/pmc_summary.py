@@ -21,7 +21,7 @@ def load(path, name):
 
 def main():
     f = load(sys.argv[1], "FETCH_SIZE"); w = load(sys.argv[2], "WRITE_SIZE")
-    out = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline",
+    out = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline",
            "workload": "final-13682 synthetic, selfcal (d_c=9), sparse variant, 1 GPU",
            "unit_note": "counter values are KB; corrected = (2*FETCH_SIZE + WRITE_SIZE)*1024 (gfx950: FETCH_SIZE tallies 128-B requests at 64 B)",
            "kernels": {}}

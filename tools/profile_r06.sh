@@ -8,16 +8,16 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out; T=r06
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has bench; then
-  timeout 900 python3 bench.py --steps 20 --warmup 5 > $O/${T}_bench_final13682.json 2> $O/${T}_bench.err
+  timeout 900 python3 bench.py --full --steps 20 --warmup 5 > $O/${T}_bench_final13682.json 2> $O/${T}_bench.err
   python3 -c "import json; b=json.load(open('$O/${T}_bench_final13682.json')); print('final-13682', b['value'], b['stages_ms_per_step'], 'iterative', b.get('iterative_ms'), 'implicit', b.get('fallback_implicit'), b['roofline']['frac'], b['roofline'].get('fp64_pipe_frac'), b['factor']['frac'], b['setup_s'], b['cpu_baseline'].get('value'))"
 fi
 if has stats; then
-  timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_stats -o st --output-format csv -- python3 bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-other-variants --no-other-workloads > $O/prof_stats.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_stats -o st --output-format csv -- python3 bench.py --full --steps 6 --warmup 1 --no-cpu-baseline --no-other-variants --no-other-workloads > $O/prof_stats.log 2>&1
   cp $O/prof_stats/st_kernel_stats.csv $O/${T}_final13682_kernel_stats.csv; head -14 $O/${T}_final13682_kernel_stats.csv | cut -c1-160
 fi
 if has pmc; then
-  timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/prof_fetch -o f --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-variants --no-other-workloads > $O/prof_fetch.log 2>&1
-  timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/prof_write -o w --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-variants --no-other-workloads > $O/prof_write.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/prof_fetch -o f --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-other-variants --no-other-workloads > $O/prof_fetch.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/prof_write -o w --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-other-variants --no-other-workloads > $O/prof_write.log 2>&1
   python3 tools/pmc_summary.py $O/prof_fetch/f_counter_collection.csv $O/prof_write/w_counter_collection.csv > $O/${T}_final13682_pmc_summary.json; head -c 700 $O/${T}_final13682_pmc_summary.json; echo
 fi
 if has timeline; then
@@ -25,11 +25,11 @@ if has timeline; then
   tools/timeline_run.sh ${T}_ladybug --workload ladybug-1723 > /dev/null 2>&1; head -5 $O/${T}_ladybug_factor_timeline.txt
 fi
 if has other; then
-  for w in ladybug-1723 venice-1778 sphere2500; do timeout 900 python3 bench.py --workload $w --steps 10 --warmup 3 > $O/${T}_bench_${w//-/}.json 2>/dev/null; done
-  timeout 600 python3 bench.py --workload final-13682-hub --steps 5 --warmup 2 --no-cpu-baseline --no-other-variants --no-other-workloads > $O/${T}_bench_final13682hub.json 2>/dev/null
-  timeout 600 python3 bench.py --mode ba --steps 10 --warmup 3 --no-cpu-baseline > $O/${T}_bench_final13682_ba6.json 2>/dev/null
-  timeout 600 python3 bench.py --workload synthetic-10k --steps 10 --warmup 3 --no-cpu-baseline > $O/${T}_bench_synthetic10k.json 2>/dev/null
-  timeout 600 python3 bench.py --workload synthetic-10k --variant implicit --steps 3 --warmup 1 --no-cpu-baseline > $O/${T}_bench_synthetic10k_implicit.json 2>/dev/null
+  for w in ladybug-1723 venice-1778 sphere2500; do timeout 900 python3 bench.py --full --workload $w --steps 10 --warmup 3 > $O/${T}_bench_${w//-/}.json 2>/dev/null; done
+  timeout 600 python3 bench.py --full --workload final-13682-hub --steps 5 --warmup 2 --no-cpu-baseline --no-other-variants --no-other-workloads > $O/${T}_bench_final13682hub.json 2>/dev/null
+  timeout 600 python3 bench.py --full --mode ba --steps 10 --warmup 3 --no-cpu-baseline > $O/${T}_bench_final13682_ba6.json 2>/dev/null
+  timeout 600 python3 bench.py --full --workload synthetic-10k --steps 10 --warmup 3 --no-cpu-baseline > $O/${T}_bench_synthetic10k.json 2>/dev/null
+  timeout 600 python3 bench.py --full --workload synthetic-10k --variant implicit --steps 3 --warmup 1 --no-cpu-baseline > $O/${T}_bench_synthetic10k_implicit.json 2>/dev/null
   for f in ladybug1723 venice1778 sphere2500 final13682hub final13682_ba6 synthetic10k synthetic10k_implicit; do python3 - $f <<'PY'
 import json, sys
 try:

@@ -18,7 +18,7 @@ os.environ.setdefault("APEX_SYNTH_CACHE", "/tmp/apex_synth_cache")
 
 
 def bench(workload, scale, extra, timeout=1500):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--scale", str(scale), "--no-cpu-baseline", "--no-other-variants",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", workload, "--scale", str(scale), "--no-cpu-baseline", "--no-other-variants",
            "--no-other-workloads", *extra]
     try:
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)

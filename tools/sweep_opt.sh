@@ -2,7 +2,7 @@
 # tools/sweep_opt.sh <option> <v1> <v2> ...   -- bench.py stage times for each value of an implementation switch
 opt=$1; shift
 for v in "$@"; do
-  python bench.py --steps 6 --warmup 2 --no-cpu-baseline --opt $opt=$v > /tmp/sweep_$v.json 2>/dev/null
+  python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --opt $opt=$v > /tmp/sweep_$v.json 2>/dev/null
   python3 - "$opt" "$v" <<'PY'
 import json, sys
 b = json.load(open(f"/tmp/sweep_{sys.argv[2]}.json")); st = b["stages_ms_per_step"]
