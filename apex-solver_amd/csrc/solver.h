@@ -110,7 +110,7 @@ class Solver : public LmBackend {
     void set_device_pair_recs(bool on) { device_pair_recs_ = on; }   // before set_structure ("device_pair_list")
     int get_pair_records(uint32_t* recs4_out, int64_t cap_slots);     // tests: the pair records as they sit on the device
     void set_auto_variant(bool on) { auto_variant_ = on; }
-    void set_variant_cost_permille(int pct) { variant_cost_permille_ = pct < 0 ? 0 : pct; }   // before set_structure (see build_plan)
+    void set_variant_cost_permille(int permille) { variant_cost_permille_ = permille < 0 ? 0 : permille; }   // before set_structure (see build_plan)
     // [0] predicted ms per solve of the direct path (tile Cholesky + sweeps; 0: never evaluated -- "matrix_free_only"), [1] of the
     // matrix-free PCG at IterativeSchurSolver's cap, [2] what set_structure chose: 0 direct, 1 matrix-free by predicted cost,
     // 2 matrix-free because the plan was refused (size / memory), 3 matrix-free by the caller's option, [3] the cap behind [1]

@@ -682,7 +682,7 @@ int Solver::assemble_local(double lambda, double diag_extra, bool for_factor) {
     stage_begin(kStAssembleCam);
     // (a tree-sharded rank that assembles for its distributed factorisation adds to its own and the top tiles only; every
     // other use of S -- PCG, exports, the ladder's diagonal -- all-reduces every touched tile and needs them all cleared)
-    HIP_TRY(tp_.zero_tiles(tree_shard_ && for_factor, nullptr, for_factor && world_ == 1));   // (the fill tiles stay as they are: tile_plan.h, first_writer_)
+    HIP_TRY(tp_.zero_tiles(tree_shard_ && for_factor, for_factor && world_ == 1));   // (the fill tiles stay as they are: tile_plan.h, first_ok_)
     launch_clear3(g_red_, g_c_, n_c_pad_, flags_, 4, stream_);   // (one launch instead of three fills)
     // identity on the padding rows of the last tile (rank 0 only: the all-reduce sums the ranks)
     // (tree sharding: by the owner of the last tile column, whose tiles are never summed -- pad_rank_)

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <array>
 #include <functional>
 #include <string>
 #include <utility>
@@ -31,8 +32,8 @@ namespace apex {
 // One call of the factorisation's launch sequence, as TilePlan::schedule_trace records it instead of issuing it.
 struct SchedOp {
     int op;             // 0 launch, 1 event record, 2 stream waits for event
-    uintptr_t stream;   // the stream the call goes to
-    uintptr_t event;    // record / wait: the event
+    uintptr_t stream;   // the stream the call goes to (TilePlan::StreamId)
+    uintptr_t event;    // record / wait: the event (level group * TilePlan::kLevelEvents + TilePlan::LevelEvent)
     int list;           // launch: 0 potrf, 1 panel solves, 2 updates, 3 the dataflow launch
     int64_t first;      // launch: first task (unit) of its list
     int count;          // ... and how many
@@ -53,8 +54,8 @@ class TilePlan {
     // present: lower-triangular nt x nt 0/1 structure (I >= J) in the FINAL order.
     // Returns "" on success or an error message.
     std::string build(int nt, const std::vector<uint8_t>& present, hipStream_t stream);
-    // build() without a device (tests): the same lists and decisions on made-up addresses; inspect with schedule_trace /
-    // check_schedule / flow_units_host.  Nothing on such a plan may be launched.
+    // build() without a device (tests): the same lists and decisions on stand-in tile addresses; inspect with schedule_trace /
+    // check_schedule / flow_units_host.  Nothing on such a plan may be launched: factor() / solve() are unsupported.
     std::string build_host_only(int nt, const std::vector<uint8_t>& present);
     // The launch sequence of one factorisation phase (0: the local level groups / everything, 1: the shared top of a
     // distributed plan) exactly as enqueue_factor issues it, recorded instead of issued.
@@ -169,7 +170,7 @@ class TilePlan {
     // of the shared top only -- tree-sharded landmarks; the other ranks' tiles are then left alone
     // skip_fill (round 5): the assembly is for the Cholesky factorisation of a single-GPU plan whose first writers are flagged
     // (first_writers_flagged()): the fill tiles are not cleared -- their first update does not read them
-    hipError_t zero_tiles(bool own_touched_only = false, hipStream_t on = nullptr /* nullptr: the plan's stream */, bool skip_fill = false);
+    hipError_t zero_tiles(bool own_touched_only = false, bool skip_fill = false);
     bool first_writers_flagged() const { return first_ok_; }
     void add_diag(int n_valid, double add_valid, double pad_value);  // diagonal += / padding rows := value
     void diag(double* out) const;                        // out[n_pad] = diagonal
@@ -187,7 +188,31 @@ class TilePlan {
     hipError_t pcg(const double* rhs, double* x, double* work, int max_iter, double tol, int* iters);
 
    private:
-    std::vector<std::vector<int>> symbolic_slots(const std::vector<uint8_t>& present);
+    using Cols = std::vector<std::vector<int>>;
+    // The level groups in execution order: this rank's columns level by level, then the shared top columns level by level
+    // (a plan that is not distributed has the first kind only); other ranks' columns get no tasks at all.
+    struct Groups {
+        int n_true_levels = 0, n_local = 0;   // elimination-tree levels (heights above the leaves); groups of this rank's columns
+        Cols cols, row_cols;                  // per group: its columns; per tile row: the columns of this rank and of the top with a tile there
+        std::vector<int> group_of;            // per column: its group (-1: another rank's)
+    };
+    struct Lists {   // what only the device step needs: the two forms of either sweep, the PCG lists
+        std::vector<TriTask> fwd, bwd; std::vector<FlowTask> flow_fwd, flow_bwd;
+        std::vector<int> sym_row_ptr; std::vector<SymEntry> sym_entries; std::vector<SymTile> sym_tiles;
+    };
+    // build()'s steps.  The host steps call no HIP function; their lists point into `tiles` / `linv` (stand-ins: build_host_only).
+    Cols symbolic_slots(const std::vector<uint8_t>& present);
+    Groups level_groups(const Cols& col_rows) const;
+    std::string refuse_by_size_or_cost(int n_true_levels);
+    std::string refuse_by_memory();
+    std::string host_lists(const std::vector<uint8_t>& present, const Cols& col_rows, const Groups& g, double* tiles, double* linv, Lists* out);
+    void level_lists(const Cols& col_rows, const Groups& g, double* tiles, double* linv);
+    void sweep_lists(const Cols& col_rows, const Groups& g, double* tiles, double* linv, Lists* out);
+    std::string flow_units(int gf, int g1, const Cols& col_rows, const Groups& g, double* tiles, double* linv, std::vector<FactorUnit>* units, double* sim_us) const;
+    std::string flow_regions(const Cols& col_rows, const Groups& g, double* tiles, double* linv);
+    void flag_first_writers(const double* tiles);
+    void sym_lists(const std::vector<uint8_t>& present, Lists* out) const;
+    std::string upload(const Lists& lists);   // the device step
     void enqueue_factor(int g0, int g1);
     void enqueue_solve(const double* rhs, double* x, double* work);
     void launch_fwd_group(int lv, double* bvec, double* yvec, hipStream_t s);
@@ -213,15 +238,22 @@ class TilePlan {
     int64_t n_potrf_ = 0, n_trsm_ = 0, n_upd_ = 0;
     hipStream_t stream_ = nullptr;
     std::vector<int> slot_h_, diag_slot_h_;
-    std::vector<int> lv_potrf_, lv_trsm_, lv_fwd_, lv_bwd_, lv_upd_round_, lv_upd_split_, lv_upd_splitd_, lv_upd_splita_, lv_upd_splitb_;
-    std::vector<std::vector<int>> fwd_cut_;  // per group: first forward task of each column that gets its own launch
+    // per level group: its first task in each list, the update rounds U1d [upd, u1o) | U1o | U2a | U2b1 | U2b2 [u2b2, next upd),
+    // the first forward task of each column that gets a launch of its own
+    struct Level { int potrf = 0, panel = 0, fwd = 0, upd = 0, u1o = 0, u2a = 0, u2b1 = 0, u2b2 = 0; std::vector<int> fwd_cut; };
+    std::vector<Level> lv_;
+    std::vector<int> bwd_step_;   // [n_levels_ + 1] first task of each backward-sweep step (root group first)
     hipStream_t side_ = nullptr;  // trailing updates that the next level does not need (enqueue_factor)
     hipStream_t side2_ = nullptr; // U2b2: the bulk of U2 (targets four levels up and more)
     int two_side_ = 1;            // option; two_side_plan_: what build() decided for this plan
     bool two_side_plan_ = false;
     hipStream_t so_ = nullptr;    // U1o: updates of the next level's off-diagonal tiles, beside its potrf
-    std::vector<hipEvent_t> ev_t_, ev_u2_, ev_o_, ev_b_, ev_b2_;   // ev_u2_: after U2a of the level; ev_b_: after its U2b
-    std::vector<bool> u2_pending_, o_pending_;
+    // enqueue_factor names its streams and events by id; only the calls it issues map them to handles.  Events per level group:
+    // after its panel solves, its U2a, its U1o, its U2b (all of side_), its U2b2 (side2_)
+    enum StreamId { kMain, kSide, kSide2, kSo };   // stream_, side_, side2_, so_
+    hipStream_t stream_of(StreamId s) const { return s == kMain ? stream_ : s == kSide ? side_ : s == kSide2 ? side2_ : so_; }
+    enum LevelEvent { kEvT, kEvU2, kEvO, kEvB, kEvB2, kLevelEvents };
+    std::vector<std::array<hipEvent_t, kLevelEvents>> ev_;
     bool split_u1_ = true;
     int split_u1_min_ = 4;
     bool overlap_ = true;
@@ -248,7 +280,6 @@ class TilePlan {
     bool poison_factor_ = false;
     hipStream_t occ_stream_ = nullptr;
     bool post_sweep_status(bool reduce);   // false: the max-reduction over the ranks failed
-    bool dry_run_ = false;
     int refused_ = 0;                       // why the last build() gave up: 1 update list beyond max_updates_, 2 tiles beyond the free memory, 3 predicted cost above cost_limit_ms_
     double predicted_ms_ = 0.0, cost_limit_ms_ = 0.0;
     int64_t max_updates_ = 80000000LL;      // tile products per factorisation a plan may hold (12.7 s at 45 TF/s)
@@ -274,7 +305,7 @@ class TilePlan {
     int* sym_row_ptr_ = nullptr;
     SymEntry* sym_entries_ = nullptr;
     double *sym_part_ = nullptr, *row_dot_ = nullptr, *blk_part_ = nullptr, *scal_ = nullptr;
-    static constexpr int kGraphs = 6;  // 0 factor (local levels), 1 both sweeps, 3 factor (top levels), 4/5 distributed solve phases (2: unused)
+    enum Graph { kGraphFactor, kGraphSweeps, kGraphFactorTop, kGraphDistSolve0, kGraphDistSolve1, kGraphs };   // (run_graph)
     hipGraphExec_t graph_exec_[kGraphs] = {};
     const double* graph_rhs_[kGraphs] = {};
     double *graph_x_[kGraphs] = {}, *graph_work_[kGraphs] = {};

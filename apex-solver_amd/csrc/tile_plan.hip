@@ -14,22 +14,24 @@
 
 namespace apex {
 
+static double* tile_at(double* base, int64_t i) { return base + (size_t)i * kNB * kNB; }   // tile i of an array of tiles
 template <typename T>
 static hipError_t dev_alloc(T** p, size_t n) {
     return hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T));
 }
 template <typename T>
-static hipError_t upload(T** dptr, const std::vector<T>& hv) {
+static hipError_t upload_vec(T** dptr, const std::vector<T>& hv) {
     if (*dptr) { (void)hipFree(*dptr); *dptr = nullptr; }
     hipError_t e = dev_alloc(dptr, hv.size());
     if (e != hipSuccess || hv.empty()) return e;
     return hipMemcpy(*dptr, hv.data(), hv.size() * sizeof(T), hipMemcpyHostToDevice);
 }
-static hipError_t alloc_zero(double** p, size_t n) {
+template <typename T>
+static hipError_t alloc_zero(T** p, size_t n) {
     if (*p) { (void)hipFree(*p); *p = nullptr; }
     hipError_t e = dev_alloc(p, n);
     if (e != hipSuccess) return e;
-    return hipMemset(*p, 0, std::max<size_t>(n, 1) * sizeof(double));
+    return hipMemset(*p, 0, std::max<size_t>(n, 1) * sizeof(T));
 }
 
 // Nested-dissection order of the nodes of an undirected graph: recursive bisection by BFS level
@@ -99,12 +101,6 @@ std::vector<int> TilePlan::order(int nt, const std::vector<uint8_t>& adjm, bool 
 }
 
 void TilePlan::release() {
-    if (dry_run_) {   // a host-only plan owns no device memory, streams or events
-        tiles_ = linv_ = sym_part_ = row_dot_ = blk_part_ = scal_ = exch_ = nullptr; flag_ = nullptr; gate_cnt_ = nullptr;
-        side_ = side2_ = so_ = nullptr;
-        ev_t_.clear(); ev_u2_.clear(); ev_o_.clear(); ev_b_.clear(); ev_b2_.clear();
-        return;
-    }
     void* ptrs[] = {tiles_, linv_, slot_, diag_slot_, flag_, potrf_tasks_, trsm_tasks_, upd_tasks_, tri_fwd_, tri_bwd_,
                     flow_fwd_, flow_bwd_, flow_part_, flow_flags_, flow_units_, flow_ver_, flow_trace_, sym_tiles_, sym_row_ptr_, sym_entries_, sym_part_, row_dot_, blk_part_, scal_, cls_, exch_, gate_cnt_};
     for (void* p : ptrs)
@@ -123,19 +119,14 @@ void TilePlan::release() {
     if (flow_err_host_) { (void)hipHostFree(flow_err_host_); flow_err_host_ = nullptr; flow_err_host_dev_ = nullptr; }
     if (pcg_host_) { (void)hipHostFree(pcg_host_); pcg_host_ = nullptr; for (hipEvent_t& ev : pcg_ev_) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; } }
     if (occ_stream_) { (void)hipStreamSynchronize(occ_stream_); (void)hipStreamDestroy(occ_stream_); occ_stream_ = nullptr; }
-    for (hipEvent_t e : ev_t_) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ev_u2_) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ev_o_) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ev_b_) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ev_b2_) (void)hipEventDestroy(e);
-    ev_t_.clear(); ev_u2_.clear(); ev_o_.clear(); ev_b_.clear(); ev_b2_.clear();
+    for (const auto& evs : ev_) for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
+    ev_.clear();
 }
 
 TilePlan::~TilePlan() {
     release();
-    if (side_) (void)hipStreamDestroy(side_);
-    if (side2_) { (void)hipStreamDestroy(side2_); side2_ = nullptr; }
-    if (so_) { (void)hipStreamDestroy(so_); so_ = nullptr; }
+    for (hipStream_t s : {side_, side2_, so_})
+        if (s) (void)hipStreamDestroy(s);
 }
 
 // Cut the elimination tree into part_world_ groups of subtrees plus a shared top.  Deterministic: every rank
@@ -296,150 +287,141 @@ std::vector<std::vector<int>> TilePlan::symbolic_slots(const std::vector<uint8_t
     return col_rows;
 }
 
-void TilePlan::build_symbolic(int nt, const std::vector<uint8_t>& present) {
-    nt_ = nt;
-    const std::vector<std::vector<int>> col_rows = symbolic_slots(present);
+// The level groups (tile_plan.h, Groups).  parent(K) = first off-diagonal row of column K.
+TilePlan::Groups TilePlan::level_groups(const Cols& col_rows) const {
+    Groups g;
     std::vector<int> level(nt_, 0);
     for (int K = 0; K < nt_; ++K)
         if (!col_rows[K].empty()) level[col_rows[K][0]] = std::max(level[col_rows[K][0]], level[K] + 1);
-    n_levels_ = 1 + *std::max_element(level.begin(), level.end());
-    n_local_groups_ = n_levels_;
-}
-
-// Host-only twin of build() (tests: no device is touched): the same symbolic work, task lists, dataflow units and schedule
-// decisions, with made-up tile addresses and stream / event handles.  The plan it leaves behind can only be inspected
-// (schedule_trace, check_schedule, flow units): factor() / solve() on it are undefined.
-std::string TilePlan::build_host_only(int nt, const std::vector<uint8_t>& present) {
-    dry_run_ = true;
-    const std::string e = build(nt, present, reinterpret_cast<hipStream_t>(uintptr_t(0x51)));
-    return e;
-}
-
-std::string TilePlan::build(int nt, const std::vector<uint8_t>& present, hipStream_t stream) {
-    if (dry_run_) { tiles_ = linv_ = nullptr; }   // (fake addresses: never freed)
-    release();
-    nt_ = nt;
-    stream_ = stream;
-    SetupTrace ptr_trace;
-    const size_t tile_elems = (size_t)kNB * kNB;
-    refused_ = 0;
-    std::vector<std::vector<int>> col_rows = symbolic_slots(present);
-    int64_t n_upd = 0;
-    for (int K = 0; K < nt_; ++K) n_upd += (int64_t)col_rows[K].size() * (col_rows[K].size() + 1) / 2;
-    // what this plan is predicted to cost per solve (reported whatever follows)
-    {
-        int n_lv = 1;
-        std::vector<int> lvl(nt_, 0);
-        for (int K = 0; K < nt_; ++K)
-            if (!col_rows[K].empty()) { lvl[col_rows[K][0]] = std::max(lvl[col_rows[K][0]], lvl[K] + 1); n_lv = std::max(n_lv, lvl[col_rows[K][0]] + 1); }
-        predicted_ms_ = predict_solve_ms(n_potrf_, n_trsm_, n_upd_, n_slots_, n_lv);
+    g.n_true_levels = 1 + *std::max_element(level.begin(), level.end());
+    g.group_of.assign(nt_, -1);
+    for (int want = 1; want <= 2; ++want) {
+        for (int lv = 0; lv < g.n_true_levels; ++lv) {
+            std::vector<int> cols;
+            for (int K = 0; K < nt_; ++K)
+                if (level[K] == lv && cls_h_[K] == want) cols.push_back(K);
+            if (cols.empty()) continue;
+            for (int K : cols) g.group_of[K] = (int)g.cols.size();
+            g.cols.push_back(std::move(cols));
+        }
+        if (want == 1) g.n_local = (int)g.cols.size();
     }
-    // (the size rule first: it is host arithmetic on the structure, so every rank of a distributed plan decides alike)
-    if (n_upd > max_updates_) { refused_ = 1; return "tile update list too large (" + std::to_string(n_upd) + " tile products per factorisation, limit " + std::to_string(max_updates_) + ")"; }
-    // (round 6) ... then the cost rule, the same kind of arithmetic: a caller that owns a cheaper way to the same step (the
-    // matrix-free PCG, Solver::set_structure) hands in what that way costs, and a plan predicted to cost more is not built
+    g.row_cols.assign(nt_, {});
+    for (int K = 0; K < nt_; ++K)
+        if (cls_h_[K] != 0)
+            for (int I : col_rows[K]) g.row_cols[I].push_back(K);
+    return g;
+}
+
+void TilePlan::build_symbolic(int nt, const std::vector<uint8_t>& present) {
+    nt_ = nt;
+    n_levels_ = n_local_groups_ = level_groups(symbolic_slots(present)).n_true_levels;
+}
+
+// what this plan is predicted to cost per solve (reported whatever follows), then the refusal rules that are host arithmetic on
+// the structure (every rank of a distributed plan decides alike): the size rule first ...
+std::string TilePlan::refuse_by_size_or_cost(int n_true_levels) {
+    predicted_ms_ = predict_solve_ms(n_potrf_, n_trsm_, n_upd_, n_slots_, n_true_levels);
+    if (n_upd_ > max_updates_) { refused_ = 1; return "tile update list too large (" + std::to_string(n_upd_) + " tile products per factorisation, limit " + std::to_string(max_updates_) + ")"; }
+    // (round 6) ... then the cost rule: a caller that owns a cheaper way to the same step (the matrix-free PCG,
+    // Solver::set_structure) hands in what that way costs, and a plan predicted to cost more is not built
     if (cost_limit_ms_ > 0.0 && predicted_ms_ > cost_limit_ms_) {
         refused_ = 3;
         char buf[160];
         snprintf(buf, sizeof buf, "predicted cost of the direct factorisation %.1f ms per solve, above the %.1f ms of the alternative", predicted_ms_, cost_limit_ms_);
         return buf;
     }
-    if (!dry_run_) {
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
-        const double need = (double)(n_slots_ + nt_) * tile_elems * 8.0;
-        if (need > 0.9 * (double)free_b) {
-            refused_ = 2;
-            return "the tile matrix needs " + std::to_string(need / 1e9) + " GB; only " + std::to_string(free_b / 1e9) + " GB free";
-        }
-    }
+    return "";
+}
 
-#define TP_TRY(expr) do { if (!dry_run_) { hipError_t _e = (expr); if (_e != hipSuccess) return std::string("HIP error in " #expr ": ") + hipGetErrorString(_e); } } while (0)
+std::string TilePlan::refuse_by_memory() {
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    const double need = (double)(n_slots_ + nt_) * kNB * kNB * 8.0;
+    if (need <= 0.9 * (double)free_b) return "";
+    refused_ = 2;
+    return "the tile matrix needs " + std::to_string(need / 1e9) + " GB; only " + std::to_string(free_b / 1e9) + " GB free";
+}
+
+#define TP_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return std::string("HIP error in " #expr ": ") + hipGetErrorString(_e); } while (0)
+
+std::string TilePlan::build(int nt, const std::vector<uint8_t>& present, hipStream_t stream) {
+    release();
+    nt_ = nt; stream_ = stream; refused_ = 0;
+    SetupTrace ptr_trace;
+    const Cols col_rows = symbolic_slots(present);
+    const Groups g = level_groups(col_rows);
+    std::string e = refuse_by_size_or_cost(g.n_true_levels);
+    if (e.empty()) e = refuse_by_memory();
+    if (!e.empty()) return e;
     ptr_trace.mark("plan: symbolic fill, slots");
-    TP_TRY(alloc_zero(&tiles_, (size_t)n_slots_ * tile_elems));
-    TP_TRY(alloc_zero(&linv_, (size_t)nt_ * tile_elems));
+    TP_TRY(alloc_zero(&tiles_, (size_t)n_slots_ * kNB * kNB));
+    TP_TRY(alloc_zero(&linv_, (size_t)nt_ * kNB * kNB));
     ptr_trace.mark("plan: tiles allocated, cleared");
-    if (dry_run_) {   // addresses that identify tiles, nothing more
-        tiles_ = reinterpret_cast<double*>(uintptr_t(1) << 44);
-        linv_ = reinterpret_cast<double*>(uintptr_t(1) << 45);
-    }
-    TP_TRY(upload(&slot_, slot_h_));
-    TP_TRY(upload(&diag_slot_, diag_slot_h_));
-    if (flag_ && !dry_run_) (void)hipFree(flag_);
-    TP_TRY(dev_alloc(&flag_, 4));
-    TP_TRY(hipMemset(flag_, 0, 4 * sizeof(int)));
+    Lists lists;
+    e = host_lists(present, col_rows, g, tiles_, linv_, &lists);
+    if (!e.empty()) return e;
+    ptr_trace.mark("plan: task lists, dataflow units");
+    e = upload(lists);
+    if (e.empty()) ptr_trace.mark("plan: uploads, streams, events");
+    return e;
+}
 
-    // ---- task lists scheduled by elimination-tree LEVEL ------------------------------------------------
-    // parent(K) = first off-diagonal row of column K; level = height above the leaves.  Columns of one
-    // level are independent: their potrf / panel solves / trailing updates run as ONE batched launch
-    // each.  Two columns of a level may update the same ancestor tile: those updates are split into
-    // conflict-free rounds (deterministic), one launch per round.
-    auto tile_ptr = [&](int I, int J) { return tiles_ + (size_t)slot_h_[(size_t)I * nt_ + J] * tile_elems; };
-    auto linv_ptr = [&](int K) { return linv_ + (size_t)K * tile_elems; };
-    std::vector<int> level(nt_, 0);
-    for (int K = 0; K < nt_; ++K)
-        if (!col_rows[K].empty()) level[col_rows[K][0]] = std::max(level[col_rows[K][0]], level[K] + 1);
-    // Level GROUPS in execution order: this rank's columns level by level, then the shared top columns level by
-    // level (a plan that is not distributed has the first kind only); other ranks' columns get no tasks at all.
-    const int n_true_levels = 1 + *std::max_element(level.begin(), level.end());
-    std::vector<std::vector<int>> level_cols;
-    std::vector<int> group_of(nt_, -1);
-    n_local_groups_ = 0;
-    for (int want = 1; want <= 2; ++want) {
-        for (int lv = 0; lv < n_true_levels; ++lv) {
-            std::vector<int> cols;
-            for (int K = 0; K < nt_; ++K)
-                if (level[K] == lv && cls_h_[K] == want) cols.push_back(K);
-            if (cols.empty()) continue;
-            for (int K : cols) group_of[K] = (int)level_cols.size();
-            level_cols.push_back(std::move(cols));
-        }
-        if (want == 1) n_local_groups_ = (int)level_cols.size();
-    }
-    n_levels_ = (int)level_cols.size();
-    std::vector<std::vector<int>> row_cols(nt_);
-    for (int K = 0; K < nt_; ++K)
-        if (cls_h_[K] != 0)
-            for (int I : col_rows[K]) row_cols[I].push_back(K);
-    std::vector<PotrfTask> potrf;
-    std::vector<GemmTask> trsm, upd;
-    std::vector<TriTask> tf, tb;
-    lv_potrf_.assign(n_levels_ + 1, 0); lv_trsm_.assign(n_levels_ + 1, 0);
-    lv_fwd_.assign(n_levels_ + 1, 0); lv_bwd_.assign(n_levels_ + 1, 0);
-    fwd_cut_.assign(n_levels_, std::vector<int>());
-    lv_upd_round_.assign(n_levels_ + 1, 0);
-    lv_upd_split_.assign(n_levels_ + 1, 0);
-    lv_upd_splita_.assign(n_levels_ + 1, 0);
-    lv_upd_splitb_.assign(n_levels_ + 1, 0);
-    lv_upd_splitd_.assign(n_levels_ + 1, 0);
-    upd_rounds_.clear();
-    upd.reserve(n_upd);
+// Host-only twin of build() (tests: no device is touched): the same host steps on a plan that owns no device resources,
+// with stand-in tile and linv addresses that identify tiles, nothing more.
+std::string TilePlan::build_host_only(int nt, const std::vector<uint8_t>& present) {
+    nt_ = nt; refused_ = 0;
+    const Cols col_rows = symbolic_slots(present);
+    const Groups g = level_groups(col_rows);
+    const std::string e = refuse_by_size_or_cost(g.n_true_levels);
+    if (!e.empty()) return e;
+    Lists lists;   // (uploaded nowhere)
+    return host_lists(present, col_rows, g, reinterpret_cast<double*>(uintptr_t(1) << 44), reinterpret_cast<double*>(uintptr_t(1) << 45), &lists);
+}
+
+// The lists of a plan, in this order: the level task lists, the two sweeps, the PCG lists, the dataflow launches, the first writers.
+std::string TilePlan::host_lists(const std::vector<uint8_t>& present, const Cols& col_rows, const Groups& g, double* tiles, double* linv, Lists* out) {
+    n_levels_ = (int)g.cols.size(); n_local_groups_ = g.n_local;
+    level_lists(col_rows, g, tiles, linv);
+    sweep_lists(col_rows, g, tiles, linv, out);
+    sym_lists(present, out);
+    n_potrf_ = (int64_t)potrf_h_.size(); n_trsm_ = (int64_t)trsm_h_.size(); n_upd_ = (int64_t)upd_h_.size();
+    // The second side stream (enqueue_factor), for the whole plan or not at all: it pays where a level carries a bulk worth
+    // overlapping (final-13682: ~1,000 tile products per level, 7.95 -> 7.5 ms; synthetic-10k 6.4 -> 6.1) and costs where the
+    // levels are small and the factorisation is its launch chain (the ladybug / venice shapes, ~100 products per level: one
+    // more stream is one more edge per level, 3.1 -> 3.5 ms).
+    two_side_plan_ = two_side_ == 2 || (two_side_ == 1 && n_upd_ >= 256 * (int64_t)n_levels_);
+    const std::string e = flow_regions(col_rows, g, tiles, linv);
+    if (e.empty()) flag_first_writers(tiles);
+    return e;
+}
+
+// ---- task lists scheduled by elimination-tree LEVEL ------------------------------------------------
+// Columns of one level are independent: their potrf / panel solves / trailing updates run as ONE batched launch
+// each.  Two columns of a level may update the same ancestor tile: those updates are split into
+// conflict-free rounds (deterministic), one launch per round.
+void TilePlan::level_lists(const Cols& col_rows, const Groups& g, double* tiles, double* linv) {
+    auto tile_ptr = [&](int I, int J) { return tile_at(tiles, slot(I, J)); };
+    potrf_h_.clear(); trsm_h_.clear(); upd_h_.clear(); upd_rounds_.clear();
+    lv_.assign(n_levels_ + 1, Level());
+    upd_h_.reserve(n_upd_);
     for (int lv = 0; lv < n_levels_; ++lv) {
         struct U { int64_t key; int K; GemmTask t; };
         std::vector<U> us;
-        for (int K : level_cols[lv]) {
+        for (int K : g.cols[lv]) {
             const auto& rows = col_rows[K];
-            potrf.push_back({tile_ptr(K, K), linv_ptr(K), K});
-            // The top columns of a distributed plan are swept by every rank, and the ranks' copies of the top solution
-            // must be BITWISE equal (a rank's own blocks are back-substituted from its copy, the result takes rank 0's;
-            // with cond(S) ~ 1e9 a last-bit difference shows up as a 1e-11 residual).  The forward step adds into shared
-            // ancestor blocks with atomics, which is order-dependent when two columns of a level run in one launch:
-            // top columns therefore get one launch each.
-            if (cls_h_[K] == 2) fwd_cut_[lv].push_back((int)tf.size());
-            tf.push_back({linv_ptr(K), nullptr, K, -1});
-            for (int I : rows) {
-                if (group_of[I] == lv + 1) trsm.push_back({tile_ptr(I, K), tile_ptr(I, K), linv_ptr(K)});   // (first: see below)
-                tf.push_back({linv_ptr(K), tile_ptr(I, K), K, I});
-            }
+            potrf_h_.push_back({tile_ptr(K, K), tile_at(linv, K), K});
+            for (int I : rows)
+                if (g.group_of[I] == lv + 1) trsm_h_.push_back({tile_ptr(I, K), tile_ptr(I, K), tile_at(linv, K)});   // (first: see below)
             for (size_t a = 0; a < rows.size(); ++a)
                 for (size_t b = 0; b <= a; ++b)
                     us.push_back({(int64_t)rows[a] * nt_ + rows[b], K, {tile_ptr(rows[a], rows[b]), tile_ptr(rows[a], K), tile_ptr(rows[b], K)}});
         }
         // the panel solves of the level: first the tiles whose ROW belongs to the next level (all that U1d(lv) reads), then the
         // others; by column inside each part
-        for (int K : level_cols[lv])
+        for (int K : g.cols[lv])
             for (int I : col_rows[K])
-                if (group_of[I] != lv + 1) trsm.push_back({tile_ptr(I, K), tile_ptr(I, K), linv_ptr(K)});
+                if (g.group_of[I] != lv + 1) trsm_h_.push_back({tile_ptr(I, K), tile_ptr(I, K), tile_at(linv, K)});
         std::stable_sort(us.begin(), us.end(), [](const U& x, const U& y) { return x.key < y.key; });
         // U1d: targets = DIAGONAL tiles of the next level's columns (what its potrf needs);
         // U1o: the other tiles of the next level's columns (what its panel solves need) -- on a third stream, beside the
@@ -450,11 +432,12 @@ std::string TilePlan::build(int nt, const std::vector<uint8_t>& present, hipStre
         // write, so U1(lv+1) waits for U2a(lv) alone -- and U2b = everything higher, which then runs beside them.
         // ... and U2b in two: U2b1 = targets in level lv+3 (all that U2a of the NEXT level collides with), which stays on U2a's
         // stream, and U2b2 = level lv+4 and above, the bulk, on a stream of its own (enqueue_factor).
+        int* const part_end[4] = {&lv_[lv].u1o, &lv_[lv].u2a, &lv_[lv].u2b1, &lv_[lv].u2b2};
         for (int part = 0; part < 5; ++part) {
             std::vector<const U*> mine;
             for (const U& u : us) {
                 const int tcol = (int)(u.key % nt_), trow = (int)(u.key / nt_);
-                const int d = group_of[tcol] - lv;
+                const int d = g.group_of[tcol] - lv;
                 const int cls = d == 1 ? (trow == tcol ? 0 : 1) : (d == 2 ? 2 : (d == 3 ? 3 : 4));
                 if (cls == part) mine.push_back(&u);
             }
@@ -470,334 +453,347 @@ std::string TilePlan::build(int nt, const std::vector<uint8_t>& present, hipStre
                 for (size_t i = 0; i < mine.size(); ++i)
                     if (round[i] == r) sel.push_back(mine[i]);
                 std::stable_sort(sel.begin(), sel.end(), [](const U* x, const U* y) { return x->K < y->K; });
-                const int64_t off = (int64_t)upd.size();
-                for (const U* u : sel) upd.push_back(u->t);
-                upd_rounds_.push_back({off, (int64_t)upd.size() - off});
+                const int64_t off = (int64_t)upd_h_.size();
+                for (const U* u : sel) upd_h_.push_back(u->t);
+                upd_rounds_.push_back({off, (int64_t)upd_h_.size() - off});
             }
-            if (part == 0) lv_upd_splitd_[lv] = (int)upd_rounds_.size();
-            if (part == 1) lv_upd_split_[lv] = (int)upd_rounds_.size();
-            if (part == 2) lv_upd_splita_[lv] = (int)upd_rounds_.size();
-            if (part == 3) lv_upd_splitb_[lv] = (int)upd_rounds_.size();
+            if (part < 4) *part_end[part] = (int)upd_rounds_.size();
         }
-        lv_potrf_[lv + 1] = (int)potrf.size();
-        lv_trsm_[lv + 1] = (int)trsm.size();
-        lv_fwd_[lv + 1] = (int)tf.size();
-        lv_upd_round_[lv + 1] = (int)upd_rounds_.size();
+        lv_[lv + 1].potrf = (int)potrf_h_.size();
+        lv_[lv + 1].panel = (int)trsm_h_.size();
+        lv_[lv + 1].upd = (int)upd_rounds_.size();
     }
-    for (int lv = n_levels_ - 1; lv >= 0; --lv) {  // backward sweep: levels from the root down
-        for (int I : level_cols[lv]) {
-            tb.push_back({linv_ptr(I), nullptr, I, -1});
-            for (int J : row_cols[I]) tb.push_back({linv_ptr(I), tile_ptr(I, J), I, J});
+}
+
+// The triangular sweeps, level by level (forward by group, backward from the root group down) and as dataflow launches.
+void TilePlan::sweep_lists(const Cols& col_rows, const Groups& g, double* tiles, double* linv, Lists* sw) {
+    auto tile_ptr = [&](int I, int J) { return tile_at(tiles, slot(I, J)); };
+    for (int lv = 0; lv < n_levels_; ++lv) {
+        for (int K : g.cols[lv]) {
+            // The top columns of a distributed plan are swept by every rank, and the ranks' copies of the top solution
+            // must be BITWISE equal (a rank's own blocks are back-substituted from its copy, the result takes rank 0's;
+            // with cond(S) ~ 1e9 a last-bit difference shows up as a 1e-11 residual).  The forward step adds into shared
+            // ancestor blocks with atomics, which is order-dependent when two columns of a level run in one launch:
+            // top columns therefore get one launch each.
+            if (cls_h_[K] == 2) lv_[lv].fwd_cut.push_back((int)sw->fwd.size());
+            sw->fwd.push_back({tile_at(linv, K), nullptr, K, -1});
+            for (int I : col_rows[K]) sw->fwd.push_back({tile_at(linv, K), tile_ptr(I, K), K, I});
         }
-        lv_bwd_[n_levels_ - lv] = (int)tb.size();
+        lv_[lv + 1].fwd = (int)sw->fwd.size();
+    }
+    bwd_step_.assign(n_levels_ + 1, 0);
+    for (int lv = n_levels_ - 1; lv >= 0; --lv) {
+        for (int I : g.cols[lv]) {
+            sw->bwd.push_back({tile_at(linv, I), nullptr, I, -1});
+            for (int J : g.row_cols[I]) sw->bwd.push_back({tile_at(linv, I), tile_ptr(I, J), I, J});
+        }
+        bwd_step_[n_levels_ - lv] = (int)sw->bwd.size();
     }
     // both sweeps as one dataflow launch each (k_tri_fwd_flow / k_tri_bwd_flow; plans that are not distributed): level
     // by level the solve tasks of the level's blocks, then the product tasks of the tiles those solutions multiply.
     // A block's products own consecutive slots of the partial array, in the order the solve task folds them.
-    std::vector<FlowTask> ft, bt;
+    const Cols& row_cols = g.row_cols;
+    std::vector<FlowTask> &ft = sw->flow_fwd, &bt = sw->flow_bwd;
     n_flow_local_ = 0;
-    {
-        // forward: slots by block row.  In a distributed plan a shared top row takes products from this rank's columns
-        // (phase 0: folded into the exchange vector, no solve) and from top columns (phase 1): the rank's sources get the
-        // first slots of the row, the top sources the rest, each in column order -- so the fold of the top sources is
-        // the same sequence of additions on every rank (the ranks' copies of the top solution must be bitwise equal).
-        std::vector<int> first(nt_ + 1, 0), own_src(nt_, 0);
-        std::vector<std::vector<int>> slot_of(nt_);
-        for (int K = 0; K < nt_; ++K) {
-            first[K + 1] = first[K] + (int)row_cols[K].size();
-            for (int J : row_cols[K]) own_src[K] += cls_h_[J] == 1;
-            int a = 0, b = own_src[K];
-            slot_of[K].reserve(row_cols[K].size());
-            for (int J : row_cols[K]) slot_of[K].push_back(cls_h_[J] == 1 ? a++ : b++);
-        }
-        // Single-GPU plans (kTriInline, round 5): the solve task of a block forms the product of its LAST-ARRIVING source itself
-        // (FlowTask::mat2 / src2 / slot2: the source solved latest, i.e. of the highest level forward, of the lowest backward) --
-        // the link of the dependency chain loses a flag hop and a trip through memory; that product task leaves the list.
-        // Only in the NARROW levels (at most kTriInline columns): where a level is wide the sweeps are bound by HBM and the
-        // second tile of a solve task only serialises two products (final-13682 with every block inlined: sweeps 0.71 -> 0.79 ms;
-        // ladybug-1723, narrow everywhere: 0.35 -> 0.28).
-        const bool inl = kTriInline > 0 && !distributed();
-        std::vector<int> fwd_inl(nt_, -1), bwd_inl(nt_, -1);
-        if (inl)
-            for (int K = 0; K < nt_; ++K) {
-                if ((int)level_cols[(size_t)group_of[K]].size() > kTriInline) continue;
-                for (int J : row_cols[K]) if (fwd_inl[K] < 0 || group_of[J] >= group_of[fwd_inl[K]]) fwd_inl[K] = J;
-                for (int I : col_rows[K]) if (bwd_inl[K] < 0 || group_of[I] < group_of[bwd_inl[K]]) bwd_inl[K] = I;
-            }
-        auto products_of = [&](int K) {
-            for (int I : col_rows[K]) {
-                if (fwd_inl[I] == K) continue;   // (formed by the solve task of block I)
-                const auto& rc = row_cols[I];
-                const int pos = (int)(std::lower_bound(rc.begin(), rc.end(), K) - rc.begin());
-                ft.push_back({tile_ptr(I, K), K, I, first[I] + slot_of[I][pos], 0});
-            }
-        };
-        auto fwd_solve = [&](int K) {
-            FlowTask t{linv_ptr(K), -1, K, first[K], (int)row_cols[K].size()};
-            if (fwd_inl[K] >= 0) {
-                const auto& rc = row_cols[K];
-                const int pos = (int)(std::lower_bound(rc.begin(), rc.end(), fwd_inl[K]) - rc.begin());
-                t.mat2 = tile_ptr(K, fwd_inl[K]); t.src2 = fwd_inl[K]; t.slot2 = slot_of[K][pos];
-            }
-            return t;
-        };
-        if (!distributed()) {
-            for (int lv = 0; lv < n_levels_; ++lv) {
-                for (int K : level_cols[lv]) ft.push_back(fwd_solve(K));
-                for (int K : level_cols[lv]) products_of(K);
-            }
-        } else {
-            for (int lv = 0; lv < n_local_groups_; ++lv) {          // phase 0: this rank's columns ...
-                for (int K : level_cols[lv]) ft.push_back({linv_ptr(K), -1, K, first[K], (int)row_cols[K].size()});
-                for (int K : level_cols[lv]) products_of(K);
-            }
-            for (int lv = n_local_groups_; lv < n_levels_; ++lv)    // ... and what they add to the shared top blocks
-                for (int K : level_cols[lv]) ft.push_back({linv_ptr(K), -2, K, first[K], own_src[K]});
-            n_flow_local_ = (int)ft.size();
-            for (int lv = n_local_groups_; lv < n_levels_; ++lv) {  // phase 1: the top columns, every rank alike
-                for (int K : level_cols[lv])
-                    ft.push_back({linv_ptr(K), -1, K, first[K] + own_src[K], (int)row_cols[K].size() - own_src[K]});
-                for (int K : level_cols[lv]) products_of(K);
-            }
-        }
-        if (!ft.empty()) {
-            for (int K = 0; K < nt_; ++K) first[K + 1] = first[K] + (int)col_rows[K].size();      // backward: by block column
-            for (int lv = n_levels_ - 1; lv >= 0; --lv) {
-                for (int I : level_cols[lv]) {
-                    FlowTask t{linv_ptr(I), -1, I, first[I], (int)col_rows[I].size()};
-                    if (bwd_inl[I] >= 0) {
-                        const auto& cr = col_rows[I];
-                        t.mat2 = tile_ptr(bwd_inl[I], I); t.src2 = bwd_inl[I];
-                        t.slot2 = (int)(std::lower_bound(cr.begin(), cr.end(), bwd_inl[I]) - cr.begin());
-                    }
-                    bt.push_back(t);
-                }
-                for (int I : level_cols[lv])
-                    for (int J : row_cols[I]) {
-                        if (bwd_inl[J] == I) continue;   // (formed by the solve task of block J)
-                        const auto& cr = col_rows[J];
-                        const int pos = (int)(std::lower_bound(cr.begin(), cr.end(), I) - cr.begin());
-                        bt.push_back({tile_ptr(I, J), I, J, first[J] + pos, 0});
-                    }
-            }
-        }
-        int64_t a = 0, b = 0;
-        for (int K = 0; K < nt_; ++K) { a += (int64_t)row_cols[K].size(); b += (int64_t)col_rows[K].size(); }
-        n_flow_parts_ = (int)std::max(a, b);
+    // forward: slots by block row.  In a distributed plan a shared top row takes products from this rank's columns
+    // (phase 0: folded into the exchange vector, no solve) and from top columns (phase 1): the rank's sources get the
+    // first slots of the row, the top sources the rest, each in column order -- so the fold of the top sources is
+    // the same sequence of additions on every rank (the ranks' copies of the top solution must be bitwise equal).
+    std::vector<int> first(nt_ + 1, 0), own_src(nt_, 0);
+    std::vector<std::vector<int>> slot_of(nt_);
+    for (int K = 0; K < nt_; ++K) {
+        first[K + 1] = first[K] + (int)row_cols[K].size();
+        for (int J : row_cols[K]) own_src[K] += cls_h_[J] == 1;
+        int a = 0, b = own_src[K];
+        slot_of[K].reserve(row_cols[K].size());
+        for (int J : row_cols[K]) slot_of[K].push_back(cls_h_[J] == 1 ? a++ : b++);
     }
+    // Single-GPU plans (kTriInline, round 5): the solve task of a block forms the product of its LAST-ARRIVING source itself
+    // (FlowTask::mat2 / src2 / slot2: the source solved latest, i.e. of the highest level forward, of the lowest backward) --
+    // the link of the dependency chain loses a flag hop and a trip through memory; that product task leaves the list.
+    // Only in the NARROW levels (at most kTriInline columns): where a level is wide the sweeps are bound by HBM and the
+    // second tile of a solve task only serialises two products (final-13682 with every block inlined: sweeps 0.71 -> 0.79 ms;
+    // ladybug-1723, narrow everywhere: 0.35 -> 0.28).
+    const bool inl = kTriInline > 0 && !distributed();
+    std::vector<int> fwd_inl(nt_, -1), bwd_inl(nt_, -1);
+    if (inl)
+        for (int K = 0; K < nt_; ++K) {
+            if ((int)g.cols[(size_t)g.group_of[K]].size() > kTriInline) continue;
+            for (int J : row_cols[K]) if (fwd_inl[K] < 0 || g.group_of[J] >= g.group_of[fwd_inl[K]]) fwd_inl[K] = J;
+            for (int I : col_rows[K]) if (bwd_inl[K] < 0 || g.group_of[I] < g.group_of[bwd_inl[K]]) bwd_inl[K] = I;
+        }
+    auto products_of = [&](int K) {
+        for (int I : col_rows[K]) {
+            if (fwd_inl[I] == K) continue;   // (formed by the solve task of block I)
+            const auto& rc = row_cols[I];
+            const int pos = (int)(std::lower_bound(rc.begin(), rc.end(), K) - rc.begin());
+            ft.push_back({tile_ptr(I, K), K, I, first[I] + slot_of[I][pos], 0});
+        }
+    };
+    auto fwd_solve = [&](int K) {
+        FlowTask t{tile_at(linv, K), -1, K, first[K], (int)row_cols[K].size()};
+        if (fwd_inl[K] >= 0) {
+            const auto& rc = row_cols[K];
+            const int pos = (int)(std::lower_bound(rc.begin(), rc.end(), fwd_inl[K]) - rc.begin());
+            t.mat2 = tile_ptr(K, fwd_inl[K]); t.src2 = fwd_inl[K]; t.slot2 = slot_of[K][pos];
+        }
+        return t;
+    };
+    if (!distributed()) {
+        for (int lv = 0; lv < n_levels_; ++lv) {
+            for (int K : g.cols[lv]) ft.push_back(fwd_solve(K));
+            for (int K : g.cols[lv]) products_of(K);
+        }
+    } else {
+        for (int lv = 0; lv < n_local_groups_; ++lv) {          // phase 0: this rank's columns ...
+            for (int K : g.cols[lv]) ft.push_back({tile_at(linv, K), -1, K, first[K], (int)row_cols[K].size()});
+            for (int K : g.cols[lv]) products_of(K);
+        }
+        for (int lv = n_local_groups_; lv < n_levels_; ++lv)    // ... and what they add to the shared top blocks
+            for (int K : g.cols[lv]) ft.push_back({tile_at(linv, K), -2, K, first[K], own_src[K]});
+        n_flow_local_ = (int)ft.size();
+        for (int lv = n_local_groups_; lv < n_levels_; ++lv) {  // phase 1: the top columns, every rank alike
+            for (int K : g.cols[lv])
+                ft.push_back({tile_at(linv, K), -1, K, first[K] + own_src[K], (int)row_cols[K].size() - own_src[K]});
+            for (int K : g.cols[lv]) products_of(K);
+        }
+    }
+    if (!ft.empty()) {
+        for (int K = 0; K < nt_; ++K) first[K + 1] = first[K] + (int)col_rows[K].size();      // backward: by block column
+        for (int lv = n_levels_ - 1; lv >= 0; --lv) {
+            for (int I : g.cols[lv]) {
+                FlowTask t{tile_at(linv, I), -1, I, first[I], (int)col_rows[I].size()};
+                if (bwd_inl[I] >= 0) {
+                    const auto& cr = col_rows[I];
+                    t.mat2 = tile_ptr(bwd_inl[I], I); t.src2 = bwd_inl[I];
+                    t.slot2 = (int)(std::lower_bound(cr.begin(), cr.end(), bwd_inl[I]) - cr.begin());
+                }
+                bt.push_back(t);
+            }
+            for (int I : g.cols[lv])
+                for (int J : row_cols[I]) {
+                    if (bwd_inl[J] == I) continue;   // (formed by the solve task of block J)
+                    const auto& cr = col_rows[J];
+                    const int pos = (int)(std::lower_bound(cr.begin(), cr.end(), I) - cr.begin());
+                    bt.push_back({tile_ptr(I, J), I, J, first[J] + pos, 0});
+                }
+        }
+    }
+    int64_t a = 0, b = 0;
+    for (int K = 0; K < nt_; ++K) { a += (int64_t)row_cols[K].size(); b += (int64_t)col_rows[K].size(); }
+    n_flow_parts_ = (int)std::max(a, b);
     n_flow_bwd_ = (int)bt.size();
     n_flow_tasks_ = (int)ft.size();
-    // symmetric matvec of the PCG variant: only tiles that are non-zero before fill
-    std::vector<int> sym_ptr(nt_ + 1, 0);
-    std::vector<SymEntry> sym;
-    std::vector<SymTile> symt;
+}
+
+// symmetric matvec of the PCG variant: only tiles that are non-zero before fill
+void TilePlan::sym_lists(const std::vector<uint8_t>& present, Lists* out) const {
+    std::vector<SymEntry>& sym = out->sym_entries;
+    out->sym_row_ptr.assign(nt_ + 1, 0);
     for (int I = 0; I < nt_; ++I) {
         for (int J = 0; J < I; ++J)
-            if (present[(size_t)I * nt_ + J]) sym.push_back({slot_h_[(size_t)I * nt_ + J], J, 0});
+            if (present[(size_t)I * nt_ + J]) sym.push_back({slot(I, J), J, 0});
         sym.push_back({diag_slot_h_[I], I, 2});
         for (int I2 = I + 1; I2 < nt_; ++I2)
-            if (present[(size_t)I2 * nt_ + I]) sym.push_back({slot_h_[(size_t)I2 * nt_ + I], I2, 1});
-        sym_ptr[I + 1] = (int)sym.size();
+            if (present[(size_t)I2 * nt_ + I]) sym.push_back({slot(I2, I), I2, 1});
+        out->sym_row_ptr[I + 1] = (int)sym.size();
         for (int J = 0; J <= I; ++J)
-            if (J == I || present[(size_t)I * nt_ + J]) symt.push_back({slot_h_[(size_t)I * nt_ + J], I, J});
+            if (J == I || present[(size_t)I * nt_ + J]) out->sym_tiles.push_back({slot(I, J), I, J});
     }
-    n_potrf_ = (int64_t)potrf.size(); n_trsm_ = (int64_t)trsm.size(); n_upd_ = (int64_t)upd.size();
-    // The second side stream (enqueue_factor), for the whole plan or not at all: it pays where a level carries a bulk worth
-    // overlapping (final-13682: ~1,000 tile products per level, 7.95 -> 7.5 ms; synthetic-10k 6.4 -> 6.1) and costs where the
-    // levels are small and the factorisation is its launch chain (the ladybug / venice shapes, ~100 products per level: one
-    // more stream is one more edge per level, 3.1 -> 3.5 ms).
-    two_side_plan_ = two_side_ == 2 || (two_side_ == 1 && n_upd_ >= 256 * (int64_t)n_levels_);
-    // ---- the trailing level groups of each phase as ONE dataflow launch (k_factor_flow, chol_kernels.hip) ----------------
-    // Units in left-looking order: per column of the region the updates into its tiles (per target in source order = the
-    // order of the level launches), its potrf, its panel solves; last the updates into tiles whose column is outside
-    // the launch (the local phase of a distributed plan adding to the shared top).  `running` replays the version
-    // counters: a unit may only wait for what EARLIER units publish (the no-deadlock argument), checked here.
-    auto make_flow_units = [&](int gf, int g1, std::vector<FactorUnit>& funits, double* sim_us) -> std::string {
-        funits.clear();
-        std::vector<int> cols;
-        std::vector<char> in_reg(nt_, 0);
-        for (int g = gf; g < g1; ++g)
-            for (int K : level_cols[g]) { cols.push_back(K); in_reg[K] = 1; }
-        auto slot_of = [&](int I, int J) { return slot_h_[(size_t)I * nt_ + J]; };
-        std::vector<std::vector<int>> src_of((size_t)n_slots_);
-        std::vector<std::pair<int, int>> outside;   // (J, I) of targets whose column is not in the launch
-        for (int K : cols) {
-            const auto& rows = col_rows[K];
-            for (size_t a = 0; a < rows.size(); ++a)
-                for (size_t b = 0; b <= a; ++b) {
-                    std::vector<int>& v = src_of[(size_t)slot_of(rows[a], rows[b])];
-                    if (v.empty() && !in_reg[rows[b]]) outside.push_back({rows[b], rows[a]});
-                    v.push_back(K);
-                }
+}
+
+namespace {
+int inc_of(const FactorUnit& u) { return (u.kind == 0 || u.kind == 3) ? kFlowUnitsPerTile : 1; }   // what a unit publishes
+
+// `running` replays the version counters: a unit may only wait for what EARLIER units publish (the no-deadlock argument)
+bool topological(const std::vector<FactorUnit>& units, size_t n_slots) {
+    std::vector<int> running(n_slots, 0);
+    for (const FactorUnit& u : units) {
+        for (int q = 0; q < 3; ++q)
+            if (u.wait_flag[q] >= 0 && running[(size_t)u.wait_flag[q]] < u.wait_val[q]) return false;
+        running[(size_t)u.pub] += inc_of(u);
+    }
+    return true;
+}
+
+// ---- dispatch order of the dataflow units = the start order of a simulated list schedule -----------------------------------
+// Workgroups are dispatched in list order, one per CU: the launch works through a WINDOW of ~256 consecutive units.
+// In plain left-looking order that window fills up with units that wait for the current column while units further
+// down the list -- updates whose sources were finished long ago -- cannot start: the bulk ends up serialised behind
+// the critical chain, and the chain then waits for the bulk (measured: tools/flow_bench).  So the units are listed in
+// the order in which a 240-processor list schedule STARTS them (a unit becomes ready when the versions it waits for
+// are reached; among ready units the one with the longest remaining chain goes first).  A unit starts after its
+// producers finish, hence after they started: still a topological order, re-checked below.
+// src_of: per tile slot, the sources of the updates into it inside the launch.  *sim_us: the makespan of the schedule.
+std::string list_schedule(const std::vector<std::vector<int>>& src_of, std::vector<FactorUnit>* units, double* sim_us) {
+    constexpr int W = kFlowUnitsPerTile;
+    std::vector<FactorUnit>& funits = *units;
+    const size_t n_slots = src_of.size();
+    const int n = (int)funits.size();
+    auto cost_of = [](const FactorUnit& u) { return u.kind == 0 ? 34.0 : (u.kind == 1 ? 10.0 : (u.kind == 3 ? 30.0 : 8.0)); };   // us, with the hop
+    std::vector<int> writer(n);           // which writer of its tile a unit belongs to
+    {
+        std::vector<int> cnt(n_slots, 0);
+        for (int x = 0; x < n; ++x) { const FactorUnit& u = funits[x]; writer[x] = cnt[(size_t)u.pub] / W; cnt[(size_t)u.pub] += inc_of(u); }
+    }
+    // remaining chain (bottom level) through the tile-version nodes (slot, writer)
+    std::vector<int> node0(n_slots + 1, 0);
+    for (size_t sl = 0; sl < n_slots; ++sl) node0[sl + 1] = node0[sl] + (int)src_of[sl].size() + 1;
+    std::vector<double> node_bl((size_t)node0[n_slots], 0.0), bl(n, 0.0);
+    for (int x = n - 1; x >= 0; --x) {
+        const FactorUnit& u = funits[x];
+        bl[x] = cost_of(u) + node_bl[(size_t)node0[(size_t)u.pub] + writer[x]];
+        for (int q = 0; q < 3; ++q)
+            if (u.wait_flag[q] >= 0) {
+                double& nb = node_bl[(size_t)node0[(size_t)u.wait_flag[q]] + u.wait_val[q] / W - 1];
+                nb = std::max(nb, bl[x]);
+            }
+    }
+    // event simulation
+    std::vector<std::vector<std::pair<int, int>>> waiters(n_slots);   // per flag: (value, unit)
+    std::vector<int> pending(n, 0), ver_sim(n_slots, 0), order;
+    order.reserve(n);
+    for (int x = 0; x < n; ++x) {
+        const FactorUnit& u = funits[x];
+        for (int q = 0; q < 3; ++q)
+            if (u.wait_flag[q] >= 0) { waiters[(size_t)u.wait_flag[q]].push_back({u.wait_val[q], x}); ++pending[x]; }
+    }
+    std::vector<size_t> woke(n_slots, 0);
+    for (auto& wl : waiters) std::sort(wl.begin(), wl.end());
+    auto worse = [&](int a, int b) { return bl[a] != bl[b] ? bl[a] < bl[b] : a > b; };   // heap top = longest chain, then list order
+    std::vector<int> ready;
+    for (int x = 0; x < n; ++x) if (pending[x] == 0) ready.push_back(x);
+    std::make_heap(ready.begin(), ready.end(), worse);
+    std::vector<std::pair<double, int>> running_ev;   // min-heap of (finish time, unit)
+    auto later = [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a > b; };
+    int free_p = 240;
+    double now = 0.0;
+    while ((int)order.size() < n) {
+        while (free_p > 0 && !ready.empty()) {
+            std::pop_heap(ready.begin(), ready.end(), worse);
+            const int x = ready.back(); ready.pop_back();
+            order.push_back(x); --free_p;
+            running_ev.push_back({now + cost_of(funits[x]), x});
+            std::push_heap(running_ev.begin(), running_ev.end(), later);
         }
-        std::sort(outside.begin(), outside.end());
-        constexpr int W = kFlowUnitsPerTile;
-        std::vector<int> running((size_t)n_slots_, 0);
-        bool order_ok = true;
-        auto emit = [&](FactorUnit u, int inc) {
-            for (int q = 0; q < 3; ++q)
-                if (u.wait_flag[q] >= 0 && running[(size_t)u.wait_flag[q]] < u.wait_val[q]) order_ok = false;
-            funits.push_back(u);
-            running[(size_t)u.pub] += inc;
-        };
-        auto n_upd_of = [&](int st) { return (int)src_of[(size_t)st].size(); };
-        // An update whose target column lies TWO level groups or more above its source column is not on the chain
-        // potrf -> panel solves -> updates of the next group's tiles -> potrf: it runs as ONE whole-tile unit (kind 3, the level
-        // kernels' rate per CU) instead of nine 48 x 48 units made for latency (round 5; "factor_flow_tile" 0: nine everywhere).
-        auto emit_updates = [&](int I, int J) {
-            const int st = slot_of(I, J);
-            for (int n = 0; n < n_upd_of(st); ++n) {
-                const int K = src_of[(size_t)st][n], sa = slot_of(I, K), sb = slot_of(J, K);
-                const bool whole = group_of[J] > group_of[K] + 1;
-                if (whole) {
-                    emit(FactorUnit{tile_ptr(I, J), tile_ptr(I, K), tile_ptr(J, K), {n > 0 ? st : -1, sa, sb},
-                                    {W * n, W * (n_upd_of(sa) + 1), W * (n_upd_of(sb) + 1)}, st, 3, 0, 0}, W);
-                    continue;
-                }
-                for (int sp = 0; sp < W; ++sp)
-                    emit(FactorUnit{tile_ptr(I, J), tile_ptr(I, K), tile_ptr(J, K), {n > 0 ? st : -1, sa, sb},
-                                    {W * n, W * (n_upd_of(sa) + 1), W * (n_upd_of(sb) + 1)}, st, 2, sp, 0}, 1);
-            }
-        };
-        for (int J : cols) {
-            const int sd = slot_of(J, J), nd = n_upd_of(sd);
-            emit_updates(J, J);
-            for (int I : col_rows[J]) emit_updates(I, J);
-            emit(FactorUnit{tile_ptr(J, J), linv_ptr(J), nullptr, {nd > 0 ? sd : -1, -1, -1}, {W * nd, 0, 0}, sd, 0, J, 0}, W);
-            for (int I : col_rows[J]) {
-                const int st = slot_of(I, J), n = n_upd_of(st);
-                for (int sp = 0; sp < W; ++sp)
-                    emit(FactorUnit{tile_ptr(I, J), tile_ptr(I, J), linv_ptr(J), {n > 0 ? st : -1, -1, sd}, {W * n, 0, W * (nd + 1)}, st, 1, sp, 0}, 1);
-            }
+        if (running_ev.empty()) return "internal error: the dataflow units do not form a schedule";
+        std::pop_heap(running_ev.begin(), running_ev.end(), later);
+        const std::pair<double, int> ev = running_ev.back(); running_ev.pop_back();
+        now = ev.first; ++free_p;
+        const FactorUnit& u = funits[ev.second];
+        const size_t f = (size_t)u.pub;
+        ver_sim[f] += inc_of(u);
+        while (woke[f] < waiters[f].size() && waiters[f][woke[f]].first <= ver_sim[f]) {
+            const int x = waiters[f][woke[f]++].second;
+            if (--pending[x] == 0) { ready.push_back(x); std::push_heap(ready.begin(), ready.end(), worse); }
         }
-        for (const auto& t : outside) emit_updates(t.second, t.first);
-        if (!order_ok) return "internal error: a dataflow factorisation unit waits for a later one";
-        // ---- dispatch order = the start order of a simulated list schedule -------------------------------------------------
-        // Workgroups are dispatched in list order, one per CU: the launch works through a WINDOW of ~256 consecutive units.
-        // In plain left-looking order that window fills up with units that wait for the current column while units further
-        // down the list -- updates whose sources were finished long ago -- cannot start: the bulk ends up serialised behind
-        // the critical chain, and the chain then waits for the bulk (measured: tools/flow_bench).  So the units are listed in
-        // the order in which a 240-processor list schedule STARTS them (a unit becomes ready when the versions it waits for
-        // are reached; among ready units the one with the longest remaining chain goes first).  A unit starts after its
-        // producers finish, hence after they started: still a topological order, re-checked below.
-        {
-            const int base = 0, n = (int)funits.size();
-            auto cost_of = [](const FactorUnit& u) { return u.kind == 0 ? 34.0 : (u.kind == 1 ? 10.0 : (u.kind == 3 ? 30.0 : 8.0)); };   // us, with the hop
-            auto inc_of = [](const FactorUnit& u) { return (u.kind == 0 || u.kind == 3) ? W : 1; };
-            std::vector<int> writer(n);           // which writer of its tile a unit belongs to
-            {
-                std::vector<int> cnt((size_t)n_slots_, 0);
-                for (int x = 0; x < n; ++x) { const FactorUnit& u = funits[base + x]; writer[x] = cnt[(size_t)u.pub] / W; cnt[(size_t)u.pub] += inc_of(u); }
+    }
+    *sim_us = now;
+    std::vector<FactorUnit> sorted(n);
+    for (int i = 0; i < n; ++i) sorted[i] = funits[order[i]];
+    funits.swap(sorted);
+    return topological(funits, n_slots) ? "" : "internal error: the scheduled dataflow order is not topological";
+}
+}  // namespace
+
+// ---- the trailing level groups [gf, g1) of a phase as ONE dataflow launch (k_factor_flow, chol_kernels.hip) ----------------
+// Units in left-looking order: per column of the region the updates into its tiles (per target in source order = the
+// order of the level launches), its potrf, its panel solves; last the updates into tiles whose column is outside
+// the launch (the local phase of a distributed plan adding to the shared top).  Checked topological (`running`), then put in
+// list-schedule order (list_schedule).
+std::string TilePlan::flow_units(int gf, int g1, const Cols& col_rows, const Groups& g, double* tiles, double* linv, std::vector<FactorUnit>* units, double* sim_us) const {
+    auto tile_ptr = [&](int I, int J) { return tile_at(tiles, slot(I, J)); };
+    std::vector<FactorUnit>& funits = *units;
+    funits.clear();
+    std::vector<int> cols;
+    std::vector<char> in_reg(nt_, 0);
+    for (int grp = gf; grp < g1; ++grp)
+        for (int K : g.cols[grp]) { cols.push_back(K); in_reg[K] = 1; }
+    std::vector<std::vector<int>> src_of((size_t)n_slots_);
+    std::vector<std::pair<int, int>> outside;   // (J, I) of targets whose column is not in the launch
+    for (int K : cols) {
+        const auto& rows = col_rows[K];
+        for (size_t a = 0; a < rows.size(); ++a)
+            for (size_t b = 0; b <= a; ++b) {
+                std::vector<int>& v = src_of[(size_t)slot(rows[a], rows[b])];
+                if (v.empty() && !in_reg[rows[b]]) outside.push_back({rows[b], rows[a]});
+                v.push_back(K);
             }
-            // remaining chain (bottom level) through the tile-version nodes (slot, writer)
-            std::vector<int> node0((size_t)n_slots_ + 1, 0);
-            for (int sl = 0; sl < n_slots_; ++sl) node0[(size_t)sl + 1] = node0[(size_t)sl] + n_upd_of(sl) + 1;
-            std::vector<double> node_bl((size_t)node0[(size_t)n_slots_], 0.0), bl(n, 0.0);
-            for (int x = n - 1; x >= 0; --x) {
-                const FactorUnit& u = funits[base + x];
-                bl[x] = cost_of(u) + node_bl[(size_t)node0[(size_t)u.pub] + writer[x]];
-                for (int q = 0; q < 3; ++q)
-                    if (u.wait_flag[q] >= 0) {
-                        double& nb = node_bl[(size_t)node0[(size_t)u.wait_flag[q]] + u.wait_val[q] / W - 1];
-                        nb = std::max(nb, bl[x]);
-                    }
+    }
+    std::sort(outside.begin(), outside.end());
+    constexpr int W = kFlowUnitsPerTile;
+    auto n_upd_of = [&](int st) { return (int)src_of[(size_t)st].size(); };
+    // An update whose target column lies TWO level groups or more above its source column is not on the chain
+    // potrf -> panel solves -> updates of the next group's tiles -> potrf: it runs as ONE whole-tile unit (kind 3, the level
+    // kernels' rate per CU) instead of nine 48 x 48 units made for latency (round 5; "factor_flow_tile" 0: nine everywhere).
+    auto emit_updates = [&](int I, int J) {
+        const int st = slot(I, J);
+        for (int n = 0; n < n_upd_of(st); ++n) {
+            const int K = src_of[(size_t)st][n], sa = slot(I, K), sb = slot(J, K);
+            const bool whole = g.group_of[J] > g.group_of[K] + 1;
+            if (whole) {
+                funits.push_back(FactorUnit{tile_ptr(I, J), tile_ptr(I, K), tile_ptr(J, K), {n > 0 ? st : -1, sa, sb},
+                                {W * n, W * (n_upd_of(sa) + 1), W * (n_upd_of(sb) + 1)}, st, 3, 0, 0});
+                continue;
             }
-            // event simulation
-            std::vector<std::vector<std::pair<int, int>>> waiters((size_t)n_slots_);   // per flag: (value, unit)
-            std::vector<int> pending(n, 0), ver_sim((size_t)n_slots_, 0), order;
-            order.reserve(n);
-            for (int x = 0; x < n; ++x) {
-                const FactorUnit& u = funits[base + x];
-                for (int q = 0; q < 3; ++q)
-                    if (u.wait_flag[q] >= 0) { waiters[(size_t)u.wait_flag[q]].push_back({u.wait_val[q], x}); ++pending[x]; }
-            }
-            std::vector<size_t> woke((size_t)n_slots_, 0);
-            for (auto& wl : waiters) std::sort(wl.begin(), wl.end());
-            auto worse = [&](int a, int b) { return bl[a] != bl[b] ? bl[a] < bl[b] : a > b; };   // heap top = longest chain, then list order
-            std::vector<int> ready;
-            for (int x = 0; x < n; ++x) if (pending[x] == 0) ready.push_back(x);
-            std::make_heap(ready.begin(), ready.end(), worse);
-            std::vector<std::pair<double, int>> running_ev;   // min-heap of (finish time, unit)
-            auto later = [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a > b; };
-            int free_p = 240;
-            double now = 0.0;
-            while ((int)order.size() < n) {
-                while (free_p > 0 && !ready.empty()) {
-                    std::pop_heap(ready.begin(), ready.end(), worse);
-                    const int x = ready.back(); ready.pop_back();
-                    order.push_back(x); --free_p;
-                    running_ev.push_back({now + cost_of(funits[base + x]), x});
-                    std::push_heap(running_ev.begin(), running_ev.end(), later);
-                }
-                if (running_ev.empty()) return "internal error: the dataflow units do not form a schedule";
-                std::pop_heap(running_ev.begin(), running_ev.end(), later);
-                const std::pair<double, int> ev = running_ev.back(); running_ev.pop_back();
-                now = ev.first; ++free_p;
-                const FactorUnit& u = funits[base + ev.second];
-                const size_t f = (size_t)u.pub;
-                ver_sim[f] += inc_of(u);
-                while (woke[f] < waiters[f].size() && waiters[f][woke[f]].first <= ver_sim[f]) {
-                    const int x = waiters[f][woke[f]++].second;
-                    if (--pending[x] == 0) { ready.push_back(x); std::push_heap(ready.begin(), ready.end(), worse); }
-                }
-            }
-            *sim_us = now;
-            std::vector<FactorUnit> sorted(n);
-            for (int i = 0; i < n; ++i) sorted[i] = funits[base + order[i]];
-            std::fill(running.begin(), running.end(), 0);
-            for (int i = 0; i < n; ++i) {
-                const FactorUnit& u = sorted[i];
-                for (int q = 0; q < 3; ++q)
-                    if (u.wait_flag[q] >= 0 && running[(size_t)u.wait_flag[q]] < u.wait_val[q]) order_ok = false;
-                running[(size_t)u.pub] += inc_of(u);
-                funits[base + i] = u;
-            }
-            if (!order_ok) return "internal error: the scheduled dataflow order is not topological";
+            for (int sp = 0; sp < W; ++sp)
+                funits.push_back(FactorUnit{tile_ptr(I, J), tile_ptr(I, K), tile_ptr(J, K), {n > 0 ? st : -1, sa, sb},
+                                {W * n, W * (n_upd_of(sa) + 1), W * (n_upd_of(sb) + 1)}, st, 2, sp, 0});
         }
-        return "";
     };
-    // Where the launch starts.  "factor_flow" > 0: the trailing groups with at most that many columns (and "factor_flow_rows"
-    // off-diagonal tiles per column).  < 0 (default): by a model -- the level launches cost max(80 us of launch chain,
-    // 0.14 us per tile product) per group, the dataflow launch what its list schedule says (it runs a tile product on one
-    // CU at a time and reads every operand past the L2: ~0.22 us per product with all CUs busy, but a level costs it ~55 us
-    // of chain instead of 80); the start with the smallest sum wins, no launch if none beats the level launches.
-    std::vector<FactorUnit> funits;
+    for (int J : cols) {
+        const int sd = slot(J, J), nd = n_upd_of(sd);
+        emit_updates(J, J);
+        for (int I : col_rows[J]) emit_updates(I, J);
+        funits.push_back(FactorUnit{tile_ptr(J, J), tile_at(linv, J), nullptr, {nd > 0 ? sd : -1, -1, -1}, {W * nd, 0, 0}, sd, 0, J, 0});
+        for (int I : col_rows[J]) {
+            const int st = slot(I, J), n = n_upd_of(st);
+            for (int sp = 0; sp < W; ++sp)
+                funits.push_back(FactorUnit{tile_ptr(I, J), tile_ptr(I, J), tile_at(linv, J), {n > 0 ? st : -1, -1, sd}, {W * n, 0, W * (nd + 1)}, st, 1, sp, 0});
+        }
+    }
+    for (const auto& t : outside) emit_updates(t.second, t.first);
+    if (!topological(funits, (size_t)n_slots_)) return "internal error: a dataflow factorisation unit waits for a later one";
+    return list_schedule(src_of, units, sim_us);
+}
+
+// Where the dataflow launch of each phase (local groups / top groups) starts.  "factor_flow" > 0: the trailing groups with at
+// most that many columns (and "factor_flow_rows" off-diagonal tiles per column).  < 0 (default): by a model -- the level
+// launches cost max(80 us of launch chain, 0.14 us per tile product) per group, the dataflow launch what its list schedule
+// says (it runs a tile product on one CU at a time and reads every operand past the L2: ~0.22 us per product with all CUs
+// busy, but a level costs it ~55 us of chain instead of 80); the start with the smallest sum wins, no launch if none beats
+// the level launches.  The units of both phases go to flow_units_h_.
+std::string TilePlan::flow_regions(const Cols& col_rows, const Groups& g, double* tiles, double* linv) {
+    auto level_us = [&](int grp) {
+        double prod = 0.0;
+        for (int K : g.cols[grp]) { const double m = (double)col_rows[K].size(); prod += m + 0.5 * m * (m + 1.0); }
+        // (round 5: by the timeline a middle level of final-13682 really takes 140-250 us, ~90 + 0.11 prod -- but the launch's
+        // own simulated time is as optimistic there, and the starts this pair of models picks ARE the measured optima:
+        // profiles/r05_flow_dyn_sweep.txt.  Both left as they are.)
+        return std::max(80.0, 0.14 * prod);
+    };
+    flow_units_h_.clear();
     for (int ph = 0; ph < 2; ++ph) {
         const int g0 = ph == 0 ? 0 : n_local_groups_, g1 = ph == 0 ? n_local_groups_ : n_levels_;
-        flow_g0_[ph] = flow_g1_[ph] = g1; flow_first_[ph] = (int)funits.size(); flow_n_[ph] = 0; flow_sim_us_[ph] = 0.0;
+        flow_g0_[ph] = flow_g1_[ph] = g1; flow_first_[ph] = (int)flow_units_h_.size(); flow_n_[ph] = 0; flow_sim_us_[ph] = 0.0;
         if (flow_cols_ == 0 || g1 - g0 < 2) continue;
-        std::vector<FactorUnit> best_units;
-        double best_sim = 0.0;
         int best_gf = g1;
         if (flow_cols_ > 0) {
-            int gf = g1;
-            while (gf > g0) {
-                const std::vector<int>& cols = level_cols[gf - 1];
+            while (best_gf > g0) {
+                const std::vector<int>& cols = g.cols[best_gf - 1];
                 bool ok = (int)cols.size() <= flow_cols_;
                 for (int K : cols) ok = ok && (int)col_rows[K].size() <= flow_rows_;
                 if (!ok) break;
-                --gf;
+                --best_gf;
             }
-            if (g1 - gf < 2) continue;   // a single group has nothing to chain
-            const std::string e = make_flow_units(gf, g1, best_units, &best_sim);
-            if (!e.empty()) return e;
-            best_gf = gf;
         } else {
-            auto level_us = [&](int g) {
-                double prod = 0.0;
-                for (int K : level_cols[g]) { const double m = (double)col_rows[K].size(); prod += m + 0.5 * m * (m + 1.0); }
-                // (round 5: by the timeline a middle level of final-13682 really takes 140-250 us, ~90 + 0.11 prod -- but the launch's
-                // own simulated time is as optimistic there, and the starts this pair of models picks ARE the measured optima:
-                // profiles/r05_flow_dyn_sweep.txt.  Both left as they are.)
-                return std::max(80.0, 0.14 * prod);
-            };
             double level_tail = 0.0, best_total = 0.0;   // cost of the groups [gf, g1) by level launches; best (level head dropped: common)
             int64_t units = 0;
             // the candidate starts, from the top down, with what the level launches would cost from there
             std::vector<std::pair<int, double>> cands;
             for (int gf = g1 - 1; gf >= g0; --gf) {
-                bool ok = (int)level_cols[gf].size() <= 64;
-                for (int K : level_cols[gf]) {
+                bool ok = (int)g.cols[gf].size() <= 64;
+                for (int K : g.cols[gf]) {
                     const int64_t m = (int64_t)col_rows[K].size();
                     ok = ok && m <= 96;
                     units += 1 + kFlowUnitsPerTile * (m + m * (m + 1) / 2);
@@ -812,141 +808,125 @@ std::string TilePlan::build(int nt, const std::vector<uint8_t>& present, hipStre
             // more at the end (round 5).
             const int batch = std::max(1, std::min<int>(8, (int)host_threads()));
             bool past = false;
-            std::string err;
-            for (size_t c0 = 0; c0 < cands.size() && !past && err.empty(); c0 += (size_t)batch) {
+            for (size_t c0 = 0; c0 < cands.size() && !past; c0 += (size_t)batch) {
                 const size_t c1 = std::min(cands.size(), c0 + (size_t)batch);
                 std::vector<double> sims(c1 - c0, 0.0);
                 std::vector<std::string> errs(c1 - c0);
                 parallel_rows((int64_t)(c1 - c0), [&](int64_t i) {
                     std::vector<FactorUnit> scratch;
-                    errs[(size_t)i] = make_flow_units(cands[c0 + (size_t)i].first, g1, scratch, &sims[(size_t)i]);
+                    errs[(size_t)i] = flow_units(cands[c0 + (size_t)i].first, g1, col_rows, g, tiles, linv, &scratch, &sims[(size_t)i]);
                 }, 1);
                 for (size_t i = 0; i < c1 - c0 && !past; ++i) {
-                    if (!errs[i].empty()) { err = errs[i]; break; }
+                    if (!errs[i].empty()) return errs[i];
                     // gain of starting the launch at gf = what the level launches would have cost from there - the launch
                     const double gain = cands[c0 + i].second - (sims[i] + 15.0);
-                    if (gain > best_total) { best_total = gain; best_gf = cands[c0 + i].first; best_sim = sims[i]; }
+                    if (gain > best_total) { best_total = gain; best_gf = cands[c0 + i].first; }
                     else if (gain < best_total - 300.0) past = true;   // past the optimum: the launch is swallowing throughput-bound levels
                 }
             }
-            if (!err.empty()) return err;
-            if (best_gf == g1) continue;
-            { double sim = 0.0; const std::string e = make_flow_units(best_gf, g1, best_units, &sim); if (!e.empty()) return e; }
         }
+        if (g1 - best_gf < 2) continue;   // no launch, or a single group: nothing to chain
+        std::vector<FactorUnit> best_units;
+        double sim = 0.0;
+        const std::string e = flow_units(best_gf, g1, col_rows, g, tiles, linv, &best_units, &sim);
+        if (!e.empty()) return e;
         flow_g0_[ph] = best_gf;
         flow_n_[ph] = (int)best_units.size();
-        flow_sim_us_[ph] = best_sim;
-        funits.insert(funits.end(), best_units.begin(), best_units.end());
+        flow_sim_us_[ph] = sim;
+        flow_units_h_.insert(flow_units_h_.end(), best_units.begin(), best_units.end());
     }
-    // ---- first writers of the fill tiles (tile_plan.h, first_ok_) ------------------------------------------------------------
-    // Two execution orders exist: the level launches alone (the lists of every level, in list order) and the level launches of
-    // the levels below a dataflow launch followed by its units (in unit order: the writers of a tile are chained in that order).
-    // A fill tile's first writer is flagged in both; touched tiles hold S and are never "first written".
+    return "";
+}
+
+// ---- first writers of the fill tiles (tile_plan.h, first_ok_) ------------------------------------------------------------
+// Two execution orders exist: the level launches alone (the lists of every level, in list order) and the level launches of
+// the levels below a dataflow launch followed by its units (in unit order: the writers of a tile are chained in that order).
+// A fill tile's first writer is flagged in both; touched tiles hold S and are never "first written".
+void TilePlan::flag_first_writers(const double* tiles) {
     first_ok_ = false;
-    if (!distributed() && n_slots_ > n_touched_ && flow_n_[1] == 0) {
-        const size_t te = tile_elems;
-        auto slot_of_ptr = [&](const double* c) { return (int64_t)((c - tiles_) / (ptrdiff_t)te); };
-        std::vector<char> seen_a((size_t)n_slots_, 0);
-        for (int64_t sl = 0; sl < n_touched_; ++sl) seen_a[(size_t)sl] = 1;
-        std::vector<char> seen_b(seen_a);
-        int64_t upd_before_flow = (int64_t)upd.size();   // the level lists that run in front of the dataflow launch
-        if (flow_n_[0] > 0) {
-            const int r = lv_upd_round_[(size_t)flow_g0_[0]];
-            if (r < (int)upd_rounds_.size()) upd_before_flow = upd_rounds_[(size_t)r].first;
-        }
-        for (size_t q = 0; q < upd.size(); ++q) {
-            const int64_t sl = slot_of_ptr(upd[q].C);
-            if ((int64_t)q < upd_before_flow) seen_b[(size_t)sl] = 1;
-            if (!seen_a[(size_t)sl]) { seen_a[(size_t)sl] = 1; upd[q].C = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(upd[q].C) | 1); }
-        }
-        // the dataflow units: the first (tile, writer) of a tile not written below the launch; its nine block units share C, A, B
-        std::vector<const double*> first_a((size_t)n_slots_, nullptr), first_b((size_t)n_slots_, nullptr);
-        for (FactorUnit& u : funits) {
-            if (u.kind != 2 && u.kind != 3) continue;
-            const int64_t sl = slot_of_ptr(u.C);
-            if (!seen_b[(size_t)sl]) { seen_b[(size_t)sl] = 1; first_a[(size_t)sl] = u.A; first_b[(size_t)sl] = u.B; }
-            if (first_a[(size_t)sl] == u.A && first_b[(size_t)sl] == u.B && first_a[(size_t)sl] != nullptr) u.kind |= kFlowFirstWriter;
-        }
-        bool all = true;
-        for (int64_t sl = n_touched_; sl < n_slots_; ++sl) all = all && seen_a[(size_t)sl] && (flow_n_[0] == 0 || seen_b[(size_t)sl]);
-        if (all) first_ok_ = true;
-        else {   // (a fill tile without an update: cannot be -- take the flags back and clear everything as before)
-            for (GemmTask& t : upd) t.C = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(t.C) & ~uintptr_t(7));
-            for (FactorUnit& u : funits) u.kind &= 15;
-        }
+    if (distributed() || n_slots_ <= n_touched_ || flow_n_[1] != 0) return;
+    auto slot_of_ptr = [&](const double* c) { return (int64_t)((c - tiles) / (ptrdiff_t)(kNB * kNB)); };
+    std::vector<char> seen_a((size_t)n_slots_, 0);
+    for (int64_t sl = 0; sl < n_touched_; ++sl) seen_a[(size_t)sl] = 1;
+    std::vector<char> seen_b(seen_a);
+    int64_t upd_before_flow = (int64_t)upd_h_.size();   // the level lists that run in front of the dataflow launch
+    if (flow_n_[0] > 0) {
+        const int r = lv_[(size_t)flow_g0_[0]].upd;
+        if (r < (int)upd_rounds_.size()) upd_before_flow = upd_rounds_[(size_t)r].first;
     }
-    ptr_trace.mark("plan: task lists, dataflow units");
-    potrf_h_ = potrf; trsm_h_ = trsm; upd_h_ = upd; flow_units_h_ = funits;   // (kept for check_schedule / the tools: small)
-    TP_TRY(upload(&flow_units_, funits));
-    if (flow_ver_ && !dry_run_) { (void)hipFree(flow_ver_); flow_ver_ = nullptr; }
-    TP_TRY(dev_alloc(&flow_ver_, (size_t)n_slots_));
-    TP_TRY(hipMemset(flow_ver_, 0, (size_t)std::max<int64_t>(n_slots_, 1) * sizeof(int)));
-    n_sym_tiles_ = (int)symt.size();
-    TP_TRY(upload(&sym_tiles_, symt));
+    for (size_t q = 0; q < upd_h_.size(); ++q) {
+        const int64_t sl = slot_of_ptr(upd_h_[q].C);
+        if ((int64_t)q < upd_before_flow) seen_b[(size_t)sl] = 1;
+        if (!seen_a[(size_t)sl]) { seen_a[(size_t)sl] = 1; upd_h_[q].C = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(upd_h_[q].C) | 1); }
+    }
+    // the dataflow units: the first (tile, writer) of a tile not written below the launch; its nine block units share C, A, B
+    std::vector<const double*> first_a((size_t)n_slots_, nullptr), first_b((size_t)n_slots_, nullptr);
+    for (FactorUnit& u : flow_units_h_) {
+        if (u.kind != 2 && u.kind != 3) continue;
+        const int64_t sl = slot_of_ptr(u.C);
+        if (!seen_b[(size_t)sl]) { seen_b[(size_t)sl] = 1; first_a[(size_t)sl] = u.A; first_b[(size_t)sl] = u.B; }
+        if (first_a[(size_t)sl] == u.A && first_b[(size_t)sl] == u.B && first_a[(size_t)sl] != nullptr) u.kind |= kFlowFirstWriter;
+    }
+    bool all = true;
+    for (int64_t sl = n_touched_; sl < n_slots_; ++sl) all = all && seen_a[(size_t)sl] && (flow_n_[0] == 0 || seen_b[(size_t)sl]);
+    if (all) first_ok_ = true;
+    else {   // (a fill tile without an update: cannot be -- take the flags back and clear everything as before)
+        for (GemmTask& t : upd_h_) t.C = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(t.C) & ~uintptr_t(7));
+        for (FactorUnit& u : flow_units_h_) u.kind &= 15;
+    }
+}
+
+// The device step of build(): the lists and maps to the device, the work arrays, the streams and events.
+std::string TilePlan::upload(const Lists& lists) {
+    TP_TRY(upload_vec(&slot_, slot_h_));
+    TP_TRY(upload_vec(&diag_slot_, diag_slot_h_));
+    TP_TRY(alloc_zero(&flag_, 4));
+    TP_TRY(upload_vec(&flow_units_, flow_units_h_));
+    TP_TRY(alloc_zero(&flow_ver_, (size_t)n_slots_));
+    n_sym_tiles_ = (int)lists.sym_tiles.size();
+    TP_TRY(upload_vec(&sym_tiles_, lists.sym_tiles));
     TP_TRY(alloc_zero(&sym_part_, (size_t)n_slots_ * 2 * kNB));
     TP_TRY(alloc_zero(&row_dot_, (size_t)nt_));
     TP_TRY(alloc_zero(&blk_part_, 2 * (size_t)((n_pad() + 255) / 256)));
     TP_TRY(alloc_zero(&scal_, 8));
-    TP_TRY(upload(&tri_fwd_, tf));
-    TP_TRY(upload(&tri_bwd_, tb));
-    TP_TRY(upload(&flow_fwd_, ft));
-    TP_TRY(upload(&flow_bwd_, bt));
+    TP_TRY(upload_vec(&tri_fwd_, lists.fwd));
+    TP_TRY(upload_vec(&tri_bwd_, lists.bwd));
+    TP_TRY(upload_vec(&flow_fwd_, lists.flow_fwd));
+    TP_TRY(upload_vec(&flow_bwd_, lists.flow_bwd));
     TP_TRY(alloc_zero(&flow_part_, (size_t)std::max(n_flow_parts_, 1) * kNB));
-    if (flow_flags_ && !dry_run_) { (void)hipFree(flow_flags_); flow_flags_ = nullptr; }
-    TP_TRY(dev_alloc(&flow_flags_, (size_t)2 * nt_ + 1));   // cnt[nt] | done[nt] | error word of the dataflow sweeps
-    TP_TRY(hipMemset(flow_flags_, 0, ((size_t)2 * nt_ + 1) * sizeof(int)));
-    if (!flow_err_host_ && !dry_run_) {
+    TP_TRY(alloc_zero(&flow_flags_, (size_t)2 * nt_ + 1));   // cnt[nt] | done[nt] | error word of the dataflow sweeps
+    if (!flow_err_host_) {
         TP_TRY(hipHostMalloc(reinterpret_cast<void**>(&flow_err_host_), 4 * sizeof(int), hipHostMallocDefault));
         flow_err_host_[0] = flow_err_host_[1] = flow_err_host_[2] = flow_err_host_[3] = 0;
         void* dp = nullptr;   // (pinned host memory is mapped: the kernels that post a word write it through this address)
         flow_err_host_dev_ = hipHostGetDevicePointer(&dp, flow_err_host_, 0) == hipSuccess ? static_cast<int*>(dp) : nullptr;
         (void)hipGetLastError();
     }
-    TP_TRY(upload(&potrf_tasks_, potrf));
-    TP_TRY(upload(&trsm_tasks_, trsm));
-    TP_TRY(upload(&upd_tasks_, upd));
-    TP_TRY(upload(&sym_row_ptr_, sym_ptr));
-    TP_TRY(upload(&cls_, cls_h_));
+    TP_TRY(upload_vec(&potrf_tasks_, potrf_h_));
+    TP_TRY(upload_vec(&trsm_tasks_, trsm_h_));
+    TP_TRY(upload_vec(&upd_tasks_, upd_h_));
+    TP_TRY(upload_vec(&sym_row_ptr_, lists.sym_row_ptr));
+    TP_TRY(upload_vec(&cls_, cls_h_));
     TP_TRY(alloc_zero(&exch_, (size_t)n_pad()));
-    TP_TRY(upload(&sym_entries_, sym));
+    TP_TRY(upload_vec(&sym_entries_, lists.sym_entries));
     // (a lowest-priority side stream was tried: no gain without graphs, +2.7 ms with them)
     // (and so was a CU-masked one that leaves 1 CU in 8 / 4 / 2 to the critical path: the same, either way)
-    if (!side_) TP_TRY(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
-    if (!so_) TP_TRY(hipStreamCreateWithFlags(&so_, hipStreamNonBlocking));
-    if (!side2_) TP_TRY(hipStreamCreateWithFlags(&side2_, hipStreamNonBlocking));
-    ev_t_.resize(n_levels_); ev_u2_.resize(n_levels_); ev_o_.resize(n_levels_); ev_b_.resize(n_levels_); ev_b2_.resize(n_levels_);
-    if (dry_run_) {   // handles that identify streams and events in a schedule trace
-        side_ = reinterpret_cast<hipStream_t>(uintptr_t(0x52)); side2_ = reinterpret_cast<hipStream_t>(uintptr_t(0x53));
-        so_ = reinterpret_cast<hipStream_t>(uintptr_t(0x54));
-        for (int i = 0; i < n_levels_; ++i) {
-            ev_t_[i] = reinterpret_cast<hipEvent_t>(uintptr_t(0x10000 + 8 * i)); ev_u2_[i] = reinterpret_cast<hipEvent_t>(uintptr_t(0x10001 + 8 * i));
-            ev_o_[i] = reinterpret_cast<hipEvent_t>(uintptr_t(0x10002 + 8 * i)); ev_b_[i] = reinterpret_cast<hipEvent_t>(uintptr_t(0x10003 + 8 * i));
-            ev_b2_[i] = reinterpret_cast<hipEvent_t>(uintptr_t(0x10004 + 8 * i));
-        }
-        gate_cnt_ = reinterpret_cast<int*>(uintptr_t(1) << 46);
-    }
-    u2_pending_.assign(n_levels_, false);
-    o_pending_.assign(n_levels_, false);
-    for (int i = 0; i < n_levels_ && !dry_run_; ++i) {
-        TP_TRY(hipEventCreateWithFlags(&ev_t_[i], hipEventDisableTiming));
-        TP_TRY(hipEventCreateWithFlags(&ev_u2_[i], hipEventDisableTiming));
-        TP_TRY(hipEventCreateWithFlags(&ev_o_[i], hipEventDisableTiming));
-        TP_TRY(hipEventCreateWithFlags(&ev_b_[i], hipEventDisableTiming));
-        TP_TRY(hipEventCreateWithFlags(&ev_b2_[i], hipEventDisableTiming));
-    }
+    for (hipStream_t* s : {&side_, &so_, &side2_})
+        if (!*s) TP_TRY(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+    ev_.assign(n_levels_, {});
+    for (auto& evs : ev_)
+        for (hipEvent_t& ev : evs) TP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     TP_TRY(hipMalloc(&gate_cnt_, (size_t)(n_levels_ + 1) * sizeof(int)));
     TP_TRY(hipDeviceSynchronize());  // the null-stream memsets above precede any work on the stream
-    ptr_trace.mark("plan: uploads, streams, events");
-#undef TP_TRY
     return "";
 }
+#undef TP_TRY
 
-hipError_t TilePlan::zero_tiles(bool own_touched_only, hipStream_t on, bool skip_fill) {
-    const hipStream_t zs = on ? on : stream_;
+hipError_t TilePlan::zero_tiles(bool own_touched_only, bool skip_fill) {
     const size_t te = (size_t)kNB * kNB * sizeof(double);
     hipError_t e = hipSuccess;
     auto clear = [&](int64_t first, int64_t count) {
-        if (e == hipSuccess && count > 0) e = hipMemsetAsync(tiles_ + (size_t)first * kNB * kNB, 0, (size_t)count * te, zs);
+        if (e == hipSuccess && count > 0) e = hipMemsetAsync(tiles_ + (size_t)first * kNB * kNB, 0, (size_t)count * te, stream_);
     };
     if (distributed() && !own_all_ && part_rank_ < (int)own_range_.size()) {
         // a rank of a distributed plan factorises its own columns and the shared top: the fill tiles of the other ranks'
@@ -959,8 +939,7 @@ hipError_t TilePlan::zero_tiles(bool own_touched_only, hipStream_t on, bool skip
         clear(0, (skip_fill && first_ok_) ? n_touched_ : n_slots_);
     }
     if (e != hipSuccess) return e;
-    if (dry_run_) return hipSuccess;
-    launch_clear_i32(flag_, 4, zs);
+    launch_clear_i32(flag_, 4, stream_);
     return hipGetLastError();
 }
 
@@ -972,15 +951,15 @@ void TilePlan::scale_sym(const double* scale) { launch_tile_scale_sym(sym_tiles_
 
 void TilePlan::diag(double* out) const { launch_tile_diag(tiles_, diag_slot_, nt_, out, stream_); }
 
-// forward step of level group lv: one launch, or one per column where the plan asks for it (fwd_cut_)
+// forward step of level group lv: one launch, or one per column where the plan asks for it (Level::fwd_cut)
 void TilePlan::launch_fwd_group(int lv, double* bvec, double* yvec, hipStream_t s) {
-    const std::vector<int>& cut = fwd_cut_[lv];
+    const std::vector<int>& cut = lv_[lv].fwd_cut;
     if (cut.size() < 2) {
-        launch_tri_step(false, tri_fwd_ + lv_fwd_[lv], lv_fwd_[lv + 1] - lv_fwd_[lv], bvec, yvec, s);
+        launch_tri_step(false, tri_fwd_ + lv_[lv].fwd, lv_[lv + 1].fwd - lv_[lv].fwd, bvec, yvec, s);
         return;
     }
     for (size_t i = 0; i < cut.size(); ++i) {
-        const int b = cut[i], e = i + 1 < cut.size() ? cut[i + 1] : lv_fwd_[lv + 1];
+        const int b = cut[i], e = i + 1 < cut.size() ? cut[i + 1] : lv_[lv + 1].fwd;
         launch_tri_step(false, tri_fwd_ + b, e - b, bvec, yvec, s);
     }
 }
@@ -1000,130 +979,121 @@ void TilePlan::enqueue_factor(int g0, int g1) {
     //   once the flood gate let the potrf start on time);
     //   potrf(lv) after U1d(lv-1) [stream order] and whatever U1d(lv-1) waited for;
     //   panel(lv) after U1o(lv-1) [event];  U1o(lv) and U2(lv) hit different columns (level lv+1 / above);
-    //   a U2 too small for the side stream runs on the main stream after the side stream's last U2b [ev_b_].
-    // Every call below goes through these shadows: with a trace attached (schedule_trace: tests, host-only plans) the call
-    // is recorded instead of issued -- what check_schedule() then proves is this very sequence.
+    //   a U2 too small for the side stream runs on the main stream after the side stream's last U2b [kEvB].
+    // Every call below goes through these shadows (streams and events by id): with a trace attached (schedule_trace: tests,
+    // host-only plans) the call is recorded instead of issued -- what check_schedule() then proves is this very sequence.
     std::vector<SchedOp>* const tr = sched_trace_;
-    auto hipStreamWaitEvent = [&](hipStream_t s, hipEvent_t e, unsigned) { if (tr) { tr->push_back({2, (uintptr_t)s, (uintptr_t)e, -1, 0, 0}); return hipSuccess; } return ::hipStreamWaitEvent(s, e, 0); };
-    auto hipEventRecord = [&](hipEvent_t e, hipStream_t s) { if (tr) { tr->push_back({1, (uintptr_t)s, (uintptr_t)e, -1, 0, 0}); return hipSuccess; } return ::hipEventRecord(e, s); };
-    auto launch_potrf_inv = [&](const PotrfTask* t, int n, int* fail, hipStream_t s, int* arrived) {
-        if (tr) { if (n > 0) tr->push_back({0, (uintptr_t)s, 0, 0, (int64_t)(t - potrf_tasks_), n}); return; }
-        apex::launch_potrf_inv(t, n, fail, s, arrived);
+    auto wait = [&](StreamId s, int lv, LevelEvent k) { if (tr) tr->push_back({2, (uintptr_t)s, (uintptr_t)lv * kLevelEvents + k, -1, 0, 0}); else (void)hipStreamWaitEvent(stream_of(s), ev_[lv][k], 0); };
+    auto record = [&](int lv, LevelEvent k, StreamId s) { if (tr) tr->push_back({1, (uintptr_t)s, (uintptr_t)lv * kLevelEvents + k, -1, 0, 0}); else (void)hipEventRecord(ev_[lv][k], stream_of(s)); };
+    auto potrf = [&](int lv) {   // (main stream)
+        const int first = lv_[lv].potrf, n = lv_[lv + 1].potrf - first;
+        if (tr) { if (n > 0) tr->push_back({0, kMain, 0, 0, first, n}); } else launch_potrf_inv(potrf_tasks_ + first, n, flag_, stream_, gate_min_ > 0 ? gate_cnt_ + lv : nullptr);
     };
-    auto launch_tile_gemm_nt = [&](const GemmTask* t, int n, double alpha, double beta, hipStream_t s) {
-        if (tr) {
-            const bool panel = beta == 0.0;
-            if (n > 0) tr->push_back({0, (uintptr_t)s, 0, panel ? 1 : 2, (int64_t)(t - (panel ? trsm_tasks_ : upd_tasks_)), n});
-            return;
+    auto panel = [&](int lv) {   // (main stream; the panel solves multiply by Linv)
+        const int first = lv_[lv].panel, n = lv_[lv + 1].panel - first;
+        if (tr) { if (n > 0) tr->push_back({0, kMain, 0, 1, first, n}); } else launch_tile_gemm_nt(trsm_tasks_ + first, n, 1.0, 0.0, stream_, /*tri_b=*/true);
+    };
+    auto updates = [&](int r0, int r1, StreamId s) {   // update rounds [r0, r1), one launch each
+        for (int r = r0; r < r1; ++r) {
+            const auto [first, n] = upd_rounds_[r];
+            if (tr) { if (n > 0) tr->push_back({0, (uintptr_t)s, 0, 2, first, (int)n}); } else launch_tile_gemm_nt(upd_tasks_ + first, (int)n, -1.0, 1.0, stream_of(s));
         }
-        apex::launch_tile_gemm_nt(t, n, alpha, beta, s, /*tri_b=*/beta == 0.0);   // the panel solves multiply by Linv
     };
-    auto launch_gate = [&](const int* a, int expected, int us, hipStream_t s) { if (!tr) apex::launch_gate(a, expected, us, s); };
-    auto hipMemsetAsync = [&](void* p, int v, size_t n, hipStream_t s) { if (tr) return hipSuccess; return ::hipMemsetAsync(p, v, n, s); };
-    auto launch_clear_i32 = [&](int* p, int64_t n, hipStream_t s) { if (!tr) apex::launch_clear_i32(p, n, s); };
-    auto launch_factor_flow = [&](const FactorUnit* u, int n, int* ver, int* fail, int* err, hipStream_t s, unsigned long long* trace) {
-        if (tr) { tr->push_back({0, (uintptr_t)s, 0, 3, (int64_t)(u - flow_units_), n}); return; }
-        apex::launch_factor_flow(u, n, ver, fail, err, s, trace);
-    };
-    const bool two = overlap_ && side_ != nullptr && n_levels_ > 2;
+    auto gate = [&](int lv, StreamId s) { if (!tr) launch_gate(gate_cnt_ + lv + 1, lv_[lv + 2].potrf - lv_[lv + 1].potrf, 150, stream_of(s)); };
+    const bool two = overlap_ && n_levels_ > 2;
     // the trailing groups [gf, g1) of this phase run as one dataflow launch behind the level launches (build())
     const int ph = (g0 == n_local_groups_ && g1 == n_levels_ && n_local_groups_ < n_levels_) ? 1 : 0;
     const int g_end = g1;
     if (flow_on_ && flow_n_[ph] > 0 && flow_g0_[ph] >= g0 && flow_g1_[ph] == g1) g1 = flow_g0_[ph];
-    if (gate_min_ > 0 && gate_cnt_) launch_clear_i32(gate_cnt_, n_levels_ + 1, stream_);
+    if (gate_min_ > 0 && !tr) launch_clear_i32(gate_cnt_, n_levels_ + 1, stream_);
     int last_a = -1, last_b = -1;   // last levels with work on the side streams A / B that the main stream has not waited for
     std::vector<int> lastb((size_t)std::max(g1 - g0, 1), -1);   // lastb[lv - g0]: the last level <= lv with U2b2 work on stream B
+    bool u2_pending = false, o_pending = false;   // the previous level group put its U2a / U1o on a side stream (recorded kEvU2 / kEvO)
     int b2_pending = -1, a_waited = -1;
     auto a_wait_upto = [&](int lvb) {   // stream A waits for stream B up to level lvb's U2b2 (B runs in order)
-        if (lvb > a_waited) { (void)hipStreamWaitEvent(side_, ev_b2_[lvb], 0); a_waited = lvb; }
+        if (lvb > a_waited) { wait(kSide, lvb, kEvB2); a_waited = lvb; }
     };
     for (int lv = g0; lv < g1; ++lv) {
-        launch_potrf_inv(potrf_tasks_ + lv_potrf_[lv], lv_potrf_[lv + 1] - lv_potrf_[lv], flag_, stream_,
-                         gate_min_ > 0 && gate_cnt_ ? gate_cnt_ + lv : nullptr);
+        potrf(lv);
         // the panel solves work on the off-diagonal tiles of this level's columns: U1o of the level below must be in
-        if (lv > g0 && o_pending_[lv - 1]) (void)hipStreamWaitEvent(stream_, ev_o_[lv - 1], 0);
-        const int r0 = lv_upd_round_[lv], rd = lv_upd_splitd_[lv], rs = lv_upd_split_[lv], r1 = lv_upd_round_[lv + 1];
+        if (lv > g0 && o_pending) wait(kMain, lv - 1, kEvO);
+        const int r0 = lv_[lv].upd, rd = lv_[lv].u1o, rs = lv_[lv].u2a, r1 = lv_[lv + 1].upd;
         int64_t n_u2 = 0, n_o = 0;
         for (int r = rs; r < r1; ++r) n_u2 += upd_rounds_[r].second;
         for (int r = rd; r < rs; ++r) n_o += upd_rounds_[r].second;
         // a cross-stream edge costs a few microseconds in the graph: only worth it when the batch is a real one
         const bool has_u2 = two && n_u2 >= overlap_min_;
-        const bool has_o = two && so_ != nullptr && split_u1_ && n_o >= split_u1_min_;
-        launch_tile_gemm_nt(trsm_tasks_ + lv_trsm_[lv], lv_trsm_[lv + 1] - lv_trsm_[lv], 1.0, 0.0, stream_);
-        if (has_u2 || has_o) (void)hipEventRecord(ev_t_[lv], stream_);
-        if (has_u2) (void)hipStreamWaitEvent(side_, ev_t_[lv], 0);
-        if (has_o) (void)hipStreamWaitEvent(so_, ev_t_[lv], 0);
-        if (two && lv > g0 && u2_pending_[lv - 1]) {
-            (void)hipStreamWaitEvent(stream_, ev_u2_[lv - 1], 0);
-            if (has_o) (void)hipStreamWaitEvent(so_, ev_u2_[lv - 1], 0);
+        const bool has_o = two && split_u1_ && n_o >= split_u1_min_;
+        panel(lv);
+        if (has_u2 || has_o) record(lv, kEvT, kMain);
+        if (has_u2) wait(kSide, lv, kEvT);
+        if (has_o) wait(kSo, lv, kEvT);
+        if (two && lv > g0 && u2_pending) {
+            wait(kMain, lv - 1, kEvU2);
+            if (has_o) wait(kSo, lv - 1, kEvU2);
         } else if (two && lv > g0 && !debug_skip_idle_wait_) {
-            // Level lv-1 put nothing on the side streams, so there is no ev_u2_[lv-1] to carry "every older side-stream update
+            // Level lv-1 put nothing on the side streams, so there is no kEvU2 of lv-1 to carry "every older side-stream update
             // precedes U1(lv)": U2b1(lv-2) [targets in level lv+1, stream A] and the U2b2 of levels <= lv-3 [stream B] may
             // still be at work on the tiles U1(lv) is about to update (and that potrf(lv+1) then reads).  Levels are assigned
             // by height, so a chain can pass through such a level.  Wait for both side streams outright.
             if (last_a >= 0) {
-                (void)hipStreamWaitEvent(stream_, ev_b_[last_a], 0);
-                if (has_o) (void)hipStreamWaitEvent(so_, ev_b_[last_a], 0);
+                wait(kMain, last_a, kEvB);
+                if (has_o) wait(kSo, last_a, kEvB);
                 last_a = -1;
             }
             if (last_b >= 0) {
-                (void)hipStreamWaitEvent(stream_, ev_b2_[last_b], 0);
-                if (has_o) (void)hipStreamWaitEvent(so_, ev_b2_[last_b], 0);
+                wait(kMain, last_b, kEvB2);
+                if (has_o) wait(kSo, last_b, kEvB2);
                 last_b = -1;
             }
         }
-        for (int r = r0; r < rd; ++r)   // U1d: what the next potrf needs
-            launch_tile_gemm_nt(upd_tasks_ + upd_rounds_[r].first, (int)upd_rounds_[r].second, -1.0, 1.0, stream_);
-        hipStream_t s1 = has_o ? so_ : stream_;
-        for (int r = rd; r < rs; ++r)   // U1o: what the next panel solves need, beside the next potrf
-            launch_tile_gemm_nt(upd_tasks_ + upd_rounds_[r].first, (int)upd_rounds_[r].second, -1.0, 1.0, s1);
-        o_pending_[lv] = has_o;
-        if (has_o) (void)hipEventRecord(ev_o_[lv], so_);
+        updates(r0, rd, kMain);   // U1d: what the next potrf needs
+        updates(rd, rs, has_o ? kSo : kMain);   // U1o: what the next panel solves need, beside the next potrf
+        o_pending = has_o;
+        if (has_o) record(lv, kEvO, kSo);
         // U2 on two streams of its own.  A (side_): U2a(lv) [targets in level lv+2: what U1(lv+1) waits for], then U2b1(lv)
         // [level lv+3].  B (side2_): U2b2(lv) [level lv+4 and above: the bulk].  Writers of one target level t, in time:
         // U2b2(<= t-4) -> U2b1(t-3) -> U2a(t-2) -> U1(t-1); B orders the first among themselves, U2b1(lv) waits for
-        // U2b2(lv-1) [ev_b2_], the rest is stream order on A and ev_u2_.  U2a(lv+1) thus waits for U2b1(lv) only, not for the
+        // U2b2(lv-1) [kEvB2], the rest is stream order on A and kEvU2.  U2a(lv+1) thus waits for U2b1(lv) only, not for the
         // bulk of level lv (on one stream it did, and through it U1d(lv+2) and the potrf behind it).
         // (only when there is such work: a stream that joins the capture must come back to it with an event)
-        const bool b2_side = has_u2 && side2_ != nullptr && two_side_plan_ && r1 > lv_upd_splitb_[lv];
+        const bool b2_side = has_u2 && two_side_plan_ && r1 > lv_[lv].u2b2;
         // flood gate: the bulk updates of a big level start when the next level's potrf workgroups sit on their CUs (they
         // follow U1d on the main stream) -- otherwise the update's grid takes every CU first and the potrf, 124 KB of LDS per
         // workgroup, waits for it to drain
-        const bool gated = has_u2 && gate_min_ > 0 && gate_cnt_ && n_u2 >= gate_min_ && lv + 1 < g1;
-        if (gated) launch_gate(gate_cnt_ + lv + 1, lv_potrf_[lv + 2] - lv_potrf_[lv + 1], 150, side_);
+        const bool gated = has_u2 && gate_min_ > 0 && n_u2 >= gate_min_ && lv + 1 < g1;
+        if (gated) gate(lv, kSide);
         // a small U2 stays on the main stream: earlier levels' U2b may still be at work on the same targets over there
         if (!has_u2 && r1 > rs) {
-            if (last_a >= 0) { (void)hipStreamWaitEvent(stream_, ev_b_[last_a], 0); last_a = -1; }
-            if (last_b >= 0) { (void)hipStreamWaitEvent(stream_, ev_b2_[last_b], 0); last_b = -1; }
+            if (last_a >= 0) { wait(kMain, last_a, kEvB); last_a = -1; }
+            if (last_b >= 0) { wait(kMain, last_b, kEvB2); last_b = -1; }
         }
-        const int ra = lv_upd_splita_[lv], rb = lv_upd_splitb_[lv];
-        hipStream_t sa = has_u2 ? side_ : stream_, sb = b2_side ? side2_ : sa;
+        const int ra = lv_[lv].u2b1, rb = lv_[lv].u2b2;
+        const StreamId sa = has_u2 ? kSide : kMain, sb = b2_side ? kSide2 : sa;
         // U2a(lv) [level lv+2] follows every U2b2 of levels <= lv-2 [their targets start at level lv+2] ...
         if (has_u2 && lv - 2 >= g0) a_wait_upto(lastb[lv - 2 - g0]);
-        for (int r = rs; r < ra; ++r)   // U2a
-            launch_tile_gemm_nt(upd_tasks_ + upd_rounds_[r].first, (int)upd_rounds_[r].second, -1.0, 1.0, sa);
-        u2_pending_[lv] = has_u2;
-        if (has_u2) (void)hipEventRecord(ev_u2_[lv], side_);   // ... and, in stream order, every earlier update on A
+        updates(rs, ra, sa);   // U2a
+        u2_pending = has_u2;
+        if (has_u2) record(lv, kEvU2, kSide);   // ... and, in stream order, every earlier update on A
         if (b2_side) {
-            (void)hipStreamWaitEvent(side2_, ev_t_[lv], 0);
-            if (gated) launch_gate(gate_cnt_ + lv + 1, lv_potrf_[lv + 2] - lv_potrf_[lv + 1], 150, side2_);
+            wait(kSide2, lv, kEvT);
+            if (gated) gate(lv, kSide2);
         }
         if (has_u2 && lv - 1 >= g0) a_wait_upto(lastb[lv - 1 - g0]);   // ... and U2b1(lv) [level lv+3] every U2b2 of levels <= lv-1
-        for (int r = ra; r < rb; ++r)   // U2b1
-            launch_tile_gemm_nt(upd_tasks_ + upd_rounds_[r].first, (int)upd_rounds_[r].second, -1.0, 1.0, sa);
-        for (int r = rb; r < r1; ++r)   // U2b2
-            launch_tile_gemm_nt(upd_tasks_ + upd_rounds_[r].first, (int)upd_rounds_[r].second, -1.0, 1.0, sb);
-        if (has_u2) { (void)hipEventRecord(ev_b_[lv], side_); last_a = lv; }
-        if (b2_side) { (void)hipEventRecord(ev_b2_[lv], side2_); last_b = lv; }
+        updates(ra, rb, sa);   // U2b1
+        updates(rb, r1, sb);   // U2b2
+        if (has_u2) { record(lv, kEvB, kSide); last_a = lv; }
+        if (b2_side) { record(lv, kEvB2, kSide2); last_b = lv; }
         lastb[lv - g0] = b2_pending = b2_side ? lv : b2_pending;
     }
-    if (g1 > g0 && o_pending_[g1 - 1]) (void)hipStreamWaitEvent(stream_, ev_o_[g1 - 1], 0);
+    if (g1 > g0 && o_pending) wait(kMain, g1 - 1, kEvO);
     // join: the last side-stream work precedes whatever follows on the main stream
-    if (last_a >= 0) (void)hipStreamWaitEvent(stream_, ev_b_[last_a], 0);
-    if (last_b >= 0) (void)hipStreamWaitEvent(stream_, ev_b2_[last_b], 0);
+    if (last_a >= 0) wait(kMain, last_a, kEvB);
+    if (last_b >= 0) wait(kMain, last_b, kEvB2);
     if (g1 < g_end) {   // every update the level launches add to the region's tiles is in: the joins above
+        if (tr) { tr->push_back({0, kMain, 0, 3, flow_first_[ph], flow_n_[ph]}); return; }
         launch_clear_i32(flow_ver_, n_slots_, stream_);
-        if (poison_factor_ && !tr)   // (tests: the version of the first unit's tile starts hugely negative and is never reached)
+        if (poison_factor_)   // (tests: the version of the first unit's tile starts hugely negative and is never reached)
             (void)hipMemsetAsync(flow_ver_ + flow_units_h_[(size_t)flow_first_[ph]].pub, 0x80, sizeof(int), stream_);
         launch_factor_flow(flow_units_ + flow_first_[ph], flow_n_[ph], flow_ver_, flag_, flag_ + 1, stream_,
                            flow_trace_ ? flow_trace_ + 3 * (size_t)flow_first_[ph] : nullptr);
@@ -1149,7 +1119,7 @@ void TilePlan::enqueue_solve(const double* rhs, double* x, double* work) {
         return;
     }
     for (int s = 0; s < n_levels_; ++s)
-        launch_tri_step(true, tri_bwd_ + lv_bwd_[s], lv_bwd_[s + 1] - lv_bwd_[s], yvec, x, stream_);
+        launch_tri_step(true, tri_bwd_ + bwd_step_[s], bwd_step_[s + 1] - bwd_step_[s], yvec, x, stream_);
 }
 
 // The distributed triangular solves (see tile_plan.h).  bvec/yvec as in enqueue_solve; masks: bit (1 << class).
@@ -1183,16 +1153,15 @@ void TilePlan::enqueue_dist_solve(int phase, const double* rhs, double* x, doubl
         for (int lv = L1; lv < n_levels_; ++lv)
             launch_fwd_group(lv, bvec, yvec, stream_);
         for (int s = 0; s < n_levels_; ++s)  // top groups first, then this rank's
-            launch_tri_step(true, tri_bwd_ + lv_bwd_[s], lv_bwd_[s + 1] - lv_bwd_[s], yvec, x, stream_);
+            launch_tri_step(true, tri_bwd_ + bwd_step_[s], bwd_step_[s + 1] - bwd_step_[s], yvec, x, stream_);
         launch_vec_select(n, x, cls_, part_rank_ == 0 ? 6 : 2, exch_, stream_);
     } else {
         (void)hipMemcpyAsync(x, exch_, n_pad() * sizeof(double), hipMemcpyDeviceToDevice, stream_);
     }
 }
 
-// graph 0: factorisation of the local levels (all levels, + fused forward sweep when rhs/work are given, in a plan
-// that is not distributed), 1: both sweeps, 2: backward sweep only, 3: factorisation of the top levels,
-// 4/5: phases 0/1 of the distributed solve
+// kGraphFactor: factorisation of the local level groups (all of them in a plan that is not distributed), kGraphSweeps: both
+// sweeps, kGraphFactorTop: factorisation of the top level groups, kGraphDistSolve0 / 1: phases 0 / 1 of the distributed solve
 bool TilePlan::run_graph(int which, const double* rhs, double* x, double* work) {
     if (!use_graphs_) return false;
     if (graph_exec_[which] && (rhs != graph_rhs_[which] || x != graph_x_[which] || work != graph_work_[which])) {
@@ -1203,9 +1172,9 @@ bool TilePlan::run_graph(int which, const double* rhs, double* x, double* work) 
         if (graph_failed_[which]) return false;
         hipGraph_t g = nullptr;
         if (hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal) != hipSuccess) { graph_failed_[which] = true; return false; }
-        if (which == 0) enqueue_factor(0, n_local_groups_);
-        else if (which == 3) enqueue_factor(n_local_groups_, n_levels_);
-        else if (which == 4 || which == 5) enqueue_dist_solve(which - 4, rhs, x, work);
+        if (which == kGraphFactor) enqueue_factor(0, n_local_groups_);
+        else if (which == kGraphFactorTop) enqueue_factor(n_local_groups_, n_levels_);
+        else if (which == kGraphDistSolve0 || which == kGraphDistSolve1) enqueue_dist_solve(which - kGraphDistSolve0, rhs, x, work);
         else enqueue_solve(rhs, x, work);
         if (hipStreamEndCapture(stream_, &g) != hipSuccess || !g) { graph_failed_[which] = true; (void)hipGetLastError(); return false; }
         hipGraphExec_t ex = nullptr;
@@ -1220,7 +1189,7 @@ bool TilePlan::run_graph(int which, const double* rhs, double* x, double* work) 
 void TilePlan::enable_tri_flow(bool on) {
     if (on == tri_flow_) return;
     tri_flow_ = on;
-    for (int which : {1, 4, 5})   // the captured sweeps change
+    for (int which : {kGraphSweeps, kGraphDistSolve0, kGraphDistSolve1})   // the captured sweeps change
         if (graph_exec_[which]) { (void)hipGraphExecDestroy(graph_exec_[which]); graph_exec_[which] = nullptr; }
 }
 
@@ -1229,7 +1198,7 @@ hipError_t TilePlan::enable_flow_trace() {
     const size_t n = 3 * (size_t)std::max(flow_n_[0] + flow_n_[1], 1);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&flow_trace_), n * sizeof(unsigned long long));
     if (e != hipSuccess) return e;
-    for (int which : {0, 3})   // the captured launches hold the old (null) pointer
+    for (int which : {kGraphFactor, kGraphFactorTop})   // the captured launches hold the old (null) pointer
         if (graph_exec_[which]) { (void)hipGraphExecDestroy(graph_exec_[which]); graph_exec_[which] = nullptr; }
     return hipMemset(flow_trace_, 0, n * sizeof(unsigned long long));
 }
@@ -1335,12 +1304,12 @@ void TilePlan::top_slot_ranges(std::pair<int64_t, int64_t> out[2]) const {
 }
 
 void TilePlan::factor_phase(int phase) {
-    if (phase == 0) { if (!run_graph(0, nullptr, nullptr, nullptr)) enqueue_factor(0, n_local_groups_); }
-    else if (!run_graph(3, nullptr, nullptr, nullptr)) enqueue_factor(n_local_groups_, n_levels_);
+    if (phase == 0) { if (!run_graph(kGraphFactor, nullptr, nullptr, nullptr)) enqueue_factor(0, n_local_groups_); }
+    else if (!run_graph(kGraphFactorTop, nullptr, nullptr, nullptr)) enqueue_factor(n_local_groups_, n_levels_);
 }
 
 void TilePlan::solve_phase(int phase, const double* rhs, double* x, double* work) {
-    if (phase == 2 || !run_graph(4 + phase, rhs, x, work)) enqueue_dist_solve(phase, rhs, x, work);
+    if (phase == 2 || !run_graph(kGraphDistSolve0 + phase, rhs, x, work)) enqueue_dist_solve(phase, rhs, x, work);
 }
 
 hipError_t TilePlan::factor(int* failed_at, bool defer_flags) {
@@ -1359,7 +1328,7 @@ hipError_t TilePlan::factor(int* failed_at, bool defer_flags) {
     if (poison_factor_) {   // (tests: the poisoned launch is not part of the captured graphs)
         enqueue_factor(0, n_levels_);
         poison_factor_ = false;
-    } else if (!run_graph(0, nullptr, nullptr, nullptr)) enqueue_factor(0, n_levels_);
+    } else if (!run_graph(kGraphFactor, nullptr, nullptr, nullptr)) enqueue_factor(0, n_levels_);
     if (defer_flags) { *failed_at = 0; return hipGetLastError(); }
     return read_flags(failed_at);
 }
@@ -1377,7 +1346,7 @@ hipError_t TilePlan::read_flags(int* failed_at) {
         // rest of the plan's life; the caller re-assembles and factorises again (factor_flow_gave_up()).
         flow_gave_up_ = true;
         flow_on_ = false;
-        for (int which : {0, 3})
+        for (int which : {kGraphFactor, kGraphFactorTop})
             if (graph_exec_[which]) { (void)hipGraphExecDestroy(graph_exec_[which]); graph_exec_[which] = nullptr; }
         (void)hipMemsetAsync(flag_ + 1, 0, sizeof(int), stream_);
     }
@@ -1432,7 +1401,7 @@ hipError_t TilePlan::solve(const double* rhs, double* x, double* work) {
     if (poison_ != 0) {   // (tests: the poisoned launch is not part of the captured graphs)
         enqueue_solve(rhs, x, work);
         poison_ = 0;
-    } else if (!run_graph(1, rhs, x, work)) enqueue_solve(rhs, x, work);
+    } else if (!run_graph(kGraphSweeps, rhs, x, work)) enqueue_solve(rhs, x, work);
     if (tri_flow_ && n_flow_tasks_ > 0) (void)post_sweep_status(false);
     return hipGetLastError();
 }
