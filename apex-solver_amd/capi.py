@@ -24,7 +24,7 @@ SYMBOLS = (
     "apexgpu_set_cg_params", "apexgpu_set_params", "apexgpu_get_params", "apexgpu_cost", "apexgpu_assemble", "apexgpu_solve_augmented",
     "apexgpu_step_stats", "apexgpu_eval_step", "apexgpu_commit_step", "apexgpu_discard_step",
     "apexgpu_parameter_norm", "apexgpu_column_norms", "apexgpu_set_column_scaling", "apexgpu_lm_optimize", "apexgpu_get_residual", "apexgpu_get_jacobian_blocks",
-    "apexgpu_get_schur", "apexgpu_get_landmark_blocks", "apexgpu_get_hessian_csc", "apexgpu_debug_invert_blocks", "apexgpu_debug_pair_lists", "apexgpu_debug_pair_lists_queued", "apexgpu_debug_pair_lists_queued_dc", "apexgpu_debug_host_structure", "apexgpu_setup_times", "apexgpu_schur_matvec", "apexgpu_set_option", "apexgpu_enable_stage_timing", "apexgpu_reset_stage_times",
+    "apexgpu_get_schur", "apexgpu_camera_covariance", "apexgpu_covariance_stats", "apexgpu_get_landmark_blocks", "apexgpu_get_hessian_csc", "apexgpu_debug_invert_blocks", "apexgpu_debug_pair_lists", "apexgpu_debug_pair_lists_queued", "apexgpu_debug_pair_lists_queued_dc", "apexgpu_debug_host_structure", "apexgpu_setup_times", "apexgpu_schur_matvec", "apexgpu_set_option", "apexgpu_enable_stage_timing", "apexgpu_reset_stage_times",
     "apexgpu_stage_times", "apexgpu_info", "apexgpu_variant_info", "apexgpu_variant_costs", "apexgpu_trim_host_cache", "apexgpu_host_cache_bytes", "apexgpu_counters", "apexgpu_debug_get_pair_records", "apexgpu_get_unique_id", "apexgpu_comm_init", "apexgpu_comm_init_shm", "apexgpu_set_shard", "apexgpu_shard_range",
     "apexgpu_debug_lockstep_solve", "apexgpu_export_step", "apexgpu_owned_landmarks", "apexgpu_debug_partition", "apexgpu_debug_check_schedule",
     "apexgpu_bal_open", "apexgpu_bal_close", "apexgpu_bal_last_error", "apexgpu_bal_sizes", "apexgpu_bal_raw",
@@ -34,7 +34,7 @@ SYMBOLS = (
     "apexgpu_pg_get_params", "apexgpu_pg_cost", "apexgpu_pg_solve_augmented", "apexgpu_pg_step_stats", "apexgpu_pg_eval_step",
     "apexgpu_pg_commit_step", "apexgpu_pg_discard_step", "apexgpu_pg_parameter_norm", "apexgpu_pg_column_norms",
     "apexgpu_pg_set_column_scaling", "apexgpu_pg_lm_optimize",
-    "apexgpu_pg_get_residual", "apexgpu_pg_get_jacobian_blocks", "apexgpu_pg_get_hessian", "apexgpu_pg_set_option",
+    "apexgpu_pg_get_residual", "apexgpu_pg_get_jacobian_blocks", "apexgpu_pg_get_hessian", "apexgpu_pg_covariance", "apexgpu_pg_covariance_stats", "apexgpu_pg_set_option",
     "apexgpu_pg_enable_stage_timing", "apexgpu_pg_reset_stage_times", "apexgpu_pg_stage_times", "apexgpu_pg_info", "apexgpu_pg_counters",
     "apexgpu_pg_set_priors", "apexgpu_pg_get_prior_residual",
     "apexgpu_g2o_open", "apexgpu_g2o_close", "apexgpu_g2o_last_error", "apexgpu_g2o_sizes", "apexgpu_g2o_raw",
@@ -128,6 +128,8 @@ def load() -> C.CDLL:
     L.apexgpu_get_residual.argtypes = [vp, vp]
     L.apexgpu_get_jacobian_blocks.argtypes = [vp, vp, vp]
     L.apexgpu_get_schur.argtypes = [vp, vp, vp]
+    L.apexgpu_camera_covariance.argtypes = [vp, vp]
+    L.apexgpu_covariance_stats.argtypes = [vp, C.POINTER(dbl * 6), vp, C.c_int]
     L.apexgpu_get_landmark_blocks.argtypes = [vp, vp, vp]
     L.apexgpu_schur_matvec.argtypes = [vp, dbl, vp, vp, vp]
     L.apexgpu_set_option.argtypes = [vp, C.c_char_p, C.c_int]
@@ -184,6 +186,8 @@ def load() -> C.CDLL:
     L.apexgpu_pg_get_residual.argtypes = [vp, vp]
     L.apexgpu_pg_get_jacobian_blocks.argtypes = [vp, vp]
     L.apexgpu_pg_get_hessian.argtypes = [vp, dbl, vp, vp]
+    L.apexgpu_pg_covariance.argtypes = [vp, vp]
+    L.apexgpu_pg_covariance_stats.argtypes = [vp, C.POINTER(dbl * 6), vp, C.c_int]
     L.apexgpu_pg_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     L.apexgpu_pg_enable_stage_timing.argtypes = [vp, C.c_int]
     L.apexgpu_pg_reset_stage_times.argtypes = [vp]

@@ -51,6 +51,21 @@ static int guarded(F&& f) noexcept {
     }
 }
 
+template <typename S>
+static int covariance_stats(S* s, double out[6], double* group_ms, int group_cap) {
+    if (!out) return APEXGPU_ERR_INVALID_INPUT;
+    const apex::TilePlan& tp = s->plan();
+    int64_t y = 0, zo = 0, zd = 0;
+    tp.covariance_op_counts(&y, &zo, &zd);
+    const std::vector<double>& ms = tp.covariance_group_ms();
+    out[0] = (double)tp.covariance_bytes(); out[1] = (double)y; out[2] = (double)zo; out[3] = (double)zd; out[4] = tp.n_levels();
+    int n = 0;
+    if (group_ms)
+        for (; n < group_cap && n < (int)ms.size(); ++n) group_ms[n] = ms[n];
+    out[5] = n;
+    return APEXGPU_OK;
+}
+
 // APEX_SEGV_BACKTRACE=1 (debugging aid): the native stack of a crash on stderr (the GPU boxes have no debugger)
 #include <execinfo.h>
 #include <signal.h>
@@ -158,6 +173,8 @@ int apexgpu_get_jacobian_blocks(apexgpu_solver* h, double* jc_out, double* jl_ou
     return guarded([&] { return h->s->get_jacobian_blocks(jc_out, jl_out); });
 }
 int apexgpu_get_schur(apexgpu_solver* h, double* S_out, double* gred_out) { H_OR_FAIL; return guarded([&] { return h->s->get_schur(S_out, gred_out); }); }
+int apexgpu_camera_covariance(apexgpu_solver* h, double* cov_out) { H_OR_FAIL; return guarded([&] { return h->s->camera_covariance(cov_out); }); }
+int apexgpu_covariance_stats(apexgpu_solver* h, double out[6], double* group_ms, int group_cap) { H_OR_FAIL; return covariance_stats(h->s, out, group_ms, group_cap); }
 int apexgpu_get_landmark_blocks(apexgpu_solver* h, double* hinv_out, double* gl_out) {
     H_OR_FAIL;
     return guarded([&] { return h->s->get_landmark_blocks(hinv_out, gl_out); });
@@ -318,6 +335,7 @@ int apexgpu_set_option(apexgpu_solver* h, const char* name, int value) {
     else if (n == "tree_sharding") h->s->set_tree_sharding(value != 0);
     else if (n == "dist_selftest") h->s->set_dist_selftest(value);
     else if (n == "nested_dissection") h->s->set_nd(value != 0, value > 1 ? value : 0);  /* value > 1: leaf size */
+    else if (n == "covariance_timing") h->s->enable_covariance_timing(value != 0);   /* per level group times of apexgpu_camera_covariance */
     else return APEXGPU_ERR_INVALID_INPUT;
     return APEXGPU_OK;
 }
@@ -641,6 +659,11 @@ int apexgpu_pg_get_hessian(apexgpu_pg_solver* h, double lambda, double* H_out, d
     PG_OR_FAIL;
     return h->s->get_hessian(lambda, H_out, g_out);
 }
+int apexgpu_pg_covariance(apexgpu_pg_solver* h, double* cov_out) {
+    PG_OR_FAIL;
+    return guarded([&] { return h->s->covariance(cov_out); });
+}
+int apexgpu_pg_covariance_stats(apexgpu_pg_solver* h, double out[6], double* group_ms, int group_cap) { PG_OR_FAIL; return covariance_stats(h->s, out, group_ms, group_cap); }
 int apexgpu_pg_set_option(apexgpu_pg_solver* h, const char* name, int value) {
     PG_OR_FAIL;
     const std::string n = name ? name : "";
@@ -657,6 +680,7 @@ int apexgpu_pg_set_option(apexgpu_pg_solver* h, const char* name, int value) {
     else if (n == "nested_dissection") h->s->set_nd(value != 0, value > 1 ? value : 0);
     else if (n == "debug_poison_sweep") h->s->debug_poison_next_solve(value);
     else if (n == "debug_poison_factor") h->s->debug_poison_next_factor();
+    else if (n == "covariance_timing") h->s->enable_covariance_timing(value != 0);
     else return APEXGPU_ERR_INVALID_INPUT;
     return APEXGPU_OK;
 }

@@ -52,6 +52,14 @@ class PoseGraphSolver : public LmBackend {
     int get_residual(double* r_out);
     int get_jacobian_blocks(double* j_out);
     int get_hessian(double lambda, double* H_out, double* g_out);  // dense J^T J + lambda I, J^T r
+    // Marginal covariances (SparseCholeskySolver::compute_covariance_matrix + extract_variable_covariances,
+    // cholesky.rs:240-256, core/problem.rs:1128-1147): the 6 x 6 diagonal blocks of the inverse of the matrix the LAST
+    // solve_augmented factorised -- J^T J + lambda I at that solve's point and lambda, in the scaled variables when Jacobi
+    // scaling was on (what get_hessian(lambda) returns at the same point) -- by selected inversion of the tile factor
+    // (TilePlan::covariance_blocks).  out[n_v][6][6], caller's vertex order, columns as get_hessian's.  kInvalidState when
+    // no valid factor is held (no solve yet, or an export / assembly since).
+    int covariance(double* out);
+    void enable_covariance_timing(bool on) { tp_.enable_covariance_timing(on); }
 
     void enable_graphs(bool on) { tp_.enable_graphs(on); }
     void enable_overlap(bool on) { tp_.enable_overlap(on); }

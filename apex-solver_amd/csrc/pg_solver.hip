@@ -301,6 +301,7 @@ int PoseGraphSolver::solve_augmented(double lambda, int variant, double* step_ou
         }
         if (!tp_.sweep_timed_out()) {
             if (eager_eval_) eager_serial_ = step_serial_;   // (the answers of THIS solve)
+            tp_.set_factor_valid(true);   // (pivots read, sweeps done: covariance() may invert this factor)
             return kOk;
         }
         // a dataflow sweep of this solve gave up (chol_kernels.hip, flow_wait): repeat it level by level (Solver::solve_augmented)
@@ -523,6 +524,19 @@ int PoseGraphSolver::get_hessian(double lambda, double* H_out, double* g_out) {
                     }
             }
     }
+    return kOk;
+}
+
+int PoseGraphSolver::covariance(double* out) {
+    if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
+    if (!out) return fail(kInvalidInput, "cov_out is NULL");
+    HIP_TRY(hipSetDevice(device_));
+    std::vector<int64_t> pos(n_v_);
+    for (int64_t v = 0; v < n_v_; ++v) pos[v] = 6 * (int64_t)vmap_[v];
+    std::string err;
+    const int rc = tp_.covariance_blocks(pos.data(), n_v_, 6, out, &err);
+    if (rc == 1) return fail(kInvalidState, "covariance: " + err);
+    if (rc != 0) return fail(kDeviceError, "covariance: " + err);
     return kOk;
 }
 

@@ -796,6 +796,7 @@ int Solver::pcg_solve() {
 // Sharded: g_red, g_c and the diagonal blocks are all-reduced once, every S p once per iteration.
 // ---------------------------------------------------------------------------------------------
 int Solver::assemble_implicit(double lambda) {
+    tp_.set_factor_valid(false);   // (the camera reduction adds to the diagonal tiles)
     const BAView v = view(cur_);
     stage_begin(kStAssembleLm);
     HIP_TRY(hipMemsetAsync(flags_, 0, 4 * sizeof(int), stream_));
@@ -903,6 +904,7 @@ int Solver::solve_augmented(double lambda, int variant, double* step_out, double
     last_pcg_iters_ = 0;   // (the PCG variants set it: apexgpu_info[5] is about THIS solve)
     ++step_serial_;
     last_lambda_ = lambda;
+    tp_.set_factor_valid(false);   // (every variant writes the tiles or leaves them stale for this point)
     int pcg_max = cg_max_iter_;
     double pcg_tol = cg_tol_;
     if (auto_fallback_ && variant != 2) {   // set_structure selected the matrix-free variant for this handle (set_auto_variant)
@@ -978,6 +980,8 @@ int Solver::solve_augmented(double lambda, int variant, double* step_out, double
         }
         if (rc != kOk || variant != 0 || !tp_.sweep_timed_out()) {
             if (rc == kOk && eager) eager_serial_ = step_serial_;   // (the answers of THIS solve: step_stats / eval_step)
+            // (pivots read, sweeps done: camera_covariance() may invert this factor -- single rank, direct variant only)
+            if (rc == kOk && variant == 0 && world_ == 1 && !tp_.distributed()) tp_.set_factor_valid(true);
             return rc;
         }
         // A dataflow sweep of THIS solve ran into its spin limit (chol_kernels.hip, flow_wait): dcam_ is wrong.  The factor is
@@ -1579,5 +1583,31 @@ int Solver::get_landmark_blocks(double* hinv_out, double* gl_out) {
     return kOk;
 }
 
+
+int Solver::camera_covariance(double* out) {
+    if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
+    if (!out) return fail(kInvalidInput, "cov_out is NULL");
+    if (world_ > 1 || tp_.distributed()) return fail(kInvalidState, "covariance: multi-rank handles are not supported (single rank only)");
+    if (matrix_free_only_)
+        return fail(kInvalidState, auto_fallback_ ? "covariance: the automatic variant selection chose the matrix-free PCG for this handle: there is no factor to invert"
+                                                  : "covariance: this handle was built matrix-free only: there is no factor to invert");
+    HIP_TRY(hipSetDevice(device_));
+    std::vector<int64_t> pos(n_cam_);
+    for (int64_t c = 0; c < n_cam_; ++c) pos[c] = (int64_t)cmap_[c] * dc_;
+    std::vector<double> blk((size_t)n_cam_ * dc_ * dc_);
+    std::string err;
+    const int rc = tp_.covariance_blocks(pos.data(), n_cam_, dc_, blk.data(), &err);
+    if (rc == 1) return fail(kInvalidState, "covariance: " + err + " (the Iterative and matrix-free variants have no factor)");
+    if (rc != 0) return fail(kDeviceError, "covariance: " + err);
+    for (int64_t c = 0; c < n_cam_; ++c) {
+        double* o = out + (size_t)c * 81;
+        std::fill(o, o + 81, 0.0);
+        for (int a = 0; a < dc_; ++a)
+            for (int b = 0; b < dc_; ++b) o[a * 9 + b] = blk[((size_t)c * dc_ + a) * dc_ + b];
+        if (dc_ == 6)   // get_schur's intrinsics rows: lambda on the diagonal, no cross terms
+            for (int a = 6; a < 9; ++a) o[a * 9 + a] = 1.0 / last_lambda_;
+    }
+    return kOk;
+}
 
 }  // namespace apex

@@ -187,6 +187,27 @@ class TilePlan {
     // Jacobi-PCG on the UNFACTORED tiles; work: 6*n_pad doubles; syncs once per iteration
     hipError_t pcg(const double* rhs, double* x, double* work, int max_iter, double tol, int* iters);
 
+    // ---- marginal covariances: selected inversion of the factor (block Takahashi recurrence) ----
+    // The tiles hold a valid factor L only between a successful single-rank factorisation + sweeps (the CALLER says so with
+    // set_factor_valid(true) once it has read the pivot flags) and the next write of the tiles: zero_tiles, add_diag,
+    // scale_sym, factor, a new build() clear the flag.
+    void set_factor_valid(bool on) { factor_valid_ = on; }
+    bool factor_valid() const { return factor_valid_; }
+    // Z = (L L^T)^-1 on the tile pattern of L, root group first; with j's off-diagonal rows I_j and Y_r = L_rj Linv_j:
+    //     Z_rj = - sum_{s in I_j} Z~_rs Y_s    (r in I_j; Z~_rs = Z_rs for r >= s, else Z_sr^T)
+    //     Z_jj = Linv_j^T Linv_j - sum_{r in I_j} Y_r^T Z_rj
+    // then out[v] = the d x d diagonal block of Z at n_pad position pos[v] (symmetrised).  L is left as it is.  The Z tiles
+    // (as many as L's), the Y tiles of the largest level group and the lists are allocated on the first call only and live
+    // until release().  Returns 0, 1 (refused: distributed plan or no valid factor; *err says why) or 2 (HIP error).  Syncs.
+    int covariance_blocks(const int64_t* pos, int64_t n_var, int d, double* out, std::string* err);
+    size_t covariance_bytes() const { return sinv_bytes_; }   // device memory the first covariance_blocks() added (0 before)
+    // per level group (execution order, root group first): milliseconds of its three launches in the last covariance_blocks()
+    // -- recorded only while enabled (events between the groups)
+    void enable_covariance_timing(bool on) { sinv_timing_ = on; }
+    const std::vector<double>& covariance_group_ms() const { return sinv_group_ms_; }
+    // tile products of one selected inversion: Y, off-diagonal Z, diagonal Z (each 2*144^3 flop)
+    void covariance_op_counts(int64_t* y, int64_t* zoff, int64_t* zdiag) const { *y = sinv_n_[0]; *zoff = sinv_n_[1]; *zdiag = sinv_n_[2]; }
+
    private:
     using Cols = std::vector<std::vector<int>>;
     // The level groups in execution order: this rank's columns level by level, then the shared top columns level by level
@@ -314,6 +335,19 @@ class TilePlan {
     // level lists, kFlowFirstWriter in the dataflow units -- and does not read its target (beta = 0): the 0.63 GB of fill tiles
     // of final-13682 are then neither cleared before a factorisation nor read by those updates (round 5).
     bool first_ok_ = false;   // (this plan qualifies: not distributed, has fill tiles, no dataflow launch over shared top groups)
+    // selected inversion (covariance_blocks): built on the first call
+    std::string sinv_setup();
+    void sinv_release();
+    bool factor_valid_ = false;
+    double *z_ = nullptr, *y_ = nullptr;
+    SinvTask* sinv_tasks_ = nullptr;
+    SinvProd* sinv_prods_ = nullptr;
+    struct SinvGroup { int task[4]; };   // [task[k], task[k + 1]): the Y, off-diagonal Z, diagonal Z launches of one level group
+    std::vector<SinvGroup> sinv_groups_;   // root group first
+    int64_t sinv_n_[3] = {0, 0, 0};
+    size_t sinv_bytes_ = 0;
+    bool sinv_timing_ = false;
+    std::vector<double> sinv_group_ms_;
     static constexpr int kTriInline = 8;       // (swept 0 / 4 / 8 / 16 / 32 / all: profiles/r05_sweep_tri_inline.txt) the dataflow sweeps: in levels of at most this many columns a block's solve task forms its last-arriving product itself (FlowTask::mat2)
     bool use_graphs_ = true;
 };

@@ -101,6 +101,7 @@ std::vector<int> TilePlan::order(int nt, const std::vector<uint8_t>& adjm, bool 
 }
 
 void TilePlan::release() {
+    sinv_release();
     void* ptrs[] = {tiles_, linv_, slot_, diag_slot_, flag_, potrf_tasks_, trsm_tasks_, upd_tasks_, tri_fwd_, tri_bwd_,
                     flow_fwd_, flow_bwd_, flow_part_, flow_flags_, flow_units_, flow_ver_, flow_trace_, sym_tiles_, sym_row_ptr_, sym_entries_, sym_part_, row_dot_, blk_part_, scal_, cls_, exch_, gate_cnt_};
     for (void* p : ptrs)
@@ -923,6 +924,7 @@ std::string TilePlan::upload(const Lists& lists) {
 #undef TP_TRY
 
 hipError_t TilePlan::zero_tiles(bool own_touched_only, bool skip_fill) {
+    factor_valid_ = false;
     const size_t te = (size_t)kNB * kNB * sizeof(double);
     hipError_t e = hipSuccess;
     auto clear = [&](int64_t first, int64_t count) {
@@ -944,10 +946,11 @@ hipError_t TilePlan::zero_tiles(bool own_touched_only, bool skip_fill) {
 }
 
 void TilePlan::add_diag(int n_valid, double add_valid, double pad_value) {
+    factor_valid_ = false;
     launch_tile_add_diag(tiles_, diag_slot_, n_valid, (int)n_pad(), add_valid, pad_value, stream_);
 }
 
-void TilePlan::scale_sym(const double* scale) { launch_tile_scale_sym(sym_tiles_, n_sym_tiles_, tiles_, scale, stream_); }
+void TilePlan::scale_sym(const double* scale) { factor_valid_ = false; launch_tile_scale_sym(sym_tiles_, n_sym_tiles_, tiles_, scale, stream_); }
 
 void TilePlan::diag(double* out) const { launch_tile_diag(tiles_, diag_slot_, nt_, out, stream_); }
 
@@ -1304,6 +1307,7 @@ void TilePlan::top_slot_ranges(std::pair<int64_t, int64_t> out[2]) const {
 }
 
 void TilePlan::factor_phase(int phase) {
+    factor_valid_ = false;
     if (phase == 0) { if (!run_graph(kGraphFactor, nullptr, nullptr, nullptr)) enqueue_factor(0, n_local_groups_); }
     else if (!run_graph(kGraphFactorTop, nullptr, nullptr, nullptr)) enqueue_factor(n_local_groups_, n_levels_);
 }
@@ -1313,6 +1317,7 @@ void TilePlan::solve_phase(int phase, const double* rhs, double* x, double* work
 }
 
 hipError_t TilePlan::factor(int* failed_at, bool defer_flags) {
+    factor_valid_ = false;
     if (distributed()) {
         if (!comm_.sum || !comm_.max_int) return hipErrorNotInitialized;  // a distributed plan needs its communicator
         factor_phase(0);
@@ -1419,6 +1424,7 @@ void TilePlan::sym_matvec(const double* x, double* y) {
 // also made on the device (k_pcg_close_iteration): the speculative iteration behind a met test changes nothing, and x, the
 // iteration count and every scalar are those of the loop that waited every time.
 hipError_t TilePlan::pcg(const double* rhs, double* x, double* work, int max_iter, double tol, int* iters) {
+    factor_valid_ = false;
     const int n = (int)n_pad();
     double *dg = work, *pre = work + n, *r = work + 2 * (size_t)n, *z = work + 3 * (size_t)n, *p = work + 4 * (size_t)n,
            *ap = work + 5 * (size_t)n;
@@ -1457,6 +1463,164 @@ hipError_t TilePlan::pcg(const double* rhs, double* x, double* work, int max_ite
     }
     *iters = it;
     return hipStreamSynchronize(stream_);   // (the speculative iteration, if any, has drained: x is final)
+}
+
+// ---- selected inversion (tile_plan.h, covariance_blocks) ----------------------------------------------------------------
+void TilePlan::sinv_release() {
+    void* ptrs[] = {z_, y_, sinv_tasks_, sinv_prods_};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    z_ = y_ = nullptr; sinv_tasks_ = nullptr; sinv_prods_ = nullptr;
+    sinv_groups_.clear(); sinv_group_ms_.clear();
+    sinv_n_[0] = sinv_n_[1] = sinv_n_[2] = 0;
+    sinv_bytes_ = 0;
+    factor_valid_ = false;
+}
+
+// The lists of the recurrence from the slot map and the level groups of the factorisation (nothing of the step path changes):
+// per group, root group first, three task lists -- Y_r = L_rj Linv_j, the off-diagonal Z_rj, the diagonal Z_jj -- whose
+// products point into L, Linv, Z and the group's Y tiles.  The columns of a group are independent: I_j holds ancestors of j
+// only, and those sit in higher groups, whose Z is complete when the group runs.
+std::string TilePlan::sinv_setup() {
+    Cols col_rows(nt_);
+    for (int K = 0; K < nt_; ++K)
+        for (int I = K + 1; I < nt_; ++I)
+            if (slot(I, K) >= 0) col_rows[K].push_back(I);
+    // Z~_rs for r, s in I_j must be a tile of L: tile-level symbolic fill makes I_j a clique (the rows of column j merge into
+    // its parent's column, and so on up the tree) -- checked, not assumed
+    for (int K = 0; K < nt_; ++K) {
+        const auto& rows = col_rows[K];
+        for (size_t a = 0; a < rows.size(); ++a)
+            for (size_t b = 0; b < a; ++b)
+                if (slot(rows[a], rows[b]) < 0)
+                    return "tile (" + std::to_string(rows[a]) + ", " + std::to_string(rows[b]) + ") of column " + std::to_string(K) +
+                           "'s rows is not a tile of the factor: the tile structure is not closed under fill";
+    }
+    const Groups g = level_groups(col_rows);
+    int64_t y_max = 0;
+    for (const auto& cols : g.cols) {
+        int64_t ny = 0;
+        for (int K : cols) ny += (int64_t)col_rows[K].size();
+        y_max = std::max(y_max, ny);
+    }
+    const size_t te = (size_t)kNB * kNB;
+    const size_t need = ((size_t)n_slots_ + (size_t)std::max<int64_t>(y_max, 1)) * te * sizeof(double);
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    if ((double)need > 0.9 * (double)free_b)
+        return "the covariance tiles need " + std::to_string(need / 1e9) + " GB; only " + std::to_string(free_b / 1e9) + " GB free";
+    std::vector<SinvTask> tasks;
+    std::vector<SinvProd> prods;
+    // (the lists point at the final addresses of Z and Y: allocate first)
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&z_), (size_t)n_slots_ * te * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&y_), (size_t)std::max<int64_t>(y_max, 1) * te * sizeof(double));
+    if (e != hipSuccess) { sinv_release(); return std::string("HIP error allocating the covariance tiles: ") + hipGetErrorString(e); }
+    auto Lt = [&](int I, int J) { return tile_at(tiles_, slot(I, J)); };
+    auto Zt = [&](int I, int J) { return tile_at(z_, slot(I, J)); };
+    sinv_groups_.clear();
+    for (int gi = (int)g.cols.size() - 1; gi >= 0; --gi) {
+        const auto& cols = g.cols[gi];
+        SinvGroup sg;
+        std::vector<int64_t> ybase(cols.size());
+        int64_t ny = 0;
+        for (size_t c = 0; c < cols.size(); ++c) { ybase[c] = ny; ny += (int64_t)col_rows[cols[c]].size(); }
+        auto Yt = [&](size_t c, size_t a) { return tile_at(y_, ybase[c] + (int64_t)a); };
+        sg.task[0] = (int)tasks.size();
+        for (size_t c = 0; c < cols.size(); ++c) {   // Y_r = L_rj Linv_j
+            const int j = cols[c];
+            for (size_t a = 0; a < col_rows[j].size(); ++a) {
+                tasks.push_back({Yt(c, a), (int)prods.size(), 1});
+                prods.push_back({Lt(col_rows[j][a], j), tile_at(linv_, j), 0, 0});
+            }
+        }
+        sg.task[1] = (int)tasks.size();
+        for (size_t c = 0; c < cols.size(); ++c) {   // Z_rj = - sum_s Z~_rs Y_s
+            const int j = cols[c];
+            const auto& rows = col_rows[j];
+            for (size_t a = 0; a < rows.size(); ++a) {
+                const int r = rows[a];
+                tasks.push_back({Zt(r, j), (int)prods.size(), (int)rows.size()});
+                for (size_t b = 0; b < rows.size(); ++b) {
+                    const int s = rows[b];
+                    if (r >= s) prods.push_back({Zt(r, s), Yt(c, b), kSinvNeg, 0});
+                    else prods.push_back({Zt(s, r), Yt(c, b), kSinvNeg | kSinvTransA, 0});
+                }
+            }
+        }
+        sg.task[2] = (int)tasks.size();
+        for (size_t c = 0; c < cols.size(); ++c) {   // Z_jj = Linv_j^T Linv_j - sum_r Y_r^T Z_rj
+            const int j = cols[c];
+            const auto& rows = col_rows[j];
+            tasks.push_back({Zt(j, j), (int)prods.size(), 1 + (int)rows.size()});
+            prods.push_back({tile_at(linv_, j), tile_at(linv_, j), kSinvTransA, 0});
+            for (size_t a = 0; a < rows.size(); ++a) prods.push_back({Yt(c, a), Zt(rows[a], j), kSinvNeg | kSinvTransA, 0});
+        }
+        sg.task[3] = (int)tasks.size();
+        sinv_n_[0] += sg.task[1] - sg.task[0];
+        sinv_groups_.push_back(sg);
+    }
+    sinv_n_[1] = sinv_n_[2] = 0;
+    for (const SinvGroup& sg : sinv_groups_) {
+        for (int t = sg.task[1]; t < sg.task[2]; ++t) sinv_n_[1] += tasks[t].count;
+        for (int t = sg.task[2]; t < sg.task[3]; ++t) sinv_n_[2] += tasks[t].count;
+    }
+    e = upload_vec(&sinv_tasks_, tasks);
+    if (e == hipSuccess) e = upload_vec(&sinv_prods_, prods);
+    if (e != hipSuccess) { sinv_release(); return std::string("HIP error uploading the covariance lists: ") + hipGetErrorString(e); }
+    sinv_bytes_ = ((size_t)n_slots_ + (size_t)std::max<int64_t>(y_max, 1)) * te * sizeof(double) + tasks.size() * sizeof(SinvTask) +
+                  prods.size() * sizeof(SinvProd);
+    return "";
+}
+
+int TilePlan::covariance_blocks(const int64_t* pos, int64_t n_var, int d, double* out, std::string* err) {
+    if (distributed() || part_world_ > 1) { *err = "covariances of a distributed plan are not supported (single rank only)"; return 1; }
+    if (!factor_valid_ || !tiles_) {
+        *err = "the tiles hold no valid factor: covariances need a successful direct (Cholesky) solve, and nothing may re-assemble the tiles in between";
+        return 1;
+    }
+    for (int64_t v = 0; v < n_var; ++v)
+        if (pos[v] < 0 || pos[v] + d > n_pad() || pos[v] / kNB != (pos[v] + d - 1) / kNB) { *err = "variable block outside one diagonal tile"; return 1; }
+    if (!z_) {
+        const std::string e = sinv_setup();
+        if (!e.empty()) { *err = e; return 2; }
+    }
+    auto hip_fail = [&](hipError_t e, const char* what) { *err = std::string("HIP error in ") + what + ": " + hipGetErrorString(e); return 2; };
+    std::vector<hipEvent_t> ev;
+    if (sinv_timing_) {
+        ev.resize(sinv_groups_.size() + 1, nullptr);
+        for (hipEvent_t& x : ev) { const hipError_t e = hipEventCreate(&x); if (e != hipSuccess) return hip_fail(e, "hipEventCreate"); }
+        (void)hipEventRecord(ev[0], stream_);
+    }
+    for (size_t gi = 0; gi < sinv_groups_.size(); ++gi) {
+        const SinvGroup& sg = sinv_groups_[gi];
+        for (int k = 0; k < 3; ++k) launch_sinv_gemm(sinv_tasks_ + sg.task[k], sg.task[k + 1] - sg.task[k], sinv_prods_, stream_);
+        if (sinv_timing_) (void)hipEventRecord(ev[gi + 1], stream_);
+    }
+    int64_t* dpos = nullptr;
+    double* dout = nullptr;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dpos), (size_t)std::max<int64_t>(n_var, 1) * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), (size_t)std::max<int64_t>(n_var * d * d, 1) * sizeof(double));
+    if (e == hipSuccess && n_var > 0) e = hipMemcpyAsync(dpos, pos, (size_t)n_var * sizeof(int64_t), hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess) {
+        launch_sinv_diag_blocks(z_, diag_slot_, dpos, n_var, d, dout, stream_);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && n_var > 0) e = hipMemcpyAsync(out, dout, (size_t)n_var * d * d * sizeof(double), hipMemcpyDeviceToHost, stream_);
+    const hipError_t se = hipStreamSynchronize(stream_);
+    if (e == hipSuccess) e = se;
+    if (dpos) (void)hipFree(dpos);
+    if (dout) (void)hipFree(dout);
+    if (sinv_timing_) {
+        sinv_group_ms_.assign(sinv_groups_.size(), 0.0);
+        for (size_t gi = 0; gi < sinv_groups_.size(); ++gi) {
+            float ms = 0.0f;
+            if (e == hipSuccess && hipEventElapsedTime(&ms, ev[gi], ev[gi + 1]) == hipSuccess) sinv_group_ms_[gi] = ms;
+        }
+        for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+    }
+    if (e != hipSuccess) return hip_fail(e, "covariance_blocks");
+    return 0;
 }
 
 }  // namespace apex

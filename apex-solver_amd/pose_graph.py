@@ -319,6 +319,27 @@ class GpuSparseCholeskySolver:
         h.check(h.L.apexgpu_pg_get_hessian(h.h, float(lam), capi.ptr(H), capi.ptr(g)))
         return H, g
 
+    def pose_covariance_blocks(self) -> np.ndarray:
+        """(n_v, 6, 6): the diagonal blocks of the inverse of the matrix the last solve factorised (J^T J + lambda I at its
+        point and lambda; scaled variables under Jacobi scaling -- what get_hessian(lambda) returns there), by selected
+        inversion of the tile factor.  Caller's vertex order.  Raises LinAlgError (InvalidState) when no factor is held
+        (no solve yet, or an assembly / export since)."""
+        h = self._need()
+        out = np.zeros((h.n_vertices, 6, 6))
+        h.check(h.L.apexgpu_pg_covariance(h.h, capi.ptr(out)))
+        return out
+
+    def compute_covariances(self) -> dict:
+        """LinearSolver::compute_covariance_matrix + Problem::extract_variable_covariances (src/linalg/mod.rs:165-215,
+        src/core/problem.rs:1128-1147): {"x{id}": 6 x 6} for every vertex."""
+        blocks = self.pose_covariance_blocks()
+        return {f"x{int(i)}": blocks[k].copy() for k, i in enumerate(self.problem.data.ids)}
+
+    def covariance_stats(self, group_cap: int = 0) -> dict:
+        from .solver import _covariance_stats
+        h = self._need()
+        return _covariance_stats(h, h.L.apexgpu_pg_covariance_stats, group_cap)
+
     def info(self) -> dict:
         h = self._need()
         a = (C.c_double * 8)()

@@ -111,6 +111,8 @@ class LevenbergMarquardtConfig:
     schur_variant: SchurVariant = SchurVariant.Sparse
     schur_preconditioner: SchurPreconditioner = SchurPreconditioner.None_
     use_jacobi_scaling: bool = False  # :352
+    # :287-294, 479-486: marginal covariances of the last factorised system into SolverResult.covariances after the loop
+    compute_covariances: bool = False
 
     @classmethod
     def new(cls) -> "LevenbergMarquardtConfig":
@@ -135,6 +137,7 @@ class LevenbergMarquardtConfig:
     def with_schur_variant(self, v): return replace(self, schur_variant=v)
     def with_schur_preconditioner(self, v): return replace(self, schur_preconditioner=v)
     def with_jacobi_scaling(self, on): return replace(self, use_jacobi_scaling=bool(on))  # :474-477
+    def with_compute_covariances(self, on): return replace(self, compute_covariances=bool(on))  # :479-486
 
     def to_c(self) -> capi.LmConfigC:
         return capi.LmConfigC(
@@ -414,6 +417,26 @@ class GpuSchurComplementSolver:
         h.check(h.L.apexgpu_get_hessian_csc(h.h, C.byref(nnz), capi.ptr(colptr), capi.ptr(rowidx), capi.ptr(vals)))
         return sp.csc_matrix((vals, rowidx, colptr), shape=(n, n))
 
+    def camera_covariance_blocks(self) -> np.ndarray:
+        """(n_cam, 9, 9): the camera blocks of (H + lambda I)^-1 = the diagonal blocks of S^-1 for the S the last direct
+        solve factorised (its point, lambda, Jacobi scaling and ladder regularisation), caller's camera order, pose 6 then
+        intrinsics 3.  BundleAdjustment mode: intrinsics 1 / lambda on the diagonal (get_schur's rows).  Raises
+        LinAlgError (InvalidState) when no factor is held: no Sparse-variant solve yet, an Iterative / matrix-free solve,
+        an export since, a sharded handle."""
+        h = self._need()
+        out = np.zeros((h.n_cam, 9, 9))
+        h.check(h.L.apexgpu_camera_covariance(h.h, capi.ptr(out)))
+        return out
+
+    def compute_covariances(self) -> dict:
+        """{"pose_{i:04}": 6 x 6, "intr_{i:04}": 3 x 3} per camera (landmarks are not computed).  The reference's Schur
+        solvers return None here; this is a superset."""
+        return camera_covariance_dict(self.camera_covariance_blocks())
+
+    def covariance_stats(self, group_cap: int = 0) -> dict:
+        h = self._need()
+        return _covariance_stats(h, h.L.apexgpu_covariance_stats, group_cap)
+
     def get_landmark_blocks(self):
         h = self._need()
         hi = np.zeros((h.n_pt, 3, 3)); gl = np.zeros((h.n_pt, 3))
@@ -521,6 +544,36 @@ class GpuSchurComplementSolver:
             self._h = None
 
 
+def camera_covariance_dict(blocks: np.ndarray) -> dict:
+    """(n_cam, 9, 9) camera blocks -> {"pose_{i:04}": 6 x 6, "intr_{i:04}": 3 x 3}."""
+    out = {}
+    for i, b in enumerate(blocks):
+        out[f"pose_{i:04}"] = b[:6, :6].copy()
+        out[f"intr_{i:04}"] = b[6:, 6:].copy()
+    return out
+
+
+def _covariance_stats(h, fn, group_cap: int) -> dict:
+    out = (C.c_double * 6)()
+    ms = np.zeros(max(int(group_cap), 1))
+    h.check(fn(h.h, C.byref(out), capi.ptr(ms), int(group_cap)))
+    return dict(extra_bytes=int(out[0]), y_products=int(out[1]), zoff_products=int(out[2]), zdiag_products=int(out[3]),
+                level_groups=int(out[4]), group_ms=ms[:int(out[5])].tolist())
+
+
+def _covariances_or_none(s):
+    """compute_covariance_matrix returning None (linalg/mod.rs:165-172): a solve without a factor (Iterative, matrix-free,
+    a handle the automatic variant selection made matrix-free) has no covariances -- None and a warning, not an error."""
+    import warnings
+    try:
+        return s.compute_covariances()
+    except capi.LinAlgError as e:
+        if e.code != -6:
+            raise
+        warnings.warn(f"covariances not computed: {e}", RuntimeWarning, stacklevel=3)
+        return None
+
+
 @dataclass
 class SolverResult:
     """src/optimizer/mod.rs:250-273 (BA subset)."""
@@ -539,6 +592,7 @@ class SolverResult:
     unsuccessful_steps: int
     history: np.ndarray  # per iteration: cost, damping, rho, accepted, |g|, |step|, predicted, trial cost
     final_damping: float = 0.0
+    covariances: dict | None = None  # mod.rs:265-272: per variable, when config.compute_covariances
 
 
 class LevenbergMarquardt:
@@ -568,13 +622,14 @@ class LevenbergMarquardt:
             s.set_parameters(problem.data.poses if initial_values is None else initial_values)
             self.linear_solver = s
             res, hist, c = s.lm_optimize(self.config)
+            cov = _covariances_or_none(s) if self.config.compute_covariances else None
             return SolverResult(
                 status=OptimizationStatus(res.status), iterations=res.iterations, initial_cost=res.initial_cost,
                 final_cost=res.final_cost, parameters=(s.get_parameters(),), elapsed_time=res.elapsed_s,
                 final_gradient_norm=res.final_gradient_norm, final_parameter_update_norm=res.final_step_norm,
                 cost_evaluations=res.cost_evaluations, jacobian_evaluations=res.jacobian_evaluations,
                 successful_steps=res.successful_steps, unsuccessful_steps=res.unsuccessful_steps, history=hist,
-                final_damping=c.damping)
+                final_damping=c.damping, covariances=cov)
         if t not in (LinearSolverType.GpuSchurComplement, LinearSolverType.SparseSchurComplement):
             raise NotImplementedError(f"{t} is a CPU solver of the reference; this backend provides GpuSchurComplement")
         d = problem.data
@@ -589,10 +644,11 @@ class LevenbergMarquardt:
         s.set_parameters(poses, intr, pts)
         self.linear_solver = s
         res, hist, c = s.lm_optimize(self.config)
+        cov = _covariances_or_none(s) if self.config.compute_covariances else None
         return SolverResult(
             status=OptimizationStatus(res.status), iterations=res.iterations, initial_cost=res.initial_cost,
             final_cost=res.final_cost, parameters=s.get_parameters(), elapsed_time=res.elapsed_s,
             final_gradient_norm=res.final_gradient_norm, final_parameter_update_norm=res.final_step_norm,
             cost_evaluations=res.cost_evaluations, jacobian_evaluations=res.jacobian_evaluations,
             successful_steps=res.successful_steps, unsuccessful_steps=res.unsuccessful_steps, history=hist,
-            final_damping=c.damping)
+            final_damping=c.damping, covariances=cov)

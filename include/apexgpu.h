@@ -201,6 +201,19 @@ int apexgpu_get_jacobian_blocks(apexgpu_solver* h, double* jc_out, double* jl_ou
 /* dense S ((9 n_cam)^2 row-major, symmetric) and g_red (9 n_cam) in the reference's camera-side
  * column order, for the last lambda; either may be NULL */
 int apexgpu_get_schur(apexgpu_solver* h, double* S_out, double* gred_out);
+/* Marginal camera covariances (LevenbergMarquardtConfig::with_compute_covariances): the 9 x 9 camera blocks of the inverse
+ * of the matrix the LAST apexgpu_solve_augmented factorised -- (H + lambda I)^-1 by the Schur-complement identity, at that
+ * solve's point, lambda and Jacobi scaling, plus its ladder regularisation if any (apexgpu_info[4]) -- from the tile factor
+ * by selected inversion.  cov_out[n_cam][9][9], caller's camera order, pose 6 then intrinsics 3 (apexgpu_get_schur's
+ * layout); BundleAdjustment mode (d_c = 6): intrinsics 1 / lambda on the diagonal, no cross terms.  Landmarks: not
+ * computed.  APEXGPU_ERR_INVALID_STATE (last_error says why): no direct (variant 0) solve since the last assembly or
+ * export, a PCG / matrix-free handle or solve, a sharded handle. */
+int apexgpu_camera_covariance(apexgpu_solver* h, double* cov_out /* n_cam*81 */);
+/* What the selected inversion behind apexgpu_camera_covariance costs: out[0] device bytes it added (allocated by the first
+ * call, 0 before), out[1..3] tile products per call (Y, off-diagonal Z, diagonal Z; 2 * 144^3 flop each), out[4] level
+ * groups; with the option "covariance_timing" on, group_ms[i] (i < group_cap) = milliseconds of level group i's launches in
+ * the last call, root group first, and out[5] = how many were written.  Any pointer but out may be NULL. */
+int apexgpu_covariance_stats(apexgpu_solver* h, double out[6], double* group_ms, int group_cap);
 int apexgpu_get_landmark_blocks(apexgpu_solver* h, double* hinv_out /* n_pt*9 */, double* gl_out /* n_pt*3 */);
 /* Parity probe of row A9: invert_landmark_blocks_with_lambda(.., 0.0) (explicit_schur.rs:365-442) -- the eigenvalue gate
  * (min_ev < 1e-12 -> + (1e-6 + max_ev 1e-6) I; max_ev / min_ev > 1e10 -> + max_ev 1e-6 I; else plain inverse) exactly as
@@ -511,6 +524,13 @@ int apexgpu_pg_lm_optimize(apexgpu_pg_solver* h, apexgpu_lm_config* cfg, apexgpu
 int apexgpu_pg_get_residual(apexgpu_pg_solver* h, double* r_out);
 int apexgpu_pg_get_jacobian_blocks(apexgpu_pg_solver* h, double* j_out);
 int apexgpu_pg_get_hessian(apexgpu_pg_solver* h, double lambda, double* H_out, double* g_out);
+/* Marginal covariances of the vertices (SparseCholeskySolver::compute_covariance_matrix + extract_variable_covariances):
+ * the 6 x 6 diagonal blocks of the inverse of the matrix the LAST apexgpu_pg_solve_augmented factorised (J^T J + lambda I at
+ * that point and lambda, scaled variables under Jacobi scaling: what apexgpu_pg_get_hessian(lambda) returns there), from the
+ * tile factor by selected inversion.  cov_out[n_v][6][6], caller's vertex order, columns as apexgpu_pg_get_hessian's.
+ * APEXGPU_ERR_INVALID_STATE: no valid factor (no solve yet, or an assembly / export since). */
+int apexgpu_pg_covariance(apexgpu_pg_solver* h, double* cov_out /* n_v*36 */);
+int apexgpu_pg_covariance_stats(apexgpu_pg_solver* h, double out[6], double* group_ms, int group_cap);   /* as apexgpu_covariance_stats */
 
 /* name: "graphs" (hipGraph replay of factor / solves), "update_overlap" (second stream for trailing updates),
  * "tri_dataflow" (triangular sweeps as one dataflow launch each), "nested_dissection" (0 off, 1 on, > 1 leaf size; before apexgpu_pg_set_structure) */
