@@ -24,7 +24,7 @@ SYMBOLS = (
     "apexgpu_set_cg_params", "apexgpu_set_params", "apexgpu_get_params", "apexgpu_cost", "apexgpu_assemble", "apexgpu_solve_augmented",
     "apexgpu_step_stats", "apexgpu_eval_step", "apexgpu_commit_step", "apexgpu_discard_step",
     "apexgpu_parameter_norm", "apexgpu_column_norms", "apexgpu_set_column_scaling", "apexgpu_lm_optimize", "apexgpu_get_residual", "apexgpu_get_jacobian_blocks",
-    "apexgpu_get_schur", "apexgpu_camera_covariance", "apexgpu_covariance_stats", "apexgpu_get_landmark_blocks", "apexgpu_get_hessian_csc", "apexgpu_debug_invert_blocks", "apexgpu_debug_pair_lists", "apexgpu_debug_pair_lists_queued", "apexgpu_debug_pair_lists_queued_dc", "apexgpu_debug_host_structure", "apexgpu_setup_times", "apexgpu_schur_matvec", "apexgpu_set_option", "apexgpu_enable_stage_timing", "apexgpu_reset_stage_times",
+    "apexgpu_get_schur", "apexgpu_camera_covariance", "apexgpu_covariance_stats", "apexgpu_landmark_covariance", "apexgpu_landmark_covariance_stats", "apexgpu_get_landmark_blocks", "apexgpu_get_hessian_csc", "apexgpu_debug_invert_blocks", "apexgpu_debug_pair_lists", "apexgpu_debug_pair_lists_queued", "apexgpu_debug_pair_lists_queued_dc", "apexgpu_debug_host_structure", "apexgpu_setup_times", "apexgpu_schur_matvec", "apexgpu_set_option", "apexgpu_enable_stage_timing", "apexgpu_reset_stage_times",
     "apexgpu_stage_times", "apexgpu_info", "apexgpu_variant_info", "apexgpu_variant_costs", "apexgpu_trim_host_cache", "apexgpu_host_cache_bytes", "apexgpu_counters", "apexgpu_debug_get_pair_records", "apexgpu_get_unique_id", "apexgpu_comm_init", "apexgpu_comm_init_shm", "apexgpu_set_shard", "apexgpu_shard_range",
     "apexgpu_debug_lockstep_solve", "apexgpu_export_step", "apexgpu_owned_landmarks", "apexgpu_debug_partition", "apexgpu_debug_check_schedule",
     "apexgpu_bal_open", "apexgpu_bal_close", "apexgpu_bal_last_error", "apexgpu_bal_sizes", "apexgpu_bal_raw",
@@ -130,6 +130,8 @@ def load() -> C.CDLL:
     L.apexgpu_get_schur.argtypes = [vp, vp, vp]
     L.apexgpu_camera_covariance.argtypes = [vp, vp]
     L.apexgpu_covariance_stats.argtypes = [vp, C.POINTER(dbl * 6), vp, C.c_int]
+    L.apexgpu_landmark_covariance.argtypes = [vp, vp]
+    L.apexgpu_landmark_covariance_stats.argtypes = [vp, C.POINTER(dbl * 4)]
     L.apexgpu_get_landmark_blocks.argtypes = [vp, vp, vp]
     L.apexgpu_schur_matvec.argtypes = [vp, dbl, vp, vp, vp]
     L.apexgpu_set_option.argtypes = [vp, C.c_char_p, C.c_int]

@@ -112,6 +112,13 @@ void launch_dot2(int64_t n, const double* a1, const double* b1, const double* a2
 // out[k] = sum_i partial[i*nk + k] in index order (one block: reproducible)
 void launch_sum_partials(const double* partial, int n, int nk, double* out, hipStream_t s);
 void launch_debug_invert_blocks(int64_t n, const double* in, double* out, int* ok, hipStream_t s);
+// Marginal landmark covariances (cov_kernels.hip): out[l][3][3] (internal landmark order) from the landmark records, the cameras
+// of the factorised parameter set (v) and the selected inverse z of S.  small_list: landmarks with at most kLcSmallK observations
+// (8 lanes each), large_list: the others (a 64-lane workgroup each, chunks of kLcChunk observations).  err[0] := 1 if a
+// camera pair fell outside z's tile pattern.
+constexpr int kLcSmallK = 8, kLcChunk = 32;
+void launch_landmark_cov(int dc, const BAView& v, const double* hinv, const TileMap& z, const int* small_list, int n_small,
+                         const int* large_list, int n_large, double* out, int* err, hipStream_t s);
 void launch_export_linearization(int dc, const BAView& v, const int* o_orig, double* r_out, double* jc_out,
                                  double* jl_out, hipStream_t s);
 

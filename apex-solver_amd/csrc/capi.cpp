@@ -175,6 +175,13 @@ int apexgpu_get_jacobian_blocks(apexgpu_solver* h, double* jc_out, double* jl_ou
 int apexgpu_get_schur(apexgpu_solver* h, double* S_out, double* gred_out) { H_OR_FAIL; return guarded([&] { return h->s->get_schur(S_out, gred_out); }); }
 int apexgpu_camera_covariance(apexgpu_solver* h, double* cov_out) { H_OR_FAIL; return guarded([&] { return h->s->camera_covariance(cov_out); }); }
 int apexgpu_covariance_stats(apexgpu_solver* h, double out[6], double* group_ms, int group_cap) { H_OR_FAIL; return covariance_stats(h->s, out, group_ms, group_cap); }
+int apexgpu_landmark_covariance(apexgpu_solver* h, double* cov_out) { H_OR_FAIL; return guarded([&] { return h->s->landmark_covariance(cov_out); }); }
+int apexgpu_landmark_covariance_stats(apexgpu_solver* h, double out[4]) {
+    H_OR_FAIL;
+    if (!out) return APEXGPU_ERR_INVALID_INPUT;
+    h->s->landmark_covariance_stats(out);
+    return APEXGPU_OK;
+}
 int apexgpu_get_landmark_blocks(apexgpu_solver* h, double* hinv_out, double* gl_out) {
     H_OR_FAIL;
     return guarded([&] { return h->s->get_landmark_blocks(hinv_out, gl_out); });
@@ -335,7 +342,7 @@ int apexgpu_set_option(apexgpu_solver* h, const char* name, int value) {
     else if (n == "tree_sharding") h->s->set_tree_sharding(value != 0);
     else if (n == "dist_selftest") h->s->set_dist_selftest(value);
     else if (n == "nested_dissection") h->s->set_nd(value != 0, value > 1 ? value : 0);  /* value > 1: leaf size */
-    else if (n == "covariance_timing") h->s->enable_covariance_timing(value != 0);   /* per level group times of apexgpu_camera_covariance */
+    else if (n == "covariance_timing") h->s->enable_covariance_timing(value != 0);   /* per level group times of apexgpu_camera_covariance, landmark pass time */
     else return APEXGPU_ERR_INVALID_INPUT;
     return APEXGPU_OK;
 }

@@ -81,6 +81,16 @@ class Solver : public LmBackend {
     // kInvalidState: no valid factor (no direct solve yet, a PCG / matrix-free solve or an export since), several ranks.
     int camera_covariance(double* out);
     void enable_covariance_timing(bool on) { tp_.enable_covariance_timing(on); }
+    // Marginal landmark covariances: the 3 x 3 landmark blocks of the inverse of the same matrix camera_covariance describes,
+    //     Sigma_ll = V_l^-1 + sum_{i,j in obs(l)} U_i^T Z_{c(i) c(j)} U_j,   U_i = W_il V_l^-1   (Schur-complement identity)
+    // with Z = S^-1 on the factor's tile pattern (reused when a camera_covariance call computed it for this factor, else the
+    // selected inversion runs first), the landmark records and the cameras of the parameter set the factor was linearised at
+    // (factor_lin_; cov_kernels.hip).  out[n_pt][3][3], caller's landmark order, symmetric bit for bit.  kInvalidState where
+    // camera_covariance refuses, and when the factor's linearisation is gone (set_parameters or new scaling since the solve).
+    int landmark_covariance(double* out);
+    // [0] device bytes of the landmark pass, [1] observation pairs sum k (k + 1) / 2, [2] 1 if the last call recomputed Z,
+    // [3] ms of the landmark kernels alone in the last call ("covariance_timing" on, else 0)
+    void landmark_covariance_stats(double out[4]) const { out[0] = (double)lc_bytes_; out[1] = (double)lc_pairs_; out[2] = lc_recomputed_ ? 1.0 : 0.0; out[3] = lc_ms_; }
     int get_landmark_blocks(double* hinv_out, double* gl_out);
     // H = J^T J of the corrected Jacobian at the current parameters as a full symmetric CSC matrix in the global column
     // order (what SparseSchurComplementSolver::get_hessian caches, explicit_schur.rs:1146-1160, 1236-1238).  Two-call
@@ -248,6 +258,20 @@ class Solver : public LmBackend {
     int variant_cost_permille_ = 1000, variant_choice_ = 0;
     double pred_direct_ms_ = 0.0, pred_mf_ms_ = 0.0;
     std::string fallback_reason_;
+    // the parameter set (0 / 1) whose linearisation the held factor is of, -1 when it can no longer be known; and whether Jacobi
+    // scaling was on for it (the scale vectors are kept until new scaling overwrites them)
+    int factor_lin_ = -1;
+    bool factor_scaled_ = false;
+    // landmark covariance pass (landmark_covariance): built on the first call
+    int lc_setup();
+    void lc_release();
+    int *lc_lists_ = nullptr, *lc_err_ = nullptr;   // [small | large] landmark lists, error word
+    double* lc_out_ = nullptr;                      // [n_pt][9], internal order
+    int lc_n_small_ = 0, lc_n_large_ = 0;
+    int64_t lc_pairs_ = 0;
+    size_t lc_bytes_ = 0;
+    bool lc_recomputed_ = false;
+    double lc_ms_ = 0.0;
     bool orec_fresh_ = false;   // orec_ holds the records of the current parameters' last linearisation
     const double* backsub_records() const { return orec_fresh_ ? orec_ : nullptr; }   // the projection records of THIS linearisation
     double* orec_ = nullptr;   // [local observations][4] projection records written by k_landmark_reduce (pair kernel, record form)

@@ -57,6 +57,7 @@ Solver::~Solver() {
                     dcam_, hinv_, g_l_, dl_, partial_, scal_, flags_, pcg_buf_, lmu_, sd_, minv_, cam_scale_, pt_scale_, lam_mask_};
     for (void* p : ptrs)
         if (p) hipFree(p);
+    lc_release();
     comm_.reset();
     if (pcg_host_) (void)hipHostFree(pcg_host_);
     if (eager_host_) (void)hipHostFree(eager_host_);
@@ -188,6 +189,7 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
                           double huber_delta) {
     if (n_cam_ <= 0 || n_pt_ <= 0) return fail(kInvalidInput, n_cam_ <= 0 ? "No camera variables found" : "No landmark variables found");
     if (n_obs_ < 0 || n_obs_ > 2000000000LL) return fail(kInvalidInput, "observation count out of range");
+    lc_release();   // (the landmark covariance lists belong to the old structure)
     // The first stream this process creates costs 0.1-0.16 s (the runtime brings up its hardware queues; measured with
     // APEX_SETUP_TRACE in bench.py, torch's context already there), the code objects of the three kernel files a few ms more:
     // both on a thread, beside the argument checks and the camera order (host only), joined in front of the first device call
@@ -579,6 +581,7 @@ int Solver::set_params(const double* poses, const double* intr, const double* po
     launch_prepare_cams(n_cam_, poses_[cur_], intr_[cur_], camp_[cur_], mode_mask(mode_), stream_);
     HIP_TRY(hipStreamSynchronize(stream_));
     have_params_ = true; have_step_ = have_trial_ = false; orec_fresh_ = false;
+    factor_lin_ = -1;   // (the current set is overwritten: the factor's linearisation is no longer known)
     return kOk;
 }
 
@@ -981,7 +984,11 @@ int Solver::solve_augmented(double lambda, int variant, double* step_out, double
         if (rc != kOk || variant != 0 || !tp_.sweep_timed_out()) {
             if (rc == kOk && eager) eager_serial_ = step_serial_;   // (the answers of THIS solve: step_stats / eval_step)
             // (pivots read, sweeps done: camera_covariance() may invert this factor -- single rank, direct variant only)
-            if (rc == kOk && variant == 0 && world_ == 1 && !tp_.distributed()) tp_.set_factor_valid(true);
+            if (rc == kOk && variant == 0 && world_ == 1 && !tp_.distributed()) {
+                tp_.set_factor_valid(true);
+                factor_lin_ = cur_;   // (commit_step flips cur_: the factorised cameras are then in the other set)
+                factor_scaled_ = scaled_;
+            }
             return rc;
         }
         // A dataflow sweep of THIS solve ran into its spin limit (chol_kernels.hip, flow_wait): dcam_ is wrong.  The factor is
@@ -1275,6 +1282,7 @@ int Solver::set_column_scaling(const double* scaling) {
     HIP_TRY(hipSetDevice(device_));
     have_step_ = false;
     if (!scaling) { scaled_ = false; return kOk; }
+    if (factor_scaled_) factor_lin_ = -1;   // (the factor's scale vectors are overwritten below)
     int rc = ensure_scale_buffers();
     if (rc != kOk) return rc;
     cam_scale_h_.assign(n_c_, 1.0);
@@ -1303,6 +1311,7 @@ int Solver::set_jacobi_scaling(bool on) {
     if (!on) { scaled_ = false; have_step_ = false; return kOk; }
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
+    if (factor_scaled_) factor_lin_ = -1;   // (the factor's scale vectors are overwritten below)
     int rc = column_norms_sq_device();
     if (rc != kOk) return rc;
     launch_scaling_from_norms_sq(n_c_pad_, cam_scale_, cam_scale_, stream_);  // padding: n2 = 0 -> 1
@@ -1607,6 +1616,92 @@ int Solver::camera_covariance(double* out) {
         if (dc_ == 6)   // get_schur's intrinsics rows: lambda on the diagonal, no cross terms
             for (int a = 6; a < 9; ++a) o[a * 9 + a] = 1.0 / last_lambda_;
     }
+    return kOk;
+}
+
+void Solver::lc_release() {
+    void* ptrs[] = {lc_lists_, lc_err_, lc_out_};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    lc_lists_ = lc_err_ = nullptr; lc_out_ = nullptr;
+    lc_n_small_ = lc_n_large_ = 0;
+    lc_pairs_ = 0; lc_bytes_ = 0;
+}
+
+// The landmark lists of the covariance pass from the observation pointers: the landmarks with at most kLcSmallK observations
+// in the landmark-major order of the assembly (neighbours share cameras, so their Z blocks meet in L2), then the others by
+// decreasing observation count (one workgroup each, launched first: the longest start earliest).
+int Solver::lc_setup() {
+    std::vector<int> ptr(n_pt_ + 1);
+    HIP_TRY(hipMemcpy(ptr.data(), pt_ptr_, (n_pt_ + 1) * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<int> small, large;
+    int64_t pairs = 0;
+    for (int64_t l = 0; l < n_pt_; ++l) {
+        const int64_t k = ptr[l + 1] - ptr[l];
+        pairs += k * (k + 1) / 2;
+        (k <= kLcSmallK ? small : large).push_back((int)l);
+    }
+    std::stable_sort(large.begin(), large.end(), [&](int a, int b) { return ptr[a + 1] - ptr[a] > ptr[b + 1] - ptr[b]; });
+    small.insert(small.end(), large.begin(), large.end());
+    const size_t b_lists = std::max<size_t>(small.size(), 1) * sizeof(int), b_out = 9 * (size_t)n_pt_ * sizeof(double);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&lc_lists_), b_lists);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&lc_err_), sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&lc_out_), b_out);
+    if (e == hipSuccess) e = hipMemcpy(lc_lists_, small.data(), small.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { lc_release(); return check_hip(e, "landmark covariance set-up"); }
+    lc_n_large_ = (int)large.size();
+    lc_n_small_ = (int)(small.size() - large.size());
+    lc_pairs_ = pairs;
+    lc_bytes_ = b_lists + sizeof(int) + b_out;
+    return kOk;
+}
+
+int Solver::landmark_covariance(double* out) {
+    if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
+    if (!out) return fail(kInvalidInput, "cov_out is NULL");
+    if (world_ > 1 || tp_.distributed()) return fail(kInvalidState, "landmark covariance: multi-rank handles are not supported (single rank only)");
+    if (matrix_free_only_)
+        return fail(kInvalidState, auto_fallback_ ? "landmark covariance: the automatic variant selection chose the matrix-free PCG for this handle: there is no factor to invert"
+                                                  : "landmark covariance: this handle was built matrix-free only: there is no factor to invert");
+    if (tp_.factor_valid() && (factor_lin_ < 0 || !have_params_))
+        return fail(kInvalidState, "landmark covariance: the linearisation point of the factor is gone (parameters or column scaling were set after the solve)");
+    HIP_TRY(hipSetDevice(device_));
+    std::string err;
+    bool recomputed = false;
+    int rc = tp_.ensure_inverse(&recomputed, &err);
+    if (rc == 1) return fail(kInvalidState, "landmark covariance: " + err + " (the Iterative and matrix-free variants have no factor)");
+    if (rc != 0) return fail(kDeviceError, "landmark covariance: " + err);
+    if (!lc_out_ && (rc = lc_setup()) != kOk) return rc;
+    lc_recomputed_ = recomputed;
+    lc_ms_ = 0.0;
+    BAView v = view(factor_lin_);   // the cameras the factor was linearised at; the points come from the landmark records
+    v.cam_scale = factor_scaled_ ? cam_scale_ : nullptr;
+    v.pt_scale = factor_scaled_ ? pt_scale_ : nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const bool timed = tp_.covariance_timing();
+    if (timed) {
+        HIP_TRY(hipEventCreate(&ev[0]));
+        HIP_TRY(hipEventCreate(&ev[1]));
+    }
+    HIP_TRY(hipMemsetAsync(lc_err_, 0, sizeof(int), stream_));
+    if (timed) HIP_TRY(hipEventRecord(ev[0], stream_));
+    launch_landmark_cov(dc_, v, hinv_, tp_.inverse_map(), lc_lists_, lc_n_small_, lc_lists_ + lc_n_small_, lc_n_large_, lc_out_, lc_err_, stream_);
+    if (timed) HIP_TRY(hipEventRecord(ev[1], stream_));
+    hipError_t e = hipGetLastError();
+    std::vector<double> blk(9 * (size_t)n_pt_);
+    int kerr = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(blk.data(), lc_out_, blk.size() * sizeof(double), hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess) e = hipMemcpyAsync(&kerr, lc_err_, sizeof(int), hipMemcpyDeviceToHost, stream_);
+    const hipError_t se = hipStreamSynchronize(stream_);
+    if (e == hipSuccess) e = se;
+    if (timed) {
+        float ms = 0.0f;
+        if (e == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) lc_ms_ = ms;
+        (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
+    }
+    if (e != hipSuccess) return check_hip(e, "landmark covariance");
+    if (kerr) return fail(kDeviceError, "landmark covariance: a covisible camera pair is not in the factor's tile pattern");
+    for (int64_t l = 0; l < n_pt_; ++l) memcpy(out + 9 * l, blk.data() + 9 * (size_t)lmap_[l], 9 * sizeof(double));
     return kOk;
 }
 

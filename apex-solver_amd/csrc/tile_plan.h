@@ -191,7 +191,7 @@ class TilePlan {
     // The tiles hold a valid factor L only between a successful single-rank factorisation + sweeps (the CALLER says so with
     // set_factor_valid(true) once it has read the pivot flags) and the next write of the tiles: zero_tiles, add_diag,
     // scale_sym, factor, a new build() clear the flag.
-    void set_factor_valid(bool on) { factor_valid_ = on; }
+    void set_factor_valid(bool on) { factor_valid_ = on; z_current_ = false; }
     bool factor_valid() const { return factor_valid_; }
     // Z = (L L^T)^-1 on the tile pattern of L, root group first; with j's off-diagonal rows I_j and Y_r = L_rj Linv_j:
     //     Z_rj = - sum_{s in I_j} Z~_rs Y_s    (r in I_j; Z~_rs = Z_rs for r >= s, else Z_sr^T)
@@ -207,6 +207,12 @@ class TilePlan {
     const std::vector<double>& covariance_group_ms() const { return sinv_group_ms_; }
     // tile products of one selected inversion: Y, off-diagonal Z, diagonal Z (each 2*144^3 flop)
     void covariance_op_counts(int64_t* y, int64_t* zoff, int64_t* zdiag) const { *y = sinv_n_[0]; *zoff = sinv_n_[1]; *zdiag = sinv_n_[2]; }
+    // Z of the held factor for a caller that reads Z itself (the landmark covariances): reuses Z when a covariance_blocks() or
+    // ensure_inverse() has computed it since the factor became valid (*recomputed = false), else runs the recurrence without
+    // the diagonal gather.  Z stays current until the factor flag is cleared or set again.  Returns as covariance_blocks.
+    int ensure_inverse(bool* recomputed, std::string* err);
+    TileMap inverse_map() const { return TileMap{z_, slot_, nt_}; }   // Z, addressed as tilemap() addresses S (valid after ensure_inverse)
+    bool covariance_timing() const { return sinv_timing_; }
 
    private:
     using Cols = std::vector<std::vector<int>>;
@@ -338,7 +344,13 @@ class TilePlan {
     // selected inversion (covariance_blocks): built on the first call
     std::string sinv_setup();
     void sinv_release();
+    int sinv_check(std::string* err) const;   // 0, or 1 with the refusal
+    // the recurrence (set-up on the first call) enqueued, with timing events when enabled (0 or 2); after the caller's
+    // synchronisation sinv_collect reads and destroys them
+    int sinv_enqueue(std::vector<hipEvent_t>* ev, std::string* err);
+    void sinv_collect(std::vector<hipEvent_t>& ev, bool ok);
     bool factor_valid_ = false;
+    bool z_current_ = false;   // z_ holds the selected inverse of the factor now in the tiles
     double *z_ = nullptr, *y_ = nullptr;
     SinvTask* sinv_tasks_ = nullptr;
     SinvProd* sinv_prods_ = nullptr;

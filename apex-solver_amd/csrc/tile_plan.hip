@@ -924,7 +924,7 @@ std::string TilePlan::upload(const Lists& lists) {
 #undef TP_TRY
 
 hipError_t TilePlan::zero_tiles(bool own_touched_only, bool skip_fill) {
-    factor_valid_ = false;
+    factor_valid_ = z_current_ = false;
     const size_t te = (size_t)kNB * kNB * sizeof(double);
     hipError_t e = hipSuccess;
     auto clear = [&](int64_t first, int64_t count) {
@@ -946,11 +946,11 @@ hipError_t TilePlan::zero_tiles(bool own_touched_only, bool skip_fill) {
 }
 
 void TilePlan::add_diag(int n_valid, double add_valid, double pad_value) {
-    factor_valid_ = false;
+    factor_valid_ = z_current_ = false;
     launch_tile_add_diag(tiles_, diag_slot_, n_valid, (int)n_pad(), add_valid, pad_value, stream_);
 }
 
-void TilePlan::scale_sym(const double* scale) { factor_valid_ = false; launch_tile_scale_sym(sym_tiles_, n_sym_tiles_, tiles_, scale, stream_); }
+void TilePlan::scale_sym(const double* scale) { factor_valid_ = z_current_ = false; launch_tile_scale_sym(sym_tiles_, n_sym_tiles_, tiles_, scale, stream_); }
 
 void TilePlan::diag(double* out) const { launch_tile_diag(tiles_, diag_slot_, nt_, out, stream_); }
 
@@ -1307,7 +1307,7 @@ void TilePlan::top_slot_ranges(std::pair<int64_t, int64_t> out[2]) const {
 }
 
 void TilePlan::factor_phase(int phase) {
-    factor_valid_ = false;
+    factor_valid_ = z_current_ = false;
     if (phase == 0) { if (!run_graph(kGraphFactor, nullptr, nullptr, nullptr)) enqueue_factor(0, n_local_groups_); }
     else if (!run_graph(kGraphFactorTop, nullptr, nullptr, nullptr)) enqueue_factor(n_local_groups_, n_levels_);
 }
@@ -1317,7 +1317,7 @@ void TilePlan::solve_phase(int phase, const double* rhs, double* x, double* work
 }
 
 hipError_t TilePlan::factor(int* failed_at, bool defer_flags) {
-    factor_valid_ = false;
+    factor_valid_ = z_current_ = false;
     if (distributed()) {
         if (!comm_.sum || !comm_.max_int) return hipErrorNotInitialized;  // a distributed plan needs its communicator
         factor_phase(0);
@@ -1424,7 +1424,7 @@ void TilePlan::sym_matvec(const double* x, double* y) {
 // also made on the device (k_pcg_close_iteration): the speculative iteration behind a met test changes nothing, and x, the
 // iteration count and every scalar are those of the loop that waited every time.
 hipError_t TilePlan::pcg(const double* rhs, double* x, double* work, int max_iter, double tol, int* iters) {
-    factor_valid_ = false;
+    factor_valid_ = z_current_ = false;
     const int n = (int)n_pad();
     double *dg = work, *pre = work + n, *r = work + 2 * (size_t)n, *z = work + 3 * (size_t)n, *p = work + 4 * (size_t)n,
            *ap = work + 5 * (size_t)n;
@@ -1474,7 +1474,7 @@ void TilePlan::sinv_release() {
     sinv_groups_.clear(); sinv_group_ms_.clear();
     sinv_n_[0] = sinv_n_[1] = sinv_n_[2] = 0;
     sinv_bytes_ = 0;
-    factor_valid_ = false;
+    factor_valid_ = z_current_ = false;
 }
 
 // The lists of the recurrence from the slot map and the level groups of the factorisation (nothing of the step path changes):
@@ -1572,30 +1572,53 @@ std::string TilePlan::sinv_setup() {
     return "";
 }
 
-int TilePlan::covariance_blocks(const int64_t* pos, int64_t n_var, int d, double* out, std::string* err) {
+int TilePlan::sinv_check(std::string* err) const {
     if (distributed() || part_world_ > 1) { *err = "covariances of a distributed plan are not supported (single rank only)"; return 1; }
     if (!factor_valid_ || !tiles_) {
         *err = "the tiles hold no valid factor: covariances need a successful direct (Cholesky) solve, and nothing may re-assemble the tiles in between";
         return 1;
     }
-    for (int64_t v = 0; v < n_var; ++v)
-        if (pos[v] < 0 || pos[v] + d > n_pad() || pos[v] / kNB != (pos[v] + d - 1) / kNB) { *err = "variable block outside one diagonal tile"; return 1; }
+    return 0;
+}
+
+int TilePlan::sinv_enqueue(std::vector<hipEvent_t>* ev, std::string* err) {
     if (!z_) {
         const std::string e = sinv_setup();
         if (!e.empty()) { *err = e; return 2; }
     }
-    auto hip_fail = [&](hipError_t e, const char* what) { *err = std::string("HIP error in ") + what + ": " + hipGetErrorString(e); return 2; };
-    std::vector<hipEvent_t> ev;
     if (sinv_timing_) {
-        ev.resize(sinv_groups_.size() + 1, nullptr);
-        for (hipEvent_t& x : ev) { const hipError_t e = hipEventCreate(&x); if (e != hipSuccess) return hip_fail(e, "hipEventCreate"); }
-        (void)hipEventRecord(ev[0], stream_);
+        ev->assign(sinv_groups_.size() + 1, nullptr);
+        for (hipEvent_t& x : *ev) {
+            const hipError_t e = hipEventCreate(&x);
+            if (e != hipSuccess) { sinv_collect(*ev, false); *err = std::string("HIP error in hipEventCreate: ") + hipGetErrorString(e); return 2; }
+        }
+        (void)hipEventRecord((*ev)[0], stream_);
     }
     for (size_t gi = 0; gi < sinv_groups_.size(); ++gi) {
         const SinvGroup& sg = sinv_groups_[gi];
         for (int k = 0; k < 3; ++k) launch_sinv_gemm(sinv_tasks_ + sg.task[k], sg.task[k + 1] - sg.task[k], sinv_prods_, stream_);
-        if (sinv_timing_) (void)hipEventRecord(ev[gi + 1], stream_);
+        if (sinv_timing_) (void)hipEventRecord((*ev)[gi + 1], stream_);
     }
+    return 0;
+}
+
+void TilePlan::sinv_collect(std::vector<hipEvent_t>& ev, bool ok) {
+    if (ev.empty()) return;
+    sinv_group_ms_.assign(ev.size() - 1, 0.0);
+    for (size_t gi = 0; gi + 1 < ev.size(); ++gi) {
+        float ms = 0.0f;
+        if (ok && ev[gi] && ev[gi + 1] && hipEventElapsedTime(&ms, ev[gi], ev[gi + 1]) == hipSuccess) sinv_group_ms_[gi] = ms;
+    }
+    for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+    ev.clear();
+}
+
+int TilePlan::covariance_blocks(const int64_t* pos, int64_t n_var, int d, double* out, std::string* err) {
+    if (const int rc = sinv_check(err)) return rc;
+    for (int64_t v = 0; v < n_var; ++v)
+        if (pos[v] < 0 || pos[v] + d > n_pad() || pos[v] / kNB != (pos[v] + d - 1) / kNB) { *err = "variable block outside one diagonal tile"; return 1; }
+    std::vector<hipEvent_t> ev;
+    if (const int rc = sinv_enqueue(&ev, err)) return rc;
     int64_t* dpos = nullptr;
     double* dout = nullptr;
     hipError_t e = hipGetLastError();
@@ -1611,15 +1634,25 @@ int TilePlan::covariance_blocks(const int64_t* pos, int64_t n_var, int d, double
     if (e == hipSuccess) e = se;
     if (dpos) (void)hipFree(dpos);
     if (dout) (void)hipFree(dout);
-    if (sinv_timing_) {
-        sinv_group_ms_.assign(sinv_groups_.size(), 0.0);
-        for (size_t gi = 0; gi < sinv_groups_.size(); ++gi) {
-            float ms = 0.0f;
-            if (e == hipSuccess && hipEventElapsedTime(&ms, ev[gi], ev[gi + 1]) == hipSuccess) sinv_group_ms_[gi] = ms;
-        }
-        for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
-    }
-    if (e != hipSuccess) return hip_fail(e, "covariance_blocks");
+    sinv_collect(ev, e == hipSuccess);
+    if (e != hipSuccess) { *err = std::string("HIP error in covariance_blocks: ") + hipGetErrorString(e); return 2; }
+    z_current_ = true;
+    return 0;
+}
+
+int TilePlan::ensure_inverse(bool* recomputed, std::string* err) {
+    *recomputed = false;
+    if (const int rc = sinv_check(err)) return rc;
+    if (z_current_) return 0;
+    std::vector<hipEvent_t> ev;
+    if (const int rc = sinv_enqueue(&ev, err)) return rc;
+    hipError_t e = hipGetLastError();
+    const hipError_t se = hipStreamSynchronize(stream_);
+    if (e == hipSuccess) e = se;
+    sinv_collect(ev, e == hipSuccess);
+    if (e != hipSuccess) { *err = std::string("HIP error in ensure_inverse: ") + hipGetErrorString(e); return 2; }
+    z_current_ = true;
+    *recomputed = true;
     return 0;
 }
 

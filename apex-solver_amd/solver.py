@@ -113,6 +113,8 @@ class LevenbergMarquardtConfig:
     use_jacobi_scaling: bool = False  # :352
     # :287-294, 479-486: marginal covariances of the last factorised system into SolverResult.covariances after the loop
     compute_covariances: bool = False
+    # with compute_covariances: also the 3 x 3 landmark blocks ("pt_{l:05}") -- Python side only, like the flag above
+    compute_landmark_covariances: bool = False
 
     @classmethod
     def new(cls) -> "LevenbergMarquardtConfig":
@@ -138,6 +140,7 @@ class LevenbergMarquardtConfig:
     def with_schur_preconditioner(self, v): return replace(self, schur_preconditioner=v)
     def with_jacobi_scaling(self, on): return replace(self, use_jacobi_scaling=bool(on))  # :474-477
     def with_compute_covariances(self, on): return replace(self, compute_covariances=bool(on))  # :479-486
+    def with_compute_landmark_covariances(self, on): return replace(self, compute_landmark_covariances=bool(on))
 
     def to_c(self) -> capi.LmConfigC:
         return capi.LmConfigC(
@@ -428,14 +431,34 @@ class GpuSchurComplementSolver:
         h.check(h.L.apexgpu_camera_covariance(h.h, capi.ptr(out)))
         return out
 
-    def compute_covariances(self) -> dict:
-        """{"pose_{i:04}": 6 x 6, "intr_{i:04}": 3 x 3} per camera (landmarks are not computed).  The reference's Schur
-        solvers return None here; this is a superset."""
-        return camera_covariance_dict(self.camera_covariance_blocks())
+    def landmark_covariance_blocks(self) -> np.ndarray:
+        """(n_pt, 3, 3): the landmark blocks of the inverse of the matrix camera_covariance_blocks describes (the last direct
+        solve's point, lambda, Jacobi scaling, eigenvalue gate and ladder regularisation), caller's landmark order, by the
+        Schur-complement identity from the selected inverse of S (reused after a camera_covariance_blocks call for the same
+        factor).  Raises LinAlgError (InvalidState) where camera_covariance_blocks does, and when the parameters or the
+        column scaling were set after the solve."""
+        h = self._need()
+        out = np.zeros((h.n_pt, 3, 3))
+        h.check(h.L.apexgpu_landmark_covariance(h.h, capi.ptr(out)))
+        return out
+
+    def compute_covariances(self, landmarks: bool = False) -> dict:
+        """{"pose_{i:04}": 6 x 6, "intr_{i:04}": 3 x 3} per camera, and with landmarks=True "pt_{l:05}": 3 x 3 per landmark.
+        The reference's Schur solvers return None here; this is a superset."""
+        out = camera_covariance_dict(self.camera_covariance_blocks())
+        if landmarks:
+            out.update(landmark_covariance_dict(self.landmark_covariance_blocks()))
+        return out
 
     def covariance_stats(self, group_cap: int = 0) -> dict:
         h = self._need()
         return _covariance_stats(h, h.L.apexgpu_covariance_stats, group_cap)
+
+    def landmark_covariance_stats(self) -> dict:
+        h = self._need()
+        out = (C.c_double * 4)()
+        h.check(h.L.apexgpu_landmark_covariance_stats(h.h, C.byref(out)))
+        return dict(extra_bytes=int(out[0]), pairs=int(out[1]), recomputed_z=bool(out[2]), landmark_ms=float(out[3]))
 
     def get_landmark_blocks(self):
         h = self._need()
@@ -553,6 +576,11 @@ def camera_covariance_dict(blocks: np.ndarray) -> dict:
     return out
 
 
+def landmark_covariance_dict(blocks: np.ndarray) -> dict:
+    """(n_pt, 3, 3) landmark blocks -> {"pt_{l:05}": 3 x 3} (the reference's landmark names)."""
+    return {f"pt_{l:05}": b.copy() for l, b in enumerate(blocks)}
+
+
 def _covariance_stats(h, fn, group_cap: int) -> dict:
     out = (C.c_double * 6)()
     ms = np.zeros(max(int(group_cap), 1))
@@ -561,12 +589,12 @@ def _covariance_stats(h, fn, group_cap: int) -> dict:
                 level_groups=int(out[4]), group_ms=ms[:int(out[5])].tolist())
 
 
-def _covariances_or_none(s):
+def _covariances_or_none(s, landmarks: bool = False):
     """compute_covariance_matrix returning None (linalg/mod.rs:165-172): a solve without a factor (Iterative, matrix-free,
     a handle the automatic variant selection made matrix-free) has no covariances -- None and a warning, not an error."""
     import warnings
     try:
-        return s.compute_covariances()
+        return s.compute_covariances(landmarks=True) if landmarks else s.compute_covariances()
     except capi.LinAlgError as e:
         if e.code != -6:
             raise
@@ -644,7 +672,8 @@ class LevenbergMarquardt:
         s.set_parameters(poses, intr, pts)
         self.linear_solver = s
         res, hist, c = s.lm_optimize(self.config)
-        cov = _covariances_or_none(s) if self.config.compute_covariances else None
+        cov = (_covariances_or_none(s, self.config.compute_landmark_covariances) if self.config.compute_covariances
+               else None)
         return SolverResult(
             status=OptimizationStatus(res.status), iterations=res.iterations, initial_cost=res.initial_cost,
             final_cost=res.final_cost, parameters=s.get_parameters(), elapsed_time=res.elapsed_s,

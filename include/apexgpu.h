@@ -205,8 +205,8 @@ int apexgpu_get_schur(apexgpu_solver* h, double* S_out, double* gred_out);
  * of the matrix the LAST apexgpu_solve_augmented factorised -- (H + lambda I)^-1 by the Schur-complement identity, at that
  * solve's point, lambda and Jacobi scaling, plus its ladder regularisation if any (apexgpu_info[4]) -- from the tile factor
  * by selected inversion.  cov_out[n_cam][9][9], caller's camera order, pose 6 then intrinsics 3 (apexgpu_get_schur's
- * layout); BundleAdjustment mode (d_c = 6): intrinsics 1 / lambda on the diagonal, no cross terms.  Landmarks: not
- * computed.  APEXGPU_ERR_INVALID_STATE (last_error says why): no direct (variant 0) solve since the last assembly or
+ * layout); BundleAdjustment mode (d_c = 6): intrinsics 1 / lambda on the diagonal, no cross terms.  Landmarks:
+ * apexgpu_landmark_covariance.  APEXGPU_ERR_INVALID_STATE (last_error says why): no direct (variant 0) solve since the last assembly or
  * export, a PCG / matrix-free handle or solve, a sharded handle. */
 int apexgpu_camera_covariance(apexgpu_solver* h, double* cov_out /* n_cam*81 */);
 /* What the selected inversion behind apexgpu_camera_covariance costs: out[0] device bytes it added (allocated by the first
@@ -214,6 +214,18 @@ int apexgpu_camera_covariance(apexgpu_solver* h, double* cov_out /* n_cam*81 */)
  * groups; with the option "covariance_timing" on, group_ms[i] (i < group_cap) = milliseconds of level group i's launches in
  * the last call, root group first, and out[5] = how many were written.  Any pointer but out may be NULL. */
 int apexgpu_covariance_stats(apexgpu_solver* h, double out[6], double* group_ms, int group_cap);
+/* Marginal landmark covariances: the 3 x 3 landmark blocks of the inverse of the same matrix apexgpu_camera_covariance
+ * describes (the LAST variant-0 solve's point, lambda, Jacobi scaling, eigenvalue gate and ladder regularisation), by the
+ * Schur-complement identity  Sigma_ll = V_l^-1 + sum_{i,j in obs(l)} U_i^T Z_{c(i) c(j)} U_j,  U_i = W_il V_l^-1,  Z = S^-1
+ * from the selected inversion (reused when an apexgpu_camera_covariance call computed it for this factor, else computed
+ * first).  cov_out[n_pt][3][3], caller's landmark order, symmetric bit for bit; repeated calls give the same bits.
+ * APEXGPU_ERR_INVALID_STATE (last_error says why) wherever apexgpu_camera_covariance refuses, and when the factor's
+ * linearisation point is gone (apexgpu_set_parameters or new column scaling after the solve). */
+int apexgpu_landmark_covariance(apexgpu_solver* h, double* cov_out /* n_pt*9 */);
+/* out[0] device bytes the landmark pass added (allocated by its first call), out[1] observation pairs per call
+ * (sum k (k + 1) / 2), out[2] 1 if the last call recomputed Z, 0 if it reused it, out[3] milliseconds of the landmark
+ * kernels alone in the last call with the option "covariance_timing" on, else 0. */
+int apexgpu_landmark_covariance_stats(apexgpu_solver* h, double out[4]);
 int apexgpu_get_landmark_blocks(apexgpu_solver* h, double* hinv_out /* n_pt*9 */, double* gl_out /* n_pt*3 */);
 /* Parity probe of row A9: invert_landmark_blocks_with_lambda(.., 0.0) (explicit_schur.rs:365-442) -- the eigenvalue gate
  * (min_ev < 1e-12 -> + (1e-6 + max_ev 1e-6) I; max_ev / min_ev > 1e10 -> + max_ev 1e-6 I; else plain inverse) exactly as
