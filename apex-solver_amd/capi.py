@@ -27,6 +27,8 @@ SYMBOLS = (
     "apexgpu_get_schur", "apexgpu_camera_covariance", "apexgpu_covariance_stats", "apexgpu_landmark_covariance", "apexgpu_landmark_covariance_stats", "apexgpu_get_landmark_blocks", "apexgpu_get_hessian_csc", "apexgpu_debug_invert_blocks", "apexgpu_debug_pair_lists", "apexgpu_debug_pair_lists_queued", "apexgpu_debug_pair_lists_queued_dc", "apexgpu_debug_host_structure", "apexgpu_setup_times", "apexgpu_schur_matvec", "apexgpu_set_option", "apexgpu_enable_stage_timing", "apexgpu_reset_stage_times",
     "apexgpu_stage_times", "apexgpu_info", "apexgpu_variant_info", "apexgpu_variant_costs", "apexgpu_trim_host_cache", "apexgpu_host_cache_bytes", "apexgpu_counters", "apexgpu_debug_get_pair_records", "apexgpu_get_unique_id", "apexgpu_comm_init", "apexgpu_comm_init_shm", "apexgpu_set_shard", "apexgpu_shard_range",
     "apexgpu_debug_lockstep_solve", "apexgpu_export_step", "apexgpu_owned_landmarks", "apexgpu_debug_partition", "apexgpu_debug_check_schedule",
+    "apexgpu_debug_tiles_create", "apexgpu_debug_tiles_pattern", "apexgpu_debug_tiles_set", "apexgpu_debug_tiles_factor",
+    "apexgpu_debug_tiles_solve", "apexgpu_debug_tiles_matvec", "apexgpu_debug_tiles_get", "apexgpu_debug_tiles_destroy",
     "apexgpu_bal_open", "apexgpu_bal_close", "apexgpu_bal_last_error", "apexgpu_bal_sizes", "apexgpu_bal_raw",
     "apexgpu_bal_variables", "apexgpu_reference_columns",
     # SE3 pose-graph backend
@@ -42,7 +44,7 @@ SYMBOLS = (
 )
 PG_NUM_STAGES = 6
 PG_STAGE_NAMES = ("assemble", "factor", "tri_solve", "step_stats", "retract", "cost")
-_NON_INT = ("apexgpu_destroy", "apexgpu_last_error", "apexgpu_version", "apexgpu_host_cache_bytes", "apexgpu_bal_close", "apexgpu_bal_last_error",
+_NON_INT = ("apexgpu_destroy", "apexgpu_debug_tiles_destroy", "apexgpu_last_error", "apexgpu_version", "apexgpu_host_cache_bytes", "apexgpu_bal_close", "apexgpu_bal_last_error",
             "apexgpu_pg_destroy", "apexgpu_pg_last_error", "apexgpu_g2o_close", "apexgpu_g2o_last_error")
 
 ERROR_NAMES = {
@@ -123,6 +125,15 @@ def load() -> C.CDLL:
     L.apexgpu_owned_landmarks.argtypes = [vp, vp]
     L.apexgpu_debug_partition.argtypes = [C.c_int, vp, C.c_int, vp]
     L.apexgpu_debug_check_schedule.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_char_p, C.c_int]
+    L.apexgpu_debug_tiles_create.argtypes = [C.c_int, C.c_int, vp, vp, C.POINTER(vp)]
+    L.apexgpu_debug_tiles_pattern.argtypes = [vp, vp, vp]
+    L.apexgpu_debug_tiles_set.argtypes = [vp, vp, C.c_int, dbl, C.c_int]
+    L.apexgpu_debug_tiles_factor.argtypes = [vp, C.POINTER(C.c_int)]
+    L.apexgpu_debug_tiles_solve.argtypes = [vp, C.c_int, vp, vp]
+    L.apexgpu_debug_tiles_matvec.argtypes = [vp, vp, vp]
+    L.apexgpu_debug_tiles_get.argtypes = [vp, C.c_int, vp]
+    L.apexgpu_debug_tiles_destroy.argtypes = [vp]
+    L.apexgpu_debug_tiles_destroy.restype = None
     L.apexgpu_set_column_scaling.argtypes = [vp, vp]
     L.apexgpu_lm_optimize.argtypes = [vp, C.POINTER(LmConfigC), C.POINTER(LmResultC), vp, C.c_int]
     L.apexgpu_get_residual.argtypes = [vp, vp]
@@ -378,6 +389,94 @@ class PgHandle:
         if getattr(self, "h", None) is not None and self.h:
             self.L.apexgpu_pg_destroy(self.h)
             self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TileCholesky:
+    """Tests only: the single-GPU tile Cholesky (TilePlan) on a matrix the caller chooses (apexgpu_debug_tiles_*).
+
+    present: (nt, nt) lower-triangular 0/1 tile structure in the final order (nothing is reordered).  Tiles are 144 x 144
+    row-major; the arrays below are indexed by slot (`slot[I, J]`, -1 outside the filled pattern)."""
+
+    OPTS = ("graphs", "factor_flow", "factor_flow_rows", "tri_dataflow", "update_overlap", "split_u1", "two_side", "flood_gate")
+    DEFAULTS = dict(graphs=1, factor_flow=-1, factor_flow_rows=24, tri_dataflow=1, update_overlap=1, split_u1=4, two_side=1, flood_gate=256)
+
+    def __init__(self, present: np.ndarray, device: int = 0, **opts):
+        unknown = set(opts) - set(self.OPTS)
+        if unknown:
+            raise ValueError(f"unknown options {sorted(unknown)}")
+        self.L = load()
+        self.h = C.c_void_p()
+        pr = np.ascontiguousarray(present, dtype=np.uint8)
+        self.nt = int(pr.shape[0])
+        o = dict(self.DEFAULTS, **opts)
+        ov = np.array([o[k] for k in self.OPTS], dtype=np.int32)
+        rc = self.L.apexgpu_debug_tiles_create(int(device), self.nt, ptr(pr), ptr(ov), C.byref(self.h))
+        if rc != 0:
+            raise LinAlgError(rc, "apexgpu_debug_tiles_create failed")
+        self.slot = np.zeros((self.nt, self.nt), dtype=np.int32)
+        info = np.zeros(8, dtype=np.int64)
+        self._check(self.L.apexgpu_debug_tiles_pattern(self.h, ptr(self.slot), ptr(info)), "pattern")
+        self.n_slots, self.n_touched, self.levels, self.first_writers_flagged = int(info[0]), int(info[1]), int(info[2]), bool(info[3])
+        self.flow_units, self.flow_groups, self.n_pad, self.nb = int(info[4]), int(info[5]), int(info[6]), int(info[7])
+
+    def _check(self, rc: int, what: str):
+        if rc != 0:
+            raise LinAlgError(rc, f"apexgpu_debug_tiles_{what} failed")
+
+    def set(self, touched: np.ndarray, n_valid: int | None = None, add_diag: float = 0.0, fill_mode: int = 0):
+        """touched: (n_touched, 144, 144) tiles in slot order, diagonal tiles in full (symmetric)."""
+        t = np.ascontiguousarray(touched, dtype=np.float64)
+        assert t.shape == (self.n_touched, self.nb, self.nb), t.shape
+        nv = self.n_pad if n_valid is None else int(n_valid)
+        self._check(self.L.apexgpu_debug_tiles_set(self.h, ptr(t), nv, float(add_diag), int(fill_mode)), "set")
+
+    def factor(self) -> int:
+        """0, or (a failed tile column + 1)."""
+        f = C.c_int(0)
+        self._check(self.L.apexgpu_debug_tiles_factor(self.h, C.byref(f)), "factor")
+        return f.value
+
+    def solve(self, rhs: np.ndarray) -> np.ndarray:
+        b = np.ascontiguousarray(np.atleast_2d(rhs), dtype=np.float64)
+        assert b.shape[1] == self.n_pad
+        x = np.empty_like(b)
+        self._check(self.L.apexgpu_debug_tiles_solve(self.h, b.shape[0], ptr(b), ptr(x)), "solve")
+        return x.reshape(np.shape(rhs))
+
+    def matvec(self, x: np.ndarray) -> np.ndarray:
+        xv = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.empty_like(xv)
+        self._check(self.L.apexgpu_debug_tiles_matvec(self.h, ptr(xv), ptr(y)), "matvec")
+        return y
+
+    def get(self, which: str) -> np.ndarray:
+        """"tiles" (raw), "L" (the tiles with the diagonal tiles masked to their lower triangle), "Linv" ((nt, 144, 144)),
+        "Z" (the selected inverse on the pattern of L)."""
+        k = {"tiles": 0, "L": 0, "Linv": 1, "Z": 2}[which]
+        out = np.empty(((self.nt if k == 1 else self.n_slots), self.nb, self.nb))
+        self._check(self.L.apexgpu_debug_tiles_get(self.h, k, ptr(out)), "get")
+        if which == "L":   # a factorised diagonal tile keeps the assembled matrix in its 16 x 16 blocks right of the diagonal
+            low = np.tril(np.ones((self.nb, self.nb), dtype=bool))
+            for K in range(self.nt):
+                out[self.slot[K, K]] = np.where(low, out[self.slot[K, K]], 0.0)
+        return out
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            self.L.apexgpu_debug_tiles_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:

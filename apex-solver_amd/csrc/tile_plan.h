@@ -108,6 +108,7 @@ class TilePlan {
     // tile operations of one factorisation: potrf+inverse, panel products, trailing updates (each 2*144^3 flop for the last two)
     void op_counts(int64_t* potrf, int64_t* trsm, int64_t* upd) const { *potrf = n_potrf_; *trsm = n_trsm_; *upd = n_upd_; }
     double* tiles() const { return tiles_; }
+    const double* linv() const { return linv_; }   // [nt] inverses of the diagonal tiles of L (written by the factorisation)
     const int* slot_host() const { return slot_h_.data(); }
     int slot(int I, int J) const { return slot_h_[(size_t)I * nt_ + J]; }
     TileMap tilemap() const { return TileMap{tiles_, slot_, nt_}; }

@@ -413,6 +413,32 @@ int apexgpu_debug_partition(int nt, const uint8_t* present, int world, int* owne
  * Returns the number of level groups (>= 0) or an error; msg receives the first violation.  (round-3 advice: the U2 split
  * had dropped the edge behind a level without side-stream work; the checker finds it on the advisor's pattern.) */
 int apexgpu_debug_check_schedule(int nt, const uint8_t* present, int world, int rank, const int opts[8], int64_t out[8], char* msg, int msg_len);
+/* Tests only: the single-GPU tile Cholesky (TilePlan) on a matrix the caller chooses, in the caller's tile order (nothing is
+ * reordered).  present: lower-triangular nt x nt 0/1 structure (I >= J); opts[8] = {graphs, factor_flow (max columns; 0 off,
+ * < 0 by cost model), factor_flow_rows, tri_dataflow, update_overlap (> 1: minimum batch), split_u1 (0 off, else minimum
+ * batch), two_side, flood_gate}.  Without a visible GPU: APEXGPU_ERR_DEVICE. */
+typedef struct apexgpu_tiles apexgpu_tiles;
+int apexgpu_debug_tiles_create(int device, int nt, const uint8_t* present, const int opts[8], apexgpu_tiles** out);
+/* slot_out[nt*nt] (may be NULL): the tile slot of (I, J), -1 outside the filled pattern; info[8] = {slots, touched slots (they
+ * come first), level groups, first writers of the fill tiles flagged, dataflow factorisation units, level groups inside
+ * the dataflow launch, n_pad, tile size} */
+int apexgpu_debug_tiles_pattern(apexgpu_tiles* h, int32_t* slot_out, int64_t info[8]);
+/* What a solver's assembly does: clear the touched tiles (the fill tiles stay as they are where the first writers are
+ * flagged), copy touched[n_touched][144][144] (slot order, diagonal tiles in full), add add_diag to the first n_valid
+ * diagonal entries and set the padding rows to identity.  fill_mode 1: the fill tiles are then set to quiet NaN, which the
+ * factorisation must never read (APEXGPU_ERR_INVALID_STATE where the plan does not flag its first writers). */
+int apexgpu_debug_tiles_set(apexgpu_tiles* h, const double* touched, int n_valid, double add_diag, int fill_mode);
+/* factor in place; *failed_at = 0 or (a failed tile column + 1).  Marks the tiles a valid factor on success. */
+int apexgpu_debug_tiles_factor(apexgpu_tiles* h, int* failed_at);
+/* x[k] = (L L^T)^-1 rhs[k] for k < n_rhs, n_pad doubles each (after a successful factor) */
+int apexgpu_debug_tiles_solve(apexgpu_tiles* h, int n_rhs, const double* rhs, double* x);
+/* y = A x on the unfactored tiles (after set, before factor), n_pad doubles */
+int apexgpu_debug_tiles_matvec(apexgpu_tiles* h, const double* x, double* y);
+/* which 0: the tiles (L after a factor; a diagonal tile's 16 x 16 blocks right of its diagonal keep the assembled matrix),
+ * out[n_slots][144][144]; 1: the inverses of L's diagonal tiles, out[nt][144][144]; 2: the selected inverse Z on the
+ * pattern of L (computed first where needed; needs a valid factor), out[n_slots][144][144] */
+int apexgpu_debug_tiles_get(apexgpu_tiles* h, int which, double* out);
+void apexgpu_debug_tiles_destroy(apexgpu_tiles* h);
 /* Host arithmetic only: the sorted camera-pair lists of the default Schur reduction for an observation list, with the
  * caller's camera order and a dense tile map (slot(I, J) = I (I + 1) / 2 + J).  counts[4] = {slots, chunks, blocks, tasks};
  * outputs may be NULL (size query): recs4 [slots][4] = {i, j, landmark, block local to the chunk} (i = 0xFFFFFFFF:
