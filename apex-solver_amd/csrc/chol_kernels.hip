@@ -1555,12 +1555,19 @@ __global__ __launch_bounds__(256) void k_pcg_step2(int n, int n_blk, double* __r
     __syncthreads();
     const double rz_t = (sc[0] + sc[1]) + (sc[2] + sc[3]);
     __shared__ int s_frozen;
-    if (tid == 0) { s_beta = rz_t / scal[0]; s_frozen = scal[4] != 0.0; }
+    __shared__ int s_stop;
+    if (tid == 0) {
+        s_beta = rz_t / scal[0]; s_frozen = scal[4] != 0.0;
+        // p.Ap ~ 0 or rz_old ~ 0 (a zero right-hand side: no camera columns, a converged start): the reference breaks before
+        // it forms beta (:703-705, :741-743).  k_pcg_close_iteration freezes behind this kernel; beta = 0 / 0 must not reach p,
+        // or the speculative iteration's x += 0 * p turns the untouched x into NaN
+        s_stop = fabs(scal[1]) < 1e-30 || fabs(scal[0]) < 1e-30;
+    }
     __syncthreads();
     if (s_frozen) return;   // (a speculative iteration behind a met termination test: p and the scalars stay)
     const double beta = s_beta;
     const int i = blockIdx.x * 256 + tid;
-    if (i < n) p[i] = pre[i] * r[i] + beta * p[i];
+    if (i < n && !s_stop) p[i] = pre[i] * r[i] + beta * p[i];
     if (blockIdx.x == 0 && tid == 0) { out2[0] = rr_t; out2[1] = rz_t; }
 }
 // The end of a PCG iteration on the device (one thread): the reference's three termination tests on this iteration's scalars

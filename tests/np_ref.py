@@ -176,14 +176,16 @@ def schur_dense(H, g, cam_dof, lam):
     return S, gred
 
 
-def retract(poses, intr, pts, step, lay, fix_pose=None):
-    """x (+) step with the right-plus SE3 retraction; returns new (poses, intr, pts).
+def retract(poses, intr, pts, step, lay, fix_pose=None, fix_intr=None, fix_pt=None, sign=1.0):
+    """x (+) sign * step with the right-plus SE3 retraction; returns new (poses, intr, pts).
     Quaternions are returned normalised (the reference stores the raw product and
-    normalises on the next use; the rotation is the same)."""
+    normalises on the next use; the rotation is the same).  The three per-DOF masks (problem.rs:185-197, 275-284:
+    a fixed DOF is zeroed in the step when it is applied) are in the caller's numbering, [n_cam][6], [n_cam][3], [n_pt][3];
+    sign = -1 is apply_negative_parameter_step (optimizer/mod.rs:343-356), under the same masks."""
     n_cam = poses.shape[0]
-    d = step[lay.pose_col[:, None] + np.arange(6)[None]].copy()
+    d = sign * step[lay.pose_col[:, None] + np.arange(6)[None]]
     if fix_pose is not None:
-        d[fix_pose.astype(bool)] = 0.0
+        d[np.asarray(fix_pose).reshape(n_cam, 6).astype(bool)] = 0.0
     R = quat_to_R(poses[:, 3:7])
     Rn = R @ so3_exp_R(d[:, 3:6])
     tn = poses[:, 0:3] + np.einsum("nij,nj->ni", R, np.einsum("nij,nj->ni", so3_V(d[:, 3:6]), d[:, 0:3]))
@@ -196,6 +198,10 @@ def retract(poses, intr, pts, step, lay, fix_pose=None):
     sgn[sgn == 0] = 1
     q *= sgn[:, None]
     new_poses = np.concatenate([tn, q], -1)
-    new_intr = intr + step[lay.intr_col[:, None] + np.arange(3)[None]]
-    new_pts = pts + step[lay.pt_col[:, None] + np.arange(3)[None]]
-    return new_poses, new_intr, new_pts
+    di = sign * step[lay.intr_col[:, None] + np.arange(3)[None]]
+    if fix_intr is not None:
+        di[np.asarray(fix_intr).reshape(n_cam, 3).astype(bool)] = 0.0
+    dp = sign * step[lay.pt_col[:, None] + np.arange(3)[None]]
+    if fix_pt is not None:
+        dp[np.asarray(fix_pt).reshape(pts.shape[0], 3).astype(bool)] = 0.0
+    return new_poses, intr + di, pts + dp

@@ -88,3 +88,33 @@ def normal_equations(r, J, e_from, e_to, pose_col):
         H[np.ix_(cols, cols)] += J[e].T @ J[e]
         g[cols] += J[e].T @ r[e]
     return H, g
+
+
+def so3_left_jacobian(th):
+    """V(theta) of the SE3 exponential (so3.rs:595-612), by its series below the small-angle threshold."""
+    a = th @ th
+    K = hat(th)
+    if a <= 1e-10:
+        return np.eye(3) + 0.5 * K
+    t = np.sqrt(a)
+    return np.eye(3) + (1 - np.cos(t)) / a * K + (t - np.sin(t)) / (a * t) * (K @ K)
+
+
+def retract(poses, step, pose_col, fix=None, sign=1.0):
+    """x (+) sign * step, vertex by vertex (se3.rs:569-583: T' = T Exp(delta), t' = t + R V(theta) rho, R' = R Exp(theta)),
+    on rotation matrices; DOF with a nonzero byte in fix[n_v][6] (caller's vertex order) are zeroed in the step first
+    (problem.rs:185-197, 275-284).  Returns [n_v][7] with the quaternion normalised, in the hemisphere of the input's."""
+    out = np.empty((len(pose_col), 7))
+    for v in range(len(pose_col)):
+        d = sign * np.asarray(step[pose_col[v]:pose_col[v] + 6], dtype=np.float64)
+        if fix is not None:
+            d = np.where(np.asarray(fix[v]).astype(bool), 0.0, d)
+        R, t = to_Rt(poses[v])
+        Rn = R @ Rotation.from_rotvec(d[3:6]).as_matrix()
+        tn = t + R @ (so3_left_jacobian(d[3:6]) @ d[0:3])
+        x, y, z, w = Rotation.from_matrix(Rn).as_quat()
+        q = np.array([w, x, y, z])
+        if q @ poses[v][3:7] < 0:
+            q = -q
+        out[v] = np.concatenate([tn, q])
+    return out
