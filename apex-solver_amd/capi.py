@@ -41,7 +41,11 @@ SYMBOLS = (
     "apexgpu_pg_set_priors", "apexgpu_pg_get_prior_residual",
     "apexgpu_g2o_open", "apexgpu_g2o_close", "apexgpu_g2o_last_error", "apexgpu_g2o_sizes", "apexgpu_g2o_raw",
     "apexgpu_g2o_problem", "apexgpu_pose_graph_columns",
+    # SE2 pose graphs: the same handle, two more lifetime calls, the SE2 content of a G2O file
+    "apexgpu_pg_create_se2", "apexgpu_pg_manifold", "apexgpu_g2o_raw_se2", "apexgpu_g2o_problem_se2",
+    "apexgpu_pose_graph_columns_se2",
 )
+MANIFOLD_SE3, MANIFOLD_SE2 = 0, 1
 PG_NUM_STAGES = 6
 PG_STAGE_NAMES = ("assemble", "factor", "tri_solve", "step_stats", "retract", "cost")
 _NON_INT = ("apexgpu_destroy", "apexgpu_debug_tiles_destroy", "apexgpu_last_error", "apexgpu_version", "apexgpu_host_cache_bytes", "apexgpu_bal_close", "apexgpu_bal_last_error",
@@ -215,6 +219,11 @@ def load() -> C.CDLL:
     L.apexgpu_g2o_raw.argtypes = [vp] * 7
     L.apexgpu_g2o_problem.argtypes = [vp] * 8
     L.apexgpu_pose_graph_columns.argtypes = [i64, vp, vp]
+    L.apexgpu_pg_create_se2.argtypes = [i64, i64, C.c_int, C.POINTER(vp)]
+    L.apexgpu_pg_manifold.argtypes = [vp, C.POINTER(C.c_int * 3)]
+    L.apexgpu_g2o_raw_se2.argtypes = [vp] * 7
+    L.apexgpu_g2o_problem_se2.argtypes = [vp] * 8
+    L.apexgpu_pose_graph_columns_se2.argtypes = [i64, vp, vp]
     for name in SYMBOLS:
         f = getattr(L, name)
         if name not in _NON_INT:
@@ -373,13 +382,16 @@ class Handle:
 class PgHandle:
     """RAII wrapper of an apexgpu_pg_solver*."""
 
-    def __init__(self, n_vertices: int, n_edges: int, device: int = 0):
+    def __init__(self, n_vertices: int, n_edges: int, device: int = 0, manifold: int = MANIFOLD_SE3):
         self.L = load()
         self.h = C.c_void_p()
-        rc = self.L.apexgpu_pg_create(n_vertices, n_edges, device, C.byref(self.h))
+        create = self.L.apexgpu_pg_create_se2 if manifold == MANIFOLD_SE2 else self.L.apexgpu_pg_create
+        rc = create(n_vertices, n_edges, device, C.byref(self.h))
         if rc != 0:
             raise LinAlgError(rc, "apexgpu_pg_create failed (no MI355X visible to HIP?)")
         self.n_vertices, self.n_edges = n_vertices, n_edges
+        self.manifold = manifold
+        self.ambient, self.dof = (3, 3) if manifold == MANIFOLD_SE2 else (7, 6)
 
     def check(self, rc: int):
         if rc != 0:

@@ -589,20 +589,32 @@ int apexgpu_debug_invert_blocks(int device, int64_t n, const double* blocks9, do
 }
 
 
-/* ---- SE3 pose-graph backend --------------------------------------------------------------------- */
+/* ---- pose-graph backend (SE3, SE2) --------------------------------------------------------------------- */
 #define PG_OR_FAIL \
     if (!h || !h->s) return APEXGPU_ERR_INVALID_STATE
 
-int apexgpu_pg_create(int64_t n_vertices, int64_t n_edges, int device, apexgpu_pg_solver** out) {
+static int pg_create(int64_t n_vertices, int64_t n_edges, int device, int manifold, apexgpu_pg_solver** out) {
     if (!out) return APEXGPU_ERR_INVALID_INPUT;
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return APEXGPU_ERR_DEVICE;
     apexgpu_pg_solver* h = new (std::nothrow) apexgpu_pg_solver();
     if (!h) return APEXGPU_ERR_INVALID_STATE;
-    h->s = new (std::nothrow) apex::PoseGraphSolver(n_vertices, n_edges, device);
+    h->s = new (std::nothrow) apex::PoseGraphSolver(n_vertices, n_edges, device, manifold);
     if (!h->s) { delete h; return APEXGPU_ERR_INVALID_STATE; }
     *out = h;
+    return APEXGPU_OK;
+}
+int apexgpu_pg_create(int64_t n_vertices, int64_t n_edges, int device, apexgpu_pg_solver** out) {
+    return pg_create(n_vertices, n_edges, device, APEXGPU_MANIFOLD_SE3, out);
+}
+int apexgpu_pg_create_se2(int64_t n_vertices, int64_t n_edges, int device, apexgpu_pg_solver** out) {
+    return pg_create(n_vertices, n_edges, device, APEXGPU_MANIFOLD_SE2, out);
+}
+int apexgpu_pg_manifold(const apexgpu_pg_solver* h, int out3[3]) {
+    PG_OR_FAIL;
+    if (!out3) return APEXGPU_ERR_INVALID_INPUT;
+    out3[0] = h->s->manifold(); out3[1] = h->s->ambient(); out3[2] = h->s->dof();
     return APEXGPU_OK;
 }
 void apexgpu_pg_destroy(apexgpu_pg_solver* h) {
@@ -712,7 +724,7 @@ int apexgpu_pg_counters(apexgpu_pg_solver* h, int64_t out[4]) {
 int apexgpu_pg_info(apexgpu_pg_solver* h, double info[8]) {
     PG_OR_FAIL;
     info[0] = h->s->n_tile_rows(); info[1] = (double)h->s->tile_count(); info[2] = (double)h->s->touched_tiles();
-    info[3] = h->s->n_levels(); info[4] = 6.0 * (double)h->s->n_vertices();
+    info[3] = h->s->n_levels(); info[4] = (double)h->s->dof() * (double)h->s->n_vertices();
     int64_t a = 0, b = 0, c = 0;
     h->s->plan().op_counts(&a, &b, &c);
     info[5] = (double)a; info[6] = (double)b; info[7] = (double)c;

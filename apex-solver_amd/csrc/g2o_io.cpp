@@ -5,7 +5,7 @@
 //   G2oLoader::load / parse_content / parse_line          crates/apex-io/src/g2o.rs:140-300
 //   parse_vertex_se3 (norm check |n-1| <= 0.01, normalise) :340-420
 //   parse_edge_se3 (21 upper-triangular information values) :488-620
-//   parse_vertex_se2 / parse_edge_se2 (validated, SE2 payload not kept: out of scope)  :303-337, 424-485
+//   parse_vertex_se2 / parse_edge_se2 (x y theta; 6 upper-triangular information values)  :303-337, 424-485
 //   variables "x{id}" sorted by id, column order = sorted names, first vertex fixed
 //                                                          bin/pose_graph_g2o.rs:748-797, 828-838
 #include "../../include/apexgpu.h"
@@ -31,6 +31,11 @@ struct apexgpu_g2o {
     std::vector<double> meas;       // 7 per edge
     std::vector<double> info;       // 36 per edge (row-major symmetric)
     int64_t n_se2_vertices = 0, n_se2_edges = 0;
+    std::vector<int64_t> ids2;      // SE2 vertex ids in file order
+    std::vector<double> poses2;     // 3 per vertex [x, y, theta]
+    std::vector<int64_t> e_from2, e_to2;
+    std::vector<double> meas2;      // 3 per edge
+    std::vector<double> info2;      // 9 per edge (row-major symmetric)
 };
 
 static thread_local std::string g_g2o_err;
@@ -220,28 +225,35 @@ static int g2o_open_impl(const char* path, apexgpu_g2o** out) {
             if (parts.size() < 5) { rc = missing_fields(line_no); break; }
             uint64_t id;
             if (!tok_usize(parts[1], id)) { rc = invalid_number(line_no, parts[1]); break; }
-            double d;
+            double d[3];
             for (int k = 2; k < 5 && rc == 0; ++k)
-                if (!tok_f64(parts[k], d)) rc = invalid_number(line_no, parts[k]);
+                if (!tok_f64(parts[k], d[k - 2])) rc = invalid_number(line_no, parts[k]);
             if (rc) break;
             if (!seen2.insert((int64_t)id).second) {
                 rc = g2o_fail(APEXGPU_G2O_ERR_DUPLICATE_VERTEX, "Duplicate vertex ID: " + std::to_string(id));
                 break;
             }
             g->n_se2_vertices++;
+            g->ids2.push_back((int64_t)id);
+            g->poses2.insert(g->poses2.end(), d, d + 3);
         } else if (tag == "EDGE_SE2") {
             if (parts.size() < 12) { rc = missing_fields(line_no); break; }
-            uint64_t id;
-            if (!tok_usize(parts[1], id)) { rc = invalid_number(line_no, parts[1]); break; }
-            if (!tok_usize(parts[2], id)) { rc = invalid_number(line_no, parts[2]); break; }
-            double d;
+            uint64_t from, to;
+            if (!tok_usize(parts[1], from)) { rc = invalid_number(line_no, parts[1]); break; }
+            if (!tok_usize(parts[2], to)) { rc = invalid_number(line_no, parts[2]); break; }
+            double d[3], iv[6];
             for (int k = 3; k < 6 && rc == 0; ++k)
-                if (!tok_f64(parts[k], d)) rc = invalid_number(line_no, parts[k]);
+                if (!tok_f64(parts[k], d[k - 3])) rc = invalid_number(line_no, parts[k]);
             for (int k = 6; k < 12 && rc == 0; ++k)
-                if (!tok_f64(parts[k], d))
+                if (!tok_f64(parts[k], iv[k - 6]))
                     rc = g2o_fail(APEXGPU_G2O_ERR_PARSE, "Parse error at line " + std::to_string(line_no) + ": Invalid information matrix values");
             if (rc) break;
             g->n_se2_edges++;
+            g->e_from2.push_back((int64_t)from);
+            g->e_to2.push_back((int64_t)to);
+            g->meas2.insert(g->meas2.end(), d, d + 3);
+            const double I[9] = {iv[0], iv[1], iv[2], iv[1], iv[3], iv[4], iv[2], iv[4], iv[5]};
+            g->info2.insert(g->info2.end(), I, I + 9);
         }
         // unknown tags are skipped silently (g2o.rs:268-270)
     }
@@ -309,15 +321,63 @@ int apexgpu_g2o_problem(const apexgpu_g2o* g, int64_t* sorted_ids, double* poses
     return 0;
 }
 
+int apexgpu_g2o_raw_se2(const apexgpu_g2o* g, int64_t* ids, double* poses3, int64_t* e_from, int64_t* e_to, double* meas3,
+                        double* info9) {
+    if (!g) return g2o_fail(APEXGPU_G2O_ERR_IO, "null handle");
+    if (ids) memcpy(ids, g->ids2.data(), g->ids2.size() * sizeof(int64_t));
+    if (poses3) memcpy(poses3, g->poses2.data(), g->poses2.size() * sizeof(double));
+    if (e_from) memcpy(e_from, g->e_from2.data(), g->e_from2.size() * sizeof(int64_t));
+    if (e_to) memcpy(e_to, g->e_to2.data(), g->e_to2.size() * sizeof(int64_t));
+    if (meas3) memcpy(meas3, g->meas2.data(), g->meas2.size() * sizeof(double));
+    if (info9) memcpy(info9, g->info2.data(), g->info2.size() * sizeof(double));
+    return 0;
+}
+
+/* The SE2 problem of bin/pose_graph_g2o.rs:366-437: as apexgpu_g2o_problem with three columns and three fixed DOF. */
+int apexgpu_g2o_problem_se2(const apexgpu_g2o* g, int64_t* sorted_ids, double* poses3, uint32_t* e_from, uint32_t* e_to,
+                            double* meas3, int64_t* pose_col, uint8_t* fix3) {
+    if (!g) return g2o_fail(APEXGPU_G2O_ERR_IO, "null handle");
+    const size_t nv = g->ids2.size(), ne = g->e_from2.size();
+    std::vector<size_t> order(nv);
+    for (size_t i = 0; i < nv; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return g->ids2[a] < g->ids2[b]; });
+    std::vector<int64_t> ids(nv);
+    for (size_t k = 0; k < nv; ++k) {
+        ids[k] = g->ids2[order[k]];
+        if (sorted_ids) sorted_ids[k] = ids[k];
+        if (poses3) memcpy(poses3 + 3 * k, g->poses2.data() + 3 * order[k], 3 * sizeof(double));
+    }
+    for (size_t e = 0; e < ne; ++e) {
+        const auto fa = std::lower_bound(ids.begin(), ids.end(), g->e_from2[e]);
+        const auto fb = std::lower_bound(ids.begin(), ids.end(), g->e_to2[e]);
+        if (fa == ids.end() || *fa != g->e_from2[e] || fb == ids.end() || *fb != g->e_to2[e])
+            return g2o_fail(APEXGPU_G2O_ERR_PARSE, "edge " + std::to_string(e) + " references a vertex that is not in the file");
+        if (e_from) e_from[e] = (uint32_t)(fa - ids.begin());
+        if (e_to) e_to[e] = (uint32_t)(fb - ids.begin());
+    }
+    if (meas3) memcpy(meas3, g->meas2.data(), g->meas2.size() * sizeof(double));
+    if (pose_col) {
+        const int rc = apexgpu_pose_graph_columns_se2((int64_t)nv, ids.data(), pose_col);
+        if (rc != 0) return rc;
+    }
+    if (fix3) {
+        memset(fix3, 0, 3 * nv);
+        if (nv > 0) memset(fix3, 1, 3);
+    }
+    return 0;
+}
+
 /* First global column of "x{id}" in the sorted-name order of src/optimizer/mod.rs:530-536
  * (names compare as strings: x0, x1, x10, x100, ..., x2, ...). */
-int apexgpu_pose_graph_columns(int64_t n_v, const int64_t* ids, int64_t* pose_col) {
+static int pose_graph_columns(int64_t n_v, const int64_t* ids, int64_t* pose_col, int dof) {
     if (n_v < 0 || (n_v > 0 && (!ids || !pose_col))) return g2o_fail(APEXGPU_G2O_ERR_PARSE, "bad arguments");
     std::vector<std::pair<std::string, int64_t>> names((size_t)n_v);
     for (int64_t v = 0; v < n_v; ++v) names[(size_t)v] = {"x" + std::to_string(ids[v]), v};
     std::sort(names.begin(), names.end());
-    for (int64_t r = 0; r < n_v; ++r) pose_col[names[(size_t)r].second] = 6 * r;
+    for (int64_t r = 0; r < n_v; ++r) pose_col[names[(size_t)r].second] = dof * r;
     return 0;
 }
+int apexgpu_pose_graph_columns(int64_t n_v, const int64_t* ids, int64_t* pose_col) { return pose_graph_columns(n_v, ids, pose_col, 6); }
+int apexgpu_pose_graph_columns_se2(int64_t n_v, const int64_t* ids, int64_t* pose_col) { return pose_graph_columns(n_v, ids, pose_col, 3); }
 
 }  // extern "C"

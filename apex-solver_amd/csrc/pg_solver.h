@@ -1,10 +1,16 @@
-// pg_solver.h -- host side of the MI355X SE3 pose-graph backend (BASELINE.json configs[1]).
+// pg_solver.h -- host side of the MI355X pose-graph backend (BASELINE.json configs[1]): SE3 and SE2 vertices.
 //
 // Mirrors SparseCholeskySolver (src/linalg/sparse/cholesky.rs:159-230) driven by the LM loop
 // (src/optimizer/levenberg_marquardt.rs:823-1031) on a problem of BetweenFactor<SE3> blocks
 // (src/factors/between_factor.rs:268-322) as bin/pose_graph_g2o.rs:748-830 builds it:
 // H = J^T J is assembled block-sparse (6x6 blocks) straight from the edges into 144x144 tiles,
 // H + lambda I is factorised by the level-scheduled tile Cholesky of TilePlan -- no Schur complement.
+//
+// One class, two manifolds.  The orchestration (speculative factor, one wait per iteration, eager step evaluation,
+// scaling, covariance, exports) does not care what a vertex is: it sees dof_ tangent columns and amb_ stored doubles per
+// vertex, kNB / dof_ vertices per tile.  Only prepare / assemble / priors / cost / retract / exports differ, and those go
+// through the enqueue_* members: SE3 -> pg_kernels.hip (6, 7, atomic edge scatter), SE2 -> pg2_kernels.hip (3, 3, the
+// row-owned assembly over the incident-edge lists of pg2_lists.h, which live with the SE2 structure only).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,17 +19,19 @@
 #include <vector>
 
 #include "lm_loop.h"
+#include "pg2_kernels.h"
 #include "pg_kernels.h"
 #include "stage_timer.h"
 #include "tile_plan.h"
 
 namespace apex {
 
+enum PgManifold { kManifoldSE3 = 0, kManifoldSE2 = 1 };
 enum PgStage { kPgAssemble = 0, kPgFactor, kPgTriSolve, kPgStats, kPgRetract, kPgCost, kPgNumStages };
 
 class PoseGraphSolver : public LmBackend {
    public:
-    PoseGraphSolver(int64_t n_v, int64_t n_e, int device);
+    PoseGraphSolver(int64_t n_v, int64_t n_e, int device, int manifold = kManifoldSE3);
     ~PoseGraphSolver() override;
 
     int set_structure(const uint32_t* e_from, const uint32_t* e_to, const double* meas7, const int64_t* pose_col,
@@ -81,6 +89,9 @@ class PoseGraphSolver : public LmBackend {
     void reset_stage_times() { timer_.reset(); }
     int stage_times(double* ms, int64_t* n) { return timer_.times(ms, n); }
     int64_t n_vertices() const { return n_v_; }
+    int manifold() const { return manifold_; }
+    int dof() const { return dof_; }           // tangent columns per vertex: 6 | 3
+    int ambient() const { return amb_; }       // stored doubles per vertex / measurement / prior: 7 | 3
     int n_tile_rows() const { return tp_.nt(); }
     int64_t tile_count() const { return tp_.n_slots(); }
     int64_t touched_tiles() const { return tp_.n_touched_slots(); }
@@ -92,12 +103,19 @@ class PoseGraphSolver : public LmBackend {
     int fail(int code, const std::string& msg) { err_ = msg; return code; }
     int check_hip(hipError_t e, const char* what);
     PGView view(int which) const;
+    PG2View view2(int which) const;
+    // the manifold-specific launches
+    void enqueue_prepare(int which);
+    void enqueue_assemble_blocks();
+    void enqueue_cost(int which, double* sumsq_out);
+    void enqueue_retract(int from, double sign, int to);
     int assemble(double lambda);
     int ensure_scale_buffer();
     int cost_of(int which, double* out);
 
     int64_t n_v_, n_e_;
     int device_;
+    int manifold_, dof_, amb_, stride_, vpt_;   // vpt_: vertices per tile = kNB / dof_
     int64_t n_ = 0, n_pad_ = 0;
     double huber_delta_ = 0.0;
     bool have_structure_ = false, have_params_ = false, have_step_ = false, have_trial_ = false;
@@ -119,6 +137,8 @@ class PoseGraphSolver : public LmBackend {
     int64_t step_serial_ = 0, eager_serial_ = -1;
     double* eager_host_ = nullptr;   // pinned: [0..2] step statistics, [3] sum of squares at the trial point
     uint32_t* prior_v_ = nullptr;
+    int *inc_ptr_ = nullptr, *prior_slot_ = nullptr;   // SE2 only: incident-edge CSR, the caller's index of each sorted prior
+    uint32_t* inc_edge_ = nullptr;
     double* prior_data_ = nullptr;
     double* prior_res_ = nullptr;   // staging of get_prior_residual
     double* meas_ = nullptr;

@@ -7,6 +7,8 @@
 #include <algorithm>
 #include <numeric>
 
+#include "pg2_device.hpp"
+#include "pg2_lists.h"
 #include "pg_device.hpp"
 
 namespace apex {
@@ -35,13 +37,16 @@ static hipError_t alloc_zero(double** p, size_t n) {
     return hipMemset(*p, 0, std::max<size_t>(n, 1) * sizeof(double));
 }
 
-PoseGraphSolver::PoseGraphSolver(int64_t n_v, int64_t n_e, int device) : n_v_(n_v), n_e_(n_e), device_(device) {}
+PoseGraphSolver::PoseGraphSolver(int64_t n_v, int64_t n_e, int device, int manifold)
+    : n_v_(n_v), n_e_(n_e), device_(device), manifold_(manifold == kManifoldSE2 ? kManifoldSE2 : kManifoldSE3),
+      dof_(manifold_ == kManifoldSE2 ? 3 : 6), amb_(manifold_ == kManifoldSE2 ? 3 : 7),
+      stride_(manifold_ == kManifoldSE2 ? kPose2Stride : kPoseStride), vpt_(kNB / dof_) {}
 
 PoseGraphSolver::~PoseGraphSolver() {
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (eager_host_) (void)hipHostFree(eager_host_);
-    void* ptrs[] = {poses_[0], poses_[1], posep_[0], posep_[1], e_from_, e_to_, meas_, fix_, g_, rhs_, d_, work_, partial_, scal_, scale_, prior_v_, prior_data_, prior_res_};
+    void* ptrs[] = {poses_[0], poses_[1], posep_[0], posep_[1], e_from_, e_to_, meas_, fix_, g_, rhs_, d_, work_, partial_, scal_, scale_, prior_v_, prior_data_, prior_res_, inc_ptr_, inc_edge_, prior_slot_};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (stream_) (void)hipStreamDestroy(stream_);
@@ -61,6 +66,40 @@ PGView PoseGraphSolver::view(int which) const {
     return v;
 }
 
+PG2View PoseGraphSolver::view2(int which) const {
+    PG2View v;
+    v.n_v = n_v_; v.n_e = n_e_;
+    v.poses = poses_[which]; v.posep = posep_[which]; v.e_from = e_from_; v.e_to = e_to_; v.meas = meas_;
+    v.huber_delta = huber_delta_;
+    v.inc_ptr = inc_ptr_; v.inc_edge = inc_edge_;
+    v.n_prior = n_prior_; v.prior_v = prior_v_; v.prior_data = prior_data_; v.prior_slot = prior_slot_;
+    return v;
+}
+
+// ---- the manifold-specific launches ----------------------------------------------------------------
+void PoseGraphSolver::enqueue_prepare(int which) {
+    if (manifold_ == kManifoldSE2) launch_pg2_prepare(n_v_, poses_[which], posep_[which], stream_);
+    else launch_pg_prepare(n_v_, poses_[which], posep_[which], stream_);
+}
+void PoseGraphSolver::enqueue_assemble_blocks() {
+    if (manifold_ == kManifoldSE2) {
+        launch_pg2_assemble(view2(cur_), tp_.tilemap(), g_, stream_);
+        launch_pg2_priors(view2(cur_), tp_.tilemap(), g_, stream_);
+    } else {
+        launch_pg_edges(view(cur_), tp_.tilemap(), g_, stream_);
+        launch_pg_priors(view(cur_), tp_.tilemap(), g_, stream_);
+    }
+}
+void PoseGraphSolver::enqueue_cost(int which, double* sumsq_out) {
+    if (manifold_ == kManifoldSE2) launch_pg2_cost(view2(which), partial_, n_partial_, sumsq_out, stream_);
+    else launch_pg_cost(view(which), partial_, n_partial_, sumsq_out, stream_);
+}
+void PoseGraphSolver::enqueue_retract(int from, double sign, int to) {
+    if (manifold_ == kManifoldSE2) launch_pg2_retract(n_v_, poses_[from], d_, sign, fix_, poses_[to], stream_);
+    else launch_pg_retract(n_v_, poses_[from], d_, sign, fix_, poses_[to], stream_);
+    enqueue_prepare(to);
+}
+
 // PriorFactor blocks (prior_factor.rs:96-108); replaces the set.  data7 in to_vector order [t, w, i, j, k].
 int PoseGraphSolver::set_priors(int64_t n, const uint32_t* vertex, const double* data7, const double* huber_delta) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
@@ -72,16 +111,25 @@ int PoseGraphSolver::set_priors(int64_t n, const uint32_t* vertex, const double*
     if (prior_v_) { (void)hipFree(prior_v_); prior_v_ = nullptr; }
     if (prior_data_) { (void)hipFree(prior_data_); prior_data_ = nullptr; }
     if (prior_res_) { (void)hipFree(prior_res_); prior_res_ = nullptr; }
+    if (prior_slot_) { (void)hipFree(prior_slot_); prior_slot_ = nullptr; }
     n_prior_ = (int)n;
     have_step_ = have_trial_ = false;
     if (n == 0) return kOk;
     std::vector<uint32_t> hv((size_t)n);
-    std::vector<double> hd((size_t)n * kPoseStride, 0.0);
+    std::vector<double> hd((size_t)n * stride_, 0.0);
+    // SE2: the blocks go to the device sorted by vertex (stable), so that one lane sums the run of a vertex in a fixed
+    // order (k_pg2_priors); prior_slot_ keeps the caller's index for the export.  SE3: the caller's order, as ever.
+    std::vector<int> order((size_t)n);
+    std::iota(order.begin(), order.end(), 0);
+    if (manifold_ == kManifoldSE2)
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return vmap_[vertex[a]] < vmap_[vertex[b]]; });
     for (int64_t k = 0; k < n; ++k) {
-        hv[k] = (uint32_t)vmap_[vertex[k]];
-        memcpy(hd.data() + (size_t)k * kPoseStride, data7 + 7 * k, 7 * sizeof(double));
-        hd[(size_t)k * kPoseStride + 7] = huber_delta ? huber_delta[k] : -1.0;
+        const int src = order[k];
+        hv[k] = (uint32_t)vmap_[vertex[src]];
+        memcpy(hd.data() + (size_t)k * stride_, data7 + (size_t)amb_ * src, amb_ * sizeof(double));
+        hd[(size_t)k * stride_ + amb_] = huber_delta ? huber_delta[src] : -1.0;
     }
+    if (manifold_ == kManifoldSE2) HIP_TRY(upload(&prior_slot_, order));
     HIP_TRY(hipMalloc(&prior_v_, hv.size() * sizeof(uint32_t)));
     HIP_TRY(hipMalloc(&prior_data_, hd.size() * sizeof(double)));
     HIP_TRY(hipMemcpy(prior_v_, hv.data(), hv.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -93,9 +141,10 @@ int PoseGraphSolver::get_prior_residual(double* r7_out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     if (n_prior_ == 0) return kOk;
     HIP_TRY(hipSetDevice(device_));
-    if (!prior_res_) HIP_TRY(hipMalloc(&prior_res_, (size_t)n_prior_ * 7 * sizeof(double)));   // kept with the priors (set_priors frees it)
-    launch_pg_prior_export(view(cur_), prior_res_, stream_);
-    HIP_TRY(hipMemcpyAsync(r7_out, prior_res_, (size_t)n_prior_ * 7 * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    if (!prior_res_) HIP_TRY(hipMalloc(&prior_res_, (size_t)n_prior_ * amb_ * sizeof(double)));   // kept with the priors (set_priors frees it)
+    if (manifold_ == kManifoldSE2) launch_pg2_prior_export(view2(cur_), prior_res_, stream_);
+    else launch_pg_prior_export(view(cur_), prior_res_, stream_);
+    HIP_TRY(hipMemcpyAsync(r7_out, prior_res_, (size_t)n_prior_ * amb_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     return kOk;
 }
@@ -111,26 +160,26 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
     if (!stream_) HIP_TRY(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     huber_delta_ = huber_delta;
     pose_col_.assign(pose_col, pose_col + n_v_);
-    n_ = 6 * n_v_;
+    n_ = dof_ * n_v_;
     const int nt = (int)((n_ + kNB - 1) / kNB);
     n_pad_ = (int64_t)nt * kNB;
 
-    // ---- internal vertex order: whole tiles of 24 consecutive vertices, permuted by a nested-dissection
+    // ---- internal vertex order: whole tiles of kNB / dof consecutive vertices, permuted by a nested-dissection
     // ordering of the tile graph (see TilePlan::order) -----------------------------------------------
     std::vector<uint8_t> adjm((size_t)nt * nt, 0);
     for (int64_t e = 0; e < n_e_; ++e) {
-        const int a = (int)(e_from[e] / kVertsPerTile), b = (int)(e_to[e] / kVertsPerTile);
+        const int a = (int)(e_from[e] / vpt_), b = (int)(e_to[e] / vpt_);
         if (a != b) { adjm[(size_t)a * nt + b] = 1; adjm[(size_t)b * nt + a] = 1; }
     }
     const std::vector<int> tperm = TilePlan::order(nt, adjm, use_nd_, nd_leaf_);
     vmap_.resize(n_v_);
-    for (int64_t v = 0; v < n_v_; ++v) vmap_[v] = (int)((int64_t)tperm[v / kVertsPerTile] * kVertsPerTile + v % kVertsPerTile);
+    for (int64_t v = 0; v < n_v_; ++v) vmap_[v] = (int)((int64_t)tperm[v / vpt_] * vpt_ + v % vpt_);
     std::vector<uint8_t> present((size_t)nt * nt, 0);
     for (int I = 0; I < nt; ++I) present[(size_t)I * nt + I] = 1;
     std::vector<uint32_t> ef(n_e_), et(n_e_);
     for (int64_t e = 0; e < n_e_; ++e) {
         ef[e] = (uint32_t)vmap_[e_from[e]]; et[e] = (uint32_t)vmap_[e_to[e]];
-        int a = (int)(ef[e] / kVertsPerTile), b = (int)(et[e] / kVertsPerTile);
+        int a = (int)(ef[e] / vpt_), b = (int)(et[e] / vpt_);
         if (a < b) std::swap(a, b);
         present[(size_t)a * nt + b] = 1;
     }
@@ -139,23 +188,33 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
         if (!err.empty()) return fail(kInvalidInput, "Hessian tiles: " + err);
     }
     // measurements are constants: normalise once (SE3::from_translation_quaternion, se3.rs:107-113)
-    std::vector<double> mp((size_t)n_e_ * kPoseStride, 0.0);
-    for (int64_t e = 0; e < n_e_; ++e) pose_normalise(meas7 + 7 * e, mp.data() + kPoseStride * e);
-    std::vector<uint8_t> fx((size_t)6 * n_v_, 0);
+    // (SE2: BetweenFactor::new keeps SE2::from_xy_angle of the measurement, se2.rs:106-110)
+    std::vector<double> mp((size_t)n_e_ * stride_, 0.0);
+    for (int64_t e = 0; e < n_e_; ++e) {
+        if (manifold_ == kManifoldSE2) se2_prepare(meas7 + 3 * e, mp.data() + (size_t)stride_ * e);
+        else pose_normalise(meas7 + 7 * e, mp.data() + (size_t)stride_ * e);
+    }
+    std::vector<uint8_t> fx((size_t)dof_ * n_v_, 0);
     if (fix6)
-        for (int64_t v = 0; v < n_v_; ++v) memcpy(fx.data() + 6 * (size_t)vmap_[v], fix6 + 6 * v, 6);
+        for (int64_t v = 0; v < n_v_; ++v) memcpy(fx.data() + dof_ * (size_t)vmap_[v], fix6 + (size_t)dof_ * v, dof_);
+    if (manifold_ == kManifoldSE2) {   // the row-owned assembly walks each vertex's incident edges
+        IncidentLists inc;
+        if (!build_incident_lists(n_v_, n_e_, ef.data(), et.data(), &inc)) return fail(kInvalidInput, "incident-edge lists: out of range");
+        HIP_TRY(upload(&inc_ptr_, inc.ptr));
+        HIP_TRY(upload(&inc_edge_, inc.edge));
+    }
     HIP_TRY(upload(&e_from_, ef));
     HIP_TRY(upload(&e_to_, et));
     HIP_TRY(upload(&meas_, mp));
     HIP_TRY(upload(&fix_, fx));
     for (int w = 0; w < 2; ++w) {
-        HIP_TRY(alloc_zero(&poses_[w], 7 * (size_t)n_v_));
-        HIP_TRY(alloc_zero(&posep_[w], kPoseStride * (size_t)n_v_));
+        HIP_TRY(alloc_zero(&poses_[w], amb_ * (size_t)n_v_));
+        HIP_TRY(alloc_zero(&posep_[w], stride_ * (size_t)n_v_));
     }
     HIP_TRY(alloc_zero(&g_, n_pad_));
     HIP_TRY(alloc_zero(&rhs_, n_pad_));
     HIP_TRY(alloc_zero(&d_, n_pad_));
-    HIP_TRY(alloc_zero(&work_, 6 * (size_t)n_pad_));
+    HIP_TRY(alloc_zero(&work_, 6 * (size_t)n_pad_));   // (TilePlan::solve workspace)
     HIP_TRY(alloc_zero(&partial_, 3 * (size_t)n_partial_));
     HIP_TRY(alloc_zero(&scal_, 16));
     HIP_TRY(hipDeviceSynchronize());
@@ -168,10 +227,12 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
 int PoseGraphSolver::set_params(const double* poses7) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
     HIP_TRY(hipSetDevice(device_));
-    std::vector<double> hp(7 * (size_t)n_v_);
-    for (int64_t v = 0; v < n_v_; ++v) memcpy(hp.data() + 7 * (size_t)vmap_[v], poses7 + 7 * v, 7 * sizeof(double));
+    std::vector<double> hp(amb_ * (size_t)n_v_);
+    for (int64_t v = 0; v < n_v_; ++v) memcpy(hp.data() + amb_ * (size_t)vmap_[v], poses7 + (size_t)amb_ * v, amb_ * sizeof(double));
+    if (manifold_ == kManifoldSE2)   // the variable is held as SE2 -> DVector gives it: theta in (-pi, pi] (se2.rs:55-63)
+        for (int64_t v = 0; v < n_v_; ++v) hp[3 * (size_t)v + 2] = se2_wrap_angle(hp[3 * (size_t)v + 2]);
     HIP_TRY(hipMemcpyAsync(poses_[cur_], hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
-    launch_pg_prepare(n_v_, poses_[cur_], posep_[cur_], stream_);
+    enqueue_prepare(cur_);
     HIP_TRY(hipStreamSynchronize(stream_));
     have_params_ = true; have_step_ = have_trial_ = false;
     return kOk;
@@ -180,16 +241,16 @@ int PoseGraphSolver::set_params(const double* poses7) {
 int PoseGraphSolver::get_params(double* poses7) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    std::vector<double> hp(7 * (size_t)n_v_);
+    std::vector<double> hp(amb_ * (size_t)n_v_);
     HIP_TRY(hipMemcpyAsync(hp.data(), poses_[cur_], hp.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    for (int64_t v = 0; v < n_v_; ++v) memcpy(poses7 + 7 * v, hp.data() + 7 * (size_t)vmap_[v], 7 * sizeof(double));
+    for (int64_t v = 0; v < n_v_; ++v) memcpy(poses7 + (size_t)amb_ * v, hp.data() + amb_ * (size_t)vmap_[v], amb_ * sizeof(double));
     return kOk;
 }
 
 int PoseGraphSolver::cost_of(int which, double* out) {
     timer_.begin(kPgCost, stream_);
-    launch_pg_cost(view(which), partial_, n_partial_, scal_, stream_);
+    enqueue_cost(which, scal_);
     timer_.end(kPgCost, stream_);
     double ss = 0.0;
     HIP_TRY(hipMemcpyAsync(&ss, scal_, sizeof(double), hipMemcpyDeviceToHost, stream_));
@@ -211,8 +272,7 @@ int PoseGraphSolver::assemble(double lambda) {
     HIP_TRY(tp_.zero_tiles());
     HIP_TRY(hipMemsetAsync(g_, 0, n_pad_ * sizeof(double), stream_));
     tp_.add_diag((int)n_, scaled_ ? 0.0 : lambda, 1.0);  // lambda on the real rows, identity on the padding rows
-    launch_pg_edges(view(cur_), tp_.tilemap(), g_, stream_);
-    launch_pg_priors(view(cur_), tp_.tilemap(), g_, stream_);
+    enqueue_assemble_blocks();
     if (scaled_) {  // Jacobi scaling: H := D H D, then the damping of the scaled system
         tp_.scale_sym(scale_);
         tp_.add_diag((int)n_, lambda, 1.0);
@@ -280,7 +340,7 @@ int PoseGraphSolver::solve_augmented(double lambda, int variant, double* step_ou
                 if (scaled_)  // the caller's variables are the scaled ones: y = step / s, gradient = s g
                     for (int64_t i = 0; i < n_; ++i) h[i] = pass == 0 ? h[i] / scale_h_[i] : h[i] * scale_h_[i];
                 for (int64_t v = 0; v < n_v_; ++v)
-                    for (int a = 0; a < 6; ++a) out[pose_col_[v] + a] = h[6 * (size_t)vmap_[v] + a];
+                    for (int a = 0; a < dof_; ++a) out[pose_col_[v] + a] = h[dof_ * (size_t)vmap_[v] + a];
             }
         } else {
             HIP_TRY(hipStreamSynchronize(stream_));
@@ -319,11 +379,10 @@ void PoseGraphSolver::enqueue_step_stats() {
 void PoseGraphSolver::enqueue_trial_point(double* sumsq_out) {
     const int t = cur_ ^ 1;
     timer_.begin(kPgRetract, stream_);
-    launch_pg_retract(n_v_, poses_[cur_], d_, 1.0, fix_, poses_[t], stream_);
-    launch_pg_prepare(n_v_, poses_[t], posep_[t], stream_);
+    enqueue_retract(cur_, 1.0, t);
     timer_.end(kPgRetract, stream_);
     timer_.begin(kPgCost, stream_);
-    launch_pg_cost(view(t), partial_, n_partial_, sumsq_out, stream_);
+    enqueue_cost(t, sumsq_out);
     timer_.end(kPgCost, stream_);
 }
 
@@ -355,8 +414,7 @@ int PoseGraphSolver::eval_step(double* trial_cost) {
     HIP_TRY(hipSetDevice(device_));
     const int t = cur_ ^ 1;
     timer_.begin(kPgRetract, stream_);
-    launch_pg_retract(n_v_, poses_[cur_], d_, 1.0, fix_, poses_[t], stream_);
-    launch_pg_prepare(n_v_, poses_[t], posep_[t], stream_);
+    enqueue_retract(cur_, 1.0, t);
     timer_.end(kPgRetract, stream_);
     have_trial_ = true;
     return cost_of(t, trial_cost);
@@ -375,8 +433,7 @@ int PoseGraphSolver::discard_step() {
     HIP_TRY(hipSetDevice(device_));
     const int t = cur_ ^ 1;
     timer_.begin(kPgRetract, stream_);
-    launch_pg_retract(n_v_, poses_[t], d_, -1.0, fix_, poses_[cur_], stream_);
-    launch_pg_prepare(n_v_, poses_[cur_], posep_[cur_], stream_);
+    enqueue_retract(t, -1.0, cur_);
     timer_.end(kPgRetract, stream_);
     HIP_TRY(hipStreamSynchronize(stream_));
     have_trial_ = false; have_step_ = false;
@@ -386,7 +443,7 @@ int PoseGraphSolver::discard_step() {
 int PoseGraphSolver::parameter_norm(double* out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    launch_sumsq(7 * n_v_, poses_[cur_], partial_, n_partial_, scal_ + 4, stream_);
+    launch_sumsq(amb_ * n_v_, poses_[cur_], partial_, n_partial_, scal_ + 4, stream_);
     double h = 0.0;
     HIP_TRY(hipMemcpyAsync(&h, scal_ + 4, sizeof h, hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
@@ -419,7 +476,7 @@ int PoseGraphSolver::column_norms(double* norms_out) {
     HIP_TRY(hipMemcpyAsync(h.data(), work_, n_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     for (int64_t v = 0; v < n_v_; ++v)
-        for (int a = 0; a < 6; ++a) norms_out[pose_col_[v] + a] = sqrt(h[6 * (size_t)vmap_[v] + a]);
+        for (int a = 0; a < dof_; ++a) norms_out[pose_col_[v] + a] = sqrt(h[dof_ * (size_t)vmap_[v] + a]);
     return kOk;
 }
 
@@ -432,7 +489,7 @@ int PoseGraphSolver::set_column_scaling(const double* scaling) {
     if (rc != kOk) return rc;
     scale_h_.assign(n_, 1.0);
     for (int64_t v = 0; v < n_v_; ++v)
-        for (int a = 0; a < 6; ++a) scale_h_[6 * (size_t)vmap_[v] + a] = scaling[pose_col_[v] + a];
+        for (int a = 0; a < dof_; ++a) scale_h_[dof_ * (size_t)vmap_[v] + a] = scaling[pose_col_[v] + a];
     for (double v : scale_h_) if (!(v > 0.0) || !std::isfinite(v)) return fail(kInvalidInput, "column scaling must be positive and finite");
     HIP_TRY(hipMemcpyAsync(scale_, scale_h_.data(), n_ * sizeof(double), hipMemcpyHostToDevice, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
@@ -468,9 +525,10 @@ int PoseGraphSolver::get_residual(double* r_out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
     double* d = nullptr;
-    HIP_TRY(dev_alloc(&d, 6 * (size_t)n_e_));
-    launch_pg_export(view(cur_), d, nullptr, stream_);
-    hipError_t e = hipMemcpyAsync(r_out, d, 6 * n_e_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
+    HIP_TRY(dev_alloc(&d, dof_ * (size_t)n_e_));
+    if (manifold_ == kManifoldSE2) launch_pg2_export(view2(cur_), d, nullptr, stream_);
+    else launch_pg_export(view(cur_), d, nullptr, stream_);
+    hipError_t e = hipMemcpyAsync(r_out, d, dof_ * n_e_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     (void)hipStreamSynchronize(stream_);
     (void)hipFree(d);
     return check_hip(e, "get_residual");
@@ -480,9 +538,11 @@ int PoseGraphSolver::get_jacobian_blocks(double* j_out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
     double* d = nullptr;
-    HIP_TRY(dev_alloc(&d, 72 * (size_t)n_e_));
-    launch_pg_export(view(cur_), nullptr, d, stream_);
-    hipError_t e = hipMemcpyAsync(j_out, d, 72 * n_e_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
+    const size_t jn = 2 * (size_t)dof_ * dof_;   // [dof][2 dof] per edge
+    HIP_TRY(dev_alloc(&d, jn * (size_t)n_e_));
+    if (manifold_ == kManifoldSE2) launch_pg2_export(view2(cur_), nullptr, d, stream_);
+    else launch_pg_export(view(cur_), nullptr, d, stream_);
+    hipError_t e = hipMemcpyAsync(j_out, d, jn * n_e_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     (void)hipStreamSynchronize(stream_);
     (void)hipFree(d);
     return check_hip(e, "get_jacobian_blocks");
@@ -497,7 +557,7 @@ int PoseGraphSolver::get_hessian(double lambda, double* H_out, double* g_out) {
     const size_t tile_elems = (size_t)kNB * kNB;
     std::vector<int64_t> col(n_, -1);
     for (int64_t v = 0; v < n_v_; ++v)
-        for (int a = 0; a < 6; ++a) col[6 * (size_t)vmap_[v] + a] = pose_col_[v] + a;
+        for (int a = 0; a < dof_; ++a) col[dof_ * (size_t)vmap_[v] + a] = pose_col_[v] + a;
     if (g_out) {
         std::vector<double> h(n_);
         HIP_TRY(hipMemcpyAsync(h.data(), g_, n_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
@@ -532,9 +592,9 @@ int PoseGraphSolver::covariance(double* out) {
     if (!out) return fail(kInvalidInput, "cov_out is NULL");
     HIP_TRY(hipSetDevice(device_));
     std::vector<int64_t> pos(n_v_);
-    for (int64_t v = 0; v < n_v_; ++v) pos[v] = 6 * (int64_t)vmap_[v];
+    for (int64_t v = 0; v < n_v_; ++v) pos[v] = dof_ * (int64_t)vmap_[v];
     std::string err;
-    const int rc = tp_.covariance_blocks(pos.data(), n_v_, 6, out, &err);
+    const int rc = tp_.covariance_blocks(pos.data(), n_v_, dof_, out, &err);
     if (rc == 1) return fail(kInvalidState, "covariance: " + err);
     if (rc != 0) return fail(kDeviceError, "covariance: " + err);
     return kOk;

@@ -5,6 +5,7 @@ The reference keeps its datasets where its downloader puts them (crates/apex-io/
 
     data/bundle_adjustment/{name}/problem-{cameras}-{points}-pre.txt      (BAL, bz2 archives unpacked by the downloader)
     data/odometry/3d/{file}.g2o                                           (e.g. sphere2500.g2o)
+    data/odometry/2d/{file}.g2o                                           (M3500, intel, mit, ring: SE2)
 
 `load_named` / `load_pose_graph` look there first (relative to $APEX_DATA_ROOT, the working directory, then the repository
 root), read what they find through the library's own readers (apexgpu_bal_open / apexgpu_g2o_open: csrc/bal_io.cpp,
@@ -27,7 +28,12 @@ BAL_FILES = {
     "venice-1778": ("venice", 1778, 993923),
     "final-13682": ("final", 13682, 4456117),
 }
-G2O_FILES = {"sphere2500": ("3d", "sphere2500.g2o")}
+G2O_FILES = {"sphere2500": ("3d", "sphere2500.g2o"),
+             # the reference's se2_datasets (bin/pose_graph_g2o.rs:1108, ODOMETRY_DATA_DIR_2D)
+             "M3500": ("2d", "M3500.g2o"), "intel": ("2d", "intel.g2o"), "mit": ("2d", "mit.g2o"), "ring": ("2d", "ring.g2o")}
+# vertex counts the synthetic stand-ins of the 2D files are generated with (M3500: 3,500; intel: 1,228 as
+# tests/integration_tests.rs:298-307 states; mit and ring: small graphs)
+_SE2_SYNTHETIC_SIZE = {"M3500": 3500, "intel": 1228, "mit": 808, "ring": 434}
 
 _REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -95,4 +101,6 @@ def load_pose_graph(shape: str, rings: int = 50, per_ring: int = 50):
         from .pose_graph import G2oLoader
 
         return G2oLoader.load(p).to_problem_data(name=shape), "real", p
+    if shape in G2O_FILES and G2O_FILES[shape][0] == "2d":
+        return synthetic.make_manhattan(_SE2_SYNTHETIC_SIZE[shape]), "synthetic", None
     return synthetic.make_sphere(rings, per_ring), "synthetic", None

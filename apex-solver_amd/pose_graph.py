@@ -1,8 +1,11 @@
-"""SE3 pose-graph path (BASELINE.json configs[1]): Python mirror of what bin/pose_graph_g2o.rs drives --
+"""Pose-graph path, SE3 and SE2 (BASELINE.json configs[1]): Python mirror of what bin/pose_graph_g2o.rs drives --
 `G2oLoader` (crates/apex-io/src/g2o.rs) over the library's C++ reader, the `Problem` of BetweenFactor<SE3>
 blocks with the first vertex fixed, and the `SparseCholesky` linear solver on the device
 (`GpuSparseCholeskySolver`, src/linalg/sparse/cholesky.rs:159-230).  Every numeric path calls
-libapexgpu.so; there is no CPU fallback."""
+libapexgpu.so; there is no CPU fallback.
+
+SE2 (the 2D half of bin/pose_graph_g2o.rs, :314-700): the same classes on 3-wide data -- pose / measurement / prior data
+= [x, y, theta], three tangent columns per vertex.  The manifold is picked from the width of `data.poses`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -39,6 +42,15 @@ class G2oGraph:
     n_vertices_se2: int = 0
     n_edges_se2: int = 0
     _problem: PoseGraphData | None = field(default=None, repr=False)
+    # the SE2 content (VertexSE2 / EdgeSE2, crates/apex-io/src/lib.rs), file order
+    vertex_ids_se2: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int64))
+    poses_se2: np.ndarray = field(default_factory=lambda: np.zeros((0, 3)))          # (n, 3) [x, y, theta]
+    edge_from_se2: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int64))
+    edge_to_se2: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int64))
+    edge_meas_se2: np.ndarray = field(default_factory=lambda: np.zeros((0, 3)))
+    edge_info_se2: np.ndarray = field(default_factory=lambda: np.zeros((0, 3, 3)))
+    _problem_se2: PoseGraphData | None = field(default=None, repr=False)
+    _problem_se2_error: tuple | None = field(default=None, repr=False)   # (code, message) the SE2 problem builder answered
 
     def vertex_count(self) -> int:
         return int(self.vertex_ids.shape[0]) + self.n_vertices_se2
@@ -46,9 +58,18 @@ class G2oGraph:
     def edge_count(self) -> int:
         return int(self.edge_from.shape[0]) + self.n_edges_se2
 
-    def to_problem_data(self, name: str = "g2o") -> PoseGraphData:
-        assert self._problem is not None
-        p = self._problem
+    def to_problem_data(self, name: str = "g2o", manifold: str | None = None) -> PoseGraphData:
+        """manifold "se3" | "se2"; None: "se2" for a file with SE2 content only, else "se3"."""
+        if manifold is None:
+            manifold = "se2" if (self.vertex_ids.shape[0] == 0 and self.n_vertices_se2 > 0) else "se3"
+        if manifold not in ("se3", "se2"):
+            raise ValueError(manifold)
+        if manifold == "se2" and self._problem_se2_error is not None:
+            # (e.g. an EDGE_SE2 that names a vertex the file does not hold: the file still loads, as it did when SE2 lines
+            # were only counted; the error belongs to whoever asks for the SE2 problem)
+            raise G2oError(*self._problem_se2_error)
+        p = self._problem_se2 if manifold == "se2" else self._problem
+        assert p is not None
         return PoseGraphData(ids=p.ids.copy(), poses=p.poses.copy(), e_from=p.e_from.copy(), e_to=p.e_to.copy(),
                              meas=p.meas.copy(), name=name)
 
@@ -74,7 +95,16 @@ class G2oLoader:
             if rc != 0:
                 raise G2oError(rc, L.apexgpu_g2o_last_error().decode())
             prob = PoseGraphData(ids=sid, poses=sp, e_from=pf, e_to=pt, meas=pm)
-            return G2oGraph(ids, poses, ef, et, meas, info, nv2.value, ne2.value, prob)
+            nv2, ne2 = nv2.value, ne2.value
+            ids2 = np.zeros(nv2, np.int64); poses2 = np.zeros((nv2, 3)); ef2 = np.zeros(ne2, np.int64); et2 = np.zeros(ne2, np.int64)
+            meas2 = np.zeros((ne2, 3)); info2 = np.zeros((ne2, 3, 3))
+            L.apexgpu_g2o_raw_se2(h, capi.ptr(ids2), capi.ptr(poses2), capi.ptr(ef2), capi.ptr(et2), capi.ptr(meas2), capi.ptr(info2))
+            sid2 = np.zeros(nv2, np.int64); sp2 = np.zeros((nv2, 3)); pf2 = np.zeros(ne2, np.uint32); pt2 = np.zeros(ne2, np.uint32)
+            pm2 = np.zeros((ne2, 3))
+            rc = L.apexgpu_g2o_problem_se2(h, capi.ptr(sid2), capi.ptr(sp2), capi.ptr(pf2), capi.ptr(pt2), capi.ptr(pm2), None, None)
+            err2 = (rc, L.apexgpu_g2o_last_error().decode()) if rc != 0 else None
+            prob2 = None if err2 else PoseGraphData(ids=sid2, poses=sp2, e_from=pf2, e_to=pt2, meas=pm2)
+            return G2oGraph(ids, poses, ef, et, meas, info, nv2, ne2, prob, ids2, poses2, ef2, et2, meas2, info2, prob2, err2)
         finally:
             L.apexgpu_g2o_close(h)
 
@@ -84,6 +114,18 @@ def write_g2o(path, data: PoseGraphData, information: np.ndarray | None = None):
     21 upper-triangular information values per edge (identity unless given)."""
     def fmt(x):
         return f"{float(x):.17e}"
+    if data.poses.shape[1] == 3:   # SE2: VERTEX_SE2 id x y theta, EDGE_SE2 from to dx dy dtheta + 6 upper-triangular values
+        with open(path, "w") as f:
+            f.write("# G2O file written by Apex Solver\n")
+            f.write(f"# SE2 vertices: {data.n_v}, SE3 vertices: 0, SE2 edges: {data.n_e}, SE3 edges: 0\n\n")
+            for k in np.argsort(data.ids, kind="stable"):
+                f.write("VERTEX_SE2 %d %s\n" % (data.ids[k], " ".join(fmt(v) for v in data.poses[k])))
+            for e in range(data.n_e):
+                I = np.eye(3) if information is None else information[e]
+                iu = [I[i, j] for i in range(3) for j in range(i, 3)]
+                f.write("EDGE_SE2 %d %d %s %s\n" % (data.ids[data.e_from[e]], data.ids[data.e_to[e]],
+                        " ".join(fmt(v) for v in data.meas[e]), " ".join(fmt(v) for v in iu)))
+        return
     with open(path, "w") as f:
         f.write("# G2O file written by Apex Solver\n")
         f.write(f"# SE2 vertices: 0, SE3 vertices: {data.n_v}, SE2 edges: 0, SE3 edges: {data.n_e}\n\n")
@@ -99,12 +141,13 @@ def write_g2o(path, data: PoseGraphData, information: np.ndarray | None = None):
                     " ".join(fmt(v) for v in (m[0], m[1], m[2], m[4], m[5], m[6], m[3])), " ".join(fmt(v) for v in iu)))
 
 
-def pose_graph_columns(ids: np.ndarray) -> np.ndarray:
-    """First global column of `x{id}` in sorted-name order (src/optimizer/mod.rs:530-536)."""
+def pose_graph_columns(ids: np.ndarray, dof: int = 6) -> np.ndarray:
+    """First global column of `x{id}` in sorted-name order (src/optimizer/mod.rs:530-536); dof 6 (SE3) | 3 (SE2)."""
     L = capi.load()
     ids = np.ascontiguousarray(ids, dtype=np.int64)
     out = np.zeros(ids.shape[0], np.int64)
-    rc = L.apexgpu_pose_graph_columns(ids.shape[0], capi.ptr(ids), capi.ptr(out))
+    fn = L.apexgpu_pose_graph_columns_se2 if dof == 3 else L.apexgpu_pose_graph_columns
+    rc = fn(ids.shape[0], capi.ptr(ids), capi.ptr(out))
     if rc != 0:
         raise G2oError(rc, L.apexgpu_g2o_last_error().decode())
     return out
@@ -120,6 +163,15 @@ def se3_as_vector(pose7) -> np.ndarray:
     return p
 
 
+def se2_as_vector(pose3) -> np.ndarray:
+    """SE2::from(DVector) -> DVector: [x, y, theta] with theta = atan2(sin, cos) (se2.rs:48-63); a theta already in
+    (-pi, pi] is its own image."""
+    p = np.asarray(pose3, dtype=np.float64).reshape(3).copy()
+    if not (-np.pi < p[2] <= np.pi):
+        p[2] = np.arctan2(np.sin(p[2]), np.cos(p[2]))
+    return p
+
+
 @dataclass
 class PoseGraphProblem:
     """The factor graph bin/pose_graph_g2o.rs:748-830 builds: variables `x{id}` (SE3), one
@@ -131,9 +183,11 @@ class PoseGraphProblem:
     priors: list = field(default_factory=list)   # (vertex index, data[7], huber delta or None) per PriorFactor block
 
     def __post_init__(self):
+        self.manifold = self.data.manifold
+        self.dof, self.ambient = (3, 3) if self.manifold == "se2" else (6, 7)
         if self.fix is None:
-            self.fix = np.zeros((self.data.n_v, 6), dtype=np.uint8)
-        self.pose_col = pose_graph_columns(self.data.ids)
+            self.fix = np.zeros((self.data.n_v, self.dof), dtype=np.uint8)
+        self.pose_col = pose_graph_columns(self.data.ids, self.dof)
 
     def add_prior(self, name: str, data=None, huber_delta: float | None = None):
         """`problem.add_residual_block(&[name], PriorFactor { data }, loss)` (src/factors/prior_factor.rs:53-113): the
@@ -146,7 +200,10 @@ class PoseGraphProblem:
         if hit.size == 0:
             raise KeyError(name)
         v = int(hit[0])
-        x = se3_as_vector(self.data.poses[v]) if data is None else np.asarray(data, dtype=np.float64).reshape(7)
+        if self.manifold == "se2":   # r = [x, y, theta] - data, three rows, Jacobian I3 (integration_tests.rs:213-231)
+            x = se2_as_vector(self.data.poses[v]) if data is None else np.asarray(data, dtype=np.float64).reshape(3)
+        else:
+            x = se3_as_vector(self.data.poses[v]) if data is None else np.asarray(data, dtype=np.float64).reshape(7)
         self.priors.append((v, x, huber_delta))
         return self
 
@@ -154,7 +211,7 @@ class PoseGraphProblem:
     def pose_graph(cls, data: PoseGraphData, huber_delta: float | None = None) -> "PoseGraphProblem":
         """The LM set-up: all six DOF of the first vertex fixed (pose_graph_g2o.rs:790-797)."""
         p = cls(data, huber_delta)
-        for dof in range(6):
+        for dof in range(p.dof):
             p.fix_variable(f"x{int(data.ids[0])}", dof)
         return p
 
@@ -169,7 +226,7 @@ class PoseGraphProblem:
 
     @property
     def total_dof(self) -> int:
-        return 6 * self.data.n_v
+        return self.dof * self.data.n_v
 
     @property
     def num_residual_blocks(self) -> int:
@@ -194,7 +251,7 @@ class GpuSparseCholeskySolver:
     def initialize_structure(self, problem: PoseGraphProblem):
         d = problem.data
         self.close()
-        h = capi.PgHandle(d.n_v, d.n_e, self.device)
+        h = capi.PgHandle(d.n_v, d.n_e, self.device, capi.MANIFOLD_SE2 if problem.manifold == "se2" else capi.MANIFOLD_SE3)
         for k, v in self._opts.items():
             h.check(h.L.apexgpu_pg_set_option(h.h, k.encode(), v))
         ef = np.ascontiguousarray(d.e_from, dtype=np.uint32); et = np.ascontiguousarray(d.e_to, dtype=np.uint32)
@@ -212,7 +269,7 @@ class GpuSparseCholeskySolver:
         """PriorFactor blocks: (vertex index, data[7], huber delta or None) each; replaces the set."""
         h = self._need()
         v = np.ascontiguousarray([q[0] for q in priors], dtype=np.uint32)
-        x = np.ascontiguousarray([q[1] for q in priors], dtype=np.float64).reshape(-1, 7)
+        x = np.ascontiguousarray([q[1] for q in priors], dtype=np.float64).reshape(-1, h.ambient)
         dl = np.ascontiguousarray([-1.0 if q[2] is None else float(q[2]) for q in priors], dtype=np.float64)
         h.check(h.L.apexgpu_pg_set_priors(h.h, len(v), capi.ptr(v), capi.ptr(x), capi.ptr(dl)))
 
@@ -220,7 +277,7 @@ class GpuSparseCholeskySolver:
         """Corrected residuals of the prior blocks at the current parameters: [n_prior][7]."""
         h = self._need()
         n = len(self.problem.priors)
-        r = np.zeros((n, 7))
+        r = np.zeros((n, h.ambient))
         if n: h.check(h.L.apexgpu_pg_get_prior_residual(h.h, capi.ptr(r)))
         return r
 
@@ -232,11 +289,13 @@ class GpuSparseCholeskySolver:
     def set_parameters(self, poses):
         h = self._need()
         p = np.ascontiguousarray(poses, dtype=np.float64)
+        if p.shape != (h.n_vertices, h.ambient):
+            raise ValueError(f"poses must be ({h.n_vertices}, {h.ambient})")
         h.check(h.L.apexgpu_pg_set_params(h.h, capi.ptr(p)))
 
     def get_parameters(self) -> np.ndarray:
         h = self._need()
-        p = np.zeros((h.n_vertices, 7))
+        p = np.zeros((h.n_vertices, h.ambient))
         h.check(h.L.apexgpu_pg_get_params(h.h, capi.ptr(p)))
         return p
 
@@ -248,7 +307,7 @@ class GpuSparseCholeskySolver:
 
     def solve_augmented_equation(self, lam: float, want_step: bool = True):
         h = self._need()
-        n = 6 * h.n_vertices
+        n = h.dof * h.n_vertices
         step = np.zeros(n) if want_step else None
         self._grad = np.zeros(n) if want_step else None
         h.check(h.L.apexgpu_pg_solve_augmented(h.h, float(lam), capi.ptr(step), capi.ptr(self._grad)))
@@ -263,14 +322,14 @@ class GpuSparseCholeskySolver:
     # AssemblyBackend::compute_column_norms / apply_column_scaling / apply_inverse_scaling (linearizer/mod.rs:229-262)
     def compute_column_norms(self) -> np.ndarray:
         h = self._need()
-        n = np.zeros(6 * h.n_vertices)
+        n = np.zeros(h.dof * h.n_vertices)
         h.check(h.L.apexgpu_pg_column_norms(h.h, capi.ptr(n)))
         return n
 
     def apply_column_scaling(self, scaling):
         h = self._need()
         a = None if scaling is None else np.ascontiguousarray(scaling, dtype=np.float64)
-        if a is not None and a.shape != (6 * h.n_vertices,):
+        if a is not None and a.shape != (h.dof * h.n_vertices,):
             raise ValueError("scaling must have total_dof entries")
         h.check(h.L.apexgpu_pg_set_column_scaling(h.h, capi.ptr(a)))
         self._scaling = a
@@ -302,19 +361,19 @@ class GpuSparseCholeskySolver:
 
     def get_residual(self) -> np.ndarray:
         h = self._need()
-        r = np.zeros((h.n_edges, 6))
+        r = np.zeros((h.n_edges, h.dof))
         h.check(h.L.apexgpu_pg_get_residual(h.h, capi.ptr(r)))
         return r
 
     def get_jacobian_blocks(self) -> np.ndarray:
         h = self._need()
-        j = np.zeros((h.n_edges, 6, 12))
+        j = np.zeros((h.n_edges, h.dof, 2 * h.dof))
         h.check(h.L.apexgpu_pg_get_jacobian_blocks(h.h, capi.ptr(j)))
         return j
 
     def get_hessian(self, lam: float = 0.0):
         h = self._need()
-        n = 6 * h.n_vertices
+        n = h.dof * h.n_vertices
         H = np.zeros((n, n)); g = np.zeros(n)
         h.check(h.L.apexgpu_pg_get_hessian(h.h, float(lam), capi.ptr(H), capi.ptr(g)))
         return H, g
@@ -325,7 +384,7 @@ class GpuSparseCholeskySolver:
         inversion of the tile factor.  Caller's vertex order.  Raises LinAlgError (InvalidState) when no factor is held
         (no solve yet, or an assembly / export since)."""
         h = self._need()
-        out = np.zeros((h.n_vertices, 6, 6))
+        out = np.zeros((h.n_vertices, h.dof, h.dof))
         h.check(h.L.apexgpu_pg_covariance(h.h, capi.ptr(out)))
         return out
 

@@ -354,7 +354,8 @@ def _make_named_uncached(shape, scale, nm, hub, cid, n_cam, n_pt, k_lo, k_hi, mi
 @dataclass
 class PoseGraphData:
     """What bin/pose_graph_g2o.rs:748-830 feeds the optimiser: vertices sorted by id with
-    pose = [tx,ty,tz,qw,qx,qy,qz]; edge e is BetweenFactor(meas[e]) on (x{ids[e_from[e]]}, x{ids[e_to[e]]})."""
+    pose = [tx,ty,tz,qw,qx,qy,qz]; edge e is BetweenFactor(meas[e]) on (x{ids[e_from[e]]}, x{ids[e_to[e]]}).
+    SE2 graphs (pose_graph_g2o.rs:366-437) use the same container with 3-wide rows: pose / meas = [x, y, theta]."""
 
     ids: np.ndarray       # (n_v,) int64, ascending
     poses: np.ndarray     # (n_v, 7) initial values
@@ -371,6 +372,10 @@ class PoseGraphData:
     @property
     def n_e(self) -> int:
         return int(self.meas.shape[0])
+
+    @property
+    def manifold(self) -> str:
+        return "se2" if self.poses.shape[1] == 3 else "se3"
 
 
 def se3_exp(tau: np.ndarray) -> np.ndarray:
@@ -429,3 +434,83 @@ def make_sphere(rings: int = 50, per_ring: int = 50, noise: float = 0.05, radius
     init[:, 3:7] /= np.linalg.norm(init[:, 3:7], axis=-1, keepdims=True)
     ids = np.arange(n, dtype=np.int64) * id_stride
     return PoseGraphData(ids=ids, poses=init, e_from=ef, e_to=et, meas=meas, truth=truth, name=f"sphere-{n}")
+
+
+# ---------------------------------------------------------------------------------------------------
+# SE2 pose graphs (the 2D half of bin/pose_graph_g2o.rs: M3500, intel, mit, ring).  PoseGraphData with 3-wide
+# rows: pose / measurement = [x, y, theta] (G2O order).
+# ---------------------------------------------------------------------------------------------------
+def se2_mul(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """(n,3) [x, y, theta] composed element by element (generator-side helper); theta comes back in (-pi, pi]."""
+    c, s = np.cos(a[:, 2]), np.sin(a[:, 2])
+    th = a[:, 2] + b[:, 2]
+    return np.stack([c * b[:, 0] - s * b[:, 1] + a[:, 0], s * b[:, 0] + c * b[:, 1] + a[:, 1], np.arctan2(np.sin(th), np.cos(th))], axis=-1)
+
+
+def se2_inv(a: np.ndarray) -> np.ndarray:
+    c, s = np.cos(a[:, 2]), np.sin(a[:, 2])
+    return np.stack([-(c * a[:, 0] + s * a[:, 1]), -(-s * a[:, 0] + c * a[:, 1]), -a[:, 2]], axis=-1)
+
+
+def se2_exp(tau: np.ndarray) -> np.ndarray:
+    th = tau[:, 2]
+    small = np.abs(th) < 1e-5
+    t = np.where(small, 1.0, th)
+    a = np.where(small, 1.0 - th * th / 6.0, np.sin(t) / t)
+    b = np.where(small, 0.5 * th, (1.0 - np.cos(t)) / t)
+    return np.stack([a * tau[:, 0] - b * tau[:, 1], b * tau[:, 0] + a * tau[:, 1], th], axis=-1)
+
+
+def make_manhattan(n: int = 3500, noise: float = 0.02, rot_noise: float = 0.01, turn_prob: float = 0.3, max_closures: int = 2,
+                   min_gap: int = 12, config_id: int = 1, id_stride: int = 1) -> PoseGraphData:
+    """Manhattan-world SE2 pose graph (the shape of M3500): a seeded walk of unit steps on a square grid of side
+    ~ sqrt(n) / 2 cells with 90-degree turns (probability `turn_prob` per step, forced at the border), an odometry edge
+    i -> i+1 per step, and for every vertex a loop-closure edge j -> i to the oldest (at most `max_closures`) earlier
+    vertices j <= i - min_gap that stand within one cell of it.  Measurements are the true relative poses times
+    Exp(N(0, noise^2) on x, y and N(0, rot_noise^2) on theta); initial values are the odometry chain from the true first
+    pose (drifting).  Edges: the n - 1 odometry edges first, then the closures by ascending i.
+
+    The generator's own counts at the defaults (config_id 1): make_manhattan(3500) has 3,500 vertices and 9,378 edges
+    (3,499 odometry + 5,879 closures); make_manhattan(10000) has 10,000 vertices and 27,281 edges.  (The real M3500 file
+    is sparser in closures; nothing here reads it.)"""
+    rng = SplitMix(SEED_BASE + 7000 + config_id)
+    side = max(4, int(np.ceil(np.sqrt(n) / 2.0)))
+    u_turn = rng.uniform(40, n)
+    u_dir = rng.uniform(41, n)
+    dxy = ((1, 0), (0, 1), (-1, 0), (0, -1))
+    x = y = side // 2
+    h = 0
+    cells: dict = {}
+    truth = np.zeros((n, 3))
+    cf, ct = [], []
+    for i in range(n):
+        if i > 0:
+            if u_turn[i] < turn_prob:
+                h = (h + (1 if u_dir[i] < 0.5 else 3)) % 4
+            for _ in range(4):   # forced turn at the border
+                nx, ny = x + dxy[h][0], y + dxy[h][1]
+                if 0 <= nx <= side and 0 <= ny <= side:
+                    break
+                h = (h + (1 if u_dir[i] < 0.5 else 3)) % 4
+            x, y = nx, ny
+        truth[i] = (x, y, (0.0, 0.5 * np.pi, np.pi, -0.5 * np.pi)[h])
+        near = []
+        for ax in (-1, 0, 1):
+            for ay in (-1, 0, 1):
+                if ax * ax + ay * ay <= 1:
+                    near.extend(j for j in cells.get((x + ax, y + ay), ()) if j <= i - min_gap)
+        for j in sorted(near)[:max_closures]:
+            cf.append(j); ct.append(i)
+        cells.setdefault((x, y), []).append(i)
+    ef = np.concatenate([np.arange(n - 1), np.array(cf, dtype=np.int64)]).astype(np.uint32)
+    et = np.concatenate([np.arange(1, n), np.array(ct, dtype=np.int64)]).astype(np.uint32)
+    m = ef.shape[0]
+    rel = se2_mul(se2_inv(truth[ef]), truth[et])
+    tau = np.stack([noise * rng.normal(50, m), noise * rng.normal(52, m), rot_noise * rng.normal(54, m)], axis=-1)
+    meas = se2_mul(rel, se2_exp(tau))
+    init = np.empty_like(truth)
+    init[0] = truth[0]
+    for k in range(n - 1):
+        init[k + 1] = se2_mul(init[k:k + 1], meas[k:k + 1])[0]
+    ids = np.arange(n, dtype=np.int64) * id_stride
+    return PoseGraphData(ids=ids, poses=init, e_from=ef, e_to=et, meas=meas, truth=truth, name=f"manhattan-{n}")

@@ -498,7 +498,7 @@ int apexgpu_bal_variables(const apexgpu_bal* b, double* poses7, double* intr3);
 int apexgpu_reference_columns(int64_t n_cam, int64_t n_pt, int64_t* intr_col, int64_t* pose_col, int64_t* pt_col);
 
 /* =================================================================================================
- * SE3 pose-graph backend (BASELINE.json configs[1]: block-sparse J^T J assembly + Cholesky, no Schur)
+ * Pose-graph backend, SE3 and SE2 (BASELINE.json configs[1]: block-sparse J^T J assembly + Cholesky, no Schur)
  *
  * Replaces, for problems made of BetweenFactor<SE3> residual blocks (bin/pose_graph_g2o.rs:748-830):
  *   BetweenFactor<SE3>::linearize                         src/factors/between_factor.rs:268-322
@@ -512,8 +512,22 @@ int apexgpu_reference_columns(int64_t n_cam, int64_t n_pt, int64_t* intr_col, in
  * ================================================================================================= */
 typedef struct apexgpu_pg_solver apexgpu_pg_solver;
 
+/* SE2 pose graphs (the 2D half of bin/pose_graph_g2o.rs, test_se2_dataset :314-700; tests/integration_tests.rs:184-345)
+ * use the SAME handle type and the same entry points.  A handle made by apexgpu_pg_create_se2 holds SE2 variables
+ * (translation + unit complex, crates/apex-manifolds/src/se2.rs:27-63): the parameter vector of a vertex, a measurement
+ * and a prior's data are [x, y, theta] (G2O order; SE2::from(DVector), se2.rs:48-53), the tangent is [x, y, theta]
+ * (BetweenFactor<SE2>::linearize, between_factor.rs:268-322; exp / log / Jr / Jr^-1 with their small-angle branches,
+ * se2.rs:252-284, 468-613), the retraction is the right-plus x * Exp(d).  Wherever an entry below says 7 (ambient size)
+ * or 6 (tangent dof) an SE2 handle reads and writes 3; each entry repeats its SE2 shape.  H is assembled without
+ * atomics (one owner per block row): two assemblies of one state, and two LM runs from one start, are bit-identical. */
+#define APEXGPU_MANIFOLD_SE3 0
+#define APEXGPU_MANIFOLD_SE2 1
+
 /* SparseCholeskySolver::new (cholesky.rs:60-70) + per-optimize state */
 int apexgpu_pg_create(int64_t n_vertices, int64_t n_edges, int device, apexgpu_pg_solver** out);
+int apexgpu_pg_create_se2(int64_t n_vertices, int64_t n_edges, int device, apexgpu_pg_solver** out);
+/* out3 = { APEXGPU_MANIFOLD_*, ambient size (7 | 3), tangent dof (6 | 3) } */
+int apexgpu_pg_manifold(const apexgpu_pg_solver* h, int out3[3]);
 void apexgpu_pg_destroy(apexgpu_pg_solver* h);
 const char* apexgpu_pg_last_error(const apexgpu_pg_solver* h);
 
@@ -521,7 +535,9 @@ const char* apexgpu_pg_last_error(const apexgpu_pg_solver* h);
  * (cholesky.rs:190-208): e_from[e] = k0 and e_to[e] = k1 of BetweenFactor e (residual block order),
  * meas7[e] = [t, qw,qx,qy,qz] of the measured k0->k1 transform, fix6[v][a] != 0 fixes tangent DOF a of
  * vertex v (Problem::fix_variable, src/core/problem.rs:185-197), huber_delta <= 0: no loss function,
- * > 0: HuberLoss(delta) on every block. */
+ * > 0: HuberLoss(delta) on every block.
+ * SE2 handle: meas7 is [n_e][3] = x y theta (SE2::from_xy_angle, se2.rs:106-110), fix6 is [n_v][3], pose_col counts 3
+ * columns per variable (apexgpu_pose_graph_columns_se2). */
 int apexgpu_pg_set_structure(apexgpu_pg_solver* h, const uint32_t* e_from, const uint32_t* e_to, const double* meas7,
                              const int64_t* pose_col, const uint8_t* fix6, double huber_delta);
 /* Problem::initialize_variables (src/core/problem.rs:686-808): poses7[v] = [t, qw,qx,qy,qz] */
@@ -529,7 +545,11 @@ int apexgpu_pg_set_structure(apexgpu_pg_solver* h, const uint32_t* e_from, const
  * tests/integration_tests.rs:98-118): r = to_vector(x_vertex) - data7 (seven rows, [t, w, i, j, k]); the Jacobian is the 7 x 7
  * identity of which the linearizer keeps the variable's six tangent columns (src/linearizer/cpu/sparse.rs:201-204);
  * huber_delta[k] <= 0 (or huber_delta == NULL): no loss on block k.  Replaces the set; after apexgpu_pg_set_structure.
- * apexgpu_pg_get_prior_residual: the corrected residuals [n][7] at the current parameters. */
+ * apexgpu_pg_get_prior_residual: the corrected residuals [n][7] at the current parameters.
+ * SE2 handle (run_se2_optimization(.., use_prior = true), tests/integration_tests.rs:213-231): data7 is [n][3], r = [x, y, theta]
+ * - data (prior_factor.rs:96-108), Jacobian the 3 x 3 identity, residuals [n][3].
+ * apexgpu_pg_set_params / get_params on an SE2 handle: poses7 is [n_v][3] = x y theta; get_params returns theta in (-pi, pi]
+ * (SE2 -> DVector, se2.rs:55-63: UnitComplex::angle). */
 int apexgpu_pg_set_priors(apexgpu_pg_solver* h, int64_t n, const uint32_t* vertex, const double* data7, const double* huber_delta);
 int apexgpu_pg_get_prior_residual(apexgpu_pg_solver* h, double* r7_out);
 int apexgpu_pg_set_params(apexgpu_pg_solver* h, const double* poses7);
@@ -540,7 +560,8 @@ int apexgpu_pg_cost(apexgpu_pg_solver* h, double* cost);
 /* assemble (src/linearizer/mod.rs:191-213) + solve_augmented_equation (cholesky.rs:159-230):
  * (J^T J + lambda I) dx = -J^T r.  step_out / grad_out (= +J^T r, get_gradient) have 6 n_vertices entries in
  * the global column order and may be NULL.  A non-positive pivot returns APEXGPU_ERR_SINGULAR_MATRIX
- * ("Cholesky factorization failed (matrix may be singular)", cholesky.rs:213-219). */
+ * ("Cholesky factorization failed (matrix may be singular)", cholesky.rs:213-219).
+ * SE2 handle: 3 n_vertices entries. */
 int apexgpu_pg_solve_augmented(apexgpu_pg_solver* h, double lambda, double* step_out, double* grad_out);
 /* out3 = { |g|, |step|, predicted reduction } (levenberg_marquardt.rs:721-746) */
 int apexgpu_pg_step_stats(apexgpu_pg_solver* h, double out3[3]);
@@ -558,7 +579,8 @@ int apexgpu_pg_lm_optimize(apexgpu_pg_solver* h, apexgpu_lm_config* cfg, apexgpu
                            apexgpu_lm_iter* history, int history_capacity);
 
 /* parity / debug exports: loss-corrected residuals [n_edges][6], Jacobians [n_edges][6][12] = [dr/dk0 | dr/dk1]
- * in residual-block order; dense H = J^T J + lambda I ([6 n_v]^2 row-major) and g = J^T r in the global column order */
+ * in residual-block order; dense H = J^T J + lambda I ([6 n_v]^2 row-major) and g = J^T r in the global column order.
+ * SE2 handle: residuals [n_edges][3], Jacobians [n_edges][3][6], H (3 n_v)^2, g 3 n_v. */
 int apexgpu_pg_get_residual(apexgpu_pg_solver* h, double* r_out);
 int apexgpu_pg_get_jacobian_blocks(apexgpu_pg_solver* h, double* j_out);
 int apexgpu_pg_get_hessian(apexgpu_pg_solver* h, double lambda, double* H_out, double* g_out);
@@ -566,8 +588,9 @@ int apexgpu_pg_get_hessian(apexgpu_pg_solver* h, double lambda, double* H_out, d
  * the 6 x 6 diagonal blocks of the inverse of the matrix the LAST apexgpu_pg_solve_augmented factorised (J^T J + lambda I at
  * that point and lambda, scaled variables under Jacobi scaling: what apexgpu_pg_get_hessian(lambda) returns there), from the
  * tile factor by selected inversion.  cov_out[n_v][6][6], caller's vertex order, columns as apexgpu_pg_get_hessian's.
- * APEXGPU_ERR_INVALID_STATE: no valid factor (no solve yet, or an assembly / export since). */
-int apexgpu_pg_covariance(apexgpu_pg_solver* h, double* cov_out /* n_v*36 */);
+ * APEXGPU_ERR_INVALID_STATE: no valid factor (no solve yet, or an assembly / export since).
+ * SE2 handle: cov_out[n_v][3][3]. */
+int apexgpu_pg_covariance(apexgpu_pg_solver* h, double* cov_out /* n_v*36 | n_v*9 */);
 int apexgpu_pg_covariance_stats(apexgpu_pg_solver* h, double out[6], double* group_ms, int group_cap);   /* as apexgpu_covariance_stats */
 
 /* name: "graphs" (hipGraph replay of factor / solves), "update_overlap" (second stream for trailing updates),
@@ -585,7 +608,8 @@ int apexgpu_pg_counters(apexgpu_pg_solver* h, int64_t out[4]);   /* as apexgpu_c
 /* ---- input path (host only): G2O files ------------------------------------------------------------
  * G2oLoader::load (crates/apex-io/src/g2o.rs:140-620): VERTEX_SE3:QUAT id x y z qx qy qz qw (norm checked to
  * 1 +- 0.01, then normalised), EDGE_SE3:QUAT from to x y z qx qy qz qw + 21 upper-triangular information
- * values; '#' comments, blank lines and unknown tags are skipped; SE2 lines are validated and counted only.
+ * values; '#' comments, blank lines and unknown tags are skipped.  VERTEX_SE2 id x y theta and EDGE_SE2 from to dx dy dtheta
+ * + 6 upper-triangular information values (g2o.rs:303-337, 424-485) are kept beside them (the *_se2 calls below).
  * Error codes mirror IoError: Io, Parse, MissingFields, InvalidNumber, DuplicateVertex, InvalidQuaternion. */
 typedef struct apexgpu_g2o apexgpu_g2o;
 #define APEXGPU_G2O_ERR_IO (-30)
@@ -608,6 +632,15 @@ int apexgpu_g2o_problem(const apexgpu_g2o* g, int64_t* sorted_ids, double* poses
                         double* meas7, int64_t* pose_col, uint8_t* fix6);
 /* first global column of variable "x{ids[v]}" in the sorted-name order of src/optimizer/mod.rs:530-536 */
 int apexgpu_pose_graph_columns(int64_t n_vertices, const int64_t* ids, int64_t* pose_col);
+/* the SE2 content of the file.  raw: file order; poses3 / meas3 = [x, y, theta]; e_from / e_to are vertex IDS; info9 row-major
+ * symmetric; any may be NULL.  problem: what bin/pose_graph_g2o.rs:366-437 builds for the LM optimiser -- vertices sorted by
+ * id, variables x{id} in sorted-name order with 3 columns each (apexgpu_pose_graph_columns_se2), the three DOF of the first
+ * vertex fixed, one BetweenFactor per EDGE_SE2 with edge.measurement only (the information matrix is not used by the factor). */
+int apexgpu_g2o_raw_se2(const apexgpu_g2o* g, int64_t* ids, double* poses3, int64_t* e_from, int64_t* e_to, double* meas3,
+                        double* info9);
+int apexgpu_g2o_problem_se2(const apexgpu_g2o* g, int64_t* sorted_ids, double* poses3, uint32_t* e_from, uint32_t* e_to,
+                            double* meas3, int64_t* pose_col, uint8_t* fix3);
+int apexgpu_pose_graph_columns_se2(int64_t n_vertices, const int64_t* ids, int64_t* pose_col);
 
 #ifdef __cplusplus
 }
