@@ -28,7 +28,7 @@ SYMBOLS = (
     "apexgpu_stage_times", "apexgpu_info", "apexgpu_variant_info", "apexgpu_variant_costs", "apexgpu_trim_host_cache", "apexgpu_host_cache_bytes", "apexgpu_counters", "apexgpu_debug_get_pair_records", "apexgpu_get_unique_id", "apexgpu_comm_init", "apexgpu_comm_init_shm", "apexgpu_set_shard", "apexgpu_shard_range",
     "apexgpu_debug_lockstep_solve", "apexgpu_export_step", "apexgpu_owned_landmarks", "apexgpu_debug_partition", "apexgpu_debug_check_schedule",
     "apexgpu_debug_tiles_create", "apexgpu_debug_tiles_pattern", "apexgpu_debug_tiles_set", "apexgpu_debug_tiles_factor",
-    "apexgpu_debug_tiles_solve", "apexgpu_debug_tiles_matvec", "apexgpu_debug_tiles_get", "apexgpu_debug_tiles_destroy",
+    "apexgpu_debug_tiles_solve", "apexgpu_debug_tiles_matvec", "apexgpu_debug_tiles_pcg", "apexgpu_debug_tiles_get", "apexgpu_debug_tiles_destroy",
     "apexgpu_bal_open", "apexgpu_bal_close", "apexgpu_bal_last_error", "apexgpu_bal_sizes", "apexgpu_bal_raw",
     "apexgpu_bal_variables", "apexgpu_reference_columns",
     # SE3 pose-graph backend
@@ -135,6 +135,7 @@ def load() -> C.CDLL:
     L.apexgpu_debug_tiles_factor.argtypes = [vp, C.POINTER(C.c_int)]
     L.apexgpu_debug_tiles_solve.argtypes = [vp, C.c_int, vp, vp]
     L.apexgpu_debug_tiles_matvec.argtypes = [vp, vp, vp]
+    L.apexgpu_debug_tiles_pcg.argtypes = [vp, vp, C.c_int, dbl, vp, C.POINTER(C.c_int), vp]
     L.apexgpu_debug_tiles_get.argtypes = [vp, C.c_int, vp]
     L.apexgpu_debug_tiles_destroy.argtypes = [vp]
     L.apexgpu_debug_tiles_destroy.restype = None
@@ -466,6 +467,15 @@ class TileCholesky:
         y = np.empty_like(xv)
         self._check(self.L.apexgpu_debug_tiles_matvec(self.h, ptr(xv), ptr(y)), "matvec")
         return y
+
+    def pcg(self, rhs: np.ndarray, max_iter: int, tol: float):
+        """Jacobi-PCG on the unfactored tiles (TilePlan::pcg): (x, iterations, scal) with scal = the loop's device scalars
+        [rz_old, p.Ap, r.r, r.z, frozen] after the call.  Voids the factor: solve() raises InvalidState until factor()."""
+        b = np.ascontiguousarray(rhs, dtype=np.float64)
+        assert b.shape == (self.n_pad,), b.shape
+        x, scal, it = np.empty_like(b), np.empty(5), C.c_int(0)
+        self._check(self.L.apexgpu_debug_tiles_pcg(self.h, ptr(b), int(max_iter), float(tol), ptr(x), C.byref(it), ptr(scal)), "pcg")
+        return x, it.value, scal
 
     def get(self, which: str) -> np.ndarray:
         """"tiles" (raw), "L" (the tiles with the diagonal tiles masked to their lower triangle), "Linv" ((nt, 144, 144)),

@@ -17,8 +17,9 @@ struct apexgpu_tiles {
     hipStream_t stream = nullptr;
     apex::TilePlan plan;
     double *rhs = nullptr, *x = nullptr, *work = nullptr;   // kept for the handle's life: the captured sweeps hold their addresses
+    double* pcg_work = nullptr;                             // 6 * n_pad doubles, allocated by the first pcg call
     ~apexgpu_tiles() {
-        for (double* p : {rhs, x, work}) if (p) (void)hipFree(p);
+        for (double* p : {rhs, x, work, pcg_work}) if (p) (void)hipFree(p);
     }
 };
 
@@ -161,6 +162,22 @@ int apexgpu_debug_tiles_matvec(apexgpu_tiles* h, const double* x, double* y) {
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(y, h->x, n * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t se = hipStreamSynchronize(h->stream);
+    return hip_rc(e != hipSuccess ? e : se);
+}
+
+int apexgpu_debug_tiles_pcg(apexgpu_tiles* h, const double* rhs, int max_iter, double tol, double* x, int* iters, double scal_out[5]) {
+    if (!h || !rhs || !x || !iters || !scal_out) return APEXGPU_ERR_INVALID_INPUT;
+    if (hipSetDevice(h->device) != hipSuccess) return APEXGPU_ERR_DEVICE;
+    apex::TilePlan& tp = h->plan;
+    const size_t n = (size_t)tp.n_pad();
+    *iters = 0;
+    if (!h->pcg_work && hipMalloc(reinterpret_cast<void**>(&h->pcg_work), 6 * n * sizeof(double)) != hipSuccess) return APEXGPU_ERR_DEVICE;
+    hipError_t e = hipMemcpyAsync(h->rhs, rhs, n * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    // (as Solver::pcg_solve: the caller's limits go through unchanged; the plan's factor is void from here on)
+    if (e == hipSuccess) e = tp.pcg(h->rhs, h->x, h->pcg_work, max_iter, tol, iters);
+    if (e == hipSuccess) e = hipMemcpyAsync(x, h->x, n * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(scal_out, tp.pcg_scalars(), 5 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
     const hipError_t se = hipStreamSynchronize(h->stream);
     return hip_rc(e != hipSuccess ? e : se);
 }

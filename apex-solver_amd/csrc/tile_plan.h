@@ -187,6 +187,7 @@ class TilePlan {
     void sym_matvec(const double* x, double* y);
     // Jacobi-PCG on the UNFACTORED tiles; work: 6*n_pad doubles; syncs once per iteration
     hipError_t pcg(const double* rhs, double* x, double* work, int max_iter, double tol, int* iters);
+    const double* pcg_scalars() const { return scal_; }   // device: {rz_old, p.Ap, r.r, r.z, frozen} as the last pcg() left them (tests)
 
     // ---- marginal covariances: selected inversion of the factor (block Takahashi recurrence) ----
     // The tiles hold a valid factor L only between a successful single-rank factorisation + sweeps (the CALLER says so with

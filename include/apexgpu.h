@@ -434,6 +434,11 @@ int apexgpu_debug_tiles_factor(apexgpu_tiles* h, int* failed_at);
 int apexgpu_debug_tiles_solve(apexgpu_tiles* h, int n_rhs, const double* rhs, double* x);
 /* y = A x on the unfactored tiles (after set, before factor), n_pad doubles */
 int apexgpu_debug_tiles_matvec(apexgpu_tiles* h, const double* x, double* y);
+/* Jacobi-preconditioned CG on the unfactored tiles (after set), as a solver's Iterative variant runs it: rhs and x are n_pad
+ * doubles, *iters the iterations counted, scal_out = the loop's device scalars {rz_old, p.Ap, r.r, r.z, frozen} as they stand
+ * after the call.  The tiles no longer count as a factor afterwards: solve answers APEXGPU_ERR_INVALID_STATE until the next
+ * factor. */
+int apexgpu_debug_tiles_pcg(apexgpu_tiles* h, const double* rhs, int max_iter, double tol, double* x, int* iters, double scal_out[5]);
 /* which 0: the tiles (L after a factor; a diagonal tile's 16 x 16 blocks right of its diagonal keep the assembled matrix),
  * out[n_slots][144][144]; 1: the inverses of L's diagonal tiles, out[nt][144][144]; 2: the selected inverse Z on the
  * pattern of L (computed first where needed; needs a valid factor), out[n_slots][144][144] */

@@ -223,6 +223,25 @@ def dominant_case(present, rng, q=14, amp=64):
     return A
 
 
+def low_rank_case(nt, r, rng, u=0.125, exp_range=(-6, 6), row_exp=None):
+    """(A, U, e): A = S (I + U U^T) S on dense(nt), U in {+-u}^(n x r), S = diag(2^e) with e drawn from exp_range (inclusive)
+    or given as row_exp.  Every row of U has the norm u sqrt(r), so I + U U^T has the constant diagonal 1 + r u^2 and the
+    Jacobi-scaled matrix is (I + U U^T) / (1 + r u^2): r + 1 distinct eigenvalues, so CG with the Jacobi preconditioner ends
+    after r + 1 iterations in exact arithmetic.  u a power of two: every entry is dyadic and exact in fp64."""
+    n = nt * NB
+    Um = rng.choice([-1.0, 1.0], size=(n, r)) * u
+    e = rng.integers(exp_range[0], exp_range[1] + 1, size=n) if row_exp is None else np.asarray(row_exp, dtype=np.int64)
+    assert e.shape == (n,)
+    A = {}
+    for I in range(nt):
+        for J in range(I + 1):
+            t = Um[I * NB:(I + 1) * NB] @ Um[J * NB:(J + 1) * NB].T   # (sums of r terms +-u^2: exact)
+            if I == J:
+                t = t + np.eye(NB)
+            A[(I, J)] = t
+    return scale_rows(A, e), Um, e
+
+
 def touched_array(A, dev):
     """The tiles of A in the plan's slot order (the first n_touched slots)."""
     out = np.zeros((dev.n_touched, NB, NB))
