@@ -571,20 +571,16 @@ int apexgpu_debug_invert_blocks(int device, int64_t n, const double* blocks9, do
     if (n < 0 || (n > 0 && (!blocks9 || !inv9_out || !ok_out))) return APEXGPU_ERR_INVALID_INPUT;
     if (n == 0) return APEXGPU_OK;
     if (hipSetDevice(device) != hipSuccess) return APEXGPU_ERR_DEVICE;
-    double *din = nullptr, *dout = nullptr;
-    int* dok = nullptr;
+    apex::DeviceBuffer<double> din, dout;
+    apex::DeviceBuffer<int> dok;
     int rc = APEXGPU_ERR_DEVICE;
-    if (hipMalloc((void**)&din, 9 * n * sizeof(double)) == hipSuccess && hipMalloc((void**)&dout, 9 * n * sizeof(double)) == hipSuccess &&
-        hipMalloc((void**)&dok, n * sizeof(int)) == hipSuccess &&
+    if (din.alloc(9 * n) == hipSuccess && dout.alloc(9 * n) == hipSuccess && dok.alloc(n) == hipSuccess &&
         hipMemcpy(din, blocks9, 9 * n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess) {
         apex::launch_debug_invert_blocks(n, din, dout, dok, nullptr);
         if (hipMemcpy(inv9_out, dout, 9 * n * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
             hipMemcpy(ok_out, dok, n * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess)
             rc = APEXGPU_OK;
     }
-    if (din) (void)hipFree(din);
-    if (dout) (void)hipFree(dout);
-    if (dok) (void)hipFree(dok);
     return rc;
 }
 

@@ -1,0 +1,82 @@
+// device_buffer.h -- the two owners of memory the library allocates through HIP: DeviceBuffer<T> (one hipMalloc block) and
+// PinnedBuffer<T> (one hipHostMalloc block).  Move-only; the destructor frees; alloc / alloc_zero / upload free what was held
+// first and return the HIP status.  Both convert to T*, so a buffer is passed, indexed, offset and null-tested as the
+// pointer it owns.  Every allocation holds at least one element: an empty list still gets an address.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include <algorithm>
+
+namespace apex {
+
+template <typename T>
+class DeviceBuffer {
+   public:
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() { reset(); }
+
+    hipError_t alloc(size_t n) {   // contents undefined
+        reset();
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p_), std::max<size_t>(n, 1) * sizeof(T));
+        if (e != hipSuccess) p_ = nullptr;
+        return e;
+    }
+    hipError_t alloc_zero(size_t n) {   // cleared on the NULL stream: the caller synchronises the device before a non-blocking stream reads it
+        const hipError_t e = alloc(n);
+        return e != hipSuccess ? e : hipMemset(p_, 0, std::max<size_t>(n, 1) * sizeof(T));
+    }
+    template <typename C>
+    hipError_t upload(const C& hv) {   // synchronous copy of anything with data() / size() and T's element size
+        static_assert(sizeof(*hv.data()) == sizeof(T), "upload: element size differs");
+        const hipError_t e = alloc(hv.size());
+        if (e != hipSuccess || hv.size() == 0) return e;
+        return hipMemcpy(p_, hv.data(), hv.size() * sizeof(T), hipMemcpyHostToDevice);
+    }
+    void reset() {
+        if (p_) { (void)hipFree(p_); p_ = nullptr; }
+    }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+
+   private:
+    T* p_ = nullptr;
+};
+
+template <typename T>
+class PinnedBuffer {
+   public:
+    PinnedBuffer() = default;
+    PinnedBuffer(PinnedBuffer&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    PinnedBuffer& operator=(PinnedBuffer&& o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    PinnedBuffer(const PinnedBuffer&) = delete;
+    PinnedBuffer& operator=(const PinnedBuffer&) = delete;
+    ~PinnedBuffer() { reset(); }
+
+    hipError_t alloc(size_t n) {
+        reset();
+        const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p_), std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault);
+        if (e != hipSuccess) p_ = nullptr;
+        return e;
+    }
+    void reset() {
+        if (p_) { (void)hipHostFree(p_); p_ = nullptr; }
+    }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+
+   private:
+    T* p_ = nullptr;
+};
+
+}  // namespace apex

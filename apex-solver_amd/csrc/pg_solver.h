@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "device_buffer.h"
 #include "lm_loop.h"
 #include "pg2_kernels.h"
 #include "pg_kernels.h"
@@ -126,25 +127,28 @@ class PoseGraphSolver : public LmBackend {
     std::vector<int64_t> pose_col_;
     std::vector<int> vmap_;  // caller's vertex -> internal vertex
     hipStream_t stream_ = nullptr;
+    // destroys stream_ when the members below it are gone: ~PoseGraphSolver synchronises the stream, then the buffers (and the
+    // plan) are freed in reverse order of declaration, then this runs
+    struct StreamLast { hipStream_t& s; ~StreamLast() { if (s) (void)hipStreamDestroy(s); } } stream_last_{stream_};
     TilePlan tp_;
-    double *poses_[2] = {nullptr, nullptr}, *posep_[2] = {nullptr, nullptr};
-    uint32_t *e_from_ = nullptr, *e_to_ = nullptr;
+    DeviceBuffer<double> poses_[2], posep_[2];
+    DeviceBuffer<uint32_t> e_from_, e_to_;
     int n_prior_ = 0;
     int n_factor_flow_timeouts_ = 0;
     // one device round trip per LM iteration (round 5, as in Solver): the pivot flags are read at the solve's final wait, and the
     // step statistics and the trial cost the LM loop asks next ride on that wait too ("one_wait", "eager_step_eval")
     bool one_wait_ = true, eager_eval_ = true;
     int64_t step_serial_ = 0, eager_serial_ = -1;
-    double* eager_host_ = nullptr;   // pinned: [0..2] step statistics, [3] sum of squares at the trial point
-    uint32_t* prior_v_ = nullptr;
-    int *inc_ptr_ = nullptr, *prior_slot_ = nullptr;   // SE2 only: incident-edge CSR, the caller's index of each sorted prior
-    uint32_t* inc_edge_ = nullptr;
-    double* prior_data_ = nullptr;
-    double* prior_res_ = nullptr;   // staging of get_prior_residual
-    double* meas_ = nullptr;
-    uint8_t* fix_ = nullptr;
-    double *g_ = nullptr, *rhs_ = nullptr, *d_ = nullptr, *work_ = nullptr, *partial_ = nullptr, *scal_ = nullptr;
-    double* scale_ = nullptr;        // Jacobi scaling, internal order, [n_pad] with 1 on the padding
+    PinnedBuffer<double> eager_host_;   // [0..2] step statistics, [3] sum of squares at the trial point
+    DeviceBuffer<uint32_t> prior_v_;
+    DeviceBuffer<int> inc_ptr_, prior_slot_;   // SE2 only: incident-edge CSR, the caller's index of each sorted prior
+    DeviceBuffer<uint32_t> inc_edge_;
+    DeviceBuffer<double> prior_data_;
+    DeviceBuffer<double> prior_res_;   // staging of get_prior_residual
+    DeviceBuffer<double> meas_;
+    DeviceBuffer<uint8_t> fix_;
+    DeviceBuffer<double> g_, rhs_, d_, work_, partial_, scal_;
+    DeviceBuffer<double> scale_;       // Jacobi scaling, internal order, [n_pad] with 1 on the padding
     std::vector<double> scale_h_;
     bool scaled_ = false;
     int n_partial_ = 256;

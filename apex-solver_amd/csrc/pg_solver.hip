@@ -19,24 +19,6 @@ namespace apex {
         if (_e != hipSuccess) return check_hip(_e, #expr); \
     } while (0)
 
-template <typename T>
-static hipError_t dev_alloc(T** p, size_t n) {
-    return hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T));
-}
-template <typename T>
-static hipError_t upload(T** dptr, const std::vector<T>& hv) {
-    if (*dptr) { (void)hipFree(*dptr); *dptr = nullptr; }
-    hipError_t e = dev_alloc(dptr, hv.size());
-    if (e != hipSuccess || hv.empty()) return e;
-    return hipMemcpy(*dptr, hv.data(), hv.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-static hipError_t alloc_zero(double** p, size_t n) {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    hipError_t e = dev_alloc(p, n);
-    if (e != hipSuccess) return e;
-    return hipMemset(*p, 0, std::max<size_t>(n, 1) * sizeof(double));
-}
-
 PoseGraphSolver::PoseGraphSolver(int64_t n_v, int64_t n_e, int device, int manifold)
     : n_v_(n_v), n_e_(n_e), device_(device), manifold_(manifold == kManifoldSE2 ? kManifoldSE2 : kManifoldSE3),
       dof_(manifold_ == kManifoldSE2 ? 3 : 6), amb_(manifold_ == kManifoldSE2 ? 3 : 7),
@@ -44,12 +26,7 @@ PoseGraphSolver::PoseGraphSolver(int64_t n_v, int64_t n_e, int device, int manif
 
 PoseGraphSolver::~PoseGraphSolver() {
     (void)hipSetDevice(device_);
-    if (stream_) (void)hipStreamSynchronize(stream_);
-    if (eager_host_) (void)hipHostFree(eager_host_);
-    void* ptrs[] = {poses_[0], poses_[1], posep_[0], posep_[1], e_from_, e_to_, meas_, fix_, g_, rhs_, d_, work_, partial_, scal_, scale_, prior_v_, prior_data_, prior_res_, inc_ptr_, inc_edge_, prior_slot_};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (stream_) (void)hipStreamDestroy(stream_);
+    if (stream_) (void)hipStreamSynchronize(stream_);   // before any buffer is freed; stream_last_ destroys the stream after them
 }
 
 int PoseGraphSolver::check_hip(hipError_t e, const char* what) {
@@ -108,13 +85,19 @@ int PoseGraphSolver::set_priors(int64_t n, const uint32_t* vertex, const double*
         if ((int64_t)vertex[k] >= n_v_) return fail(kInvalidInput, "prior on a vertex that does not exist");
     HIP_TRY(hipSetDevice(device_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    if (prior_v_) { (void)hipFree(prior_v_); prior_v_ = nullptr; }
-    if (prior_data_) { (void)hipFree(prior_data_); prior_data_ = nullptr; }
-    if (prior_res_) { (void)hipFree(prior_res_); prior_res_ = nullptr; }
-    if (prior_slot_) { (void)hipFree(prior_slot_); prior_slot_ = nullptr; }
-    n_prior_ = (int)n;
     have_step_ = have_trial_ = false;
-    if (n == 0) return kOk;
+    // The new set goes up into locals and replaces the members (and n_prior_) only when every upload has succeeded: a failed
+    // call leaves the old priors fully in place, a call with n = 0 none at all.
+    DeviceBuffer<uint32_t> new_v;
+    DeviceBuffer<double> new_data;
+    DeviceBuffer<int> new_slot;
+    auto install = [&] {
+        prior_v_ = std::move(new_v); prior_data_ = std::move(new_data); prior_slot_ = std::move(new_slot);
+        prior_res_.reset();   // (sized by the old count: get_prior_residual allocates it again)
+        n_prior_ = (int)n;
+        return kOk;
+    };
+    if (n == 0) return install();
     std::vector<uint32_t> hv((size_t)n);
     std::vector<double> hd((size_t)n * stride_, 0.0);
     // SE2: the blocks go to the device sorted by vertex (stable), so that one lane sums the run of a vertex in a fixed
@@ -129,19 +112,17 @@ int PoseGraphSolver::set_priors(int64_t n, const uint32_t* vertex, const double*
         memcpy(hd.data() + (size_t)k * stride_, data7 + (size_t)amb_ * src, amb_ * sizeof(double));
         hd[(size_t)k * stride_ + amb_] = huber_delta ? huber_delta[src] : -1.0;
     }
-    if (manifold_ == kManifoldSE2) HIP_TRY(upload(&prior_slot_, order));
-    HIP_TRY(hipMalloc(&prior_v_, hv.size() * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&prior_data_, hd.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(prior_v_, hv.data(), hv.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(prior_data_, hd.data(), hd.size() * sizeof(double), hipMemcpyHostToDevice));
-    return kOk;
+    if (manifold_ == kManifoldSE2) HIP_TRY(new_slot.upload(order));
+    HIP_TRY(new_v.upload(hv));
+    HIP_TRY(new_data.upload(hd));
+    return install();
 }
 
 int PoseGraphSolver::get_prior_residual(double* r7_out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     if (n_prior_ == 0) return kOk;
     HIP_TRY(hipSetDevice(device_));
-    if (!prior_res_) HIP_TRY(hipMalloc(&prior_res_, (size_t)n_prior_ * amb_ * sizeof(double)));   // kept with the priors (set_priors frees it)
+    if (!prior_res_) HIP_TRY(prior_res_.alloc((size_t)n_prior_ * amb_));   // kept with the priors (set_priors frees it)
     if (manifold_ == kManifoldSE2) launch_pg2_prior_export(view2(cur_), prior_res_, stream_);
     else launch_pg_prior_export(view(cur_), prior_res_, stream_);
     HIP_TRY(hipMemcpyAsync(r7_out, prior_res_, (size_t)n_prior_ * amb_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
@@ -200,23 +181,23 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
     if (manifold_ == kManifoldSE2) {   // the row-owned assembly walks each vertex's incident edges
         IncidentLists inc;
         if (!build_incident_lists(n_v_, n_e_, ef.data(), et.data(), &inc)) return fail(kInvalidInput, "incident-edge lists: out of range");
-        HIP_TRY(upload(&inc_ptr_, inc.ptr));
-        HIP_TRY(upload(&inc_edge_, inc.edge));
+        HIP_TRY(inc_ptr_.upload(inc.ptr));
+        HIP_TRY(inc_edge_.upload(inc.edge));
     }
-    HIP_TRY(upload(&e_from_, ef));
-    HIP_TRY(upload(&e_to_, et));
-    HIP_TRY(upload(&meas_, mp));
-    HIP_TRY(upload(&fix_, fx));
+    HIP_TRY(e_from_.upload(ef));
+    HIP_TRY(e_to_.upload(et));
+    HIP_TRY(meas_.upload(mp));
+    HIP_TRY(fix_.upload(fx));
     for (int w = 0; w < 2; ++w) {
-        HIP_TRY(alloc_zero(&poses_[w], amb_ * (size_t)n_v_));
-        HIP_TRY(alloc_zero(&posep_[w], stride_ * (size_t)n_v_));
+        HIP_TRY(poses_[w].alloc_zero(amb_ * (size_t)n_v_));
+        HIP_TRY(posep_[w].alloc_zero(stride_ * (size_t)n_v_));
     }
-    HIP_TRY(alloc_zero(&g_, n_pad_));
-    HIP_TRY(alloc_zero(&rhs_, n_pad_));
-    HIP_TRY(alloc_zero(&d_, n_pad_));
-    HIP_TRY(alloc_zero(&work_, 6 * (size_t)n_pad_));   // (TilePlan::solve workspace)
-    HIP_TRY(alloc_zero(&partial_, 3 * (size_t)n_partial_));
-    HIP_TRY(alloc_zero(&scal_, 16));
+    HIP_TRY(g_.alloc_zero(n_pad_));
+    HIP_TRY(rhs_.alloc_zero(n_pad_));
+    HIP_TRY(d_.alloc_zero(n_pad_));
+    HIP_TRY(work_.alloc_zero(6 * (size_t)n_pad_));   // (TilePlan::solve workspace)
+    HIP_TRY(partial_.alloc_zero(3 * (size_t)n_partial_));
+    HIP_TRY(scal_.alloc_zero(16));
     HIP_TRY(hipDeviceSynchronize());
     have_structure_ = true;
     have_params_ = have_step_ = have_trial_ = false;
@@ -325,7 +306,7 @@ int PoseGraphSolver::solve_augmented(double lambda, int variant, double* step_ou
         timer_.end(kPgTriSolve, stream_);
         have_step_ = true;
         if (eager_eval_) {   // what the LM loop asks next rides on this solve's wait (step_stats, eval_step)
-            if (!eager_host_) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&eager_host_), 8 * sizeof(double), hipHostMallocDefault));
+            if (!eager_host_) HIP_TRY(eager_host_.alloc(8));
             enqueue_step_stats();
             enqueue_trial_point(scal_ + 4);
             HIP_TRY(hipMemcpyAsync(eager_host_, scal_ + 1, 4 * sizeof(double), hipMemcpyDeviceToHost, stream_));
@@ -454,7 +435,7 @@ int PoseGraphSolver::parameter_norm(double* out) {
 // ---- Jacobi column scaling (process_jacobian_generic, optimizer/mod.rs:749-763) -------------------
 int PoseGraphSolver::ensure_scale_buffer() {
     if (scale_) return kOk;
-    HIP_TRY(dev_alloc(&scale_, (size_t)n_pad_));
+    HIP_TRY(scale_.alloc((size_t)n_pad_));
     std::vector<double> ones(n_pad_, 1.0);
     HIP_TRY(hipMemcpy(scale_, ones.data(), n_pad_ * sizeof(double), hipMemcpyHostToDevice));
     return kOk;
@@ -524,27 +505,25 @@ int PoseGraphSolver::lm_optimize(LmConfig* cfg, LmResult* res, LmIterRecord* his
 int PoseGraphSolver::get_residual(double* r_out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    double* d = nullptr;
-    HIP_TRY(dev_alloc(&d, dof_ * (size_t)n_e_));
+    DeviceBuffer<double> d;
+    HIP_TRY(d.alloc(dof_ * (size_t)n_e_));
     if (manifold_ == kManifoldSE2) launch_pg2_export(view2(cur_), d, nullptr, stream_);
     else launch_pg_export(view(cur_), d, nullptr, stream_);
     hipError_t e = hipMemcpyAsync(r_out, d, dof_ * n_e_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     (void)hipStreamSynchronize(stream_);
-    (void)hipFree(d);
     return check_hip(e, "get_residual");
 }
 
 int PoseGraphSolver::get_jacobian_blocks(double* j_out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    double* d = nullptr;
+    DeviceBuffer<double> d;
     const size_t jn = 2 * (size_t)dof_ * dof_;   // [dof][2 dof] per edge
-    HIP_TRY(dev_alloc(&d, jn * (size_t)n_e_));
+    HIP_TRY(d.alloc(jn * (size_t)n_e_));
     if (manifold_ == kManifoldSE2) launch_pg2_export(view2(cur_), nullptr, d, stream_);
     else launch_pg_export(view(cur_), nullptr, d, stream_);
     hipError_t e = hipMemcpyAsync(j_out, d, jn * n_e_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     (void)hipStreamSynchronize(stream_);
-    (void)hipFree(d);
     return check_hip(e, "get_jacobian_blocks");
 }
 

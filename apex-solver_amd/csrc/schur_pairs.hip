@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "ba_device.hpp"
+#include "device_buffer.h"
 #include "host_parallel.h"
 
 namespace apex {
@@ -406,17 +407,16 @@ hipError_t launch_build_pair_recs_q(int64_t n_rows, const int* rows, const int* 
     if (e != hipSuccess) return e;
     e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
-    int* scratch = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&scratch), (size_t)std::max(n_runs, 1) * sizeof(int));
+    DeviceBuffer<int> scratch;
+    e = scratch.alloc((size_t)std::max(n_runs, 1));
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(scratch, 0, (size_t)std::max(n_runs, 1) * sizeof(int), s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_build_pair_recs_q, dim3((unsigned)n_rows), dim3(64), 0, s, n_rows, rows, run_ptr, run_cj, run_piece0, piece, task,
-                           cam_ptr, cam_obs, o_pt, pt_ptr, o_cam, scratch, recs, pair_queue_len(9), pair_queues(9));
+                           cam_ptr, cam_obs, o_pt, pt_ptr, o_cam, scratch.get(), recs, pair_queue_len(9), pair_queues(9));
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
-    (void)hipFree(scratch);
     return e;
 }
 

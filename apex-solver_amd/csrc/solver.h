@@ -12,6 +12,7 @@
 #include <utility>
 #include <vector>
 
+#include "device_buffer.h"
 #include "ba_kernels.h"
 #include "chol_kernels.h"
 #include "lm_loop.h"
@@ -225,20 +226,23 @@ class Solver : public LmBackend {
 
     // device
     hipStream_t stream_ = nullptr;
+    // destroys stream_ when the members below it are gone: ~Solver joins free_thread_ and synchronises the stream, then the
+    // buffers (and the plan) are freed in reverse order of declaration, then this runs
+    struct StreamLast { hipStream_t& s; ~StreamLast() { if (s) (void)hipStreamDestroy(s); } } stream_last_{stream_};
     // host -> device copies of caller (pageable) memory through two pinned chunks: the DMA of one overlaps the memcpy into the other
     int upload_staged(void* dst_dev, const void* src_host, size_t bytes);
-    void* pin_[2] = {nullptr, nullptr};
+    PinnedBuffer<char> pin_[2];
     hipEvent_t pin_ev_[2] = {nullptr, nullptr};
     bool pin_busy_[2] = {false, false};   // pin_ev_[b] has been recorded behind a DMA out of pin_[b] and not waited for yet
-    double *poses_[2] = {nullptr, nullptr}, *intr_[2] = {nullptr, nullptr}, *pts_[2] = {nullptr, nullptr};
-    double* camp_[2] = {nullptr, nullptr};  // prepared cameras of the two parameter sets
-    PairTask* ptasks_ = nullptr;     // rows_form_ 3: the sorted camera-pair list (schur_pairs.h)
-    PairChunk* pchunks_ = nullptr;
-    PairBlock* pblocks_ = nullptr;
-    PairRec* precs_ = nullptr;
-    PairQDesc* pqdesc_ = nullptr;    // rows_form_ 4 (and d_c = 9): the queued layout's descriptors, else null
-    uint8_t *o_slot_ = nullptr, *wg_cam_n_ = nullptr;   // camera staging lists of the landmark-major kernels (BAView::o_slot)
-    uint32_t* wg_cam_list_ = nullptr;
+    DeviceBuffer<double> poses_[2], intr_[2], pts_[2];
+    DeviceBuffer<double> camp_[2];  // prepared cameras of the two parameter sets
+    DeviceBuffer<PairTask> ptasks_;     // rows_form_ 3: the sorted camera-pair list (schur_pairs.h)
+    DeviceBuffer<PairChunk> pchunks_;
+    DeviceBuffer<PairBlock> pblocks_;
+    DeviceBuffer<PairRec> precs_;
+    DeviceBuffer<PairQDesc> pqdesc_;    // rows_form_ 4 (and d_c = 9): the queued layout's descriptors, else null
+    DeviceBuffer<uint8_t> o_slot_, wg_cam_n_;   // camera staging lists of the landmark-major kernels (BAView::o_slot)
+    DeviceBuffer<uint32_t> wg_cam_list_;
     bool matrix_free_only_opt_ = false;   // the caller's option ("matrix_free_only")
     bool matrix_free_only_ = false;       // the effective state of the structure that is built: the option, or the automatic selection
     bool one_wait_ = true;   // "one_wait": one host wait per Cholesky solve (solve_augmented); 0 = three, as in rounds 1-4
@@ -250,8 +254,8 @@ class Solver : public LmBackend {
     bool eager_eval_ = true;
     bool trial_pts_written_ = false;   // the back-substitution of this solve has written the trial points (enqueue_trial_point skips them)
     int64_t step_serial_ = 0, eager_serial_ = -1;
-    double* eager_host_ = nullptr;               // pinned: [0..5] step statistics, [6] sum of squares at the trial point
-    double* pcg_host_ = nullptr;                 // pinned: two slots of the matrix-free PCG's scalars (read one iteration behind)
+    PinnedBuffer<double> eager_host_;            // [0..5] step statistics, [6] sum of squares at the trial point
+    PinnedBuffer<double> pcg_host_;              // two slots of the matrix-free PCG's scalars (read one iteration behind)
     hipEvent_t pcg_ev_[2] = {nullptr, nullptr};
     bool device_pair_recs_ = true;   // queued layout: the pair records are written by the device (k_build_pair_recs_q), not built on the host and copied
     bool auto_variant_ = true, auto_fallback_ = false;   // see set_auto_variant
@@ -265,8 +269,8 @@ class Solver : public LmBackend {
     // landmark covariance pass (landmark_covariance): built on the first call
     int lc_setup();
     void lc_release();
-    int *lc_lists_ = nullptr, *lc_err_ = nullptr;   // [small | large] landmark lists, error word
-    double* lc_out_ = nullptr;                      // [n_pt][9], internal order
+    DeviceBuffer<int> lc_lists_, lc_err_;   // [small | large] landmark lists, error word
+    DeviceBuffer<double> lc_out_;           // [n_pt][9], internal order
     int lc_n_small_ = 0, lc_n_large_ = 0;
     int64_t lc_pairs_ = 0;
     size_t lc_bytes_ = 0;
@@ -274,7 +278,7 @@ class Solver : public LmBackend {
     double lc_ms_ = 0.0;
     bool orec_fresh_ = false;   // orec_ holds the records of the current parameters' last linearisation
     const double* backsub_records() const { return orec_fresh_ ? orec_ : nullptr; }   // the projection records of THIS linearisation
-    double* orec_ = nullptr;   // [local observations][4] projection records written by k_landmark_reduce (pair kernel, record form)
+    DeviceBuffer<double> orec_;   // [local observations][4] projection records written by k_landmark_reduce (pair kernel, record form)
     int n_ptasks_ = 0;
     int64_t n_pair_blocks_ = 0, n_pair_slots_ = 0;
     bool pair_queued_ = false;       // what build_pair_lists arrived at (PairLists::queued)
@@ -283,16 +287,15 @@ class Solver : public LmBackend {
                                      // S(ci, cj) stored once by one wave, no atomics, no LDS accumulators: what six-column cameras
                                      // run).  Select before set_structure.  (Rounds 1-3 also carried a global-atomics form, 135 ms,
                                      // and two LDS row forms, 9.7 / 6.0 ms: deleted in rounds 4 and 6.)
-    uint32_t *o_cam_ = nullptr, *o_pt_ = nullptr, *co_pt_ = nullptr;
-    double2* co_uv_ = nullptr;
-    int* co_rank_ = nullptr;
-    double2* o_uv_ = nullptr;
-    int *o_orig_ = nullptr, *pt_ptr_ = nullptr, *cam_ptr_ = nullptr, *cam_obs_ = nullptr;
-    uint8_t *fix_pose_ = nullptr, *fix_intr_ = nullptr, *fix_pt_ = nullptr;
+    DeviceBuffer<uint32_t> o_cam_, o_pt_, co_pt_;
+    DeviceBuffer<double> o_uv_, co_uv_;   // [local observations][2]: BAView reads them as double2
+    DeviceBuffer<int> co_rank_;
+    DeviceBuffer<int> o_orig_, pt_ptr_, cam_ptr_, cam_obs_;
+    DeviceBuffer<uint8_t> fix_pose_, fix_intr_, fix_pt_;
     TilePlan tp_;  // tiles of S, their factorisation and solves
-    double *g_c_ = nullptr, *g_red_ = nullptr, *dcam_ = nullptr, *hinv_ = nullptr, *g_l_ = nullptr, *dl_ = nullptr;
-    double *partial_ = nullptr, *scal_ = nullptr;  // reduction scratch, scalar outputs
-    int* flags_ = nullptr;                          // [0] landmark inversion error
+    DeviceBuffer<double> g_c_, g_red_, dcam_, hinv_, g_l_, dl_;
+    DeviceBuffer<double> partial_, scal_;  // reduction scratch, scalar outputs
+    DeviceBuffer<int> flags_;              // [0] landmark inversion error
     std::vector<int> cmap_, cinv_;   // external camera -> internal camera and back
     bool use_nd_ = true;
     bool hubs_last_ = true;     // order cameras covisible with > max(16, 10 sqrt(n_cam)) others last (ba_structure.h)
@@ -303,10 +306,10 @@ class Solver : public LmBackend {
     bool tree_shard_ = false;   // what set_structure arrived at
     int dist_selftest_ = 0;
     std::vector<int> lmap_;     // external landmark -> internal landmark (identity unless tree sharded)
-    uint8_t* lam_mask_ = nullptr;  // tree sharding: cameras whose diagonal block gets lambda on this rank
-    double* pcg_buf_ = nullptr;                    // 7 vectors of n_c_pad
-    double *lmu_ = nullptr, *sd_ = nullptr, *minv_ = nullptr;  // matrix-free variant: {pt, u_l} records, diag blocks of S, their inverses
-    double *cam_scale_ = nullptr, *pt_scale_ = nullptr;   // Jacobi scaling, internal order ([n_c_pad] with 1 on the padding, [3 n_pt])
+    DeviceBuffer<uint8_t> lam_mask_;  // tree sharding: cameras whose diagonal block gets lambda on this rank
+    DeviceBuffer<double> pcg_buf_;                 // 7 vectors of n_c_pad
+    DeviceBuffer<double> lmu_, sd_, minv_;  // matrix-free variant: {pt, u_l} records, diag blocks of S, their inverses
+    DeviceBuffer<double> cam_scale_, pt_scale_;   // Jacobi scaling, internal order ([n_c_pad] with 1 on the padding, [3 n_pt])
     std::vector<double> cam_scale_h_, pt_scale_h_;
     bool scaled_ = false;
     int n_partial_ = 1024;

@@ -29,11 +29,6 @@ void warm_chol_kernels(hipStream_t s);
         if (!(expr)) return fail(kDeviceError, comm_->error());                         \
     } while (0)
 
-template <typename T>
-static hipError_t dev_alloc(T** p, size_t n) {
-    return hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T));
-}
-
 // OptimizeParams<POSE, LANDMARK, INTRINSIC> of every mode as 4 POSE + 2 LANDMARK + INTRINSIC (src/factors/mod.rs:82-101)
 int mode_mask(int mode) {
     static const int m[7] = {6 /* BundleAdjustment */, 7 /* SelfCalibration */, 4 /* OnlyPose */, 2 /* OnlyLandmarks */,
@@ -51,22 +46,10 @@ Solver::~Solver() {
     if (free_thread_.joinable()) free_thread_.join();
     HostBlockCache::get().release();   // the last handle returns the cached blocks to the system
     hipSetDevice(device_);
-    if (stream_) hipStreamSynchronize(stream_);
-    void* ptrs[] = {poses_[0], poses_[1], intr_[0], intr_[1], pts_[0], pts_[1], camp_[0], camp_[1], ptasks_, pchunks_, pblocks_, precs_, pqdesc_, orec_, o_slot_, wg_cam_n_, wg_cam_list_, o_cam_, o_pt_, o_uv_, o_orig_, pt_ptr_,
-                    cam_ptr_, cam_obs_, co_pt_, co_uv_, co_rank_, fix_pose_, fix_intr_, fix_pt_, g_c_, g_red_,
-                    dcam_, hinv_, g_l_, dl_, partial_, scal_, flags_, pcg_buf_, lmu_, sd_, minv_, cam_scale_, pt_scale_, lam_mask_};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    lc_release();
+    if (stream_) hipStreamSynchronize(stream_);   // (and the join above) before any buffer is freed; stream_last_ destroys the stream after them
     comm_.reset();
-    if (pcg_host_) (void)hipHostFree(pcg_host_);
-    if (eager_host_) (void)hipHostFree(eager_host_);
     for (hipEvent_t e : pcg_ev_) if (e) (void)hipEventDestroy(e);
-    for (int b = 0; b < 2; ++b) {
-        if (pin_[b]) (void)hipHostFree(pin_[b]);
-        if (pin_ev_[b]) (void)hipEventDestroy(pin_ev_[b]);
-    }
-    if (stream_) hipStreamDestroy(stream_);
+    for (hipEvent_t e : pin_ev_) if (e) (void)hipEventDestroy(e);
 }
 
 // A hipMemcpy from pageable memory is staged by the runtime in small pieces (0.19 s for the 107 MB of final-13682's points:
@@ -76,7 +59,7 @@ int Solver::upload_staged(void* dst_dev, const void* src_host, size_t bytes) {
     constexpr size_t kChunk = (size_t)16 << 20;
     if (bytes <= ((size_t)1 << 20)) return check_hip(hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, stream_), "upload");
     for (int b = 0; b < 2; ++b) {
-        if (!pin_[b]) HIP_TRY(hipHostMalloc(&pin_[b], kChunk, hipHostMallocDefault));
+        if (!pin_[b]) HIP_TRY(pin_[b].alloc(kChunk));
         if (!pin_ev_[b]) HIP_TRY(hipEventCreateWithFlags(&pin_ev_[b], hipEventDisableTiming));
     }
     size_t i = 0;
@@ -108,10 +91,10 @@ BAView Solver::view(int which) const {
     BAView v;
     v.n_cam = n_cam_; v.n_pt = n_pt_; v.n_obs = (int64_t)o_orig_h_.size();
     v.camp = camp_[which]; v.camq = camp_[which] + (size_t)kCamStride * n_cam_; v.pts = pts_[which];
-    v.o_cam = o_cam_; v.o_pt = o_pt_; v.o_uv = o_uv_; v.pt_ptr = pt_ptr_;
+    v.o_cam = o_cam_; v.o_pt = o_pt_; v.o_uv = reinterpret_cast<const double2*>(o_uv_.get()); v.pt_ptr = pt_ptr_;
     v.huber_delta = huber_delta_;
     v.mask_code = mode_mask(mode_);
-    v.co_pt = co_pt_; v.co_uv = co_uv_; v.co_rank = co_rank_;
+    v.co_pt = co_pt_; v.co_uv = reinterpret_cast<const double2*>(co_uv_.get()); v.co_rank = co_rank_;
     v.cam_scale = scaled_ ? cam_scale_ : nullptr;
     v.pt_scale = scaled_ ? pt_scale_ : nullptr;
     v.lam_mask = tree_shard_ ? lam_mask_ : nullptr;
@@ -194,9 +177,8 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     // APEX_SETUP_TRACE in bench.py, torch's context already there), the code objects of the three kernel files a few ms more:
     // both on a thread, beside the argument checks and the camera order (host only), joined in front of the first device call
     // below (device_ready) -- round 5.
-    double* raw_uv = nullptr;   // (device thread -> uploader thread, which joins the former through device_ready)
+    DeviceBuffer<double> raw_uv;   // (device thread -> uploader thread, which joins the former through device_ready)
     const bool raw_uv_wanted = device_gathers_ && world_ == 1 && !(comm_ && world_ > 1);
-    struct RawFree { double*& p; ~RawFree() { if (p) { (void)hipFree(p); p = nullptr; } } } raw_free{raw_uv};
     std::promise<hipError_t> init_p;
     std::shared_future<hipError_t> init_f = init_p.get_future().share();
     std::promise<bool> validated_p;   // (the 0.5 GB copy of the measurements does not start for a call that is about to be refused)
@@ -209,9 +191,9 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
         wt.mark("device thread: device, stream");
         if (e != hipSuccess) return;
         if (raw_uv_wanted && validated_f.get()) {   // the caller's measurements as they are, beside the host's list building -- once the lists are valid
-            if (hipMalloc(reinterpret_cast<void**>(&raw_uv), std::max<size_t>(2 * (size_t)n_obs_, 2) * sizeof(double)) != hipSuccess ||
+            if (raw_uv.alloc(std::max<size_t>(2 * (size_t)n_obs_, 2)) != hipSuccess ||
                 hipMemcpy(raw_uv, obs_uv, 2 * (size_t)n_obs_ * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-                if (raw_uv) { (void)hipFree(raw_uv); raw_uv = nullptr; }
+                raw_uv.reset();
                 (void)hipGetLastError();
             }
             wt.mark("device thread: measurements up");
@@ -337,11 +319,8 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     n_hubs_ = hs.n_hubs; n_border_tiles_ = hs.n_border_tiles;
     o_orig_h_.assign(hs.o_orig.begin(), hs.o_orig.end());
     n_pairs_ = hs.n_pairs; n_present_ = hs.n_present;
-    if (lam_mask_) { hipFree(lam_mask_); lam_mask_ = nullptr; }
-    if (tree_shard_) {
-        HIP_TRY(dev_alloc(&lam_mask_, hs.lam_mask.size()));
-        HIP_TRY(hipMemcpy(lam_mask_, hs.lam_mask.data(), hs.lam_mask.size(), hipMemcpyHostToDevice));
-    }
+    lam_mask_.reset();
+    if (tree_shard_) HIP_TRY(lam_mask_.upload(hs.lam_mask));
     // ---- uploads of everything that does not depend on the tile plan, on a thread of their own: the observation lists
     // (1.7 GB on final-13682), the camera staging lists, the masks and the work arrays go to the device while this thread
     // builds the tile plan and the pair list (round 5: 0.09 s of copies under 0.27 s of host work) -------------------------
@@ -351,20 +330,6 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     const auto &o_uv = hs.o_uv, &co_uv = hs.co_uv;
     const auto &pt_ptr = hs.pt_ptr, &cam_ptr = hs.cam_ptr;
     const auto &cam_obs = hs.cam_obs, &co_rank = hs.co_rank;
-    auto up = [&](auto** dptr, const auto& hv) -> hipError_t {
-        using T = typename std::remove_reference<decltype(hv)>::type::value_type;
-        if (*dptr) { hipFree(*dptr); *dptr = nullptr; }
-        hipError_t e = dev_alloc(reinterpret_cast<T**>(dptr), hv.size());
-        if (e != hipSuccess) return e;
-        if (hv.empty()) return hipSuccess;
-        return hipMemcpy(*dptr, hv.data(), hv.size() * sizeof(T), hipMemcpyHostToDevice);
-    };
-    auto alloc = [&](double** p, size_t n) -> hipError_t {
-        if (*p) { hipFree(*p); *p = nullptr; }
-        hipError_t e = dev_alloc(p, n);
-        if (e != hipSuccess) return e;
-        return hipMemset(*p, 0, std::max<size_t>(n, 1) * sizeof(double));
-    };
     // (the uploader thread keeps its own error text: err_ belongs to the calling thread)
     std::string up_err;
 #define UP_TRY(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) { up_err = std::string("HIP error in " #expr ": ") + hipGetErrorString(_e); return (int)kDeviceError; } } while (0)
@@ -392,17 +357,17 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
                 }
             });
             static_assert(kCamStageCap <= 254, "slot 255 means not staged");
-            UP_TRY(up(&o_slot_, slot));
-            UP_TRY(up(&wg_cam_n_, wn));
-            UP_TRY(up(&wg_cam_list_, wlist));
+            UP_TRY(o_slot_.upload(slot));
+            UP_TRY(wg_cam_n_.upload(wn));
+            UP_TRY(wg_cam_list_.upload(wlist));
         }
-        UP_TRY(up(&o_cam_, o_cam));
-        UP_TRY(up(&o_pt_, o_pt));
-        UP_TRY(up(&o_orig_, o_orig_h_));
-        UP_TRY(up(&pt_ptr_, pt_ptr));
-        UP_TRY(up(&cam_ptr_, cam_ptr));
-        UP_TRY(up(&cam_obs_, cam_obs));
-        UP_TRY(up(&co_rank_, co_rank));
+        UP_TRY(o_cam_.upload(o_cam));
+        UP_TRY(o_pt_.upload(o_pt));
+        UP_TRY(o_orig_.upload(o_orig_h_));
+        UP_TRY(pt_ptr_.upload(pt_ptr));
+        UP_TRY(cam_ptr_.upload(cam_ptr));
+        UP_TRY(cam_obs_.upload(cam_obs));
+        UP_TRY(co_rank_.upload(co_rank));
         if (so.device_gathers) {
             // the caller's measurements go up as they are (one contiguous copy, no host gather), the three lists that are
             // permutations of what is on the device already are made there
@@ -411,32 +376,28 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
             double* raw = raw_uv;
             hipError_t ge = hipSuccess;
             if (!raw) {
-                UP_TRY(hipMalloc(reinterpret_cast<void**>(&raw_uv), std::max<size_t>(2 * (size_t)n_obs_, 2) * sizeof(double)));
+                UP_TRY(raw_uv.alloc(std::max<size_t>(2 * (size_t)n_obs_, 2)));
                 raw = raw_uv;
                 ge = hipMemcpy(raw, obs_uv, 2 * (size_t)n_obs_ * sizeof(double), hipMemcpyHostToDevice);
             }
-            // (plain allocations: every element is written by the gathers.  NOT the zero-filling alloc -- its hipMemset runs on the
+            // (plain allocations: every element is written by the gathers.  NOT alloc_zero -- its hipMemset runs on the
             // null stream, which stream_ (non-blocking) does not follow: the clear could land AFTER the gather had written the
             // array; seen once in 36 problems of the population test as a step of garbage)
-            auto fresh = [](auto** pp, size_t n) -> hipError_t {
-                if (*pp) { (void)hipFree(*pp); *pp = nullptr; }
-                return hipMalloc(reinterpret_cast<void**>(pp), std::max<size_t>(n, 1) * sizeof(**pp));
-            };
-            if (ge == hipSuccess) ge = fresh(reinterpret_cast<double**>(&o_uv_), 2 * n_loc);
-            if (ge == hipSuccess) ge = fresh(reinterpret_cast<double**>(&co_uv_), 2 * n_loc);
-            if (ge == hipSuccess) ge = fresh(&co_pt_, n_loc);
+            if (ge == hipSuccess) ge = o_uv_.alloc(2 * n_loc);
+            if (ge == hipSuccess) ge = co_uv_.alloc(2 * n_loc);
+            if (ge == hipSuccess) ge = co_pt_.alloc(n_loc);
             if (ge == hipSuccess) {
-                launch_gather_uv((int64_t)n_loc, o_orig_, raw, reinterpret_cast<double*>(o_uv_), stream_);
-                launch_gather_uv((int64_t)n_loc, cam_obs_, reinterpret_cast<const double*>(o_uv_), reinterpret_cast<double*>(co_uv_), stream_);
+                launch_gather_uv((int64_t)n_loc, o_orig_, raw, o_uv_, stream_);
+                launch_gather_uv((int64_t)n_loc, cam_obs_, o_uv_, co_uv_, stream_);
                 launch_gather_u32((int64_t)n_loc, cam_obs_, o_pt_, co_pt_, stream_);
                 ge = hipStreamSynchronize(stream_);
             }
-            (void)hipFree(raw_uv); raw_uv = nullptr;
+            raw_uv.reset();
             UP_TRY(ge);
         } else {
-            UP_TRY(up(reinterpret_cast<double**>(&o_uv_), o_uv));
-            UP_TRY(up(&co_pt_, co_pt));
-            UP_TRY(up(reinterpret_cast<double**>(&co_uv_), co_uv));
+            UP_TRY(o_uv_.upload(o_uv));
+            UP_TRY(co_pt_.upload(co_pt));
+            UP_TRY(co_uv_.upload(co_uv));
         }
         {
             std::vector<uint8_t> fp(6 * n_cam_, 0), fi(3 * n_cam_, 0), fl(3 * n_pt_, 0);
@@ -446,35 +407,33 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
             }
             if (fix_pt)
                 for (int64_t l = 0; l < n_pt_; ++l) memcpy(fl.data() + 3 * (size_t)lmap_[l], fix_pt + 3 * l, 3);
-            UP_TRY(up(&fix_pose_, fp));
-            UP_TRY(up(&fix_intr_, fi));
-            UP_TRY(up(&fix_pt_, fl));
+            UP_TRY(fix_pose_.upload(fp));
+            UP_TRY(fix_intr_.upload(fi));
+            UP_TRY(fix_pt_.upload(fl));
         }
         for (int w = 0; w < 2; ++w) {
-            UP_TRY(alloc(&poses_[w], 7 * n_cam_));
-            UP_TRY(alloc(&intr_[w], 3 * n_cam_));
-            UP_TRY(alloc(&pts_[w], 3 * n_pt_));
-            UP_TRY(alloc(&camp_[w], (size_t)(kCamStride + kCamQStride) * n_cam_));   // [n_cam][16] records | [n_cam][10] compact form
+            UP_TRY(poses_[w].alloc_zero(7 * n_cam_));
+            UP_TRY(intr_[w].alloc_zero(3 * n_cam_));
+            UP_TRY(pts_[w].alloc_zero(3 * n_pt_));
+            UP_TRY(camp_[w].alloc_zero((size_t)(kCamStride + kCamQStride) * n_cam_));   // [n_cam][16] records | [n_cam][10] compact form
         }
-        UP_TRY(alloc(&g_c_, n_c_pad_));
-        UP_TRY(alloc(&g_red_, n_c_pad_));
-        UP_TRY(alloc(&dcam_, n_c_pad_));
-        UP_TRY(alloc(&hinv_, (size_t)kLmStride * n_pt_));  // landmark records: Hll^-1 | g_l | point
+        UP_TRY(g_c_.alloc_zero(n_c_pad_));
+        UP_TRY(g_red_.alloc_zero(n_c_pad_));
+        UP_TRY(dcam_.alloc_zero(n_c_pad_));
+        UP_TRY(hinv_.alloc_zero((size_t)kLmStride * n_pt_));  // landmark records: Hll^-1 | g_l | point
         // projection records of the local observations (xn, yn, p_w.z, sqrt(rho')): the record form of the pair kernel
-        UP_TRY(alloc(&orec_, 4 * (size_t)o_cam.size()));
-        UP_TRY(alloc(&g_l_, 3 * n_pt_));
-        UP_TRY(alloc(&dl_, 3 * n_pt_));
-        UP_TRY(alloc(&partial_, 3 * (size_t)n_partial_));
-        UP_TRY(alloc(&scal_, 32));
-        UP_TRY(alloc(&pcg_buf_, 7 * (size_t)n_c_pad_));
-        UP_TRY(alloc(&lmu_, (size_t)kLmuStride * n_pt_));
-        UP_TRY(alloc(&sd_, (size_t)n_cam_ * dc_ * dc_));
-        UP_TRY(alloc(&minv_, (size_t)n_cam_ * dc_ * dc_));
-        if (flags_) hipFree(flags_);
-        UP_TRY(dev_alloc(&flags_, 4));
-        UP_TRY(hipMemset(flags_, 0, 4 * sizeof(int)));
+        UP_TRY(orec_.alloc_zero(4 * (size_t)o_cam.size()));
+        UP_TRY(g_l_.alloc_zero(3 * n_pt_));
+        UP_TRY(dl_.alloc_zero(3 * n_pt_));
+        UP_TRY(partial_.alloc_zero(3 * (size_t)n_partial_));
+        UP_TRY(scal_.alloc_zero(32));
+        UP_TRY(pcg_buf_.alloc_zero(7 * (size_t)n_c_pad_));
+        UP_TRY(lmu_.alloc_zero((size_t)kLmuStride * n_pt_));
+        UP_TRY(sd_.alloc_zero((size_t)n_cam_ * dc_ * dc_));
+        UP_TRY(minv_.alloc_zero((size_t)n_cam_ * dc_ * dc_));
+        UP_TRY(flags_.alloc_zero(4));
         for (int b = 0; b < 2; ++b) {   // the pinned chunks of upload_staged: mapped here, not in the caller's first set_params
-            if (!pin_[b]) UP_TRY(hipHostMalloc(&pin_[b], (size_t)16 << 20, hipHostMallocDefault));
+            if (!pin_[b]) UP_TRY(pin_[b].alloc((size_t)16 << 20));
             if (!pin_ev_[b]) UP_TRY(hipEventCreateWithFlags(&pin_ev_[b], hipEventDisableTiming));
         }
         up_seconds = since(t0);
@@ -508,34 +467,31 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     hs.release_scratch();
     tr.mark("plan + Schur lists (observation lists uploading beside them)");
     const auto t_up2 = std::chrono::steady_clock::now();
-    HIP_TRY(up(&ptasks_, pl.tasks));
-    HIP_TRY(up(&pchunks_, pl.chunks));
-    HIP_TRY(up(&pblocks_, pl.blocks));
+    HIP_TRY(ptasks_.upload(pl.tasks));
+    HIP_TRY(pchunks_.upload(pl.chunks));
+    HIP_TRY(pblocks_.upload(pl.blocks));
     if (recs_on_device && pl.queued) {
         // the records of the queued layout are written by the device from the observation lists the uploader put there
         // (schur_pairs.h, PairDeviceTables): 17 MB of tables up instead of 1.56 GB of records built and copied
-        int *d_rows = nullptr, *d_run_ptr = nullptr, *d_run_piece0 = nullptr;
-        uint32_t* d_run_cj = nullptr;
-        int2 *d_piece = nullptr, *d_task = nullptr;
-        if (precs_) { hipFree(precs_); precs_ = nullptr; }
-        hipError_t e = dev_alloc(&precs_, (size_t)dtab.n_slots);
-        if (e == hipSuccess) e = up(&d_rows, dtab.rows);
-        if (e == hipSuccess) e = up(&d_run_ptr, dtab.run_ptr);
-        if (e == hipSuccess) e = up(&d_run_cj, dtab.run_cj);
-        if (e == hipSuccess) e = up(&d_run_piece0, dtab.run_piece0);
-        if (e == hipSuccess) e = up(&d_piece, dtab.piece);
-        if (e == hipSuccess) e = up(&d_task, dtab.task);
+        DeviceBuffer<int> d_rows, d_run_ptr, d_run_piece0;   // (tables of this call only: freed on every way out of the block)
+        DeviceBuffer<uint32_t> d_run_cj;
+        DeviceBuffer<int2> d_piece, d_task;
+        hipError_t e = precs_.alloc((size_t)dtab.n_slots);
+        if (e == hipSuccess) e = d_rows.upload(dtab.rows);
+        if (e == hipSuccess) e = d_run_ptr.upload(dtab.run_ptr);
+        if (e == hipSuccess) e = d_run_cj.upload(dtab.run_cj);
+        if (e == hipSuccess) e = d_run_piece0.upload(dtab.run_piece0);
+        if (e == hipSuccess) e = d_piece.upload(dtab.piece);
+        if (e == hipSuccess) e = d_task.upload(dtab.task);
         if (e == hipSuccess)
             e = launch_build_pair_recs_q(n_cam_, d_rows, d_run_ptr, d_run_cj, d_run_piece0, d_piece, d_task, cam_ptr_, cam_obs_, o_pt_, pt_ptr_, o_cam_,
                                          precs_, dtab.n_slots, stream_);
-        for (void* q : {(void*)d_rows, (void*)d_run_ptr, (void*)d_run_cj, (void*)d_run_piece0, (void*)d_piece, (void*)d_task})
-            if (q) (void)hipFree(q);
         HIP_TRY(e);
     } else {
-        HIP_TRY(up(&precs_, pl.recs));
+        HIP_TRY(precs_.upload(pl.recs));
     }
-    if (pqdesc_) { hipFree(pqdesc_); pqdesc_ = nullptr; }
-    if (pl.queued) HIP_TRY(up(&pqdesc_, pl.qdesc));
+    pqdesc_.reset();
+    if (pl.queued) HIP_TRY(pqdesc_.upload(pl.qdesc));
     up_seconds += since(t_up2);
     (void)t_up;
 
@@ -852,7 +808,7 @@ int Solver::implicit_pcg_solve(double lambda, int max_iter, double tol) {
     double *x = dcam_, *r = pcg_buf_, *z = pcg_buf_ + n_c_pad_, *p = pcg_buf_ + 2 * n_c_pad_, *ap = pcg_buf_ + 3 * n_c_pad_;
     double* sc = scal_ + 16;   // [0] r.r  [1] r.z  [2] p.Ap  [4] rz_old  [5] frozen  [6] beta (chol_kernels.h)
     if (!pcg_host_) {
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&pcg_host_), 16 * sizeof(double), hipHostMallocDefault));
+        HIP_TRY(pcg_host_.alloc(16));
         for (hipEvent_t& ev : pcg_ev_) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
     HIP_TRY(hipMemsetAsync(x, 0, n_c_pad_ * sizeof(double), stream_));
@@ -954,7 +910,7 @@ int Solver::solve_augmented(double lambda, int variant, double* step_out, double
         HIP_TRY(hipGetLastError());
         have_step_ = true;
         if (eager) {
-            if (!eager_host_) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&eager_host_), 8 * sizeof(double), hipHostMallocDefault));
+            if (!eager_host_) HIP_TRY(eager_host_.alloc(8));
             rc = enqueue_step_stats();
             if (rc == kOk) rc = enqueue_trial_point(scal_ + 6);
             if (rc != kOk) return rc;
@@ -1227,8 +1183,8 @@ int Solver::parameter_norm(double* out) {
 // ---------------------------------------------------------------------------------------------
 int Solver::ensure_scale_buffers() {
     if (cam_scale_) return kOk;
-    HIP_TRY(dev_alloc(&cam_scale_, (size_t)n_c_pad_));
-    HIP_TRY(dev_alloc(&pt_scale_, (size_t)std::max<int64_t>(3 * n_pt_, 1)));
+    HIP_TRY(cam_scale_.alloc((size_t)n_c_pad_));
+    HIP_TRY(pt_scale_.alloc((size_t)(3 * n_pt_)));
     return kOk;
 }
 
@@ -1338,29 +1294,27 @@ int Solver::lm_optimize(LmConfig* cfg, LmResult* res, LmIterRecord* hist, int hi
 int Solver::get_residual(double* r_out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    double* d = nullptr;
-    HIP_TRY(dev_alloc(&d, 2 * n_obs_));
+    DeviceBuffer<double> d;
+    HIP_TRY(d.alloc(2 * n_obs_));
     hipMemsetAsync(d, 0, 2 * n_obs_ * sizeof(double), stream_);
     launch_export_linearization(dc_, view(cur_), o_orig_, d, nullptr, nullptr, stream_);
     hipError_t e = hipMemcpyAsync(r_out, d, 2 * n_obs_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     hipStreamSynchronize(stream_);
-    hipFree(d);
     return check_hip(e, "get_residual");
 }
 
 int Solver::get_jacobian_blocks(double* jc_out, double* jl_out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    double *dj = nullptr, *dl = nullptr;
-    HIP_TRY(dev_alloc(&dj, 2 * dc_ * n_obs_));
-    HIP_TRY(dev_alloc(&dl, 6 * n_obs_));
+    DeviceBuffer<double> dj, dl;
+    HIP_TRY(dj.alloc(2 * dc_ * n_obs_));
+    HIP_TRY(dl.alloc(6 * n_obs_));
     hipMemsetAsync(dj, 0, 2 * dc_ * n_obs_ * sizeof(double), stream_);
     hipMemsetAsync(dl, 0, 6 * n_obs_ * sizeof(double), stream_);
     launch_export_linearization(dc_, view(cur_), o_orig_, nullptr, dj, dl, stream_);
     hipError_t e1 = hipMemcpyAsync(jc_out, dj, 2 * dc_ * n_obs_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     hipError_t e2 = hipMemcpyAsync(jl_out, dl, 6 * n_obs_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     hipStreamSynchronize(stream_);
-    hipFree(dj); hipFree(dl);
     int rc = check_hip(e1, "get_jacobian_blocks");
     return rc != kOk ? rc : check_hip(e2, "get_jacobian_blocks");
 }
@@ -1620,10 +1574,7 @@ int Solver::camera_covariance(double* out) {
 }
 
 void Solver::lc_release() {
-    void* ptrs[] = {lc_lists_, lc_err_, lc_out_};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    lc_lists_ = lc_err_ = nullptr; lc_out_ = nullptr;
+    lc_lists_.reset(); lc_err_.reset(); lc_out_.reset();   // (null lc_out_: landmark_covariance sets up again)
     lc_n_small_ = lc_n_large_ = 0;
     lc_pairs_ = 0; lc_bytes_ = 0;
 }
@@ -1644,10 +1595,9 @@ int Solver::lc_setup() {
     std::stable_sort(large.begin(), large.end(), [&](int a, int b) { return ptr[a + 1] - ptr[a] > ptr[b + 1] - ptr[b]; });
     small.insert(small.end(), large.begin(), large.end());
     const size_t b_lists = std::max<size_t>(small.size(), 1) * sizeof(int), b_out = 9 * (size_t)n_pt_ * sizeof(double);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&lc_lists_), b_lists);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&lc_err_), sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&lc_out_), b_out);
-    if (e == hipSuccess) e = hipMemcpy(lc_lists_, small.data(), small.size() * sizeof(int), hipMemcpyHostToDevice);
+    hipError_t e = lc_lists_.upload(small);
+    if (e == hipSuccess) e = lc_err_.alloc(1);
+    if (e == hipSuccess) e = lc_out_.alloc(9 * (size_t)n_pt_);
     if (e != hipSuccess) { lc_release(); return check_hip(e, "landmark covariance set-up"); }
     lc_n_large_ = (int)large.size();
     lc_n_small_ = (int)(small.size() - large.size());

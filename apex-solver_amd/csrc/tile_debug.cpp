@@ -15,12 +15,9 @@
 struct apexgpu_tiles {
     int device = 0;
     hipStream_t stream = nullptr;
-    apex::TilePlan plan;
-    double *rhs = nullptr, *x = nullptr, *work = nullptr;   // kept for the handle's life: the captured sweeps hold their addresses
-    double* pcg_work = nullptr;                             // 6 * n_pad doubles, allocated by the first pcg call
-    ~apexgpu_tiles() {
-        for (double* p : {rhs, x, work, pcg_work}) if (p) (void)hipFree(p);
-    }
+    apex::DeviceBuffer<double> rhs, x, work;   // kept for the handle's life: the captured sweeps hold their addresses
+    apex::DeviceBuffer<double> pcg_work;       // 6 * n_pad doubles, allocated by the first pcg call
+    apex::TilePlan plan;                       // (declared last: its graph execs go before the buffers they point into)
 };
 
 namespace {
@@ -68,9 +65,9 @@ int apexgpu_debug_tiles_create(int device, int nt, const uint8_t* present, const
         std::string err;
         if (e == hipSuccess) err = tp.build(nt, std::vector<uint8_t>(present, present + (size_t)nt * nt), h->stream);
         const size_t n = (size_t)tp.n_pad();
-        if (e == hipSuccess && err.empty()) e = hipMalloc(reinterpret_cast<void**>(&h->rhs), n * sizeof(double));
-        if (e == hipSuccess && err.empty()) e = hipMalloc(reinterpret_cast<void**>(&h->x), n * sizeof(double));
-        if (e == hipSuccess && err.empty()) e = hipMalloc(reinterpret_cast<void**>(&h->work), 2 * n * sizeof(double));
+        if (e == hipSuccess && err.empty()) e = h->rhs.alloc(n);
+        if (e == hipSuccess && err.empty()) e = h->x.alloc(n);
+        if (e == hipSuccess && err.empty()) e = h->work.alloc(2 * n);
         if (e != hipSuccess || !err.empty()) {
             apexgpu_debug_tiles_destroy(h);
             return e != hipSuccess ? APEXGPU_ERR_DEVICE : APEXGPU_ERR_INVALID_STATE;
@@ -84,8 +81,8 @@ void apexgpu_debug_tiles_destroy(apexgpu_tiles* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     hipStream_t s = h->stream;
-    if (s) (void)hipStreamSynchronize(s);
-    delete h;   // (the plan releases its device memory; the stream is the handle's)
+    if (s) (void)hipStreamSynchronize(s);   // in this order: the stream drained, then the plan and the buffers, then the stream
+    delete h;
     if (s) (void)hipStreamDestroy(s);
 }
 
@@ -172,7 +169,7 @@ int apexgpu_debug_tiles_pcg(apexgpu_tiles* h, const double* rhs, int max_iter, d
     apex::TilePlan& tp = h->plan;
     const size_t n = (size_t)tp.n_pad();
     *iters = 0;
-    if (!h->pcg_work && hipMalloc(reinterpret_cast<void**>(&h->pcg_work), 6 * n * sizeof(double)) != hipSuccess) return APEXGPU_ERR_DEVICE;
+    if (!h->pcg_work && h->pcg_work.alloc(6 * n) != hipSuccess) return APEXGPU_ERR_DEVICE;
     hipError_t e = hipMemcpyAsync(h->rhs, rhs, n * sizeof(double), hipMemcpyHostToDevice, h->stream);
     // (as Solver::pcg_solve: the caller's limits go through unchanged; the plan's factor is void from here on)
     if (e == hipSuccess) e = tp.pcg(h->rhs, h->x, h->pcg_work, max_iter, tol, iters);

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "chol_kernels.h"
+#include "device_buffer.h"
 
 namespace apex {
 
@@ -39,7 +40,36 @@ struct SchedOp {
     int count;          // ... and how many
 };
 
-class TilePlan {
+// Everything a TilePlan allocates through HIP, as a base of its own: release() drops all of it with one assignment (no list
+// of members to keep in step), and the base is destroyed after ~TilePlan has destroyed the graph execs that point into it.
+struct TilePlanMemory {
+    DeviceBuffer<double> tiles_, linv_;
+    DeviceBuffer<int> slot_, diag_slot_, flag_;
+    DeviceBuffer<int> cls_;          // per tile column: 0 another rank's, 1 this rank's, 2 top (shared)
+    DeviceBuffer<double> exch_;
+    DeviceBuffer<int> gate_cnt_;     // [levels + 1] potrf workgroups that have started, per level
+    DeviceBuffer<PotrfTask> potrf_tasks_;
+    DeviceBuffer<GemmTask> trsm_tasks_, upd_tasks_;
+    DeviceBuffer<TriTask> tri_fwd_, tri_bwd_;
+    DeviceBuffer<FlowTask> flow_fwd_, flow_bwd_;   // dataflow triangular sweeps (single-GPU plans)
+    DeviceBuffer<double> flow_part_;               // one 144-vector per off-diagonal tile
+    DeviceBuffer<int> flow_flags_;                 // cnt[nt] | done[nt] | error word
+    PinnedBuffer<double> pcg_host_;                // two slots of PCG scalars (pcg(): read one iteration behind)
+    PinnedBuffer<int> flow_err_host_;              // [0] the error word behind the last solve(), [1..2] debug_occupy_cus
+    DeviceBuffer<FactorUnit> flow_units_;          // dataflow factorisation of the top groups: [phase 0 units | phase 1 units]
+    DeviceBuffer<int> flow_ver_;                   // per tile slot: finished strips of in-launch writers
+    DeviceBuffer<unsigned long long> flow_trace_;
+    DeviceBuffer<SymTile> sym_tiles_;
+    DeviceBuffer<int> sym_row_ptr_;
+    DeviceBuffer<SymEntry> sym_entries_;
+    DeviceBuffer<double> sym_part_, row_dot_, blk_part_, scal_;
+    // selected inversion (covariance_blocks): allocated on the first call
+    DeviceBuffer<double> z_, y_;
+    DeviceBuffer<SinvTask> sinv_tasks_;
+    DeviceBuffer<SinvProd> sinv_prods_;
+};
+
+class TilePlan : private TilePlanMemory {
    public:
     TilePlan() = default;
     ~TilePlan();
@@ -259,8 +289,6 @@ class TilePlan {
     std::vector<int> owner_h_;    // per tile column: owning rank, -1 top
     std::vector<std::pair<int64_t, int64_t>> own_range_;  // per rank: slots of the touched tiles of its columns
     std::vector<std::pair<int64_t, int64_t>> own_fill_;   // per rank: slots of the fill tiles of its columns
-    int* cls_ = nullptr;
-    double* exch_ = nullptr;
     Comm comm_;
     int64_t n_t_nt_ = 0, n_f_nt_ = 0;   // slot order: touched non-top | touched top | fill non-top | fill top
     int64_t n_slots_ = 0, n_touched_ = 0;
@@ -289,21 +317,10 @@ class TilePlan {
     int gate_min_ = 256;  // U2 batches of at least this many tasks get the flood gate.  Before U2 was split into U2a / U2b the gate was worth 0.3-0.4 ms on
                           // final-13682 (8.3 -> 7.9, any threshold 2 .. 250); after the split it is neutral there (7.6-7.7 either way), +2-3 % on the
                           // dense fronts of ladybug / venice, -2 % on sphere2500's small batches: kept for the large batches only
-    int* gate_cnt_ = nullptr;   // [levels + 1] potrf workgroups that have started, per level
     int overlap_min_ = 2;   // U2 batches smaller than this stay on the main stream (swept 1..1024: flat up to 64)
     std::vector<std::pair<int64_t, int64_t>> upd_rounds_;
-    double *tiles_ = nullptr, *linv_ = nullptr;
-    int *slot_ = nullptr, *diag_slot_ = nullptr, *flag_ = nullptr;
-    PotrfTask* potrf_tasks_ = nullptr;
-    GemmTask *trsm_tasks_ = nullptr, *upd_tasks_ = nullptr;
-    TriTask *tri_fwd_ = nullptr, *tri_bwd_ = nullptr;
-    FlowTask *flow_fwd_ = nullptr, *flow_bwd_ = nullptr;   // dataflow triangular sweeps (single-GPU plans)
-    double* flow_part_ = nullptr;                          // one 144-vector per off-diagonal tile
-    int* flow_flags_ = nullptr;                            // cnt[nt] | done[nt] | error word
-    double* pcg_host_ = nullptr;                           // pinned: two slots of PCG scalars (pcg(): read one iteration behind)
     hipEvent_t pcg_ev_[2] = {nullptr, nullptr};
     int* flow_err_host_dev_ = nullptr;                     // the device address of flow_err_host_ (mapped pinned memory)
-    int* flow_err_host_ = nullptr;                         // pinned: [0] the error word behind the last solve(), [1..2] debug_occupy_cus
     int n_sweep_timeouts_ = 0;
     int poison_ = 0;
     bool poison_factor_ = false;
@@ -317,9 +334,6 @@ class TilePlan {
     std::vector<PotrfTask> potrf_h_;
     std::vector<GemmTask> trsm_h_, upd_h_;
     std::vector<FactorUnit> flow_units_h_;
-    FactorUnit* flow_units_ = nullptr;   // dataflow factorisation of the top groups: [phase 0 units | phase 1 units]
-    int* flow_ver_ = nullptr;            // per tile slot: finished strips of in-launch writers
-    unsigned long long* flow_trace_ = nullptr;
     int flow_cols_ = -1, flow_rows_ = 24;   // -1: the start of the launch is chosen by a cost model (build())
     int flow_g0_[2] = {0, 0}, flow_g1_[2] = {0, 0};   // per phase (local groups / top groups): the groups inside the launch
     int flow_first_[2] = {0, 0}, flow_n_[2] = {0, 0};
@@ -329,11 +343,7 @@ class TilePlan {
     int n_flow_tasks_ = 0, n_flow_bwd_ = 0, n_flow_parts_ = 0;
     int n_flow_local_ = 0;   // distributed plans: the forward tasks of phase 0 (the rest: the top columns, phase 1)
     bool tri_flow_ = true;
-    SymTile* sym_tiles_ = nullptr;
     int n_sym_tiles_ = 0;
-    int* sym_row_ptr_ = nullptr;
-    SymEntry* sym_entries_ = nullptr;
-    double *sym_part_ = nullptr, *row_dot_ = nullptr, *blk_part_ = nullptr, *scal_ = nullptr;
     enum Graph { kGraphFactor, kGraphSweeps, kGraphFactorTop, kGraphDistSolve0, kGraphDistSolve1, kGraphs };   // (run_graph)
     hipGraphExec_t graph_exec_[kGraphs] = {};
     const double* graph_rhs_[kGraphs] = {};
@@ -353,9 +363,6 @@ class TilePlan {
     void sinv_collect(std::vector<hipEvent_t>& ev, bool ok);
     bool factor_valid_ = false;
     bool z_current_ = false;   // z_ holds the selected inverse of the factor now in the tiles
-    double *z_ = nullptr, *y_ = nullptr;
-    SinvTask* sinv_tasks_ = nullptr;
-    SinvProd* sinv_prods_ = nullptr;
     struct SinvGroup { int task[4]; };   // [task[k], task[k + 1]): the Y, off-diagonal Z, diagonal Z launches of one level group
     std::vector<SinvGroup> sinv_groups_;   // root group first
     int64_t sinv_n_[3] = {0, 0, 0};

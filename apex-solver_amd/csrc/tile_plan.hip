@@ -15,24 +15,6 @@
 namespace apex {
 
 static double* tile_at(double* base, int64_t i) { return base + (size_t)i * kNB * kNB; }   // tile i of an array of tiles
-template <typename T>
-static hipError_t dev_alloc(T** p, size_t n) {
-    return hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T));
-}
-template <typename T>
-static hipError_t upload_vec(T** dptr, const std::vector<T>& hv) {
-    if (*dptr) { (void)hipFree(*dptr); *dptr = nullptr; }
-    hipError_t e = dev_alloc(dptr, hv.size());
-    if (e != hipSuccess || hv.empty()) return e;
-    return hipMemcpy(*dptr, hv.data(), hv.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-template <typename T>
-static hipError_t alloc_zero(T** p, size_t n) {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    hipError_t e = dev_alloc(p, n);
-    if (e != hipSuccess) return e;
-    return hipMemset(*p, 0, std::max<size_t>(n, 1) * sizeof(T));
-}
 
 // Nested-dissection order of the nodes of an undirected graph: recursive bisection by BFS level
 // structures from a pseudo-peripheral node; the middle level is the separator and is ordered after
@@ -101,24 +83,15 @@ std::vector<int> TilePlan::order(int nt, const std::vector<uint8_t>& adjm, bool 
 }
 
 void TilePlan::release() {
-    sinv_release();
-    void* ptrs[] = {tiles_, linv_, slot_, diag_slot_, flag_, potrf_tasks_, trsm_tasks_, upd_tasks_, tri_fwd_, tri_bwd_,
-                    flow_fwd_, flow_bwd_, flow_part_, flow_flags_, flow_units_, flow_ver_, flow_trace_, sym_tiles_, sym_row_ptr_, sym_entries_, sym_part_, row_dot_, blk_part_, scal_, cls_, exch_, gate_cnt_};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    tiles_ = linv_ = sym_part_ = row_dot_ = blk_part_ = scal_ = exch_ = nullptr;
-    slot_ = diag_slot_ = flag_ = sym_row_ptr_ = cls_ = nullptr;
-    potrf_tasks_ = nullptr; trsm_tasks_ = upd_tasks_ = nullptr; tri_fwd_ = tri_bwd_ = nullptr;
-    flow_fwd_ = flow_bwd_ = nullptr; flow_part_ = nullptr; flow_flags_ = nullptr; n_flow_tasks_ = 0;
-    flow_units_ = nullptr; flow_ver_ = nullptr; flow_trace_ = nullptr; flow_n_[0] = flow_n_[1] = 0; flow_on_ = true; flow_gave_up_ = false;
-    sym_tiles_ = nullptr; sym_entries_ = nullptr;
-    gate_cnt_ = nullptr;
-    for (int i = 0; i < kGraphs; ++i) {
+    for (int i = 0; i < kGraphs; ++i) {   // the graph execs first: their nodes point into the buffers freed below
         if (graph_exec_[i]) { (void)hipGraphExecDestroy(graph_exec_[i]); graph_exec_[i] = nullptr; }
         graph_failed_[i] = false;
     }
-    if (flow_err_host_) { (void)hipHostFree(flow_err_host_); flow_err_host_ = nullptr; flow_err_host_dev_ = nullptr; }
-    if (pcg_host_) { (void)hipHostFree(pcg_host_); pcg_host_ = nullptr; for (hipEvent_t& ev : pcg_ev_) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; } }
+    sinv_release();
+    static_cast<TilePlanMemory&>(*this) = TilePlanMemory();   // frees every device and pinned block of the plan
+    n_flow_tasks_ = 0; flow_n_[0] = flow_n_[1] = 0; flow_on_ = true; flow_gave_up_ = false;
+    flow_err_host_dev_ = nullptr;
+    for (hipEvent_t& ev : pcg_ev_) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
     if (occ_stream_) { (void)hipStreamSynchronize(occ_stream_); (void)hipStreamDestroy(occ_stream_); occ_stream_ = nullptr; }
     for (const auto& evs : ev_) for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
     ev_.clear();
@@ -356,8 +329,8 @@ std::string TilePlan::build(int nt, const std::vector<uint8_t>& present, hipStre
     if (e.empty()) e = refuse_by_memory();
     if (!e.empty()) return e;
     ptr_trace.mark("plan: symbolic fill, slots");
-    TP_TRY(alloc_zero(&tiles_, (size_t)n_slots_ * kNB * kNB));
-    TP_TRY(alloc_zero(&linv_, (size_t)nt_ * kNB * kNB));
+    TP_TRY(tiles_.alloc_zero((size_t)n_slots_ * kNB * kNB));
+    TP_TRY(linv_.alloc_zero((size_t)nt_ * kNB * kNB));
     ptr_trace.mark("plan: tiles allocated, cleared");
     Lists lists;
     e = host_lists(present, col_rows, g, tiles_, linv_, &lists);
@@ -879,37 +852,37 @@ void TilePlan::flag_first_writers(const double* tiles) {
 
 // The device step of build(): the lists and maps to the device, the work arrays, the streams and events.
 std::string TilePlan::upload(const Lists& lists) {
-    TP_TRY(upload_vec(&slot_, slot_h_));
-    TP_TRY(upload_vec(&diag_slot_, diag_slot_h_));
-    TP_TRY(alloc_zero(&flag_, 4));
-    TP_TRY(upload_vec(&flow_units_, flow_units_h_));
-    TP_TRY(alloc_zero(&flow_ver_, (size_t)n_slots_));
+    TP_TRY(slot_.upload(slot_h_));
+    TP_TRY(diag_slot_.upload(diag_slot_h_));
+    TP_TRY(flag_.alloc_zero(4));
+    TP_TRY(flow_units_.upload(flow_units_h_));
+    TP_TRY(flow_ver_.alloc_zero((size_t)n_slots_));
     n_sym_tiles_ = (int)lists.sym_tiles.size();
-    TP_TRY(upload_vec(&sym_tiles_, lists.sym_tiles));
-    TP_TRY(alloc_zero(&sym_part_, (size_t)n_slots_ * 2 * kNB));
-    TP_TRY(alloc_zero(&row_dot_, (size_t)nt_));
-    TP_TRY(alloc_zero(&blk_part_, 2 * (size_t)((n_pad() + 255) / 256)));
-    TP_TRY(alloc_zero(&scal_, 8));
-    TP_TRY(upload_vec(&tri_fwd_, lists.fwd));
-    TP_TRY(upload_vec(&tri_bwd_, lists.bwd));
-    TP_TRY(upload_vec(&flow_fwd_, lists.flow_fwd));
-    TP_TRY(upload_vec(&flow_bwd_, lists.flow_bwd));
-    TP_TRY(alloc_zero(&flow_part_, (size_t)std::max(n_flow_parts_, 1) * kNB));
-    TP_TRY(alloc_zero(&flow_flags_, (size_t)2 * nt_ + 1));   // cnt[nt] | done[nt] | error word of the dataflow sweeps
+    TP_TRY(sym_tiles_.upload(lists.sym_tiles));
+    TP_TRY(sym_part_.alloc_zero((size_t)n_slots_ * 2 * kNB));
+    TP_TRY(row_dot_.alloc_zero((size_t)nt_));
+    TP_TRY(blk_part_.alloc_zero(2 * (size_t)((n_pad() + 255) / 256)));
+    TP_TRY(scal_.alloc_zero(8));
+    TP_TRY(tri_fwd_.upload(lists.fwd));
+    TP_TRY(tri_bwd_.upload(lists.bwd));
+    TP_TRY(flow_fwd_.upload(lists.flow_fwd));
+    TP_TRY(flow_bwd_.upload(lists.flow_bwd));
+    TP_TRY(flow_part_.alloc_zero((size_t)std::max(n_flow_parts_, 1) * kNB));
+    TP_TRY(flow_flags_.alloc_zero((size_t)2 * nt_ + 1));   // cnt[nt] | done[nt] | error word of the dataflow sweeps
     if (!flow_err_host_) {
-        TP_TRY(hipHostMalloc(reinterpret_cast<void**>(&flow_err_host_), 4 * sizeof(int), hipHostMallocDefault));
+        TP_TRY(flow_err_host_.alloc(4));
         flow_err_host_[0] = flow_err_host_[1] = flow_err_host_[2] = flow_err_host_[3] = 0;
         void* dp = nullptr;   // (pinned host memory is mapped: the kernels that post a word write it through this address)
         flow_err_host_dev_ = hipHostGetDevicePointer(&dp, flow_err_host_, 0) == hipSuccess ? static_cast<int*>(dp) : nullptr;
         (void)hipGetLastError();
     }
-    TP_TRY(upload_vec(&potrf_tasks_, potrf_h_));
-    TP_TRY(upload_vec(&trsm_tasks_, trsm_h_));
-    TP_TRY(upload_vec(&upd_tasks_, upd_h_));
-    TP_TRY(upload_vec(&sym_row_ptr_, lists.sym_row_ptr));
-    TP_TRY(upload_vec(&cls_, cls_h_));
-    TP_TRY(alloc_zero(&exch_, (size_t)n_pad()));
-    TP_TRY(upload_vec(&sym_entries_, lists.sym_entries));
+    TP_TRY(potrf_tasks_.upload(potrf_h_));
+    TP_TRY(trsm_tasks_.upload(trsm_h_));
+    TP_TRY(upd_tasks_.upload(upd_h_));
+    TP_TRY(sym_row_ptr_.upload(lists.sym_row_ptr));
+    TP_TRY(cls_.upload(cls_h_));
+    TP_TRY(exch_.alloc_zero((size_t)n_pad()));
+    TP_TRY(sym_entries_.upload(lists.sym_entries));
     // (a lowest-priority side stream was tried: no gain without graphs, +2.7 ms with them)
     // (and so was a CU-masked one that leaves 1 CU in 8 / 4 / 2 to the critical path: the same, either way)
     for (hipStream_t* s : {&side_, &so_, &side2_})
@@ -917,7 +890,7 @@ std::string TilePlan::upload(const Lists& lists) {
     ev_.assign(n_levels_, {});
     for (auto& evs : ev_)
         for (hipEvent_t& ev : evs) TP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    TP_TRY(hipMalloc(&gate_cnt_, (size_t)(n_levels_ + 1) * sizeof(int)));
+    TP_TRY(gate_cnt_.alloc((size_t)(n_levels_ + 1)));
     TP_TRY(hipDeviceSynchronize());  // the null-stream memsets above precede any work on the stream
     return "";
 }
@@ -1199,7 +1172,7 @@ void TilePlan::enable_tri_flow(bool on) {
 hipError_t TilePlan::enable_flow_trace() {
     if (flow_trace_) return hipSuccess;
     const size_t n = 3 * (size_t)std::max(flow_n_[0] + flow_n_[1], 1);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&flow_trace_), n * sizeof(unsigned long long));
+    hipError_t e = flow_trace_.alloc(n);
     if (e != hipSuccess) return e;
     for (int which : {kGraphFactor, kGraphFactorTop})   // the captured launches hold the old (null) pointer
         if (graph_exec_[which]) { (void)hipGraphExecDestroy(graph_exec_[which]); graph_exec_[which] = nullptr; }
@@ -1431,7 +1404,7 @@ hipError_t TilePlan::pcg(const double* rhs, double* x, double* work, int max_ite
     double* sc = scal_;  // [0] rz_old  [1] p.Ap  [2] r.r  [3] r.z  [4] frozen
     hipError_t e;
     if (!pcg_host_) {
-        if ((e = hipHostMalloc(reinterpret_cast<void**>(&pcg_host_), 16 * sizeof(double), hipHostMallocDefault)) != hipSuccess) return e;
+        if ((e = pcg_host_.alloc(16)) != hipSuccess) return e;
         for (hipEvent_t& ev : pcg_ev_) if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
     }
     launch_tile_diag(tiles_, diag_slot_, nt_, dg, stream_);
@@ -1467,10 +1440,7 @@ hipError_t TilePlan::pcg(const double* rhs, double* x, double* work, int max_ite
 
 // ---- selected inversion (tile_plan.h, covariance_blocks) ----------------------------------------------------------------
 void TilePlan::sinv_release() {
-    void* ptrs[] = {z_, y_, sinv_tasks_, sinv_prods_};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    z_ = y_ = nullptr; sinv_tasks_ = nullptr; sinv_prods_ = nullptr;
+    z_.reset(); y_.reset(); sinv_tasks_.reset(); sinv_prods_.reset();   // (null z_: sinv_enqueue sets up again)
     sinv_groups_.clear(); sinv_group_ms_.clear();
     sinv_n_[0] = sinv_n_[1] = sinv_n_[2] = 0;
     sinv_bytes_ = 0;
@@ -1512,8 +1482,8 @@ std::string TilePlan::sinv_setup() {
     std::vector<SinvTask> tasks;
     std::vector<SinvProd> prods;
     // (the lists point at the final addresses of Z and Y: allocate first)
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&z_), (size_t)n_slots_ * te * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&y_), (size_t)std::max<int64_t>(y_max, 1) * te * sizeof(double));
+    hipError_t e = z_.alloc((size_t)n_slots_ * te);
+    if (e == hipSuccess) e = y_.alloc((size_t)std::max<int64_t>(y_max, 1) * te);
     if (e != hipSuccess) { sinv_release(); return std::string("HIP error allocating the covariance tiles: ") + hipGetErrorString(e); }
     auto Lt = [&](int I, int J) { return tile_at(tiles_, slot(I, J)); };
     auto Zt = [&](int I, int J) { return tile_at(z_, slot(I, J)); };
@@ -1564,8 +1534,8 @@ std::string TilePlan::sinv_setup() {
         for (int t = sg.task[1]; t < sg.task[2]; ++t) sinv_n_[1] += tasks[t].count;
         for (int t = sg.task[2]; t < sg.task[3]; ++t) sinv_n_[2] += tasks[t].count;
     }
-    e = upload_vec(&sinv_tasks_, tasks);
-    if (e == hipSuccess) e = upload_vec(&sinv_prods_, prods);
+    e = sinv_tasks_.upload(tasks);
+    if (e == hipSuccess) e = sinv_prods_.upload(prods);
     if (e != hipSuccess) { sinv_release(); return std::string("HIP error uploading the covariance lists: ") + hipGetErrorString(e); }
     sinv_bytes_ = ((size_t)n_slots_ + (size_t)std::max<int64_t>(y_max, 1)) * te * sizeof(double) + tasks.size() * sizeof(SinvTask) +
                   prods.size() * sizeof(SinvProd);
@@ -1619,11 +1589,11 @@ int TilePlan::covariance_blocks(const int64_t* pos, int64_t n_var, int d, double
         if (pos[v] < 0 || pos[v] + d > n_pad() || pos[v] / kNB != (pos[v] + d - 1) / kNB) { *err = "variable block outside one diagonal tile"; return 1; }
     std::vector<hipEvent_t> ev;
     if (const int rc = sinv_enqueue(&ev, err)) return rc;
-    int64_t* dpos = nullptr;
-    double* dout = nullptr;
+    DeviceBuffer<int64_t> dpos;
+    DeviceBuffer<double> dout;
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dpos), (size_t)std::max<int64_t>(n_var, 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), (size_t)std::max<int64_t>(n_var * d * d, 1) * sizeof(double));
+    if (e == hipSuccess) e = dpos.alloc((size_t)std::max<int64_t>(n_var, 0));
+    if (e == hipSuccess) e = dout.alloc((size_t)std::max<int64_t>(n_var * d * d, 0));
     if (e == hipSuccess && n_var > 0) e = hipMemcpyAsync(dpos, pos, (size_t)n_var * sizeof(int64_t), hipMemcpyHostToDevice, stream_);
     if (e == hipSuccess) {
         launch_sinv_diag_blocks(z_, diag_slot_, dpos, n_var, d, dout, stream_);
@@ -1632,8 +1602,6 @@ int TilePlan::covariance_blocks(const int64_t* pos, int64_t n_var, int d, double
     if (e == hipSuccess && n_var > 0) e = hipMemcpyAsync(out, dout, (size_t)n_var * d * d * sizeof(double), hipMemcpyDeviceToHost, stream_);
     const hipError_t se = hipStreamSynchronize(stream_);
     if (e == hipSuccess) e = se;
-    if (dpos) (void)hipFree(dpos);
-    if (dout) (void)hipFree(dout);
     sinv_collect(ev, e == hipSuccess);
     if (e != hipSuccess) { *err = std::string("HIP error in covariance_blocks: ") + hipGetErrorString(e); return 2; }
     z_current_ = true;
