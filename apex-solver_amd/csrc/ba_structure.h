@@ -71,6 +71,15 @@ struct BaHostStructure {
     // dev_tables != NULL (queued layout only): the pair RECORDS are left to the device (PairDeviceTables, schur_pairs.h)
     void build_schur_lists(const BaStructOptions& o, const int* slot_host, PairDeviceTables* dev_tables = nullptr);
     void release_scratch();   // the full-problem lists step 2 needed
+    // Camera staging lists of the landmark-major kernels (ba_kernels.h, BAView::o_slot), from o_cam and pt_ptr: per workgroup of
+    // kLmWg landmarks the first kCamStageCap distinct cameras (wg_list, wg_n of them), per observation its camera's place in
+    // that list (slot; 255: not staged)
+    struct CamStaging {
+        raw_vector<uint8_t> slot;
+        std::vector<uint8_t> wg_n;
+        raw_vector<uint32_t> wg_list;
+    };
+    CamStaging build_cam_staging() const;
 
    private:
     std::vector<int64_t> lp_;                    // landmark buckets of the caller's list (build_order -> build_obs_lists)

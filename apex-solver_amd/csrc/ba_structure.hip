@@ -389,6 +389,31 @@ std::string BaHostStructure::build_obs_lists(const uint32_t* cam_idx, const uint
     return "";
 }
 
+BaHostStructure::CamStaging BaHostStructure::build_cam_staging() const {
+    static_assert(kCamStageCap <= 254, "slot 255 means not staged");
+    const int64_t n_wg = (n_pt + kLmWg - 1) / kLmWg;
+    CamStaging st;
+    st.slot.resize(o_cam.size());
+    st.wg_n.assign((size_t)std::max<int64_t>(n_wg, 1), 0);
+    st.wg_list.resize((size_t)std::max<int64_t>(n_wg, 1) * kCamStageCap);
+    parallel_ranges(n_wg, 64, [&](int64_t wb, int64_t we) {
+        std::vector<int> where(n_cam, -1), stamp(n_cam, -1);
+        for (int64_t w = wb; w < we; ++w) {
+            const int64_t l0 = w * kLmWg, l1 = std::min<int64_t>(n_pt, l0 + kLmWg);
+            int n = 0;
+            uint32_t* list = st.wg_list.data() + (size_t)w * kCamStageCap;
+            for (int64_t i = pt_ptr[l0]; i < pt_ptr[l1]; ++i) {
+                const uint32_t c = o_cam[i];
+                if (stamp[c] != (int)w) { stamp[c] = (int)w; where[c] = n < kCamStageCap ? n : 255; if (n < kCamStageCap) list[n++] = c; }
+                st.slot[i] = (uint8_t)where[c];
+            }
+            for (int k = n; k < kCamStageCap; ++k) list[k] = 0;
+            st.wg_n[w] = (uint8_t)n;
+        }
+    });
+    return st;
+}
+
 void BaHostStructure::release_scratch() {
     raw_vector<uint32_t>().swap(cam_i_); raw_vector<uint32_t>().swap(pt_i_);
     std::vector<int64_t>().swap(full_ptr_); raw_vector<int>().swap(full_obs_);

@@ -130,7 +130,7 @@ class Solver : public LmBackend {
     void set_device_pair_recs(bool on) { device_pair_recs_ = on; }   // before set_structure ("device_pair_list")
     int get_pair_records(uint32_t* recs4_out, int64_t cap_slots);     // tests: the pair records as they sit on the device
     void set_auto_variant(bool on) { auto_variant_ = on; }
-    void set_variant_cost_permille(int permille) { variant_cost_permille_ = permille < 0 ? 0 : permille; }   // before set_structure (see build_plan)
+    void set_variant_cost_permille(int permille) { variant_cost_permille_ = permille < 0 ? 0 : permille; }   // before set_structure (see choose_and_build_plan)
     // [0] predicted ms per solve of the direct path (tile Cholesky + sweeps; 0: never evaluated -- "matrix_free_only"), [1] of the
     // matrix-free PCG at IterativeSchurSolver's cap, [2] what set_structure chose: 0 direct, 1 matrix-free by predicted cost,
     // 2 matrix-free because the plan was refused (size / memory), 3 matrix-free by the caller's option, [3] the cap behind [1]
@@ -175,7 +175,7 @@ class Solver : public LmBackend {
 
    private:
     int fail(int code, const std::string& msg);
-    int check_hip(hipError_t e, const char* what);
+    int check_hip(hipError_t e, const char* what, std::string* err = nullptr);   // err: where the text goes instead of err_
     BAView view(int which) const;
     TileMap tilemap() const;
     // for_factor: the result feeds tp_.factor() (a distributed plan then leaves the top tiles to the factorisation's
@@ -197,6 +197,21 @@ class Solver : public LmBackend {
     int cost_of(int which, double* out);
     void stage_begin(int st);
     void stage_end(int st);
+    // The steps of set_structure in the order it runs them (solver.hip).  Setup is the state of one call, its comments say
+    // which thread owns what; a step that runs on the uploader thread writes its error text to `err`, never to err_.
+    struct Setup;
+    void device_thread_body(Setup& su);
+    hipError_t device_ready(const Setup& su);
+    int validate_indices(Setup& su);
+    void choose_and_build_plan(Setup& su);
+    void planner_body(Setup& su);
+    int adopt_host_structure(Setup& su);
+    void uploader_body(Setup& su);
+    int upload_observation_lists(Setup& su, std::string* err);
+    int upload_fixed_masks(const Setup& su, std::string* err);
+    int alloc_work_arrays(std::string* err);
+    int upload_pair_lists(Setup& su, const PairDeviceTables& dtab, bool recs_on_device);
+    void hand_lists_to_free_thread(Setup& su);
 
     // sizes
     int64_t n_cam_, n_pt_, n_obs_;
@@ -250,7 +265,6 @@ class Solver : public LmBackend {
     // trial point with its cost (apexgpu_eval_step) -- is enqueued behind the back-substitution and read at the solve's own wait:
     // the two calls then answer from the host, without a launch or a wait of their own (three device round trips per LM
     // iteration become one).  The answers are those of this very solve (step_serial_); single rank.
-    bool device_gathers_ = true;   // "device_gathers": set-up, single rank: o_uv / co_uv / co_pt are permuted on the device (ba_structure.h)
     bool eager_eval_ = true;
     bool trial_pts_written_ = false;   // the back-substitution of this solve has written the trial points (enqueue_trial_point skips them)
     int64_t step_serial_ = 0, eager_serial_ = -1;

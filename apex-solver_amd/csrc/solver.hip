@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <functional>
 #include <future>
 #include <numeric>
 
@@ -17,9 +18,10 @@ void warm_ba_kernels(hipStream_t s);
 void warm_schur_pairs(hipStream_t s);
 void warm_chol_kernels(hipStream_t s);
 
-#define HIP_TRY(expr)                                         \
+// HIP_TRY(expr): the text of a failure goes to err_; HIP_TRY(expr, err): to *err (a step on a thread that does not own err_)
+#define HIP_TRY(expr, ...)                                    \
     do {                                                      \
-        int _rc = check_hip((expr), #expr);                   \
+        int _rc = check_hip((expr), #expr, ##__VA_ARGS__);    \
         if (_rc != kOk) return _rc;                           \
     } while (0)
 
@@ -82,9 +84,10 @@ int Solver::fail(int code, const std::string& msg) {
     return code;
 }
 
-int Solver::check_hip(hipError_t e, const char* what) {
+int Solver::check_hip(hipError_t e, const char* what, std::string* err) {
     if (e == hipSuccess) return kOk;
-    return fail(kDeviceError, std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
+    *(err ? err : &err_) = std::string("HIP error in ") + what + ": " + hipGetErrorString(e);
+    return kDeviceError;
 }
 
 BAView Solver::view(int which) const {
@@ -166,153 +169,165 @@ void shard_range(int64_t n_pt, const int64_t* ptr, int rank, int world, int64_t*
 // ---------------------------------------------------------------------------------------------
 // structure
 // ---------------------------------------------------------------------------------------------
-int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const double* obs_uv,
-                          const int64_t* intr_col, const int64_t* pose_col, const int64_t* pt_col,
-                          const uint8_t* fix_pose, const uint8_t* fix_intr, const uint8_t* fix_pt,
-                          double huber_delta) {
-    if (n_cam_ <= 0 || n_pt_ <= 0) return fail(kInvalidInput, n_cam_ <= 0 ? "No camera variables found" : "No landmark variables found");
-    if (n_obs_ < 0 || n_obs_ > 2000000000LL) return fail(kInvalidInput, "observation count out of range");
-    lc_release();   // (the landmark covariance lists belong to the old structure)
-    // The first stream this process creates costs 0.1-0.16 s (the runtime brings up its hardware queues; measured with
-    // APEX_SETUP_TRACE in bench.py, torch's context already there), the code objects of the three kernel files a few ms more:
-    // both on a thread, beside the argument checks and the camera order (host only), joined in front of the first device call
-    // below (device_ready) -- round 5.
-    DeviceBuffer<double> raw_uv;   // (device thread -> uploader thread, which joins the former through device_ready)
-    const bool raw_uv_wanted = device_gathers_ && world_ == 1 && !(comm_ && world_ > 1);
-    std::promise<hipError_t> init_p;
-    std::shared_future<hipError_t> init_f = init_p.get_future().share();
-    std::promise<bool> validated_p;   // (the 0.5 GB copy of the measurements does not start for a call that is about to be refused)
-    std::shared_future<bool> validated_f = validated_p.get_future().share();
-    std::thread warmer([this, &init_p, &raw_uv, raw_uv_wanted, obs_uv, validated_f] {
-        SetupTrace wt;
-        hipError_t e = hipSetDevice(device_);
-        if (e == hipSuccess && !stream_) e = hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking);
-        init_p.set_value(e);
-        wt.mark("device thread: device, stream");
-        if (e != hipSuccess) return;
-        if (raw_uv_wanted && validated_f.get()) {   // the caller's measurements as they are, beside the host's list building -- once the lists are valid
-            if (raw_uv.alloc(std::max<size_t>(2 * (size_t)n_obs_, 2)) != hipSuccess ||
-                hipMemcpy(raw_uv, obs_uv, 2 * (size_t)n_obs_ * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-                raw_uv.reset();
-                (void)hipGetLastError();
-            }
-            wt.mark("device thread: measurements up");
-        }
-        hipStream_t ws = nullptr;
-        if (hipStreamCreateWithFlags(&ws, hipStreamNonBlocking) != hipSuccess) return;
-        warm_ba_kernels(ws); warm_schur_pairs(ws); warm_chol_kernels(ws);
-        (void)hipStreamSynchronize(ws);
-        (void)hipStreamDestroy(ws);
-        wt.mark("device thread: code objects");
-    });
-    auto device_ready = [this, init_f]() -> hipError_t {   // (any thread: the calling thread's device is set as well)
-        const hipError_t e = init_f.get();
-        return e != hipSuccess ? e : hipSetDevice(device_);
-    };
-    struct WJoiner { std::thread& t; ~WJoiner() { if (t.joinable()) t.join(); } } wjoiner{warmer};
-    // (declared behind the joiner: destroyed before it, so an early return releases the device thread before it is joined)
-    struct Unblock { std::promise<bool>& p; bool done = false; void set(bool v) { if (!done) { done = true; p.set_value(v); } } ~Unblock() { set(false); } } validated{validated_p};
-    SetupTrace tr;
-    {
-        std::atomic<int64_t> bad(n_obs_);   // first observation that references a missing variable
-        parallel_ranges(n_obs_, 1 << 18, [&](int64_t b, int64_t e) {
-            for (int64_t i = b; i < e; ++i)
-                if (cam_idx[i] >= (uint64_t)n_cam_ || pt_idx[i] >= (uint64_t)n_pt_) {
-                    int64_t cur = bad.load();
-                    while (i < cur && !bad.compare_exchange_weak(cur, i)) {}
-                    return;
-                }
-        });
-        if (bad.load() < n_obs_) return fail(kInvalidInput, "observation " + std::to_string(bad.load()) + " references a missing variable");
-    }
-    validated.set(true);
-    huber_delta_ = huber_delta;
-    intr_col_.assign(intr_col, intr_col + n_cam_);
-    pose_col_.assign(pose_col, pose_col + n_cam_);
-    pt_col_.assign(pt_col, pt_col + n_pt_);
-    // (the caller's factor list is NOT kept: get_hessian_csc, the one reader, rebuilds it from the device's observation
-    // lists on demand -- 0.1 s of set-up on final-13682 for an export the LM loop never calls)
-    tr.mark("validate the index lists");
+static double seconds_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
 
-    // ---- everything derived from the observation list on the host (ba_structure.h): internal camera order (hub
-    // cameras last, nested dissection of the tile graph), tile structure, landmark sharding, observation lists ------
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
-    HostBlockCache::get().begin_setup();
-    matrix_free_only_ = matrix_free_only_opt_;   // (an automatic selection of an earlier set_structure on this handle does not stick)
-    auto_fallback_ = false; fallback_reason_.clear();
+// The state of ONE set_structure call, shared by the calling thread and its three helpers: the device thread (device,
+// stream, the caller's measurements, code objects), the planner (tile plan, variant selection) and the uploader (everything
+// that does not depend on the plan).  Every field names the one thread that writes it and the point after which the
+// others may read it.
+struct Solver::Setup {
+    // the caller's arguments: set before any thread starts, read-only afterwards
+    const uint32_t *cam_idx = nullptr, *pt_idx = nullptr;
+    const double* obs_uv = nullptr;
+    const uint8_t *fix_pose = nullptr, *fix_intr = nullptr, *fix_pt = nullptr;
+    bool raw_uv_wanted = false;   // single rank: the device thread copies the measurements as they are
+    // calling thread, before the planner and the uploader start; schur_form alone is rewritten later (after the planner is
+    // joined), and neither helper reads that field
     BaStructOptions so;
-    so.dc = dc_; so.use_nd = use_nd_; so.nd_leaf = nd_leaf_; so.hubs_last = hubs_last_;
-    so.rank = rank_; so.world = world_; so.dist_factor = dist_factor_; so.tree_sharding = tree_sharding_;
-    so.dist_selftest = dist_selftest_; so.schur_form = rows_form_;
-    so.device_gathers = device_gathers_ && world_ == 1;
-    std::unique_ptr<BaHostStructure> hs_owner(new BaHostStructure);
-    BaHostStructure& hs = *hs_owner;
-    // Camera order and tile structure first; then the tile plan (symbolic fill, task lists, 1.4 GB of device allocations: 0.06-
-    // 0.1 s, mostly serial) is built on a thread of its own BESIDE the observation lists (0.1 s), which do not need it (round 5).
-    // A distributed plan with tree sharding previews the partition inside the list phase on the same TilePlan: no overlap then.
-    hs.build_order(n_cam_, n_pt_, n_obs_, cam_idx, pt_idx, so, tp_);
-    nt_ = hs.nt;
-    std::vector<uint8_t> present_plan = hs.present;   // (the plan's own copy: a matrix-free handle keeps the diagonal only)
+    // calling thread.  The planner reads nothing of it (present_plan is its copy); the uploader reads the lists
+    // build_obs_lists left, complete before it starts, while the calling thread adds the Schur lists (hs->pl)
+    std::unique_ptr<BaHostStructure> hs{new BaHostStructure};
+    // planner (or the calling thread where the plan is built in line): read after planner.join()
+    std::vector<uint8_t> present_plan;   // the plan's own copy of hs->present: a matrix-free handle keeps the diagonal only
     std::string plan_err;
     double plan_seconds = 0.0;
-    auto build_plan = [&]() {
-        const auto t_plan = std::chrono::steady_clock::now();
-        (void)hipSetDevice(device_);
-        if (matrix_free_only_) {   // S is never formed: keep the diagonal tiles (Schur-Jacobi blocks are read from them), nothing else
-            std::fill(present_plan.begin(), present_plan.end(), (uint8_t)0);
-            for (int I = 0; I < nt_; ++I) present_plan[(size_t)I * nt_ + I] = 1;
-        }
-        tp_.enable_graphs(use_graphs_);
-        auto_fallback_ = false; fallback_reason_.clear();
-        // Variant selection by predicted cost (round 6; the reference's dispatch never fails on the fill of S and a drop-in backend
-        // should not spend 10 s where it owns a 0.5 s way to the same step: levenberg_marquardt.rs:1039-1082).  The matrix-free
-        // PCG costs at most its cap times one S p -- two passes over the observations, 160 bytes each at the 4.5 TB/s the two
-        // kernels sustain (1.01 ms on final-13682, 0.45 ms on synthetic-10k: DESIGN section 5) -- whatever the structure; the tile
-        // plan refuses to be built when its own prediction (TilePlan::predict_solve_ms) is above that.  Both numbers are host
-        // arithmetic on the replicated structure: every rank decides alike.  "variant_cost_permille" scales the matrix-free side
-        // (tests move the crossover onto small problems; 0: the rule is off).
-        pred_mf_ms_ = 500.0 * (160.0 * (double)n_obs_ / 4.5e12 * 1e3 + 0.02) * (double)variant_cost_permille_ / 1000.0;
-        pred_direct_ms_ = 0.0; variant_choice_ = matrix_free_only_ ? 3 : 0;
-        tp_.set_cost_limit_ms((auto_variant_ && !matrix_free_only_ && variant_cost_permille_ > 0) ? pred_mf_ms_ : 0.0);
-        std::string e = tp_.build(nt_, present_plan, stream_);
-        if (!matrix_free_only_) pred_direct_ms_ = tp_.predicted_ms();
-        // A structure whose direct factorisation is out of reach (a photo collection: S dense at tile granularity) is not an
-        // error of the caller's: the reference's LM never fails on the fill of S.  The handle becomes matrix-free only by itself
-        // and answers every variant with the matrix-free PCG (set_auto_variant).  The update-list rule is pure host arithmetic
-        // on the replicated structure (every rank decides alike); the memory rule depends on the device and is single-rank only.
-        const bool refused_size = tp_.refused_too_large(), refused_mem = tp_.refused_no_memory() && world_ == 1, refused_cost = tp_.refused_by_cost();
-        if (!e.empty() && auto_variant_ && !matrix_free_only_ && (refused_size || refused_mem || refused_cost)) {
-            auto_fallback_ = true; matrix_free_only_ = true;
-            variant_choice_ = refused_cost ? 1 : 2;
-            fallback_reason_ = (refused_cost ? "matrix-free PCG (IterativeSchurSolver semantics) selected by predicted cost (" : "the direct factorisation of S was refused (") + e +
-                               (refused_cost ? ")" : "): matrix-free PCG (IterativeSchurSolver semantics) selected");
-            tp_.set_cost_limit_ms(0.0);
-            std::fill(present_plan.begin(), present_plan.end(), (uint8_t)0);
-            for (int I = 0; I < nt_; ++I) present_plan[(size_t)I * nt_ + I] = 1;
-            e = tp_.build(nt_, present_plan, stream_);
-        }
-        plan_err = e;
-        plan_seconds = since(t_plan);
-    };
-    tr.mark("camera order, tile structure");
-    std::thread planner;
-    struct PJoiner { std::thread& t; ~PJoiner() { if (t.joinable()) t.join(); } } pjoiner{planner};
-    const bool plan_beside_lists = !BaHostStructure::needs_owner_preview(so);
-    if (plan_beside_lists)
-        planner = std::thread([&] {
-            try {
-                if (device_ready() != hipSuccess) { plan_err = "the device could not be initialised"; return; }
-                build_plan();
-            } catch (const std::exception& ex) { plan_err = std::string("tile plan: ") + ex.what(); }
-        });
-    {
-        const std::string e = hs.build_obs_lists(cam_idx, pt_idx, obs_uv, so, tp_);
-        if (!e.empty()) return fail(kInvalidInput, e);
+    // uploader, which keeps its own error text (err_ belongs to the calling thread): read after uploader.join().  The
+    // calling thread then adds the pair lists' copy time to up_seconds
+    std::string up_err;
+    int up_rc = kOk;
+    double up_seconds = 0.0;
+    // device thread; the uploader takes it over (and frees it) after joining the device thread
+    DeviceBuffer<double> raw_uv;
+    // set by the device thread once the device and stream_ are there: device_ready() waits for it on any thread
+    std::promise<hipError_t> init_p;
+    std::shared_future<hipError_t> init_f = init_p.get_future().share();
+    // set by the calling thread (release_device_thread): the 0.5 GB copy of the measurements does not start for a call
+    // that is about to be refused.  The device thread waits for it
+    std::promise<bool> validated_p;
+    std::shared_future<bool> validated_f = validated_p.get_future().share();
+    bool validated_set = false;   // calling thread
+    SetupTrace tr;                // calling thread
+    std::chrono::steady_clock::time_point t_begin;   // calling thread
+    // started and joined by the calling thread; the device thread alone is joined by the uploader where it takes raw_uv over
+    std::thread device_thread, planner, uploader;
+
+    void release_device_thread(bool valid) {
+        if (!validated_set) { validated_set = true; validated_p.set_value(valid); }
     }
-    tr.mark("observation lists");
-    HIP_TRY(device_ready());
-    tr.mark("waited for the device thread");
+    // Every way out of set_structure, early returns and exceptions included: the device thread is released before anything
+    // is joined (it may still wait for the verdict on the index lists); the uploader is joined first because it may itself
+    // be joining the device thread; the planner waits for nothing but the device thread's first step.
+    ~Setup() {
+        release_device_thread(false);
+        if (uploader.joinable()) uploader.join();
+        if (planner.joinable()) planner.join();
+        if (device_thread.joinable()) device_thread.join();
+    }
+};
+
+// The first stream this process creates costs 0.1-0.16 s (the runtime brings up its hardware queues; measured with
+// APEX_SETUP_TRACE in bench.py, torch's context already there), the code objects of the three kernel files a few ms more:
+// both on a thread, beside the argument checks and the camera order (host only), joined in front of the first device call
+// (device_ready) -- round 5.
+void Solver::device_thread_body(Setup& su) {
+    SetupTrace wt;
+    hipError_t e = hipSetDevice(device_);
+    if (e == hipSuccess && !stream_) e = hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking);
+    su.init_p.set_value(e);
+    wt.mark("device thread: device, stream");
+    if (e != hipSuccess) return;
+    if (su.raw_uv_wanted && su.validated_f.get()) {   // the caller's measurements as they are, beside the host's list building -- once the lists are valid
+        if (su.raw_uv.alloc(std::max<size_t>(2 * (size_t)n_obs_, 2)) != hipSuccess ||
+            hipMemcpy(su.raw_uv, su.obs_uv, 2 * (size_t)n_obs_ * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+            su.raw_uv.reset();
+            (void)hipGetLastError();
+        }
+        wt.mark("device thread: measurements up");
+    }
+    hipStream_t ws = nullptr;
+    if (hipStreamCreateWithFlags(&ws, hipStreamNonBlocking) != hipSuccess) return;
+    warm_ba_kernels(ws); warm_schur_pairs(ws); warm_chol_kernels(ws);
+    (void)hipStreamSynchronize(ws);
+    (void)hipStreamDestroy(ws);
+    wt.mark("device thread: code objects");
+}
+
+hipError_t Solver::device_ready(const Setup& su) {   // (any thread: the calling thread's device is set as well)
+    const hipError_t e = su.init_f.get();
+    return e != hipSuccess ? e : hipSetDevice(device_);
+}
+
+int Solver::validate_indices(Setup& su) {
+    std::atomic<int64_t> bad(n_obs_);   // first observation that references a missing variable
+    const uint32_t *cam_idx = su.cam_idx, *pt_idx = su.pt_idx;
+    const uint64_t n_cam = (uint64_t)n_cam_, n_pt = (uint64_t)n_pt_;
+    parallel_ranges(n_obs_, 1 << 18, [&bad, cam_idx, pt_idx, n_cam, n_pt](int64_t b, int64_t e) {
+        for (int64_t i = b; i < e; ++i)
+            if (cam_idx[i] >= n_cam || pt_idx[i] >= n_pt) {
+                int64_t cur = bad.load();
+                while (i < cur && !bad.compare_exchange_weak(cur, i)) {}
+                return;
+            }
+    });
+    if (bad.load() < n_obs_) return fail(kInvalidInput, "observation " + std::to_string(bad.load()) + " references a missing variable");
+    return kOk;
+}
+
+// The tile plan and with it the variant this structure runs: the decision is made afresh for every structure (an automatic
+// selection of an earlier set_structure on this handle does not stick), on whichever thread builds the plan.
+void Solver::choose_and_build_plan(Setup& su) {
+    const auto t_plan = std::chrono::steady_clock::now();
+    (void)hipSetDevice(device_);
+    matrix_free_only_ = matrix_free_only_opt_;
+    auto_fallback_ = false; fallback_reason_.clear();
+    std::vector<uint8_t>& present_plan = su.present_plan;
+    if (matrix_free_only_) {   // S is never formed: keep the diagonal tiles (Schur-Jacobi blocks are read from them), nothing else
+        std::fill(present_plan.begin(), present_plan.end(), (uint8_t)0);
+        for (int I = 0; I < nt_; ++I) present_plan[(size_t)I * nt_ + I] = 1;
+    }
+    tp_.enable_graphs(use_graphs_);
+    // Variant selection by predicted cost (round 6; the reference's dispatch never fails on the fill of S and a drop-in backend
+    // should not spend 10 s where it owns a 0.5 s way to the same step: levenberg_marquardt.rs:1039-1082).  The matrix-free
+    // PCG costs at most its cap times one S p -- two passes over the observations, 160 bytes each at the 4.5 TB/s the two
+    // kernels sustain (1.01 ms on final-13682, 0.45 ms on synthetic-10k: DESIGN section 5) -- whatever the structure; the tile
+    // plan refuses to be built when its own prediction (TilePlan::predict_solve_ms) is above that.  Both numbers are host
+    // arithmetic on the replicated structure: every rank decides alike.  "variant_cost_permille" scales the matrix-free side
+    // (tests move the crossover onto small problems; 0: the rule is off).
+    pred_mf_ms_ = 500.0 * (160.0 * (double)n_obs_ / 4.5e12 * 1e3 + 0.02) * (double)variant_cost_permille_ / 1000.0;
+    pred_direct_ms_ = 0.0; variant_choice_ = matrix_free_only_ ? 3 : 0;
+    tp_.set_cost_limit_ms((auto_variant_ && !matrix_free_only_ && variant_cost_permille_ > 0) ? pred_mf_ms_ : 0.0);
+    std::string e = tp_.build(nt_, present_plan, stream_);
+    if (!matrix_free_only_) pred_direct_ms_ = tp_.predicted_ms();
+    // A structure whose direct factorisation is out of reach (a photo collection: S dense at tile granularity) is not an
+    // error of the caller's: the reference's LM never fails on the fill of S.  The handle becomes matrix-free only by itself
+    // and answers every variant with the matrix-free PCG (set_auto_variant).  The update-list rule is pure host arithmetic
+    // on the replicated structure (every rank decides alike); the memory rule depends on the device and is single-rank only.
+    const bool refused_size = tp_.refused_too_large(), refused_mem = tp_.refused_no_memory() && world_ == 1, refused_cost = tp_.refused_by_cost();
+    if (!e.empty() && auto_variant_ && !matrix_free_only_ && (refused_size || refused_mem || refused_cost)) {
+        auto_fallback_ = true; matrix_free_only_ = true;
+        variant_choice_ = refused_cost ? 1 : 2;
+        fallback_reason_ = (refused_cost ? "matrix-free PCG (IterativeSchurSolver semantics) selected by predicted cost (" : "the direct factorisation of S was refused (") + e +
+                           (refused_cost ? ")" : "): matrix-free PCG (IterativeSchurSolver semantics) selected");
+        tp_.set_cost_limit_ms(0.0);
+        std::fill(present_plan.begin(), present_plan.end(), (uint8_t)0);
+        for (int I = 0; I < nt_; ++I) present_plan[(size_t)I * nt_ + I] = 1;
+        e = tp_.build(nt_, present_plan, stream_);
+    }
+    su.plan_err = e;
+    su.plan_seconds = seconds_since(t_plan);
+}
+
+void Solver::planner_body(Setup& su) {   // (nothing may escape a thread)
+    try {
+        if (device_ready(su) != hipSuccess) { su.plan_err = "the device could not be initialised"; return; }
+        choose_and_build_plan(su);
+    } catch (const std::exception& ex) { su.plan_err = std::string("tile plan: ") + ex.what(); }
+}
+
+int Solver::adopt_host_structure(Setup& su) {
+    const BaHostStructure& hs = *su.hs;
     n_c_ = hs.n_c; nt_ = hs.nt; n_c_pad_ = hs.n_c_pad;
     cmap_ = hs.cmap; cinv_ = hs.cinv; lmap_ = hs.lmap;
     lm_lo_ = hs.lm_lo; lm_hi_ = hs.lm_hi; tree_shard_ = hs.tree_shard; pad_rank_ = hs.pad_rank;
@@ -321,152 +336,118 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     n_pairs_ = hs.n_pairs; n_present_ = hs.n_present;
     lam_mask_.reset();
     if (tree_shard_) HIP_TRY(lam_mask_.upload(hs.lam_mask));
-    // ---- uploads of everything that does not depend on the tile plan, on a thread of their own: the observation lists
-    // (1.7 GB on final-13682), the camera staging lists, the masks and the work arrays go to the device while this thread
-    // builds the tile plan and the pair list (round 5: 0.09 s of copies under 0.27 s of host work) -------------------------
-    const auto t_up = std::chrono::steady_clock::now();
-    double up_seconds = 0.0;
-    const auto &o_cam = hs.o_cam, &o_pt = hs.o_pt, &co_pt = hs.co_pt;
-    const auto &o_uv = hs.o_uv, &co_uv = hs.co_uv;
-    const auto &pt_ptr = hs.pt_ptr, &cam_ptr = hs.cam_ptr;
-    const auto &cam_obs = hs.cam_obs, &co_rank = hs.co_rank;
-    // (the uploader thread keeps its own error text: err_ belongs to the calling thread)
-    std::string up_err;
-#define UP_TRY(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) { up_err = std::string("HIP error in " #expr ": ") + hipGetErrorString(_e); return (int)kDeviceError; } } while (0)
-    auto upload_lists = [&]() -> int {
-        const auto t0 = std::chrono::steady_clock::now();
-        UP_TRY(hipSetDevice(device_));
-        {   // camera staging lists of the landmark-major kernels (ba_kernels.h, BAView::o_slot)
-            const int64_t n_wg = (n_pt_ + kLmWg - 1) / kLmWg;
-            raw_vector<uint8_t> slot(o_cam.size());
-            std::vector<uint8_t> wn((size_t)std::max<int64_t>(n_wg, 1), 0);
-            raw_vector<uint32_t> wlist((size_t)std::max<int64_t>(n_wg, 1) * kCamStageCap);
-            parallel_ranges(n_wg, 64, [&](int64_t wb, int64_t we) {
-                std::vector<int> where(n_cam_, -1), stamp(n_cam_, -1);
-                for (int64_t w = wb; w < we; ++w) {
-                    const int64_t l0 = w * kLmWg, l1 = std::min<int64_t>(n_pt_, l0 + kLmWg);
-                    int n = 0;
-                    uint32_t* list = wlist.data() + (size_t)w * kCamStageCap;
-                    for (int64_t i = pt_ptr[l0]; i < pt_ptr[l1]; ++i) {
-                        const uint32_t c = o_cam[i];
-                        if (stamp[c] != (int)w) { stamp[c] = (int)w; where[c] = n < kCamStageCap ? n : 255; if (n < kCamStageCap) list[n++] = c; }
-                        slot[i] = (uint8_t)where[c];
-                    }
-                    for (int k = n; k < kCamStageCap; ++k) list[k] = 0;
-                    wn[w] = (uint8_t)n;
-                }
-            });
-            static_assert(kCamStageCap <= 254, "slot 255 means not staged");
-            UP_TRY(o_slot_.upload(slot));
-            UP_TRY(wg_cam_n_.upload(wn));
-            UP_TRY(wg_cam_list_.upload(wlist));
-        }
-        UP_TRY(o_cam_.upload(o_cam));
-        UP_TRY(o_pt_.upload(o_pt));
-        UP_TRY(o_orig_.upload(o_orig_h_));
-        UP_TRY(pt_ptr_.upload(pt_ptr));
-        UP_TRY(cam_ptr_.upload(cam_ptr));
-        UP_TRY(cam_obs_.upload(cam_obs));
-        UP_TRY(co_rank_.upload(co_rank));
-        if (so.device_gathers) {
-            // the caller's measurements go up as they are (one contiguous copy, no host gather), the three lists that are
-            // permutations of what is on the device already are made there
-            const size_t n_loc = o_cam.size();
-            if (warmer.joinable()) warmer.join();   // (the measurements went up on the device thread, beside the list building)
-            double* raw = raw_uv;
-            hipError_t ge = hipSuccess;
-            if (!raw) {
-                UP_TRY(raw_uv.alloc(std::max<size_t>(2 * (size_t)n_obs_, 2)));
-                raw = raw_uv;
-                ge = hipMemcpy(raw, obs_uv, 2 * (size_t)n_obs_ * sizeof(double), hipMemcpyHostToDevice);
-            }
-            // (plain allocations: every element is written by the gathers.  NOT alloc_zero -- its hipMemset runs on the
-            // null stream, which stream_ (non-blocking) does not follow: the clear could land AFTER the gather had written the
-            // array; seen once in 36 problems of the population test as a step of garbage)
-            if (ge == hipSuccess) ge = o_uv_.alloc(2 * n_loc);
-            if (ge == hipSuccess) ge = co_uv_.alloc(2 * n_loc);
-            if (ge == hipSuccess) ge = co_pt_.alloc(n_loc);
-            if (ge == hipSuccess) {
-                launch_gather_uv((int64_t)n_loc, o_orig_, raw, o_uv_, stream_);
-                launch_gather_uv((int64_t)n_loc, cam_obs_, o_uv_, co_uv_, stream_);
-                launch_gather_u32((int64_t)n_loc, cam_obs_, o_pt_, co_pt_, stream_);
-                ge = hipStreamSynchronize(stream_);
-            }
-            raw_uv.reset();
-            UP_TRY(ge);
-        } else {
-            UP_TRY(o_uv_.upload(o_uv));
-            UP_TRY(co_pt_.upload(co_pt));
-            UP_TRY(co_uv_.upload(co_uv));
-        }
-        {
-            std::vector<uint8_t> fp(6 * n_cam_, 0), fi(3 * n_cam_, 0), fl(3 * n_pt_, 0);
-            for (int64_t c = 0; c < n_cam_; ++c) {
-                if (fix_pose) memcpy(fp.data() + 6 * (size_t)cmap_[c], fix_pose + 6 * c, 6);
-                if (fix_intr) memcpy(fi.data() + 3 * (size_t)cmap_[c], fix_intr + 3 * c, 3);
-            }
-            if (fix_pt)
-                for (int64_t l = 0; l < n_pt_; ++l) memcpy(fl.data() + 3 * (size_t)lmap_[l], fix_pt + 3 * l, 3);
-            UP_TRY(fix_pose_.upload(fp));
-            UP_TRY(fix_intr_.upload(fi));
-            UP_TRY(fix_pt_.upload(fl));
-        }
-        for (int w = 0; w < 2; ++w) {
-            UP_TRY(poses_[w].alloc_zero(7 * n_cam_));
-            UP_TRY(intr_[w].alloc_zero(3 * n_cam_));
-            UP_TRY(pts_[w].alloc_zero(3 * n_pt_));
-            UP_TRY(camp_[w].alloc_zero((size_t)(kCamStride + kCamQStride) * n_cam_));   // [n_cam][16] records | [n_cam][10] compact form
-        }
-        UP_TRY(g_c_.alloc_zero(n_c_pad_));
-        UP_TRY(g_red_.alloc_zero(n_c_pad_));
-        UP_TRY(dcam_.alloc_zero(n_c_pad_));
-        UP_TRY(hinv_.alloc_zero((size_t)kLmStride * n_pt_));  // landmark records: Hll^-1 | g_l | point
-        // projection records of the local observations (xn, yn, p_w.z, sqrt(rho')): the record form of the pair kernel
-        UP_TRY(orec_.alloc_zero(4 * (size_t)o_cam.size()));
-        UP_TRY(g_l_.alloc_zero(3 * n_pt_));
-        UP_TRY(dl_.alloc_zero(3 * n_pt_));
-        UP_TRY(partial_.alloc_zero(3 * (size_t)n_partial_));
-        UP_TRY(scal_.alloc_zero(32));
-        UP_TRY(pcg_buf_.alloc_zero(7 * (size_t)n_c_pad_));
-        UP_TRY(lmu_.alloc_zero((size_t)kLmuStride * n_pt_));
-        UP_TRY(sd_.alloc_zero((size_t)n_cam_ * dc_ * dc_));
-        UP_TRY(minv_.alloc_zero((size_t)n_cam_ * dc_ * dc_));
-        UP_TRY(flags_.alloc_zero(4));
-        for (int b = 0; b < 2; ++b) {   // the pinned chunks of upload_staged: mapped here, not in the caller's first set_params
-            if (!pin_[b]) UP_TRY(pin_[b].alloc((size_t)16 << 20));
-            if (!pin_ev_[b]) UP_TRY(hipEventCreateWithFlags(&pin_ev_[b], hipEventDisableTiming));
-        }
-        up_seconds = since(t0);
-        return kOk;
-    };
-#undef UP_TRY
-    int up_rc = kOk;
-    std::thread uploader([&] {   // (nothing may escape a thread: an allocation failure becomes this call's status)
-        try { up_rc = upload_lists(); }
-        catch (const std::exception& ex) { up_rc = kDeviceError; up_err = std::string("set_structure uploads: ") + ex.what(); }
-    });
-    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{uploader};
+    return kOk;
+}
 
-    // ---- the tile plan: built beside the lists above, or here (distributed plans with tree sharding) -------------
-    if (plan_beside_lists) planner.join(); else build_plan();
-    if (matrix_free_only_) so.schur_form = -1;
-    if (!plan_err.empty()) { uploader.join(); return fail(kInvalidInput, "reduced camera matrix: " + plan_err); }
-    hs.seconds[2] = plan_seconds;
-    // ---- task lists of the selected form of the Schur reduction (they need the slot map) ------------------------------
-    // (tried in round 5: the pair list built from a host-only twin's slot map BEFORE the planner thread is done -- the host pool
-    // is shared, the three threads then slow one another down: set-up 0.26-0.28 s against 0.24)
-    PairDeviceTables dtab;
-    const bool recs_on_device = device_pair_recs_ && so.schur_form == 4 && dc_ == 9;
-    hs.build_schur_lists(so, tp_.slot_host(), recs_on_device ? &dtab : nullptr);
-    n_ptasks_ = (int)hs.pl.tasks.size();
-    n_pair_blocks_ = hs.pl.n_blocks; pair_queued_ = hs.pl.queued;
-    n_pair_slots_ = (recs_on_device && hs.pl.queued) ? dtab.n_slots : (int64_t)hs.pl.recs.size();
-    const PairLists& pl = hs.pl;
-    uploader.join();
-    if (up_rc != kOk) return fail(up_rc, up_err);
-    hs.release_scratch();
-    tr.mark("plan + Schur lists (observation lists uploading beside them)");
-    const auto t_up2 = std::chrono::steady_clock::now();
+// Uploads of everything that does not depend on the tile plan, on a thread of their own: the observation lists (1.7 GB on
+// final-13682), the camera staging lists, the masks and the work arrays go to the device while the calling thread builds
+// the tile plan and the pair list (round 5: 0.09 s of copies under 0.27 s of host work).
+void Solver::uploader_body(Setup& su) {   // (nothing may escape a thread: an allocation failure becomes this call's status)
+    try {
+        const auto t0 = std::chrono::steady_clock::now();
+        int rc = upload_observation_lists(su, &su.up_err);
+        if (rc == kOk) rc = upload_fixed_masks(su, &su.up_err);
+        if (rc == kOk) rc = alloc_work_arrays(&su.up_err);
+        if (rc == kOk) su.up_seconds = seconds_since(t0);
+        su.up_rc = rc;
+    } catch (const std::exception& ex) { su.up_rc = kDeviceError; su.up_err = std::string("set_structure uploads: ") + ex.what(); }
+}
+
+int Solver::upload_observation_lists(Setup& su, std::string* err) {
+    const BaHostStructure& hs = *su.hs;
+    HIP_TRY(hipSetDevice(device_), err);   // (the first step on its thread)
+    {
+        const BaHostStructure::CamStaging st = hs.build_cam_staging();   // (host work hidden on this thread)
+        HIP_TRY(o_slot_.upload(st.slot), err);
+        HIP_TRY(wg_cam_n_.upload(st.wg_n), err);
+        HIP_TRY(wg_cam_list_.upload(st.wg_list), err);
+    }
+    HIP_TRY(o_cam_.upload(hs.o_cam), err);
+    HIP_TRY(o_pt_.upload(hs.o_pt), err);
+    HIP_TRY(o_orig_.upload(o_orig_h_), err);
+    HIP_TRY(pt_ptr_.upload(hs.pt_ptr), err);
+    HIP_TRY(cam_ptr_.upload(hs.cam_ptr), err);
+    HIP_TRY(cam_obs_.upload(hs.cam_obs), err);
+    HIP_TRY(co_rank_.upload(hs.co_rank), err);
+    if (!su.so.device_gathers) {
+        HIP_TRY(o_uv_.upload(hs.o_uv), err);
+        HIP_TRY(co_pt_.upload(hs.co_pt), err);
+        HIP_TRY(co_uv_.upload(hs.co_uv), err);
+        return kOk;
+    }
+    // the caller's measurements go up as they are (one contiguous copy, no host gather), the three lists that are
+    // permutations of what is on the device already are made there
+    const size_t n_loc = hs.o_cam.size();
+    if (su.device_thread.joinable()) su.device_thread.join();   // (the measurements went up on the device thread, beside the list building)
+    hipError_t ge = hipSuccess;
+    if (!su.raw_uv) {
+        HIP_TRY(su.raw_uv.alloc(std::max<size_t>(2 * (size_t)n_obs_, 2)), err);
+        ge = hipMemcpy(su.raw_uv, su.obs_uv, 2 * (size_t)n_obs_ * sizeof(double), hipMemcpyHostToDevice);
+    }
+    // (plain allocations: every element is written by the gathers.  NOT alloc_zero -- its hipMemset runs on the
+    // null stream, which stream_ (non-blocking) does not follow: the clear could land AFTER the gather had written the
+    // array; seen once in 36 problems of the population test as a step of garbage)
+    if (ge == hipSuccess) ge = o_uv_.alloc(2 * n_loc);
+    if (ge == hipSuccess) ge = co_uv_.alloc(2 * n_loc);
+    if (ge == hipSuccess) ge = co_pt_.alloc(n_loc);
+    if (ge == hipSuccess) {
+        launch_gather_uv((int64_t)n_loc, o_orig_, su.raw_uv, o_uv_, stream_);
+        launch_gather_uv((int64_t)n_loc, cam_obs_, o_uv_, co_uv_, stream_);
+        launch_gather_u32((int64_t)n_loc, cam_obs_, o_pt_, co_pt_, stream_);
+        ge = hipStreamSynchronize(stream_);
+    }
+    su.raw_uv.reset();
+    HIP_TRY(ge, err);
+    return kOk;
+}
+
+int Solver::upload_fixed_masks(const Setup& su, std::string* err) {
+    std::vector<uint8_t> fp(6 * n_cam_, 0), fi(3 * n_cam_, 0), fl(3 * n_pt_, 0);
+    for (int64_t c = 0; c < n_cam_; ++c) {
+        if (su.fix_pose) memcpy(fp.data() + 6 * (size_t)cmap_[c], su.fix_pose + 6 * c, 6);
+        if (su.fix_intr) memcpy(fi.data() + 3 * (size_t)cmap_[c], su.fix_intr + 3 * c, 3);
+    }
+    if (su.fix_pt)
+        for (int64_t l = 0; l < n_pt_; ++l) memcpy(fl.data() + 3 * (size_t)lmap_[l], su.fix_pt + 3 * l, 3);
+    HIP_TRY(fix_pose_.upload(fp), err);
+    HIP_TRY(fix_intr_.upload(fi), err);
+    HIP_TRY(fix_pt_.upload(fl), err);
+    return kOk;
+}
+
+int Solver::alloc_work_arrays(std::string* err) {
+    for (int w = 0; w < 2; ++w) {
+        HIP_TRY(poses_[w].alloc_zero(7 * n_cam_), err);
+        HIP_TRY(intr_[w].alloc_zero(3 * n_cam_), err);
+        HIP_TRY(pts_[w].alloc_zero(3 * n_pt_), err);
+        HIP_TRY(camp_[w].alloc_zero((size_t)(kCamStride + kCamQStride) * n_cam_), err);   // [n_cam][16] records | [n_cam][10] compact form
+    }
+    HIP_TRY(g_c_.alloc_zero(n_c_pad_), err);
+    HIP_TRY(g_red_.alloc_zero(n_c_pad_), err);
+    HIP_TRY(dcam_.alloc_zero(n_c_pad_), err);
+    HIP_TRY(hinv_.alloc_zero((size_t)kLmStride * n_pt_), err);  // landmark records: Hll^-1 | g_l | point
+    // projection records of the local observations (xn, yn, p_w.z, sqrt(rho')): the record form of the pair kernel
+    HIP_TRY(orec_.alloc_zero(4 * o_orig_h_.size()), err);
+    HIP_TRY(g_l_.alloc_zero(3 * n_pt_), err);
+    HIP_TRY(dl_.alloc_zero(3 * n_pt_), err);
+    HIP_TRY(partial_.alloc_zero(3 * (size_t)n_partial_), err);
+    HIP_TRY(scal_.alloc_zero(32), err);
+    HIP_TRY(pcg_buf_.alloc_zero(7 * (size_t)n_c_pad_), err);
+    HIP_TRY(lmu_.alloc_zero((size_t)kLmuStride * n_pt_), err);
+    HIP_TRY(sd_.alloc_zero((size_t)n_cam_ * dc_ * dc_), err);
+    HIP_TRY(minv_.alloc_zero((size_t)n_cam_ * dc_ * dc_), err);
+    HIP_TRY(flags_.alloc_zero(4), err);
+    for (int b = 0; b < 2; ++b) {   // the pinned chunks of upload_staged: mapped here, not in the caller's first set_params
+        if (!pin_[b]) HIP_TRY(pin_[b].alloc((size_t)16 << 20), err);
+        if (!pin_ev_[b]) HIP_TRY(hipEventCreateWithFlags(&pin_ev_[b], hipEventDisableTiming), err);
+    }
+    return kOk;
+}
+
+// The task lists of the Schur reduction, after the uploader is joined (the device builds the records from its lists).
+int Solver::upload_pair_lists(Setup& su, const PairDeviceTables& dtab, bool recs_on_device) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const PairLists& pl = su.hs->pl;
     HIP_TRY(ptasks_.upload(pl.tasks));
     HIP_TRY(pchunks_.upload(pl.chunks));
     HIP_TRY(pblocks_.upload(pl.blocks));
@@ -492,23 +473,97 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     }
     pqdesc_.reset();
     if (pl.queued) HIP_TRY(pqdesc_.upload(pl.qdesc));
-    up_seconds += since(t_up2);
-    (void)t_up;
+    su.up_seconds += seconds_since(t0);
+    return kOk;
+}
 
-    HIP_TRY(hipDeviceSynchronize());  // the null-stream memsets above precede any work on stream_
-    hs.seconds[4] = up_seconds;   // (copy time; the first part of it ran beside the plan and the pair list)
-    hs.seconds[5] = since(t_begin);
-    for (int k = 0; k < 6; ++k) setup_s_[k] = hs.seconds[k];
-    tr.mark("set_structure body");
-    // the host lists (3.7 GB on final-13682) are unmapped off the caller's path: 0.2 s
+// the host lists (3.7 GB on final-13682) are unmapped off the caller's path: 0.2 s
+void Solver::hand_lists_to_free_thread(Setup& su) {
     if (free_thread_.joinable()) free_thread_.join();
+    const char* fm = getenv("APEX_SETUP_FREE");   // experiment switch: "sync" frees on the caller's path, "leak" never
+    if (fm && !strcmp(fm, "sync")) su.hs.reset();
+    else if (fm && !strcmp(fm, "leak")) (void)su.hs.release();
+    else free_thread_ = std::thread([p = su.hs.release()] { delete p; (void)HostBlockCache::get().end_setup(); });   // (what only an older, larger structure used goes back to the system)
+}
+
+int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const double* obs_uv,
+                          const int64_t* intr_col, const int64_t* pose_col, const int64_t* pt_col,
+                          const uint8_t* fix_pose, const uint8_t* fix_intr, const uint8_t* fix_pt,
+                          double huber_delta) {
+    if (n_cam_ <= 0 || n_pt_ <= 0) return fail(kInvalidInput, n_cam_ <= 0 ? "No camera variables found" : "No landmark variables found");
+    if (n_obs_ < 0 || n_obs_ > 2000000000LL) return fail(kInvalidInput, "observation count out of range");
+    lc_release();   // (the landmark covariance lists belong to the old structure)
+    Setup su;   // (its destructor releases and joins whatever thread is still out, on every return below)
+    su.cam_idx = cam_idx; su.pt_idx = pt_idx; su.obs_uv = obs_uv;
+    su.fix_pose = fix_pose; su.fix_intr = fix_intr; su.fix_pt = fix_pt;
+    su.raw_uv_wanted = world_ == 1;
+    su.device_thread = std::thread(&Solver::device_thread_body, this, std::ref(su));
+    { const int rc = validate_indices(su); if (rc != kOk) return rc; }
+    su.release_device_thread(true);
+    huber_delta_ = huber_delta;
+    intr_col_.assign(intr_col, intr_col + n_cam_);
+    pose_col_.assign(pose_col, pose_col + n_cam_);
+    pt_col_.assign(pt_col, pt_col + n_pt_);
+    // (the caller's factor list is NOT kept: get_hessian_csc, the one reader, rebuilds it from the device's observation
+    // lists on demand -- 0.1 s of set-up on final-13682 for an export the LM loop never calls)
+    su.tr.mark("validate the index lists");
+
+    // ---- everything derived from the observation list on the host (ba_structure.h): internal camera order (hub
+    // cameras last, nested dissection of the tile graph), tile structure, landmark sharding, observation lists ------
+    su.t_begin = std::chrono::steady_clock::now();
+    HostBlockCache::get().begin_setup();
+    BaStructOptions& so = su.so;
+    so.dc = dc_; so.use_nd = use_nd_; so.nd_leaf = nd_leaf_; so.hubs_last = hubs_last_;
+    so.rank = rank_; so.world = world_; so.dist_factor = dist_factor_; so.tree_sharding = tree_sharding_;
+    so.dist_selftest = dist_selftest_; so.schur_form = rows_form_;
+    so.device_gathers = world_ == 1;
+    BaHostStructure& hs = *su.hs;
+    // Camera order and tile structure first; then the tile plan (symbolic fill, task lists, 1.4 GB of device allocations: 0.06-
+    // 0.1 s, mostly serial) is built on a thread of its own BESIDE the observation lists (0.1 s), which do not need it (round 5).
+    // A distributed plan with tree sharding previews the partition inside the list phase on the same TilePlan: no overlap then.
+    hs.build_order(n_cam_, n_pt_, n_obs_, cam_idx, pt_idx, so, tp_);
+    nt_ = hs.nt;
+    su.present_plan = hs.present;
+    su.tr.mark("camera order, tile structure");
+    const bool plan_beside_lists = !BaHostStructure::needs_owner_preview(so);
+    if (plan_beside_lists) su.planner = std::thread(&Solver::planner_body, this, std::ref(su));
     {
-        const char* fm = getenv("APEX_SETUP_FREE");   // experiment switch: "sync" frees on the caller's path, "leak" never
-        if (fm && !strcmp(fm, "sync")) hs_owner.reset();
-        else if (fm && !strcmp(fm, "leak")) (void)hs_owner.release();
-        else free_thread_ = std::thread([p = hs_owner.release()] { delete p; (void)HostBlockCache::get().end_setup(); });   // (what only an older, larger structure used goes back to the system)
+        const std::string e = hs.build_obs_lists(cam_idx, pt_idx, obs_uv, so, tp_);
+        if (!e.empty()) return fail(kInvalidInput, e);
     }
-    tr.mark("host lists handed to the free thread");
+    su.tr.mark("observation lists");
+    HIP_TRY(device_ready(su));
+    su.tr.mark("waited for the device thread");
+    { const int rc = adopt_host_structure(su); if (rc != kOk) return rc; }
+    su.uploader = std::thread(&Solver::uploader_body, this, std::ref(su));
+
+    // ---- the tile plan: built beside the lists above, or here (distributed plans with tree sharding) -------------
+    if (plan_beside_lists) su.planner.join(); else choose_and_build_plan(su);
+    if (matrix_free_only_) so.schur_form = -1;
+    if (!su.plan_err.empty()) return fail(kInvalidInput, "reduced camera matrix: " + su.plan_err);
+    hs.seconds[2] = su.plan_seconds;
+    // ---- task lists of the selected form of the Schur reduction (they need the slot map) ------------------------------
+    // (tried in round 5: the pair list built from a host-only twin's slot map BEFORE the planner thread is done -- the host pool
+    // is shared, the three threads then slow one another down: set-up 0.26-0.28 s against 0.24)
+    PairDeviceTables dtab;
+    const bool recs_on_device = device_pair_recs_ && so.schur_form == 4 && dc_ == 9;
+    hs.build_schur_lists(so, tp_.slot_host(), recs_on_device ? &dtab : nullptr);
+    n_ptasks_ = (int)hs.pl.tasks.size();
+    n_pair_blocks_ = hs.pl.n_blocks; pair_queued_ = hs.pl.queued;
+    n_pair_slots_ = (recs_on_device && hs.pl.queued) ? dtab.n_slots : (int64_t)hs.pl.recs.size();
+    su.uploader.join();
+    if (su.up_rc != kOk) return fail(su.up_rc, su.up_err);
+    hs.release_scratch();
+    su.tr.mark("plan + Schur lists (observation lists uploading beside them)");
+    { const int rc = upload_pair_lists(su, dtab, recs_on_device); if (rc != kOk) return rc; }
+
+    HIP_TRY(hipDeviceSynchronize());  // the null-stream memsets of the work arrays precede any work on stream_
+    hs.seconds[4] = su.up_seconds;   // (copy time; the first part of it ran beside the plan and the pair list)
+    hs.seconds[5] = seconds_since(su.t_begin);
+    for (int k = 0; k < 6; ++k) setup_s_[k] = hs.seconds[k];
+    su.tr.mark("set_structure body");
+    hand_lists_to_free_thread(su);
+    su.tr.mark("host lists handed to the free thread");
 
     have_structure_ = true;
     have_params_ = have_step_ = have_trial_ = false;

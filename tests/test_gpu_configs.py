@@ -493,6 +493,37 @@ def test_variant_is_selected_by_predicted_cost(oracle):
     s.close()
 
 
+def test_a_refused_index_list_leaves_the_handle_usable():
+    """One observation names camera n_cam: apexgpu_set_structure returns APEXGPU_ERR_INVALID_INPUT and says which observation
+    -- after the set-up's device thread has started, which waits for the verdict on the index lists and has to be released
+    and joined on that way out.  The same handle then takes the valid list, and its step is that of a fresh handle."""
+    import dataclasses
+
+    d = pkg.synthetic.make_problem(120, 6000, 3, 7, config_id=1)
+    prob = Problem.bundle_adjustment(d, OptimizationType.SelfCalibration, 1.0)
+    k = d.n_obs // 2
+    cam_bad = d.cam_idx.copy()
+    cam_bad[k] = d.n_cam
+    bad = Problem.bundle_adjustment(dataclasses.replace(d, cam_idx=cam_bad), OptimizationType.SelfCalibration, 1.0)
+    s = GpuSchurComplementSolver(0)
+    with pytest.raises(pkg.capi.LinAlgError) as ei:
+        s.initialize_structure(bad)
+    assert ei.value.code == -5 and ei.value.kind == "InvalidInput"
+    assert f"observation {k} references a missing variable" in str(ei.value)
+    s._problem = bad      # (recorded on success only; reinitialize_structure checks the new counts against it)
+    s.reinitialize_structure(prob)
+    s.set_parameters(d.poses, d.intr, d.points)
+    step = s.solve_augmented_equation(1e-3).copy()
+    grad = s.get_gradient().copy()
+    s.close()
+    _, fresh = make(d, "selfcal")
+    step_fresh = fresh.solve_augmented_equation(1e-3)
+    print("after a refused index list: step / gradient against a fresh handle", rel(step, step_fresh), rel(grad, fresh.get_gradient()))
+    assert np.isfinite(step).all() and np.linalg.norm(step) > 0
+    assert rel(step, step_fresh) < 1e-12 and rel(grad, fresh.get_gradient()) < 1e-12
+    fresh.close()
+
+
 def test_host_block_cache_lives_with_the_handles():
     """The set-up's big host blocks (observation lists, pair list) are cached for the next set_structure -- but only while a
     handle is alive: apexgpu_destroy of the last one returns everything to the system (apexgpu_host_cache_bytes), and a smaller
