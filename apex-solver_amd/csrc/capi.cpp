@@ -66,6 +66,40 @@ static int covariance_stats(S* s, double out[6], double* group_ms, int group_cap
     return APEXGPU_OK;
 }
 
+// What both handles answer alike (tile_backend.h), over the handle's solver type: the option names they share (false: not one
+// of them), the four counters, the stage-timing switch.
+template <typename S>
+static bool shared_option(S* s, const std::string& n, int value) {
+    if (n == "graphs") s->enable_graphs(value != 0);
+    else if (n == "update_overlap") { s->enable_overlap(value != 0); if (value > 1) s->set_overlap_min(value); }
+    else if (n == "tri_dataflow") s->enable_tri_flow(value != 0);
+    else if (n == "split_u1") s->set_split_u1(value);
+    else if (n == "flood_gate") s->set_gate_min(value);
+    else if (n == "two_side") s->set_two_side(value);
+    else if (n == "eager_step_eval") s->set_eager_step_eval(value != 0);
+    else if (n == "one_wait") s->set_one_wait(value != 0);
+    else if (n == "factor_flow") s->set_factor_flow(value, 0);          // max columns per level group inside the dataflow launch (0: off)
+    else if (n == "factor_flow_rows") s->set_factor_flow(s->plan().factor_flow_cols(), value);
+    else if (n == "debug_poison_sweep") s->debug_poison_next_solve(value);   /* tests: 1 / 2 = the next solve's forward / backward dataflow sweep times out */
+    else if (n == "debug_poison_factor") s->debug_poison_next_factor();       /* tests: the next factorisation's dataflow launch times out */
+    else if (n == "nested_dissection") s->set_nd(value != 0, value > 1 ? value : 0);  /* value > 1: leaf size */
+    else if (n == "covariance_timing") s->enable_covariance_timing(value != 0);   /* per level group times of the covariance calls, landmark pass time */
+    else return false;
+    return true;
+}
+template <typename S>
+static int counters(S* s, int64_t out[4]) {
+    if (!out) return APEXGPU_ERR_INVALID_INPUT;
+    out[0] = s->sweep_timeouts(); out[1] = s->plan().tri_flow() ? 1 : 0; out[2] = s->factor_flow_timeouts(); out[3] = s->plan().factor_flow_groups();
+    return APEXGPU_OK;
+}
+template <typename S>
+static int stage_timing(S* s, int on) {
+    if (on > 1) s->enable_stage_timing_only((uint32_t)on >> 1);   // bit k + 1 of `on`: stage k alone is timed
+    else s->enable_stage_timing(on != 0);
+    return APEXGPU_OK;
+}
+
 // APEX_SEGV_BACKTRACE=1 (debugging aid): the native stack of a crash on stderr (the GPU boxes have no debugger)
 #include <execinfo.h>
 #include <signal.h>
@@ -319,38 +353,23 @@ int apexgpu_set_option(apexgpu_solver* h, const char* name, int value) {
         if (value != 3 && value != 4) return APEXGPU_ERR_INVALID_INPUT;
         h->s->set_schur_form(value);
     }
-    else if (n == "graphs") h->s->enable_graphs(value != 0);
-    else if (n == "update_overlap") { h->s->enable_overlap(value != 0); if (value > 1) h->s->set_overlap_min(value); }
-    else if (n == "tri_dataflow") h->s->enable_tri_flow(value != 0);
-    else if (n == "split_u1") h->s->set_split_u1(value);
-    else if (n == "flood_gate") h->s->set_gate_min(value);
-    else if (n == "two_side") h->s->set_two_side(value);
+    else if (shared_option(h->s, n, value)) return APEXGPU_OK;
     else if (n == "matrix_free_only") h->s->set_matrix_free_only(value != 0);
     else if (n == "auto_variant") h->s->set_auto_variant(value != 0);
     else if (n == "variant_cost_permille") h->s->set_variant_cost_permille(value);
     else if (n == "device_pair_list") h->s->set_device_pair_recs(value != 0);
-    else if (n == "eager_step_eval") h->s->set_eager_step_eval(value != 0);
-    else if (n == "one_wait") h->s->set_one_wait(value != 0);
     else if (n == "max_tile_updates") h->s->set_max_tile_updates(value);
-    else if (n == "factor_flow") h->s->set_factor_flow(value, 0);          // max columns per level group inside the dataflow launch (0: off)
-    else if (n == "factor_flow_rows") h->s->set_factor_flow(h->s->plan().factor_flow_cols(), value);
-    else if (n == "debug_poison_sweep") h->s->debug_poison_next_solve(value);   /* tests: 1 / 2 = the next solve's forward / backward dataflow sweep times out */
-    else if (n == "debug_poison_factor") h->s->debug_poison_next_factor();       /* tests: the next factorisation's dataflow launch times out */
     else if (n == "debug_occupy_cus") return h->s->debug_occupy_cus(value, 40000);   /* tests: block `value` CUs for 40 ms, starting now */
     else if (n == "hubs_last") h->s->set_hubs_last(value != 0);
     else if (n == "dist_factor") h->s->set_dist_factor(value != 0);
     else if (n == "tree_sharding") h->s->set_tree_sharding(value != 0);
     else if (n == "dist_selftest") h->s->set_dist_selftest(value);
-    else if (n == "nested_dissection") h->s->set_nd(value != 0, value > 1 ? value : 0);  /* value > 1: leaf size */
-    else if (n == "covariance_timing") h->s->enable_covariance_timing(value != 0);   /* per level group times of apexgpu_camera_covariance, landmark pass time */
     else return APEXGPU_ERR_INVALID_INPUT;
     return APEXGPU_OK;
 }
 int apexgpu_enable_stage_timing(apexgpu_solver* h, int on) {
     H_OR_FAIL;
-    if (on > 1) h->s->enable_stage_timing_only((uint32_t)on >> 1);   // bit k + 1 of `on`: stage k alone is timed
-    else h->s->enable_stage_timing(on != 0);
-    return APEXGPU_OK;
+    return stage_timing(h->s, on);
 }
 int apexgpu_reset_stage_times(apexgpu_solver* h) { H_OR_FAIL; h->s->reset_stage_times(); return APEXGPU_OK; }
 int apexgpu_stage_times(apexgpu_solver* h, double ms[APEXGPU_NUM_STAGES], int64_t calls[APEXGPU_NUM_STAGES]) {
@@ -413,9 +432,7 @@ int apexgpu_variant_info(apexgpu_solver* h, int asked_variant, int* used_variant
 
 int apexgpu_counters(apexgpu_solver* h, int64_t out[4]) {
     H_OR_FAIL;
-    if (!out) return APEXGPU_ERR_INVALID_INPUT;
-    out[0] = h->s->sweep_timeouts(); out[1] = h->s->plan().tri_flow() ? 1 : 0; out[2] = h->s->factor_flow_timeouts(); out[3] = h->s->plan().factor_flow_groups();
-    return APEXGPU_OK;
+    return counters(h->s, out);
 }
 
 int apexgpu_get_unique_id(void* out128) {
@@ -682,28 +699,11 @@ int apexgpu_pg_covariance_stats(apexgpu_pg_solver* h, double out[6], double* gro
 int apexgpu_pg_set_option(apexgpu_pg_solver* h, const char* name, int value) {
     PG_OR_FAIL;
     const std::string n = name ? name : "";
-    if (n == "graphs") h->s->enable_graphs(value != 0);
-    else if (n == "update_overlap") { h->s->enable_overlap(value != 0); if (value > 1) h->s->set_overlap_min(value); }
-    else if (n == "tri_dataflow") h->s->enable_tri_flow(value != 0);
-    else if (n == "two_side") h->s->set_two_side(value);
-    else if (n == "factor_flow") h->s->set_factor_flow(value, 0);
-    else if (n == "factor_flow_rows") h->s->set_factor_flow(h->s->plan().factor_flow_cols(), value);
-    else if (n == "flood_gate") h->s->set_gate_min(value);
-    else if (n == "split_u1") h->s->set_split_u1(value);
-    else if (n == "one_wait") h->s->set_one_wait(value != 0);
-    else if (n == "eager_step_eval") h->s->set_eager_step_eval(value != 0);
-    else if (n == "nested_dissection") h->s->set_nd(value != 0, value > 1 ? value : 0);
-    else if (n == "debug_poison_sweep") h->s->debug_poison_next_solve(value);
-    else if (n == "debug_poison_factor") h->s->debug_poison_next_factor();
-    else if (n == "covariance_timing") h->s->enable_covariance_timing(value != 0);
-    else return APEXGPU_ERR_INVALID_INPUT;
-    return APEXGPU_OK;
+    return shared_option(h->s, n, value) ? APEXGPU_OK : APEXGPU_ERR_INVALID_INPUT;
 }
 int apexgpu_pg_enable_stage_timing(apexgpu_pg_solver* h, int on) {
     PG_OR_FAIL;
-    if (on > 1) h->s->enable_stage_timing_only((uint32_t)on >> 1);   // bit k + 1 of `on`: stage k alone is timed
-    else h->s->enable_stage_timing(on != 0);
-    return APEXGPU_OK;
+    return stage_timing(h->s, on);
 }
 int apexgpu_pg_reset_stage_times(apexgpu_pg_solver* h) { PG_OR_FAIL; h->s->reset_stage_times(); return APEXGPU_OK; }
 int apexgpu_pg_stage_times(apexgpu_pg_solver* h, double ms[APEXGPU_PG_NUM_STAGES], int64_t calls[APEXGPU_PG_NUM_STAGES]) {
@@ -713,9 +713,7 @@ int apexgpu_pg_stage_times(apexgpu_pg_solver* h, double ms[APEXGPU_PG_NUM_STAGES
 }
 int apexgpu_pg_counters(apexgpu_pg_solver* h, int64_t out[4]) {
     PG_OR_FAIL;
-    if (!out) return APEXGPU_ERR_INVALID_INPUT;
-    out[0] = h->s->sweep_timeouts(); out[1] = h->s->plan().tri_flow() ? 1 : 0; out[2] = h->s->factor_flow_timeouts(); out[3] = h->s->plan().factor_flow_groups();
-    return APEXGPU_OK;
+    return counters(h->s, out);
 }
 int apexgpu_pg_info(apexgpu_pg_solver* h, double info[8]) {
     PG_OR_FAIL;

@@ -18,19 +18,16 @@
 #include <string>
 #include <vector>
 
-#include "device_buffer.h"
-#include "lm_loop.h"
 #include "pg2_kernels.h"
 #include "pg_kernels.h"
-#include "stage_timer.h"
-#include "tile_plan.h"
+#include "tile_backend.h"
 
 namespace apex {
 
 enum PgManifold { kManifoldSE3 = 0, kManifoldSE2 = 1 };
 enum PgStage { kPgAssemble = 0, kPgFactor, kPgTriSolve, kPgStats, kPgRetract, kPgCost, kPgNumStages };
 
-class PoseGraphSolver : public LmBackend {
+class PoseGraphSolver : public TileBackend {
    public:
     PoseGraphSolver(int64_t n_v, int64_t n_e, int device, int manifold = kManifoldSE3);
     ~PoseGraphSolver() override;
@@ -68,27 +65,7 @@ class PoseGraphSolver : public LmBackend {
     // (TilePlan::covariance_blocks).  out[n_v][6][6], caller's vertex order, columns as get_hessian's.  kInvalidState when
     // no valid factor is held (no solve yet, or an export / assembly since).
     int covariance(double* out);
-    void enable_covariance_timing(bool on) { tp_.enable_covariance_timing(on); }
 
-    void enable_graphs(bool on) { tp_.enable_graphs(on); }
-    void enable_overlap(bool on) { tp_.enable_overlap(on); }
-    void enable_tri_flow(bool on) { tp_.enable_tri_flow(on); }
-    int sweep_timeouts() const { return tp_.sweep_timeouts(); }
-    void debug_poison_next_solve(int which) { tp_.debug_poison_next_solve(which); }
-    void set_split_u1(int min_tasks) { tp_.set_split_u1(min_tasks); }
-    void set_one_wait(bool on) { one_wait_ = on; }
-    void set_eager_step_eval(bool on) { eager_eval_ = on; }
-    void set_overlap_min(int n) { tp_.set_overlap_min(n); }
-    void set_gate_min(int n) { tp_.set_gate_min(n); }
-    void set_two_side(int mode) { tp_.set_two_side(mode); }
-    void set_factor_flow(int max_cols, int max_rows) { tp_.set_factor_flow(max_cols, max_rows); }
-    int factor_flow_timeouts() const { return n_factor_flow_timeouts_; }
-    void debug_poison_next_factor() { tp_.debug_poison_next_factor(); }
-    void set_nd(bool on, int leaf) { use_nd_ = on; if (leaf > 0) nd_leaf_ = leaf; }
-    void enable_stage_timing(bool on) { timer_.enable(on); }
-    void enable_stage_timing_only(uint32_t stage_mask) { timer_.enable_only(stage_mask); }
-    void reset_stage_times() { timer_.reset(); }
-    int stage_times(double* ms, int64_t* n) { return timer_.times(ms, n); }
     int64_t n_vertices() const { return n_v_; }
     int manifold() const { return manifold_; }
     int dof() const { return dof_; }           // tangent columns per vertex: 6 | 3
@@ -96,13 +73,14 @@ class PoseGraphSolver : public LmBackend {
     int n_tile_rows() const { return tp_.nt(); }
     int64_t tile_count() const { return tp_.n_slots(); }
     int64_t touched_tiles() const { return tp_.n_touched_slots(); }
-    int n_levels() const { return tp_.n_levels(); }
-    const TilePlan& plan() const { return tp_; }
-    const char* last_error() const override { return err_.c_str(); }
 
    private:
-    int fail(int code, const std::string& msg) { err_ = msg; return code; }
-    int check_hip(hipError_t e, const char* what);
+    // the direct solve's hooks (tile_backend.h)
+    int rebuild_system(double lambda, double reg) override;
+    int factor_now(int* failed, bool defer_flags) override;
+    int enqueue_sweeps() override;
+    int finish_step(double* step_out, double* grad_out) override;
+    int recover_factor(double lambda, int failed, bool gave_up) override;
     PGView view(int which) const;
     PG2View view2(int which) const;
     // the manifold-specific launches
@@ -115,31 +93,15 @@ class PoseGraphSolver : public LmBackend {
     int cost_of(int which, double* out);
 
     int64_t n_v_, n_e_;
-    int device_;
     int manifold_, dof_, amb_, stride_, vpt_;   // vpt_: vertices per tile = kNB / dof_
     int64_t n_ = 0, n_pad_ = 0;
     double huber_delta_ = 0.0;
-    bool have_structure_ = false, have_params_ = false, have_step_ = false, have_trial_ = false;
-    int cur_ = 0;
-    double last_lambda_ = 0.0;
-    bool use_nd_ = true;
-    int nd_leaf_ = 2;
+    bool have_structure_ = false, have_params_ = false;
     std::vector<int64_t> pose_col_;
     std::vector<int> vmap_;  // caller's vertex -> internal vertex
-    hipStream_t stream_ = nullptr;
-    // destroys stream_ when the members below it are gone: ~PoseGraphSolver synchronises the stream, then the buffers (and the
-    // plan) are freed in reverse order of declaration, then this runs
-    struct StreamLast { hipStream_t& s; ~StreamLast() { if (s) (void)hipStreamDestroy(s); } } stream_last_{stream_};
-    TilePlan tp_;
     DeviceBuffer<double> poses_[2], posep_[2];
     DeviceBuffer<uint32_t> e_from_, e_to_;
     int n_prior_ = 0;
-    int n_factor_flow_timeouts_ = 0;
-    // one device round trip per LM iteration (round 5, as in Solver): the pivot flags are read at the solve's final wait, and the
-    // step statistics and the trial cost the LM loop asks next ride on that wait too ("one_wait", "eager_step_eval")
-    bool one_wait_ = true, eager_eval_ = true;
-    int64_t step_serial_ = 0, eager_serial_ = -1;
-    PinnedBuffer<double> eager_host_;   // [0..2] step statistics, [3] sum of squares at the trial point
     DeviceBuffer<uint32_t> prior_v_;
     DeviceBuffer<int> inc_ptr_, prior_slot_;   // SE2 only: incident-edge CSR, the caller's index of each sorted prior
     DeviceBuffer<uint32_t> inc_edge_;
@@ -152,8 +114,6 @@ class PoseGraphSolver : public LmBackend {
     std::vector<double> scale_h_;
     bool scaled_ = false;
     int n_partial_ = 256;
-    StageTimer<kPgNumStages> timer_;
-    std::string err_;
 };
 
 }  // namespace apex

@@ -13,25 +13,14 @@
 
 namespace apex {
 
-#define HIP_TRY(expr)                                      \
-    do {                                                   \
-        hipError_t _e = (expr);                            \
-        if (_e != hipSuccess) return check_hip(_e, #expr); \
-    } while (0)
-
 PoseGraphSolver::PoseGraphSolver(int64_t n_v, int64_t n_e, int device, int manifold)
-    : n_v_(n_v), n_e_(n_e), device_(device), manifold_(manifold == kManifoldSE2 ? kManifoldSE2 : kManifoldSE3),
+    : TileBackend(device, kPgNumStages, /*nd_leaf=*/2), n_v_(n_v), n_e_(n_e), manifold_(manifold == kManifoldSE2 ? kManifoldSE2 : kManifoldSE3),
       dof_(manifold_ == kManifoldSE2 ? 3 : 6), amb_(manifold_ == kManifoldSE2 ? 3 : 7),
       stride_(manifold_ == kManifoldSE2 ? kPose2Stride : kPoseStride), vpt_(kNB / dof_) {}
 
 PoseGraphSolver::~PoseGraphSolver() {
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);   // before any buffer is freed; stream_last_ destroys the stream after them
-}
-
-int PoseGraphSolver::check_hip(hipError_t e, const char* what) {
-    if (e == hipSuccess) return kOk;
-    return fail(kDeviceError, std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
 }
 
 PGView PoseGraphSolver::view(int which) const {
@@ -262,94 +251,79 @@ int PoseGraphSolver::assemble(double lambda) {
     return kOk;
 }
 
+// the damped system (J^T J + lambda I) dx = -J^T r at the current parameters, ready to factorise
+int PoseGraphSolver::rebuild_system(double lambda, double) {
+    const int rc = assemble(lambda);
+    if (rc != kOk) return rc;
+    launch_pg_negate(n_pad_, g_, rhs_, stream_);
+    if (scaled_) launch_vec_mul(n_pad_, rhs_, scale_, rhs_, stream_);  // -D g
+    return kOk;
+}
+
+int PoseGraphSolver::factor_now(int* failed, bool defer_flags) {
+    timer_.begin(kPgFactor, stream_);
+    HIP_TRY(tp_.factor(failed, defer_flags));
+    timer_.end(kPgFactor, stream_);
+    return kOk;
+}
+
+// No ladder here: a give-up is repaired (H again, the level launches), a failed pivot is the caller's error.
+int PoseGraphSolver::recover_factor(double lambda, int failed, bool gave_up) {
+    if (gave_up) {
+        const int rc = factor_again(lambda, 0.0, &failed);
+        if (rc != kOk) return rc;
+    }
+    return failed ? fail(kSingularMatrix, "Cholesky factorization failed (matrix may be singular)") : kOk;
+}
+
 // SparseCholeskySolver::solve_augmented_equation (cholesky.rs:159-230): (J^T J + lambda I) dx = -J^T r
 int PoseGraphSolver::solve_augmented(double lambda, int variant, double* step_out, double* grad_out) {
     if (!have_params_) return fail(kInvalidState, "Block structure not built or parameters not set");
     if (variant != 0) return fail(kInvalidInput, "the pose-graph backend has the sparse Cholesky solver only");
     HIP_TRY(hipSetDevice(device_));
-    have_step_ = false;
-    have_trial_ = false;   // (this solve's eager step evaluation overwrites the trial poses)
-    ++step_serial_;
-    last_lambda_ = lambda;
-    int rc = assemble(lambda);
-    if (rc != kOk) return rc;
-    launch_pg_negate(n_pad_, g_, rhs_, stream_);
-    if (scaled_) launch_vec_mul(n_pad_, rhs_, scale_, rhs_, stream_);  // -D g
-    timer_.begin(kPgFactor, stream_);
-    int failed = 0;
-    // (one_wait_: the pivot flags and the dataflow launch's time-out word are read at the final wait below; the sweeps over a
-    // failed factor are then void and the old path runs from the assembly on)
-    bool speculative = one_wait_;
-    HIP_TRY(tp_.factor(&failed, /*defer_flags=*/speculative));
-    auto after_time_out = [&]() -> int {
-        // the dataflow launch of the top groups timed out (the plan is back on the level launches): H is half updated
-        ++n_factor_flow_timeouts_;
-        int r = assemble(lambda);
-        if (r != kOk) return r;
-        launch_pg_negate(n_pad_, g_, rhs_, stream_);
-        if (scaled_) launch_vec_mul(n_pad_, rhs_, scale_, rhs_, stream_);
-        timer_.begin(kPgFactor, stream_);
-        HIP_TRY(tp_.factor(&failed));
-        timer_.end(kPgFactor, stream_);
-        if (tp_.factor_flow_gave_up()) return fail(kDeviceError, "dataflow factorisation timed out twice");
-        return kOk;
-    };
-    timer_.end(kPgFactor, stream_);
-    if (!speculative) {
-        if (tp_.factor_flow_gave_up()) { rc = after_time_out(); if (rc != kOk) return rc; }
-        if (failed) return fail(kSingularMatrix, "Cholesky factorization failed (matrix may be singular)");
+    begin_solve(lambda);
+    int rc = rebuild_system(lambda, 0.0);
+    if (rc == kOk && !one_wait_) {   // the flags are waited for right behind the factorisation
+        int failed = 0;
+        rc = factor_fresh(lambda, 0.0, &failed);
+        if (rc == kOk) rc = recover_factor(lambda, failed, false);   // (a failed pivot)
     }
-    for (int attempt = 0;; ++attempt) {
-        timer_.begin(kPgTriSolve, stream_);
-        HIP_TRY(tp_.solve(rhs_, d_, work_));
-        if (scaled_) launch_vec_mul(n_pad_, d_, scale_, d_, stream_);  // apply_inverse_scaling: step = D y
-        timer_.end(kPgTriSolve, stream_);
-        have_step_ = true;
-        if (eager_eval_) {   // what the LM loop asks next rides on this solve's wait (step_stats, eval_step)
-            if (!eager_host_) HIP_TRY(eager_host_.alloc(8));
-            enqueue_step_stats();
-            enqueue_trial_point(scal_ + 4);
-            HIP_TRY(hipMemcpyAsync(eager_host_, scal_ + 1, 4 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        }
-        if (step_out || grad_out) {
-            std::vector<double> h(n_);
-            for (int pass = 0; pass < 2; ++pass) {
-                double* out = pass == 0 ? step_out : grad_out;
-                if (!out) continue;
-                HIP_TRY(hipMemcpyAsync(h.data(), pass == 0 ? d_ : g_, n_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
-                HIP_TRY(hipStreamSynchronize(stream_));
-                if (scaled_)  // the caller's variables are the scaled ones: y = step / s, gradient = s g
-                    for (int64_t i = 0; i < n_; ++i) h[i] = pass == 0 ? h[i] / scale_h_[i] : h[i] * scale_h_[i];
-                for (int64_t v = 0; v < n_v_; ++v)
-                    for (int a = 0; a < dof_; ++a) out[pose_col_[v] + a] = h[dof_ * (size_t)vmap_[v] + a];
-            }
-        } else {
+    return rc != kOk ? rc : direct_solve(one_wait_, lambda, step_out, grad_out);
+}
+
+int PoseGraphSolver::enqueue_sweeps() {
+    timer_.begin(kPgTriSolve, stream_);
+    HIP_TRY(tp_.solve(rhs_, d_, work_));
+    if (scaled_) launch_vec_mul(n_pad_, d_, scale_, d_, stream_);  // apply_inverse_scaling: step = D y
+    timer_.end(kPgTriSolve, stream_);
+    return kOk;
+}
+
+int PoseGraphSolver::finish_step(double* step_out, double* grad_out) {
+    have_step_ = true;
+    if (eager_eval_) {   // what the LM loop asks next rides on this solve's wait: eager_host_ [0..2] step statistics, [3] sum of squares at the trial point
+        if (!eager_host_) HIP_TRY(eager_host_.alloc(8));
+        enqueue_step_stats();
+        enqueue_trial_point(scal_ + 4);
+        HIP_TRY(hipMemcpyAsync(eager_host_, scal_ + 1, 4 * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    }
+    if (step_out || grad_out) {
+        std::vector<double> h(n_);
+        for (int pass = 0; pass < 2; ++pass) {
+            double* out = pass == 0 ? step_out : grad_out;
+            if (!out) continue;
+            HIP_TRY(hipMemcpyAsync(h.data(), pass == 0 ? d_ : g_, n_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
             HIP_TRY(hipStreamSynchronize(stream_));
+            if (scaled_)  // the caller's variables are the scaled ones: y = step / s, gradient = s g
+                for (int64_t i = 0; i < n_; ++i) h[i] = pass == 0 ? h[i] / scale_h_[i] : h[i] * scale_h_[i];
+            for (int64_t v = 0; v < n_v_; ++v)
+                for (int a = 0; a < dof_; ++a) out[pose_col_[v] + a] = h[dof_ * (size_t)vmap_[v] + a];
         }
-        if (speculative) {   // the flags the old path read behind the factorisation
-            speculative = false;
-            HIP_TRY(tp_.read_flags(&failed));
-            if (tp_.factor_flow_gave_up()) {
-                have_step_ = false;
-                (void)tp_.sweep_timed_out();   // (clears the word a sweep over a broken factor may have raised)
-                rc = after_time_out();
-                if (rc != kOk) return rc;
-                if (failed) return fail(kSingularMatrix, "Cholesky factorization failed (matrix may be singular)");
-                attempt = -1;
-                continue;   // the sweeps once more, over the good factor
-            }
-            if (failed) { have_step_ = false; (void)tp_.sweep_timed_out(); return fail(kSingularMatrix, "Cholesky factorization failed (matrix may be singular)"); }
-        }
-        if (!tp_.sweep_timed_out()) {
-            if (eager_eval_) eager_serial_ = step_serial_;   // (the answers of THIS solve)
-            tp_.set_factor_valid(true);   // (pivots read, sweeps done: covariance() may invert this factor)
-            return kOk;
-        }
-        // a dataflow sweep of this solve gave up (chol_kernels.hip, flow_wait): repeat it level by level (Solver::solve_augmented)
-        have_step_ = false;
-        if (attempt > 0 || !tp_.tri_flow()) return fail(kDeviceError, "triangular sweep timed out");
-        tp_.enable_tri_flow(false);
+    } else {
+        HIP_TRY(hipStreamSynchronize(stream_));
     }
+    if (eager_eval_) eager_serial_ = step_serial_;   // (the answers of THIS solve)
+    return kOk;
 }
 
 void PoseGraphSolver::enqueue_step_stats() {
@@ -369,7 +343,7 @@ void PoseGraphSolver::enqueue_trial_point(double* sumsq_out) {
 
 int PoseGraphSolver::step_stats(double out3[3]) {
     if (!have_step_) return fail(kInvalidState, "no step computed");
-    if (eager_serial_ == step_serial_ && eager_host_) {   // read at the solve's wait
+    if (answered_at_wait()) {
         out3[0] = sqrt(eager_host_[0]); out3[1] = sqrt(eager_host_[1]); out3[2] = 0.5 * eager_host_[2];
         return kOk;
     }
@@ -386,7 +360,7 @@ int PoseGraphSolver::step_stats(double out3[3]) {
 
 int PoseGraphSolver::eval_step(double* trial_cost) {
     if (!have_step_) return fail(kInvalidState, "no step computed");
-    if (eager_serial_ == step_serial_ && eager_host_) {   // the trial point is in place, its cost was read at the solve's wait
+    if (answered_at_wait()) {   // the trial point is in place
         have_trial_ = true;
         const double nrm = sqrt(eager_host_[3]);
         *trial_cost = 0.5 * nrm * nrm;

@@ -12,14 +12,11 @@
 #include <utility>
 #include <vector>
 
-#include "device_buffer.h"
 #include "ba_kernels.h"
 #include "chol_kernels.h"
-#include "lm_loop.h"
 #include "schur_pairs.h"
-#include "stage_timer.h"
 #include "comm.h"
-#include "tile_plan.h"
+#include "tile_backend.h"
 
 
 namespace apex {
@@ -30,7 +27,7 @@ enum Stage { kStAssembleCam = 0, kStAssembleLm, kStScatter, kStAllReduce, kStFac
 int mode_mask(int mode);  // 4 POSE + 2 LANDMARK + INTRINSIC of an APEXGPU_MODE_*
 void shard_range(int64_t n_pt, const int64_t* ptr, int rank, int world, int64_t* lo, int64_t* hi);
 
-class Solver : public LmBackend {
+class Solver : public TileBackend {
    public:
     Solver(int64_t n_cam, int64_t n_pt, int64_t n_obs, int mode, int device);
     ~Solver();
@@ -81,7 +78,6 @@ class Solver : public LmBackend {
     // d_c = 6: the intrinsics rows of get_schur's matrix are lambda on the diagonal, so theirs are 1 / lambda, no cross terms.
     // kInvalidState: no valid factor (no direct solve yet, a PCG / matrix-free solve or an export since), several ranks.
     int camera_covariance(double* out);
-    void enable_covariance_timing(bool on) { tp_.enable_covariance_timing(on); }
     // Marginal landmark covariances: the 3 x 3 landmark blocks of the inverse of the same matrix camera_covariance describes,
     //     Sigma_ll = V_l^-1 + sum_{i,j in obs(l)} U_i^T Z_{c(i) c(j)} U_j,   U_i = W_il V_l^-1   (Schur-complement identity)
     // with Z = S^-1 on the factor's tile pattern (reused when a camera_covariance call computed it for this factor, else the
@@ -102,19 +98,8 @@ class Solver : public LmBackend {
     int n_tile_rows() const { return nt_; }
     double last_reg() const { return last_reg_; }
     int last_pcg_iters() const { return last_pcg_iters_; }
-    int stage_times(double* ms, int64_t* launches);  // averaged HIP-event time per stage since reset
-    void reset_stage_times();
-    void enable_stage_timing(bool on) { timer_.enable(on); }
-    void enable_stage_timing_only(uint32_t stage_mask) { timer_.enable_only(stage_mask); }
-    void enable_graphs(bool on) { use_graphs_ = on; tp_.enable_graphs(on); }
-    void enable_overlap(bool on) { tp_.enable_overlap(on); }
-    void enable_tri_flow(bool on) { tp_.enable_tri_flow(on); }
-    int sweep_timeouts() const { return tp_.sweep_timeouts(); }   // dataflow sweeps that gave up and were repeated level by level
-    void debug_poison_next_solve(int which) { tp_.debug_poison_next_solve(which); }
+    void enable_graphs(bool on) { use_graphs_ = on; TileBackend::enable_graphs(on); }   // (set_structure hands use_graphs_ to the plan again)
     int debug_occupy_cus(int n_cus, int micros) { return check_hip(tp_.debug_occupy_cus(n_cus, micros), "debug_occupy_cus"); }
-    void set_split_u1(int min_tasks) { tp_.set_split_u1(min_tasks); }
-    void set_overlap_min(int n) { tp_.set_overlap_min(n); }
-    void set_gate_min(int n) { tp_.set_gate_min(n); }
     // before set_structure: the handle will only run the matrix-free variant (2, IterativeSchurSolver).  S is never formed, so
     // neither is its tile structure beyond the diagonal blocks the Schur-Jacobi preconditioner needs, nor the pair list: the
     // set-up and the LM iteration no longer depend on the fill of S (a photo collection whose S is dense: tools/structure_sweep.py)
@@ -125,8 +110,6 @@ class Solver : public LmBackend {
     // variants 0 / 1 are answered by the matrix-free PCG (IterativeSchurSolver semantics, implicit_schur.rs:835-946): variant 0
     // at that solver's own defaults (500 iterations, 1e-9: implicit_schur.rs:94-95), variant 1 at the caller's cg parameters.
     // "auto_variant" 0 restores the refusal.  variant_used() / variant_reason() say what happened (apexgpu_variant_info).
-    void set_eager_step_eval(bool on) { eager_eval_ = on; }
-    void set_one_wait(bool on) { one_wait_ = on; }
     void set_device_pair_recs(bool on) { device_pair_recs_ = on; }   // before set_structure ("device_pair_list")
     int get_pair_records(uint32_t* recs4_out, int64_t cap_slots);     // tests: the pair records as they sit on the device
     void set_auto_variant(bool on) { auto_variant_ = on; }
@@ -139,13 +122,8 @@ class Solver : public LmBackend {
     int variant_used(int asked) const { return (auto_fallback_ && asked != 2) ? 2 : asked; }
     bool auto_fallback() const { return auto_fallback_; }
     const std::string& variant_reason() const { return fallback_reason_; }
-    void set_two_side(int mode) { tp_.set_two_side(mode); }
-    void set_factor_flow(int max_cols, int max_rows) { tp_.set_factor_flow(max_cols, max_rows); }
-    int factor_flow_timeouts() const { return n_factor_flow_timeouts_; }
-    void debug_poison_next_factor() { tp_.debug_poison_next_factor(); }
     void set_schur_form(int v) { rows_form_ = v == 4 ? 4 : 3; }   // 4 queued layout (default; nine-column cameras), 3 one running block per wave
     bool has_structure() const { return have_structure_; }
-    void set_nd(bool on, int leaf) { use_nd_ = on; if (leaf > 0) nd_leaf_ = leaf; }
     void set_hubs_last(bool on) { hubs_last_ = on; }
     int n_hubs() const { return n_hubs_; }
     void set_dist_factor(bool on) { dist_factor_ = on; }   // before set_structure
@@ -153,8 +131,6 @@ class Solver : public LmBackend {
     void set_dist_selftest(int world) { dist_selftest_ = world; }  // before set_structure; single rank only
     int owned_landmarks(uint8_t* mask) const;
     bool tree_sharded() const { return tree_shard_; }
-    int n_levels() const { return tp_.n_levels(); }
-    const TilePlan& plan() const { return tp_; }
     double schur_scatter_pairs() const { return (double)n_pairs_; }
     double pair_blocks() const { return (double)n_pair_blocks_; }
     double pair_slots() const { return (double)n_pair_slots_; }
@@ -169,13 +145,19 @@ class Solver : public LmBackend {
     int comm_init_shm(int world, int rank, const char* name);              // host shared memory (bring-up / tests, comm.h)
     int set_shard(int rank, int world);  // without RCCL: assemble only this rank's landmark range
 
-    const char* last_error() const override { return err_.c_str(); }
     int dc() const { return dc_; }
     int64_t cam_dof_internal() const { return n_c_; }
 
    private:
-    int fail(int code, const std::string& msg);
-    int check_hip(hipError_t e, const char* what, std::string* err = nullptr);   // err: where the text goes instead of err_
+    // the direct solve's hooks (tile_backend.h)
+    int rebuild_system(double lambda, double reg) override { return assemble(lambda, reg, true); }
+    int factor_now(int* failed_at, bool defer_flags) override;
+    int enqueue_sweeps() override;
+    int finish_step(double* step_out, double* grad_out) override;
+    int recover_factor(double lambda, int failed, bool gave_up) override;
+    const int* own_flag() const override { return flags_; }
+    int own_flag_raised() override { return fail(kSingularMatrix, "Landmark block is singular"); }
+    void keep_factor() override;
     BAView view(int which) const;
     TileMap tilemap() const;
     // for_factor: the result feeds tp_.factor() (a distributed plan then leaves the top tiles to the factorisation's
@@ -188,11 +170,8 @@ class Solver : public LmBackend {
     int implicit_matvec(const double* x, double lam_local, double* y, bool reduce);
     int ensure_scale_buffers();
     int column_norms_sq_device();   // -> n2 in cam_scale_ / pt_scale_ (camera part all-reduced over the shards)
-    int factor_and_solve(double lambda);
-    int cholesky_attempt(int* failed_at);
-    int cholesky_on_fresh_s(double lambda, double reg, int* failed_at);
-    int n_factor_flow_timeouts_ = 0;
-    int tri_solve();
+    int factor_with_ladder(double lambda);
+    int ladder(double lambda);
     int pcg_solve();
     int cost_of(int which, double* out);
     void stage_begin(int st);
@@ -215,13 +194,12 @@ class Solver : public LmBackend {
 
     // sizes
     int64_t n_cam_, n_pt_, n_obs_;
-    int mode_, dc_, device_;
+    int mode_, dc_;
     int64_t n_c_ = 0, n_c_pad_ = 0;
     int nt_ = 0;
     double huber_delta_ = 1.0;
-    bool have_structure_ = false, have_params_ = false, have_step_ = false, have_trial_ = false;
-    int cur_ = 0;  // index of the current parameter set (0/1); the other one is the trial set
-    double last_lambda_ = 0.0, last_reg_ = 0.0;
+    bool have_structure_ = false, have_params_ = false;
+    double last_reg_ = 0.0;
     int last_pcg_iters_ = 0;
     int cg_max_iter_ = 200;   // SparseSchurComplementSolver::new (explicit_schur.rs:211-212)
     double cg_tol_ = 1e-6;
@@ -239,11 +217,7 @@ class Solver : public LmBackend {
     std::vector<int> o_orig_h_;
     std::thread free_thread_;   // unmaps the set-up's host lists off the caller's path
 
-    // device
-    hipStream_t stream_ = nullptr;
-    // destroys stream_ when the members below it are gone: ~Solver joins free_thread_ and synchronises the stream, then the
-    // buffers (and the plan) are freed in reverse order of declaration, then this runs
-    struct StreamLast { hipStream_t& s; ~StreamLast() { if (s) (void)hipStreamDestroy(s); } } stream_last_{stream_};
+    // device (stream_ and tp_ are TileBackend's: ~Solver joins free_thread_ and synchronises the stream, the buffers below are freed, then the plan, the stream last)
     // host -> device copies of caller (pageable) memory through two pinned chunks: the DMA of one overlaps the memcpy into the other
     int upload_staged(void* dst_dev, const void* src_host, size_t bytes);
     PinnedBuffer<char> pin_[2];
@@ -260,15 +234,7 @@ class Solver : public LmBackend {
     DeviceBuffer<uint32_t> wg_cam_list_;
     bool matrix_free_only_opt_ = false;   // the caller's option ("matrix_free_only")
     bool matrix_free_only_ = false;       // the effective state of the structure that is built: the option, or the automatic selection
-    bool one_wait_ = true;   // "one_wait": one host wait per Cholesky solve (solve_augmented); 0 = three, as in rounds 1-4
-    // "eager_step_eval" (round 5): what the LM loop asks next of every solve -- the step statistics (apexgpu_step_stats) and the
-    // trial point with its cost (apexgpu_eval_step) -- is enqueued behind the back-substitution and read at the solve's own wait:
-    // the two calls then answer from the host, without a launch or a wait of their own (three device round trips per LM
-    // iteration become one).  The answers are those of this very solve (step_serial_); single rank.
-    bool eager_eval_ = true;
     bool trial_pts_written_ = false;   // the back-substitution of this solve has written the trial points (enqueue_trial_point skips them)
-    int64_t step_serial_ = 0, eager_serial_ = -1;
-    PinnedBuffer<double> eager_host_;            // [0..5] step statistics, [6] sum of squares at the trial point
     PinnedBuffer<double> pcg_host_;              // two slots of the matrix-free PCG's scalars (read one iteration behind)
     hipEvent_t pcg_ev_[2] = {nullptr, nullptr};
     bool device_pair_recs_ = true;   // queued layout: the pair records are written by the device (k_build_pair_recs_q), not built on the host and copied
@@ -306,15 +272,12 @@ class Solver : public LmBackend {
     DeviceBuffer<int> co_rank_;
     DeviceBuffer<int> o_orig_, pt_ptr_, cam_ptr_, cam_obs_;
     DeviceBuffer<uint8_t> fix_pose_, fix_intr_, fix_pt_;
-    TilePlan tp_;  // tiles of S, their factorisation and solves
     DeviceBuffer<double> g_c_, g_red_, dcam_, hinv_, g_l_, dl_;
     DeviceBuffer<double> partial_, scal_;  // reduction scratch, scalar outputs
     DeviceBuffer<int> flags_;              // [0] landmark inversion error
     std::vector<int> cmap_, cinv_;   // external camera -> internal camera and back
-    bool use_nd_ = true;
     bool hubs_last_ = true;     // order cameras covisible with > max(16, 10 sqrt(n_cam)) others last (ba_structure.h)
     int n_hubs_ = 0, n_border_tiles_ = 1;
-    int nd_leaf_ = 16;
     bool dist_factor_ = true;   // world > 1: factorise the elimination tree's subtrees on their owner ranks (tile_plan.h)
     bool tree_sharding_ = true; // ... and give every landmark to the rank whose columns it touches (set_structure)
     bool tree_shard_ = false;   // what set_structure arrived at
@@ -330,10 +293,6 @@ class Solver : public LmBackend {
 
     bool use_graphs_ = true;
     double setup_s_[6] = {0, 0, 0, 0, 0, 0};  // set_structure by phase: order + tile structure, landmark / camera lists, tile plan, Schur lists, uploads, total
-
-    StageTimer<kNumStages> timer_;
-
-    std::string err_;
 };
 
 }  // namespace apex

@@ -18,13 +18,6 @@ void warm_ba_kernels(hipStream_t s);
 void warm_schur_pairs(hipStream_t s);
 void warm_chol_kernels(hipStream_t s);
 
-// HIP_TRY(expr): the text of a failure goes to err_; HIP_TRY(expr, err): to *err (a step on a thread that does not own err_)
-#define HIP_TRY(expr, ...)                                    \
-    do {                                                      \
-        int _rc = check_hip((expr), #expr, ##__VA_ARGS__);    \
-        if (_rc != kOk) return _rc;                           \
-    } while (0)
-
 // every collective's result is surfaced as APEXGPU_ERR_DEVICE with the transport's own text (comm.h)
 #define COMM_TRY(expr)                                                                  \
     do {                                                                                \
@@ -39,7 +32,7 @@ int mode_mask(int mode) {
 }
 
 Solver::Solver(int64_t n_cam, int64_t n_pt, int64_t n_obs, int mode, int device)
-    : n_cam_(n_cam), n_pt_(n_pt), n_obs_(n_obs), mode_(mode), dc_(mode_mask(mode) & 1 ? 9 : 6), device_(device) {
+    : TileBackend(device, kNumStages, /*nd_leaf=*/16), n_cam_(n_cam), n_pt_(n_pt), n_obs_(n_obs), mode_(mode), dc_(mode_mask(mode) & 1 ? 9 : 6) {
     lm_lo_ = 0; lm_hi_ = n_pt;
     HostBlockCache::get().retain();   // (the set-up's host blocks are cached only while a handle is alive: host_parallel.h)
 }
@@ -79,17 +72,6 @@ int Solver::upload_staged(void* dst_dev, const void* src_host, size_t bytes) {
     return kOk;
 }
 
-int Solver::fail(int code, const std::string& msg) {
-    err_ = msg;
-    return code;
-}
-
-int Solver::check_hip(hipError_t e, const char* what, std::string* err) {
-    if (e == hipSuccess) return kOk;
-    *(err ? err : &err_) = std::string("HIP error in ") + what + ": " + hipGetErrorString(e);
-    return kDeviceError;
-}
-
 BAView Solver::view(int which) const {
     BAView v;
     v.n_cam = n_cam_; v.n_pt = n_pt_; v.n_obs = (int64_t)o_orig_h_.size();
@@ -113,8 +95,6 @@ TileMap Solver::tilemap() const { return tp_.tilemap(); }
 
 void Solver::stage_begin(int st) { timer_.begin(st, stream_); }
 void Solver::stage_end(int st) { timer_.end(st, stream_); }
-void Solver::reset_stage_times() { timer_.reset(); }
-int Solver::stage_times(double* ms, int64_t* launches) { return timer_.times(ms, launches); }
 
 int Solver::set_shard(int rank, int world) {
     if (have_structure_) return fail(kInvalidState, "set_shard must precede set_structure");
@@ -728,30 +708,16 @@ int Solver::assemble_finish() {
     return kOk;
 }
 
-int Solver::cholesky_attempt(int* failed_at) {
+int Solver::factor_now(int* failed_at, bool defer_flags) {
     stage_begin(kStFactor);
-    const hipError_t fe = tp_.factor(failed_at);
+    const hipError_t fe = tp_.factor(failed_at, defer_flags);
     if (fe != hipSuccess && !comm_err_.empty()) return fail(kDeviceError, comm_err_);
     HIP_TRY(fe);
     stage_end(kStFactor);
     return kOk;
 }
 
-// cholesky_attempt on the S that assemble(lambda, reg, true) has just built.  Should the dataflow launch of the top groups
-// time out (TilePlan::factor_flow_gave_up: the tiles are half updated and the plan has gone back to the level launches, in a
-// distributed plan on every rank alike), S is built again and factorised once more.
-int Solver::cholesky_on_fresh_s(double lambda, double reg, int* failed_at) {
-    int rc = cholesky_attempt(failed_at);
-    if (rc != kOk || !tp_.factor_flow_gave_up()) return rc;
-    ++n_factor_flow_timeouts_;
-    rc = assemble(lambda, reg, true);
-    if (rc != kOk) return rc;
-    rc = cholesky_attempt(failed_at);
-    if (rc == kOk && tp_.factor_flow_gave_up()) return fail(kDeviceError, "dataflow factorisation timed out twice");
-    return rc;
-}
-
-int Solver::tri_solve() {
+int Solver::enqueue_sweeps() {
     stage_begin(kStTriSolve);
     const hipError_t se = tp_.solve(g_red_, dcam_, pcg_buf_);
     if (se != hipSuccess && !comm_err_.empty()) return fail(kDeviceError, comm_err_);
@@ -760,15 +726,29 @@ int Solver::tri_solve() {
     return kOk;
 }
 
-// solve_with_cholesky (explicit_schur.rs:539-634) incl. the regularisation ladder
-int Solver::factor_and_solve(double lambda) {
+// solve_with_cholesky (explicit_schur.rs:539-634) incl. the regularisation ladder, up to the factor (direct_solve runs the sweeps)
+int Solver::factor_with_ladder(double lambda) {
     int failed = 0;
     last_reg_ = 0.0;
-    int rc = cholesky_on_fresh_s(lambda, 0.0, &failed);
-    if (rc != kOk) return rc;
-    if (!failed) return tri_solve();
+    const int rc = factor_fresh(lambda, 0.0, &failed);
+    return (rc != kOk || !failed) ? rc : ladder(lambda);
+}
+
+// A speculative factorisation went wrong: what was enqueued behind it is void.  A failed pivot takes the waited-for path from
+// the top (S again, the factorisation, the ladder); after a give-up the repaired factorisation stands in for that path's first.
+int Solver::recover_factor(double lambda, int failed, bool gave_up) {
+    if (!gave_up) {
+        const int rc = assemble(lambda, 0.0, true);
+        return rc != kOk ? rc : factor_with_ladder(lambda);
+    }
+    const int rc = factor_again(lambda, 0.0, &failed);
+    return (rc != kOk || !failed) ? rc : ladder(lambda);
+}
+
+int Solver::ladder(double lambda) {
     // the factorisation overwrote S: re-assemble it to read trace and max |diag| (:563-579)
-    rc = assemble(lambda, 0.0);
+    int failed = 0;
+    int rc = assemble(lambda, 0.0);
     if (rc != kOk) return rc;
     double* diag = pcg_buf_;
     tp_.diag(diag);
@@ -786,9 +766,9 @@ int Solver::factor_and_solve(double lambda) {
         const double reg = base * pow(10.0, (double)(attempt - 4));
         rc = assemble(lambda, reg, true);
         if (rc != kOk) return rc;
-        rc = cholesky_on_fresh_s(lambda, reg, &failed);
+        rc = factor_fresh(lambda, reg, &failed);
         if (rc != kOk) return rc;
-        if (!failed) { last_reg_ = reg; return tri_solve(); }
+        if (!failed) { last_reg_ = reg; return kOk; }
     }
     return fail(kSingularMatrix, "Schur complement singular after 5 regularization attempts (max reg = " + std::to_string(base) + ")");
 }
@@ -913,11 +893,8 @@ int Solver::implicit_pcg_solve(double lambda, int max_iter, double tol) {
 int Solver::solve_augmented(double lambda, int variant, double* step_out, double* grad_out) {
     if (!have_params_) return fail(kInvalidState, "Block structure not built or parameters not set");
     HIP_TRY(hipSetDevice(device_));
-    have_step_ = false;
-    have_trial_ = false;   // (the eager step evaluation of this solve overwrites the trial parameter set: an earlier eval_step is void)
+    begin_solve(lambda);
     last_pcg_iters_ = 0;   // (the PCG variants set it: apexgpu_info[5] is about THIS solve)
-    ++step_serial_;
-    last_lambda_ = lambda;
     tp_.set_factor_valid(false);   // (every variant writes the tiles or leaves them stale for this point)
     int pcg_max = cg_max_iter_;
     double pcg_tol = cg_tol_;
@@ -927,91 +904,55 @@ int Solver::solve_augmented(double lambda, int variant, double* step_out, double
     }
     int rc = (variant == 2) ? assemble_implicit(lambda) : assemble(lambda, 0.0, variant == 0);
     if (rc != kOk) return rc;
-    // ONE host wait per Cholesky solve (round 5).  Until round 4 the host waited three times inside this call -- for the
-    // landmark-inversion flag behind the assembly, for the pivot flag behind the factorisation, for the step at the end -- and
-    // the GPU idled through a synchronisation plus a graph launch each time.  On a single rank the factorisation, the sweeps and
-    // the back-substitution are now enqueued back to back and the two flags are read at the final wait; a singular landmark
-    // block, a failed pivot or a dataflow time-out then takes the old path from the top (re-assembly, ladder), results unchanged.
-    const bool one_wait = one_wait_ && variant == 0 && !(comm_ && world_ > 1) && !tp_.distributed();
-    bool speculative = false;
-    if (one_wait) {
-        int failed = 0;
+    // ONE host wait per Cholesky solve (TileBackend::direct_solve) on a single rank.  Otherwise the host waits three times inside
+    // this call -- for the landmark-inversion flag behind the assembly, for the pivot flag behind the factorisation, for the step
+    // at the end -- and the GPU idles through a synchronisation plus a graph launch each time.
+    const bool speculative = one_wait_ && variant == 0 && !(comm_ && world_ > 1) && !tp_.distributed();
+    if (speculative) {
         last_reg_ = 0.0;
-        stage_begin(kStFactor);
-        const hipError_t fe = tp_.factor(&failed, /*defer_flags=*/true);
-        HIP_TRY(fe);
-        stage_end(kStFactor);
-        rc = tri_solve();
-        if (rc != kOk) return rc;
-        speculative = true;
     } else {
-    int lm_err = 0;
-    HIP_TRY(hipMemcpyAsync(&lm_err, flags_, sizeof(int), hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    if (lm_err) return fail(kSingularMatrix, "Landmark block is singular");
-    rc = (variant == 2) ? implicit_pcg_solve(lambda, pcg_max, pcg_tol) : (variant == 1) ? pcg_solve() : factor_and_solve(lambda);
-    if (rc != kOk) return rc;
-    }
-    for (int attempt = 0;; ++attempt) {
-        stage_begin(kStBackSub);
-        if (scaled_) launch_vec_mul(n_c_, dcam_, cam_scale_, dcam_, stream_);  // apply_inverse_scaling: dc = D_c y
-        // what the LM loop asks next (step statistics, trial cost) rides on this solve's wait (solver.h, eager_eval_); the trial
-        // POINTS are written by the back-substitution itself
-        const bool eager = eager_eval_ && !(comm_ && world_ > 1);
-        trial_pts_written_ = eager && fix_pt_ != nullptr;
-        launch_back_substitute(dc_, view(cur_), hinv_, g_l_, dcam_, dl_, stream_, backsub_records(), trial_pts_written_ ? fix_pt_ : nullptr,
-                               trial_pts_written_ ? pts_[cur_ ^ 1] : nullptr);
-        stage_end(kStBackSub);
-        HIP_TRY(hipGetLastError());
-        have_step_ = true;
-        if (eager) {
-            if (!eager_host_) HIP_TRY(eager_host_.alloc(8));
-            rc = enqueue_step_stats();
-            if (rc == kOk) rc = enqueue_trial_point(scal_ + 6);
-            if (rc != kOk) return rc;
-            HIP_TRY(hipMemcpyAsync(eager_host_, scal_, 7 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        }
-        rc = export_step(step_out, grad_out);   // (synchronises: the sweeps' error word is on the host now)
-        if (rc == kOk && speculative) {   // the flags the old path read before going on
-            speculative = false;
-            int lm_err = 0, failed = 0;
-            HIP_TRY(hipMemcpyAsync(&lm_err, flags_, sizeof(int), hipMemcpyDeviceToHost, stream_));
-            HIP_TRY(tp_.read_flags(&failed));   // (synchronises; raises factor_flow_gave_up() on a dataflow time-out)
-            if (lm_err) { have_step_ = false; return fail(kSingularMatrix, "Landmark block is singular"); }
-            const bool gave_up = tp_.factor_flow_gave_up();
-            if (failed || gave_up) {
-                // what was enqueued behind the failed factorisation is void: S again, then the old path (ladder included)
-                have_step_ = false;
-                (void)tp_.sweep_timed_out();   // (clears the word a sweep over a broken factor may have raised)
-                if (gave_up) ++n_factor_flow_timeouts_;
-                rc = assemble(lambda, 0.0, true);
-                if (rc != kOk) return rc;
-                rc = factor_and_solve(lambda);
-                if (rc != kOk) return rc;
-                attempt = -1;   // (the loop's counter is for the sweep time-outs of the solve that follows)
-                continue;       // back-substitution and export once more
-            }
-        }
-        if (rc != kOk || variant != 0 || !tp_.sweep_timed_out()) {
-            if (rc == kOk && eager) eager_serial_ = step_serial_;   // (the answers of THIS solve: step_stats / eval_step)
-            // (pivots read, sweeps done: camera_covariance() may invert this factor -- single rank, direct variant only)
-            if (rc == kOk && variant == 0 && world_ == 1 && !tp_.distributed()) {
-                tp_.set_factor_valid(true);
-                factor_lin_ = cur_;   // (commit_step flips cur_: the factorised cameras are then in the other set)
-                factor_scaled_ = scaled_;
-            }
-            return rc;
-        }
-        // A dataflow sweep of THIS solve ran into its spin limit (chol_kernels.hip, flow_wait): dcam_ is wrong.  The factor is
-        // intact, so the solve is repeated with the level-by-level sweeps -- for this call and for the rest of the plan's
-        // life (a device that starved a sweep once will do it again, and every time-out costs ~2 s).  In a distributed plan
-        // the word was max-reduced: every rank is here.
-        have_step_ = false;
-        if (attempt > 0 || !tp_.tri_flow()) return fail(kDeviceError, "triangular sweep timed out");
-        tp_.enable_tri_flow(false);
-        rc = tri_solve();
+        int lm_err = 0;
+        HIP_TRY(hipMemcpyAsync(&lm_err, flags_, sizeof(int), hipMemcpyDeviceToHost, stream_));
+        HIP_TRY(hipStreamSynchronize(stream_));
+        if (lm_err) return own_flag_raised();
+        rc = (variant == 2) ? implicit_pcg_solve(lambda, pcg_max, pcg_tol) : (variant == 1) ? pcg_solve() : factor_with_ladder(lambda);
         if (rc != kOk) return rc;
     }
+    // (the PCG variants have the camera step in dcam_: no sweeps, no sweep time-out to look for, no factor to keep)
+    return variant == 0 ? direct_solve(speculative, lambda, step_out, grad_out) : finish_step(step_out, grad_out);
+}
+
+// the camera step is in dcam_: scaling back, back-substitution, the eager evaluation, the export and its wait
+int Solver::finish_step(double* step_out, double* grad_out) {
+    stage_begin(kStBackSub);
+    if (scaled_) launch_vec_mul(n_c_, dcam_, cam_scale_, dcam_, stream_);  // apply_inverse_scaling: dc = D_c y
+    // what the LM loop asks next (step statistics, trial cost) rides on this solve's wait (tile_backend.h, eager_eval_; single
+    // rank); the trial POINTS are written by the back-substitution itself
+    const bool eager = eager_eval_ && !(comm_ && world_ > 1);
+    trial_pts_written_ = eager && fix_pt_ != nullptr;
+    launch_back_substitute(dc_, view(cur_), hinv_, g_l_, dcam_, dl_, stream_, backsub_records(), trial_pts_written_ ? fix_pt_ : nullptr,
+                           trial_pts_written_ ? pts_[cur_ ^ 1] : nullptr);
+    stage_end(kStBackSub);
+    HIP_TRY(hipGetLastError());
+    have_step_ = true;
+    if (eager) {   // eager_host_: [0..5] step statistics, [6] sum of squares at the trial point
+        if (!eager_host_) HIP_TRY(eager_host_.alloc(8));
+        int rc = enqueue_step_stats();
+        if (rc == kOk) rc = enqueue_trial_point(scal_ + 6);
+        if (rc != kOk) return rc;
+        HIP_TRY(hipMemcpyAsync(eager_host_, scal_, 7 * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    }
+    const int rc = export_step(step_out, grad_out);   // (synchronises)
+    if (rc == kOk && eager) eager_serial_ = step_serial_;   // (the answers of THIS solve: step_stats / eval_step)
+    return rc;
+}
+
+// camera_covariance() may invert this factor -- single rank only
+void Solver::keep_factor() {
+    if (world_ != 1 || tp_.distributed()) return;
+    tp_.set_factor_valid(true);
+    factor_lin_ = cur_;   // (commit_step flips cur_: the factorised cameras are then in the other set)
+    factor_scaled_ = scaled_;
 }
 
 // the last step / gradient in the reference's global column order (syncs)
@@ -1150,7 +1091,7 @@ static void stats_from_sums(const double h[6], double out3[3]) {
 }
 int Solver::step_stats(double out3[3]) {
     if (!have_step_) return fail(kInvalidState, "no step computed");
-    if (eager_serial_ == step_serial_ && eager_host_) { stats_from_sums(eager_host_, out3); return kOk; }   // read at the solve's wait
+    if (answered_at_wait()) { stats_from_sums(eager_host_, out3); return kOk; }
     HIP_TRY(hipSetDevice(device_));
     const int rc = enqueue_step_stats();
     if (rc != kOk) return rc;
@@ -1178,7 +1119,7 @@ int Solver::enqueue_trial_point(double* sumsq_out) {
 }
 int Solver::eval_step(double* trial_cost) {
     if (!have_step_) return fail(kInvalidState, "no step computed");
-    if (eager_serial_ == step_serial_ && eager_host_) {   // the trial point is in place and its cost was read at the solve's wait
+    if (answered_at_wait()) {   // the trial point is in place
         have_trial_ = true;
         const double nrm = sqrt(eager_host_[6]);
         *trial_cost = 0.5 * nrm * nrm;

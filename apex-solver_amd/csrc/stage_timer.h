@@ -11,9 +11,9 @@
 
 namespace apex {
 
-template <int N>
 class StageTimer {
    public:
+    explicit StageTimer(int n_stages) : n_stages_(n_stages) {}
     ~StageTimer() {
         resolve();
         for (hipEvent_t e : pool_) (void)hipEventDestroy(e);
@@ -35,12 +35,12 @@ class StageTimer {
     }
     void reset() {
         resolve();
-        for (int i = 0; i < N; ++i) { ms_[i] = 0; n_[i] = 0; }
+        for (int i = 0; i < n_stages_; ++i) { ms_[i] = 0; n_[i] = 0; }
     }
     int times(double* ms, int64_t* launches) {
         resolve();
-        for (int i = 0; i < N; ++i) { ms[i] = ms_[i]; launches[i] = n_[i]; }
-        return N;
+        for (int i = 0; i < n_stages_; ++i) { ms[i] = ms_[i]; launches[i] = n_[i]; }
+        return n_stages_;
     }
 
    private:
@@ -59,13 +59,15 @@ class StageTimer {
         }
         pending_.clear();
     }
+    static constexpr int kMaxStages = 16;
+    const int n_stages_;
     bool on_ = false;
     uint32_t mask_ = ~0u;
     std::vector<hipEvent_t> pool_;
-    std::pair<hipEvent_t, hipEvent_t> open_[N] = {};
+    std::pair<hipEvent_t, hipEvent_t> open_[kMaxStages] = {};
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending_;
-    double ms_[N] = {0};
-    int64_t n_[N] = {0};
+    double ms_[kMaxStages] = {0};
+    int64_t n_[kMaxStages] = {0};
 };
 
 }  // namespace apex

@@ -1,0 +1,95 @@
+// tile_backend.h -- what the two backends that factorise on a TilePlan share (solver.h: S of bundle adjustment, pg_solver.h: H of a
+// pose graph): the plan, the stream and their order of destruction, the state of one solve, the switches that go to the plan, and
+// the protocol around one direct solve -- speculative factorisation, one host wait, the repairs of a dataflow launch that gave up.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "device_buffer.h"
+#include "lm_loop.h"
+#include "stage_timer.h"
+#include "tile_plan.h"
+
+namespace apex {
+
+// HIP_TRY(expr): the text of a failure goes to err_; HIP_TRY(expr, err): to *err (a step on a thread that does not own err_)
+#define HIP_TRY(expr, ...)                                    \
+    do {                                                      \
+        int _rc = check_hip((expr), #expr, ##__VA_ARGS__);    \
+        if (_rc != kOk) return _rc;                           \
+    } while (0)
+
+class TileBackend : public LmBackend {
+   public:
+    void enable_graphs(bool on) { tp_.enable_graphs(on); }
+    void enable_overlap(bool on) { tp_.enable_overlap(on); }
+    void enable_tri_flow(bool on) { tp_.enable_tri_flow(on); }
+    int sweep_timeouts() const { return tp_.sweep_timeouts(); }   // dataflow sweeps that gave up and were repeated level by level
+    void debug_poison_next_solve(int which) { tp_.debug_poison_next_solve(which); }
+    void debug_poison_next_factor() { tp_.debug_poison_next_factor(); }
+    void set_split_u1(int min_tasks) { tp_.set_split_u1(min_tasks); }
+    void set_overlap_min(int n) { tp_.set_overlap_min(n); }
+    void set_gate_min(int n) { tp_.set_gate_min(n); }
+    void set_two_side(int mode) { tp_.set_two_side(mode); }
+    void set_factor_flow(int max_cols, int max_rows) { tp_.set_factor_flow(max_cols, max_rows); }
+    int factor_flow_timeouts() const { return n_factor_flow_timeouts_; }
+    // "one_wait": one host wait per direct solve (direct_solve), 0 = the flags are waited for where they are raised.
+    // "eager_step_eval": what the LM loop asks next of every solve -- the step statistics and the trial point with its cost --
+    // is enqueued behind the step and read at the solve's own wait: step_stats / eval_step then answer from the host, without a
+    // launch or a wait of their own (three device round trips per LM iteration become one).
+    void set_one_wait(bool on) { one_wait_ = on; }
+    void set_eager_step_eval(bool on) { eager_eval_ = on; }
+    void set_nd(bool on, int leaf) { use_nd_ = on; if (leaf > 0) nd_leaf_ = leaf; }
+    void enable_covariance_timing(bool on) { tp_.enable_covariance_timing(on); }
+    void enable_stage_timing(bool on) { timer_.enable(on); }
+    void enable_stage_timing_only(uint32_t stage_mask) { timer_.enable_only(stage_mask); }
+    void reset_stage_times() { timer_.reset(); }
+    int stage_times(double* ms, int64_t* launches) { return timer_.times(ms, launches); }   // averaged HIP-event time per stage since reset
+    int n_levels() const { return tp_.n_levels(); }
+    const TilePlan& plan() const { return tp_; }
+    const char* last_error() const override { return err_.c_str(); }
+
+   protected:
+    TileBackend(int device, int n_stages, int nd_leaf) : device_(device), nd_leaf_(nd_leaf), timer_(n_stages) {}
+    int fail(int code, const std::string& msg) { err_ = msg; return code; }
+    int check_hip(hipError_t e, const char* what, std::string* err = nullptr);   // err: where the text goes instead of err_
+    void begin_solve(double lambda) { have_step_ = have_trial_ = false; ++step_serial_; last_lambda_ = lambda; }   // (a solve's eager evaluation overwrites the trial set: an earlier eval_step is void)
+    bool answered_at_wait() const { return eager_serial_ == step_serial_ && eager_host_; }   // step_stats / eval_step: read at this solve's wait
+    // The sweeps and the step on the system rebuild_system() built, to the one host wait.  speculative: the factorisation is
+    // enqueued here with its flags deferred to that wait; else the caller has factorised and read them.
+    int direct_solve(bool speculative, double lambda, double* step_out, double* grad_out);
+    int factor_fresh(double lambda, double reg, int* failed);   // factor_now on the system rebuild_system(lambda, reg) has just built, flags waited for; a give-up is repaired
+    int factor_again(double lambda, double reg, int* failed);   // after a dataflow factorisation that gave up
+
+    // What the protocol asks of a solver ("The direct solve's hooks, by name").
+    virtual int rebuild_system(double lambda, double reg) = 0;            // the matrix (diagonal + reg) and right-hand side, ready to factorise
+    virtual int factor_now(int* failed, bool defer_flags) = 0;           // tp_.factor under the solver's stage timer
+    virtual int enqueue_sweeps() = 0;                                     // tp_.solve into the solver's step vector
+    virtual int finish_step(double* step_out, double* grad_out) = 0;     // the rest of the step, eager evaluation, export; ends in the host wait
+    virtual int recover_factor(double lambda, int failed, bool gave_up) = 0;   // a factorisation with a failed pivot or a give-up: a good factor, or the error
+    virtual const int* own_flag() const { return nullptr; }              // a device flag of the solver's own, read at the speculative solve's wait
+    virtual int own_flag_raised() { return kOk; }                         // ... and the failure it stands for
+    virtual void keep_factor() { tp_.set_factor_valid(true); }            // pivots read, sweeps clean: the covariance calls may invert this factor
+
+    int device_;
+    bool have_step_ = false, have_trial_ = false;
+    int cur_ = 0;  // index of the current parameter set (0/1); the other one is the trial set
+    double last_lambda_ = 0.0;
+    bool one_wait_ = true, eager_eval_ = true;
+    int64_t step_serial_ = 0, eager_serial_ = -1;   // eager_serial_ == step_serial_: eager_host_ holds the answers of THIS solve
+    int n_factor_flow_timeouts_ = 0;
+    bool use_nd_ = true;
+    int nd_leaf_;
+    std::string err_;
+    hipStream_t stream_ = nullptr;
+    // destroys stream_ when the members below it and every member of the solver are gone: the solver's destructor synchronises the
+    // stream, then its buffers are freed, then the plan and the rest here in reverse order of declaration, then this runs
+    struct StreamLast { hipStream_t& s; ~StreamLast() { if (s) (void)hipStreamDestroy(s); } } stream_last_{stream_};
+    TilePlan tp_;   // the tiles, their factorisation and solves
+    StageTimer timer_;
+    PinnedBuffer<double> eager_host_;   // the eager evaluation's sums, in the solver's own layout
+};
+
+}  // namespace apex

@@ -1,0 +1,64 @@
+// tile_backend.hip -- see tile_backend.h
+#include "tile_backend.h"
+
+namespace apex {
+
+int TileBackend::check_hip(hipError_t e, const char* what, std::string* err) {
+    if (e == hipSuccess) return kOk;
+    *(err ? err : &err_) = std::string("HIP error in ") + what + ": " + hipGetErrorString(e);
+    return kDeviceError;
+}
+
+// The dataflow launch of the top groups timed out (TilePlan::factor_flow_gave_up: the tiles are half updated and the plan has gone
+// back to the level launches, in a distributed plan on every rank alike): the system is built again and factorised once more.
+int TileBackend::factor_again(double lambda, double reg, int* failed) {
+    ++n_factor_flow_timeouts_;
+    int rc = rebuild_system(lambda, reg);
+    if (rc == kOk) rc = factor_now(failed, false);
+    if (rc == kOk && tp_.factor_flow_gave_up()) return fail(kDeviceError, "dataflow factorisation timed out twice");
+    return rc;
+}
+
+int TileBackend::factor_fresh(double lambda, double reg, int* failed) {
+    const int rc = factor_now(failed, false);
+    return (rc != kOk || !tp_.factor_flow_gave_up()) ? rc : factor_again(lambda, reg, failed);
+}
+
+// ONE host wait per direct solve.  The factorisation, the sweeps and what finish_step() adds are enqueued back to back, and the
+// pivot flag, the dataflow launch's time-out word and the solver's own flag are read at the final wait; what was enqueued behind
+// a bad factorisation is then void, recover_factor() takes the waited-for path from the assembly on, and the sweeps run once more.
+int TileBackend::direct_solve(bool speculative, double lambda, double* step_out, double* grad_out) {
+    int failed = 0;
+    int rc = speculative ? factor_now(&failed, /*defer_flags=*/true) : kOk;
+    for (int attempt = 0; rc == kOk; ++attempt) {
+        rc = enqueue_sweeps();
+        if (rc == kOk) rc = finish_step(step_out, grad_out);   // (synchronises: the sweeps' error word is on the host now)
+        if (rc != kOk) break;
+        if (speculative) {   // the flags the waited-for path read before going on
+            speculative = false;
+            int own = 0;
+            if (own_flag()) HIP_TRY(hipMemcpyAsync(&own, own_flag(), sizeof(int), hipMemcpyDeviceToHost, stream_));
+            HIP_TRY(tp_.read_flags(&failed));   // (synchronises; raises factor_flow_gave_up() on a dataflow time-out)
+            if (own) { have_step_ = false; return own_flag_raised(); }
+            const bool gave_up = tp_.factor_flow_gave_up();
+            if (failed || gave_up) {
+                have_step_ = false;
+                (void)tp_.sweep_timed_out();   // (clears the word a sweep over a broken factor may have raised)
+                rc = recover_factor(lambda, failed, gave_up);
+                attempt = -1;   // (the loop's counter is for the sweep time-outs of the solve that follows)
+                continue;       // the sweeps and the step once more, over the good factor
+            }
+        }
+        if (!tp_.sweep_timed_out()) { keep_factor(); return kOk; }
+        // A dataflow sweep of THIS solve ran into its spin limit (chol_kernels.hip, flow_wait): the step is wrong.  The factor is
+        // intact, so the solve is repeated with the level-by-level sweeps -- for this call and for the rest of the plan's
+        // life (a device that starved a sweep once will do it again, and every time-out costs ~2 s).  In a distributed plan
+        // the word was max-reduced: every rank is here.
+        have_step_ = false;
+        if (attempt > 0 || !tp_.tri_flow()) return fail(kDeviceError, "triangular sweep timed out");
+        tp_.enable_tri_flow(false);
+    }
+    return rc;
+}
+
+}  // namespace apex

@@ -146,3 +146,59 @@ def test_factor_flow_timeout_is_caught_in_the_same_solve_and_repaired():
     again = s.solve_augmented_equation(1e-3).copy()         # the handle stays on the level launches
     assert rel(again, want) < 1e-7 and s.counters()["factor_flow_timeouts"] == 1
     s.close()
+
+
+def test_factor_flow_timeout_is_repaired_without_the_one_wait_path():
+    """The same give-up with "one_wait" off: the flag word is read right behind the factorisation (not at the solve's final
+    wait), S is assembled again and factorised with the level launches before any sweep is enqueued."""
+    d = pkg.datasets.load_named("ladybug-1723", 0.25)[0]
+    prob = Problem.bundle_adjustment(d, OptimizationType.SelfCalibration, 1.0)
+    ref = GpuSchurComplementSolver(0).with_option("factor_flow", 0).with_option("one_wait", 0).initialize_structure(prob)
+    ref.set_parameters(d.poses, d.intr, d.points)
+    want = ref.solve_augmented_equation(1e-3).copy()
+    ref.close()
+    s = GpuSchurComplementSolver(0).with_option("factor_flow", 8).with_option("one_wait", 0).initialize_structure(prob)
+    s.set_parameters(d.poses, d.intr, d.points)
+    good = s.solve_augmented_equation(1e-3).copy()
+    c0 = s.counters()
+    assert c0["factor_flow_groups"] >= 2 and c0["factor_flow_timeouts"] == 0, c0
+    assert rel(good, want) < 1e-7
+    s.set_option("debug_poison_factor", 1)
+    got = s.solve_augmented_equation(1e-3).copy()
+    c = s.counters()
+    print("one_wait off, counters after the poisoned factorisation:", c, "vs level launches", rel(got, want))
+    assert c["factor_flow_timeouts"] == 1 and np.all(np.isfinite(got)) and rel(got, want) < 1e-7
+    gn, sn, pred = s.step_stats()
+    assert np.isfinite([gn, sn, pred]).all() and pred > 0
+    again = s.solve_augmented_equation(1e-3).copy()         # the handle stays on the level launches
+    assert rel(again, want) < 1e-7 and s.counters()["factor_flow_timeouts"] == 1
+    s.close()
+
+
+def test_pose_graph_factor_flow_timeout_is_caught_in_the_same_solve_and_repaired():
+    """The same give-up on a pose-graph handle (one wait per solve): H is assembled again, factorised with the level launches
+    and the sweeps run once more over the good factor; the step, the statistics and the trial cost are the repaired ones."""
+    d = pkg.synthetic.make_sphere(50, 70)
+    prob = PoseGraphProblem.pose_graph(d)
+    ref = GpuSparseCholeskySolver(0).with_option("factor_flow", 0).initialize_structure(prob)
+    ref.set_parameters(d.poses)
+    want = ref.solve_augmented_equation(1e-3).copy()
+    assert ref.counters()["factor_flow_groups"] == 0
+    ref.close()
+    s = GpuSparseCholeskySolver(0).with_option("factor_flow", 8).initialize_structure(prob)
+    s.set_parameters(d.poses)
+    good = s.solve_augmented_equation(1e-3).copy()
+    c0 = s.counters()
+    assert c0["factor_flow_groups"] >= 2 and c0["factor_flow_timeouts"] == 0, c0
+    # (H is assembled with fp64 atomics: two factorisations agree to rounding times cond(H))
+    assert rel(good, want) < 1e-7
+    s.set_option("debug_poison_factor", 1)
+    got = s.solve_augmented_equation(1e-3).copy()
+    c = s.counters()
+    print("pose graph, counters after the poisoned factorisation:", c, "vs level launches", rel(got, want))
+    assert c["factor_flow_timeouts"] == 1 and np.all(np.isfinite(got)) and rel(got, want) < 1e-7
+    gn, sn, pred = s.step_stats()
+    assert np.isfinite([gn, sn, pred]).all() and pred > 0 and np.isfinite(s.eval_step())
+    again = s.solve_augmented_equation(1e-3).copy()         # the handle stays on the level launches
+    assert rel(again, want) < 1e-7 and s.counters()["factor_flow_timeouts"] == 1
+    s.close()
