@@ -26,29 +26,9 @@
 
 #include "ba_device.hpp"
 #include "ba_kernels.h"
+#include "device_reduce.hpp"
 
 namespace apex {
-
-// ------------------------------------------------------------------------------------------
-// reductions
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;  // valid in lane 0
-}
-
-// sum over the 256 threads of a block; result valid in thread 0.  `scratch` holds 4 doubles.
-__device__ __forceinline__ double block_sum_256(double v, double* scratch) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) scratch[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) r = (scratch[0] + scratch[1]) + (scratch[2] + scratch[3]);
-    __syncthreads();
-    return r;
-}
 
 // (memory layout -> register layout, see ba_kernels.h: six 16-byte loads, the expansion is register moves)
 __device__ __forceinline__ void load_lm_record(const double* __restrict__ rec, size_t l, double out[kLmStride]) {

@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "chol_kernels.h"
+#include "device_reduce.hpp"
 #include <algorithm>
 
 namespace apex {
@@ -757,12 +758,6 @@ __global__ __launch_bounds__(576) void k_tile_gemm_nt_small_strip(const GemmTask
         }
 }
 
-__device__ __forceinline__ double wave_sum64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------
 // One step of a tile triangular solve, ONE launch per tile column (forward) / tile row (backward):
 //   forward  K : y_K = Linv_KK b_K ;  b_I -= L_IK y_K  for every tile (I,K) below the diagonal
@@ -1485,7 +1480,7 @@ __global__ __launch_bounds__(256) void k_sym_tile_gather(const int* __restrict__
         y[(size_t)I * NB + tid] = acc;
     }
     double d = (tid < NB) ? acc * p[(size_t)I * NB + tid] : 0.0;
-    d = wave_sum64(d);
+    d = wave_sum(d);
     if ((tid & 63) == 0) sc[tid >> 6] = d;
     __syncthreads();
     if (tid == 0) row_dot[I] = (sc[0] + sc[1]) + (sc[2] + sc[3]);
@@ -1503,7 +1498,7 @@ __global__ __launch_bounds__(256) void k_pcg_step1(int n, int nt, const double* 
     const int tid = threadIdx.x;
     double pap = 0.0;
     for (int i = tid; i < nt; i += 256) pap += row_dot[i];
-    pap = wave_sum64(pap);
+    pap = wave_sum(pap);
     if ((tid & 63) == 0) sc[tid >> 6] = pap;
     __syncthreads();
     if (tid == 0) {
@@ -1524,7 +1519,7 @@ __global__ __launch_bounds__(256) void k_pcg_step1(int n, int nt, const double* 
         r[i] = ri;
         rr = ri * ri; rz = ri * (pre[i] * ri);
     }
-    rr = wave_sum64(rr); rz = wave_sum64(rz);
+    rr = wave_sum(rr); rz = wave_sum(rz);
     __syncthreads();
     if ((tid & 63) == 0) { sc[tid >> 6] = rr; }
     __syncthreads();
@@ -1546,7 +1541,7 @@ __global__ __launch_bounds__(256) void k_pcg_step2(int n, int n_blk, double* __r
     const int tid = threadIdx.x;
     double rr = 0.0, rz = 0.0;
     for (int i = tid; i < n_blk; i += 256) { rr += blk_part[2 * i]; rz += blk_part[2 * i + 1]; }
-    rr = wave_sum64(rr); rz = wave_sum64(rz);
+    rr = wave_sum(rr); rz = wave_sum(rz);
     if ((tid & 63) == 0) sc[tid >> 6] = rr;
     __syncthreads();
     const double rr_t = (sc[0] + sc[1]) + (sc[2] + sc[3]);
@@ -1647,32 +1642,12 @@ __global__ __launch_bounds__(256) void k_dot(int n, const double* __restrict__ a
     __shared__ double sc[4];
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) s += a[i] * b[i];
-    s = wave_sum64(s);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) sc[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) out[0] = (sc[0] + sc[1]) + (sc[2] + sc[3]);
 }
 
-// x += alpha p ; r -= alpha ap
-__global__ __launch_bounds__(256) void k_pcg_update_xr(int n, double alpha, const double* __restrict__ p,
-                                                         const double* __restrict__ ap, double* __restrict__ x,
-                                                         double* __restrict__ r) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    x[i] += alpha * p[i];
-    r[i] -= alpha * ap[i];
-}
-// the same with alpha = rz_old / p.Ap taken from the device (p.Ap has just been reduced there: no host round trip in the middle of
-// the iteration); |p.Ap| < 1e-20: nothing is touched -- the host breaks on the same test when it reads the scalars
-__global__ __launch_bounds__(256) void k_pcg_update_xr_dev(int n, double rz_old, const double* __restrict__ pap_ptr, const double* __restrict__ p,
-                                                             const double* __restrict__ ap, double* __restrict__ x, double* __restrict__ r) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const double pap = pap_ptr[0];
-    if (i >= n || fabs(pap) < 1e-20) return;
-    const double alpha = rz_old / pap;
-    x[i] += alpha * p[i];
-    r[i] -= alpha * ap[i];
-}
 // ---- the matrix-free PCG with its scalars on the device (Solver::implicit_pcg_solve reads them one iteration behind) ----------
 // sc: [0] r.r  [1] r.z  [2] p.Ap  [3] -  [4] rz_old  [5] frozen  [6] beta
 __global__ void k_pcg_implicit_begin(double* __restrict__ sc) { sc[4] = sc[0]; sc[5] = 0.0; sc[6] = 0.0; }   // (sc[0] = r.z of the start)
@@ -1695,12 +1670,6 @@ __global__ void k_pcg_implicit_close(double* __restrict__ sc, double abs_tol) {
 __global__ __launch_bounds__(256) void k_pcg_update_p_sc(int n, const double* __restrict__ sc, const double* __restrict__ z, double* __restrict__ p) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n && sc[5] == 0.0) p[i] = z[i] + sc[6] * p[i];
-}
-// p = z + beta p
-__global__ __launch_bounds__(256) void k_pcg_update_p(int n, double beta, const double* __restrict__ z,
-                                                        double* __restrict__ p) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = z[i] + beta * p[i];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1824,12 +1793,6 @@ void launch_pcg_init(int n, const double* diag, const double* b, double* pre, do
 void launch_dot(int n, const double* a, const double* b, double* out, hipStream_t s) {
     hipLaunchKernelGGL(k_dot, dim3(1), dim3(256), 0, s, n, a, b, out);
 }
-void launch_pcg_update_xr(int n, double alpha, const double* p, const double* ap, double* x, double* r, hipStream_t s) {
-    hipLaunchKernelGGL(k_pcg_update_xr, dim3((n + 255) / 256), dim3(256), 0, s, n, alpha, p, ap, x, r);
-}
-void launch_pcg_update_xr_dev(int n, double rz_old, const double* pap, const double* p, const double* ap, double* x, double* r, hipStream_t s) {
-    hipLaunchKernelGGL(k_pcg_update_xr_dev, dim3((n + 255) / 256), dim3(256), 0, s, n, rz_old, pap, p, ap, x, r);
-}
 void launch_pcg_implicit_begin(double* sc, hipStream_t s) { hipLaunchKernelGGL(k_pcg_implicit_begin, dim3(1), dim3(1), 0, s, sc); }
 void launch_pcg_update_xr_sc(int n, const double* sc, const double* p, const double* ap, double* x, double* r, hipStream_t s) {
     hipLaunchKernelGGL(k_pcg_update_xr_sc, dim3((n + 255) / 256), dim3(256), 0, s, n, sc, p, ap, x, r);
@@ -1837,9 +1800,6 @@ void launch_pcg_update_xr_sc(int n, const double* sc, const double* p, const dou
 void launch_pcg_implicit_close(double* sc, double abs_tol, hipStream_t s) { hipLaunchKernelGGL(k_pcg_implicit_close, dim3(1), dim3(1), 0, s, sc, abs_tol); }
 void launch_pcg_update_p_sc(int n, const double* sc, const double* z, double* p, hipStream_t s) {
     hipLaunchKernelGGL(k_pcg_update_p_sc, dim3((n + 255) / 256), dim3(256), 0, s, n, sc, z, p);
-}
-void launch_pcg_update_p(int n, double beta, const double* z, double* p, hipStream_t s) {
-    hipLaunchKernelGGL(k_pcg_update_p, dim3((n + 255) / 256), dim3(256), 0, s, n, beta, z, p);
 }
 
 // ------------------------------------------------------------------------------------------

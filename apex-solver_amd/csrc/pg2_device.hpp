@@ -1,4 +1,5 @@
-// pg2_device.hpp -- per-edge SE2 pose-graph math shared by the kernels in pg2_kernels.hip.
+// pg2_device.hpp -- per-edge SE2 pose-graph math behind the kernels of pg_kernels.hip, and Se2Manifold, the trait through
+// which the manifold-generic kernels there reach it.
 //
 // APEX_HD (host+device) like pg_device.hpp, so tests/host_harness_se2.cpp runs the same code on the CPU.
 //
@@ -247,5 +248,41 @@ APEX_HD void pg2_assemble_row(uint32_t v, const double* __restrict__ posep, cons
         }
     }
 }
+
+// The SE2 side of the trait pg_device.hpp describes at Se3Manifold.
+struct Se2Manifold {
+    static constexpr int kDof = 3;                 // tangent columns per vertex
+    static constexpr int kAmb = 3;                 // stored doubles per vertex / measurement / prior: x y theta
+    static constexpr int kStride = kPose2Stride;   // doubles per prepared pose / measurement (x y cos sin) / prior block
+    static constexpr bool kPriorOnPrepared = false;   // the prior sees [x, y, theta] itself
+
+    static APEX_HD void prepare(const double* __restrict__ v, double* __restrict__ o) { se2_prepare(v, o); }
+    static APEX_HD void plus(const double* x, const double* d, double* o) { se2_plus(x, d, o); }
+    static APEX_HD void residual(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m, double r[3]) {
+        double A[4];
+        between2_residual(k0, k1, m, r, A);
+    }
+    static APEX_HD double prior_residual(const double* __restrict__ x, const double* __restrict__ data, double delta, double r[3]) {
+        return prior2_eval(x, data, delta, r);
+    }
+    static APEX_HD double cost_add_prior(double acc, const double r[3]) {   // the block's squared norm first, then one add
+        return acc + (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    }
+    // corrected residual [3] and Jacobian [3][6] = [dr/dk0 | dr/dk1] of one edge (either may be null); sqrt(rho') is
+    // applied inside between2_corrected
+    static APEX_HD void export_edge(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                                    double huber_delta, double* __restrict__ r_out, double* __restrict__ j_out) {
+        double r[3], J0[9], J1[9];
+        between2_corrected(k0, k1, m, huber_delta, r, J0, J1);
+        if (r_out)
+            for (int i = 0; i < 3; ++i) r_out[i] = r[i];
+        if (j_out)
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    j_out[6 * i + j] = J0[3 * i + j];
+                    j_out[6 * i + 3 + j] = J1[3 * i + j];
+                }
+    }
+};
 
 }  // namespace apex

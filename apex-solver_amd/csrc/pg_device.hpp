@@ -1,4 +1,5 @@
-// pg_device.hpp -- per-edge SE3 pose-graph math shared by the kernels in pg_kernels.hip.
+// pg_device.hpp -- per-edge SE3 pose-graph math behind the kernels of pg_kernels.hip, and Se3Manifold, the trait through
+// which the manifold-generic kernels there reach it.
 //
 // APEX_HD (host+device) like ba_device.hpp, so tests/host_harness.cpp runs the same code on the CPU.
 //
@@ -240,5 +241,64 @@ APEX_HD void jtr(const Jac6& A, const double r[6], double g[6]) {
         g[3 + i] = (A.T[i] * r[0] + A.T[3 + i] * r[1] + A.T[6 + i] * r[2]) + (A.P[i] * r[3] + A.P[3 + i] * r[4] + A.P[6 + i] * r[5]);
     }
 }
+
+// PriorFactor on an SE3 variable (prior_factor.rs:96-108): r = to_vector(x) - data over the 7 stored doubles of the prepared
+// pose (SE3::from(DVector).to_vector(), unit quaternion), J = the first six columns of I7; returns sqrt(rho') of the
+// block's Huber loss
+APEX_HD double prior_eval(const double* __restrict__ x7, const double* __restrict__ data7, double delta, double r[7]) {
+    double s = 0.0;
+#pragma unroll
+    for (int a = 0; a < 7; ++a) { r[a] = x7[a] - data7[a]; s += r[a] * r[a]; }
+    const double sc = pg_huber_scale(delta, s);
+#pragma unroll
+    for (int a = 0; a < 7; ++a) r[a] *= sc;
+    return sc;
+}
+
+// What the manifold-generic kernels of pg_kernels.hip know about a vertex type: three sizes and forwarders to the math
+// above.  Se2Manifold (pg2_device.hpp) is the other one.  Each manifold keeps its own order of operations behind these
+// names -- where the Huber factor is applied, how a prior's squares are added -- because the bits depend on it.
+struct Se3Manifold {
+    static constexpr int kDof = 6;      // tangent columns per vertex
+    static constexpr int kAmb = 7;      // stored doubles per vertex / measurement / prior: t(3) q(4)
+    static constexpr int kStride = 8;   // doubles per prepared pose / measurement / prior block: t(3) q(4) pad
+    static constexpr bool kPriorOnPrepared = true;   // the prior sees the normalised pose
+
+    static APEX_HD void prepare(const double* __restrict__ v, double* __restrict__ o) { pose_normalise(v, o); }
+    static APEX_HD void plus(const double* x, const double* d, double* o) { se3_plus(x, d, o); }
+    static APEX_HD void residual(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m, double r[6]) {
+        double tA[3], qA[4], D[9];
+        between_residual(k0, k1, m, r, tA, qA, D);
+    }
+    static APEX_HD double prior_residual(const double* __restrict__ x, const double* __restrict__ data, double delta, double r[7]) {
+        return prior_eval(x, data, delta, r);
+    }
+    static APEX_HD double cost_add_prior(double acc, const double r[7]) {   // one chain through the accumulator
+#pragma unroll
+        for (int a = 0; a < 7; ++a) acc += r[a] * r[a];
+        return acc;
+    }
+    // corrected residual [6] and Jacobian [6][12] = [dr/dk0 | dr/dk1] of one edge (either may be null); sqrt(rho') is
+    // applied at the store
+    static APEX_HD void export_edge(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                                    double huber_delta, double* __restrict__ r_out, double* __restrict__ j_out) {
+        double r[6];
+        Jac6 J[2];
+        between_linearize(k0, k1, m, r, J[0], J[1]);
+        const double sc = pg_huber_scale(huber_delta, r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+        if (r_out)
+            for (int i = 0; i < 6; ++i) r_out[i] = sc * r[i];
+        if (j_out)
+            for (int w = 0; w < 2; ++w)
+                for (int i = 0; i < 3; ++i)
+                    for (int j = 0; j < 3; ++j) {
+                        double* o = j_out + 6 * w;
+                        o[12 * i + j] = sc * J[w].P[3 * i + j];
+                        o[12 * i + 3 + j] = sc * J[w].T[3 * i + j];
+                        o[12 * (i + 3) + j] = 0.0;
+                        o[12 * (i + 3) + 3 + j] = sc * J[w].P[3 * i + j];
+                    }
+    }
+};
 
 }  // namespace apex

@@ -1,4 +1,5 @@
-// pg_kernels.h -- launchers of the SE3 pose-graph kernels (BASELINE.json configs[1]).
+// pg_kernels.h -- launchers of the pose-graph kernels (pg_kernels.hip; BASELINE.json configs[1]).  Every launcher that
+// depends on what a vertex is takes the manifold and picks the instantiation (Se3Manifold | Se2Manifold) itself.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,35 +8,42 @@
 
 namespace apex {
 
-constexpr int kPoseStride = 8;      // doubles per prepared pose / measurement: t(3) q(4) pad
-constexpr int kVertsPerTile = kNB / 6;  // 24 vertices per 144-row tile
+enum PgManifold { kManifoldSE3 = 0, kManifoldSE2 = 1 };
 
-// Read-only view of one parameter set + the edge list (internal vertex numbering).
+// Read-only view of one parameter set + the edge list (internal vertex numbering).  Sizes per manifold (SE3 | SE2):
+// amb = 7 | 3 stored doubles per vertex, stride = 8 | 4 doubles per prepared pose, measurement and prior block.
 struct PGView {
     int64_t n_v, n_e;
-    const double* posep;     // [n_v][8] prepared poses (unit quaternion)
+    const double* posep;     // [n_v][stride] prepared poses: t, unit quaternion, pad | x y cos sin
     const uint32_t* e_from;  // [n_e] k0 of BetweenFactor
     const uint32_t* e_to;    // [n_e] k1
-    const double* meas;      // [n_e][8] prepared measurements
+    const double* meas;      // [n_e][stride] prepared measurements
     double huber_delta;      // <= 0: no loss function
-    // PriorFactor blocks (prior_factor.rs:96-108): r = to_vector(x_v) - data, 7 rows; J = the first six columns of I7
+    // PriorFactor blocks (prior_factor.rs:96-108): r = to_vector(x_v) - data, amb rows.  SE3: the caller's order, x_v the
+    // prepared pose, J = the first six columns of I7.  SE2: sorted by vertex (stable), x_v = [x, y, theta], J = I3.
     int n_prior = 0;
-    const uint32_t* prior_v = nullptr;   // [n_prior] vertex (device order)
-    const double* prior_data = nullptr;  // [n_prior][8]: data (7) | the block's Huber delta (<= 0: none)
+    const uint32_t* prior_v = nullptr;    // [n_prior] vertex (device order)
+    const double* prior_data = nullptr;   // [n_prior][stride]: data (amb) | the block's Huber delta (<= 0: none)
+    // SE2 only (null for SE3)
+    const double* poses = nullptr;        // [n_v][3] x y theta (what the prior sees)
+    const int* inc_ptr = nullptr;         // [n_v + 1] incident-edge CSR of the row-owned assembly (pg2_lists.h)
+    const uint32_t* inc_edge = nullptr;
+    const int* prior_slot = nullptr;      // [n_prior] the caller's index of the block (export order)
 };
 
-void launch_pg_prepare(int64_t n, const double* poses7, double* posep, hipStream_t s);
-// H (tiles, lower triangle) += J^T J over all edges, g += J^T r  (tiles and g zeroed by the caller)
-void launch_pg_edges(const PGView& v, const TileMap& tm, double* g, hipStream_t s);
-// the prior blocks' J^T J (+= sc^2 on the six diagonal entries of the vertex) and J^T r; after launch_pg_edges
-void launch_pg_priors(const PGView& v, const TileMap& tm, double* g, hipStream_t s);
-// corrected prior residuals [n_prior][7]
-void launch_pg_prior_export(const PGView& v, double* r7_out, hipStream_t s);
-void launch_pg_cost(const PGView& v, double* partial, int n_partial, double* out_sumsq, hipStream_t s);
-void launch_pg_retract(int64_t n_v, const double* poses, const double* d, double sign, const uint8_t* fix,
+void launch_pg_prepare(int manifold, int64_t n, const double* poses, double* posep, hipStream_t s);
+// H (tiles, lower triangle) += J^T J, g += J^T r over the edges, then the prior blocks' J^T J (sc^2 on the diagonal entries
+// of the vertex) and J^T r; tiles and g zeroed by the caller.  Two launches, and two algorithms:
+//   SE3  k_pg_edges + k_pg_priors      edge-major, fp64 atomics, priors in the caller's order
+//   SE2  k_pg2_assemble + k_pg2_priors row-owned, no atomics, a fixed order of summation per destination
+void launch_pg_assemble(int manifold, const PGView& v, const TileMap& tm, double* g, hipStream_t s);
+// corrected prior residuals [n_prior][amb], the caller's order
+void launch_pg_prior_export(int manifold, const PGView& v, double* r_out, hipStream_t s);
+void launch_pg_cost(int manifold, const PGView& v, double* partial, int n_partial, double* out_sumsq, hipStream_t s);
+void launch_pg_retract(int manifold, int64_t n_v, const double* poses, const double* d, double sign, const uint8_t* fix,
                        double* poses_out, hipStream_t s);
 void launch_pg_negate(int64_t n, const double* x, double* y, hipStream_t s);
-// corrected residuals [n_e][6] and Jacobians [n_e][6][12] in the kernel's edge order
-void launch_pg_export(const PGView& v, double* r_out, double* j_out, hipStream_t s);
+// corrected residuals [n_e][dof] and Jacobians [n_e][dof][2 dof] = [dr/dk0 | dr/dk1] in the kernel's edge order
+void launch_pg_export(int manifold, const PGView& v, double* r_out, double* j_out, hipStream_t s);
 
 }  // namespace apex

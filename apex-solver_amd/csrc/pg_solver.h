@@ -8,9 +8,10 @@
 //
 // One class, two manifolds.  The orchestration (speculative factor, one wait per iteration, eager step evaluation,
 // scaling, covariance, exports) does not care what a vertex is: it sees dof_ tangent columns and amb_ stored doubles per
-// vertex, kNB / dof_ vertices per tile.  Only prepare / assemble / priors / cost / retract / exports differ, and those go
-// through the enqueue_* members: SE3 -> pg_kernels.hip (6, 7, atomic edge scatter), SE2 -> pg2_kernels.hip (3, 3, the
-// row-owned assembly over the incident-edge lists of pg2_lists.h, which live with the SE2 structure only).
+// vertex, kNB / dof_ vertices per tile.  Only prepare / assemble / priors / cost / retract / exports differ, and the
+// launchers of pg_kernels.h take manifold_ for that: the same kernels instantiated for Se3Manifold (6, 7) or Se2Manifold
+// (3, 3), and one assembly each -- SE3 the atomic edge scatter, SE2 the row-owned assembly over the incident-edge lists
+// of pg2_lists.h, which live with the SE2 structure only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,13 +19,11 @@
 #include <string>
 #include <vector>
 
-#include "pg2_kernels.h"
 #include "pg_kernels.h"
 #include "tile_backend.h"
 
 namespace apex {
 
-enum PgManifold { kManifoldSE3 = 0, kManifoldSE2 = 1 };
 enum PgStage { kPgAssemble = 0, kPgFactor, kPgTriSolve, kPgStats, kPgRetract, kPgCost, kPgNumStages };
 
 class PoseGraphSolver : public TileBackend {
@@ -82,12 +81,7 @@ class PoseGraphSolver : public TileBackend {
     int finish_step(double* step_out, double* grad_out) override;
     int recover_factor(double lambda, int failed, bool gave_up) override;
     PGView view(int which) const;
-    PG2View view2(int which) const;
-    // the manifold-specific launches
-    void enqueue_prepare(int which);
-    void enqueue_assemble_blocks();
-    void enqueue_cost(int which, double* sumsq_out);
-    void enqueue_retract(int from, double sign, int to);
+    void enqueue_retract(int from, double sign, int to);   // retraction + the prepared poses of the result
     int assemble(double lambda);
     int ensure_scale_buffer();
     int cost_of(int which, double* out);

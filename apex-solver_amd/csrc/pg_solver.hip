@@ -15,55 +15,31 @@ namespace apex {
 
 PoseGraphSolver::PoseGraphSolver(int64_t n_v, int64_t n_e, int device, int manifold)
     : TileBackend(device, kPgNumStages, /*nd_leaf=*/2), n_v_(n_v), n_e_(n_e), manifold_(manifold == kManifoldSE2 ? kManifoldSE2 : kManifoldSE3),
-      dof_(manifold_ == kManifoldSE2 ? 3 : 6), amb_(manifold_ == kManifoldSE2 ? 3 : 7),
-      stride_(manifold_ == kManifoldSE2 ? kPose2Stride : kPoseStride), vpt_(kNB / dof_) {}
+      dof_(manifold_ == kManifoldSE2 ? Se2Manifold::kDof : Se3Manifold::kDof),
+      amb_(manifold_ == kManifoldSE2 ? Se2Manifold::kAmb : Se3Manifold::kAmb),
+      stride_(manifold_ == kManifoldSE2 ? Se2Manifold::kStride : Se3Manifold::kStride), vpt_(kNB / dof_) {}
 
 PoseGraphSolver::~PoseGraphSolver() {
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);   // before any buffer is freed; stream_last_ destroys the stream after them
 }
 
+// (the SE2-only members are empty buffers, so null, on an SE3 graph)
 PGView PoseGraphSolver::view(int which) const {
     PGView v;
     v.n_v = n_v_; v.n_e = n_e_;
     v.posep = posep_[which]; v.e_from = e_from_; v.e_to = e_to_; v.meas = meas_;
     v.huber_delta = huber_delta_;
     v.n_prior = n_prior_; v.prior_v = prior_v_; v.prior_data = prior_data_;
-    return v;
-}
-
-PG2View PoseGraphSolver::view2(int which) const {
-    PG2View v;
-    v.n_v = n_v_; v.n_e = n_e_;
-    v.poses = poses_[which]; v.posep = posep_[which]; v.e_from = e_from_; v.e_to = e_to_; v.meas = meas_;
-    v.huber_delta = huber_delta_;
-    v.inc_ptr = inc_ptr_; v.inc_edge = inc_edge_;
-    v.n_prior = n_prior_; v.prior_v = prior_v_; v.prior_data = prior_data_; v.prior_slot = prior_slot_;
-    return v;
-}
-
-// ---- the manifold-specific launches ----------------------------------------------------------------
-void PoseGraphSolver::enqueue_prepare(int which) {
-    if (manifold_ == kManifoldSE2) launch_pg2_prepare(n_v_, poses_[which], posep_[which], stream_);
-    else launch_pg_prepare(n_v_, poses_[which], posep_[which], stream_);
-}
-void PoseGraphSolver::enqueue_assemble_blocks() {
     if (manifold_ == kManifoldSE2) {
-        launch_pg2_assemble(view2(cur_), tp_.tilemap(), g_, stream_);
-        launch_pg2_priors(view2(cur_), tp_.tilemap(), g_, stream_);
-    } else {
-        launch_pg_edges(view(cur_), tp_.tilemap(), g_, stream_);
-        launch_pg_priors(view(cur_), tp_.tilemap(), g_, stream_);
+        v.poses = poses_[which]; v.inc_ptr = inc_ptr_; v.inc_edge = inc_edge_; v.prior_slot = prior_slot_;
     }
+    return v;
 }
-void PoseGraphSolver::enqueue_cost(int which, double* sumsq_out) {
-    if (manifold_ == kManifoldSE2) launch_pg2_cost(view2(which), partial_, n_partial_, sumsq_out, stream_);
-    else launch_pg_cost(view(which), partial_, n_partial_, sumsq_out, stream_);
-}
+
 void PoseGraphSolver::enqueue_retract(int from, double sign, int to) {
-    if (manifold_ == kManifoldSE2) launch_pg2_retract(n_v_, poses_[from], d_, sign, fix_, poses_[to], stream_);
-    else launch_pg_retract(n_v_, poses_[from], d_, sign, fix_, poses_[to], stream_);
-    enqueue_prepare(to);
+    launch_pg_retract(manifold_, n_v_, poses_[from], d_, sign, fix_, poses_[to], stream_);
+    launch_pg_prepare(manifold_, n_v_, poses_[to], posep_[to], stream_);
 }
 
 // PriorFactor blocks (prior_factor.rs:96-108); replaces the set.  data7 in to_vector order [t, w, i, j, k].
@@ -112,8 +88,7 @@ int PoseGraphSolver::get_prior_residual(double* r7_out) {
     if (n_prior_ == 0) return kOk;
     HIP_TRY(hipSetDevice(device_));
     if (!prior_res_) HIP_TRY(prior_res_.alloc((size_t)n_prior_ * amb_));   // kept with the priors (set_priors frees it)
-    if (manifold_ == kManifoldSE2) launch_pg2_prior_export(view2(cur_), prior_res_, stream_);
-    else launch_pg_prior_export(view(cur_), prior_res_, stream_);
+    launch_pg_prior_export(manifold_, view(cur_), prior_res_, stream_);
     HIP_TRY(hipMemcpyAsync(r7_out, prior_res_, (size_t)n_prior_ * amb_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     return kOk;
@@ -202,7 +177,7 @@ int PoseGraphSolver::set_params(const double* poses7) {
     if (manifold_ == kManifoldSE2)   // the variable is held as SE2 -> DVector gives it: theta in (-pi, pi] (se2.rs:55-63)
         for (int64_t v = 0; v < n_v_; ++v) hp[3 * (size_t)v + 2] = se2_wrap_angle(hp[3 * (size_t)v + 2]);
     HIP_TRY(hipMemcpyAsync(poses_[cur_], hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
-    enqueue_prepare(cur_);
+    launch_pg_prepare(manifold_, n_v_, poses_[cur_], posep_[cur_], stream_);
     HIP_TRY(hipStreamSynchronize(stream_));
     have_params_ = true; have_step_ = have_trial_ = false;
     return kOk;
@@ -220,7 +195,7 @@ int PoseGraphSolver::get_params(double* poses7) {
 
 int PoseGraphSolver::cost_of(int which, double* out) {
     timer_.begin(kPgCost, stream_);
-    enqueue_cost(which, scal_);
+    launch_pg_cost(manifold_, view(which), partial_, n_partial_, scal_, stream_);
     timer_.end(kPgCost, stream_);
     double ss = 0.0;
     HIP_TRY(hipMemcpyAsync(&ss, scal_, sizeof(double), hipMemcpyDeviceToHost, stream_));
@@ -242,7 +217,7 @@ int PoseGraphSolver::assemble(double lambda) {
     HIP_TRY(tp_.zero_tiles());
     HIP_TRY(hipMemsetAsync(g_, 0, n_pad_ * sizeof(double), stream_));
     tp_.add_diag((int)n_, scaled_ ? 0.0 : lambda, 1.0);  // lambda on the real rows, identity on the padding rows
-    enqueue_assemble_blocks();
+    launch_pg_assemble(manifold_, view(cur_), tp_.tilemap(), g_, stream_);
     if (scaled_) {  // Jacobi scaling: H := D H D, then the damping of the scaled system
         tp_.scale_sym(scale_);
         tp_.add_diag((int)n_, lambda, 1.0);
@@ -337,7 +312,7 @@ void PoseGraphSolver::enqueue_trial_point(double* sumsq_out) {
     enqueue_retract(cur_, 1.0, t);
     timer_.end(kPgRetract, stream_);
     timer_.begin(kPgCost, stream_);
-    enqueue_cost(t, sumsq_out);
+    launch_pg_cost(manifold_, view(t), partial_, n_partial_, sumsq_out, stream_);
     timer_.end(kPgCost, stream_);
 }
 
@@ -481,8 +456,7 @@ int PoseGraphSolver::get_residual(double* r_out) {
     HIP_TRY(hipSetDevice(device_));
     DeviceBuffer<double> d;
     HIP_TRY(d.alloc(dof_ * (size_t)n_e_));
-    if (manifold_ == kManifoldSE2) launch_pg2_export(view2(cur_), d, nullptr, stream_);
-    else launch_pg_export(view(cur_), d, nullptr, stream_);
+    launch_pg_export(manifold_, view(cur_), d, nullptr, stream_);
     hipError_t e = hipMemcpyAsync(r_out, d, dof_ * n_e_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     (void)hipStreamSynchronize(stream_);
     return check_hip(e, "get_residual");
@@ -494,8 +468,7 @@ int PoseGraphSolver::get_jacobian_blocks(double* j_out) {
     DeviceBuffer<double> d;
     const size_t jn = 2 * (size_t)dof_ * dof_;   // [dof][2 dof] per edge
     HIP_TRY(d.alloc(jn * (size_t)n_e_));
-    if (manifold_ == kManifoldSE2) launch_pg2_export(view2(cur_), nullptr, d, stream_);
-    else launch_pg_export(view(cur_), nullptr, d, stream_);
+    launch_pg_export(manifold_, view(cur_), nullptr, d, stream_);
     hipError_t e = hipMemcpyAsync(j_out, d, jn * n_e_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     (void)hipStreamSynchronize(stream_);
     return check_hip(e, "get_jacobian_blocks");

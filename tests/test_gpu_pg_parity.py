@@ -351,3 +351,50 @@ def test_lm_with_prior_gauge_matches_the_oracle_loop():
     assert abs(res.initial_cost - ref["initial_cost"]) <= 1e-12 * ref["initial_cost"]
     assert abs(res.final_cost - ref["final_cost"]) <= 1e-7 * ref["final_cost"]
     assert res.final_cost < 0.5 * res.initial_cost
+
+
+# ---- the grid-stride pass of the cost kernel ------------------------------------------------------------------
+def _random_path_graph(manifold, n_v, seed):
+    """Vertices 0 .. n_v - 1 in a path (edge i: i -> i + 1; block-tridiagonal, no fill), random poses and measurements."""
+    rng = np.random.default_rng(seed)
+
+    def poses(n):
+        if manifold == "se2":
+            return np.column_stack([10.0 * rng.standard_normal((n, 2)), rng.uniform(-np.pi, np.pi, n)])
+        q = rng.standard_normal((n, 4))
+        return np.column_stack([10.0 * rng.standard_normal((n, 3)), q / np.linalg.norm(q, axis=1, keepdims=True)])
+
+    e = np.arange(n_v - 1, dtype=np.uint32)
+    return pkg.synthetic.PoseGraphData(ids=np.arange(n_v, dtype=np.int64), poses=poses(n_v), e_from=e, e_to=e + 1, meas=poses(n_v - 1))
+
+
+def _path_slice(d, v0, v1):
+    """The sub-path on vertices v0 .. v1 inclusive: edges v0 .. v1 - 1 of d with their poses and measurements."""
+    e = np.arange(v1 - v0, dtype=np.uint32)
+    return pkg.synthetic.PoseGraphData(ids=d.ids[v0:v1 + 1], poses=d.poses[v0:v1 + 1], e_from=e, e_to=e + 1, meas=d.meas[v0:v1])
+
+
+def _device_cost(d):
+    s = GpuSparseCholeskySolver().initialize_structure(PoseGraphProblem(d))
+    s.set_parameters(d.poses)
+    c = s.compute_cost()
+    s.close()
+    return c
+
+
+@pytest.mark.parametrize("manifold", ["se3", "se2"])
+def test_cost_grid_stride_pass_equals_the_sum_of_single_pass_parts(manifold):
+    """The cost kernel runs 256 blocks of 256 threads, so only a graph above 65,536 edges sends a thread round its
+    grid-stride loop a second time -- every other graph of the suite stays below.  A path of 66,000 vertices (65,999
+    edges) against the device's own cost of the same edges in two handles of 33,000 and 32,999 edges, each one pass (the
+    path the numpy references and the oracle pin): equal to rel 1e-13, a few ulp over 66,000 non-negative terms summed by
+    two different fixed trees.  No solve: set_structure, set_params, cost."""
+    n_v = 66000
+    d = _random_path_graph(manifold, n_v, seed=11)
+    assert d.n_e == 65999 > 256 * 256
+    mid = 33000
+    parts = [_device_cost(_path_slice(d, 0, mid)), _device_cost(_path_slice(d, mid, n_v - 1))]
+    whole = _device_cost(d)
+    print(f"{manifold}: whole {whole!r}  parts {parts!r}  rel {abs(whole - sum(parts)) / sum(parts):.3e}")
+    assert parts[0] > 0.0 and parts[1] > 0.0
+    assert abs(whole - sum(parts)) <= 1e-13 * sum(parts)
