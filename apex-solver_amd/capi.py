@@ -27,6 +27,7 @@ SYMBOLS = (
     "apexgpu_get_schur", "apexgpu_camera_covariance", "apexgpu_covariance_stats", "apexgpu_landmark_covariance", "apexgpu_landmark_covariance_stats", "apexgpu_get_landmark_blocks", "apexgpu_get_hessian_csc", "apexgpu_debug_invert_blocks", "apexgpu_debug_pair_lists", "apexgpu_debug_pair_lists_queued", "apexgpu_debug_pair_lists_queued_dc", "apexgpu_debug_host_structure", "apexgpu_setup_times", "apexgpu_schur_matvec", "apexgpu_set_option", "apexgpu_enable_stage_timing", "apexgpu_reset_stage_times",
     "apexgpu_stage_times", "apexgpu_info", "apexgpu_variant_info", "apexgpu_variant_costs", "apexgpu_trim_host_cache", "apexgpu_host_cache_bytes", "apexgpu_counters", "apexgpu_debug_get_pair_records", "apexgpu_get_unique_id", "apexgpu_comm_init", "apexgpu_comm_init_shm", "apexgpu_set_shard", "apexgpu_shard_range",
     "apexgpu_debug_lockstep_solve", "apexgpu_export_step", "apexgpu_owned_landmarks", "apexgpu_debug_partition", "apexgpu_debug_check_schedule",
+    "apexgpu_debug_schedule_ops",
     "apexgpu_debug_tiles_create", "apexgpu_debug_tiles_pattern", "apexgpu_debug_tiles_set", "apexgpu_debug_tiles_factor",
     "apexgpu_debug_tiles_solve", "apexgpu_debug_tiles_matvec", "apexgpu_debug_tiles_pcg", "apexgpu_debug_tiles_get", "apexgpu_debug_tiles_destroy",
     "apexgpu_bal_open", "apexgpu_bal_close", "apexgpu_bal_last_error", "apexgpu_bal_sizes", "apexgpu_bal_raw",
@@ -129,6 +130,7 @@ def load() -> C.CDLL:
     L.apexgpu_owned_landmarks.argtypes = [vp, vp]
     L.apexgpu_debug_partition.argtypes = [C.c_int, vp, C.c_int, vp]
     L.apexgpu_debug_check_schedule.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_char_p, C.c_int]
+    L.apexgpu_debug_schedule_ops.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int]
     L.apexgpu_debug_tiles_create.argtypes = [C.c_int, C.c_int, vp, vp, C.POINTER(vp)]
     L.apexgpu_debug_tiles_pattern.argtypes = [vp, vp, vp]
     L.apexgpu_debug_tiles_set.argtypes = [vp, vp, C.c_int, dbl, C.c_int]
@@ -262,6 +264,24 @@ def check_schedule(present: np.ndarray, world: int = 1, rank: int = 0, two_side:
         raise LinAlgError(rc, "apexgpu_debug_check_schedule: " + msg.value.decode())
     return dict(levels=rc, calls=int(out[0]), launches=int(out[1]), violations=int(out[2]) + int(out[3]), violations_top=int(out[3]),
                 flow_units=int(out[4]), flow_groups=int(out[5]), waits=int(out[6]), dropped=bool(out[7]), first=msg.value.decode())
+
+
+def schedule_ops(present: np.ndarray, phase: int = 0, world: int = 1, rank: int = 0, two_side: int = 1, overlap: int = 1, split_u1: int = 4,
+                 flood_gate: int = 256, factor_flow: int = -1, factor_flow_rows: int = 24) -> np.ndarray:
+    """Host only: the factorisation's launch sequence of one phase as rows {op, stream, event, list, first, count}
+    (apexgpu_debug_schedule_ops; options as check_schedule)."""
+    L = load()
+    pr = np.ascontiguousarray(present, dtype=np.uint8)
+    nt = pr.shape[0]
+    opts = np.array([two_side, overlap, split_u1, flood_gate, factor_flow, factor_flow_rows, 0, -1], dtype=np.int32)
+    args = (nt, pr.ctypes.data_as(C.c_void_p), int(world), int(rank), opts.ctypes.data_as(C.c_void_p), int(phase))
+    n = L.apexgpu_debug_schedule_ops(*args, None, 0)
+    if n < 0:
+        raise LinAlgError(n, "apexgpu_debug_schedule_ops")
+    rows = np.zeros((n, 6), dtype=np.int64)
+    if n and L.apexgpu_debug_schedule_ops(*args, rows.ctypes.data_as(C.c_void_p), n) != n:
+        raise LinAlgError(-6, "apexgpu_debug_schedule_ops")
+    return rows
 
 
 HOST_STRUCTURE_STATS = ("tile_rows", "hub_cameras", "border_tiles", "touched_tiles", "tiles", "etree_levels", "top_columns",

@@ -295,10 +295,8 @@ int apexgpu_debug_partition(int nt, const uint8_t* present, int world, int* owne
     });
 }
 
-int apexgpu_debug_check_schedule(int nt, const uint8_t* present, int world, int rank, const int opts[8], int64_t out[8], char* msg, int msg_len) {
-    if (nt <= 0 || !present || !opts || !out || world < 1 || rank < 0 || rank >= world) return APEXGPU_ERR_INVALID_INPUT;
-    return guarded([&]() -> int {
-    apex::TilePlan tp;
+// the host-only plan of apexgpu_debug_check_schedule / apexgpu_debug_schedule_ops; returns build_host_only's message
+static std::string schedule_plan(apex::TilePlan& tp, int nt, const uint8_t* present, int world, int rank, const int opts[8]) {
     if (world > 1) tp.set_partition(rank, world);
     tp.set_two_side(opts[0]);
     tp.enable_overlap(opts[1] != 0); if (opts[1] > 1) tp.set_overlap_min(opts[1]);
@@ -306,8 +304,14 @@ int apexgpu_debug_check_schedule(int nt, const uint8_t* present, int world, int 
     tp.set_gate_min(opts[3]);
     tp.set_factor_flow(opts[4], opts[5]);
     tp.debug_skip_idle_level_wait(opts[6] != 0);
-    const std::vector<uint8_t> pr(present, present + (size_t)nt * nt);
-    const std::string e = tp.build_host_only(nt, pr);
+    return tp.build_host_only(nt, std::vector<uint8_t>(present, present + (size_t)nt * nt));
+}
+
+int apexgpu_debug_check_schedule(int nt, const uint8_t* present, int world, int rank, const int opts[8], int64_t out[8], char* msg, int msg_len) {
+    if (nt <= 0 || !present || !opts || !out || world < 1 || rank < 0 || rank >= world) return APEXGPU_ERR_INVALID_INPUT;
+    return guarded([&]() -> int {
+    apex::TilePlan tp;
+    const std::string e = schedule_plan(tp, nt, present, world, rank, opts);
     std::string first;
     if (!e.empty()) { if (msg && msg_len > 0) snprintf(msg, (size_t)msg_len, "%s", e.c_str()); return APEXGPU_ERR_INVALID_STATE; }
     for (int k = 0; k < 8; ++k) out[k] = 0;
@@ -316,18 +320,32 @@ int apexgpu_debug_check_schedule(int nt, const uint8_t* present, int world, int 
         if (opts[7] >= 0 && ph == 0) {   // drop the opts[7]-th stream wait of the sequence: the checker must notice when it mattered
             int seen = 0;
             for (size_t i = 0; i < ops.size(); ++i)
-                if (ops[i].op == 2 && seen++ == opts[7]) { ops.erase(ops.begin() + (long)i); out[7] = 1; break; }
+                if (ops[i].op == apex::kOpWait && seen++ == opts[7]) { ops.erase(ops.begin() + (long)i); out[7] = 1; break; }
         }
         std::string why;
         const int bad = tp.check_schedule(ops, &why);
-        out[0] += (int64_t)ops.size();
-        for (const apex::SchedOp& o : ops) { out[1] += o.op == 0; out[6] += o.op == 2; }
+        for (const apex::SchedOp& o : ops) { out[0] += o.op <= apex::kOpWait; out[1] += o.op == apex::kOpLaunch; out[6] += o.op == apex::kOpWait; }
         out[2 + ph] = bad;
         if (bad && first.empty()) first = why;
     }
     out[4] = tp.factor_flow_units(); out[5] = tp.factor_flow_groups();
     if (msg && msg_len > 0) snprintf(msg, (size_t)msg_len, "%s", first.c_str());
     return tp.n_levels();
+    });
+}
+
+int apexgpu_debug_schedule_ops(int nt, const uint8_t* present, int world, int rank, const int opts[8], int phase, int64_t* rows, int max_rows) {
+    if (nt <= 0 || !present || !opts || world < 1 || rank < 0 || rank >= world || phase < 0 || phase > 1 || max_rows < 0 || (max_rows > 0 && !rows)) return APEXGPU_ERR_INVALID_INPUT;
+    return guarded([&]() -> int {
+    apex::TilePlan tp;
+    if (!schedule_plan(tp, nt, present, world, rank, opts).empty()) return APEXGPU_ERR_INVALID_STATE;
+    const std::vector<apex::SchedOp> ops = tp.schedule_trace(phase);
+    for (size_t i = 0; i < ops.size() && i < (size_t)max_rows; ++i) {
+        const apex::SchedOp& o = ops[i];
+        int64_t* r = rows + 6 * i;
+        r[0] = o.op; r[1] = (int64_t)o.stream; r[2] = (int64_t)o.event; r[3] = o.list; r[4] = o.first; r[5] = o.count;
+    }
+    return (int)ops.size();
     });
 }
 

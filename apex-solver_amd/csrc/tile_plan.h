@@ -27,18 +27,9 @@
 
 #include "chol_kernels.h"
 #include "device_buffer.h"
+#include "factor_schedule.h"
 
 namespace apex {
-
-// One call of the factorisation's launch sequence, as TilePlan::schedule_trace records it instead of issuing it.
-struct SchedOp {
-    int op;             // 0 launch, 1 event record, 2 stream waits for event
-    uintptr_t stream;   // the stream the call goes to (TilePlan::StreamId)
-    uintptr_t event;    // record / wait: the event (level group * TilePlan::kLevelEvents + TilePlan::LevelEvent)
-    int list;           // launch: 0 potrf, 1 panel solves, 2 updates, 3 the dataflow launch
-    int64_t first;      // launch: first task (unit) of its list
-    int count;          // ... and how many
-};
 
 // Everything a TilePlan allocates through HIP, as a base of its own: release() drops all of it with one assignment (no list
 // of members to keep in step), and the base is destroyed after ~TilePlan has destroyed the graph execs that point into it.
@@ -88,12 +79,10 @@ class TilePlan : private TilePlanMemory {
     // check_schedule / flow_units_host.  Nothing on such a plan may be launched: factor() / solve() are unsupported.
     std::string build_host_only(int nt, const std::vector<uint8_t>& present);
     // The launch sequence of one factorisation phase (0: the local level groups / everything, 1: the shared top of a
-    // distributed plan) exactly as enqueue_factor issues it, recorded instead of issued.
-    std::vector<SchedOp> schedule_trace(int phase);
-    // Proves a recorded sequence race free: stream order + event edges give a happens-before relation; every two launches
-    // that touch one tile, at least one of them writing it, must be ordered by it, and no two tasks of one launch may write
-    // one tile (or one read what another writes).  Returns the number of violations (0 = proven) and describes the first.
-    int check_schedule(const std::vector<SchedOp>& ops, std::string* first_violation) const;
+    // distributed plan): the very list enqueue_factor issues (factor_schedule.h).
+    std::vector<SchedOp> schedule_trace(int phase) const;
+    // apex::check_schedule on this plan's task lists
+    int check_schedule(const std::vector<SchedOp>& ops, std::string* first_violation) const { return apex::check_schedule(ops, potrf_h_, trsm_h_, upd_h_, flow_units_h_, first_violation); }
     const std::vector<FactorUnit>& flow_units_host() const { return flow_units_h_; }
     void debug_skip_idle_level_wait(bool on) { debug_skip_idle_wait_ = on; }
     // The host half of build() alone: symbolic fill, partition, slot map, level count (slot_host(), n_slots(),
@@ -272,7 +261,9 @@ class TilePlan : private TilePlanMemory {
     void flag_first_writers(const double* tiles);
     void sym_lists(const std::vector<uint8_t>& present, Lists* out) const;
     std::string upload(const Lists& lists);   // the device step
-    void enqueue_factor(int g0, int g1);
+    ScheduleInput input() const;
+    void issue(const std::vector<SchedOp>& ops);   // one HIP call per op
+    void enqueue_factor(int g0, int g1) { issue(factor_schedule(input(), g0, g1)); }
     void enqueue_solve(const double* rhs, double* x, double* work);
     void launch_fwd_group(int lv, double* bvec, double* yvec, hipStream_t s);
     void enqueue_dist_solve(int phase, const double* rhs, double* x, double* work);
@@ -295,21 +286,15 @@ class TilePlan : private TilePlanMemory {
     int64_t n_potrf_ = 0, n_trsm_ = 0, n_upd_ = 0;
     hipStream_t stream_ = nullptr;
     std::vector<int> slot_h_, diag_slot_h_;
-    // per level group: its first task in each list, the update rounds U1d [upd, u1o) | U1o | U2a | U2b1 | U2b2 [u2b2, next upd),
-    // the first forward task of each column that gets a launch of its own
-    struct Level { int potrf = 0, panel = 0, fwd = 0, upd = 0, u1o = 0, u2a = 0, u2b1 = 0, u2b2 = 0; std::vector<int> fwd_cut; };
-    std::vector<Level> lv_;
+    std::vector<Level> lv_;       // [n_levels_ + 1] (factor_schedule.h)
     std::vector<int> bwd_step_;   // [n_levels_ + 1] first task of each backward-sweep step (root group first)
-    hipStream_t side_ = nullptr;  // trailing updates that the next level does not need (enqueue_factor)
+    hipStream_t side_ = nullptr;  // trailing updates that the next level does not need (factor_schedule)
     hipStream_t side2_ = nullptr; // U2b2: the bulk of U2 (targets four levels up and more)
     int two_side_ = 1;            // option; two_side_plan_: what build() decided for this plan
     bool two_side_plan_ = false;
     hipStream_t so_ = nullptr;    // U1o: updates of the next level's off-diagonal tiles, beside its potrf
-    // enqueue_factor names its streams and events by id; only the calls it issues map them to handles.  Events per level group:
-    // after its panel solves, its U2a, its U1o, its U2b (all of side_), its U2b2 (side2_)
-    enum StreamId { kMain, kSide, kSide2, kSo };   // stream_, side_, side2_, so_
-    hipStream_t stream_of(StreamId s) const { return s == kMain ? stream_ : s == kSide ? side_ : s == kSide2 ? side2_ : so_; }
-    enum LevelEvent { kEvT, kEvU2, kEvO, kEvB, kEvB2, kLevelEvents };
+    // the handles behind the schedule's stream and event ids (issue)
+    hipStream_t stream_of(uintptr_t s) const { return s == kMain ? stream_ : s == kSide ? side_ : s == kSide2 ? side2_ : so_; }
     std::vector<std::array<hipEvent_t, kLevelEvents>> ev_;
     bool split_u1_ = true;
     int split_u1_min_ = 4;
@@ -330,7 +315,6 @@ class TilePlan : private TilePlanMemory {
     double predicted_ms_ = 0.0, cost_limit_ms_ = 0.0;
     int64_t max_updates_ = 80000000LL;      // tile products per factorisation a plan may hold (12.7 s at 45 TF/s)
     bool debug_skip_idle_wait_ = false;   // tests only: bring back the round-3 schedule bug (no wait after a level without side-stream work)
-    std::vector<SchedOp>* sched_trace_ = nullptr;
     std::vector<PotrfTask> potrf_h_;
     std::vector<GemmTask> trsm_h_, upd_h_;
     std::vector<FactorUnit> flow_units_h_;

@@ -360,7 +360,7 @@ std::string TilePlan::host_lists(const std::vector<uint8_t>& present, const Cols
     sweep_lists(col_rows, g, tiles, linv, out);
     sym_lists(present, out);
     n_potrf_ = (int64_t)potrf_h_.size(); n_trsm_ = (int64_t)trsm_h_.size(); n_upd_ = (int64_t)upd_h_.size();
-    // The second side stream (enqueue_factor), for the whole plan or not at all: it pays where a level carries a bulk worth
+    // The second side stream (factor_schedule), for the whole plan or not at all: it pays where a level carries a bulk worth
     // overlapping (final-13682: ~1,000 tile products per level, 7.95 -> 7.5 ms; synthetic-10k 6.4 -> 6.1) and costs where the
     // levels are small and the factorisation is its launch chain (the ladybug / venice shapes, ~100 products per level: one
     // more stream is one more edge per level, 3.1 -> 3.5 ms).
@@ -401,11 +401,11 @@ void TilePlan::level_lists(const Cols& col_rows, const Groups& g, double* tiles,
         // U1o: the other tiles of the next level's columns (what its panel solves need) -- on a third stream, beside the
         //      next potrf;
         // U2: targets further up the tree -- these run on the side stream, overlapped with the next
-        // level's potrf and panel solves (see enqueue_factor)
+        // level's potrf and panel solves (see factor_schedule)
         // U2 itself in two parts: U2a = targets in the columns of level lv+2 -- the only ones the NEXT level's U1 updates also
         // write, so U1(lv+1) waits for U2a(lv) alone -- and U2b = everything higher, which then runs beside them.
         // ... and U2b in two: U2b1 = targets in level lv+3 (all that U2a of the NEXT level collides with), which stays on U2a's
-        // stream, and U2b2 = level lv+4 and above, the bulk, on a stream of its own (enqueue_factor).
+        // stream, and U2b2 = level lv+4 and above, the bulk, on a stream of its own (factor_schedule).
         int* const part_end[4] = {&lv_[lv].u1o, &lv_[lv].u2a, &lv_[lv].u2b1, &lv_[lv].u2b2};
         for (int part = 0; part < 5; ++part) {
             std::vector<const U*> mine;
@@ -943,136 +943,33 @@ void TilePlan::launch_fwd_group(int lv, double* bvec, double* yvec, hipStream_t 
 // The factorisation and the triangular solves are static launch sequences for a given structure:
 // they are captured once into hipGraphs (a few hundred dependent launches would otherwise be paced by
 // host launch overhead) and replayed every iteration.
-void TilePlan::enqueue_factor(int g0, int g1) {
-    // Three streams.  Main: potrf(lv), panel solves(lv), U1d(lv) = the updates of the next level's DIAGONAL tiles (all
-    // its potrf needs).  Third: U1o(lv) = the updates of the other tiles of the next level's columns, beside that
-    // potrf; the next panel solves wait for them.  Side: U2(lv) = every other update of level lv, overlapped with
-    // potrf / panel solves of level lv+1 (one workgroup resp. a few dozen: they leave the chip nearly empty).
-    // Ordering that keeps every tile's read-modify-write sequence race free:
-    //   U2(lv) after the panel solves of lv;  U1d(lv), U1o(lv) after U2a(lv-1) -- the part of U2(lv-1) whose targets lie in
-    //   the columns of level lv+1, and with it (side-stream order) every older side-stream update; U2b(lv-1), targets in
-    //   level lv+2 and above, runs on beside them (round 3: the wait for the whole of U2(lv-1) had become the critical chain
-    //   once the flood gate let the potrf start on time);
-    //   potrf(lv) after U1d(lv-1) [stream order] and whatever U1d(lv-1) waited for;
-    //   panel(lv) after U1o(lv-1) [event];  U1o(lv) and U2(lv) hit different columns (level lv+1 / above);
-    //   a U2 too small for the side stream runs on the main stream after the side stream's last U2b [kEvB].
-    // Every call below goes through these shadows (streams and events by id): with a trace attached (schedule_trace: tests,
-    // host-only plans) the call is recorded instead of issued -- what check_schedule() then proves is this very sequence.
-    std::vector<SchedOp>* const tr = sched_trace_;
-    auto wait = [&](StreamId s, int lv, LevelEvent k) { if (tr) tr->push_back({2, (uintptr_t)s, (uintptr_t)lv * kLevelEvents + k, -1, 0, 0}); else (void)hipStreamWaitEvent(stream_of(s), ev_[lv][k], 0); };
-    auto record = [&](int lv, LevelEvent k, StreamId s) { if (tr) tr->push_back({1, (uintptr_t)s, (uintptr_t)lv * kLevelEvents + k, -1, 0, 0}); else (void)hipEventRecord(ev_[lv][k], stream_of(s)); };
-    auto potrf = [&](int lv) {   // (main stream)
-        const int first = lv_[lv].potrf, n = lv_[lv + 1].potrf - first;
-        if (tr) { if (n > 0) tr->push_back({0, kMain, 0, 0, first, n}); } else launch_potrf_inv(potrf_tasks_ + first, n, flag_, stream_, gate_min_ > 0 ? gate_cnt_ + lv : nullptr);
-    };
-    auto panel = [&](int lv) {   // (main stream; the panel solves multiply by Linv)
-        const int first = lv_[lv].panel, n = lv_[lv + 1].panel - first;
-        if (tr) { if (n > 0) tr->push_back({0, kMain, 0, 1, first, n}); } else launch_tile_gemm_nt(trsm_tasks_ + first, n, 1.0, 0.0, stream_, /*tri_b=*/true);
-    };
-    auto updates = [&](int r0, int r1, StreamId s) {   // update rounds [r0, r1), one launch each
-        for (int r = r0; r < r1; ++r) {
-            const auto [first, n] = upd_rounds_[r];
-            if (tr) { if (n > 0) tr->push_back({0, (uintptr_t)s, 0, 2, first, (int)n}); } else launch_tile_gemm_nt(upd_tasks_ + first, (int)n, -1.0, 1.0, stream_of(s));
+ScheduleInput TilePlan::input() const {
+    return ScheduleInput{lv_, upd_rounds_, n_levels_, n_local_groups_, overlap_, overlap_min_, split_u1_, split_u1_min_, two_side_plan_,
+                         gate_min_, debug_skip_idle_wait_, flow_on_,
+                         {{flow_g0_[0], flow_g1_[0], flow_first_[0], flow_n_[0]}, {flow_g0_[1], flow_g1_[1], flow_first_[1], flow_n_[1]}}};
+}
+
+// The factorisation's launch sequence (factor_schedule), call by call: the list check_schedule proves is the list issued.
+void TilePlan::issue(const std::vector<SchedOp>& ops) {
+    for (const SchedOp& o : ops) {
+        const hipStream_t s = stream_of(o.stream);
+        switch (o.op) {
+            case kOpLaunch:
+                if (o.list == 0) launch_potrf_inv(potrf_tasks_ + o.first, o.count, flag_, s, o.arrive >= 0 ? gate_cnt_ + o.arrive : nullptr);
+                else if (o.list == 1) launch_tile_gemm_nt(trsm_tasks_ + o.first, o.count, 1.0, 0.0, s, /*tri_b=*/true);
+                else if (o.list == 2) launch_tile_gemm_nt(upd_tasks_ + o.first, o.count, -1.0, 1.0, s);
+                else launch_factor_flow(flow_units_ + o.first, o.count, flow_ver_, flag_, flag_ + 1, s, flow_trace_ ? flow_trace_ + 3 * (size_t)o.first : nullptr);
+                break;
+            case kOpRecord: (void)hipEventRecord(ev_[o.event / kLevelEvents][o.event % kLevelEvents], s); break;
+            case kOpWait: (void)hipStreamWaitEvent(s, ev_[o.event / kLevelEvents][o.event % kLevelEvents], 0); break;
+            case kOpGate: launch_gate(gate_cnt_ + o.first, o.count, 150, s); break;
+            case kOpClearGates: launch_clear_i32(gate_cnt_, o.count, s); break;
+            case kOpClearVersions:
+                launch_clear_i32(flow_ver_, n_slots_, s);
+                if (poison_factor_)   // (tests: the version of the first unit's tile starts hugely negative and is never reached)
+                    (void)hipMemsetAsync(flow_ver_ + flow_units_h_[(size_t)o.first].pub, 0x80, sizeof(int), s);
+                break;
         }
-    };
-    auto gate = [&](int lv, StreamId s) { if (!tr) launch_gate(gate_cnt_ + lv + 1, lv_[lv + 2].potrf - lv_[lv + 1].potrf, 150, stream_of(s)); };
-    const bool two = overlap_ && n_levels_ > 2;
-    // the trailing groups [gf, g1) of this phase run as one dataflow launch behind the level launches (build())
-    const int ph = (g0 == n_local_groups_ && g1 == n_levels_ && n_local_groups_ < n_levels_) ? 1 : 0;
-    const int g_end = g1;
-    if (flow_on_ && flow_n_[ph] > 0 && flow_g0_[ph] >= g0 && flow_g1_[ph] == g1) g1 = flow_g0_[ph];
-    if (gate_min_ > 0 && !tr) launch_clear_i32(gate_cnt_, n_levels_ + 1, stream_);
-    int last_a = -1, last_b = -1;   // last levels with work on the side streams A / B that the main stream has not waited for
-    std::vector<int> lastb((size_t)std::max(g1 - g0, 1), -1);   // lastb[lv - g0]: the last level <= lv with U2b2 work on stream B
-    bool u2_pending = false, o_pending = false;   // the previous level group put its U2a / U1o on a side stream (recorded kEvU2 / kEvO)
-    int b2_pending = -1, a_waited = -1;
-    auto a_wait_upto = [&](int lvb) {   // stream A waits for stream B up to level lvb's U2b2 (B runs in order)
-        if (lvb > a_waited) { wait(kSide, lvb, kEvB2); a_waited = lvb; }
-    };
-    for (int lv = g0; lv < g1; ++lv) {
-        potrf(lv);
-        // the panel solves work on the off-diagonal tiles of this level's columns: U1o of the level below must be in
-        if (lv > g0 && o_pending) wait(kMain, lv - 1, kEvO);
-        const int r0 = lv_[lv].upd, rd = lv_[lv].u1o, rs = lv_[lv].u2a, r1 = lv_[lv + 1].upd;
-        int64_t n_u2 = 0, n_o = 0;
-        for (int r = rs; r < r1; ++r) n_u2 += upd_rounds_[r].second;
-        for (int r = rd; r < rs; ++r) n_o += upd_rounds_[r].second;
-        // a cross-stream edge costs a few microseconds in the graph: only worth it when the batch is a real one
-        const bool has_u2 = two && n_u2 >= overlap_min_;
-        const bool has_o = two && split_u1_ && n_o >= split_u1_min_;
-        panel(lv);
-        if (has_u2 || has_o) record(lv, kEvT, kMain);
-        if (has_u2) wait(kSide, lv, kEvT);
-        if (has_o) wait(kSo, lv, kEvT);
-        if (two && lv > g0 && u2_pending) {
-            wait(kMain, lv - 1, kEvU2);
-            if (has_o) wait(kSo, lv - 1, kEvU2);
-        } else if (two && lv > g0 && !debug_skip_idle_wait_) {
-            // Level lv-1 put nothing on the side streams, so there is no kEvU2 of lv-1 to carry "every older side-stream update
-            // precedes U1(lv)": U2b1(lv-2) [targets in level lv+1, stream A] and the U2b2 of levels <= lv-3 [stream B] may
-            // still be at work on the tiles U1(lv) is about to update (and that potrf(lv+1) then reads).  Levels are assigned
-            // by height, so a chain can pass through such a level.  Wait for both side streams outright.
-            if (last_a >= 0) {
-                wait(kMain, last_a, kEvB);
-                if (has_o) wait(kSo, last_a, kEvB);
-                last_a = -1;
-            }
-            if (last_b >= 0) {
-                wait(kMain, last_b, kEvB2);
-                if (has_o) wait(kSo, last_b, kEvB2);
-                last_b = -1;
-            }
-        }
-        updates(r0, rd, kMain);   // U1d: what the next potrf needs
-        updates(rd, rs, has_o ? kSo : kMain);   // U1o: what the next panel solves need, beside the next potrf
-        o_pending = has_o;
-        if (has_o) record(lv, kEvO, kSo);
-        // U2 on two streams of its own.  A (side_): U2a(lv) [targets in level lv+2: what U1(lv+1) waits for], then U2b1(lv)
-        // [level lv+3].  B (side2_): U2b2(lv) [level lv+4 and above: the bulk].  Writers of one target level t, in time:
-        // U2b2(<= t-4) -> U2b1(t-3) -> U2a(t-2) -> U1(t-1); B orders the first among themselves, U2b1(lv) waits for
-        // U2b2(lv-1) [kEvB2], the rest is stream order on A and kEvU2.  U2a(lv+1) thus waits for U2b1(lv) only, not for the
-        // bulk of level lv (on one stream it did, and through it U1d(lv+2) and the potrf behind it).
-        // (only when there is such work: a stream that joins the capture must come back to it with an event)
-        const bool b2_side = has_u2 && two_side_plan_ && r1 > lv_[lv].u2b2;
-        // flood gate: the bulk updates of a big level start when the next level's potrf workgroups sit on their CUs (they
-        // follow U1d on the main stream) -- otherwise the update's grid takes every CU first and the potrf, 124 KB of LDS per
-        // workgroup, waits for it to drain
-        const bool gated = has_u2 && gate_min_ > 0 && n_u2 >= gate_min_ && lv + 1 < g1;
-        if (gated) gate(lv, kSide);
-        // a small U2 stays on the main stream: earlier levels' U2b may still be at work on the same targets over there
-        if (!has_u2 && r1 > rs) {
-            if (last_a >= 0) { wait(kMain, last_a, kEvB); last_a = -1; }
-            if (last_b >= 0) { wait(kMain, last_b, kEvB2); last_b = -1; }
-        }
-        const int ra = lv_[lv].u2b1, rb = lv_[lv].u2b2;
-        const StreamId sa = has_u2 ? kSide : kMain, sb = b2_side ? kSide2 : sa;
-        // U2a(lv) [level lv+2] follows every U2b2 of levels <= lv-2 [their targets start at level lv+2] ...
-        if (has_u2 && lv - 2 >= g0) a_wait_upto(lastb[lv - 2 - g0]);
-        updates(rs, ra, sa);   // U2a
-        u2_pending = has_u2;
-        if (has_u2) record(lv, kEvU2, kSide);   // ... and, in stream order, every earlier update on A
-        if (b2_side) {
-            wait(kSide2, lv, kEvT);
-            if (gated) gate(lv, kSide2);
-        }
-        if (has_u2 && lv - 1 >= g0) a_wait_upto(lastb[lv - 1 - g0]);   // ... and U2b1(lv) [level lv+3] every U2b2 of levels <= lv-1
-        updates(ra, rb, sa);   // U2b1
-        updates(rb, r1, sb);   // U2b2
-        if (has_u2) { record(lv, kEvB, kSide); last_a = lv; }
-        if (b2_side) { record(lv, kEvB2, kSide2); last_b = lv; }
-        lastb[lv - g0] = b2_pending = b2_side ? lv : b2_pending;
-    }
-    if (g1 > g0 && o_pending) wait(kMain, g1 - 1, kEvO);
-    // join: the last side-stream work precedes whatever follows on the main stream
-    if (last_a >= 0) wait(kMain, last_a, kEvB);
-    if (last_b >= 0) wait(kMain, last_b, kEvB2);
-    if (g1 < g_end) {   // every update the level launches add to the region's tiles is in: the joins above
-        if (tr) { tr->push_back({0, kMain, 0, 3, flow_first_[ph], flow_n_[ph]}); return; }
-        launch_clear_i32(flow_ver_, n_slots_, stream_);
-        if (poison_factor_)   // (tests: the version of the first unit's tile starts hugely negative and is never reached)
-            (void)hipMemsetAsync(flow_ver_ + flow_units_h_[(size_t)flow_first_[ph]].pub, 0x80, sizeof(int), stream_);
-        launch_factor_flow(flow_units_ + flow_first_[ph], flow_n_[ph], flow_ver_, flag_, flag_ + 1, stream_,
-                           flow_trace_ ? flow_trace_ + 3 * (size_t)flow_first_[ph] : nullptr);
     }
 }
 
@@ -1188,90 +1085,8 @@ hipError_t TilePlan::read_flow_trace(std::vector<FactorUnit>* units, std::vector
     return hipMemcpy(stamps->data(), flow_trace_, 3 * n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
 }
 
-std::vector<SchedOp> TilePlan::schedule_trace(int phase) {
-    std::vector<SchedOp> ops;
-    sched_trace_ = &ops;
-    if (phase == 0) enqueue_factor(0, n_local_groups_);
-    else enqueue_factor(n_local_groups_, n_levels_);
-    sched_trace_ = nullptr;
-    return ops;
-}
-
-int TilePlan::check_schedule(const std::vector<SchedOp>& ops, std::string* first_violation) const {
-    // vector clocks over the streams that appear: clock[s] = how many launches of stream s happen before this point
-    std::vector<uintptr_t> streams;
-    auto sid = [&](uintptr_t s) { for (size_t i = 0; i < streams.size(); ++i) if (streams[i] == s) return (int)i; streams.push_back(s); return (int)streams.size() - 1; };
-    for (const SchedOp& o : ops) (void)sid(o.stream);
-    const int S = (int)streams.size();
-    typedef std::vector<int> Clock;
-    std::vector<Clock> now((size_t)S, Clock((size_t)S, 0));     // per stream: what precedes its next call
-    std::vector<std::pair<uintptr_t, Clock>> events;             // last record of each event
-    struct Access { int launch; bool write; };
-    struct Launch { int stream, pos; Clock before; const SchedOp* op; };
-    std::vector<Launch> launches;
-    std::vector<std::pair<const double*, Access>> acc;
-    int bad = 0;
-    auto complain = [&](const std::string& m) { if (bad++ == 0 && first_violation) *first_violation = m; };
-    auto describe = [&](const Launch& l) {
-        static const char* const names[] = {"potrf", "panel solves", "updates", "dataflow launch"};
-        return std::string(names[l.op->list]) + " [" + std::to_string(l.op->first) + ", +" + std::to_string(l.op->count) + ") on stream " + std::to_string(l.stream);
-    };
-    for (const SchedOp& o : ops) {
-        const int s = sid(o.stream);
-        if (o.op == 1) {
-            bool found = false;
-            for (auto& e : events) if (e.first == o.event) { e.second = now[(size_t)s]; found = true; }
-            if (!found) events.push_back({o.event, now[(size_t)s]});
-        } else if (o.op == 2) {
-            bool found = false;
-            for (const auto& e : events)
-                if (e.first == o.event) { for (int k = 0; k < S; ++k) now[(size_t)s][(size_t)k] = std::max(now[(size_t)s][(size_t)k], e.second[(size_t)k]); found = true; }
-            if (!found) complain("a stream waits for an event that was never recorded");
-        } else {
-            const int li = (int)launches.size();
-            launches.push_back({s, now[(size_t)s][(size_t)s] + 1, now[(size_t)s], &o});
-            now[(size_t)s][(size_t)s] += 1;
-            // the tiles the launch touches; inside one launch no tile may be written twice or read and written by two tasks
-            std::vector<std::pair<const double*, int>> local;   // (tile, +1 write / 0 read) of this launch
-            auto touch = [&](const double* t, bool w) { acc.push_back({t, {li, w}}); local.push_back({t, w ? 1 : 0}); };
-            for (int64_t q = o.first; q < o.first + o.count; ++q) {
-                if (o.list == 0) { touch(potrf_h_[(size_t)q].A, true); touch(potrf_h_[(size_t)q].Linv, true); }
-                else if (o.list == 1) { touch(trsm_h_[(size_t)q].C, true); touch(trsm_h_[(size_t)q].B, false); }
-                else if (o.list == 2) { touch(reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(upd_h_[(size_t)q].C) & ~uintptr_t(7)), true); touch(upd_h_[(size_t)q].A, false); touch(upd_h_[(size_t)q].B, false); }
-                else {   // the dataflow launch orders its own units (version counters): one writer of everything it touches
-                    const FactorUnit& u = flow_units_h_[(size_t)q];
-                    touch(u.C, true);
-                    if ((u.kind & 15) == 0) touch(u.A, true);
-                }
-            }
-            if (o.list != 3) {
-                std::sort(local.begin(), local.end());
-                for (size_t i = 0; i < local.size();) {
-                    size_t j = i; int writes = 0;
-                    while (j < local.size() && local[j].first == local[i].first) writes += local[j++].second;
-                    if (writes >= 1 && j - i >= 2) { complain("two tasks of one launch touch a tile that one of them writes: " + describe(launches.back())); break; }
-                    i = j;
-                }
-            }
-        }
-    }
-    // every pair of launches on one tile with a writer among them must be ordered
-    std::sort(acc.begin(), acc.end(), [](const std::pair<const double*, Access>& a, const std::pair<const double*, Access>& b) {
-        return a.first != b.first ? a.first < b.first : a.second.launch < b.second.launch; });
-    for (size_t i = 0; i < acc.size();) {
-        size_t j = i;
-        while (j < acc.size() && acc[j].first == acc[i].first) ++j;
-        for (size_t a = i; a < j; ++a)
-            for (size_t b = a + 1; b < j; ++b) {
-                const Access &x = acc[a].second, &y = acc[b].second;
-                if (x.launch == y.launch || (!x.write && !y.write)) continue;
-                const Launch &lx = launches[(size_t)x.launch], &ly = launches[(size_t)y.launch];   // lx was issued first
-                if (ly.before[(size_t)lx.stream] < lx.pos)
-                    complain("unordered accesses to one tile: " + describe(lx) + " and " + describe(ly));
-            }
-        i = j;
-    }
-    return bad;
+std::vector<SchedOp> TilePlan::schedule_trace(int phase) const {
+    return phase == 0 ? factor_schedule(input(), 0, n_local_groups_) : factor_schedule(input(), n_local_groups_, n_levels_);
 }
 
 void TilePlan::top_slot_ranges(std::pair<int64_t, int64_t> out[2]) const {

@@ -403,16 +403,24 @@ int apexgpu_owned_landmarks(apexgpu_solver* h, uint8_t* mask);
  * status. */
 int apexgpu_debug_partition(int nt, const uint8_t* present, int world, int* owner_out);
 /* Host-only proof that the factorisation's launch sequence is race free for one tile structure (no device is touched):
- * the plan is built on made-up addresses, TilePlan::enqueue_factor records its launches / event records / stream waits
- * instead of issuing them, and every two launches that touch one tile with a writer among them must be ordered by stream
- * order + event edges; tasks of one launch must not share a written tile.  present: lower-triangular nt x nt structure in
+ * the plan is built on made-up addresses, factor_schedule() lists the launches / event records / stream waits that
+ * TilePlan::enqueue_factor would issue, and every two launches that touch one tile with a writer among them must be ordered by
+ * stream order + event edges; tasks of one launch must not share a written tile.  present: lower-triangular nt x nt structure in
  * the final tile order.  opts = {two_side, update_overlap (>1: minimum batch), split_u1, flood_gate, factor_flow,
  * factor_flow_rows, tests: bring back the round-3 idle-level bug, tests: drop that stream wait of phase 0 (-1: none)}.
- * out = {calls, launches, violations of phase 0 (local level groups / everything), violations of phase 1 (shared top of a
+ * out = {launches + event records + stream waits, launches, violations of phase 0 (local level groups / everything), violations of phase 1 (shared top of a
  * distributed plan), dataflow units, level groups inside dataflow launches, stream waits, 1 if a wait was dropped}.
  * Returns the number of level groups (>= 0) or an error; msg receives the first violation.  (round-3 advice: the U2 split
  * had dropped the edge behind a level without side-stream work; the checker finds it on the advisor's pattern.) */
 int apexgpu_debug_check_schedule(int nt, const uint8_t* present, int world, int rank, const int opts[8], int64_t out[8], char* msg, int msg_len);
+/* The same plan's launch sequence of one phase (0 / 1 as above), call by call, in issue order: rows[6 * i ..] = {op, stream,
+ * event, list, first, count} of call i.  op: 0 launch of tile tasks [first, first + count) of list 0 potrf / 1 panel solves /
+ * 2 updates / 3 dataflow units; 1 event record, 2 stream waits for event (event = level group * 5 + {0 after the panel
+ * solves, 1 U2a, 2 U1o, 3 U2b, 4 U2b2}); 3 flood gate on arrival counter `first`, `count` arrivals expected; 4 clear of
+ * `count` arrival counters; 5 clear of the dataflow launch's version counters.  stream: 0 main, 1 side, 2 second side, 3 U1o;
+ * list = -1 and event = 0 where unused.  opts[7] is ignored.  At most max_rows rows are written (rows may be NULL when
+ * max_rows is 0); returns the number of calls or an error. */
+int apexgpu_debug_schedule_ops(int nt, const uint8_t* present, int world, int rank, const int opts[8], int phase, int64_t* rows, int max_rows);
 /* Tests only: the single-GPU tile Cholesky (TilePlan) on a matrix the caller chooses, in the caller's tile order (nothing is
  * reordered).  present: lower-triangular nt x nt 0/1 structure (I >= J); opts[8] = {graphs, factor_flow (max columns; 0 off,
  * < 0 by cost model), factor_flow_rows, tri_dataflow, update_overlap (> 1: minimum batch), split_u1 (0 off, else minimum

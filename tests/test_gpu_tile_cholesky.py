@@ -248,6 +248,50 @@ def test_fill_patterns_never_read_their_fill_tiles(name):
             assert np.array_equal(r["L"], run0["L"]) and np.array_equal(r["Linv"], run0["Linv"]), opts
 
 
+_SCHED_ON = dict(two_side=2, update_overlap=1, split_u1=1, flood_gate=2)
+_sched_case = {}
+
+
+def _schedule_case():
+    """grid(4, 4) (fill, 16 level groups), its matrix and the bits of the fully serial schedule: computed once."""
+    if not _sched_case:
+        pat = tr.grid(4, 4)
+        A = tr.dominant_case(pat, np.random.default_rng(51))
+        with _mk(pat, update_overlap=0, flood_gate=0, two_side=0, factor_flow=0, graphs=0) as dev:
+            ref = _run(dev, A, z=False)
+        assert ref["failed"] == 0
+        _sched_case.update(pat=pat, A=A, ref=ref)
+    return _sched_case["pat"], _sched_case["A"], _sched_case["ref"]
+
+
+@pytest.mark.parametrize("factor_flow", [0, 64])
+@pytest.mark.parametrize("graphs", [0, 1])
+def test_issued_schedule_gives_the_serial_bits(graphs, factor_flow):
+    """Every kind of call of the factorisation's schedule (factor_schedule.h) played by TilePlan::issue, directly and through a
+    captured graph.  On grid(4, 4) with every switch on and gates from two tasks up, the level launches use all four streams,
+    event records and waits, gates on both side streams and the clear of the arrival counters (factor_flow 0); factor_flow 64
+    takes all groups into the dataflow launch behind the clear of its version counters -- read off
+    apexgpu_debug_schedule_ops below.  L and Linv carry the bits of the serial schedule (main stream only, no gate, no
+    graph), and a second factorisation on the same handle (the graph's replay) gives them again."""
+    from apex_solver_amd import capi
+
+    pat, A, ref = _schedule_case()
+    rows = capi.schedule_ops(pat, two_side=2, overlap=1, split_u1=1, flood_gate=2, factor_flow=factor_flow)
+    kinds, launches = set(rows[:, 0].tolist()), rows[rows[:, 0] == 0]
+    if factor_flow == 0:
+        assert kinds == {0, 1, 2, 3, 4} and set(launches[:, 1].tolist()) == {0, 1, 2, 3} and set(launches[:, 3].tolist()) == {0, 1, 2}
+        assert set(rows[rows[:, 0] == 3][:, 1].tolist()) == {1, 2}
+    else:
+        assert kinds == {0, 4, 5} and launches[:, 3].tolist() == [3]
+    with _mk(pat, graphs=graphs, factor_flow=factor_flow, **_SCHED_ON) as dev:
+        assert (dev.flow_units > 0) == (factor_flow != 0)
+        for again in (0, 1):
+            run = _run(dev, A, z=False)
+            assert run["failed"] == 0
+            for k in ("L", "Linv"):
+                assert np.array_equal(run[k], ref[k]), (k, graphs, factor_flow, again)
+
+
 def test_padding_rows_are_identity():
     """The last tile with 37 padding rows: add_diag makes them identity; x is 0 there; the rest meets the bounds."""
     pat = tr.band(3)
