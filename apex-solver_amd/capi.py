@@ -27,7 +27,7 @@ SYMBOLS = (
     "apexgpu_get_schur", "apexgpu_camera_covariance", "apexgpu_covariance_stats", "apexgpu_landmark_covariance", "apexgpu_landmark_covariance_stats", "apexgpu_get_landmark_blocks", "apexgpu_get_hessian_csc", "apexgpu_debug_invert_blocks", "apexgpu_debug_pair_lists", "apexgpu_debug_pair_lists_queued", "apexgpu_debug_pair_lists_queued_dc", "apexgpu_debug_host_structure", "apexgpu_setup_times", "apexgpu_schur_matvec", "apexgpu_set_option", "apexgpu_enable_stage_timing", "apexgpu_reset_stage_times",
     "apexgpu_stage_times", "apexgpu_info", "apexgpu_variant_info", "apexgpu_variant_costs", "apexgpu_trim_host_cache", "apexgpu_host_cache_bytes", "apexgpu_counters", "apexgpu_debug_get_pair_records", "apexgpu_get_unique_id", "apexgpu_comm_init", "apexgpu_comm_init_shm", "apexgpu_set_shard", "apexgpu_shard_range",
     "apexgpu_debug_lockstep_solve", "apexgpu_export_step", "apexgpu_owned_landmarks", "apexgpu_debug_partition", "apexgpu_debug_check_schedule",
-    "apexgpu_debug_schedule_ops",
+    "apexgpu_debug_schedule_ops", "apexgpu_debug_sinv_lists", "apexgpu_debug_sinv_lists_direct",
     "apexgpu_debug_tiles_create", "apexgpu_debug_tiles_pattern", "apexgpu_debug_tiles_set", "apexgpu_debug_tiles_factor",
     "apexgpu_debug_tiles_solve", "apexgpu_debug_tiles_matvec", "apexgpu_debug_tiles_pcg", "apexgpu_debug_tiles_get", "apexgpu_debug_tiles_destroy",
     "apexgpu_bal_open", "apexgpu_bal_close", "apexgpu_bal_last_error", "apexgpu_bal_sizes", "apexgpu_bal_raw",
@@ -131,6 +131,8 @@ def load() -> C.CDLL:
     L.apexgpu_debug_partition.argtypes = [C.c_int, vp, C.c_int, vp]
     L.apexgpu_debug_check_schedule.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_char_p, C.c_int]
     L.apexgpu_debug_schedule_ops.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int]
+    L.apexgpu_debug_sinv_lists.argtypes = [C.c_int, vp, vp, C.c_int, vp, vp]
+    L.apexgpu_debug_sinv_lists_direct.argtypes = [C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_char_p, C.c_int]
     L.apexgpu_debug_tiles_create.argtypes = [C.c_int, C.c_int, vp, vp, C.POINTER(vp)]
     L.apexgpu_debug_tiles_pattern.argtypes = [vp, vp, vp]
     L.apexgpu_debug_tiles_set.argtypes = [vp, vp, C.c_int, dbl, C.c_int]
@@ -138,7 +140,7 @@ def load() -> C.CDLL:
     L.apexgpu_debug_tiles_solve.argtypes = [vp, C.c_int, vp, vp]
     L.apexgpu_debug_tiles_matvec.argtypes = [vp, vp, vp]
     L.apexgpu_debug_tiles_pcg.argtypes = [vp, vp, C.c_int, dbl, vp, C.POINTER(C.c_int), vp]
-    L.apexgpu_debug_tiles_get.argtypes = [vp, C.c_int, vp]
+    L.apexgpu_debug_tiles_get.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int)]
     L.apexgpu_debug_tiles_destroy.argtypes = [vp]
     L.apexgpu_debug_tiles_destroy.restype = None
     L.apexgpu_set_column_scaling.argtypes = [vp, vp]
@@ -282,6 +284,42 @@ def schedule_ops(present: np.ndarray, phase: int = 0, world: int = 1, rank: int 
     if n and L.apexgpu_debug_schedule_ops(*args, rows.ctypes.data_as(C.c_void_p), n) != n:
         raise LinAlgError(-6, "apexgpu_debug_schedule_ops")
     return rows
+
+
+def _sinv_rows(call, what, msg=None):
+    counts = np.zeros(4, dtype=np.int64)
+    n = call(None, 0, ptr(counts))
+    if n < 0:
+        raise LinAlgError(n, what + (": " + msg.value.decode() if msg is not None else ""))
+    rows = np.zeros((n, 6), dtype=np.int64)
+    if n and call(ptr(rows), n, ptr(counts)) != n:
+        raise LinAlgError(-6, what)
+    return rows, counts
+
+
+def sinv_lists(present: np.ndarray, with_slots: bool = False):
+    """Host only: the task lists of the selected inversion of the single-rank plan of one tile structure, tiles by name
+    (apexgpu_debug_sinv_lists): (rows, counts) with rows {kind, group, C.array, C.tile, first, count} per task, then
+    {3, A.array, A.tile, B.array, B.tile, op} per product; counts = products per kind, Y tiles of the largest group.
+    with_slots: (rows, counts, slot), slot the plan's (nt, nt) slot map."""
+    L = load()
+    pr = np.ascontiguousarray(present, dtype=np.uint8)
+    slot = np.zeros(pr.shape, dtype=np.int32)
+    out = _sinv_rows(lambda rows, n, counts: L.apexgpu_debug_sinv_lists(pr.shape[0], ptr(pr), rows, n, counts, ptr(slot)), "apexgpu_debug_sinv_lists")
+    return out + (slot,) if with_slots else out
+
+
+def sinv_lists_direct(slot: np.ndarray, groups):
+    """The same from a caller-given slot map ((nt, nt), -1 where absent) and level groups (lists of tile columns, leaves
+    first), with no plan in between (apexgpu_debug_sinv_lists_direct); a refusal raises InvalidState with the builder's
+    message."""
+    L = load()
+    sl = np.ascontiguousarray(slot, dtype=np.int32)
+    gp = np.cumsum([0] + [len(g) for g in groups]).astype(np.int32)
+    gc = np.array([c for g in groups for c in g] + [0], dtype=np.int32)   # (never empty: a pointer to pass)
+    msg = C.create_string_buffer(512)
+    return _sinv_rows(lambda rows, n, counts: L.apexgpu_debug_sinv_lists_direct(sl.shape[0], ptr(sl), len(groups), ptr(gp), ptr(gc), rows, n, counts, msg, 512),
+                      "apexgpu_debug_sinv_lists_direct", msg)
 
 
 HOST_STRUCTURE_STATS = ("tile_rows", "hub_cameras", "border_tiles", "touched_tiles", "tiles", "etree_levels", "top_columns",
@@ -499,10 +537,14 @@ class TileCholesky:
 
     def get(self, which: str) -> np.ndarray:
         """"tiles" (raw), "L" (the tiles with the diagonal tiles masked to their lower triangle), "Linv" ((nt, 144, 144)),
-        "Z" (the selected inverse on the pattern of L)."""
+        "Z" (the selected inverse on the pattern of L; self.z_recomputed then says whether this call computed it or found
+        it current)."""
         k = {"tiles": 0, "L": 0, "Linv": 1, "Z": 2}[which]
         out = np.empty(((self.nt if k == 1 else self.n_slots), self.nb, self.nb))
-        self._check(self.L.apexgpu_debug_tiles_get(self.h, k, ptr(out)), "get")
+        rec = C.c_int(0)
+        self._check(self.L.apexgpu_debug_tiles_get(self.h, k, ptr(out), C.byref(rec)), "get")
+        if k == 2:
+            self.z_recomputed = bool(rec.value)
         if which == "L":   # a factorised diagonal tile keeps the assembled matrix in its 16 x 16 blocks right of the diagonal
             low = np.tril(np.ones((self.nb, self.nb), dtype=bool))
             for K in range(self.nt):

@@ -11,6 +11,7 @@
 
 #include "ba_structure.h"
 #include "pg_solver.h"
+#include "sinv_lists.h"
 #include "solver.h"
 #ifdef APEX_WITH_RCCL
 #include <rccl/rccl.h>
@@ -55,10 +56,11 @@ template <typename S>
 static int covariance_stats(S* s, double out[6], double* group_ms, int group_cap) {
     if (!out) return APEXGPU_ERR_INVALID_INPUT;
     const apex::TilePlan& tp = s->plan();
+    const apex::SelectedInverse& inv = tp.inverse();
     int64_t y = 0, zo = 0, zd = 0;
-    tp.covariance_op_counts(&y, &zo, &zd);
-    const std::vector<double>& ms = tp.covariance_group_ms();
-    out[0] = (double)tp.covariance_bytes(); out[1] = (double)y; out[2] = (double)zo; out[3] = (double)zd; out[4] = tp.n_levels();
+    inv.op_counts(&y, &zo, &zd);
+    const std::vector<double>& ms = inv.group_ms();
+    out[0] = (double)inv.bytes(); out[1] = (double)y; out[2] = (double)zo; out[3] = (double)zd; out[4] = tp.n_levels();
     int n = 0;
     if (group_ms)
         for (; n < group_cap && n < (int)ms.size(); ++n) group_ms[n] = ms[n];
@@ -346,6 +348,58 @@ int apexgpu_debug_schedule_ops(int nt, const uint8_t* present, int world, int ra
         r[0] = o.op; r[1] = (int64_t)o.stream; r[2] = (int64_t)o.event; r[3] = o.list; r[4] = o.first; r[5] = o.count;
     }
     return (int)ops.size();
+    });
+}
+
+// rows of apexgpu_debug_sinv_lists / _direct (include/apexgpu.h)
+static int sinv_rows(const apex::SinvLists& l, int64_t* rows, int max_rows, int64_t counts[4]) {
+    const size_t n = l.tasks.size() + l.prods.size();
+    size_t i = 0;
+    for (size_t g = 0; g < l.groups.size(); ++g)
+        for (int k = 0; k < 3; ++k)
+            for (int t = l.groups[g][k]; t < l.groups[g][k + 1] && i < (size_t)max_rows; ++t, ++i) {
+                const apex::SinvTaskH& tk = l.tasks[t];
+                int64_t* r = rows + 6 * i;
+                r[0] = k; r[1] = (int64_t)g; r[2] = tk.C.array; r[3] = tk.C.tile; r[4] = tk.first; r[5] = tk.count;
+            }
+    for (size_t p = 0; p < l.prods.size() && l.tasks.size() + p < (size_t)max_rows; ++p) {
+        const apex::SinvProdH& pr = l.prods[p];
+        int64_t* r = rows + 6 * (l.tasks.size() + p);
+        r[0] = 3; r[1] = pr.A.array; r[2] = pr.A.tile; r[3] = pr.B.array; r[4] = pr.B.tile; r[5] = pr.op;
+    }
+    if (counts) { counts[0] = l.n[0]; counts[1] = l.n[1]; counts[2] = l.n[2]; counts[3] = l.y_max; }
+    return (int)n;
+}
+
+int apexgpu_debug_sinv_lists(int nt, const uint8_t* present, int64_t* rows, int max_rows, int64_t counts[4], int32_t* slot_out) {
+    if (nt <= 0 || !present || max_rows < 0 || (max_rows > 0 && !rows)) return APEXGPU_ERR_INVALID_INPUT;
+    return guarded([&]() -> int {
+    apex::TilePlan tp;
+    if (!tp.build_host_only(nt, std::vector<uint8_t>(present, present + (size_t)nt * nt)).empty()) return APEXGPU_ERR_INVALID_STATE;
+    if (slot_out) memcpy(slot_out, tp.slot_host(), (size_t)nt * nt * sizeof(int32_t));
+    apex::SinvLists lists;
+    if (!apex::build_sinv_lists(nt, tp.slot_host(), tp.group_columns(), &lists).empty()) return APEXGPU_ERR_INVALID_STATE;
+    return sinv_rows(lists, rows, max_rows, counts);
+    });
+}
+
+int apexgpu_debug_sinv_lists_direct(int nt, const int32_t* slot, int n_groups, const int32_t* group_ptr, const int32_t* group_cols,
+                                    int64_t* rows, int max_rows, int64_t counts[4], char* msg, int msg_len) {
+    if (nt <= 0 || !slot || n_groups < 0 || !group_ptr || !group_cols || max_rows < 0 || (max_rows > 0 && !rows)) return APEXGPU_ERR_INVALID_INPUT;
+    return guarded([&]() -> int {
+    std::vector<std::vector<int>> groups(n_groups);
+    for (int g = 0; g < n_groups; ++g) {
+        if (group_ptr[g] < 0 || group_ptr[g + 1] < group_ptr[g]) return APEXGPU_ERR_INVALID_INPUT;
+        for (int i = group_ptr[g]; i < group_ptr[g + 1]; ++i) {
+            if (group_cols[i] < 0 || group_cols[i] >= nt || slot[(size_t)group_cols[i] * nt + group_cols[i]] < 0) return APEXGPU_ERR_INVALID_INPUT;
+            groups[g].push_back(group_cols[i]);
+        }
+    }
+    apex::SinvLists lists;
+    const std::string e = apex::build_sinv_lists(nt, slot, groups, &lists);
+    if (msg && msg_len > 0) snprintf(msg, (size_t)msg_len, "%s", e.c_str());
+    if (!e.empty()) return APEXGPU_ERR_INVALID_STATE;
+    return sinv_rows(lists, rows, max_rows, counts);
     });
 }
 

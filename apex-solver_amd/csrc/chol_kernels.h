@@ -41,12 +41,6 @@ void launch_tile_add_diag(double* tiles, const int* diag_slot, int n_valid, int 
 void launch_vec_select(int n, const double* in, const int* cls, int mask, double* out, hipStream_t s);
 void launch_vec_merge(int n, const double* src, const int* cls, int mask, double* dst, hipStream_t s);
 void launch_tile_scale_sym(const SymTile* list, int n, double* tiles, const double* scale /* n_pad */, hipStream_t s);
-
-// ---- selected inversion (TilePlan::covariance_blocks) ----
-// one launch: nine workgroups per task (one per 48 x 48 block of C); no atomics, a fixed summation order
-void launch_sinv_gemm(const SinvTask* tasks, int n_tasks, const SinvProd* prods, hipStream_t s);
-// out[v][a][b] = (Z[p + a][p + b] + Z[p + b][p + a]) / 2, p = pos[v] (a d x d block inside one diagonal tile of Z)
-void launch_sinv_diag_blocks(const double* z, const int* diag_slot, const int64_t* pos, int64_t n_var, int d, double* out, hipStream_t s);
 void launch_pcg_init(int n, const double* diag, const double* b, double* pre, double* x, double* r, double* z, double* p,
                      hipStream_t s);
 void launch_dot(int n, const double* a, const double* b, double* out, hipStream_t s);

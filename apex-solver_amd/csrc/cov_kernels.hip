@@ -1,7 +1,7 @@
 // cov_kernels.hip -- marginal landmark covariances from the selected inverse of S.
 //
 // With V_l^-1 the (damped, gated, scaled) 3 x 3 inverse the Schur complement used, W_i = Jc_i^T Jl_i the camera-landmark
-// block of observation i, and Z = S^-1 on the tile pattern of the factor (TilePlan::covariance_blocks / ensure_inverse), the
+// block of observation i, and Z = S^-1 on the tile pattern of the factor (SelectedInverse::blocks / ensure, tile_sinv.h), the
 // landmark block of the inverse of the factorised matrix is
 //     Sigma_ll = D_l^-1 (Hinv_l + sum_{i,j in obs(l)} U_i^T Z_{c(i) c(j)} U_j) D_l^-1,     U_i = D_c W_i Hinv_l
 // where Hinv_l = D_l V_l^-1 D_l is the landmark record (ba_kernels.h) and D the Jacobi scaling (identity when off).  This is the

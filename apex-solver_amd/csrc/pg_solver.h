@@ -61,7 +61,7 @@ class PoseGraphSolver : public TileBackend {
     // cholesky.rs:240-256, core/problem.rs:1128-1147): the 6 x 6 diagonal blocks of the inverse of the matrix the LAST
     // solve_augmented factorised -- J^T J + lambda I at that solve's point and lambda, in the scaled variables when Jacobi
     // scaling was on (what get_hessian(lambda) returns at the same point) -- by selected inversion of the tile factor
-    // (TilePlan::covariance_blocks).  out[n_v][6][6], caller's vertex order, columns as get_hessian's.  kInvalidState when
+    // (SelectedInverse::blocks, tile_sinv.h).  out[n_v][6][6], caller's vertex order, columns as get_hessian's.  kInvalidState when
     // no valid factor is held (no solve yet, or an export / assembly since).
     int covariance(double* out);
 

@@ -520,7 +520,7 @@ int PoseGraphSolver::covariance(double* out) {
     std::vector<int64_t> pos(n_v_);
     for (int64_t v = 0; v < n_v_; ++v) pos[v] = dof_ * (int64_t)vmap_[v];
     std::string err;
-    const int rc = tp_.covariance_blocks(pos.data(), n_v_, dof_, out, &err);
+    const int rc = tp_.inverse().blocks(pos.data(), n_v_, dof_, out, &err);
     if (rc == 1) return fail(kInvalidState, "covariance: " + err);
     if (rc != 0) return fail(kDeviceError, "covariance: " + err);
     return kOk;

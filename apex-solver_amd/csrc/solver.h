@@ -73,7 +73,7 @@ class Solver : public TileBackend {
     // Marginal camera covariances: the 9 x 9 camera blocks of (H + lambda I)^-1 -- by the Schur-complement identity exactly
     // the diagonal blocks of S^-1, S the reduced camera matrix the LAST solve_augmented factorised (variant 0 only: at that
     // solve's point, lambda and Jacobi scaling, plus its ladder regularisation if one was needed, apexgpu_info[4]) -- by
-    // selected inversion of the tile factor (TilePlan::covariance_blocks; the reference computes the whole inverse densely,
+    // selected inversion of the tile factor (SelectedInverse::blocks, tile_sinv.h; the reference computes the whole inverse densely,
     // cholesky.rs:240-256).  out[n_cam][9][9], caller's camera order, pose 6 then intrinsics 3 (get_schur's layout).
     // d_c = 6: the intrinsics rows of get_schur's matrix are lambda on the diagonal, so theirs are 1 / lambda, no cross terms.
     // kInvalidState: no valid factor (no direct solve yet, a PCG / matrix-free solve or an export since), several ranks.

@@ -1555,7 +1555,7 @@ int Solver::camera_covariance(double* out) {
     for (int64_t c = 0; c < n_cam_; ++c) pos[c] = (int64_t)cmap_[c] * dc_;
     std::vector<double> blk((size_t)n_cam_ * dc_ * dc_);
     std::string err;
-    const int rc = tp_.covariance_blocks(pos.data(), n_cam_, dc_, blk.data(), &err);
+    const int rc = tp_.inverse().blocks(pos.data(), n_cam_, dc_, blk.data(), &err);
     if (rc == 1) return fail(kInvalidState, "covariance: " + err + " (the Iterative and matrix-free variants have no factor)");
     if (rc != 0) return fail(kDeviceError, "covariance: " + err);
     for (int64_t c = 0; c < n_cam_; ++c) {
@@ -1614,7 +1614,7 @@ int Solver::landmark_covariance(double* out) {
     HIP_TRY(hipSetDevice(device_));
     std::string err;
     bool recomputed = false;
-    int rc = tp_.ensure_inverse(&recomputed, &err);
+    int rc = tp_.inverse().ensure(&recomputed, &err);
     if (rc == 1) return fail(kInvalidState, "landmark covariance: " + err + " (the Iterative and matrix-free variants have no factor)");
     if (rc != 0) return fail(kDeviceError, "landmark covariance: " + err);
     if (!lc_out_ && (rc = lc_setup()) != kOk) return rc;
@@ -1624,14 +1624,14 @@ int Solver::landmark_covariance(double* out) {
     v.cam_scale = factor_scaled_ ? cam_scale_ : nullptr;
     v.pt_scale = factor_scaled_ ? pt_scale_ : nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timed = tp_.covariance_timing();
+    const bool timed = tp_.inverse().timing();
     if (timed) {
         HIP_TRY(hipEventCreate(&ev[0]));
         HIP_TRY(hipEventCreate(&ev[1]));
     }
     HIP_TRY(hipMemsetAsync(lc_err_, 0, sizeof(int), stream_));
     if (timed) HIP_TRY(hipEventRecord(ev[0], stream_));
-    launch_landmark_cov(dc_, v, hinv_, tp_.inverse_map(), lc_lists_, lc_n_small_, lc_lists_ + lc_n_small_, lc_n_large_, lc_out_, lc_err_, stream_);
+    launch_landmark_cov(dc_, v, hinv_, tp_.inverse().map(), lc_lists_, lc_n_small_, lc_lists_ + lc_n_small_, lc_n_large_, lc_out_, lc_err_, stream_);
     if (timed) HIP_TRY(hipEventRecord(ev[1], stream_));
     hipError_t e = hipGetLastError();
     std::vector<double> blk(9 * (size_t)n_pt_);

@@ -42,7 +42,7 @@ class TileBackend : public LmBackend {
     void set_one_wait(bool on) { one_wait_ = on; }
     void set_eager_step_eval(bool on) { eager_eval_ = on; }
     void set_nd(bool on, int leaf) { use_nd_ = on; if (leaf > 0) nd_leaf_ = leaf; }
-    void enable_covariance_timing(bool on) { tp_.enable_covariance_timing(on); }
+    void enable_covariance_timing(bool on) { tp_.inverse().enable_timing(on); }
     void enable_stage_timing(bool on) { timer_.enable(on); }
     void enable_stage_timing_only(uint32_t stage_mask) { timer_.enable_only(stage_mask); }
     void reset_stage_times() { timer_.reset(); }

@@ -179,8 +179,9 @@ int apexgpu_debug_tiles_pcg(apexgpu_tiles* h, const double* rhs, int max_iter, d
     return hip_rc(e != hipSuccess ? e : se);
 }
 
-int apexgpu_debug_tiles_get(apexgpu_tiles* h, int which, double* out) {
+int apexgpu_debug_tiles_get(apexgpu_tiles* h, int which, double* out, int* recomputed_out) {
     if (!h || !out || which < 0 || which > 2) return APEXGPU_ERR_INVALID_INPUT;
+    if (recomputed_out) *recomputed_out = 0;
     if (hipSetDevice(h->device) != hipSuccess) return APEXGPU_ERR_DEVICE;
     apex::TilePlan& tp = h->plan;
     const double* src = tp.tiles();
@@ -189,10 +190,12 @@ int apexgpu_debug_tiles_get(apexgpu_tiles* h, int which, double* out) {
     if (which == 2) {
         bool recomputed = false;
         std::string err;
-        const int rc = tp.ensure_inverse(&recomputed, &err);
+        apex::SelectedInverse& inv = tp.inverse();
+        const int rc = inv.ensure(&recomputed, &err);
         if (rc == 1) return APEXGPU_ERR_INVALID_STATE;
         if (rc != 0) return APEXGPU_ERR_DEVICE;
-        src = tp.inverse_map().tiles;
+        src = inv.map().tiles;
+        if (recomputed_out) *recomputed_out = recomputed ? 1 : 0;
     }
     hipError_t e = hipMemcpyAsync(out, src, count * kTile * sizeof(double), hipMemcpyDeviceToHost, h->stream);
     const hipError_t se = hipStreamSynchronize(h->stream);

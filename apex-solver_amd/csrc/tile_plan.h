@@ -6,6 +6,7 @@
 //   build()   symbolic Cholesky fill, elimination-tree levels, slot map, batched task lists, uploads
 //   factor() / solve()   level-scheduled tile Cholesky and triangular solves, replayed as hipGraphs
 //   pcg()     Jacobi-preconditioned CG on the unfactored tiles (solve_with_pcg, explicit_schur.rs:639-756)
+//   inverse() the selected inversion of the held factor (marginal covariances): a class of its own, tile_sinv.h
 //
 // Distributed factorisation (set_partition(rank, world) before build()): the elimination tree is cut below its top
 // separators into `world` groups of independent subtrees.  A rank factorises the columns of ITS subtrees only (the
@@ -28,6 +29,7 @@
 #include "chol_kernels.h"
 #include "device_buffer.h"
 #include "factor_schedule.h"
+#include "tile_sinv.h"
 
 namespace apex {
 
@@ -54,10 +56,6 @@ struct TilePlanMemory {
     DeviceBuffer<int> sym_row_ptr_;
     DeviceBuffer<SymEntry> sym_entries_;
     DeviceBuffer<double> sym_part_, row_dot_, blk_part_, scal_;
-    // selected inversion (covariance_blocks): allocated on the first call
-    DeviceBuffer<double> z_, y_;
-    DeviceBuffer<SinvTask> sinv_tasks_;
-    DeviceBuffer<SinvProd> sinv_prods_;
 };
 
 class TilePlan : private TilePlanMemory {
@@ -124,6 +122,7 @@ class TilePlan : private TilePlanMemory {
     int64_t n_slots() const { return n_slots_; }
     int64_t n_touched_slots() const { return n_touched_; }  // tiles non-zero before fill come first
     int n_levels() const { return n_levels_; }
+    const std::vector<std::vector<int>>& group_columns() const { return group_cols_; }   // per level group, execution order: its tile columns
     // tile operations of one factorisation: potrf+inverse, panel products, trailing updates (each 2*144^3 flop for the last two)
     void op_counts(int64_t* potrf, int64_t* trsm, int64_t* upd) const { *potrf = n_potrf_; *trsm = n_trsm_; *upd = n_upd_; }
     double* tiles() const { return tiles_; }
@@ -208,32 +207,15 @@ class TilePlan : private TilePlanMemory {
     hipError_t pcg(const double* rhs, double* x, double* work, int max_iter, double tol, int* iters);
     const double* pcg_scalars() const { return scal_; }   // device: {rz_old, p.Ap, r.r, r.z, frozen} as the last pcg() left them (tests)
 
-    // ---- marginal covariances: selected inversion of the factor (block Takahashi recurrence) ----
     // The tiles hold a valid factor L only between a successful single-rank factorisation + sweeps (the CALLER says so with
     // set_factor_valid(true) once it has read the pivot flags) and the next write of the tiles: zero_tiles, add_diag,
-    // scale_sym, factor, a new build() clear the flag.
-    void set_factor_valid(bool on) { factor_valid_ = on; z_current_ = false; }
+    // scale_sym, factor, pcg, a new build() clear the flag.  Every such write and every factor declared valid starts a new
+    // epoch, by which the selected inversion knows whether its Z is of the factor now held.
+    void set_factor_valid(bool on) { factor_valid_ = on; ++factor_epoch_; }
     bool factor_valid() const { return factor_valid_; }
-    // Z = (L L^T)^-1 on the tile pattern of L, root group first; with j's off-diagonal rows I_j and Y_r = L_rj Linv_j:
-    //     Z_rj = - sum_{s in I_j} Z~_rs Y_s    (r in I_j; Z~_rs = Z_rs for r >= s, else Z_sr^T)
-    //     Z_jj = Linv_j^T Linv_j - sum_{r in I_j} Y_r^T Z_rj
-    // then out[v] = the d x d diagonal block of Z at n_pad position pos[v] (symmetrised).  L is left as it is.  The Z tiles
-    // (as many as L's), the Y tiles of the largest level group and the lists are allocated on the first call only and live
-    // until release().  Returns 0, 1 (refused: distributed plan or no valid factor; *err says why) or 2 (HIP error).  Syncs.
-    int covariance_blocks(const int64_t* pos, int64_t n_var, int d, double* out, std::string* err);
-    size_t covariance_bytes() const { return sinv_bytes_; }   // device memory the first covariance_blocks() added (0 before)
-    // per level group (execution order, root group first): milliseconds of its three launches in the last covariance_blocks()
-    // -- recorded only while enabled (events between the groups)
-    void enable_covariance_timing(bool on) { sinv_timing_ = on; }
-    const std::vector<double>& covariance_group_ms() const { return sinv_group_ms_; }
-    // tile products of one selected inversion: Y, off-diagonal Z, diagonal Z (each 2*144^3 flop)
-    void covariance_op_counts(int64_t* y, int64_t* zoff, int64_t* zdiag) const { *y = sinv_n_[0]; *zoff = sinv_n_[1]; *zdiag = sinv_n_[2]; }
-    // Z of the held factor for a caller that reads Z itself (the landmark covariances): reuses Z when a covariance_blocks() or
-    // ensure_inverse() has computed it since the factor became valid (*recomputed = false), else runs the recurrence without
-    // the diagonal gather.  Z stays current until the factor flag is cleared or set again.  Returns as covariance_blocks.
-    int ensure_inverse(bool* recomputed, std::string* err);
-    TileMap inverse_map() const { return TileMap{z_, slot_, nt_}; }   // Z, addressed as tilemap() addresses S (valid after ensure_inverse)
-    bool covariance_timing() const { return sinv_timing_; }
+    // marginal covariances of the held factor (tile_sinv.h), on a view of the plan as it is at this call
+    SelectedInverse& inverse();
+    const SelectedInverse& inverse() const { return inverse_; }   // its counters and times
 
    private:
     using Cols = std::vector<std::vector<int>>;
@@ -337,22 +319,11 @@ class TilePlan : private TilePlanMemory {
     // level lists, kFlowFirstWriter in the dataflow units -- and does not read its target (beta = 0): the 0.63 GB of fill tiles
     // of final-13682 are then neither cleared before a factorisation nor read by those updates (round 5).
     bool first_ok_ = false;   // (this plan qualifies: not distributed, has fill tiles, no dataflow launch over shared top groups)
-    // selected inversion (covariance_blocks): built on the first call
-    std::string sinv_setup();
-    void sinv_release();
-    int sinv_check(std::string* err) const;   // 0, or 1 with the refusal
-    // the recurrence (set-up on the first call) enqueued, with timing events when enabled (0 or 2); after the caller's
-    // synchronisation sinv_collect reads and destroys them
-    int sinv_enqueue(std::vector<hipEvent_t>* ev, std::string* err);
-    void sinv_collect(std::vector<hipEvent_t>& ev, bool ok);
-    bool factor_valid_ = false;
-    bool z_current_ = false;   // z_ holds the selected inverse of the factor now in the tiles
-    struct SinvGroup { int task[4]; };   // [task[k], task[k + 1]): the Y, off-diagonal Z, diagonal Z launches of one level group
-    std::vector<SinvGroup> sinv_groups_;   // root group first
-    int64_t sinv_n_[3] = {0, 0, 0};
-    size_t sinv_bytes_ = 0;
-    bool sinv_timing_ = false;
-    std::vector<double> sinv_group_ms_;
+    void tiles_written() { factor_valid_ = false; ++factor_epoch_; }   // the one place (with set_factor_valid) that touches these two
+    bool factor_valid_{false};
+    uint64_t factor_epoch_ = 0;
+    Cols group_cols_;   // the level groups' columns in execution order (host_lists)
+    SelectedInverse inverse_;
     static constexpr int kTriInline = 8;       // (swept 0 / 4 / 8 / 16 / 32 / all: profiles/r05_sweep_tri_inline.txt) the dataflow sweeps: in levels of at most this many columns a block's solve task forms its last-arriving product itself (FlowTask::mat2)
     bool use_graphs_ = true;
 };

@@ -87,7 +87,8 @@ void TilePlan::release() {
         if (graph_exec_[i]) { (void)hipGraphExecDestroy(graph_exec_[i]); graph_exec_[i] = nullptr; }
         graph_failed_[i] = false;
     }
-    sinv_release();
+    inverse_.release();
+    tiles_written();
     static_cast<TilePlanMemory&>(*this) = TilePlanMemory();   // frees every device and pinned block of the plan
     n_flow_tasks_ = 0; flow_n_[0] = flow_n_[1] = 0; flow_on_ = true; flow_gave_up_ = false;
     flow_err_host_dev_ = nullptr;
@@ -356,6 +357,7 @@ std::string TilePlan::build_host_only(int nt, const std::vector<uint8_t>& presen
 // The lists of a plan, in this order: the level task lists, the two sweeps, the PCG lists, the dataflow launches, the first writers.
 std::string TilePlan::host_lists(const std::vector<uint8_t>& present, const Cols& col_rows, const Groups& g, double* tiles, double* linv, Lists* out) {
     n_levels_ = (int)g.cols.size(); n_local_groups_ = g.n_local;
+    group_cols_ = g.cols;
     level_lists(col_rows, g, tiles, linv);
     sweep_lists(col_rows, g, tiles, linv, out);
     sym_lists(present, out);
@@ -897,7 +899,7 @@ std::string TilePlan::upload(const Lists& lists) {
 #undef TP_TRY
 
 hipError_t TilePlan::zero_tiles(bool own_touched_only, bool skip_fill) {
-    factor_valid_ = z_current_ = false;
+    tiles_written();
     const size_t te = (size_t)kNB * kNB * sizeof(double);
     hipError_t e = hipSuccess;
     auto clear = [&](int64_t first, int64_t count) {
@@ -919,11 +921,11 @@ hipError_t TilePlan::zero_tiles(bool own_touched_only, bool skip_fill) {
 }
 
 void TilePlan::add_diag(int n_valid, double add_valid, double pad_value) {
-    factor_valid_ = z_current_ = false;
+    tiles_written();
     launch_tile_add_diag(tiles_, diag_slot_, n_valid, (int)n_pad(), add_valid, pad_value, stream_);
 }
 
-void TilePlan::scale_sym(const double* scale) { factor_valid_ = z_current_ = false; launch_tile_scale_sym(sym_tiles_, n_sym_tiles_, tiles_, scale, stream_); }
+void TilePlan::scale_sym(const double* scale) { tiles_written(); launch_tile_scale_sym(sym_tiles_, n_sym_tiles_, tiles_, scale, stream_); }
 
 void TilePlan::diag(double* out) const { launch_tile_diag(tiles_, diag_slot_, nt_, out, stream_); }
 
@@ -1095,7 +1097,7 @@ void TilePlan::top_slot_ranges(std::pair<int64_t, int64_t> out[2]) const {
 }
 
 void TilePlan::factor_phase(int phase) {
-    factor_valid_ = z_current_ = false;
+    tiles_written();
     if (phase == 0) { if (!run_graph(kGraphFactor, nullptr, nullptr, nullptr)) enqueue_factor(0, n_local_groups_); }
     else if (!run_graph(kGraphFactorTop, nullptr, nullptr, nullptr)) enqueue_factor(n_local_groups_, n_levels_);
 }
@@ -1105,7 +1107,7 @@ void TilePlan::solve_phase(int phase, const double* rhs, double* x, double* work
 }
 
 hipError_t TilePlan::factor(int* failed_at, bool defer_flags) {
-    factor_valid_ = z_current_ = false;
+    tiles_written();
     if (distributed()) {
         if (!comm_.sum || !comm_.max_int) return hipErrorNotInitialized;  // a distributed plan needs its communicator
         factor_phase(0);
@@ -1212,7 +1214,7 @@ void TilePlan::sym_matvec(const double* x, double* y) {
 // also made on the device (k_pcg_close_iteration): the speculative iteration behind a met test changes nothing, and x, the
 // iteration count and every scalar are those of the loop that waited every time.
 hipError_t TilePlan::pcg(const double* rhs, double* x, double* work, int max_iter, double tol, int* iters) {
-    factor_valid_ = z_current_ = false;
+    tiles_written();
     const int n = (int)n_pad();
     double *dg = work, *pre = work + n, *r = work + 2 * (size_t)n, *z = work + 3 * (size_t)n, *p = work + 4 * (size_t)n,
            *ap = work + 5 * (size_t)n;
@@ -1253,190 +1255,15 @@ hipError_t TilePlan::pcg(const double* rhs, double* x, double* work, int max_ite
     return hipStreamSynchronize(stream_);   // (the speculative iteration, if any, has drained: x is final)
 }
 
-// ---- selected inversion (tile_plan.h, covariance_blocks) ----------------------------------------------------------------
-void TilePlan::sinv_release() {
-    z_.reset(); y_.reset(); sinv_tasks_.reset(); sinv_prods_.reset();   // (null z_: sinv_enqueue sets up again)
-    sinv_groups_.clear(); sinv_group_ms_.clear();
-    sinv_n_[0] = sinv_n_[1] = sinv_n_[2] = 0;
-    sinv_bytes_ = 0;
-    factor_valid_ = z_current_ = false;
-}
-
-// The lists of the recurrence from the slot map and the level groups of the factorisation (nothing of the step path changes):
-// per group, root group first, three task lists -- Y_r = L_rj Linv_j, the off-diagonal Z_rj, the diagonal Z_jj -- whose
-// products point into L, Linv, Z and the group's Y tiles.  The columns of a group are independent: I_j holds ancestors of j
-// only, and those sit in higher groups, whose Z is complete when the group runs.
-std::string TilePlan::sinv_setup() {
-    Cols col_rows(nt_);
-    for (int K = 0; K < nt_; ++K)
-        for (int I = K + 1; I < nt_; ++I)
-            if (slot(I, K) >= 0) col_rows[K].push_back(I);
-    // Z~_rs for r, s in I_j must be a tile of L: tile-level symbolic fill makes I_j a clique (the rows of column j merge into
-    // its parent's column, and so on up the tree) -- checked, not assumed
-    for (int K = 0; K < nt_; ++K) {
-        const auto& rows = col_rows[K];
-        for (size_t a = 0; a < rows.size(); ++a)
-            for (size_t b = 0; b < a; ++b)
-                if (slot(rows[a], rows[b]) < 0)
-                    return "tile (" + std::to_string(rows[a]) + ", " + std::to_string(rows[b]) + ") of column " + std::to_string(K) +
-                           "'s rows is not a tile of the factor: the tile structure is not closed under fill";
-    }
-    const Groups g = level_groups(col_rows);
-    int64_t y_max = 0;
-    for (const auto& cols : g.cols) {
-        int64_t ny = 0;
-        for (int K : cols) ny += (int64_t)col_rows[K].size();
-        y_max = std::max(y_max, ny);
-    }
-    const size_t te = (size_t)kNB * kNB;
-    const size_t need = ((size_t)n_slots_ + (size_t)std::max<int64_t>(y_max, 1)) * te * sizeof(double);
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    if ((double)need > 0.9 * (double)free_b)
-        return "the covariance tiles need " + std::to_string(need / 1e9) + " GB; only " + std::to_string(free_b / 1e9) + " GB free";
-    std::vector<SinvTask> tasks;
-    std::vector<SinvProd> prods;
-    // (the lists point at the final addresses of Z and Y: allocate first)
-    hipError_t e = z_.alloc((size_t)n_slots_ * te);
-    if (e == hipSuccess) e = y_.alloc((size_t)std::max<int64_t>(y_max, 1) * te);
-    if (e != hipSuccess) { sinv_release(); return std::string("HIP error allocating the covariance tiles: ") + hipGetErrorString(e); }
-    auto Lt = [&](int I, int J) { return tile_at(tiles_, slot(I, J)); };
-    auto Zt = [&](int I, int J) { return tile_at(z_, slot(I, J)); };
-    sinv_groups_.clear();
-    for (int gi = (int)g.cols.size() - 1; gi >= 0; --gi) {
-        const auto& cols = g.cols[gi];
-        SinvGroup sg;
-        std::vector<int64_t> ybase(cols.size());
-        int64_t ny = 0;
-        for (size_t c = 0; c < cols.size(); ++c) { ybase[c] = ny; ny += (int64_t)col_rows[cols[c]].size(); }
-        auto Yt = [&](size_t c, size_t a) { return tile_at(y_, ybase[c] + (int64_t)a); };
-        sg.task[0] = (int)tasks.size();
-        for (size_t c = 0; c < cols.size(); ++c) {   // Y_r = L_rj Linv_j
-            const int j = cols[c];
-            for (size_t a = 0; a < col_rows[j].size(); ++a) {
-                tasks.push_back({Yt(c, a), (int)prods.size(), 1});
-                prods.push_back({Lt(col_rows[j][a], j), tile_at(linv_, j), 0, 0});
-            }
-        }
-        sg.task[1] = (int)tasks.size();
-        for (size_t c = 0; c < cols.size(); ++c) {   // Z_rj = - sum_s Z~_rs Y_s
-            const int j = cols[c];
-            const auto& rows = col_rows[j];
-            for (size_t a = 0; a < rows.size(); ++a) {
-                const int r = rows[a];
-                tasks.push_back({Zt(r, j), (int)prods.size(), (int)rows.size()});
-                for (size_t b = 0; b < rows.size(); ++b) {
-                    const int s = rows[b];
-                    if (r >= s) prods.push_back({Zt(r, s), Yt(c, b), kSinvNeg, 0});
-                    else prods.push_back({Zt(s, r), Yt(c, b), kSinvNeg | kSinvTransA, 0});
-                }
-            }
-        }
-        sg.task[2] = (int)tasks.size();
-        for (size_t c = 0; c < cols.size(); ++c) {   // Z_jj = Linv_j^T Linv_j - sum_r Y_r^T Z_rj
-            const int j = cols[c];
-            const auto& rows = col_rows[j];
-            tasks.push_back({Zt(j, j), (int)prods.size(), 1 + (int)rows.size()});
-            prods.push_back({tile_at(linv_, j), tile_at(linv_, j), kSinvTransA, 0});
-            for (size_t a = 0; a < rows.size(); ++a) prods.push_back({Yt(c, a), Zt(rows[a], j), kSinvNeg | kSinvTransA, 0});
-        }
-        sg.task[3] = (int)tasks.size();
-        sinv_n_[0] += sg.task[1] - sg.task[0];
-        sinv_groups_.push_back(sg);
-    }
-    sinv_n_[1] = sinv_n_[2] = 0;
-    for (const SinvGroup& sg : sinv_groups_) {
-        for (int t = sg.task[1]; t < sg.task[2]; ++t) sinv_n_[1] += tasks[t].count;
-        for (int t = sg.task[2]; t < sg.task[3]; ++t) sinv_n_[2] += tasks[t].count;
-    }
-    e = sinv_tasks_.upload(tasks);
-    if (e == hipSuccess) e = sinv_prods_.upload(prods);
-    if (e != hipSuccess) { sinv_release(); return std::string("HIP error uploading the covariance lists: ") + hipGetErrorString(e); }
-    sinv_bytes_ = ((size_t)n_slots_ + (size_t)std::max<int64_t>(y_max, 1)) * te * sizeof(double) + tasks.size() * sizeof(SinvTask) +
-                  prods.size() * sizeof(SinvProd);
-    return "";
-}
-
-int TilePlan::sinv_check(std::string* err) const {
-    if (distributed() || part_world_ > 1) { *err = "covariances of a distributed plan are not supported (single rank only)"; return 1; }
-    if (!factor_valid_ || !tiles_) {
-        *err = "the tiles hold no valid factor: covariances need a successful direct (Cholesky) solve, and nothing may re-assemble the tiles in between";
-        return 1;
-    }
-    return 0;
-}
-
-int TilePlan::sinv_enqueue(std::vector<hipEvent_t>* ev, std::string* err) {
-    if (!z_) {
-        const std::string e = sinv_setup();
-        if (!e.empty()) { *err = e; return 2; }
-    }
-    if (sinv_timing_) {
-        ev->assign(sinv_groups_.size() + 1, nullptr);
-        for (hipEvent_t& x : *ev) {
-            const hipError_t e = hipEventCreate(&x);
-            if (e != hipSuccess) { sinv_collect(*ev, false); *err = std::string("HIP error in hipEventCreate: ") + hipGetErrorString(e); return 2; }
-        }
-        (void)hipEventRecord((*ev)[0], stream_);
-    }
-    for (size_t gi = 0; gi < sinv_groups_.size(); ++gi) {
-        const SinvGroup& sg = sinv_groups_[gi];
-        for (int k = 0; k < 3; ++k) launch_sinv_gemm(sinv_tasks_ + sg.task[k], sg.task[k + 1] - sg.task[k], sinv_prods_, stream_);
-        if (sinv_timing_) (void)hipEventRecord((*ev)[gi + 1], stream_);
-    }
-    return 0;
-}
-
-void TilePlan::sinv_collect(std::vector<hipEvent_t>& ev, bool ok) {
-    if (ev.empty()) return;
-    sinv_group_ms_.assign(ev.size() - 1, 0.0);
-    for (size_t gi = 0; gi + 1 < ev.size(); ++gi) {
-        float ms = 0.0f;
-        if (ok && ev[gi] && ev[gi + 1] && hipEventElapsedTime(&ms, ev[gi], ev[gi + 1]) == hipSuccess) sinv_group_ms_[gi] = ms;
-    }
-    for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
-    ev.clear();
-}
-
-int TilePlan::covariance_blocks(const int64_t* pos, int64_t n_var, int d, double* out, std::string* err) {
-    if (const int rc = sinv_check(err)) return rc;
-    for (int64_t v = 0; v < n_var; ++v)
-        if (pos[v] < 0 || pos[v] + d > n_pad() || pos[v] / kNB != (pos[v] + d - 1) / kNB) { *err = "variable block outside one diagonal tile"; return 1; }
-    std::vector<hipEvent_t> ev;
-    if (const int rc = sinv_enqueue(&ev, err)) return rc;
-    DeviceBuffer<int64_t> dpos;
-    DeviceBuffer<double> dout;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = dpos.alloc((size_t)std::max<int64_t>(n_var, 0));
-    if (e == hipSuccess) e = dout.alloc((size_t)std::max<int64_t>(n_var * d * d, 0));
-    if (e == hipSuccess && n_var > 0) e = hipMemcpyAsync(dpos, pos, (size_t)n_var * sizeof(int64_t), hipMemcpyHostToDevice, stream_);
-    if (e == hipSuccess) {
-        launch_sinv_diag_blocks(z_, diag_slot_, dpos, n_var, d, dout, stream_);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && n_var > 0) e = hipMemcpyAsync(out, dout, (size_t)n_var * d * d * sizeof(double), hipMemcpyDeviceToHost, stream_);
-    const hipError_t se = hipStreamSynchronize(stream_);
-    if (e == hipSuccess) e = se;
-    sinv_collect(ev, e == hipSuccess);
-    if (e != hipSuccess) { *err = std::string("HIP error in covariance_blocks: ") + hipGetErrorString(e); return 2; }
-    z_current_ = true;
-    return 0;
-}
-
-int TilePlan::ensure_inverse(bool* recomputed, std::string* err) {
-    *recomputed = false;
-    if (const int rc = sinv_check(err)) return rc;
-    if (z_current_) return 0;
-    std::vector<hipEvent_t> ev;
-    if (const int rc = sinv_enqueue(&ev, err)) return rc;
-    hipError_t e = hipGetLastError();
-    const hipError_t se = hipStreamSynchronize(stream_);
-    if (e == hipSuccess) e = se;
-    sinv_collect(ev, e == hipSuccess);
-    if (e != hipSuccess) { *err = std::string("HIP error in ensure_inverse: ") + hipGetErrorString(e); return 2; }
-    z_current_ = true;
-    *recomputed = true;
-    return 0;
+SelectedInverse& TilePlan::inverse() {
+    SinvPlanView v;
+    v.tiles = tiles_; v.linv = linv_; v.slot = slot_; v.diag_slot = diag_slot_;
+    v.nt = nt_; v.n_slots = n_slots_; v.stream = stream_;
+    v.slot_host = slot_h_.data(); v.group_cols = &group_cols_;
+    v.distributed = distributed() || part_world_ > 1;
+    v.factor_valid = factor_valid_; v.factor_epoch = factor_epoch_;
+    inverse_.bind(v);
+    return inverse_;
 }
 
 }  // namespace apex

@@ -1,6 +1,6 @@
 // tile_tasks.h -- the task records of the tile Cholesky / triangular-solve / PCG / selected-inversion kernels: plain structs
-// that the host builds into lists (TilePlan) and the kernels read (chol_kernels.hip).  No HIP type: host-only code
-// (factor_schedule.cpp) includes this file alone.
+// that the host builds into lists (TilePlan, SelectedInverse) and the kernels read (chol_kernels.hip, sinv_kernels.hip).  No HIP
+// type: host-only code (factor_schedule.cpp, sinv_lists.cpp) includes this file alone.
 #pragma once
 
 namespace apex {
@@ -61,7 +61,7 @@ struct SymEntry {  // one tile of block-row I of the symmetric tile matrix
 
 struct SymTile { int slot, I, J; };  // a structurally non-zero tile (I >= J) of S
 
-// ---- selected inversion (TilePlan::covariance_blocks) ----
+// ---- selected inversion (tile_sinv.h; the lists by name: sinv_lists.h) ----
 constexpr int kSinvTransA = 1, kSinvTransB = 2, kSinvNeg = 4;   // SinvProd::op bits
 struct SinvProd {   // one term op(A) op(B) of a sum (kSinvNeg: subtracted); A, B are 144 x 144 row-major tiles
     const double* A;

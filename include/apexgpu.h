@@ -421,6 +421,23 @@ int apexgpu_debug_check_schedule(int nt, const uint8_t* present, int world, int 
  * list = -1 and event = 0 where unused.  opts[7] is ignored.  At most max_rows rows are written (rows may be NULL when
  * max_rows is 0); returns the number of calls or an error. */
 int apexgpu_debug_schedule_ops(int nt, const uint8_t* present, int world, int rank, const int opts[8], int phase, int64_t* rows, int max_rows);
+/* Host arithmetic only: the task lists of the selected inversion (marginal covariances) of the single-rank plan of a tile
+ * structure, tiles by name.  Rows of six integers, every task first, then every product, both in list order:
+ *   task     {kind, group, C.array, C.tile, first, count}: kind 0 Y / 1 off-diagonal Z / 2 diagonal Z; group counted from the root
+ *            group (0); C := the sum of the products [first, first + count) of the product list, in that order
+ *   product  {3, A.array, A.tile, B.array, B.tile, op}: the term op(A) op(B); op bit 0 A transposed, bit 1 B transposed, bit 2 subtracted
+ * array: 0 L (tile = slot), 1 the inverses of L's diagonal tiles (tile = tile column), 2 Z (slot), 3 Y (index inside the
+ * group's block of Y tiles).  Groups run in order, inside a group kind 0, then 1, then 2, each as one launch.  counts (may be
+ * NULL) = {Y products, off-diagonal Z products, diagonal Z products, Y tiles of the largest group}; slot_out (may be NULL)
+ * receives the plan's slot map, slot_out[I * nt + J], -1 outside the filled pattern.  At most max_rows rows are written (rows
+ * may be NULL when max_rows is 0); returns the number of rows or an error. */
+int apexgpu_debug_sinv_lists(int nt, const uint8_t* present, int64_t* rows, int max_rows, int64_t counts[4], int32_t* slot_out);
+/* The same lists from a slot map and level groups the caller gives (no plan: this is how a pattern that symbolic fill would
+ * never produce reaches the builder's check).  slot[I * nt + J] for I >= J, -1 where the tile is absent; group g holds the tile
+ * columns group_cols[group_ptr[g] .. group_ptr[g + 1]), groups in the execution order of the factorisation (leaves first).
+ * APEXGPU_ERR_INVALID_STATE with the refusal in msg when the rows of a column are not pairwise tiles of the pattern. */
+int apexgpu_debug_sinv_lists_direct(int nt, const int32_t* slot, int n_groups, const int32_t* group_ptr, const int32_t* group_cols,
+                                    int64_t* rows, int max_rows, int64_t counts[4], char* msg, int msg_len);
 /* Tests only: the single-GPU tile Cholesky (TilePlan) on a matrix the caller chooses, in the caller's tile order (nothing is
  * reordered).  present: lower-triangular nt x nt 0/1 structure (I >= J); opts[8] = {graphs, factor_flow (max columns; 0 off,
  * < 0 by cost model), factor_flow_rows, tri_dataflow, update_overlap (> 1: minimum batch), split_u1 (0 off, else minimum
@@ -449,8 +466,9 @@ int apexgpu_debug_tiles_matvec(apexgpu_tiles* h, const double* x, double* y);
 int apexgpu_debug_tiles_pcg(apexgpu_tiles* h, const double* rhs, int max_iter, double tol, double* x, int* iters, double scal_out[5]);
 /* which 0: the tiles (L after a factor; a diagonal tile's 16 x 16 blocks right of its diagonal keep the assembled matrix),
  * out[n_slots][144][144]; 1: the inverses of L's diagonal tiles, out[nt][144][144]; 2: the selected inverse Z on the
- * pattern of L (computed first where needed; needs a valid factor), out[n_slots][144][144] */
-int apexgpu_debug_tiles_get(apexgpu_tiles* h, int which, double* out);
+ * pattern of L (computed first unless it is still that of the held factor; needs a valid factor), out[n_slots][144][144].
+ * recomputed (may be NULL): 1 when this call ran the selected inversion, else 0 */
+int apexgpu_debug_tiles_get(apexgpu_tiles* h, int which, double* out, int* recomputed);
 void apexgpu_debug_tiles_destroy(apexgpu_tiles* h);
 /* Host arithmetic only: the sorted camera-pair lists of the default Schur reduction for an observation list, with the
  * caller's camera order and a dense tile map (slot(I, J) = I (I + 1) / 2 + J).  counts[4] = {slots, chunks, blocks, tasks};

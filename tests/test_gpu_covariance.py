@@ -1,4 +1,4 @@
-"""Marginal covariances by selected inversion of the tile factor (TilePlan::covariance_blocks): the diagonal blocks of the
+"""Marginal covariances by selected inversion of the tile factor (SelectedInverse::blocks): the diagonal blocks of the
 inverse of the matrix the last direct solve factorised, against dense numpy inverses of the matrices the exports return.
 Tolerances per 6 x 6 / 9 x 9 block (relative Frobenius): 1e-10 at lambda = 1e4, 1e-7 at lambda = 1e-3 -- the step-parity
 bounds of the suite."""

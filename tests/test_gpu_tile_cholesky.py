@@ -322,6 +322,47 @@ def test_padding_rows_are_identity():
             assert tr.solve_ratio(A1, L, x[k], b[k], 3) <= 1.0
 
 
+def test_selected_inverse_is_current_exactly_until_the_tiles_are_written():
+    """grid(4, 4): 16 tile columns, fill, several level groups, Z_sr^T products.  Z read twice is computed once; every write of
+    the tiles the handle can reach -- set, a factorisation that fails on a non-positive pivot, pcg -- voids it (InvalidState);
+    a fresh factor of the same tiles recomputes it to the same bits."""
+    from apex_solver_amd.capi import LinAlgError
+
+    pat = tr.grid(4, 4)
+    A = tr.dominant_case(pat, np.random.default_rng(101))
+    bad = {k: v.copy() for k, v in A.items()}
+    bad[(0, 0)][0, 0] = -A[(0, 0)][0, 0]   # the first pivot of tile column 0
+    with _mk(pat) as dev:
+        T = tr.touched_array(A, dev)
+
+        def refactor():
+            dev.set(T)
+            assert dev.factor() == 0
+            z = dev.get("Z")
+            assert dev.z_recomputed
+            return z
+
+        def void():
+            with pytest.raises(LinAlgError) as e:
+                dev.get("Z")
+            assert e.value.kind == "InvalidState"
+
+        Z0 = refactor()
+        assert dev.levels > 2 and tr.has_fill(pat)
+        Z1 = dev.get("Z")
+        assert not dev.z_recomputed and np.array_equal(Z1, Z0)
+        dev.set(T)
+        void()
+        assert np.array_equal(refactor(), Z0)
+        dev.set(tr.touched_array(bad, dev))
+        assert dev.factor() == 1
+        void()
+        assert np.array_equal(refactor(), Z0)
+        dev.pcg(np.ones(dev.n_pad), 1, 1e-8)
+        void()
+        assert np.array_equal(refactor(), Z0)
+
+
 @pytest.mark.parametrize("factor_flow", [0, -1])
 def test_indefinite_pivot_is_reported_in_its_column(factor_flow):
     """One clearly negative pivot (exactly <= -1e-3 of its diagonal) in tile column K of a chain: failed_at == K + 1 (the
