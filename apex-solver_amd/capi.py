@@ -27,7 +27,7 @@ SYMBOLS = (
     "apexgpu_get_schur", "apexgpu_camera_covariance", "apexgpu_covariance_stats", "apexgpu_landmark_covariance", "apexgpu_landmark_covariance_stats", "apexgpu_get_landmark_blocks", "apexgpu_get_hessian_csc", "apexgpu_debug_invert_blocks", "apexgpu_debug_pair_lists", "apexgpu_debug_pair_lists_queued", "apexgpu_debug_pair_lists_queued_dc", "apexgpu_debug_host_structure", "apexgpu_setup_times", "apexgpu_schur_matvec", "apexgpu_set_option", "apexgpu_enable_stage_timing", "apexgpu_reset_stage_times",
     "apexgpu_stage_times", "apexgpu_info", "apexgpu_variant_info", "apexgpu_variant_costs", "apexgpu_trim_host_cache", "apexgpu_host_cache_bytes", "apexgpu_counters", "apexgpu_debug_get_pair_records", "apexgpu_get_unique_id", "apexgpu_comm_init", "apexgpu_comm_init_shm", "apexgpu_set_shard", "apexgpu_shard_range",
     "apexgpu_debug_lockstep_solve", "apexgpu_export_step", "apexgpu_owned_landmarks", "apexgpu_debug_partition", "apexgpu_debug_check_schedule",
-    "apexgpu_debug_schedule_ops", "apexgpu_debug_sinv_lists", "apexgpu_debug_sinv_lists_direct",
+    "apexgpu_debug_schedule_ops", "apexgpu_debug_plan_lists", "apexgpu_debug_sinv_lists", "apexgpu_debug_sinv_lists_direct",
     "apexgpu_debug_tiles_create", "apexgpu_debug_tiles_pattern", "apexgpu_debug_tiles_set", "apexgpu_debug_tiles_factor",
     "apexgpu_debug_tiles_solve", "apexgpu_debug_tiles_matvec", "apexgpu_debug_tiles_pcg", "apexgpu_debug_tiles_get", "apexgpu_debug_tiles_destroy",
     "apexgpu_bal_open", "apexgpu_bal_close", "apexgpu_bal_last_error", "apexgpu_bal_sizes", "apexgpu_bal_raw",
@@ -131,6 +131,7 @@ def load() -> C.CDLL:
     L.apexgpu_debug_partition.argtypes = [C.c_int, vp, C.c_int, vp]
     L.apexgpu_debug_check_schedule.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_char_p, C.c_int]
     L.apexgpu_debug_schedule_ops.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int]
+    L.apexgpu_debug_plan_lists.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int]
     L.apexgpu_debug_sinv_lists.argtypes = [C.c_int, vp, vp, C.c_int, vp, vp]
     L.apexgpu_debug_sinv_lists_direct.argtypes = [C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_char_p, C.c_int]
     L.apexgpu_debug_tiles_create.argtypes = [C.c_int, C.c_int, vp, vp, C.POINTER(vp)]
@@ -283,6 +284,30 @@ def schedule_ops(present: np.ndarray, phase: int = 0, world: int = 1, rank: int 
     rows = np.zeros((n, 6), dtype=np.int64)
     if n and L.apexgpu_debug_schedule_ops(*args, rows.ctypes.data_as(C.c_void_p), n) != n:
         raise LinAlgError(-6, "apexgpu_debug_schedule_ops")
+    return rows
+
+
+# the tables of apexgpu_debug_plan_lists (include/apexgpu.h), in its numbering: name, columns of a row
+PLAN_TABLES = (("scalars", 23), ("slots", 3), ("columns", 4), ("owner_ranges", 5), ("levels", 9), ("fwd_cut", 2), ("upd_rounds", 2),
+               ("bwd_step", 1), ("potrf", 5), ("panel", 7), ("upd", 7), ("fwd", 6), ("bwd", 6), ("flow_fwd", 10), ("flow_bwd", 10),
+               ("units", 16), ("sym_row_ptr", 1), ("sym_entries", 3), ("sym_tiles", 3), ("group_cols", 2))
+
+
+def plan_lists(present: np.ndarray, which: str, world: int = 1, rank: int = 0, two_side: int = 1, overlap: int = 1, split_u1: int = 4,
+               flood_gate: int = 256, factor_flow: int = -1, factor_flow_rows: int = 24) -> np.ndarray:
+    """Host only: one table of the plan's structure and task lists, tiles by name (apexgpu_debug_plan_lists; `which` a name of
+    PLAN_TABLES; options as check_schedule)."""
+    L = load()
+    pr = np.ascontiguousarray(present, dtype=np.uint8)
+    w = [n for n, _ in PLAN_TABLES].index(which)
+    opts = np.array([two_side, overlap, split_u1, flood_gate, factor_flow, factor_flow_rows, 0, -1], dtype=np.int32)
+    args = (pr.shape[0], pr.ctypes.data_as(C.c_void_p), int(world), int(rank), opts.ctypes.data_as(C.c_void_p), w)
+    n = L.apexgpu_debug_plan_lists(*args, None, 0)
+    if n < 0:
+        raise LinAlgError(n, "apexgpu_debug_plan_lists")
+    rows = np.zeros((n, PLAN_TABLES[w][1]), dtype=np.int64)
+    if n and L.apexgpu_debug_plan_lists(*args, rows.ctypes.data_as(C.c_void_p), n) != n:
+        raise LinAlgError(-6, "apexgpu_debug_plan_lists")
     return rows
 
 

@@ -3,9 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tile_tasks.h"   // kNB
+
 namespace apex {
 
-constexpr int kNB = 144;          // S tile edge: 16*9 = 24*6, multiple of the 16-wide f64 MFMA
 constexpr int kScatterCap = 128;  // observations one Schur-scatter workgroup stages in LDS
 constexpr int kScatterBlk = 64;   // block size used to split landmarks with more observations
 

@@ -13,7 +13,7 @@
 #include "ba_kernels.h"
 #include "host_parallel.h"
 #include "schur_pairs.h"
-#include "tile_plan.h"
+#include "plan_lists.h"
 
 namespace apex {
 
@@ -56,18 +56,21 @@ struct BaHostStructure {
     PairLists pl;                      // the Schur reduction's task lists (schur_pairs.h)
     double seconds[6] = {0, 0, 0, 0, 0, 0};  // order + tile structure | sharding + lists | tile plan | Schur lists | uploads | total
 
-    // Step 1: camera order, tile structure, sharding, observation lists.  Applies the partition settings to `tp`
-    // (host calls only).  Returns "" or an error message.
+    // the tile plan's partition settings (build_order): the caller hands them to TilePlan::set_partition / set_own_all
+    int part_rank = 0, part_world = 1;
+    bool part_own_all = false;   // self-test: the distributed schedule for part_world ranks, all played by this one
+
+    // Step 1: camera order, tile structure, sharding, observation lists.  Returns "" or an error message.
     std::string build_lists(int64_t n_cam, int64_t n_pt, int64_t n_obs, const uint32_t* cam_idx, const uint32_t* pt_idx,
-                            const double* obs_uv, const BaStructOptions& o, TilePlan& tp);
+                            const double* obs_uv, const BaStructOptions& o);
     // Step 1 in its two halves (round 5): build_order leaves the camera order and the tile structure (`present`) -- all the tile
     // plan needs, so TilePlan::build may run on another thread beside build_obs_lists, which reads `present` only through
-    // tp.preview_owners and only when needs_owner_preview() (a distributed plan with tree sharding: no overlap then).
+    // plan_owners and only when needs_owner_preview() (a distributed plan with tree sharding: no overlap then).
     void build_order(int64_t n_cam, int64_t n_pt, int64_t n_obs, const uint32_t* cam_idx, const uint32_t* pt_idx,
-                     const BaStructOptions& o, TilePlan& tp);
-    std::string build_obs_lists(const uint32_t* cam_idx, const uint32_t* pt_idx, const double* obs_uv, const BaStructOptions& o, TilePlan& tp);
+                     const BaStructOptions& o);
+    std::string build_obs_lists(const uint32_t* cam_idx, const uint32_t* pt_idx, const double* obs_uv, const BaStructOptions& o);
     static bool needs_owner_preview(const BaStructOptions& o) { return o.world > 1 && o.dist_factor && o.tree_sharding; }
-    // Step 2, after tp.build() / tp.build_symbolic(): the task lists of the selected Schur form
+    // Step 2, once the slot map exists (TilePlan::build / plan_structure): the task lists of the selected Schur form
     // dev_tables != NULL (queued layout only): the pair RECORDS are left to the device (PairDeviceTables, schur_pairs.h)
     void build_schur_lists(const BaStructOptions& o, const int* slot_host, PairDeviceTables* dev_tables = nullptr);
     void release_scratch();   // the full-problem lists step 2 needed

@@ -21,13 +21,13 @@ double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock:
 }  // namespace
 
 std::string BaHostStructure::build_lists(int64_t n_cam_, int64_t n_pt_, int64_t n_obs_, const uint32_t* cam_idx,
-                                         const uint32_t* pt_idx, const double* obs_uv, const BaStructOptions& o, TilePlan& tp) {
-    build_order(n_cam_, n_pt_, n_obs_, cam_idx, pt_idx, o, tp);
-    return build_obs_lists(cam_idx, pt_idx, obs_uv, o, tp);
+                                         const uint32_t* pt_idx, const double* obs_uv, const BaStructOptions& o) {
+    build_order(n_cam_, n_pt_, n_obs_, cam_idx, pt_idx, o);
+    return build_obs_lists(cam_idx, pt_idx, obs_uv, o);
 }
 
 void BaHostStructure::build_order(int64_t n_cam_, int64_t n_pt_, int64_t n_obs_, const uint32_t* cam_idx,
-                                  const uint32_t* pt_idx, const BaStructOptions& o, TilePlan& tp) {
+                                  const uint32_t* pt_idx, const BaStructOptions& o) {
     const double t_begin = now_s();
     SetupTrace tr;
     n_cam = n_cam_; n_pt = n_pt_; n_obs = n_obs_; dc = o.dc;
@@ -231,7 +231,7 @@ void BaHostStructure::build_order(int64_t n_cam_, int64_t n_pt_, int64_t n_obs_,
     n_border_tiles = std::max(1, std::min(n_border_tiles, nt));
     std::vector<int> tperm(nt);
     std::iota(tperm.begin(), tperm.end(), 0);
-    if (o.use_nd && nt - n_border_tiles >= 23) tperm = TilePlan::order(nt, adjm, true, o.nd_leaf, n_border_tiles);
+    if (o.use_nd && nt - n_border_tiles >= 23) tperm = tile_order(nt, adjm, true, o.nd_leaf, n_border_tiles);
     tr.mark("order: nested dissection");
     cmap.resize(n_cam);
     cinv.assign(n_cam, -1);
@@ -252,22 +252,15 @@ void BaHostStructure::build_order(int64_t n_cam_, int64_t n_pt_, int64_t n_obs_,
     n_present = 0;
     for (uint8_t b : present) n_present += b;
     tr.mark("order: maps");
-    // ---- the plan's partition settings (host calls only) ------------------------------------------------------------------
-    tp.set_partition(rank, (o.dist_factor && world > 1) ? world : 1);
-    tp.set_own_all(false);
-    if (o.dist_selftest > 1 && world == 1) {  // self-test: the distributed schedule for that many ranks, all played by this one
-        tp.set_partition(0, o.dist_selftest);
-        tp.set_own_all(true);
-        TilePlan::Comm tc;
-        tc.sum = [](double*, size_t, hipStream_t) { return true; };
-        tc.max_int = [](int*, size_t, hipStream_t) { return true; };
-        tp.set_comm(std::move(tc));
-    }
+    // ---- the plan's partition settings ------------------------------------------------------------------------------------
+    part_rank = rank; part_world = (o.dist_factor && world > 1) ? world : 1;
+    part_own_all = o.dist_selftest > 1 && world == 1;   // self-test: the distributed schedule for that many ranks, all played by this one
+    if (part_own_all) { part_rank = 0; part_world = o.dist_selftest; }
     seconds[0] = now_s() - t_begin;
 }
 
 std::string BaHostStructure::build_obs_lists(const uint32_t* cam_idx, const uint32_t* pt_idx, const double* obs_uv,
-                                             const BaStructOptions& o, TilePlan& tp) {
+                                             const BaStructOptions& o) {
     SetupTrace tr;
     const int cpt = kNB / dc;
     const int rank = o.rank, world = o.world;
@@ -280,7 +273,6 @@ std::string BaHostStructure::build_obs_lists(const uint32_t* cam_idx, const uint
     std::iota(lmap.begin(), lmap.end(), 0);
     tree_shard = false;
     lm_lo = 0; lm_hi = n_pt;
-    if (false) tp.set_partition(rank, (o.dist_factor && world > 1) ? world : 1);
     pad_rank = 0;
     lam_mask.clear();
     // Tree sharding (distributed Cholesky, no communicator-less test shards): a landmark's cameras form a clique of
@@ -289,7 +281,7 @@ std::string BaHostStructure::build_obs_lists(const uint32_t* cam_idx, const uint
     // no reduce of S at all, only the top tiles are summed (which the distributed factorisation does anyway).
     // Landmarks seen by top cameras only go to the least loaded rank.  Landmarks are renumbered so that every
     // rank's set is one contiguous internal range.
-    const std::vector<int> owner = needs_owner_preview(o) ? tp.preview_owners(nt, present) : std::vector<int>();
+    const std::vector<int> owner = needs_owner_preview(o) ? plan_owners(nt, present, part_world) : std::vector<int>();
     if (!owner.empty()) {
         std::vector<int> lm_owner(n_pt, -1);
         std::vector<int64_t> load(world, 0);

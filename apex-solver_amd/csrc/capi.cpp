@@ -286,10 +286,7 @@ extern "C" {
 int apexgpu_debug_partition(int nt, const uint8_t* present, int world, int* owner_out) {
     if (nt <= 0 || !present || !owner_out || world < 1) return APEXGPU_ERR_INVALID_INPUT;
     return guarded([&]() -> int {
-    apex::TilePlan tp;
-    tp.set_partition(0, world);
-    const std::vector<uint8_t> pr(present, present + (size_t)nt * nt);
-    const std::vector<int> owner = tp.preview_owners(nt, pr);
+    const std::vector<int> owner = apex::plan_owners(nt, std::vector<uint8_t>(present, present + (size_t)nt * nt), world);
     if (owner.empty()) { for (int i = 0; i < nt; ++i) owner_out[i] = 0; return 0; }
     int n_top = 0;
     for (int i = 0; i < nt; ++i) { owner_out[i] = owner[i]; n_top += owner[i] < 0; }
@@ -297,57 +294,149 @@ int apexgpu_debug_partition(int nt, const uint8_t* present, int world, int* owne
     });
 }
 
-// the host-only plan of apexgpu_debug_check_schedule / apexgpu_debug_schedule_ops; returns build_host_only's message
-static std::string schedule_plan(apex::TilePlan& tp, int nt, const uint8_t* present, int world, int rank, const int opts[8]) {
-    if (world > 1) tp.set_partition(rank, world);
-    tp.set_two_side(opts[0]);
-    tp.enable_overlap(opts[1] != 0); if (opts[1] > 1) tp.set_overlap_min(opts[1]);
-    tp.set_split_u1(opts[2]);
-    tp.set_gate_min(opts[3]);
-    tp.set_factor_flow(opts[4], opts[5]);
-    tp.debug_skip_idle_level_wait(opts[6] != 0);
-    return tp.build_host_only(nt, std::vector<uint8_t>(present, present + (size_t)nt * nt));
+// The host-only plan of the apexgpu_debug_* calls that take opts[8]: structure and lists on the stand-in bases, the schedule
+// switches; err = why it was refused.
+struct HostPlan {
+    apex::PlanStructure s; apex::PlanLists l; apex::ScheduleSwitches w; std::string err;
+    std::vector<apex::SchedOp> schedule(int phase) const {
+        const int cut = s.n_local_groups;
+        return phase == 0 ? apex::factor_schedule(apex::schedule_input(s, l, w), 0, cut) : apex::factor_schedule(apex::schedule_input(s, l, w), cut, s.n_levels());
+    }
+};
+static HostPlan host_plan(int nt, const uint8_t* present, int world, int rank, const int opts[8]) {
+    HostPlan h;
+    apex::PlanOptions o;
+    if (world > 1) { o.rank = rank; o.world = world; }
+    o.two_side = opts[0];
+    h.w.overlap = opts[1] != 0; if (opts[1] > 1) h.w.overlap_min = opts[1];
+    h.w.split_u1 = opts[2] > 0; if (opts[2] > 0) h.w.split_u1_min = opts[2];
+    h.w.gate_min = opts[3];
+    o.flow_cols = opts[4]; if (opts[5] > 0) o.flow_rows = opts[5];
+    h.w.skip_idle_wait = opts[6] != 0;
+    const std::vector<uint8_t> pr(present, present + (size_t)nt * nt);
+    h.s = apex::plan_structure(nt, pr, o);
+    h.err = apex::build_plan_lists(h.s, pr, o, reinterpret_cast<double*>(apex::kStandInTiles), reinterpret_cast<double*>(apex::kStandInLinv), &h.l);
+    return h;
 }
 
 int apexgpu_debug_check_schedule(int nt, const uint8_t* present, int world, int rank, const int opts[8], int64_t out[8], char* msg, int msg_len) {
     if (nt <= 0 || !present || !opts || !out || world < 1 || rank < 0 || rank >= world) return APEXGPU_ERR_INVALID_INPUT;
     return guarded([&]() -> int {
-    apex::TilePlan tp;
-    const std::string e = schedule_plan(tp, nt, present, world, rank, opts);
+    const HostPlan hp = host_plan(nt, present, world, rank, opts);
+    const std::string& e = hp.err;
     std::string first;
     if (!e.empty()) { if (msg && msg_len > 0) snprintf(msg, (size_t)msg_len, "%s", e.c_str()); return APEXGPU_ERR_INVALID_STATE; }
     for (int k = 0; k < 8; ++k) out[k] = 0;
     for (int ph = 0; ph < 2; ++ph) {
-        std::vector<apex::SchedOp> ops = tp.schedule_trace(ph);
+        std::vector<apex::SchedOp> ops = hp.schedule(ph);
         if (opts[7] >= 0 && ph == 0) {   // drop the opts[7]-th stream wait of the sequence: the checker must notice when it mattered
             int seen = 0;
             for (size_t i = 0; i < ops.size(); ++i)
                 if (ops[i].op == apex::kOpWait && seen++ == opts[7]) { ops.erase(ops.begin() + (long)i); out[7] = 1; break; }
         }
         std::string why;
-        const int bad = tp.check_schedule(ops, &why);
+        const int bad = apex::check_schedule(ops, hp.l.potrf, hp.l.panel, hp.l.upd, hp.l.units, &why);
         for (const apex::SchedOp& o : ops) { out[0] += o.op <= apex::kOpWait; out[1] += o.op == apex::kOpLaunch; out[6] += o.op == apex::kOpWait; }
         out[2 + ph] = bad;
         if (bad && first.empty()) first = why;
     }
-    out[4] = tp.factor_flow_units(); out[5] = tp.factor_flow_groups();
+    const apex::PlanLists::Flow* f = hp.l.flow;
+    out[4] = f[0].n + f[1].n; out[5] = (f[0].g1 - f[0].g0) + (f[1].g1 - f[1].g0);
     if (msg && msg_len > 0) snprintf(msg, (size_t)msg_len, "%s", first.c_str());
-    return tp.n_levels();
+    return hp.s.n_levels();
     });
 }
 
 int apexgpu_debug_schedule_ops(int nt, const uint8_t* present, int world, int rank, const int opts[8], int phase, int64_t* rows, int max_rows) {
     if (nt <= 0 || !present || !opts || world < 1 || rank < 0 || rank >= world || phase < 0 || phase > 1 || max_rows < 0 || (max_rows > 0 && !rows)) return APEXGPU_ERR_INVALID_INPUT;
     return guarded([&]() -> int {
-    apex::TilePlan tp;
-    if (!schedule_plan(tp, nt, present, world, rank, opts).empty()) return APEXGPU_ERR_INVALID_STATE;
-    const std::vector<apex::SchedOp> ops = tp.schedule_trace(phase);
+    const HostPlan hp = host_plan(nt, present, world, rank, opts);
+    if (!hp.err.empty()) return APEXGPU_ERR_INVALID_STATE;
+    const std::vector<apex::SchedOp> ops = hp.schedule(phase);
     for (size_t i = 0; i < ops.size() && i < (size_t)max_rows; ++i) {
         const apex::SchedOp& o = ops[i];
         int64_t* r = rows + 6 * i;
         r[0] = o.op; r[1] = (int64_t)o.stream; r[2] = (int64_t)o.event; r[3] = o.list; r[4] = o.first; r[5] = o.count;
     }
     return (int)ops.size();
+    });
+}
+
+// One table of apexgpu_debug_plan_lists (include/apexgpu.h) as rows of `*width` integers.  Tiles by name: (array, index) with
+// array 0 the tiles (index = slot), 1 linv (index = tile column), (-1, -1) null.
+static int plan_table(const apex::PlanStructure& s, const apex::PlanLists& l, const double* tiles, const double* linv, int which, std::vector<int64_t>* out, int* width) {
+    constexpr ptrdiff_t kTile = (ptrdiff_t)apex::kNB * apex::kNB;
+    auto clean = [](const double* p) { return reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(p) & ~uintptr_t(7)); };
+    auto in_linv = [&](const double* p) { return p >= linv && p < linv + s.nt * kTile; };
+    auto arr = [&](const double* p) -> int64_t { p = clean(p); return !p ? -1 : in_linv(p) ? 1 : 0; };
+    auto idx = [&](const double* p) -> int64_t { p = clean(p); return !p ? -1 : in_linv(p) ? (p - linv) / kTile : (p - tiles) / kTile; };
+    auto bits = [](double v) { int64_t b; memcpy(&b, &v, sizeof b); return b; };
+    auto row = [&](std::initializer_list<int64_t> v) { *width = (int)v.size(); out->insert(out->end(), v); };
+    auto gemm = [&](const std::vector<apex::GemmTask>& v) {
+        *width = 7;
+        for (const apex::GemmTask& t : v) row({arr(t.C), idx(t.C), (int64_t)(reinterpret_cast<uintptr_t>(t.C) & 1), arr(t.A), idx(t.A), arr(t.B), idx(t.B)});
+    };
+    auto tri = [&](const std::vector<apex::TriTask>& v) {
+        *width = 6;
+        for (const apex::TriTask& t : v) row({arr(t.Mdiag), idx(t.Mdiag), arr(t.Moff), idx(t.Moff), t.k, t.other});
+    };
+    auto flow = [&](const std::vector<apex::FlowTask>& v) {
+        *width = 10;
+        for (const apex::FlowTask& t : v) row({arr(t.mat), idx(t.mat), t.src, t.dst, t.part, t.count, arr(t.mat2), idx(t.mat2), t.src2, t.slot2});
+    };
+    const int nt = s.nt;
+    switch (which) {
+        case 0: {
+            const apex::PlanLists::Flow* f = l.flow;
+            row({s.n_levels(), s.n_local_groups, s.n_top_cols, s.n_slots, s.n_touched, (int64_t)l.potrf.size(), (int64_t)l.panel.size(), (int64_t)l.upd.size(),
+                 l.two_side_plan, l.first_ok, f[0].g0, f[0].g1, f[0].first, f[0].n, f[1].g0, f[1].g1, f[1].first, f[1].n, l.n_flow_local, l.n_flow_parts,
+                 bits(s.predicted_ms), bits(f[0].sim_us), bits(f[1].sim_us)});
+            break;
+        }
+        case 1: *width = 3; for (int I = 0; I < nt; ++I) for (int J = 0; J < nt; ++J) if (s.slot_of(I, J) >= 0) row({I, J, s.slot_of(I, J)}); break;
+        case 2: *width = 4; for (int K = 0; K < nt; ++K) row({K, s.cls[K], s.owner[K], s.diag_slot[K]}); break;
+        case 3:   // per owner: its touched and fill slot ranges; last the ranges of the shared top
+            for (size_t o = 0; o < s.own_range.size(); ++o) row({(int64_t)o, s.own_range[o].first, s.own_range[o].second, s.own_fill[o].first, s.own_fill[o].second});
+            row({-1, s.n_t_nt, s.n_touched - s.n_t_nt, s.n_f_nt, s.n_slots - s.n_f_nt});
+            break;
+        case 4: *width = 9; for (const apex::Level& v : l.lv) row({v.potrf, v.panel, v.fwd, v.upd, v.u1o, v.u2a, v.u2b1, v.u2b2, (int64_t)v.fwd_cut.size()}); break;
+        case 5: *width = 2; for (size_t g = 0; g < l.lv.size(); ++g) for (int c : l.lv[g].fwd_cut) row({(int64_t)g, c}); break;
+        case 6: *width = 2; for (const auto& r : l.upd_rounds) row({r.first, r.second}); break;
+        case 7: *width = 1; for (int b : l.bwd_step) row({b}); break;
+        case 8: *width = 5; for (const apex::PotrfTask& t : l.potrf) row({arr(t.A), idx(t.A), arr(t.Linv), idx(t.Linv), t.K}); break;
+        case 9: gemm(l.panel); break;
+        case 10: gemm(l.upd); break;
+        case 11: tri(l.fwd); break;
+        case 12: tri(l.bwd); break;
+        case 13: flow(l.flow_fwd); break;
+        case 14: flow(l.flow_bwd); break;
+        case 15:
+            *width = 16;
+            for (const apex::FactorUnit& u : l.units)
+                row({arr(u.C), idx(u.C), arr(u.A), idx(u.A), arr(u.B), idx(u.B), u.wait_flag[0], u.wait_flag[1], u.wait_flag[2], u.wait_val[0], u.wait_val[1], u.wait_val[2],
+                     u.pub, u.kind, u.strip, u.pad});
+            break;
+        case 16: *width = 1; for (int v : l.sym_row_ptr) row({v}); break;
+        case 17: *width = 3; for (const apex::SymEntry& e : l.sym_entries) row({e.slot, e.other, e.kind}); break;
+        case 18: *width = 3; for (const apex::SymTile& t : l.sym_tiles) row({t.slot, t.I, t.J}); break;
+        case 19: *width = 2; for (size_t g = 0; g < s.group_cols.size(); ++g) for (int K : s.group_cols[g]) row({(int64_t)g, K}); break;
+        default: return APEXGPU_ERR_INVALID_INPUT;
+    }
+    return APEXGPU_OK;
+}
+
+int apexgpu_debug_plan_lists(int nt, const uint8_t* present, int world, int rank, const int opts[8], int which, int64_t* rows, int max_rows) {
+    if (nt <= 0 || !present || !opts || world < 1 || rank < 0 || rank >= world || max_rows < 0 || (max_rows > 0 && !rows)) return APEXGPU_ERR_INVALID_INPUT;
+    return guarded([&]() -> int {
+    const HostPlan hp = host_plan(nt, present, world, rank, opts);
+    if (!hp.err.empty()) return APEXGPU_ERR_INVALID_STATE;
+    std::vector<int64_t> out;
+    int width = 1;
+    const int rc = plan_table(hp.s, hp.l, reinterpret_cast<const double*>(apex::kStandInTiles), reinterpret_cast<const double*>(apex::kStandInLinv), which, &out, &width);
+    if (rc != APEXGPU_OK) return rc;
+    const size_t n = out.size() / (size_t)width;
+    if (max_rows > 0) memcpy(rows, out.data(), std::min(n, (size_t)max_rows) * (size_t)width * sizeof(int64_t));
+    return (int)n;
     });
 }
 
@@ -374,11 +463,11 @@ static int sinv_rows(const apex::SinvLists& l, int64_t* rows, int max_rows, int6
 int apexgpu_debug_sinv_lists(int nt, const uint8_t* present, int64_t* rows, int max_rows, int64_t counts[4], int32_t* slot_out) {
     if (nt <= 0 || !present || max_rows < 0 || (max_rows > 0 && !rows)) return APEXGPU_ERR_INVALID_INPUT;
     return guarded([&]() -> int {
-    apex::TilePlan tp;
-    if (!tp.build_host_only(nt, std::vector<uint8_t>(present, present + (size_t)nt * nt)).empty()) return APEXGPU_ERR_INVALID_STATE;
-    if (slot_out) memcpy(slot_out, tp.slot_host(), (size_t)nt * nt * sizeof(int32_t));
+    const apex::PlanStructure s = apex::plan_structure(nt, std::vector<uint8_t>(present, present + (size_t)nt * nt), apex::PlanOptions());
+    if (s.refused) return APEXGPU_ERR_INVALID_STATE;
+    if (slot_out) memcpy(slot_out, s.slot.data(), (size_t)nt * nt * sizeof(int32_t));
     apex::SinvLists lists;
-    if (!apex::build_sinv_lists(nt, tp.slot_host(), tp.group_columns(), &lists).empty()) return APEXGPU_ERR_INVALID_STATE;
+    if (!apex::build_sinv_lists(nt, s.slot.data(), s.group_cols, &lists).empty()) return APEXGPU_ERR_INVALID_STATE;
     return sinv_rows(lists, rows, max_rows, counts);
     });
 }
@@ -632,23 +721,23 @@ int apexgpu_debug_host_structure(int64_t n_cam, int64_t n_pt, int64_t n_obs, int
         so.use_nd = opts[0] != 0; if (opts[0] > 1) so.nd_leaf = opts[0];
         so.hubs_last = opts[1] != 0; so.dist_factor = opts[2] != 0; so.tree_sharding = opts[3] != 0; so.schur_form = opts[4];
         so.rank = rank; so.world = world;
-        apex::TilePlan tp;
         apex::BaHostStructure hs;
         std::vector<double> uv(2 * (size_t)n_obs, 0.0);
-        const std::string e = hs.build_lists(n_cam, n_pt, n_obs, cam_idx, pt_idx, uv.data(), so, tp);
+        const std::string e = hs.build_lists(n_cam, n_pt, n_obs, cam_idx, pt_idx, uv.data(), so);
         if (!e.empty()) return APEXGPU_ERR_INVALID_INPUT;
-        tp.build_symbolic(hs.nt, hs.present);
-        hs.build_schur_lists(so, tp.slot_host());
+        apex::PlanOptions po;
+        po.rank = hs.part_rank; po.world = hs.part_world; po.own_all = hs.part_own_all;
+        const apex::PlanStructure ps = apex::plan_structure(hs.nt, hs.present, po);
+        hs.build_schur_lists(so, ps.slot.data());
         const double t_all = hs.seconds[0] + hs.seconds[1] + hs.seconds[3];
-        const double st[16] = {(double)hs.nt, (double)hs.n_hubs, (double)hs.n_border_tiles, (double)hs.n_present, (double)tp.n_slots(),
-                               (double)tp.n_levels(), (double)tp.n_top_columns(), hs.tree_shard ? 1.0 : 0.0, hs.seconds[0], hs.seconds[1],
+        const double st[16] = {(double)hs.nt, (double)hs.n_hubs, (double)hs.n_border_tiles, (double)hs.n_present, (double)ps.n_slots,
+                               (double)ps.n_true_levels, (double)ps.n_top_cols, hs.tree_shard ? 1.0 : 0.0, hs.seconds[0], hs.seconds[1],
                                0.0, hs.seconds[3], 0.0, t_all, (double)hs.n_pairs, (double)hs.pl.n_blocks};
         for (int k = 0; k < 16; ++k) stats_out[k] = st[k];
         if (cmap_out) for (int64_t c = 0; c < n_cam; ++c) cmap_out[c] = hs.cmap[c];
         if (owned_out) for (int64_t l = 0; l < n_pt; ++l) owned_out[l] = (hs.lmap[l] >= hs.lm_lo && hs.lmap[l] < hs.lm_hi) ? 1 : 0;
         if (tile_owner_out) {
-            const std::vector<int> ow = tp.preview_owners(hs.nt, hs.present);
-            for (int t = 0; t < hs.nt; ++t) tile_owner_out[t] = ow.empty() ? -1 : ow[t];
+            for (int t = 0; t < hs.nt; ++t) tile_owner_out[t] = ps.n_top_cols > 0 ? ps.owner[t] : -1;
         }
         return APEXGPU_OK;
     });

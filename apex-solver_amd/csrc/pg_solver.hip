@@ -110,13 +110,13 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
     n_pad_ = (int64_t)nt * kNB;
 
     // ---- internal vertex order: whole tiles of kNB / dof consecutive vertices, permuted by a nested-dissection
-    // ordering of the tile graph (see TilePlan::order) -----------------------------------------------
+    // ordering of the tile graph (see tile_order, plan_lists.h) -----------------------------------------------
     std::vector<uint8_t> adjm((size_t)nt * nt, 0);
     for (int64_t e = 0; e < n_e_; ++e) {
         const int a = (int)(e_from[e] / vpt_), b = (int)(e_to[e] / vpt_);
         if (a != b) { adjm[(size_t)a * nt + b] = 1; adjm[(size_t)b * nt + a] = 1; }
     }
-    const std::vector<int> tperm = TilePlan::order(nt, adjm, use_nd_, nd_leaf_);
+    const std::vector<int> tperm = tile_order(nt, adjm, use_nd_, nd_leaf_);
     vmap_.resize(n_v_);
     for (int64_t v = 0; v < n_v_; ++v) vmap_[v] = (int)((int64_t)tperm[v / vpt_] * vpt_ + v % vpt_);
     std::vector<uint8_t> present((size_t)nt * nt, 0);

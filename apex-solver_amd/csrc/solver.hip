@@ -272,7 +272,7 @@ void Solver::choose_and_build_plan(Setup& su) {
     // should not spend 10 s where it owns a 0.5 s way to the same step: levenberg_marquardt.rs:1039-1082).  The matrix-free
     // PCG costs at most its cap times one S p -- two passes over the observations, 160 bytes each at the 4.5 TB/s the two
     // kernels sustain (1.01 ms on final-13682, 0.45 ms on synthetic-10k: DESIGN section 5) -- whatever the structure; the tile
-    // plan refuses to be built when its own prediction (TilePlan::predict_solve_ms) is above that.  Both numbers are host
+    // plan refuses to be built when its own prediction (predict_solve_ms, plan_lists.h) is above that.  Both numbers are host
     // arithmetic on the replicated structure: every rank decides alike.  "variant_cost_permille" scales the matrix-free side
     // (tests move the crossover onto small problems; 0: the rule is off).
     pred_mf_ms_ = 500.0 * (160.0 * (double)n_obs_ / 4.5e12 * 1e3 + 0.02) * (double)variant_cost_permille_ / 1000.0;
@@ -500,15 +500,23 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     BaHostStructure& hs = *su.hs;
     // Camera order and tile structure first; then the tile plan (symbolic fill, task lists, 1.4 GB of device allocations: 0.06-
     // 0.1 s, mostly serial) is built on a thread of its own BESIDE the observation lists (0.1 s), which do not need it (round 5).
-    // A distributed plan with tree sharding previews the partition inside the list phase on the same TilePlan: no overlap then.
-    hs.build_order(n_cam_, n_pt_, n_obs_, cam_idx, pt_idx, so, tp_);
+    // A distributed plan with tree sharding previews the partition inside the list phase (plan_owners): no overlap then.
+    hs.build_order(n_cam_, n_pt_, n_obs_, cam_idx, pt_idx, so);
+    tp_.set_partition(hs.part_rank, hs.part_world);
+    tp_.set_own_all(hs.part_own_all);
+    if (hs.part_own_all) {   // (self-test: one rank plays every owner, the exchanges are no-ops)
+        TilePlan::Comm tc;
+        tc.sum = [](double*, size_t, hipStream_t) { return true; };
+        tc.max_int = [](int*, size_t, hipStream_t) { return true; };
+        tp_.set_comm(std::move(tc));
+    }
     nt_ = hs.nt;
     su.present_plan = hs.present;
     su.tr.mark("camera order, tile structure");
     const bool plan_beside_lists = !BaHostStructure::needs_owner_preview(so);
     if (plan_beside_lists) su.planner = std::thread(&Solver::planner_body, this, std::ref(su));
     {
-        const std::string e = hs.build_obs_lists(cam_idx, pt_idx, obs_uv, so, tp_);
+        const std::string e = hs.build_obs_lists(cam_idx, pt_idx, obs_uv, so);
         if (!e.empty()) return fail(kInvalidInput, e);
     }
     su.tr.mark("observation lists");

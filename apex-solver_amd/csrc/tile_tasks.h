@@ -5,6 +5,8 @@
 
 namespace apex {
 
+constexpr int kNB = 144;   // S tile edge: 16*9 = 24*6, multiple of the 16-wide f64 MFMA
+
 struct GemmTask {  // C = beta*C + alpha * A * B^T on 144x144 row-major tiles
     double* C;
     const double* A;

@@ -421,6 +421,23 @@ int apexgpu_debug_check_schedule(int nt, const uint8_t* present, int world, int 
  * list = -1 and event = 0 where unused.  opts[7] is ignored.  At most max_rows rows are written (rows may be NULL when
  * max_rows is 0); returns the number of calls or an error. */
 int apexgpu_debug_schedule_ops(int nt, const uint8_t* present, int world, int rank, const int opts[8], int phase, int64_t* rows, int max_rows);
+/* The same plan's structure and task lists, one table per call, as rows of integers in list order (host only; opts[6], opts[7]
+ * are ignored).  A tile is written as (array, index): array 0 the tiles (index = slot), 1 the inverses of L's diagonal tiles
+ * (index = tile column), (-1, -1) a null pointer.  which / columns:
+ *    0 one row {level groups, local groups, top columns, slots, touched slots, potrf tasks, panel tasks, update tasks, two_side
+ *      decided, first writers flagged, per phase {g0, g1, first unit, units} of the dataflow launch, forward dataflow tasks of
+ *      phase 0, partial vectors, bit patterns of predicted ms and of either phase's simulated us}
+ *    1 slot map {I, J, slot}    2 columns {K, class, owner, diagonal slot}
+ *    3 per owner {owner, touched first, count, fill first, count}, last the shared top's ranges with owner -1
+ *    4 level table {potrf, panel, fwd, upd, u1o, u2a, u2b1, u2b2, forward cuts}    5 forward cuts {level group, first task}
+ *    6 update rounds {first, count}    7 backward steps {first task}
+ *    8 potrf {A, Linv, K}    9 panel solves, 10 updates {C, first-writer bit of C, A, B}
+ *   11 forward, 12 backward level sweep {Mdiag, Moff, k, other}
+ *   13 forward, 14 backward dataflow sweep {mat, src, dst, part, count, mat2, src2, slot2}
+ *   15 dataflow units {C, A, B, wait_flag[3], wait_val[3], pub, kind, strip, pad}
+ *   16 PCG row pointers, 17 PCG entries {slot, other, kind}, 18 PCG tiles {slot, I, J}    19 level groups {group, column}
+ * At most max_rows rows are written (rows may be NULL when max_rows is 0); returns the number of rows or an error. */
+int apexgpu_debug_plan_lists(int nt, const uint8_t* present, int world, int rank, const int opts[8], int which, int64_t* rows, int max_rows);
 /* Host arithmetic only: the task lists of the selected inversion (marginal covariances) of the single-rank plan of a tile
  * structure, tiles by name.  Rows of six integers, every task first, then every product, both in list order:
  *   task     {kind, group, C.array, C.tile, first, count}: kind 0 Y / 1 off-diagonal Z / 2 diagonal Z; group counted from the root

@@ -248,6 +248,37 @@ def test_fill_patterns_never_read_their_fill_tiles(name):
             assert np.array_equal(r["L"], run0["L"]) and np.array_equal(r["Linv"], run0["Linv"]), opts
 
 
+@pytest.mark.parametrize("shape", ["grid3x4", "band48"])
+def test_device_plan_is_the_host_value(shape):
+    """The plan TilePlan::build makes on the device's tile addresses against the host value built with no device on stand-in
+    addresses (plan_lists.h; apexgpu_debug_plan_lists): the slot map, the slot / touched / level-group counts, the first-writer
+    verdict, the dataflow units and groups.  grid(3, 4): 12 tiles with fill; band(48, 3): 48 level groups, no fill.  Then one
+    factorisation + solve on that plan (the exact-reference cases of this file run on plans built the same way)."""
+    from apex_solver_amd import capi
+
+    pat = tr.grid(3, 4) if shape == "grid3x4" else tr.band(48, 3)
+    nt = pat.shape[0]
+    assert tr.has_fill(pat) == (shape == "grid3x4")
+    sc = capi.plan_lists(pat, "scalars")[0]
+    slot = np.full((nt, nt), -1, dtype=np.int32)
+    rows = capi.plan_lists(pat, "slots")
+    slot[rows[:, 0], rows[:, 1]] = rows[:, 2]
+    with _mk(pat) as dev:
+        assert np.array_equal(dev.slot, slot)
+        assert (dev.n_slots, dev.n_touched, dev.levels) == (int(sc[3]), int(sc[4]), int(sc[0]))
+        assert dev.first_writers_flagged == bool(sc[9])
+        assert dev.flow_units == int(sc[13] + sc[17]) and dev.flow_groups == int((sc[11] - sc[10]) + (sc[15] - sc[14]))
+        assert dev.flow_units == len(capi.plan_lists(pat, "units"))
+        A = tr.dominant_case(pat, np.random.default_rng(61))
+        if shape == "grid3x4":
+            check_case("host-value plan grid3x4", dev, pat, A, z_cols=None)
+        else:
+            run = _run(dev, A, z=False, rhs=np.random.default_rng(62).standard_normal((1, nt * NB)))
+            assert run["failed"] == 0 and np.isfinite(run["L"]).all() and np.isfinite(run["x"]).all()
+            Lh = tr.from_slots(run["L"], dev, tr.filled_pattern(pat))
+            assert tr.factor_ratio(A, Lh, pat) <= 1.0
+
+
 _SCHED_ON = dict(two_side=2, update_overlap=1, split_u1=1, flood_gate=2)
 _sched_case = {}
 
