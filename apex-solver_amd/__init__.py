@@ -13,6 +13,7 @@ from . import layout, synthetic  # noqa: F401
 
 __all__ = ["layout", "synthetic"]
 from . import bal, capi, datasets, pose_graph, solver  # noqa: F401,E402
-from .pose_graph import G2oLoader, GpuSparseCholeskySolver, PoseGraphProblem  # noqa: F401,E402
+from .pose_graph import (DogLegConfig, G2oLoader, GaussNewtonConfig, GpuSparseCholeskySolver,  # noqa: F401,E402
+                         PoseGraphProblem)
 from .solver import (GpuSchurComplementSolver, LevenbergMarquardt, LevenbergMarquardtConfig,  # noqa: F401,E402
                      LinearSolverType, OptimizationStatus, OptimizationType, Problem, SchurVariant, SolverResult)

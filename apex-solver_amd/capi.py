@@ -45,6 +45,8 @@ SYMBOLS = (
     # SE2 pose graphs: the same handle, two more lifetime calls, the SE2 content of a G2O file
     "apexgpu_pg_create_se2", "apexgpu_pg_manifold", "apexgpu_g2o_raw_se2", "apexgpu_g2o_problem_se2",
     "apexgpu_pose_graph_columns_se2",
+    # Gauss-Newton and Dog-Leg on pose graphs
+    "apexgpu_pg_jv_gram", "apexgpu_pg_dogleg_step", "apexgpu_pg_gn_optimize", "apexgpu_pg_dogleg_optimize",
 )
 MANIFOLD_SE3, MANIFOLD_SE2 = 0, 1
 PG_NUM_STAGES = 6
@@ -90,6 +92,29 @@ class LmResultC(C.Structure):
         ("unsuccessful_steps", C.c_int),
     ]
 
+
+class GnConfigC(C.Structure):
+    _fields_ = [
+        ("max_iterations", C.c_int), ("cost_tolerance", C.c_double), ("parameter_tolerance", C.c_double),
+        ("gradient_tolerance", C.c_double), ("min_cost_threshold", C.c_double), ("timeout_s", C.c_double),
+        ("variant", C.c_int), ("use_jacobi_scaling", C.c_int),
+    ]
+
+
+class DlConfigC(C.Structure):
+    _fields_ = [("max_iterations", C.c_int)] + [(n, C.c_double) for n in (
+        "cost_tolerance", "parameter_tolerance", "gradient_tolerance", "trust_region_radius", "trust_region_min",
+        "trust_region_max", "trust_region_decrease_factor", "good_step_quality", "poor_step_quality", "mu", "min_mu", "max_mu",
+        "mu_increase_factor", "min_cost_threshold", "timeout_s")] + [
+        ("variant", C.c_int), ("use_jacobi_scaling", C.c_int), ("enable_step_reuse", C.c_int)]
+
+
+class DlIterC(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("cost", "radius", "mu", "rho", "accepted", "gradient_norm", "step_norm",
+                                          "predicted_reduction", "trial_cost", "step_type", "beta", "reused")]
+
+
+DL_STEP_TYPES = ("GaussNewton", "SteepestDescent", "DogLeg")   # StepType (dog_leg.rs), the value of step_type
 
 _lib = None
 
@@ -206,6 +231,10 @@ def load() -> C.CDLL:
     L.apexgpu_pg_column_norms.argtypes = [vp, vp]
     L.apexgpu_pg_set_column_scaling.argtypes = [vp, vp]
     L.apexgpu_pg_lm_optimize.argtypes = [vp, C.POINTER(LmConfigC), C.POINTER(LmResultC), vp, C.c_int]
+    L.apexgpu_pg_jv_gram.argtypes = [vp, vp, vp, C.POINTER(dbl * 3)]
+    L.apexgpu_pg_dogleg_step.argtypes = [vp, dbl, dbl, C.c_int, C.POINTER(dbl * 8)]
+    L.apexgpu_pg_gn_optimize.argtypes = [vp, C.POINTER(GnConfigC), C.POINTER(LmResultC), vp, C.c_int]
+    L.apexgpu_pg_dogleg_optimize.argtypes = [vp, C.POINTER(DlConfigC), C.POINTER(LmResultC), vp, C.c_int]
     L.apexgpu_pg_get_residual.argtypes = [vp, vp]
     L.apexgpu_pg_get_jacobian_blocks.argtypes = [vp, vp]
     L.apexgpu_pg_get_hessian.argtypes = [vp, dbl, vp, vp]

@@ -26,6 +26,10 @@ struct apexgpu_solver {
 static_assert(sizeof(apexgpu_lm_config) == sizeof(apex::LmConfig), "LmConfig layout");
 static_assert(sizeof(apexgpu_lm_iter) == sizeof(apex::LmIterRecord), "LmIterRecord layout");
 static_assert(sizeof(apexgpu_lm_result) == sizeof(apex::LmResult), "LmResult layout");
+static_assert(sizeof(apexgpu_gn_config) == sizeof(apex::GnConfig), "GnConfig layout");
+static_assert(sizeof(apexgpu_dl_config) == sizeof(apex::DlConfig), "DlConfig layout");
+static_assert(sizeof(apexgpu_dl_iter) == sizeof(apex::DlIterRecord), "DlIterRecord layout");
+static_assert(sizeof(apex::DoglegStepInfo) == 8 * sizeof(double), "DoglegStepInfo layout");
 static_assert(APEXGPU_NUM_STAGES == apex::kNumStages, "stage count");
 static_assert(APEXGPU_PG_NUM_STAGES == apex::kPgNumStages, "pose-graph stage count");
 
@@ -836,6 +840,29 @@ int apexgpu_pg_lm_optimize(apexgpu_pg_solver* h, apexgpu_lm_config* cfg, apexgpu
     if (!cfg || !result) return APEXGPU_ERR_INVALID_INPUT;
     return h->s->lm_optimize(reinterpret_cast<apex::LmConfig*>(cfg), reinterpret_cast<apex::LmResult*>(result),
                              reinterpret_cast<apex::LmIterRecord*>(history), history ? history_capacity : 0);
+}
+int apexgpu_pg_jv_gram(apexgpu_pg_solver* h, const double* a, const double* b, double out3[3]) {
+    PG_OR_FAIL;
+    if (!a || !b || !out3) return APEXGPU_ERR_INVALID_INPUT;
+    return guarded([&] { return h->s->jv_gram(a, b, out3); });
+}
+int apexgpu_pg_dogleg_step(apexgpu_pg_solver* h, double mu, double radius, int reuse, double out8[8]) {
+    PG_OR_FAIL;
+    return guarded([&] { return h->s->dogleg_step(mu, radius, reuse, reinterpret_cast<apex::DoglegStepInfo*>(out8)); });
+}
+int apexgpu_pg_gn_optimize(apexgpu_pg_solver* h, apexgpu_gn_config* cfg, apexgpu_lm_result* result, apexgpu_lm_iter* history,
+                           int history_capacity) {
+    PG_OR_FAIL;
+    if (!cfg || !result) return APEXGPU_ERR_INVALID_INPUT;
+    return h->s->gn_optimize(reinterpret_cast<apex::GnConfig*>(cfg), reinterpret_cast<apex::LmResult*>(result),
+                             reinterpret_cast<apex::LmIterRecord*>(history), history ? history_capacity : 0);
+}
+int apexgpu_pg_dogleg_optimize(apexgpu_pg_solver* h, apexgpu_dl_config* cfg, apexgpu_lm_result* result, apexgpu_dl_iter* history,
+                               int history_capacity) {
+    PG_OR_FAIL;
+    if (!cfg || !result) return APEXGPU_ERR_INVALID_INPUT;
+    return h->s->dogleg_optimize(reinterpret_cast<apex::DlConfig*>(cfg), reinterpret_cast<apex::LmResult*>(result),
+                                 reinterpret_cast<apex::DlIterRecord*>(history), history ? history_capacity : 0);
 }
 int apexgpu_pg_get_residual(apexgpu_pg_solver* h, double* r_out) { PG_OR_FAIL; return h->s->get_residual(r_out); }
 int apexgpu_pg_get_jacobian_blocks(apexgpu_pg_solver* h, double* j_out) { PG_OR_FAIL; return h->s->get_jacobian_blocks(j_out); }

@@ -9,6 +9,23 @@
 
 namespace apex {
 
+int check_convergence(const ConvergenceParams& p) {
+    if (!std::isfinite(p.cost) || !std::isfinite(p.step_norm) || !std::isfinite(p.gradient_norm)) return kInvalidNumericalValues;
+    if (p.timeout_s > 0.0 && p.elapsed_s >= p.timeout_s) return kTimeout;
+    if (p.iteration >= p.max_iterations) return kMaxIterationsReached;
+    if (!p.step_accepted) return -1;
+    if (p.gradient_norm < p.gradient_tolerance) return kGradientToleranceReached;
+    if (p.iteration > 0) {
+        const double rel_step_tol = p.parameter_tolerance * (p.parameter_norm + p.parameter_tolerance);
+        if (p.step_norm <= rel_step_tol) return kParameterToleranceReached;
+        const double cc = fabs(p.cost_before - p.cost);
+        if (cc / std::max(p.cost_before, 1e-10) < p.cost_tolerance) return kCostToleranceReached;
+    }
+    if (p.min_cost_threshold >= 0.0 && p.cost < p.min_cost_threshold) return kMinCostThresholdReached;
+    if (p.has_trust_region && p.trust_region_radius < p.min_trust_region_radius) return kTrustRegionRadiusTooSmall;
+    return -1;
+}
+
 int run_lm(LmBackend& b, LmConfig* cfg, LmResult* res, LmIterRecord* hist, int hist_cap) {
     const auto t0 = std::chrono::steady_clock::now();
     double lambda = cfg->damping, nu = cfg->damping_nu;
@@ -78,23 +95,9 @@ int run_lm(LmBackend& b, LmConfig* cfg, LmResult* res, LmIterRecord* hist, int h
         if (rc != kOk) return rc;
         const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         const double cost_before = accepted ? cur_cost + cost_reduction : cur_cost;
-        int stt = -1;
-        if (!std::isfinite(cur_cost) || !std::isfinite(sn) || !std::isfinite(gn)) stt = kInvalidNumericalValues;
-        else if (cfg->timeout_s > 0.0 && elapsed >= cfg->timeout_s) stt = kTimeout;
-        else if (iteration >= cfg->max_iterations) stt = kMaxIterationsReached;
-        else if (accepted) {
-            if (gn < cfg->gradient_tolerance) stt = kGradientToleranceReached;
-            if (stt < 0 && iteration > 0) {
-                const double rel_step_tol = cfg->parameter_tolerance * (pnorm + cfg->parameter_tolerance);
-                if (sn <= rel_step_tol) stt = kParameterToleranceReached;
-                else {
-                    const double cc = fabs(cost_before - cur_cost);
-                    if (cc / std::max(cost_before, 1e-10) < cfg->cost_tolerance) stt = kCostToleranceReached;
-                }
-            }
-            if (stt < 0 && cfg->min_cost_threshold >= 0.0 && cur_cost < cfg->min_cost_threshold) stt = kMinCostThresholdReached;
-            if (stt < 0 && cfg->trust_region_radius < cfg->min_trust_region_radius) stt = kTrustRegionRadiusTooSmall;
-        }
+        const int stt = check_convergence({iteration, cost_before, cur_cost, pnorm, sn, gn, elapsed, accepted != 0, cfg->max_iterations,
+                                           cfg->gradient_tolerance, cfg->parameter_tolerance, cfg->cost_tolerance, cfg->min_cost_threshold,
+                                           cfg->timeout_s, true, cfg->trust_region_radius, cfg->min_trust_region_radius});
         if (stt >= 0) { status = stt; ++iteration; break; }
         ++iteration;
     }

@@ -58,6 +58,21 @@ struct LmResult {
     int cost_evaluations, jacobian_evaluations, successful_steps, unsuccessful_steps;
 };
 
+// check_convergence (src/optimizer/mod.rs:591-658), shared by the three loops (lm_loop.cpp, tr_loop.cpp).  cost_before is
+// ConvergenceParams::current_cost, cost its new_cost.  has_trust_region false: the loop has none (Gauss-Newton passes None).
+struct ConvergenceParams {
+    int iteration;
+    double cost_before, cost, parameter_norm, step_norm, gradient_norm, elapsed_s;
+    bool step_accepted;
+    int max_iterations;
+    double gradient_tolerance, parameter_tolerance, cost_tolerance;
+    double min_cost_threshold;   // < 0: None
+    double timeout_s;            // <= 0: None
+    bool has_trust_region;
+    double trust_region_radius, min_trust_region_radius;
+};
+int check_convergence(const ConvergenceParams& p);   // an LmStatus, or -1 to go on
+
 class LmBackend {
    public:
     virtual ~LmBackend() = default;

@@ -268,6 +268,18 @@ struct Se2Manifold {
     static APEX_HD double cost_add_prior(double acc, const double r[3]) {   // the block's squared norm first, then one add
         return acc + (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
     }
+    // u = J~0 a0 + J~1 a1, w = J~0 b0 + J~1 b1 for the corrected Jacobians of one edge (the linearisation of pg2_assemble_row:
+    // between2_corrected); a0 / b0: the three tangent entries of k0's vertex, a1 / b1 of k1's
+    static APEX_HD void edge_jv(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m, double huber_delta,
+                                const double a0[3], const double a1[3], const double b0[3], const double b1[3], double u[3], double w[3]) {
+        double r[3], J0[9], J1[9];
+        between2_corrected(k0, k1, m, huber_delta, r, J0, J1);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            u[i] = (J0[3 * i] * a0[0] + J0[3 * i + 1] * a0[1] + J0[3 * i + 2] * a0[2]) + (J1[3 * i] * a1[0] + J1[3 * i + 1] * a1[1] + J1[3 * i + 2] * a1[2]);
+            w[i] = (J0[3 * i] * b0[0] + J0[3 * i + 1] * b0[1] + J0[3 * i + 2] * b0[2]) + (J1[3 * i] * b1[0] + J1[3 * i + 1] * b1[1] + J1[3 * i + 2] * b1[2]);
+        }
+    }
     // corrected residual [3] and Jacobian [3][6] = [dr/dk0 | dr/dk1] of one edge (either may be null); sqrt(rho') is
     // applied inside between2_corrected
     static APEX_HD void export_edge(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,

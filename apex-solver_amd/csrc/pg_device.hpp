@@ -278,6 +278,29 @@ struct Se3Manifold {
         for (int a = 0; a < 7; ++a) acc += r[a] * r[a];
         return acc;
     }
+    // u = J~0 a0 + J~1 a1, w = J~0 b0 + J~1 b1 for the corrected Jacobians J~ = sqrt(rho') [dr/dk0 | dr/dk1] of one edge
+    // (the linearisation of k_pg_edges; a0 / b0: the six tangent entries of k0's vertex, a1 / b1 of k1's).  J = [P T; 0 P]:
+    // J x = (P x_t + T x_r, P x_r).  sqrt(rho') multiplies the 12 products, not the 36 Jacobian entries.
+    static APEX_HD void edge_jv(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m, double huber_delta,
+                                const double a0[6], const double a1[6], const double b0[6], const double b1[6], double u[6], double w[6]) {
+        double r[6];
+        Jac6 J0, J1;
+        between_linearize(k0, k1, m, r, J0, J1);
+        const double sc = pg_huber_scale(huber_delta, r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            double ut = 0.0, ur = 0.0, wt = 0.0, wr = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double p0 = J0.P[3 * i + j], t0 = J0.T[3 * i + j], p1 = J1.P[3 * i + j], t1 = J1.T[3 * i + j];
+                ut += (p0 * a0[j] + t0 * a0[3 + j]) + (p1 * a1[j] + t1 * a1[3 + j]);
+                ur += p0 * a0[3 + j] + p1 * a1[3 + j];
+                wt += (p0 * b0[j] + t0 * b0[3 + j]) + (p1 * b1[j] + t1 * b1[3 + j]);
+                wr += p0 * b0[3 + j] + p1 * b1[3 + j];
+            }
+            u[i] = sc * ut; u[3 + i] = sc * ur; w[i] = sc * wt; w[3 + i] = sc * wr;
+        }
+    }
     // corrected residual [6] and Jacobian [6][12] = [dr/dk0 | dr/dk1] of one edge (either may be null); sqrt(rho') is
     // applied at the store
     static APEX_HD void export_edge(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,

@@ -6,6 +6,9 @@
 //   k_pg_cost_partial<M>  edge-major    1/2 |r~|^2 at a (trial) parameter set
 //   k_pg_retract<M>       vertex-major  x (+) d with the fixed-DOF mask (src/core/problem.rs:185-197)
 //   k_pg_prior_export<M>, k_pg_export<M>  parity exports
+//   k_pg_jv_gram<M>       edge-major    |J a|^2, (J a).(J b), |J b|^2 matrix-free: the products with H = J^T J the Dog-Leg step needs
+//                                       (dog_leg.rs:776-803, 948-960) once the tiles hold L instead of H
+//   k_dl_dots, k_dl_combine, k_dl_blend  the rest of a Dog-Leg step on plain vectors (dogleg_combine.hpp)
 // The assembly is one algorithm per manifold:
 //   k_pg_edges      SE3  edge-major    r, dr/dk0, dr/dk1 per edge in registers (never written to memory), loss correction,
 //                                      then H_aa += Ja^T Ja, H_bb += Jb^T Jb, H_(hi,lo) += J_hi^T J_lo, g_a += Ja^T r,
@@ -24,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_reduce.hpp"
+#include "dogleg_combine.hpp"
 #include "pg2_device.hpp"
 #include "pg_device.hpp"
 #include "pg_kernels.h"
@@ -273,6 +277,102 @@ __global__ __launch_bounds__(256) void k_pg_export(PGView v, double* __restrict_
                    j_out ? j_out + 2 * M::kDof * M::kDof * e : nullptr);
 }
 
+// ---- Dog-Leg -------------------------------------------------------------------------------------------------------
+// g.Hg, g.Hh, h.Hh for H = J^T J without H: with u = J a, w = J b they are u.u, u.w, w.w, summed over the residual blocks.
+// One pass over the edges and priors, each edge linearised as the assembly does (M::edge_jv); a, b in internal column order.
+// A self-loop reads both of its vertex segments from the same place, so both Jacobians land on one vertex by themselves.  A
+// prior block is J~ = sc [I_dof; 0]: it adds sc^2 a_v.a_v etc.  No atomics: partial[3 block + k], then k_sum_partials in index
+// order -- two calls on one state give the same bits, on both manifolds.
+template <class M>
+__global__ __launch_bounds__(256) void k_pg_jv_gram(PGView v, const double* __restrict__ a, const double* __restrict__ b,
+                                                     double* __restrict__ partial) {
+    __shared__ double scratch[4];
+    constexpr int D = M::kDof;
+    double uu = 0.0, uw = 0.0, ww = 0.0;
+    if (blockIdx.x == 0)
+        for (int k = threadIdx.x; k < v.n_prior; k += 256) {
+            double r[M::kAmb];
+            const double sc = prior_at<M>(v, k, r);
+            const size_t c = (size_t)D * v.prior_v[k];
+            double aa = 0.0, ab = 0.0, bb = 0.0;
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                const double ai = a[c + i], bi = b[c + i];
+                aa += ai * ai; ab += ai * bi; bb += bi * bi;
+            }
+            const double s2 = sc * sc;
+            uu += s2 * aa; uw += s2 * ab; ww += s2 * bb;
+        }
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < v.n_e; e += (int64_t)gridDim.x * 256) {
+        const uint32_t from = v.e_from[e], to = v.e_to[e];
+        double k0[M::kStride], k1[M::kStride], m[M::kStride], a0[D], a1[D], b0[D], b1[D], u[D], w[D];
+        load_pose<M>(v.posep, from, k0);
+        load_pose<M>(v.posep, to, k1);
+        load_pose<M>(v.meas, e, m);
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            a0[i] = a[(size_t)D * from + i]; a1[i] = a[(size_t)D * to + i];
+            b0[i] = b[(size_t)D * from + i]; b1[i] = b[(size_t)D * to + i];
+        }
+        M::edge_jv(k0, k1, m, v.huber_delta, a0, a1, b0, b1, u, w);
+        double su = 0.0, sx = 0.0, sw = 0.0;
+#pragma unroll
+        for (int i = 0; i < D; ++i) { su += u[i] * u[i]; sx += u[i] * w[i]; sw += w[i] * w[i]; }
+        uu += su; uw += sx; ww += sw;
+    }
+    uu = block_sum_256(uu, scratch);
+    uw = block_sum_256(uw, scratch);
+    ww = block_sum_256(ww, scratch);
+    if (threadIdx.x == 0) { partial[3 * blockIdx.x] = uu; partial[3 * blockIdx.x + 1] = uw; partial[3 * blockIdx.x + 2] = ww; }
+}
+
+// The inner products of the scaled gradient g_s = D g and the scaled Gauss-Newton step y = D^-1 d (d: the unscaled step the
+// sweeps leave): partial = {g_s.g_s, y.y, g_s.y}.  On the way: a_out = D g_s (the direction k_pg_jv_gram prices g_s with; may be
+// null without scaling, where it is g itself) and h_out = d (the cached step: d is overwritten by the blended step).
+__global__ __launch_bounds__(256) void k_dl_dots(int64_t n, const double* __restrict__ g, const double* __restrict__ d,
+                                                   const double* __restrict__ scale, double* __restrict__ a_out,
+                                                   double* __restrict__ h_out, double* __restrict__ partial) {
+    __shared__ double scratch[4];
+    double gg = 0.0, hh = 0.0, gh = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double s = scale ? scale[i] : 1.0, di = d[i];
+        const double gs = g[i] * s, y = scale ? di / s : di;
+        gg += gs * gs; hh += y * y; gh += gs * y;
+        if (a_out) a_out[i] = gs * s;
+        h_out[i] = di;
+    }
+    gg = block_sum_256(gg, scratch);
+    hh = block_sum_256(hh, scratch);
+    gh = block_sum_256(gh, scratch);
+    if (threadIdx.x == 0) { partial[3 * blockIdx.x] = gg; partial[3 * blockIdx.x + 1] = hh; partial[3 * blockIdx.x + 2] = gh; }
+}
+
+// one lane: the six sums and the radius -> {alpha, beta, c_g, c_h, |step_s|, predicted reduction, type}
+__global__ void k_dl_combine(const double* __restrict__ sums6, double delta, double* __restrict__ out7) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const DoglegSums s{sums6[0], sums6[1], sums6[2], sums6[3], sums6[4], sums6[5]};
+    const DoglegStep o = dogleg_combine(s, delta);
+    out7[0] = o.alpha; out7[1] = o.beta; out7[2] = o.c_g; out7[3] = o.c_h; out7[4] = o.step_norm; out7[5] = o.predicted_reduction;
+    out7[6] = (double)o.type;
+}
+
+// step = D (c_g (-g_s) + c_h y) = c_h h - c_g D^2 g into d_out, and the partial sums of |step|^2.  coef = {c_g, c_h} on the device.
+__global__ __launch_bounds__(256) void k_dl_blend(int64_t n, const double* __restrict__ g, const double* __restrict__ scale,
+                                                    const double* __restrict__ h, const double* __restrict__ coef,
+                                                    double* __restrict__ d_out, double* __restrict__ partial) {
+    __shared__ double scratch[4];
+    const double cg = coef[0], ch = coef[1];
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double s = scale ? scale[i] : 1.0;
+        const double st = ch * h[i] - cg * ((g[i] * s) * s);
+        d_out[i] = st;
+        acc += st * st;
+    }
+    acc = block_sum_256(acc, scratch);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+
 // ---- launchers -----------------------------------------------------------------------------------------------------
 static inline int grid256(int64_t n) { return (int)((n + 255) / 256); }
 
@@ -326,6 +426,27 @@ void launch_pg_export(int manifold, const PGView& v, double* r_out, double* j_ou
     with_manifold(manifold, [&](auto M) {
         hipLaunchKernelGGL(k_pg_export<decltype(M)>, dim3(grid256(v.n_e)), dim3(256), 0, s, v, r_out, j_out);
     });
+}
+
+void launch_pg_jv_gram(int manifold, const PGView& v, const double* a, const double* b, double* partial, int n_partial,
+                       double* out3, hipStream_t s) {
+    with_manifold(manifold, [&](auto M) {
+        hipLaunchKernelGGL(k_pg_jv_gram<decltype(M)>, dim3(n_partial), dim3(256), 0, s, v, a, b, partial);
+    });
+    launch_sum_partials(partial, n_partial, 3, out3, s);
+}
+void launch_dl_dots(int64_t n, const double* g, const double* d, const double* scale, double* a_out, double* h_out,
+                    double* partial, int n_partial, double* out3, hipStream_t s) {
+    hipLaunchKernelGGL(k_dl_dots, dim3(n_partial), dim3(256), 0, s, n, g, d, scale, a_out, h_out, partial);
+    launch_sum_partials(partial, n_partial, 3, out3, s);
+}
+void launch_dl_combine(const double* sums6, double delta, double* out7, hipStream_t s) {
+    hipLaunchKernelGGL(k_dl_combine, dim3(1), dim3(64), 0, s, sums6, delta, out7);
+}
+void launch_dl_blend(int64_t n, const double* g, const double* scale, const double* h, const double* coef, double* d_out,
+                     double* partial, int n_partial, double* out_sumsq, hipStream_t s) {
+    hipLaunchKernelGGL(k_dl_blend, dim3(n_partial), dim3(256), 0, s, n, g, scale, h, coef, d_out, partial);
+    launch_sum_partials(partial, n_partial, 1, out_sumsq, s);
 }
 
 }  // namespace apex

@@ -21,12 +21,13 @@
 
 #include "pg_kernels.h"
 #include "tile_backend.h"
+#include "tr_loop.h"
 
 namespace apex {
 
 enum PgStage { kPgAssemble = 0, kPgFactor, kPgTriSolve, kPgStats, kPgRetract, kPgCost, kPgNumStages };
 
-class PoseGraphSolver : public TileBackend {
+class PoseGraphSolver : public TileBackend, public TrBackend {
    public:
     PoseGraphSolver(int64_t n_v, int64_t n_e, int device, int manifold = kManifoldSE3);
     ~PoseGraphSolver() override;
@@ -48,6 +49,15 @@ class PoseGraphSolver : public TileBackend {
     int discard_step() override;
     int parameter_norm(double* out) override;
     int lm_optimize(LmConfig* cfg, LmResult* res, LmIterRecord* hist, int hist_cap);
+    // Gauss-Newton and Dog-Leg (tr_loop.h).  dogleg_step runs to ONE host wait, fresh or reused: behind the sweeps come the inner
+    // products, the Gram pass over the edges (k_pg_jv_gram), the combine (one lane), the blended step into d_, the trial point
+    // and its cost; step_stats / eval_step then answer from the host.  A reused step starts at the combine: the six sums of
+    // the last fresh solve, g_ and the cached Gauss-Newton step (hgn_) are all it reads.
+    int dogleg_step(double mu, double radius, int reuse, DoglegStepInfo* out) override;
+    int gn_optimize(GnConfig* cfg, LmResult* res, LmIterRecord* hist, int hist_cap);
+    int dogleg_optimize(DlConfig* cfg, LmResult* res, DlIterRecord* hist, int hist_cap);
+    // parity export: {|J a|^2, (J a).(J b), |J b|^2} at the current parameters; a, b in the caller's column order, as given
+    int jv_gram(const double* a, const double* b, double out3[3]);
     // Jacobi column scaling (optimizer/mod.rs:749-763), same contract as Solver's
     int column_norms(double* norms_out);
     int set_column_scaling(const double* scaling);
@@ -85,6 +95,8 @@ class PoseGraphSolver : public TileBackend {
     int assemble(double lambda);
     int ensure_scale_buffer();
     int cost_of(int which, double* out);
+    int enqueue_dogleg_tail(bool fresh);   // everything of a Dog-Leg step behind the sweeps, up to the copy to dl_host_
+    void drop_dogleg_cache() { have_dl_cache_ = false; }
 
     int64_t n_v_, n_e_;
     int manifold_, dof_, amb_, stride_, vpt_;   // vpt_: vertices per tile = kNB / dof_
@@ -108,6 +120,14 @@ class PoseGraphSolver : public TileBackend {
     std::vector<double> scale_h_;
     bool scaled_ = false;
     int n_partial_ = 256;
+    // Dog-Leg state.  dls_: [0..5] the six sums of dogleg_combine.hpp (kept from the last fresh solve), [6..12] the combine's
+    // answer, [13] |step|^2, [14] the trial point's sum of squares; dl_host_ is its pinned copy.
+    DeviceBuffer<double> hgn_, dl_a_, dls_;   // the cached (unscaled) Gauss-Newton step; D^2 g; the scalars
+    PinnedBuffer<double> dl_host_;
+    double dl_radius_ = 0.0;
+    bool dl_mode_ = false;         // finish_step: the Dog-Leg tail instead of the LM statistics
+    bool have_dl_cache_ = false;   // g_, hgn_, dls_[0..5] belong to one solve and scale_ is what it was then
+    bool step_is_dl_ = false;      // the step in d_ is a Dog-Leg step: step_stats / eval_step answer from dl_host_
 };
 
 }  // namespace apex

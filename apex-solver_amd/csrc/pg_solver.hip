@@ -51,6 +51,7 @@ int PoseGraphSolver::set_priors(int64_t n, const uint32_t* vertex, const double*
     HIP_TRY(hipSetDevice(device_));
     HIP_TRY(hipStreamSynchronize(stream_));
     have_step_ = have_trial_ = false;
+    drop_dogleg_cache();
     // The new set goes up into locals and replaces the members (and n_prior_) only when every upload has succeeded: a failed
     // call leaves the old priors fully in place, a call with n = 0 none at all.
     DeviceBuffer<uint32_t> new_v;
@@ -165,6 +166,8 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
     HIP_TRY(hipDeviceSynchronize());
     have_structure_ = true;
     have_params_ = have_step_ = have_trial_ = false;
+    drop_dogleg_cache();
+    hgn_.reset(); dl_a_.reset(); dls_.reset();   // (sized by the old structure: dogleg_step allocates them again)
     cur_ = 0;
     return kOk;
 }
@@ -180,6 +183,7 @@ int PoseGraphSolver::set_params(const double* poses7) {
     launch_pg_prepare(manifold_, n_v_, poses_[cur_], posep_[cur_], stream_);
     HIP_TRY(hipStreamSynchronize(stream_));
     have_params_ = true; have_step_ = have_trial_ = false;
+    drop_dogleg_cache();
     return kOk;
 }
 
@@ -213,6 +217,7 @@ int PoseGraphSolver::cost(double* out) {
 
 // H + lambda I (tiles) and g = J^T r at the current parameters
 int PoseGraphSolver::assemble(double lambda) {
+    drop_dogleg_cache();   // (g_ is overwritten)
     timer_.begin(kPgAssemble, stream_);
     HIP_TRY(tp_.zero_tiles());
     HIP_TRY(hipMemsetAsync(g_, 0, n_pad_ * sizeof(double), stream_));
@@ -257,6 +262,7 @@ int PoseGraphSolver::solve_augmented(double lambda, int variant, double* step_ou
     if (variant != 0) return fail(kInvalidInput, "the pose-graph backend has the sparse Cholesky solver only");
     HIP_TRY(hipSetDevice(device_));
     begin_solve(lambda);
+    step_is_dl_ = false;
     int rc = rebuild_system(lambda, 0.0);
     if (rc == kOk && !one_wait_) {   // the flags are waited for right behind the factorisation
         int failed = 0;
@@ -276,6 +282,12 @@ int PoseGraphSolver::enqueue_sweeps() {
 
 int PoseGraphSolver::finish_step(double* step_out, double* grad_out) {
     have_step_ = true;
+    if (dl_mode_) {   // dogleg_step: the sweeps have left the Gauss-Newton step in d_
+        const int rc = enqueue_dogleg_tail(true);
+        if (rc != kOk) return rc;
+        HIP_TRY(hipStreamSynchronize(stream_));
+        return kOk;
+    }
     if (eager_eval_) {   // what the LM loop asks next rides on this solve's wait: eager_host_ [0..2] step statistics, [3] sum of squares at the trial point
         if (!eager_host_) HIP_TRY(eager_host_.alloc(8));
         enqueue_step_stats();
@@ -318,6 +330,10 @@ void PoseGraphSolver::enqueue_trial_point(double* sumsq_out) {
 
 int PoseGraphSolver::step_stats(double out3[3]) {
     if (!have_step_) return fail(kInvalidState, "no step computed");
+    if (step_is_dl_) {   // |g_s|, |step|, -s.g - 1/2 s.Hs (dog_leg.rs:1046, 1222, 948-960)
+        out3[0] = sqrt(dl_host_[0]); out3[1] = sqrt(dl_host_[13]); out3[2] = dl_host_[11];
+        return kOk;
+    }
     if (answered_at_wait()) {
         out3[0] = sqrt(eager_host_[0]); out3[1] = sqrt(eager_host_[1]); out3[2] = 0.5 * eager_host_[2];
         return kOk;
@@ -335,6 +351,12 @@ int PoseGraphSolver::step_stats(double out3[3]) {
 
 int PoseGraphSolver::eval_step(double* trial_cost) {
     if (!have_step_) return fail(kInvalidState, "no step computed");
+    if (step_is_dl_) {   // dogleg_step has put the trial point in place
+        have_trial_ = true;
+        const double nrm = sqrt(dl_host_[14]);
+        *trial_cost = 0.5 * nrm * nrm;
+        return kOk;
+    }
     if (answered_at_wait()) {   // the trial point is in place
         have_trial_ = true;
         const double nrm = sqrt(eager_host_[3]);
@@ -414,6 +436,7 @@ int PoseGraphSolver::set_column_scaling(const double* scaling) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built");
     HIP_TRY(hipSetDevice(device_));
     have_step_ = false;
+    drop_dogleg_cache();
     if (!scaling) { scaled_ = false; return kOk; }
     int rc = ensure_scale_buffer();
     if (rc != kOk) return rc;
@@ -428,7 +451,7 @@ int PoseGraphSolver::set_column_scaling(const double* scaling) {
 }
 
 int PoseGraphSolver::set_jacobi_scaling(bool on) {
-    if (!on) { scaled_ = false; have_step_ = false; return kOk; }
+    if (!on) { scaled_ = false; have_step_ = false; drop_dogleg_cache(); return kOk; }
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
     int rc = ensure_scale_buffer();
@@ -448,6 +471,98 @@ int PoseGraphSolver::set_jacobi_scaling(bool on) {
 int PoseGraphSolver::lm_optimize(LmConfig* cfg, LmResult* res, LmIterRecord* hist, int hist_cap) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     return run_lm(*this, cfg, res, hist, hist_cap);
+}
+
+// ---- Gauss-Newton and Dog-Leg (tr_loop.h) -------------------------------------------------------------------------
+int PoseGraphSolver::enqueue_dogleg_tail(bool fresh) {
+    const double* sc = scaled_ ? scale_.get() : nullptr;
+    timer_.begin(kPgStats, stream_);
+    if (fresh) {
+        // g_s = D g, y = D^-1 d: g_s.g_s, y.y, g_s.y; then g_s.H_s g_s = |J D g_s|^2, g_s.H_s y = (J D g_s).(J D y), y.H_s y = |J D y|^2 with
+        // D y = d, the unscaled step the sweeps left -- the Gram kernel never sees D
+        launch_dl_dots(n_, g_, d_, sc, scaled_ ? dl_a_.get() : nullptr, hgn_, partial_, n_partial_, dls_, stream_);
+        launch_pg_jv_gram(manifold_, view(cur_), scaled_ ? dl_a_.get() : g_.get(), d_, partial_, n_partial_, dls_ + 3, stream_);
+    }
+    launch_dl_combine(dls_, dl_radius_, dls_ + 6, stream_);
+    launch_dl_blend(n_, g_, sc, hgn_, dls_ + 8, d_, partial_, n_partial_, dls_ + 13, stream_);
+    timer_.end(kPgStats, stream_);
+    enqueue_trial_point(dls_ + 14);
+    HIP_TRY(hipMemcpyAsync(dl_host_, dls_, 16 * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    return kOk;
+}
+
+int PoseGraphSolver::dogleg_step(double mu, double radius, int reuse, DoglegStepInfo* out) {
+    if (!have_params_) return fail(kInvalidState, "Block structure not built or parameters not set");
+    if (!(radius > 0.0) || !(mu >= 0.0)) return fail(kInvalidInput, "dogleg_step: the radius must be positive and mu non-negative");
+    HIP_TRY(hipSetDevice(device_));
+    if (!dls_) {
+        HIP_TRY(hgn_.alloc_zero(n_pad_));
+        HIP_TRY(dl_a_.alloc_zero(n_pad_));
+        HIP_TRY(dls_.alloc_zero(16));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    if (!dl_host_) HIP_TRY(dl_host_.alloc(16));
+    dl_radius_ = radius;
+    int rc;
+    if (reuse) {
+        if (!have_dl_cache_) return fail(kInvalidState, "no cached Dog-Leg solve to reuse");
+        begin_solve(last_lambda_);
+        rc = enqueue_dogleg_tail(false);
+        if (rc == kOk) rc = check_hip(hipStreamSynchronize(stream_), "dogleg_step");
+        if (rc == kOk) have_step_ = true;
+    } else {
+        begin_solve(mu);
+        dl_mode_ = true;
+        rc = rebuild_system(mu, 0.0);   // (drops the cache)
+        if (rc == kOk && !one_wait_) {
+            int failed = 0;
+            rc = factor_fresh(mu, 0.0, &failed);
+            if (rc == kOk) rc = recover_factor(mu, failed, false);
+        }
+        if (rc == kOk) rc = direct_solve(one_wait_, mu, nullptr, nullptr);
+        dl_mode_ = false;
+        if (rc == kOk) have_dl_cache_ = true;
+    }
+    if (rc != kOk) return rc;
+    step_is_dl_ = true;
+    if (out) {
+        const double* h = dl_host_;
+        out->gradient_norm = sqrt(h[0]); out->step_norm = sqrt(h[13]); out->predicted_reduction = h[11]; out->step_type = h[12];
+        out->alpha = h[6]; out->beta = h[7]; out->scaled_step_norm = h[10]; out->reused = reuse ? 1.0 : 0.0;
+    }
+    return kOk;
+}
+
+int PoseGraphSolver::gn_optimize(GnConfig* cfg, LmResult* res, LmIterRecord* hist, int hist_cap) {
+    if (!have_params_) return fail(kInvalidState, "no parameters set");
+    if (cfg->variant != 0) return fail(kInvalidInput, "the pose-graph backend has the sparse Cholesky solver only");
+    return run_gauss_newton(*this, cfg, res, hist, hist_cap);
+}
+
+int PoseGraphSolver::dogleg_optimize(DlConfig* cfg, LmResult* res, DlIterRecord* hist, int hist_cap) {
+    if (!have_params_) return fail(kInvalidState, "no parameters set");
+    if (cfg->variant != 0) return fail(kInvalidInput, "the pose-graph backend has the sparse Cholesky solver only");
+    if (!(cfg->trust_region_radius > 0.0) || !(cfg->mu >= 0.0)) return fail(kInvalidInput, "Dog-Leg: the radius must be positive and mu non-negative");
+    return run_dogleg(*this, cfg, res, hist, hist_cap);
+}
+
+int PoseGraphSolver::jv_gram(const double* a, const double* b, double out3[3]) {
+    if (!have_params_) return fail(kInvalidState, "no parameters set");
+    HIP_TRY(hipSetDevice(device_));
+    std::vector<double> ha(n_pad_, 0.0), hb(n_pad_, 0.0);
+    for (int64_t v = 0; v < n_v_; ++v)
+        for (int k = 0; k < dof_; ++k) {
+            ha[dof_ * (size_t)vmap_[v] + k] = a[pose_col_[v] + k];
+            hb[dof_ * (size_t)vmap_[v] + k] = b[pose_col_[v] + k];
+        }
+    DeviceBuffer<double> da, db;
+    HIP_TRY(hipStreamSynchronize(stream_));
+    HIP_TRY(da.upload(ha));
+    HIP_TRY(db.upload(hb));
+    launch_pg_jv_gram(manifold_, view(cur_), da, db, partial_, n_partial_, scal_ + 5, stream_);
+    hipError_t e = hipMemcpyAsync(out3, scal_ + 5, 3 * sizeof(double), hipMemcpyDeviceToHost, stream_);
+    (void)hipStreamSynchronize(stream_);   // (before da / db are freed)
+    return check_hip(e, "jv_gram");
 }
 
 // ---- parity / debug exports ------------------------------------------------------------------

@@ -21,7 +21,7 @@ namespace apex {
         if (_rc != kOk) return _rc;                           \
     } while (0)
 
-class TileBackend : public LmBackend {
+class TileBackend : public virtual LmBackend {   // (virtual: a solver may also be a TrBackend, tr_loop.h)
    public:
     void enable_graphs(bool on) { tp_.enable_graphs(on); }
     void enable_overlap(bool on) { tp_.enable_overlap(on); }

@@ -233,6 +233,61 @@ class PoseGraphProblem:
         return self.data.n_e + len(self.priors)
 
 
+@dataclass
+class GaussNewtonConfig:
+    """Defaults of gauss_newton.rs:236-255; fields the loop never reads (min_diagonal, max_condition_number) are not reproduced."""
+
+    max_iterations: int = 50
+    cost_tolerance: float = 1e-6
+    parameter_tolerance: float = 1e-8
+    gradient_tolerance: float = 1e-10
+    timeout: float | None = None
+    min_cost_threshold: float | None = None
+    use_jacobi_scaling: bool = False
+    variant: int = 0   # the sparse Cholesky solver; anything else is refused
+
+    def to_c(self) -> capi.GnConfigC:
+        return capi.GnConfigC(self.max_iterations, self.cost_tolerance, self.parameter_tolerance, self.gradient_tolerance,
+                              -1.0 if self.min_cost_threshold is None else self.min_cost_threshold,
+                              -1.0 if self.timeout is None else float(self.timeout), int(self.variant),
+                              1 if self.use_jacobi_scaling else 0)
+
+
+@dataclass
+class DogLegConfig:
+    """Defaults of dog_leg.rs:353-399; fields the loop never reads (trust_region_increase_factor -- the radius grows by the
+    literal 3 --, min_step_quality, min_relative_decrease, max_condition_number) are not reproduced."""
+
+    max_iterations: int = 50
+    cost_tolerance: float = 1e-6
+    parameter_tolerance: float = 1e-8
+    gradient_tolerance: float = 1e-10
+    timeout: float | None = None
+    trust_region_radius: float = 1e4
+    trust_region_min: float = 1e-12
+    trust_region_max: float = 1e12
+    trust_region_decrease_factor: float = 0.5
+    good_step_quality: float = 0.75
+    poor_step_quality: float = 0.25
+    use_jacobi_scaling: bool = True
+    initial_mu: float = 1e-4
+    min_mu: float = 1e-8
+    max_mu: float = 1.0
+    mu_increase_factor: float = 10.0
+    enable_step_reuse: bool = True
+    min_cost_threshold: float | None = None
+    variant: int = 0   # the sparse Cholesky solver; anything else is refused
+
+    def to_c(self) -> capi.DlConfigC:
+        return capi.DlConfigC(self.max_iterations, self.cost_tolerance, self.parameter_tolerance, self.gradient_tolerance,
+                              self.trust_region_radius, self.trust_region_min, self.trust_region_max,
+                              self.trust_region_decrease_factor, self.good_step_quality, self.poor_step_quality,
+                              self.initial_mu, self.min_mu, self.max_mu, self.mu_increase_factor,
+                              -1.0 if self.min_cost_threshold is None else self.min_cost_threshold,
+                              -1.0 if self.timeout is None else float(self.timeout), int(self.variant),
+                              1 if self.use_jacobi_scaling else 0, 1 if self.enable_step_reuse else 0)
+
+
 class GpuSparseCholeskySolver:
     """Device counterpart of SparseCholeskySolver (src/linalg/sparse/cholesky.rs) for pose graphs:
     `solve_augmented_equation(lambda)` linearises the BetweenFactors, assembles J^T J + lambda I
@@ -434,6 +489,50 @@ class GpuSparseCholeskySolver:
         n = res.iterations
         H = np.array([[getattr(hist[i], f) for f, _ in capi.LmIterC._fields_] for i in range(min(n, cap))])
         return res, H.reshape(-1, 8), c
+
+    def gn_optimize(self, cfg: GaussNewtonConfig):
+        """GaussNewton::optimize (gauss_newton.rs:559-720) on the device: (result, history (n, 8) in LmIterC's columns with
+        damping = rho = 0 and accepted = 1, the config as the loop left it)."""
+        h = self._need()
+        c = cfg.to_c()
+        res = capi.LmResultC()
+        cap = cfg.max_iterations + 2
+        hist = (capi.LmIterC * cap)()
+        h.check(h.L.apexgpu_pg_gn_optimize(h.h, C.byref(c), C.byref(res), C.cast(hist, C.c_void_p), cap))
+        H = np.array([[getattr(hist[i], f) for f, _ in capi.LmIterC._fields_] for i in range(min(res.iterations, cap))])
+        return res, H.reshape(-1, 8), c
+
+    def dogleg_optimize(self, cfg: DogLegConfig):
+        """DogLeg::optimize (dog_leg.rs:1143-1354) on the device: (result, history (n, 12) in DlIterC's columns, the config as
+        the loop left it -- trust_region_radius and mu hold their final values)."""
+        h = self._need()
+        c = cfg.to_c()
+        res = capi.LmResultC()
+        cap = cfg.max_iterations + 2
+        hist = (capi.DlIterC * cap)()
+        h.check(h.L.apexgpu_pg_dogleg_optimize(h.h, C.byref(c), C.byref(res), C.cast(hist, C.c_void_p), cap))
+        H = np.array([[getattr(hist[i], f) for f, _ in capi.DlIterC._fields_] for i in range(min(res.iterations, cap))])
+        return res, H.reshape(-1, 12), c
+
+    def dogleg_step(self, mu: float, radius: float, reuse: bool = False) -> dict:
+        """One Dog-Leg step and its trial point at the current parameters; eval_step / commit_step / discard_step follow.
+        reuse: rebuild the step from the cached solve at the new radius (no assembly, no factorisation)."""
+        h = self._need()
+        o = (C.c_double * 8)()
+        h.check(h.L.apexgpu_pg_dogleg_step(h.h, float(mu), float(radius), 1 if reuse else 0, C.byref(o)))
+        return dict(gradient_norm=o[0], step_norm=o[1], predicted_reduction=o[2], step_type=int(o[3]), alpha=o[4], beta=o[5],
+                    scaled_step_norm=o[6], reused=bool(o[7]))
+
+    def jv_gram(self, a, b):
+        """(|J a|^2, (J a).(J b), |J b|^2) at the current parameters, matrix-free; a, b in the global column order."""
+        h = self._need()
+        n = h.dof * h.n_vertices
+        a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
+        if a.shape != (n,) or b.shape != (n,):
+            raise ValueError("a and b must have total_dof entries")
+        o = (C.c_double * 3)()
+        h.check(h.L.apexgpu_pg_jv_gram(h.h, capi.ptr(a), capi.ptr(b), C.byref(o)))
+        return o[0], o[1], o[2]
 
     def close(self):
         if self._h is not None:

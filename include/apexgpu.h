@@ -626,6 +626,64 @@ int apexgpu_pg_set_column_scaling(apexgpu_pg_solver* h, const double* scaling);
 int apexgpu_pg_lm_optimize(apexgpu_pg_solver* h, apexgpu_lm_config* cfg, apexgpu_lm_result* result,
                            apexgpu_lm_iter* history, int history_capacity);
 
+/* ---- Gauss-Newton and Dog-Leg on pose graphs (gauss_newton.rs:559-720, dog_leg.rs:1143-1354) ----------------------
+ * The reference's other two optimisers over the same sparse Cholesky solver.  Fields of GaussNewtonConfig / DogLegConfig the loops
+ * never read are not reproduced.  variant must be 0. */
+typedef struct {
+    int max_iterations;             /* 50                                           gauss_newton.rs:239 */
+    double cost_tolerance;          /* 1e-6 */
+    double parameter_tolerance;     /* 1e-8 */
+    double gradient_tolerance;      /* 1e-10 */
+    double min_cost_threshold;      /* < 0: None */
+    double timeout_s;               /* <= 0: None */
+    int variant;                    /* 0 */
+    int use_jacobi_scaling;         /* 0                                            :247 */
+} apexgpu_gn_config;
+
+typedef struct {
+    int max_iterations;                  /* 50                                      dog_leg.rs:358 */
+    double cost_tolerance;               /* 1e-6 */
+    double parameter_tolerance;          /* 1e-8 */
+    double gradient_tolerance;           /* 1e-10 */
+    double trust_region_radius;          /* 1e4   (in/out: final value)             :367 */
+    double trust_region_min;             /* 1e-12 */
+    double trust_region_max;             /* 1e12 */
+    double trust_region_decrease_factor; /* 0.5 */
+    double good_step_quality;            /* 0.75 */
+    double poor_step_quality;            /* 0.25 */
+    double mu;                           /* initial_mu 1e-4 (in/out: final value)   :382 */
+    double min_mu;                       /* 1e-8 */
+    double max_mu;                       /* 1.0 */
+    double mu_increase_factor;           /* 10 */
+    double min_cost_threshold;           /* < 0: None */
+    double timeout_s;                    /* <= 0: None */
+    int variant;                         /* 0 */
+    int use_jacobi_scaling;              /* 1                                       :378 */
+    int enable_step_reuse;               /* 1                                       :388 */
+} apexgpu_dl_config;
+
+/* radius and mu: after the iteration's update; step_type 0 GaussNewton, 1 SteepestDescent, 2 DogLeg; reused 1: the step was
+ * rebuilt from the cached solve (dog_leg.rs:969-1017) */
+typedef struct {
+    double cost, radius, mu, rho, accepted, gradient_norm, step_norm, predicted_reduction, trial_cost, step_type, beta, reused;
+} apexgpu_dl_iter;
+
+/* out3 = { |J a|^2, (J a).(J b), |J b|^2 } = { a.Ha, a.Hb, b.Hb } for H = J^T J at the current parameters, in one pass over the
+ * edges and priors (no matrix is built).  a, b: total-dof entries in the global column order, taken as given (no scaling). */
+int apexgpu_pg_jv_gram(apexgpu_pg_solver* h, const double* a, const double* b, double out3[3]);
+/* One Dog-Leg step at the current parameters (compute_optimization_step_generic, dog_leg.rs:963-1089) and its trial point:
+ * apexgpu_pg_step_stats / eval_step / commit_step / discard_step follow as after apexgpu_pg_solve_augmented.
+ * reuse = 0: solves (H + mu I) h = -g; APEXGPU_ERR_SINGULAR_MATRIX when the factorisation fails.  reuse = 1: the step from the
+ * cached h, g, Cauchy point of the last reuse = 0 call at the new radius, without assembly or factorisation;
+ * APEXGPU_ERR_INVALID_STATE when there is none (or parameters, priors, scaling were set, or another solve / export ran, since).
+ * out8 = { |g|, |step| (unscaled), predicted reduction, step type, alpha, beta, |step| in the scaled variables, reused }. */
+int apexgpu_pg_dogleg_step(apexgpu_pg_solver* h, double mu, double radius, int reuse, double out8[8]);
+/* history rows: apexgpu_lm_iter with damping = 0, rho = 0, accepted = 1.  result->jacobian_evaluations counts iterations. */
+int apexgpu_pg_gn_optimize(apexgpu_pg_solver* h, apexgpu_gn_config* cfg, apexgpu_lm_result* result, apexgpu_lm_iter* history,
+                           int history_capacity);
+int apexgpu_pg_dogleg_optimize(apexgpu_pg_solver* h, apexgpu_dl_config* cfg, apexgpu_lm_result* result, apexgpu_dl_iter* history,
+                               int history_capacity);
+
 /* parity / debug exports: loss-corrected residuals [n_edges][6], Jacobians [n_edges][6][12] = [dr/dk0 | dr/dk1]
  * in residual-block order; dense H = J^T J + lambda I ([6 n_v]^2 row-major) and g = J^T r in the global column order.
  * SE2 handle: residuals [n_edges][3], Jacobians [n_edges][3][6], H (3 n_v)^2, g 3 n_v. */
