@@ -47,8 +47,15 @@ SYMBOLS = (
     "apexgpu_pose_graph_columns_se2",
     # Gauss-Newton and Dog-Leg on pose graphs
     "apexgpu_pg_jv_gram", "apexgpu_pg_dogleg_step", "apexgpu_pg_gn_optimize", "apexgpu_pg_dogleg_optimize",
+    # the robust loss family on pose graphs
+    "apexgpu_pg_set_loss", "apexgpu_pg_get_loss", "apexgpu_loss_evaluate",
 )
 MANIFOLD_SE3, MANIFOLD_SE2 = 0, 1
+# APEXGPU_LOSS_* of include/apexgpu.h, in value order
+LOSS_KINDS = ("NONE", "L2", "L1", "HUBER", "CAUCHY", "FAIR", "GEMAN_MCCLURE", "WELSCH", "TUKEY", "ANDREWS", "RAMSAY",
+              "TRIMMED_MEAN", "LP_NORM", "BARRON", "T_DISTRIBUTION")
+(LOSS_NONE, LOSS_L2, LOSS_L1, LOSS_HUBER, LOSS_CAUCHY, LOSS_FAIR, LOSS_GEMAN_MCCLURE, LOSS_WELSCH, LOSS_TUKEY, LOSS_ANDREWS,
+ LOSS_RAMSAY, LOSS_TRIMMED_MEAN, LOSS_LP_NORM, LOSS_BARRON, LOSS_T_DISTRIBUTION) = range(15)
 PG_NUM_STAGES = 6
 PG_STAGE_NAMES = ("assemble", "factor", "tri_solve", "step_stats", "retract", "cost")
 _NON_INT = ("apexgpu_destroy", "apexgpu_debug_tiles_destroy", "apexgpu_last_error", "apexgpu_version", "apexgpu_host_cache_bytes", "apexgpu_bal_close", "apexgpu_bal_last_error",
@@ -220,6 +227,9 @@ def load() -> C.CDLL:
     L.apexgpu_pg_set_params.argtypes = [vp, vp]
     L.apexgpu_pg_set_priors.argtypes = [vp, C.c_int64, vp, vp, vp]
     L.apexgpu_pg_get_prior_residual.argtypes = [vp, vp]
+    L.apexgpu_pg_set_loss.argtypes = [vp, C.c_int, dbl, dbl]
+    L.apexgpu_pg_get_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(dbl * 2)]
+    L.apexgpu_loss_evaluate.argtypes = [C.c_int, dbl, dbl, dbl, C.POINTER(dbl * 6)]
     L.apexgpu_pg_get_params.argtypes = [vp, vp]
     L.apexgpu_pg_cost.argtypes = [vp, C.POINTER(dbl)]
     L.apexgpu_pg_solve_augmented.argtypes = [vp, dbl, vp, vp]

@@ -871,6 +871,24 @@ int apexgpu_pg_set_priors(apexgpu_pg_solver* h, int64_t n, const uint32_t* verte
     if (n > 0 && (!vertex || !data7)) return APEXGPU_ERR_INVALID_INPUT;
     return h->s->set_priors(n, vertex, data7, huber_delta);
 }
+int apexgpu_pg_set_loss(apexgpu_pg_solver* h, int kind, double p0, double p1) {
+    PG_OR_FAIL;
+    return guarded([&] { return h->s->set_loss(kind, p0, p1); });
+}
+int apexgpu_pg_get_loss(const apexgpu_pg_solver* h, int* kind, double out2[2]) {
+    PG_OR_FAIL;
+    if (!kind || !out2) return APEXGPU_ERR_INVALID_INPUT;
+    h->s->get_loss(kind, out2);
+    return APEXGPU_OK;
+}
+int apexgpu_loss_evaluate(int kind, double p0, double p1, double s, double out6[6]) {
+    apex::PgLoss l;
+    if (!out6 || !apex::pg_loss_make(kind, p0, p1, &l)) return APEXGPU_ERR_INVALID_INPUT;
+    apex::pg_loss_evaluate(l, s, out6);
+    const apex::PgCorrector c = apex::pg_corrector(out6, s);
+    out6[3] = c.sqrt_rho1; out6[4] = c.residual_scaling; out6[5] = c.alpha_sq_norm;
+    return APEXGPU_OK;
+}
 int apexgpu_pg_get_prior_residual(apexgpu_pg_solver* h, double* r7_out) {
     PG_OR_FAIL;
     return h->s->get_prior_residual(r7_out);

@@ -21,6 +21,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "pg_device.hpp"
 
 namespace apex {
@@ -176,6 +178,49 @@ APEX_HD void between2_corrected(const double* __restrict__ k0, const double* __r
     }
 }
 
+// The same under the general loss (pg_loss.hpp; the type of the loss parameter is the compile-time policy, pg_device.hpp).
+// First arm: the lines above with
+// sqrt(rho').  Second arm, literally (corrector.rs:241-253, 292-298): r~ = residual_scaling r, J~ = sqrt(rho') (J - a r r^T J).
+// false: rho' = 0, the edge contributes nothing; r, J0, J1 are zero.
+APEX_HD bool between2_corrected(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                                const PgLoss& loss, double r[3], double J0[9], double J1[9]) {
+    between2_linearize(k0, k1, m, r, J0, J1);
+    const PgCorrector c = pg_loss_corrector(loss, r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    const double sc = c.sqrt_rho1;
+    if (sc == 0.0) {
+        r[0] = r[1] = r[2] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { J0[i] = 0.0; J1[i] = 0.0; }
+        return false;
+    }
+    if (c.alpha_sq_norm == 0.0) {
+        if (sc != 1.0) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) r[i] *= sc;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) { J0[i] *= sc; J1[i] *= sc; }
+        }
+        return true;
+    }
+    const double a = c.alpha_sq_norm;
+    double w0[3] = {0.0, 0.0, 0.0}, w1[3] = {0.0, 0.0, 0.0};   // r^T J
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        w0[j] = r[0] * J0[j] + r[1] * J0[3 + j] + r[2] * J0[6 + j];
+        w1[j] = r[0] * J1[j] + r[1] * J1[3 + j] + r[2] * J1[6 + j];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            J0[3 * i + j] = sc * (J0[3 * i + j] - a * r[i] * w0[j]);
+            J1[3 * i + j] = sc * (J1[3 * i + j] - a * r[i] * w1[j]);
+        }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) r[i] *= c.residual_scaling;
+    return true;
+}
+
 // H += A^T B (3 x 3 row-major), g += A^T r
 APEX_HD void jtj3_acc(const double* __restrict__ A, const double* __restrict__ B, double* __restrict__ H) {
 #pragma unroll
@@ -214,10 +259,10 @@ APEX_HD void se2_plus(const double* __restrict__ v3, const double d[3], double* 
 // self-loop listed once (pg2_lists.h).  Every edge of the list is re-linearised; H_vv and g_v accumulate in registers in
 // list order; for an other endpoint u < v the block J_v^T J_u goes to add_off(u, B) -- blocks (v, u) with u < v are touched
 // by the owner of row v only, so a plain read-add-write there has no race and duplicate edges sum in list order.
-template <typename AddOff>
+template <typename AddOff, typename LossParam>
 APEX_HD void pg2_assemble_row(uint32_t v, const double* __restrict__ posep, const double* __restrict__ meas,
                               const uint32_t* __restrict__ e_from, const uint32_t* __restrict__ e_to,
-                              const int* __restrict__ inc_ptr, const uint32_t* __restrict__ inc_edge, double huber_delta,
+                              const int* __restrict__ inc_ptr, const uint32_t* __restrict__ inc_edge, const LossParam& loss,
                               double Hvv[9], double gv[3], AddOff add_off) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) Hvv[i] = 0.0;
@@ -225,8 +270,13 @@ APEX_HD void pg2_assemble_row(uint32_t v, const double* __restrict__ posep, cons
     for (int k = inc_ptr[v]; k < inc_ptr[v + 1]; ++k) {
         const uint32_t e = inc_edge[k], a = e_from[e], b = e_to[e];
         double r[3], J0[9], J1[9];
-        between2_corrected(posep + kPose2Stride * (size_t)a, posep + kPose2Stride * (size_t)b, meas + kPose2Stride * (size_t)e,
-                           huber_delta, r, J0, J1);
+        if constexpr (std::is_same<LossParam, PgLoss>::value) {   // (an edge with rho' = 0 is skipped)
+            if (!between2_corrected(posep + kPose2Stride * (size_t)a, posep + kPose2Stride * (size_t)b,
+                                    meas + kPose2Stride * (size_t)e, loss, r, J0, J1)) continue;
+        } else {
+            between2_corrected(posep + kPose2Stride * (size_t)a, posep + kPose2Stride * (size_t)b, meas + kPose2Stride * (size_t)e,
+                               loss, r, J0, J1);
+        }
         if (a == b) {   // self-loop: both Jacobians hit the same columns
 #pragma unroll
             for (int i = 0; i < 9; ++i) J0[i] += J1[i];
@@ -270,10 +320,11 @@ struct Se2Manifold {
     }
     // u = J~0 a0 + J~1 a1, w = J~0 b0 + J~1 b1 for the corrected Jacobians of one edge (the linearisation of pg2_assemble_row:
     // between2_corrected); a0 / b0: the three tangent entries of k0's vertex, a1 / b1 of k1's
-    static APEX_HD void edge_jv(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m, double huber_delta,
+    template <typename LossParam>
+    static APEX_HD void edge_jv(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m, const LossParam& loss,
                                 const double a0[3], const double a1[3], const double b0[3], const double b1[3], double u[3], double w[3]) {
         double r[3], J0[9], J1[9];
-        between2_corrected(k0, k1, m, huber_delta, r, J0, J1);
+        (void)between2_corrected(k0, k1, m, loss, r, J0, J1);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             u[i] = (J0[3 * i] * a0[0] + J0[3 * i + 1] * a0[1] + J0[3 * i + 2] * a0[2]) + (J1[3 * i] * a1[0] + J1[3 * i + 1] * a1[1] + J1[3 * i + 2] * a1[2]);
@@ -282,10 +333,11 @@ struct Se2Manifold {
     }
     // corrected residual [3] and Jacobian [3][6] = [dr/dk0 | dr/dk1] of one edge (either may be null); sqrt(rho') is
     // applied inside between2_corrected
+    template <typename LossParam>
     static APEX_HD void export_edge(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
-                                    double huber_delta, double* __restrict__ r_out, double* __restrict__ j_out) {
+                                    const LossParam& loss, double* __restrict__ r_out, double* __restrict__ j_out) {
         double r[3], J0[9], J1[9];
-        between2_corrected(k0, k1, m, huber_delta, r, J0, J1);
+        (void)between2_corrected(k0, k1, m, loss, r, J0, J1);
         if (r_out)
             for (int i = 0; i < 3; ++i) r_out[i] = r[i];
         if (j_out)

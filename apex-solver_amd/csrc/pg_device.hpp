@@ -19,6 +19,7 @@
 // 3x3 products instead of a 6x6x6 one.
 #pragma once
 #include "ba_device.hpp"
+#include "pg_loss.hpp"
 
 namespace apex {
 
@@ -242,6 +243,56 @@ APEX_HD void jtr(const Jac6& A, const double r[6], double g[6]) {
     }
 }
 
+// ---- the general loss (pg_loss.hpp) ---------------------------------------------------------------------------------
+// The compile-time loss policy is the type of the loss parameter: a double is the Huber delta of set_structure and selects
+// the code above and below exactly as it was; a PgLoss selects the general corrector.  A kernel is instantiated once per
+// policy and its launcher picks (pg_kernels.hip).
+struct LossLegacy  { using Param = double; static constexpr bool kGeneral = false; };
+struct LossGeneral { using Param = PgLoss; static constexpr bool kGeneral = true; };
+
+// One SE3 edge under the general corrector, in the form the assembly uses.  J~ = sqrt(rho') (J - a r r^T J) is never formed:
+// it would lose the [P T; 0 P] shape.  With w_v = J_v^T r (J and r uncorrected, s = |r|^2, a = alpha_sq_norm):
+//     J~_a^T J~_b = rho' (J_a^T J_b - a (2 - a s) w_a w_b^T)
+//     J~_v^T r~   = sqrt(rho') residual_scaling (1 - a s) w_v
+//     J~ x        = sqrt(rho') (J x - a r (w . x))
+// In the first arm a = 0 and this is rho' J^T J, rho' w, sqrt(rho') J x.
+struct EdgeNormal6 {
+    PgCorrector c;
+    double s;             // |r|^2
+    double w0[6], w1[6];  // J0^T r, J1^T r
+    double rho1, kap, gsc;   // sqrt_rho1^2, a (2 - a s), sqrt_rho1 residual_scaling (1 - a s)
+
+    // H = J_a^T J_b (jtj) -> J~_a^T J~_b
+    APEX_HD void correct(double H[36], const double wa[6], const double wb[6]) const {
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j < 6; ++j) H[6 * i + j] = rho1 * (H[6 * i + j] - kap * wa[i] * wb[j]);
+    }
+    APEX_HD void grad(const double w[6], double g[6]) const {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) g[i] = gsc * w[i];
+    }
+};
+
+// The uncorrected linearisation, then the corrector and what EdgeNormal6 needs.  false: rho' = 0, the edge contributes nothing.
+// (between_linearize is called whole, exactly as the huber_delta path calls it: splitting it into a residual and a Jacobian
+// half so that the loss could run in between changed the instructions of the huber_delta kernels as well.)
+APEX_HD bool between_linearize_general(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                                       const PgLoss& loss, double r[6], Jac6& J0, Jac6& J1, EdgeNormal6& n) {
+    between_linearize(k0, k1, m, r, J0, J1);
+    n.s = r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3] + r[4] * r[4] + r[5] * r[5];
+    n.c = pg_loss_corrector(loss, n.s);
+    if (n.c.sqrt_rho1 == 0.0) return false;
+    const double as = n.c.alpha_sq_norm * n.s;
+    n.rho1 = n.c.sqrt_rho1 * n.c.sqrt_rho1;
+    n.kap = n.c.alpha_sq_norm * (2.0 - as);
+    n.gsc = n.c.sqrt_rho1 * n.c.residual_scaling * (1.0 - as);
+    jtr(J0, r, n.w0);
+    jtr(J1, r, n.w1);
+    return true;
+}
+
 // PriorFactor on an SE3 variable (prior_factor.rs:96-108): r = to_vector(x) - data over the 7 stored doubles of the prepared
 // pose (SE3::from(DVector).to_vector(), unit quaternion), J = the first six columns of I7; returns sqrt(rho') of the
 // block's Huber loss
@@ -300,6 +351,72 @@ struct Se3Manifold {
             }
             u[i] = sc * ut; u[3 + i] = sc * ur; w[i] = sc * wt; w[3 + i] = sc * wr;
         }
+    }
+    // the same under the general loss: J~ x = sqrt(rho') (J x - a r (w . x)), w . x = w0 . x0 + w1 . x1 (EdgeNormal6)
+    static APEX_HD void edge_jv(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m, const PgLoss& loss,
+                                const double a0[6], const double a1[6], const double b0[6], const double b1[6], double u[6], double w[6]) {
+        double r[6];
+        Jac6 J0, J1;
+        EdgeNormal6 n;
+        if (!between_linearize_general(k0, k1, m, loss, r, J0, J1, n)) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) { u[i] = 0.0; w[i] = 0.0; }
+            return;
+        }
+        double wa = 0.0, wb = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) { wa += n.w0[i] * a0[i] + n.w1[i] * a1[i]; wb += n.w0[i] * b0[i] + n.w1[i] * b1[i]; }
+        const double sc = n.c.sqrt_rho1;
+        wa *= n.c.alpha_sq_norm; wb *= n.c.alpha_sq_norm;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            double ut = 0.0, ur = 0.0, wt = 0.0, wr = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double p0 = J0.P[3 * i + j], t0 = J0.T[3 * i + j], p1 = J1.P[3 * i + j], t1 = J1.T[3 * i + j];
+                ut += (p0 * a0[j] + t0 * a0[3 + j]) + (p1 * a1[j] + t1 * a1[3 + j]);
+                ur += p0 * a0[3 + j] + p1 * a1[3 + j];
+                wt += (p0 * b0[j] + t0 * b0[3 + j]) + (p1 * b1[j] + t1 * b1[3 + j]);
+                wr += p0 * b0[3 + j] + p1 * b1[3 + j];
+            }
+            u[i] = sc * (ut - r[i] * wa); u[3 + i] = sc * (ur - r[3 + i] * wa);
+            w[i] = sc * (wt - r[i] * wb); w[3 + i] = sc * (wr - r[3 + i] * wb);
+        }
+    }
+    // corrected residual [6] and Jacobian [6][12] = [dr/dk0 | dr/dk1] of one edge (either may be null) under the general
+    // loss.  First arm: the legacy stores with sqrt(rho') (Huber through this path gives Huber's bits).  Second arm: the
+    // literal J~ = sqrt(rho') (J - a r r^T J) (corrector.rs:241-253), dense -- this kernel is not hot.
+    static APEX_HD void export_edge(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                                    const PgLoss& loss, double* __restrict__ r_out, double* __restrict__ j_out) {
+        double r[6];
+        Jac6 J[2];
+        between_linearize(k0, k1, m, r, J[0], J[1]);
+        const double s = r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3] + r[4] * r[4] + r[5] * r[5];
+        const PgCorrector c = pg_loss_corrector(loss, s);
+        const double sc = c.sqrt_rho1;
+        if (r_out)
+            for (int i = 0; i < 6; ++i) r_out[i] = c.residual_scaling * r[i];
+        if (!j_out) return;
+        double rtj[12];
+        jtr(J[0], r, rtj);
+        jtr(J[1], r, rtj + 6);
+        for (int w = 0; w < 2; ++w)
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    double* o = j_out + 6 * w;
+                    if (c.alpha_sq_norm == 0.0) {
+                        o[12 * i + j] = sc * J[w].P[3 * i + j];
+                        o[12 * i + 3 + j] = sc * J[w].T[3 * i + j];
+                        o[12 * (i + 3) + j] = 0.0;
+                        o[12 * (i + 3) + 3 + j] = sc * J[w].P[3 * i + j];
+                    } else {
+                        const double a = c.alpha_sq_norm, wl = rtj[6 * w + j], wh = rtj[6 * w + 3 + j];
+                        o[12 * i + j] = sc * (J[w].P[3 * i + j] - a * r[i] * wl);
+                        o[12 * i + 3 + j] = sc * (J[w].T[3 * i + j] - a * r[i] * wh);
+                        o[12 * (i + 3) + j] = sc * (0.0 - a * r[3 + i] * wl);
+                        o[12 * (i + 3) + 3 + j] = sc * (J[w].P[3 * i + j] - a * r[3 + i] * wh);
+                    }
+                }
     }
     // corrected residual [6] and Jacobian [6][12] = [dr/dk0 | dr/dk1] of one edge (either may be null); sqrt(rho') is
     // applied at the store

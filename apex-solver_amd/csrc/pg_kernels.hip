@@ -54,6 +54,13 @@ __device__ __forceinline__ double* h_block_ptr(const TileMap& tm, uint32_t vr, u
     return tm.tiles + (size_t)slot * (kNB * kNB) + (size_t)((vr % vpt) * DOF) * kNB + (vc % vpt) * DOF;
 }
 
+// what the per-edge math of policy LP takes as its loss: the Huber delta | the PgLoss
+template <class LP>
+__device__ __forceinline__ const typename LP::Param& loss_param(const PGView& v) {
+    if constexpr (LP::kGeneral) return v.loss;
+    else return v.huber_delta;
+}
+
 // r0^2 + r1^2 + ... left to right, as the one expression it used to be spelled as
 template <int N>
 __device__ __forceinline__ double sumsq(const double r[N]) {
@@ -92,6 +99,9 @@ __global__ __launch_bounds__(256) void k_pg_prepare(int64_t n, const double* __r
 }
 
 // ---- SE3 assembly: edge-major, fp64 atomics ------------------------------------------------------------------------
+// LP = LossGeneral: J0, J1, r stay uncorrected and every block and gradient segment is corrected as it is formed
+// (EdgeNormal6, pg_device.hpp); an edge whose rho' is 0 leaves before any block is formed.
+template <class LP>
 __global__ __launch_bounds__(256) void k_pg_edges(PGView v, TileMap tm, double* __restrict__ g) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= v.n_e) return;
@@ -101,17 +111,23 @@ __global__ __launch_bounds__(256) void k_pg_edges(PGView v, TileMap tm, double* 
     load_pose<Se3Manifold>(v.posep, b, k1);
     load_pose<Se3Manifold>(v.meas, e, m);
     Jac6 J0, J1;
-    between_linearize(k0, k1, m, r, J0, J1);
-    // loss correction: r and J scale by sqrt(rho') (corrector.rs:143-181; rho'' <= 0 for Huber)
-    const double sc = pg_huber_scale(v.huber_delta, sumsq<6>(r));
-    if (sc != 1.0) {
+    [[maybe_unused]] EdgeNormal6 nf;
+    if constexpr (LP::kGeneral) {
+        if (!between_linearize_general(k0, k1, m, v.loss, r, J0, J1, nf)) return;
+    } else {
+        between_linearize(k0, k1, m, r, J0, J1);
+        // loss correction: r and J scale by sqrt(rho') (corrector.rs:143-181; rho'' <= 0 for Huber)
+        const double sc = pg_huber_scale(v.huber_delta, sumsq<6>(r));
+        if (sc != 1.0) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) r[i] *= sc;
+            for (int i = 0; i < 6; ++i) r[i] *= sc;
 #pragma unroll
-        for (int i = 0; i < 9; ++i) { J0.P[i] *= sc; J0.T[i] *= sc; J1.P[i] *= sc; J1.T[i] *= sc; }
+            for (int i = 0; i < 9; ++i) { J0.P[i] *= sc; J0.T[i] *= sc; J1.P[i] *= sc; J1.T[i] *= sc; }
+        }
     }
     double H[36], gv[6];
     jtj(J0, J0, H);
+    if constexpr (LP::kGeneral) nf.correct(H, nf.w0, nf.w0);
     {
         double* blk = h_block_ptr<6>(tm, a, a);
 #pragma unroll
@@ -120,6 +136,7 @@ __global__ __launch_bounds__(256) void k_pg_edges(PGView v, TileMap tm, double* 
             for (int j = 0; j <= i; ++j) unsafeAtomicAdd(blk + i * kNB + j, H[6 * i + j]);
     }
     jtj(J1, J1, H);
+    if constexpr (LP::kGeneral) nf.correct(H, nf.w1, nf.w1);
     {
         double* blk = h_block_ptr<6>(tm, b, b);
 #pragma unroll
@@ -129,24 +146,32 @@ __global__ __launch_bounds__(256) void k_pg_edges(PGView v, TileMap tm, double* 
     }
     if (a != b) {
         double* blk;
-        if (a > b) { jtj(J0, J1, H); blk = h_block_ptr<6>(tm, a, b); }
-        else       { jtj(J1, J0, H); blk = h_block_ptr<6>(tm, b, a); }
+        if (a > b) {
+            jtj(J0, J1, H); blk = h_block_ptr<6>(tm, a, b);
+            if constexpr (LP::kGeneral) nf.correct(H, nf.w0, nf.w1);
+        } else {
+            jtj(J1, J0, H); blk = h_block_ptr<6>(tm, b, a);
+            if constexpr (LP::kGeneral) nf.correct(H, nf.w1, nf.w0);
+        }
 #pragma unroll
         for (int i = 0; i < 6; ++i)
 #pragma unroll
             for (int j = 0; j < 6; ++j) unsafeAtomicAdd(blk + i * kNB + j, H[6 * i + j]);
     } else {  // self-loop: both Jacobians hit the same columns, the cross terms land on the diagonal block
         jtj(J0, J1, H);
+        if constexpr (LP::kGeneral) nf.correct(H, nf.w0, nf.w1);   // (the rank-one term's two cross terms ride on H + H^T below)
         double* blk = h_block_ptr<6>(tm, a, a);
 #pragma unroll
         for (int i = 0; i < 6; ++i)
 #pragma unroll
             for (int j = 0; j <= i; ++j) unsafeAtomicAdd(blk + i * kNB + j, H[6 * i + j] + H[6 * j + i]);
     }
-    jtr(J0, r, gv);
+    if constexpr (LP::kGeneral) nf.grad(nf.w0, gv);
+    else jtr(J0, r, gv);
 #pragma unroll
     for (int i = 0; i < 6; ++i) unsafeAtomicAdd(g + (size_t)a * 6 + i, gv[i]);
-    jtr(J1, r, gv);
+    if constexpr (LP::kGeneral) nf.grad(nf.w1, gv);
+    else jtr(J1, r, gv);
 #pragma unroll
     for (int i = 0; i < 6; ++i) unsafeAtomicAdd(g + (size_t)b * 6 + i, gv[i]);
 }
@@ -166,12 +191,13 @@ __global__ __launch_bounds__(64) void k_pg_priors(PGView v, TileMap tm, double* 
 }
 
 // ---- SE2 assembly: row-owned ---------------------------------------------------------------------------------------
+template <class LP>
 __global__ __launch_bounds__(256) void k_pg2_assemble(PGView v, TileMap tm, double* __restrict__ g) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= v.n_v) return;
     const uint32_t row = (uint32_t)i;
     double H[9], gv[3];
-    pg2_assemble_row(row, v.posep, v.meas, v.e_from, v.e_to, v.inc_ptr, v.inc_edge, v.huber_delta, H, gv,
+    pg2_assemble_row(row, v.posep, v.meas, v.e_from, v.e_to, v.inc_ptr, v.inc_edge, loss_param<LP>(v), H, gv,
                      [&](uint32_t u, const double* B) {
                          double* blk = h_block_ptr<3>(tm, row, u);
 #pragma unroll
@@ -220,7 +246,7 @@ __global__ __launch_bounds__(64) void k_pg_prior_export(PGView v, double* __rest
     for (int a = 0; a < M::kAmb; ++a) r_out[M::kAmb * o + a] = r[a];
 }
 
-template <class M>
+template <class M, class LP>
 __global__ __launch_bounds__(256) void k_pg_cost_partial(PGView v, double* __restrict__ partial) {
     __shared__ double scratch[4];
     double acc = 0.0;
@@ -237,8 +263,13 @@ __global__ __launch_bounds__(256) void k_pg_cost_partial(PGView v, double* __res
         load_pose<M>(v.meas, e, m);
         M::residual(k0, k1, m, r);
         const double s = sumsq<M::kDof>(r);
-        const double sc = pg_huber_scale(v.huber_delta, s);
-        acc += (sc * sc) * s;
+        if constexpr (LP::kGeneral) {   // |r~|^2 = residual_scaling^2 s: in the second arm that is not rho' s
+            const double sc = pg_loss_corrector(v.loss, s).residual_scaling;
+            acc += (sc * sc) * s;
+        } else {
+            const double sc = pg_huber_scale(v.huber_delta, s);
+            acc += (sc * sc) * s;
+        }
     }
     acc = block_sum_256(acc, scratch);
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
@@ -265,7 +296,7 @@ __global__ __launch_bounds__(256) void k_pg_negate(int64_t n, const double* __re
     if (i < n) y[i] = -x[i];
 }
 
-template <class M>
+template <class M, class LP>
 __global__ __launch_bounds__(256) void k_pg_export(PGView v, double* __restrict__ r_out, double* __restrict__ j_out) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= v.n_e) return;
@@ -273,7 +304,7 @@ __global__ __launch_bounds__(256) void k_pg_export(PGView v, double* __restrict_
     load_pose<M>(v.posep, v.e_from[e], k0);
     load_pose<M>(v.posep, v.e_to[e], k1);
     load_pose<M>(v.meas, e, m);
-    M::export_edge(k0, k1, m, v.huber_delta, r_out ? r_out + M::kDof * e : nullptr,
+    M::export_edge(k0, k1, m, loss_param<LP>(v), r_out ? r_out + M::kDof * e : nullptr,
                    j_out ? j_out + 2 * M::kDof * M::kDof * e : nullptr);
 }
 
@@ -283,7 +314,7 @@ __global__ __launch_bounds__(256) void k_pg_export(PGView v, double* __restrict_
 // A self-loop reads both of its vertex segments from the same place, so both Jacobians land on one vertex by themselves.  A
 // prior block is J~ = sc [I_dof; 0]: it adds sc^2 a_v.a_v etc.  No atomics: partial[3 block + k], then k_sum_partials in index
 // order -- two calls on one state give the same bits, on both manifolds.
-template <class M>
+template <class M, class LP>
 __global__ __launch_bounds__(256) void k_pg_jv_gram(PGView v, const double* __restrict__ a, const double* __restrict__ b,
                                                      double* __restrict__ partial) {
     __shared__ double scratch[4];
@@ -314,7 +345,7 @@ __global__ __launch_bounds__(256) void k_pg_jv_gram(PGView v, const double* __re
             a0[i] = a[(size_t)D * from + i]; a1[i] = a[(size_t)D * to + i];
             b0[i] = b[(size_t)D * from + i]; b1[i] = b[(size_t)D * to + i];
         }
-        M::edge_jv(k0, k1, m, v.huber_delta, a0, a1, b0, b1, u, w);
+        M::edge_jv(k0, k1, m, loss_param<LP>(v), a0, a1, b0, b1, u, w);
         double su = 0.0, sx = 0.0, sw = 0.0;
 #pragma unroll
         for (int i = 0; i < D; ++i) { su += u[i] * u[i]; sx += u[i] * w[i]; sw += w[i] * w[i]; }
@@ -382,6 +413,12 @@ static inline void with_manifold(int manifold, F f) {
     if (manifold == kManifoldSE2) f(Se2Manifold{});
     else f(Se3Manifold{});
 }
+// the one place a view's loss becomes a policy type: the legacy instantiation unless a loss was set through apexgpu_pg_set_loss
+template <class F>
+static inline void with_loss(const PGView& v, F f) {
+    if (v.loss.kind != kLossNone) f(LossGeneral{});
+    else f(LossLegacy{});
+}
 
 void launch_pg_prepare(int manifold, int64_t n, const double* poses, double* posep, hipStream_t s) {
     if (n <= 0) return;
@@ -392,10 +429,16 @@ void launch_pg_prepare(int manifold, int64_t n, const double* poses, double* pos
 void launch_pg_assemble(int manifold, const PGView& v, const TileMap& tm, double* g, hipStream_t s) {
     const dim3 prior_grid((v.n_prior + 63) / 64);
     if (manifold == kManifoldSE2) {
-        if (v.n_v > 0) hipLaunchKernelGGL(k_pg2_assemble, dim3(grid256(v.n_v)), dim3(256), 0, s, v, tm, g);
+        if (v.n_v > 0)
+            with_loss(v, [&](auto LP) {
+                hipLaunchKernelGGL(k_pg2_assemble<decltype(LP)>, dim3(grid256(v.n_v)), dim3(256), 0, s, v, tm, g);
+            });
         if (v.n_prior > 0) hipLaunchKernelGGL(k_pg2_priors, prior_grid, dim3(64), 0, s, v, tm, g);
     } else {
-        if (v.n_e > 0) hipLaunchKernelGGL(k_pg_edges, dim3(grid256(v.n_e)), dim3(256), 0, s, v, tm, g);
+        if (v.n_e > 0)
+            with_loss(v, [&](auto LP) {
+                hipLaunchKernelGGL(k_pg_edges<decltype(LP)>, dim3(grid256(v.n_e)), dim3(256), 0, s, v, tm, g);
+            });
         if (v.n_prior > 0) hipLaunchKernelGGL(k_pg_priors, prior_grid, dim3(64), 0, s, v, tm, g);
     }
 }
@@ -407,7 +450,9 @@ void launch_pg_prior_export(int manifold, const PGView& v, double* r_out, hipStr
 }
 void launch_pg_cost(int manifold, const PGView& v, double* partial, int n_partial, double* out_sumsq, hipStream_t s) {
     with_manifold(manifold, [&](auto M) {
-        hipLaunchKernelGGL(k_pg_cost_partial<decltype(M)>, dim3(n_partial), dim3(256), 0, s, v, partial);
+        with_loss(v, [&](auto LP) {
+            hipLaunchKernelGGL((k_pg_cost_partial<decltype(M), decltype(LP)>), dim3(n_partial), dim3(256), 0, s, v, partial);
+        });
     });
     launch_sum_partials(partial, n_partial, 1, out_sumsq, s);
 }
@@ -424,14 +469,18 @@ void launch_pg_negate(int64_t n, const double* x, double* y, hipStream_t s) {
 void launch_pg_export(int manifold, const PGView& v, double* r_out, double* j_out, hipStream_t s) {
     if (v.n_e <= 0) return;
     with_manifold(manifold, [&](auto M) {
-        hipLaunchKernelGGL(k_pg_export<decltype(M)>, dim3(grid256(v.n_e)), dim3(256), 0, s, v, r_out, j_out);
+        with_loss(v, [&](auto LP) {
+            hipLaunchKernelGGL((k_pg_export<decltype(M), decltype(LP)>), dim3(grid256(v.n_e)), dim3(256), 0, s, v, r_out, j_out);
+        });
     });
 }
 
 void launch_pg_jv_gram(int manifold, const PGView& v, const double* a, const double* b, double* partial, int n_partial,
                        double* out3, hipStream_t s) {
     with_manifold(manifold, [&](auto M) {
-        hipLaunchKernelGGL(k_pg_jv_gram<decltype(M)>, dim3(n_partial), dim3(256), 0, s, v, a, b, partial);
+        with_loss(v, [&](auto LP) {
+            hipLaunchKernelGGL((k_pg_jv_gram<decltype(M), decltype(LP)>), dim3(n_partial), dim3(256), 0, s, v, a, b, partial);
+        });
     });
     launch_sum_partials(partial, n_partial, 3, out3, s);
 }

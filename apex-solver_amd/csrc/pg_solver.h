@@ -36,6 +36,10 @@ class PoseGraphSolver : public TileBackend, public TrBackend {
                       const uint8_t* fix6, double huber_delta);
     int set_params(const double* poses7);
     int set_priors(int64_t n, const uint32_t* vertex, const double* data7, const double* huber_delta);   // PriorFactor blocks
+    // The loss of every BetweenFactor block (pose_graph_g2o.rs:413-436; pg_loss.hpp), in place of set_structure's huber_delta.
+    // Priors keep their per-block Huber delta.  Drops a pending step and the Dog-Leg cache like set_priors.
+    int set_loss(int kind, double p0, double p1);
+    void get_loss(int* kind, double out2[2]) const;
     int get_prior_residual(double* r7_out);
     int get_params(double* poses7);
 
@@ -102,6 +106,8 @@ class PoseGraphSolver : public TileBackend, public TrBackend {
     int manifold_, dof_, amb_, stride_, vpt_;   // vpt_: vertices per tile = kNB / dof_
     int64_t n_ = 0, n_pad_ = 0;
     double huber_delta_ = 0.0;
+    bool loss_set_ = false;   // set_loss has replaced huber_delta_ (until the next set_structure)
+    PgLoss loss_;             // kLossNone unless loss_set_
     bool have_structure_ = false, have_params_ = false;
     std::vector<int64_t> pose_col_;
     std::vector<int> vmap_;  // caller's vertex -> internal vertex

@@ -29,7 +29,14 @@ PGView PoseGraphSolver::view(int which) const {
     PGView v;
     v.n_v = n_v_; v.n_e = n_e_;
     v.posep = posep_[which]; v.e_from = e_from_; v.e_to = e_to_; v.meas = meas_;
+    // set_loss: no loss, L2 and Huber are what the huber_delta kernels compute, so they run there (the same bits as a delta given
+    // to set_structure); every other kind selects the general-loss instantiations through v.loss.kind
     v.huber_delta = huber_delta_;
+    if (loss_set_) {
+        const bool legacy = loss_.kind == kLossNone || loss_.kind == kLossL2 || loss_.kind == kLossHuber;
+        v.huber_delta = loss_.kind == kLossHuber ? loss_.p0 : -1.0;
+        if (!legacy) v.loss = loss_;
+    }
     v.n_prior = n_prior_; v.prior_v = prior_v_; v.prior_data = prior_data_;
     if (manifold_ == kManifoldSE2) {
         v.poses = poses_[which]; v.inc_ptr = inc_ptr_; v.inc_edge = inc_edge_; v.prior_slot = prior_slot_;
@@ -84,6 +91,27 @@ int PoseGraphSolver::set_priors(int64_t n, const uint32_t* vertex, const double*
     return install();
 }
 
+int PoseGraphSolver::set_loss(int kind, double p0, double p1) {
+    if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
+    PgLoss l;
+    if (!pg_loss_make(kind, p0, p1, &l)) return fail(kInvalidInput, "set_loss: unknown loss kind or a parameter its constructor refuses");
+    HIP_TRY(hipSetDevice(device_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    have_step_ = have_trial_ = false;
+    drop_dogleg_cache();
+    loss_ = l;
+    loss_set_ = true;
+    return kOk;
+}
+
+// what the edges carry: the loss of set_loss, else set_structure's Huber delta (or none)
+void PoseGraphSolver::get_loss(int* kind, double out2[2]) const {
+    out2[0] = out2[1] = 0.0;
+    if (loss_set_) { *kind = loss_.kind; out2[0] = loss_.p0; out2[1] = loss_.p1; }
+    else if (huber_delta_ > 0.0) { *kind = kLossHuber; out2[0] = huber_delta_; }
+    else *kind = kLossNone;
+}
+
 int PoseGraphSolver::get_prior_residual(double* r7_out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     if (n_prior_ == 0) return kOk;
@@ -105,6 +133,8 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
     HIP_TRY(hipSetDevice(device_));
     if (!stream_) HIP_TRY(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     huber_delta_ = huber_delta;
+    loss_set_ = false;
+    loss_ = PgLoss{};
     pose_col_.assign(pose_col, pose_col + n_v_);
     n_ = dof_ * n_v_;
     const int nt = (int)((n_ + kNB - 1) / kNB);

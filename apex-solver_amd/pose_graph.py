@@ -172,6 +172,58 @@ def se2_as_vector(pose3) -> np.ndarray:
     return p
 
 
+@dataclass(frozen=True)
+class Loss:
+    """One loss of src/core/loss_functions.rs as the C ABI takes it: kind = capi.LOSS_*, p0 = scale | p | nu | Barron's
+    alpha, p1 = Barron's scale."""
+
+    kind: int
+    p0: float = 0.0
+    p1: float = 0.0
+
+    def evaluate(self, s: float) -> np.ndarray:
+        """[rho, rho', rho'', sqrt_rho1, residual_scaling, alpha_sq_norm] at the squared norm s (host arithmetic of the
+        library: LossFunction::evaluate and Corrector::new)."""
+        o = (C.c_double * 6)()
+        rc = capi.load().apexgpu_loss_evaluate(int(self.kind), float(self.p0), float(self.p1), float(s), C.byref(o))
+        if rc != 0:
+            raise capi.LinAlgError(rc, "loss parameters out of range")
+        return np.array(o[:])
+
+
+# create_loss_function of bin/pose_graph_g2o.rs:256-311: name -> (kind, default scale, how the scale becomes (p0, p1))
+_LOSS_NAMES = {
+    "huber": (capi.LOSS_HUBER, 1.345), "cauchy": (capi.LOSS_CAUCHY, 2.3849), "fair": (capi.LOSS_FAIR, 1.3999),
+    "welsch": (capi.LOSS_WELSCH, 2.9846), "tukey": (capi.LOSS_TUKEY, 4.6851),
+    "geman": (capi.LOSS_GEMAN_MCCLURE, 1.0), "gemanmcclure": (capi.LOSS_GEMAN_MCCLURE, 1.0),
+    "andrews": (capi.LOSS_ANDREWS, 1.339), "ramsay": (capi.LOSS_RAMSAY, 0.3),
+    "trimmed": (capi.LOSS_TRIMMED_MEAN, 2.0), "trimmedmean": (capi.LOSS_TRIMMED_MEAN, 2.0),
+    "lp": (capi.LOSS_LP_NORM, 1.5),
+    "t-distribution": (capi.LOSS_T_DISTRIBUTION, 5.0), "tdistribution": (capi.LOSS_T_DISTRIBUTION, 5.0),
+}
+_BARRON_ALPHA = {"barron0": 0.0, "barron1": 1.0, "barron-2": -2.0, "adaptive-barron": 0.0, "adaptivebarron": 0.0}
+
+
+def create_loss_function(name: str, scale: float | None = None) -> Loss:
+    """`--loss-function NAME --loss-scale SCALE` of bin/pose_graph_g2o.rs:256-311: the seventeen names, their aliases and
+    default scales; case-insensitive.  lp takes the scale as p, t-distribution as nu; l2 and l1 take none."""
+    low = name.lower()
+    if low == "l2":
+        return Loss(capi.LOSS_L2)
+    if low == "l1":
+        return Loss(capi.LOSS_L1)
+    if low in _BARRON_ALPHA:
+        loss = Loss(capi.LOSS_BARRON, _BARRON_ALPHA[low], 1.0 if scale is None else float(scale))
+    elif low in _LOSS_NAMES:
+        kind, default = _LOSS_NAMES[low]
+        loss = Loss(kind, default if scale is None else float(scale))
+    else:
+        raise ValueError(f"Unknown loss function: {name}. Valid options: l2, l1, huber, cauchy, fair, welsch, tukey, geman, "
+                         "andrews, ramsay, trimmed, lp, barron0, barron1, barron-2, t-distribution, adaptive-barron")
+    loss.evaluate(0.0)   # (the constructor's check of the scale: InvalidInput)
+    return loss
+
+
 @dataclass
 class PoseGraphProblem:
     """The factor graph bin/pose_graph_g2o.rs:748-830 builds: variables `x{id}` (SE3), one
@@ -181,8 +233,11 @@ class PoseGraphProblem:
     huber_delta: float | None = None
     fix: np.ndarray = field(default=None)
     priors: list = field(default_factory=list)   # (vertex index, data[7], huber delta or None) per PriorFactor block
+    loss: Loss | None = None   # the loss of every BetweenFactor block; mutually exclusive with huber_delta
 
     def __post_init__(self):
+        if self.loss is not None and self.huber_delta is not None:
+            raise ValueError("PoseGraphProblem: give either loss or huber_delta, not both")
         self.manifold = self.data.manifold
         self.dof, self.ambient = (3, 3) if self.manifold == "se2" else (6, 7)
         if self.fix is None:
@@ -208,9 +263,9 @@ class PoseGraphProblem:
         return self
 
     @classmethod
-    def pose_graph(cls, data: PoseGraphData, huber_delta: float | None = None) -> "PoseGraphProblem":
+    def pose_graph(cls, data: PoseGraphData, huber_delta: float | None = None, loss: Loss | None = None) -> "PoseGraphProblem":
         """The LM set-up: all six DOF of the first vertex fixed (pose_graph_g2o.rs:790-797)."""
-        p = cls(data, huber_delta)
+        p = cls(data, huber_delta, loss=loss)
         for dof in range(p.dof):
             p.fix_variable(f"x{int(data.ids[0])}", dof)
         return p
@@ -316,9 +371,23 @@ class GpuSparseCholeskySolver:
         delta = -1.0 if problem.huber_delta is None else float(problem.huber_delta)
         h.check(h.L.apexgpu_pg_set_structure(h.h, capi.ptr(ef), capi.ptr(et), capi.ptr(meas), capi.ptr(col), capi.ptr(fix), delta))
         self._h, self.problem = h, problem
+        if problem.loss is not None:
+            self.set_loss(problem.loss)
         if problem.priors:
             self.set_priors(problem.priors)
         return self
+
+    def set_loss(self, loss: Loss | None):
+        """The loss of every BetweenFactor block from here on (None: no loss); replaces the problem's huber_delta."""
+        h = self._need()
+        loss = Loss(capi.LOSS_NONE) if loss is None else loss
+        h.check(h.L.apexgpu_pg_set_loss(h.h, int(loss.kind), float(loss.p0), float(loss.p1)))
+
+    def get_loss(self) -> Loss:
+        h = self._need()
+        k = C.c_int(); p = (C.c_double * 2)()
+        h.check(h.L.apexgpu_pg_get_loss(h.h, C.byref(k), C.byref(p)))
+        return Loss(k.value, p[0], p[1])
 
     def set_priors(self, priors):
         """PriorFactor blocks: (vertex index, data[7], huber delta or None) each; replaces the set."""

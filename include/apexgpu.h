@@ -600,6 +600,38 @@ int apexgpu_pg_set_structure(apexgpu_pg_solver* h, const uint32_t* e_from, const
  * (SE2 -> DVector, se2.rs:55-63: UnitComplex::angle). */
 int apexgpu_pg_set_priors(apexgpu_pg_solver* h, int64_t n, const uint32_t* vertex, const double* data7, const double* huber_delta);
 int apexgpu_pg_get_prior_residual(apexgpu_pg_solver* h, double* r7_out);
+
+/* ---- robust loss family of the pose-graph front end (bin/pose_graph_g2o.rs:256-311, src/core/loss_functions.rs) ----------
+ * p0 = scale (HUBER, CAUCHY, FAIR, GEMAN_MCCLURE, WELSCH, TUKEY, ANDREWS, RAMSAY, TRIMMED_MEAN) | p (LP_NORM) |
+ * nu (T_DISTRIBUTION) | alpha (BARRON); p1 = BARRON's scale; ignored otherwise.  AdaptiveBarron is BARRON. */
+#define APEXGPU_LOSS_NONE 0
+#define APEXGPU_LOSS_L2 1
+#define APEXGPU_LOSS_L1 2
+#define APEXGPU_LOSS_HUBER 3
+#define APEXGPU_LOSS_CAUCHY 4
+#define APEXGPU_LOSS_FAIR 5
+#define APEXGPU_LOSS_GEMAN_MCCLURE 6
+#define APEXGPU_LOSS_WELSCH 7
+#define APEXGPU_LOSS_TUKEY 8
+#define APEXGPU_LOSS_ANDREWS 9
+#define APEXGPU_LOSS_RAMSAY 10
+#define APEXGPU_LOSS_TRIMMED_MEAN 11
+#define APEXGPU_LOSS_LP_NORM 12
+#define APEXGPU_LOSS_BARRON 13
+#define APEXGPU_LOSS_T_DISTRIBUTION 14
+/* The loss of every BetweenFactor block (pose_graph_g2o.rs:413-436), with the full corrector (src/core/corrector.rs:143-181,
+ * 241-253: where rho'' > 0 the residual is rescaled and the Jacobian gets a rank-one correction).  After
+ * apexgpu_pg_set_structure; replaces huber_delta's loss until the next set_structure; prior blocks keep their own Huber
+ * delta.  Invalidates a pending step and a cached Dog-Leg solve like apexgpu_pg_set_priors.  An edge whose rho' is 0
+ * contributes nothing; if that empties a pivot the solve answers APEXGPU_ERR_SINGULAR_MATRIX.
+ * APEXGPU_ERR_INVALID_INPUT where the reference's new() fails (scale <= 0, p <= 0, nu <= 0), for a NaN parameter (which the
+ * reference would accept) or where kind is unknown;
+ * APEXGPU_ERR_INVALID_STATE before set_structure.  APEXGPU_LOSS_NONE: no loss. */
+int apexgpu_pg_set_loss(apexgpu_pg_solver* h, int kind, double p0, double p1);
+/* what the edges carry: the loss of set_loss, else HUBER with set_structure's delta, else NONE; out2 = {p0, p1} */
+int apexgpu_pg_get_loss(const apexgpu_pg_solver* h, int* kind, double out2[2]);
+/* host only, no device: out6 = { rho, rho', rho'', sqrt_rho1, residual_scaling, alpha_sq_norm } at squared norm s */
+int apexgpu_loss_evaluate(int kind, double p0, double p1, double s, double out6[6]);
 int apexgpu_pg_set_params(apexgpu_pg_solver* h, const double* poses7);
 int apexgpu_pg_get_params(apexgpu_pg_solver* h, double* poses7);
 
