@@ -45,17 +45,11 @@ class PoseGraphSolver : public TileBackend, public TrBackend {
 
     int cost(double* out) override;
     int solve_augmented(double lambda, int variant, double* step_out, double* grad_out) override;
-    int step_stats(double out3[3]) override;
-    int eval_step(double* trial_cost) override;
-    void enqueue_step_stats();                       // (the kernels of the two calls above, without the read-back)
-    void enqueue_trial_point(double* sumsq_out);
-    int commit_step() override;
-    int discard_step() override;
     int parameter_norm(double* out) override;
     int lm_optimize(LmConfig* cfg, LmResult* res, LmIterRecord* hist, int hist_cap);
     // Gauss-Newton and Dog-Leg (tr_loop.h).  dogleg_step runs to ONE host wait, fresh or reused: behind the sweeps come the inner
     // products, the Gram pass over the edges (k_pg_jv_gram), the combine (one lane), the blended step into d_, the trial point
-    // and its cost; step_stats / eval_step then answer from the host.  A reused step starts at the combine: the six sums of
+    // and its cost, posted as this solve's answers: step_stats / eval_step then answer from the host.  A reused step starts at the combine: the six sums of
     // the last fresh solve, g_ and the cached Gauss-Newton step (hgn_) are all it reads.
     int dogleg_step(double mu, double radius, int reuse, DoglegStepInfo* out) override;
     int gn_optimize(GnConfig* cfg, LmResult* res, LmIterRecord* hist, int hist_cap);
@@ -95,10 +89,15 @@ class PoseGraphSolver : public TileBackend, public TrBackend {
     int finish_step(double* step_out, double* grad_out) override;
     int recover_factor(double lambda, int failed, bool gave_up) override;
     PGView view(int which) const;
-    void enqueue_retract(int from, double sign, int to);   // retraction + the prepared poses of the result
+    int enqueue_step_stats() override;
+    int enqueue_trial_point(double* sumsq_out) override;
+    int enqueue_retract(int from, double sign, int to) override;   // retraction + the prepared poses of the result
+    // scal_: [1..3] the step's sums, [4] the trial point's sum of squares -- read here only
+    double* step_sums(int* n) override { *n = 3; return scal_ + 1; }
+    StepAnswers answers_from_sums(const double* h) const override { return {sqrt(h[0]), sqrt(h[1]), 0.5 * h[2], h[3]}; }
     int assemble(double lambda);
     int ensure_scale_buffer();
-    int cost_of(int which, double* out);
+    int solve_damped(double lambda, double* step_out, double* grad_out);   // solve_augmented behind its checks; the fresh Dog-Leg solve
     int enqueue_dogleg_tail(bool fresh);   // everything of a Dog-Leg step behind the sweeps, up to the copy to dl_host_
     void drop_dogleg_cache() { have_dl_cache_ = false; }
 
@@ -133,7 +132,6 @@ class PoseGraphSolver : public TileBackend, public TrBackend {
     double dl_radius_ = 0.0;
     bool dl_mode_ = false;         // finish_step: the Dog-Leg tail instead of the LM statistics
     bool have_dl_cache_ = false;   // g_, hgn_, dls_[0..5] belong to one solve and scale_ is what it was then
-    bool step_is_dl_ = false;      // the step in d_ is a Dog-Leg step: step_stats / eval_step answer from dl_host_
 };
 
 }  // namespace apex

@@ -44,9 +44,12 @@ PGView PoseGraphSolver::view(int which) const {
     return v;
 }
 
-void PoseGraphSolver::enqueue_retract(int from, double sign, int to) {
+int PoseGraphSolver::enqueue_retract(int from, double sign, int to) {
+    timer_.begin(kPgRetract, stream_);
     launch_pg_retract(manifold_, n_v_, poses_[from], d_, sign, fix_, poses_[to], stream_);
     launch_pg_prepare(manifold_, n_v_, poses_[to], posep_[to], stream_);
+    timer_.end(kPgRetract, stream_);
+    return kOk;
 }
 
 // PriorFactor blocks (prior_factor.rs:96-108); replaces the set.  data7 in to_vector order [t, w, i, j, k].
@@ -57,7 +60,7 @@ int PoseGraphSolver::set_priors(int64_t n, const uint32_t* vertex, const double*
         if ((int64_t)vertex[k] >= n_v_) return fail(kInvalidInput, "prior on a vertex that does not exist");
     HIP_TRY(hipSetDevice(device_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    have_step_ = have_trial_ = false;
+    st_.invalidate();
     drop_dogleg_cache();
     // The new set goes up into locals and replaces the members (and n_prior_) only when every upload has succeeded: a failed
     // call leaves the old priors fully in place, a call with n = 0 none at all.
@@ -97,7 +100,7 @@ int PoseGraphSolver::set_loss(int kind, double p0, double p1) {
     if (!pg_loss_make(kind, p0, p1, &l)) return fail(kInvalidInput, "set_loss: unknown loss kind or a parameter its constructor refuses");
     HIP_TRY(hipSetDevice(device_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    have_step_ = have_trial_ = false;
+    st_.invalidate();
     drop_dogleg_cache();
     loss_ = l;
     loss_set_ = true;
@@ -117,7 +120,7 @@ int PoseGraphSolver::get_prior_residual(double* r7_out) {
     if (n_prior_ == 0) return kOk;
     HIP_TRY(hipSetDevice(device_));
     if (!prior_res_) HIP_TRY(prior_res_.alloc((size_t)n_prior_ * amb_));   // kept with the priors (set_priors frees it)
-    launch_pg_prior_export(manifold_, view(cur_), prior_res_, stream_);
+    launch_pg_prior_export(manifold_, view(st_.cur), prior_res_, stream_);
     HIP_TRY(hipMemcpyAsync(r7_out, prior_res_, (size_t)n_prior_ * amb_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     return kOk;
@@ -195,10 +198,10 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
     HIP_TRY(scal_.alloc_zero(16));
     HIP_TRY(hipDeviceSynchronize());
     have_structure_ = true;
-    have_params_ = have_step_ = have_trial_ = false;
+    have_params_ = false; st_.invalidate();
     drop_dogleg_cache();
     hgn_.reset(); dl_a_.reset(); dls_.reset();   // (sized by the old structure: dogleg_step allocates them again)
-    cur_ = 0;
+    st_.cur = 0;
     return kOk;
 }
 
@@ -209,10 +212,10 @@ int PoseGraphSolver::set_params(const double* poses7) {
     for (int64_t v = 0; v < n_v_; ++v) memcpy(hp.data() + amb_ * (size_t)vmap_[v], poses7 + (size_t)amb_ * v, amb_ * sizeof(double));
     if (manifold_ == kManifoldSE2)   // the variable is held as SE2 -> DVector gives it: theta in (-pi, pi] (se2.rs:55-63)
         for (int64_t v = 0; v < n_v_; ++v) hp[3 * (size_t)v + 2] = se2_wrap_angle(hp[3 * (size_t)v + 2]);
-    HIP_TRY(hipMemcpyAsync(poses_[cur_], hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
-    launch_pg_prepare(manifold_, n_v_, poses_[cur_], posep_[cur_], stream_);
+    HIP_TRY(hipMemcpyAsync(poses_[st_.cur], hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+    launch_pg_prepare(manifold_, n_v_, poses_[st_.cur], posep_[st_.cur], stream_);
     HIP_TRY(hipStreamSynchronize(stream_));
-    have_params_ = true; have_step_ = have_trial_ = false;
+    have_params_ = true; st_.invalidate();
     drop_dogleg_cache();
     return kOk;
 }
@@ -221,28 +224,23 @@ int PoseGraphSolver::get_params(double* poses7) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
     std::vector<double> hp(amb_ * (size_t)n_v_);
-    HIP_TRY(hipMemcpyAsync(hp.data(), poses_[cur_], hp.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(hp.data(), poses_[st_.cur], hp.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     for (int64_t v = 0; v < n_v_; ++v) memcpy(poses7 + (size_t)amb_ * v, hp.data() + amb_ * (size_t)vmap_[v], amb_ * sizeof(double));
-    return kOk;
-}
-
-int PoseGraphSolver::cost_of(int which, double* out) {
-    timer_.begin(kPgCost, stream_);
-    launch_pg_cost(manifold_, view(which), partial_, n_partial_, scal_, stream_);
-    timer_.end(kPgCost, stream_);
-    double ss = 0.0;
-    HIP_TRY(hipMemcpyAsync(&ss, scal_, sizeof(double), hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    const double nrm = sqrt(ss);  // compute_cost: 0.5 * norm_l2()^2 (optimizer/mod.rs:358-361)
-    *out = 0.5 * nrm * nrm;
     return kOk;
 }
 
 int PoseGraphSolver::cost(double* out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    return cost_of(cur_, out);
+    timer_.begin(kPgCost, stream_);
+    launch_pg_cost(manifold_, view(st_.cur), partial_, n_partial_, scal_, stream_);
+    timer_.end(kPgCost, stream_);
+    double ss = 0.0;
+    HIP_TRY(hipMemcpyAsync(&ss, scal_, sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    *out = cost_from_sumsq(ss);
+    return kOk;
 }
 
 // H + lambda I (tiles) and g = J^T r at the current parameters
@@ -252,7 +250,7 @@ int PoseGraphSolver::assemble(double lambda) {
     HIP_TRY(tp_.zero_tiles());
     HIP_TRY(hipMemsetAsync(g_, 0, n_pad_ * sizeof(double), stream_));
     tp_.add_diag((int)n_, scaled_ ? 0.0 : lambda, 1.0);  // lambda on the real rows, identity on the padding rows
-    launch_pg_assemble(manifold_, view(cur_), tp_.tilemap(), g_, stream_);
+    launch_pg_assemble(manifold_, view(st_.cur), tp_.tilemap(), g_, stream_);
     if (scaled_) {  // Jacobi scaling: H := D H D, then the damping of the scaled system
         tp_.scale_sym(scale_);
         tp_.add_diag((int)n_, lambda, 1.0);
@@ -291,9 +289,11 @@ int PoseGraphSolver::solve_augmented(double lambda, int variant, double* step_ou
     if (!have_params_) return fail(kInvalidState, "Block structure not built or parameters not set");
     if (variant != 0) return fail(kInvalidInput, "the pose-graph backend has the sparse Cholesky solver only");
     HIP_TRY(hipSetDevice(device_));
+    return solve_damped(lambda, step_out, grad_out);
+}
+int PoseGraphSolver::solve_damped(double lambda, double* step_out, double* grad_out) {
     begin_solve(lambda);
-    step_is_dl_ = false;
-    int rc = rebuild_system(lambda, 0.0);
+    int rc = rebuild_system(lambda, 0.0);   // (drops the Dog-Leg cache)
     if (rc == kOk && !one_wait_) {   // the flags are waited for right behind the factorisation
         int failed = 0;
         rc = factor_fresh(lambda, 0.0, &failed);
@@ -311,19 +311,14 @@ int PoseGraphSolver::enqueue_sweeps() {
 }
 
 int PoseGraphSolver::finish_step(double* step_out, double* grad_out) {
-    have_step_ = true;
+    st_.step_computed();
     if (dl_mode_) {   // dogleg_step: the sweeps have left the Gauss-Newton step in d_
         const int rc = enqueue_dogleg_tail(true);
         if (rc != kOk) return rc;
         HIP_TRY(hipStreamSynchronize(stream_));
         return kOk;
     }
-    if (eager_eval_) {   // what the LM loop asks next rides on this solve's wait: eager_host_ [0..2] step statistics, [3] sum of squares at the trial point
-        if (!eager_host_) HIP_TRY(eager_host_.alloc(8));
-        enqueue_step_stats();
-        enqueue_trial_point(scal_ + 4);
-        HIP_TRY(hipMemcpyAsync(eager_host_, scal_ + 1, 4 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    }
+    if (eager_eval_) { const int rc = enqueue_eager_eval(); if (rc != kOk) return rc; }   // what the LM loop asks next rides on this solve's wait
     if (step_out || grad_out) {
         std::vector<double> h(n_);
         for (int pass = 0; pass < 2; ++pass) {
@@ -339,93 +334,29 @@ int PoseGraphSolver::finish_step(double* step_out, double* grad_out) {
     } else {
         HIP_TRY(hipStreamSynchronize(stream_));
     }
-    if (eager_eval_) eager_serial_ = step_serial_;   // (the answers of THIS solve)
+    if (eager_eval_) post_eager_answers();
     return kOk;
 }
 
-void PoseGraphSolver::enqueue_step_stats() {
+int PoseGraphSolver::enqueue_step_stats() {
     timer_.begin(kPgStats, stream_);
     launch_step_stats(n_, g_, d_, last_lambda_, scaled_ ? scale_ : nullptr, partial_, n_partial_, scal_ + 1, stream_);
     timer_.end(kPgStats, stream_);
+    return kOk;
 }
-void PoseGraphSolver::enqueue_trial_point(double* sumsq_out) {
-    const int t = cur_ ^ 1;
-    timer_.begin(kPgRetract, stream_);
-    enqueue_retract(cur_, 1.0, t);
-    timer_.end(kPgRetract, stream_);
+int PoseGraphSolver::enqueue_trial_point(double* sumsq_out) {
+    const int t = st_.cur ^ 1;
+    enqueue_retract(st_.cur, 1.0, t);
     timer_.begin(kPgCost, stream_);
     launch_pg_cost(manifold_, view(t), partial_, n_partial_, sumsq_out, stream_);
     timer_.end(kPgCost, stream_);
-}
-
-int PoseGraphSolver::step_stats(double out3[3]) {
-    if (!have_step_) return fail(kInvalidState, "no step computed");
-    if (step_is_dl_) {   // |g_s|, |step|, -s.g - 1/2 s.Hs (dog_leg.rs:1046, 1222, 948-960)
-        out3[0] = sqrt(dl_host_[0]); out3[1] = sqrt(dl_host_[13]); out3[2] = dl_host_[11];
-        return kOk;
-    }
-    if (answered_at_wait()) {
-        out3[0] = sqrt(eager_host_[0]); out3[1] = sqrt(eager_host_[1]); out3[2] = 0.5 * eager_host_[2];
-        return kOk;
-    }
-    HIP_TRY(hipSetDevice(device_));
-    enqueue_step_stats();
-    double h[3];
-    HIP_TRY(hipMemcpyAsync(h, scal_ + 1, sizeof h, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    out3[0] = sqrt(h[0]);   // gradient.norm_l2()          (levenberg_marquardt.rs:746)
-    out3[1] = sqrt(h[1]);   // step.norm_l2()              (:890)
-    out3[2] = 0.5 * h[2];   // compute_predicted_reduction (:721-727)
-    return kOk;
-}
-
-int PoseGraphSolver::eval_step(double* trial_cost) {
-    if (!have_step_) return fail(kInvalidState, "no step computed");
-    if (step_is_dl_) {   // dogleg_step has put the trial point in place
-        have_trial_ = true;
-        const double nrm = sqrt(dl_host_[14]);
-        *trial_cost = 0.5 * nrm * nrm;
-        return kOk;
-    }
-    if (answered_at_wait()) {   // the trial point is in place
-        have_trial_ = true;
-        const double nrm = sqrt(eager_host_[3]);
-        *trial_cost = 0.5 * nrm * nrm;
-        return kOk;
-    }
-    HIP_TRY(hipSetDevice(device_));
-    const int t = cur_ ^ 1;
-    timer_.begin(kPgRetract, stream_);
-    enqueue_retract(cur_, 1.0, t);
-    timer_.end(kPgRetract, stream_);
-    have_trial_ = true;
-    return cost_of(t, trial_cost);
-}
-
-int PoseGraphSolver::commit_step() {
-    if (!have_trial_) return fail(kInvalidState, "no trial point");
-    cur_ ^= 1;
-    have_trial_ = false; have_step_ = false;
-    return kOk;
-}
-
-// apply_negative_parameter_step (optimizer/mod.rs:343-356): inverse retraction of the trial point
-int PoseGraphSolver::discard_step() {
-    if (!have_trial_) return fail(kInvalidState, "no trial point");
-    HIP_TRY(hipSetDevice(device_));
-    const int t = cur_ ^ 1;
-    timer_.begin(kPgRetract, stream_);
-    enqueue_retract(t, -1.0, cur_);
-    timer_.end(kPgRetract, stream_);
-    HIP_TRY(hipStreamSynchronize(stream_));
-    have_trial_ = false; have_step_ = false;
     return kOk;
 }
 
 int PoseGraphSolver::parameter_norm(double* out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    launch_sumsq(amb_ * n_v_, poses_[cur_], partial_, n_partial_, scal_ + 4, stream_);
+    launch_sumsq(amb_ * n_v_, poses_[st_.cur], partial_, n_partial_, scal_ + 4, stream_);
     double h = 0.0;
     HIP_TRY(hipMemcpyAsync(&h, scal_ + 4, sizeof h, hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
@@ -452,7 +383,7 @@ int PoseGraphSolver::column_norms(double* norms_out) {
     int rc = assemble(0.0);
     scaled_ = was;
     if (rc != kOk) return rc;
-    have_step_ = false;
+    st_.invalidate_step();
     tp_.diag(work_);
     std::vector<double> h(n_);
     HIP_TRY(hipMemcpyAsync(h.data(), work_, n_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
@@ -465,7 +396,7 @@ int PoseGraphSolver::column_norms(double* norms_out) {
 int PoseGraphSolver::set_column_scaling(const double* scaling) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built");
     HIP_TRY(hipSetDevice(device_));
-    have_step_ = false;
+    st_.invalidate_step();
     drop_dogleg_cache();
     if (!scaling) { scaled_ = false; return kOk; }
     int rc = ensure_scale_buffer();
@@ -481,7 +412,7 @@ int PoseGraphSolver::set_column_scaling(const double* scaling) {
 }
 
 int PoseGraphSolver::set_jacobi_scaling(bool on) {
-    if (!on) { scaled_ = false; have_step_ = false; drop_dogleg_cache(); return kOk; }
+    if (!on) { scaled_ = false; st_.invalidate_step(); drop_dogleg_cache(); return kOk; }
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
     int rc = ensure_scale_buffer();
@@ -494,7 +425,7 @@ int PoseGraphSolver::set_jacobi_scaling(bool on) {
     scale_h_.resize(n_);
     HIP_TRY(hipMemcpyAsync(scale_h_.data(), scale_, n_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    scaled_ = true; have_step_ = false;
+    scaled_ = true; st_.invalidate_step();
     return kOk;
 }
 
@@ -511,7 +442,7 @@ int PoseGraphSolver::enqueue_dogleg_tail(bool fresh) {
         // g_s = D g, y = D^-1 d: g_s.g_s, y.y, g_s.y; then g_s.H_s g_s = |J D g_s|^2, g_s.H_s y = (J D g_s).(J D y), y.H_s y = |J D y|^2 with
         // D y = d, the unscaled step the sweeps left -- the Gram kernel never sees D
         launch_dl_dots(n_, g_, d_, sc, scaled_ ? dl_a_.get() : nullptr, hgn_, partial_, n_partial_, dls_, stream_);
-        launch_pg_jv_gram(manifold_, view(cur_), scaled_ ? dl_a_.get() : g_.get(), d_, partial_, n_partial_, dls_ + 3, stream_);
+        launch_pg_jv_gram(manifold_, view(st_.cur), scaled_ ? dl_a_.get() : g_.get(), d_, partial_, n_partial_, dls_ + 3, stream_);
     }
     launch_dl_combine(dls_, dl_radius_, dls_ + 6, stream_);
     launch_dl_blend(n_, g_, sc, hgn_, dls_ + 8, d_, partial_, n_partial_, dls_ + 13, stream_);
@@ -539,24 +470,17 @@ int PoseGraphSolver::dogleg_step(double mu, double radius, int reuse, DoglegStep
         begin_solve(last_lambda_);
         rc = enqueue_dogleg_tail(false);
         if (rc == kOk) rc = check_hip(hipStreamSynchronize(stream_), "dogleg_step");
-        if (rc == kOk) have_step_ = true;
+        if (rc == kOk) st_.step_computed();
     } else {
-        begin_solve(mu);
         dl_mode_ = true;
-        rc = rebuild_system(mu, 0.0);   // (drops the cache)
-        if (rc == kOk && !one_wait_) {
-            int failed = 0;
-            rc = factor_fresh(mu, 0.0, &failed);
-            if (rc == kOk) rc = recover_factor(mu, failed, false);
-        }
-        if (rc == kOk) rc = direct_solve(one_wait_, mu, nullptr, nullptr);
+        rc = solve_damped(mu, nullptr, nullptr);
         dl_mode_ = false;
         if (rc == kOk) have_dl_cache_ = true;
     }
     if (rc != kOk) return rc;
-    step_is_dl_ = true;
+    const double* h = dl_host_;   // |g_s|, |step|, -s.g - 1/2 s.Hs (dog_leg.rs:1046, 1222, 948-960); the trial point is in place
+    st_.post_answers({sqrt(h[0]), sqrt(h[13]), h[11], h[14]});
     if (out) {
-        const double* h = dl_host_;
         out->gradient_norm = sqrt(h[0]); out->step_norm = sqrt(h[13]); out->predicted_reduction = h[11]; out->step_type = h[12];
         out->alpha = h[6]; out->beta = h[7]; out->scaled_step_norm = h[10]; out->reused = reuse ? 1.0 : 0.0;
     }
@@ -589,7 +513,7 @@ int PoseGraphSolver::jv_gram(const double* a, const double* b, double out3[3]) {
     HIP_TRY(hipStreamSynchronize(stream_));
     HIP_TRY(da.upload(ha));
     HIP_TRY(db.upload(hb));
-    launch_pg_jv_gram(manifold_, view(cur_), da, db, partial_, n_partial_, scal_ + 5, stream_);
+    launch_pg_jv_gram(manifold_, view(st_.cur), da, db, partial_, n_partial_, scal_ + 5, stream_);
     hipError_t e = hipMemcpyAsync(out3, scal_ + 5, 3 * sizeof(double), hipMemcpyDeviceToHost, stream_);
     (void)hipStreamSynchronize(stream_);   // (before da / db are freed)
     return check_hip(e, "jv_gram");
@@ -601,7 +525,7 @@ int PoseGraphSolver::get_residual(double* r_out) {
     HIP_TRY(hipSetDevice(device_));
     DeviceBuffer<double> d;
     HIP_TRY(d.alloc(dof_ * (size_t)n_e_));
-    launch_pg_export(manifold_, view(cur_), d, nullptr, stream_);
+    launch_pg_export(manifold_, view(st_.cur), d, nullptr, stream_);
     hipError_t e = hipMemcpyAsync(r_out, d, dof_ * n_e_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     (void)hipStreamSynchronize(stream_);
     return check_hip(e, "get_residual");
@@ -613,7 +537,7 @@ int PoseGraphSolver::get_jacobian_blocks(double* j_out) {
     DeviceBuffer<double> d;
     const size_t jn = 2 * (size_t)dof_ * dof_;   // [dof][2 dof] per edge
     HIP_TRY(d.alloc(jn * (size_t)n_e_));
-    launch_pg_export(manifold_, view(cur_), nullptr, d, stream_);
+    launch_pg_export(manifold_, view(st_.cur), nullptr, d, stream_);
     hipError_t e = hipMemcpyAsync(j_out, d, jn * n_e_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     (void)hipStreamSynchronize(stream_);
     return check_hip(e, "get_jacobian_blocks");
@@ -624,7 +548,7 @@ int PoseGraphSolver::get_hessian(double lambda, double* H_out, double* g_out) {
     HIP_TRY(hipSetDevice(device_));
     int rc = assemble(lambda);
     if (rc != kOk) return rc;
-    have_step_ = false;
+    st_.invalidate_step();
     const size_t tile_elems = (size_t)kNB * kNB;
     std::vector<int64_t> col(n_, -1);
     for (int64_t v = 0; v < n_v_; ++v)

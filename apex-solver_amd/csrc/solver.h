@@ -43,12 +43,6 @@ class Solver : public TileBackend {
     int cost(double* out) override;                         // A16 on the current parameters
     int solve_augmented(double lambda, int variant, double* step_out, double* grad_out) override;
     int assemble_only(double lambda);
-    int step_stats(double out3[3]) override;                // |g|, |step|, predicted reduction
-    int eval_step(double* trial_cost) override;             // x (+) step into the trial set, A16 there
-    int enqueue_step_stats();                               // (the kernels of the two calls above, without the read-back)
-    int enqueue_trial_point(double* sumsq_out);
-    int commit_step() override;
-    int discard_step() override;                            // reference semantics: trial (+) (-step)
     int parameter_norm(double* out) override;
     int lm_optimize(LmConfig* cfg, LmResult* res, LmIterRecord* hist, int hist_cap);
     // Jacobi column scaling (optimizer/mod.rs:749-763; AssemblyBackend::compute_column_norms / apply_column_scaling,
@@ -158,6 +152,14 @@ class Solver : public TileBackend {
     const int* own_flag() const override { return flags_; }
     int own_flag_raised() override { return fail(kSingularMatrix, "Landmark block is singular"); }
     void keep_factor() override;
+    int enqueue_step_stats() override;
+    int enqueue_trial_point(double* sumsq_out) override;
+    int enqueue_retract(int from, double sign, int to) override { retract_sets(from, sign, to, n_pt_); return kOk; }
+    // scal_: [0..5] the camera and the landmark half of the step's sums, [6] the trial point's sum of squares -- read here only
+    double* step_sums(int* n) override { *n = 6; return scal_; }
+    StepAnswers answers_from_sums(const double* h) const override { return {sqrt(h[0] + h[3]), sqrt(h[1] + h[4]), 0.5 * (h[2] + h[5]), h[6]}; }
+    void params_moved() override { orec_fresh_ = false; }
+    void retract_sets(int from, double sign, int to, int64_t n_pt);
     BAView view(int which) const;
     TileMap tilemap() const;
     // for_factor: the result feeds tp_.factor() (a distributed plan then leaves the top tiles to the factorisation's
@@ -173,7 +175,6 @@ class Solver : public TileBackend {
     int factor_with_ladder(double lambda);
     int ladder(double lambda);
     int pcg_solve();
-    int cost_of(int which, double* out);
     void stage_begin(int st);
     void stage_end(int st);
     // The steps of set_structure in the order it runs them (solver.hip).  Setup is the state of one call, its comments say

@@ -554,8 +554,8 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     su.tr.mark("host lists handed to the free thread");
 
     have_structure_ = true;
-    have_params_ = have_step_ = have_trial_ = false;
-    cur_ = 0;
+    have_params_ = false; st_.invalidate();
+    st_.cur = 0;
     return kOk;
 }
 
@@ -567,8 +567,8 @@ int Solver::set_params(const double* poses, const double* intr, const double* po
         memcpy(hp.data() + 7 * (size_t)cmap_[c], poses + 7 * c, 7 * sizeof(double));
         memcpy(hi.data() + 3 * (size_t)cmap_[c], intr + 3 * c, 3 * sizeof(double));
     }
-    HIP_TRY(hipMemcpyAsync(poses_[cur_], hp.data(), 7 * n_cam_ * sizeof(double), hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipMemcpyAsync(intr_[cur_], hi.data(), 3 * n_cam_ * sizeof(double), hipMemcpyHostToDevice, stream_));
+    HIP_TRY(hipMemcpyAsync(poses_[st_.cur], hp.data(), 7 * n_cam_ * sizeof(double), hipMemcpyHostToDevice, stream_));
+    HIP_TRY(hipMemcpyAsync(intr_[st_.cur], hi.data(), 3 * n_cam_ * sizeof(double), hipMemcpyHostToDevice, stream_));
     std::vector<double> hpt;
     const double* src_pts = points;
     if (tree_shard_) {  // landmarks are renumbered so that every rank's set is one internal range
@@ -576,10 +576,10 @@ int Solver::set_params(const double* poses, const double* intr, const double* po
         for (int64_t l = 0; l < n_pt_; ++l) memcpy(hpt.data() + 3 * (size_t)lmap_[l], points + 3 * l, 3 * sizeof(double));
         src_pts = hpt.data();
     }
-    { const int rc = upload_staged(pts_[cur_], src_pts, 3 * (size_t)n_pt_ * sizeof(double)); if (rc != kOk) return rc; }
-    launch_prepare_cams(n_cam_, poses_[cur_], intr_[cur_], camp_[cur_], mode_mask(mode_), stream_);
+    { const int rc = upload_staged(pts_[st_.cur], src_pts, 3 * (size_t)n_pt_ * sizeof(double)); if (rc != kOk) return rc; }
+    launch_prepare_cams(n_cam_, poses_[st_.cur], intr_[st_.cur], camp_[st_.cur], mode_mask(mode_), stream_);
     HIP_TRY(hipStreamSynchronize(stream_));
-    have_params_ = true; have_step_ = have_trial_ = false; orec_fresh_ = false;
+    have_params_ = true; st_.invalidate(); orec_fresh_ = false;
     factor_lin_ = -1;   // (the current set is overwritten: the factor's linearisation is no longer known)
     return kOk;
 }
@@ -602,14 +602,14 @@ int Solver::get_params(double* poses, double* intr, double* points) {
         HIP_TRY(hipStreamSynchronize(stream_));
         for (int r = 0; r < world_; ++r) {
             const int64_t a = rng[2 * r], b = rng[2 * r + 1];
-            if (b > a) COMM_TRY(comm_->broadcast(pts_[cur_] + 3 * a, 3 * (b - a), r, stream_));
+            if (b > a) COMM_TRY(comm_->broadcast(pts_[st_.cur] + 3 * a, 3 * (b - a), r, stream_));
         }
     }
     std::vector<double> hp(7 * n_cam_), hi(3 * n_cam_);
-    HIP_TRY(hipMemcpyAsync(hp.data(), poses_[cur_], 7 * n_cam_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipMemcpyAsync(hi.data(), intr_[cur_], 3 * n_cam_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(hp.data(), poses_[st_.cur], 7 * n_cam_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(hi.data(), intr_[st_.cur], 3 * n_cam_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     std::vector<double> hpt(tree_shard_ ? 3 * n_pt_ : 0);
-    HIP_TRY(hipMemcpyAsync(tree_shard_ ? hpt.data() : points, pts_[cur_], 3 * n_pt_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(tree_shard_ ? hpt.data() : points, pts_[st_.cur], 3 * n_pt_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     if (tree_shard_)
         for (int64_t l = 0; l < n_pt_; ++l) memcpy(points + 3 * l, hpt.data() + 3 * (size_t)lmap_[l], 3 * sizeof(double));
@@ -623,9 +623,11 @@ int Solver::get_params(double* poses, double* intr, double* points) {
 // ---------------------------------------------------------------------------------------------
 // cost (A16)
 // ---------------------------------------------------------------------------------------------
-int Solver::cost_of(int which, double* out) {
+int Solver::cost(double* out) {
+    if (!have_params_) return fail(kInvalidState, "no parameters set");
+    HIP_TRY(hipSetDevice(device_));
     stage_begin(kStCost);
-    launch_cost(view(which), partial_, n_partial_, scal_, stream_);
+    launch_cost(view(st_.cur), partial_, n_partial_, scal_, stream_);
     if (comm_ && world_ > 1)
         COMM_TRY(comm_->all_reduce_sum(scal_, 1, stream_));
     stage_end(kStCost);
@@ -633,15 +635,8 @@ int Solver::cost_of(int which, double* out) {
     double ss = 0.0;
     HIP_TRY(hipMemcpyAsync(&ss, scal_, sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    const double nrm = sqrt(ss);  // compute_cost: 0.5 * norm_l2()^2 (optimizer/mod.rs:358-361)
-    *out = 0.5 * nrm * nrm;
+    *out = cost_from_sumsq(ss);
     return kOk;
-}
-
-int Solver::cost(double* out) {
-    if (!have_params_) return fail(kInvalidState, "no parameters set");
-    HIP_TRY(hipSetDevice(device_));
-    return cost_of(cur_, out);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -679,7 +674,7 @@ int Solver::assemble(double lambda, double diag_extra, bool for_factor) {
 
 // this rank's part of S, g_red, g_c (its landmarks), before any exchange
 int Solver::assemble_local(double lambda, double diag_extra, bool for_factor) {
-    const BAView v = view(cur_);
+    const BAView v = view(st_.cur);
     const TileMap tm = tilemap();
     stage_begin(kStAssembleCam);
     // (a tree-sharded rank that assembles for its distributed factorisation adds to its own and the top tiles only; every
@@ -799,7 +794,7 @@ int Solver::pcg_solve() {
 // ---------------------------------------------------------------------------------------------
 int Solver::assemble_implicit(double lambda) {
     tp_.set_factor_valid(false);   // (the camera reduction adds to the diagonal tiles)
-    const BAView v = view(cur_);
+    const BAView v = view(st_.cur);
     stage_begin(kStAssembleLm);
     HIP_TRY(hipMemsetAsync(flags_, 0, 4 * sizeof(int), stream_));
     launch_landmark_reduce(dc_, v, lambda, hinv_, g_l_, flags_, lmu_, stream_, orec_);
@@ -838,7 +833,7 @@ int Solver::implicit_matvec(const double* x, double lam_local, double* y, bool r
         launch_vec_mul(n_c_, x, cam_scale_, t, stream_);
         xin = t;
     }
-    launch_implicit_matvec(dc_, view(cur_), cam_ptr_, hinv_, lmu_, xin, lam_local, y, stream_, backsub_records());
+    launch_implicit_matvec(dc_, view(st_.cur), cam_ptr_, hinv_, lmu_, xin, lam_local, y, stream_, backsub_records());
     if (reduce && comm_ && world_ > 1)
         COMM_TRY(comm_->all_reduce_sum(y, (size_t)n_c_, stream_));
     if (scaled_) launch_vec_mul(n_c_, y, cam_scale_, y, stream_);
@@ -938,20 +933,14 @@ int Solver::finish_step(double* step_out, double* grad_out) {
     // rank); the trial POINTS are written by the back-substitution itself
     const bool eager = eager_eval_ && !(comm_ && world_ > 1);
     trial_pts_written_ = eager && fix_pt_ != nullptr;
-    launch_back_substitute(dc_, view(cur_), hinv_, g_l_, dcam_, dl_, stream_, backsub_records(), trial_pts_written_ ? fix_pt_ : nullptr,
-                           trial_pts_written_ ? pts_[cur_ ^ 1] : nullptr);
+    launch_back_substitute(dc_, view(st_.cur), hinv_, g_l_, dcam_, dl_, stream_, backsub_records(), trial_pts_written_ ? fix_pt_ : nullptr,
+                           trial_pts_written_ ? pts_[st_.cur ^ 1] : nullptr);
     stage_end(kStBackSub);
     HIP_TRY(hipGetLastError());
-    have_step_ = true;
-    if (eager) {   // eager_host_: [0..5] step statistics, [6] sum of squares at the trial point
-        if (!eager_host_) HIP_TRY(eager_host_.alloc(8));
-        int rc = enqueue_step_stats();
-        if (rc == kOk) rc = enqueue_trial_point(scal_ + 6);
-        if (rc != kOk) return rc;
-        HIP_TRY(hipMemcpyAsync(eager_host_, scal_, 7 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    }
+    st_.step_computed();
+    if (eager) { const int rc = enqueue_eager_eval(); if (rc != kOk) return rc; }
     const int rc = export_step(step_out, grad_out);   // (synchronises)
-    if (rc == kOk && eager) eager_serial_ = step_serial_;   // (the answers of THIS solve: step_stats / eval_step)
+    if (rc == kOk && eager) post_eager_answers();
     return rc;
 }
 
@@ -959,7 +948,7 @@ int Solver::finish_step(double* step_out, double* grad_out) {
 void Solver::keep_factor() {
     if (world_ != 1 || tp_.distributed()) return;
     tp_.set_factor_valid(true);
-    factor_lin_ = cur_;   // (commit_step flips cur_: the factorised cameras are then in the other set)
+    factor_lin_ = st_.cur;   // (commit_step flips st_.cur: the factorised cameras are then in the other set)
     factor_scaled_ = scaled_;
 }
 
@@ -1005,7 +994,7 @@ int Solver::dist_phase(int phase, double lambda) {
     if (matrix_free_only_) return fail(kInvalidState, "this handle was built matrix-free only (\"matrix_free_only\"): the explicit S does not exist");
     HIP_TRY(hipSetDevice(device_));
     switch (phase) {
-        case 0: have_step_ = false; last_lambda_ = lambda; return assemble_local(lambda, 0.0, true);
+        case 0: st_.invalidate_step(); last_lambda_ = lambda; return assemble_local(lambda, 0.0, true);
         case 1: {
             int rc = assemble_finish();
             if (rc != kOk) return rc;
@@ -1039,9 +1028,9 @@ int Solver::dist_phase(int phase, double lambda) {
         case 5:
             tp_.solve_phase(2, g_red_, dcam_, pcg_buf_);
             if (scaled_) launch_vec_mul(n_c_, dcam_, cam_scale_, dcam_, stream_);
-            launch_back_substitute(dc_, view(cur_), hinv_, g_l_, dcam_, dl_, stream_, backsub_records());
+            launch_back_substitute(dc_, view(st_.cur), hinv_, g_l_, dcam_, dl_, stream_, backsub_records());
             HIP_TRY(hipStreamSynchronize(stream_));
-            have_step_ = true;
+            st_.step_computed();
             return kOk;
         default: return fail(kInvalidInput, "phase out of range");
     }
@@ -1072,7 +1061,7 @@ void Solver::dist_buffers(int point, std::vector<DistBuf>* sums, int** max_flag)
 int Solver::assemble_only(double lambda) {
     if (!have_params_) return fail(kInvalidState, "Block structure not built or parameters not set");
     HIP_TRY(hipSetDevice(device_));
-    have_step_ = false;
+    st_.invalidate_step();
     last_lambda_ = lambda;
     int rc = assemble(lambda, 0.0);
     if (rc != kOk) return rc;
@@ -1092,32 +1081,19 @@ int Solver::enqueue_step_stats() {
     stage_end(kStStats);
     return kOk;
 }
-static void stats_from_sums(const double h[6], double out3[3]) {
-    out3[0] = sqrt(h[0] + h[3]);          // gradient.norm_l2()          (levenberg_marquardt.rs:746)
-    out3[1] = sqrt(h[1] + h[4]);          // step.norm_l2()              (:890)
-    out3[2] = 0.5 * (h[2] + h[5]);        // compute_predicted_reduction (:721-727)
-}
-int Solver::step_stats(double out3[3]) {
-    if (!have_step_) return fail(kInvalidState, "no step computed");
-    if (answered_at_wait()) { stats_from_sums(eager_host_, out3); return kOk; }
-    HIP_TRY(hipSetDevice(device_));
-    const int rc = enqueue_step_stats();
-    if (rc != kOk) return rc;
-    double h[6];
-    HIP_TRY(hipMemcpyAsync(h, scal_, sizeof h, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    stats_from_sums(h, out3);
-    return kOk;
+// set `to` = set `from` (+) sign * step over the cameras and n_pt of the points, and the prepared cameras of the result
+void Solver::retract_sets(int from, double sign, int to, int64_t n_pt) {
+    stage_begin(kStRetract);
+    launch_retract(dc_, n_cam_, n_pt, poses_[from], intr_[from], pts_[from], dcam_, dl_, sign, fix_pose_, fix_intr_, fix_pt_,
+                   poses_[to], intr_[to], pts_[to], stream_);
+    launch_prepare_cams(n_cam_, poses_[to], intr_[to], camp_[to], mode_mask(mode_), stream_);
+    stage_end(kStRetract);
 }
 // the trial point x (+) step in the other parameter set and the sum of squared corrected residuals there (device scalar)
 int Solver::enqueue_trial_point(double* sumsq_out) {
-    const int t = cur_ ^ 1;
-    stage_begin(kStRetract);
-    launch_retract(dc_, n_cam_, trial_pts_written_ ? 0 : n_pt_, poses_[cur_], intr_[cur_], pts_[cur_], dcam_, dl_, 1.0, fix_pose_, fix_intr_,
-                   fix_pt_, poses_[t], intr_[t], pts_[t], stream_);   // (the points: by k_back_substitute when trial_pts_written_)
+    const int t = st_.cur ^ 1;
+    retract_sets(st_.cur, 1.0, t, trial_pts_written_ ? 0 : n_pt_);   // (the points: by k_back_substitute when trial_pts_written_)
     trial_pts_written_ = false;
-    launch_prepare_cams(n_cam_, poses_[t], intr_[t], camp_[t], mode_mask(mode_), stream_);
-    stage_end(kStRetract);
     stage_begin(kStCost);
     launch_cost(view(t), partial_, n_partial_, sumsq_out, stream_);
     if (comm_ && world_ > 1)
@@ -1125,54 +1101,14 @@ int Solver::enqueue_trial_point(double* sumsq_out) {
     stage_end(kStCost);
     return kOk;
 }
-int Solver::eval_step(double* trial_cost) {
-    if (!have_step_) return fail(kInvalidState, "no step computed");
-    if (answered_at_wait()) {   // the trial point is in place
-        have_trial_ = true;
-        const double nrm = sqrt(eager_host_[6]);
-        *trial_cost = 0.5 * nrm * nrm;
-        return kOk;
-    }
-    HIP_TRY(hipSetDevice(device_));
-    const int t = cur_ ^ 1;
-    stage_begin(kStRetract);
-    launch_retract(dc_, n_cam_, n_pt_, poses_[cur_], intr_[cur_], pts_[cur_], dcam_, dl_, 1.0, fix_pose_, fix_intr_,
-                   fix_pt_, poses_[t], intr_[t], pts_[t], stream_);
-    launch_prepare_cams(n_cam_, poses_[t], intr_[t], camp_[t], mode_mask(mode_), stream_);
-    stage_end(kStRetract);
-    have_trial_ = true;
-    return cost_of(t, trial_cost);
-}
-int Solver::commit_step() {
-    if (!have_trial_) return fail(kInvalidState, "no trial point");
-    cur_ ^= 1;
-    have_trial_ = false; have_step_ = false; orec_fresh_ = false;
-    return kOk;
-}
-
-// apply_negative_parameter_step (optimizer/mod.rs:343-356): the rejected trial point is moved back
-// by the inverse retraction, it is NOT restored from a snapshot.
-int Solver::discard_step() {
-    if (!have_trial_) return fail(kInvalidState, "no trial point");
-    HIP_TRY(hipSetDevice(device_));
-    const int t = cur_ ^ 1;
-    stage_begin(kStRetract);
-    launch_retract(dc_, n_cam_, n_pt_, poses_[t], intr_[t], pts_[t], dcam_, dl_, -1.0, fix_pose_, fix_intr_, fix_pt_,
-                   poses_[cur_], intr_[cur_], pts_[cur_], stream_);
-    launch_prepare_cams(n_cam_, poses_[cur_], intr_[cur_], camp_[cur_], mode_mask(mode_), stream_);
-    stage_end(kStRetract);
-    HIP_TRY(hipStreamSynchronize(stream_));
-    have_trial_ = false; have_step_ = false; orec_fresh_ = false;
-    return kOk;
-}
 
 int Solver::parameter_norm(double* out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    launch_sumsq(7 * n_cam_, poses_[cur_], partial_, n_partial_, scal_ + 9, stream_);
-    launch_sumsq(3 * n_cam_, intr_[cur_], partial_, n_partial_, scal_ + 10, stream_);
+    launch_sumsq(7 * n_cam_, poses_[st_.cur], partial_, n_partial_, scal_ + 9, stream_);
+    launch_sumsq(3 * n_cam_, intr_[st_.cur], partial_, n_partial_, scal_ + 10, stream_);
     // points: in a sharded run only the owned range is current on this rank
-    launch_sumsq(3 * (lm_hi_ - lm_lo_), pts_[cur_] + 3 * lm_lo_, partial_, n_partial_, scal_ + 11, stream_);
+    launch_sumsq(3 * (lm_hi_ - lm_lo_), pts_[st_.cur] + 3 * lm_lo_, partial_, n_partial_, scal_ + 11, stream_);
     if (comm_ && world_ > 1)
         COMM_TRY(comm_->all_reduce_sum(scal_ + 11, 1, stream_));
     double h[3];
@@ -1198,7 +1134,7 @@ int Solver::column_norms_sq_device() {
     if (rc != kOk) return rc;
     const bool was = scaled_;
     scaled_ = false;
-    const BAView v = view(cur_);
+    const BAView v = view(st_.cur);
     scaled_ = was;
     HIP_TRY(hipMemsetAsync(cam_scale_, 0, n_c_pad_ * sizeof(double), stream_));
     HIP_TRY(hipMemsetAsync(pt_scale_, 0, std::max<int64_t>(3 * n_pt_, 1) * sizeof(double), stream_));
@@ -1240,7 +1176,7 @@ int Solver::column_norms(double* norms_out) {
 int Solver::set_column_scaling(const double* scaling) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built");
     HIP_TRY(hipSetDevice(device_));
-    have_step_ = false;
+    st_.invalidate_step();
     if (!scaling) { scaled_ = false; return kOk; }
     if (factor_scaled_) factor_lin_ = -1;   // (the factor's scale vectors are overwritten below)
     int rc = ensure_scale_buffers();
@@ -1268,7 +1204,7 @@ int Solver::set_column_scaling(const double* scaling) {
 
 // iteration 0 of the reference's loop: norms of the current Jacobian -> s = 1 / (1 + norm), kept for the whole optimize
 int Solver::set_jacobi_scaling(bool on) {
-    if (!on) { scaled_ = false; have_step_ = false; return kOk; }
+    if (!on) { scaled_ = false; st_.invalidate_step(); return kOk; }
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
     if (factor_scaled_) factor_lin_ = -1;   // (the factor's scale vectors are overwritten below)
@@ -1280,7 +1216,7 @@ int Solver::set_jacobi_scaling(bool on) {
     HIP_TRY(hipMemcpyAsync(cam_scale_h_.data(), cam_scale_, n_c_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipMemcpyAsync(pt_scale_h_.data(), pt_scale_, 3 * n_pt_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    scaled_ = true; have_step_ = false;
+    scaled_ = true; st_.invalidate_step();
     return kOk;
 }
 
@@ -1301,7 +1237,7 @@ int Solver::get_residual(double* r_out) {
     DeviceBuffer<double> d;
     HIP_TRY(d.alloc(2 * n_obs_));
     hipMemsetAsync(d, 0, 2 * n_obs_ * sizeof(double), stream_);
-    launch_export_linearization(dc_, view(cur_), o_orig_, d, nullptr, nullptr, stream_);
+    launch_export_linearization(dc_, view(st_.cur), o_orig_, d, nullptr, nullptr, stream_);
     hipError_t e = hipMemcpyAsync(r_out, d, 2 * n_obs_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     hipStreamSynchronize(stream_);
     return check_hip(e, "get_residual");
@@ -1315,7 +1251,7 @@ int Solver::get_jacobian_blocks(double* jc_out, double* jl_out) {
     HIP_TRY(dl.alloc(6 * n_obs_));
     hipMemsetAsync(dj, 0, 2 * dc_ * n_obs_ * sizeof(double), stream_);
     hipMemsetAsync(dl, 0, 6 * n_obs_ * sizeof(double), stream_);
-    launch_export_linearization(dc_, view(cur_), o_orig_, nullptr, dj, dl, stream_);
+    launch_export_linearization(dc_, view(st_.cur), o_orig_, nullptr, dj, dl, stream_);
     hipError_t e1 = hipMemcpyAsync(jc_out, dj, 2 * dc_ * n_obs_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     hipError_t e2 = hipMemcpyAsync(jl_out, dl, 6 * n_obs_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     hipStreamSynchronize(stream_);
@@ -1377,7 +1313,7 @@ int Solver::get_schur(double* S_out, double* gred_out) {
 int Solver::schur_matvec(double lambda, const double* x_in, double* y_explicit, double* y_implicit) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    have_step_ = false;
+    st_.invalidate_step();
     const int64_t nref = 9 * n_cam_;
     auto ref_row = [&](int64_t i) -> int64_t {
         const int64_t ci = i / dc_; const int a = (int)(i - ci * dc_);

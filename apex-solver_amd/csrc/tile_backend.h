@@ -1,5 +1,5 @@
 // tile_backend.h -- what the two backends that factorise on a TilePlan share (solver.h: S of bundle adjustment, pg_solver.h: H of a
-// pose graph): the plan, the stream and their order of destruction, the state of one solve, the switches that go to the plan, and
+// pose graph): the plan, the stream and their order of destruction, the state of one solve and the trial-step protocol on it, the switches that go to the plan, and
 // the protocol around one direct solve -- speculative factorisation, one host wait, the repairs of a dataflow launch that gave up.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 #include "device_buffer.h"
 #include "lm_loop.h"
 #include "stage_timer.h"
+#include "step_state.h"
 #include "tile_plan.h"
 
 namespace apex {
@@ -50,13 +51,22 @@ class TileBackend : public virtual LmBackend {   // (virtual: a solver may also 
     int n_levels() const { return tp_.n_levels(); }
     const TilePlan& plan() const { return tp_; }
     const char* last_error() const override { return err_.c_str(); }
+    // The trial-step protocol behind a solve, on StepState (step_state.h): answers the solve posted at its own wait are served from
+    // the host, else the hooks below are enqueued and read back with one wait.
+    int step_stats(double out3[3]) final;       // |g|, |step|, predicted reduction
+    int eval_step(double* trial_cost) final;    // x (+) step into the trial set, its cost
+    int commit_step() final;
+    int discard_step() final;                   // reference semantics: trial (+) (-step), not a snapshot
 
    protected:
     TileBackend(int device, int n_stages, int nd_leaf) : device_(device), nd_leaf_(nd_leaf), timer_(n_stages) {}
     int fail(int code, const std::string& msg) { err_ = msg; return code; }
     int check_hip(hipError_t e, const char* what, std::string* err = nullptr);   // err: where the text goes instead of err_
-    void begin_solve(double lambda) { have_step_ = have_trial_ = false; ++step_serial_; last_lambda_ = lambda; }   // (a solve's eager evaluation overwrites the trial set: an earlier eval_step is void)
-    bool answered_at_wait() const { return eager_serial_ == step_serial_ && eager_host_; }   // step_stats / eval_step: read at this solve's wait
+    void begin_solve(double lambda) { st_.begin_solve(); last_lambda_ = lambda; }
+    // finish_step's eager evaluation, enqueued behind the step; then, when finish_step has waited, the answers of THIS solve
+    int enqueue_eager_eval();
+    void post_eager_answers() { st_.post_answers(answers_from_sums(eager_host_)); }
+    int answers_of_step(bool trial, StepAnswers* out);
     // The sweeps and the step on the system rebuild_system() built, to the one host wait.  speculative: the factorisation is
     // enqueued here with its flags deferred to that wait; else the caller has factorised and read them.
     int direct_solve(bool speculative, double lambda, double* step_out, double* grad_out);
@@ -72,13 +82,18 @@ class TileBackend : public virtual LmBackend {   // (virtual: a solver may also 
     virtual const int* own_flag() const { return nullptr; }              // a device flag of the solver's own, read at the speculative solve's wait
     virtual int own_flag_raised() { return kOk; }                         // ... and the failure it stands for
     virtual void keep_factor() { tp_.set_factor_valid(true); }            // pivots read, sweeps clean: the covariance calls may invert this factor
+    // ... and the trial-step protocol (same section)
+    virtual int enqueue_step_stats() = 0;                                 // the step's sums into step_sums()
+    virtual int enqueue_trial_point(double* sumsq_out) = 0;               // current (+) step into the trial set, the sum of squares there
+    virtual int enqueue_retract(int from, double sign, int to) = 0;       // set `to` = set `from` (+) sign * step, ready to be evaluated
+    virtual double* step_sums(int* n) = 0;                                // device: the *n sums of enqueue_step_stats, the trial point's slot behind them
+    virtual StepAnswers answers_from_sums(const double* h) const = 0;     // a host copy of those *n + 1 doubles as named answers
+    virtual void params_moved() {}                                        // the current parameters are other ones now (commit, discard)
 
     int device_;
-    bool have_step_ = false, have_trial_ = false;
-    int cur_ = 0;  // index of the current parameter set (0/1); the other one is the trial set
+    StepState st_;
     double last_lambda_ = 0.0;
     bool one_wait_ = true, eager_eval_ = true;
-    int64_t step_serial_ = 0, eager_serial_ = -1;   // eager_serial_ == step_serial_: eager_host_ holds the answers of THIS solve
     int n_factor_flow_timeouts_ = 0;
     bool use_nd_ = true;
     int nd_leaf_;
@@ -89,7 +104,7 @@ class TileBackend : public virtual LmBackend {   // (virtual: a solver may also 
     struct StreamLast { hipStream_t& s; ~StreamLast() { if (s) (void)hipStreamDestroy(s); } } stream_last_{stream_};
     TilePlan tp_;   // the tiles, their factorisation and solves
     StageTimer timer_;
-    PinnedBuffer<double> eager_host_;   // the eager evaluation's sums, in the solver's own layout
+    PinnedBuffer<double> eager_host_;   // the eager evaluation's sums as step_sums() lays them out: read by answers_from_sums only
 };
 
 }  // namespace apex

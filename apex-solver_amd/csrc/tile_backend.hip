@@ -39,10 +39,10 @@ int TileBackend::direct_solve(bool speculative, double lambda, double* step_out,
             int own = 0;
             if (own_flag()) HIP_TRY(hipMemcpyAsync(&own, own_flag(), sizeof(int), hipMemcpyDeviceToHost, stream_));
             HIP_TRY(tp_.read_flags(&failed));   // (synchronises; raises factor_flow_gave_up() on a dataflow time-out)
-            if (own) { have_step_ = false; return own_flag_raised(); }
+            if (own) { st_.invalidate_step(); return own_flag_raised(); }
             const bool gave_up = tp_.factor_flow_gave_up();
             if (failed || gave_up) {
-                have_step_ = false;
+                st_.invalidate_step();
                 (void)tp_.sweep_timed_out();   // (clears the word a sweep over a broken factor may have raised)
                 rc = recover_factor(lambda, failed, gave_up);
                 attempt = -1;   // (the loop's counter is for the sweep time-outs of the solve that follows)
@@ -54,11 +54,72 @@ int TileBackend::direct_solve(bool speculative, double lambda, double* step_out,
         // intact, so the solve is repeated with the level-by-level sweeps -- for this call and for the rest of the plan's
         // life (a device that starved a sweep once will do it again, and every time-out costs ~2 s).  In a distributed plan
         // the word was max-reduced: every rank is here.
-        have_step_ = false;
+        st_.invalidate_step();
         if (attempt > 0 || !tp_.tri_flow()) return fail(kDeviceError, "triangular sweep timed out");
         tp_.enable_tri_flow(false);
     }
     return rc;
+}
+
+// ---- the trial-step protocol (lm_loop.h) ---------------------------------------------------------------------------------
+int TileBackend::enqueue_eager_eval() {
+    if (!eager_host_) HIP_TRY(eager_host_.alloc(8));
+    int n = 0;
+    double* sums = step_sums(&n);
+    int rc = enqueue_step_stats();
+    if (rc == kOk) rc = enqueue_trial_point(sums + n);
+    if (rc != kOk) return rc;
+    HIP_TRY(hipMemcpyAsync(eager_host_, sums, (n + 1) * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    return kOk;
+}
+
+// The answers of the last solve: posted at its wait, else the statistics -- or the trial point and its sum of squares -- are
+// enqueued and read back with one wait.
+int TileBackend::answers_of_step(bool trial, StepAnswers* out) {
+    const StepAnswers* posted = nullptr;
+    if (const Status rc = trial ? st_.ask_trial(&posted) : st_.ask_stats(&posted)) return fail(rc, st_.refusal);
+    if (posted) { *out = *posted; return kOk; }
+    HIP_TRY(hipSetDevice(device_));
+    int n = 0;
+    double* sums = step_sums(&n);
+    if (trial) st_.trial_written();
+    const int rc = trial ? enqueue_trial_point(sums + n) : enqueue_step_stats();
+    if (rc != kOk) return rc;
+    HIP_TRY(hipGetLastError());
+    double h[8] = {};
+    HIP_TRY(hipMemcpyAsync(h + (trial ? n : 0), sums + (trial ? n : 0), (trial ? 1 : n) * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    *out = answers_from_sums(h);
+    return kOk;
+}
+int TileBackend::step_stats(double out3[3]) {
+    StepAnswers a;
+    const int rc = answers_of_step(false, &a);
+    if (rc == kOk) { out3[0] = a.gradient_norm; out3[1] = a.step_norm; out3[2] = a.predicted_reduction; }
+    return rc;
+}
+int TileBackend::eval_step(double* trial_cost) {
+    StepAnswers a;
+    const int rc = answers_of_step(true, &a);
+    if (rc == kOk) *trial_cost = cost_from_sumsq(a.trial_sumsq);
+    return rc;
+}
+int TileBackend::commit_step() {
+    if (const Status rc = st_.commit()) return fail(rc, st_.refusal);
+    params_moved();
+    return kOk;
+}
+// apply_negative_parameter_step (optimizer/mod.rs:343-356): the rejected trial point is moved back by the inverse retraction,
+// it is NOT restored from a snapshot.
+int TileBackend::discard_step() {
+    if (const Status rc = st_.begin_discard()) return fail(rc, st_.refusal);
+    HIP_TRY(hipSetDevice(device_));
+    const int rc = enqueue_retract(st_.cur ^ 1, -1.0, st_.cur);
+    if (rc != kOk) return rc;
+    HIP_TRY(hipStreamSynchronize(stream_));
+    (void)st_.finish_discard();
+    params_moved();
+    return kOk;
 }
 
 }  // namespace apex
