@@ -6,13 +6,14 @@ Host-side modules:
   layout     the reference's lexicographic global column layout
   capi       ctypes binding of the C-ABI library (include/apexgpu.h)
   solver     Python mirror of the reference's Problem / LevenbergMarquardt surface
+  loss       the robust loss family of both front ends: Loss, create_loss_function
   pose_graph SE3 pose-graph path: G2O reader, PoseGraphProblem, GpuSparseCholeskySolver
   datasets   real BAL / G2O files in the reference's data/ layout when present, the synthetic shapes otherwise
 """
 from . import layout, synthetic  # noqa: F401
 
 __all__ = ["layout", "synthetic"]
-from . import bal, capi, datasets, pose_graph, solver  # noqa: F401,E402
+from . import bal, capi, datasets, loss, pose_graph, solver  # noqa: F401,E402
 from .pose_graph import (DogLegConfig, G2oLoader, GaussNewtonConfig, GpuSparseCholeskySolver,  # noqa: F401,E402
                          PoseGraphProblem)
 from .solver import (GpuSchurComplementSolver, LevenbergMarquardt, LevenbergMarquardtConfig,  # noqa: F401,E402

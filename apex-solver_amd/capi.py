@@ -48,7 +48,7 @@ SYMBOLS = (
     # Gauss-Newton and Dog-Leg on pose graphs
     "apexgpu_pg_jv_gram", "apexgpu_pg_dogleg_step", "apexgpu_pg_gn_optimize", "apexgpu_pg_dogleg_optimize",
     # the robust loss family on pose graphs
-    "apexgpu_pg_set_loss", "apexgpu_pg_get_loss", "apexgpu_loss_evaluate",
+    "apexgpu_pg_set_loss", "apexgpu_pg_get_loss", "apexgpu_loss_evaluate", "apexgpu_set_loss", "apexgpu_get_loss",
 )
 MANIFOLD_SE3, MANIFOLD_SE2 = 0, 1
 # APEXGPU_LOSS_* of include/apexgpu.h, in value order
@@ -228,6 +228,8 @@ def load() -> C.CDLL:
     L.apexgpu_pg_set_priors.argtypes = [vp, C.c_int64, vp, vp, vp]
     L.apexgpu_pg_get_prior_residual.argtypes = [vp, vp]
     L.apexgpu_pg_set_loss.argtypes = [vp, C.c_int, dbl, dbl]
+    L.apexgpu_set_loss.argtypes = [vp, C.c_int, dbl, dbl]
+    L.apexgpu_get_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(dbl * 2)]
     L.apexgpu_pg_get_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(dbl * 2)]
     L.apexgpu_loss_evaluate.argtypes = [C.c_int, dbl, dbl, dbl, C.POINTER(dbl * 6)]
     L.apexgpu_pg_get_params.argtypes = [vp, vp]

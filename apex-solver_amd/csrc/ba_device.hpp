@@ -16,6 +16,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "pg_loss.hpp"
+
 #ifndef APEX_HD
 #if defined(__HIPCC__)
 #define APEX_HD __host__ __device__ __forceinline__
@@ -194,9 +196,22 @@ APEX_HD double huber_sqrt_rho1(double delta, double s) {
     return 1.0;
 }
 
+// The loss policy of the per-observation functions: the TYPE of the loss argument selects the code.  A double
+// is set_structure's huber_delta and the code above, unchanged; a PgLoss is the general family of pg_loss.hpp.  Only losses
+// whose corrector always takes its first arm reach a BA kernel (pg_loss_first_arm_only: alpha = 0, residual_scaling =
+// sqrt(rho')), so that one scalar per observation is the whole correction -- what the projection record has room for.
+APEX_HD double loss_sqrt_rho1(double huber_delta, double s) { return huber_sqrt_rho1(huber_delta, s); }
+APEX_HD double loss_sqrt_rho1(const PgLoss& loss, double s) { return pg_loss_corrector(loss, s).sqrt_rho1; }
+// The kernels' side of it: a kernel that linearises observations is a template over a parameter pack LOSS that is empty (the
+// loss is v.huber_delta; argument list and device code are those of the kernel before the loss family) or one PgLoss, which is
+// then a kernel argument of its own, right after the view.
+template <class VIEW> APEX_HD double loss_arg(const VIEW& v) { return v.huber_delta; }
+template <class VIEW> APEX_HD const PgLoss& loss_arg(const VIEW&, const PgLoss& loss) { return loss; }
+
 // Residual only (A16).  Returns validity; r is the CORRECTED residual.
+template <class LOSS>
 APEX_HD bool residual_obs(const Cam& c, const double pw[3], double u_obs, double v_obs,
-                          double huber_delta, double r[2]) {
+                          LOSS loss, double r[2]) {
     APEX_FP_EXACT
     double pc[3];
     cam_transform(c, pw, pc);
@@ -207,7 +222,7 @@ APEX_HD bool residual_obs(const Cam& c, const double pw[3], double u_obs, double
     double d = fma(c.k2, r4, fma(c.k1, r2, 1.0));
     double r0 = fma(c.f, xn * d, -u_obs);
     double r1 = fma(c.f, yn * d, -v_obs);
-    double w = huber_sqrt_rho1(huber_delta, fma(r0, r0, r1 * r1));
+    double w = loss_sqrt_rho1(loss, fma(r0, r0, r1 * r1));
     r[0] = r0 * w; r[1] = r1 * w;
     return true;
 }
@@ -223,9 +238,9 @@ APEX_HD bool residual_obs(const Cam& c, const double pw[3], double u_obs, double
 // now so that the pair kernel finds what it needs of a landmark -- six entries of Hll^-1 and p_w.x, p_w.y -- in ONE 64-byte line.)
 // the the record form of the Schur pair kernel (schur_pairs.hip, jac_from_rec)
 // rebuilds J from it instead of re-linearising the observation once per pair.  A point behind the camera: weight 0.
-template <int DC, bool MASKED = true>
+template <int DC, bool MASKED = true, class LOSS = double>
 APEX_HD bool linearize_obs(const Cam& c, const double pw[3], double u_obs, double v_obs,
-                           double huber_delta, double r[2], double Jc[2][DC], double Jl[2][3], double* rec4 = nullptr) {
+                           LOSS loss, double r[2], double Jc[2][DC], double Jl[2][3], double* rec4 = nullptr) {
     APEX_FP_EXACT
     double pc[3];
     cam_transform(c, pw, pc);
@@ -261,7 +276,7 @@ APEX_HD bool linearize_obs(const Cam& c, const double pw[3], double u_obs, doubl
     Jp[1][1] = f * (dyd_dyn * inz);
     Jp[1][2] = f * fma(dyd_dxn, dxn_dz, dyd_dyn * dyn_dz);
     const double* R = c.R;
-    double w = huber_sqrt_rho1(huber_delta, fma(r0, r0, r1 * r1));
+    double w = loss_sqrt_rho1(loss, fma(r0, r0, r1 * r1));
     if (rec4) { rec4[0] = xn; rec4[1] = yn; rec4[2] = pw[2]; rec4[3] = w; }
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {

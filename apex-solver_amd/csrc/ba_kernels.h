@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pg_loss.hpp"
 #include "tile_tasks.h"   // kNB
 
 namespace apex {
@@ -68,16 +69,19 @@ struct TileMap {
     int nt;
 };
 
+// The launchers of the kernels that linearise an observation take the loss last.  NULL: the kernels that know v.huber_delta
+// only.  Else (a loss of the family that huber_delta cannot express and whose corrector keeps to its first arm):
+// the general-loss instantiations, which receive *loss as a kernel argument of their own and do not read v.huber_delta.
 void launch_cam_reduce(int dc, const BAView& v, const TileMap& tm, const int* cam_ptr, const int* cam_obs,
                        double lambda, int add_lambda, const double* hinv, const double* g_l, int with_self, double* g_c,
-                       double* g_red, hipStream_t s);
+                       double* g_red, hipStream_t s, const PgLoss* loss = nullptr);
 // orec (may be NULL): [n_obs][4] projection records (xn, yn, p_w.z, sqrt(rho')), landmark-major, for the record form of
 // the Schur pair kernel (schur_pairs.hip) and of the back-substitution
 void launch_landmark_reduce(int dc, const BAView& v, double lambda, double* hinv, double* g_l, int* err_flag,
-                            double* lmu /* may be NULL */, hipStream_t s, double* orec = nullptr);
+                            double* lmu /* may be NULL */, hipStream_t s, double* orec = nullptr, const PgLoss* loss = nullptr);
 // A18 (implicit_schur.rs): y = S x matrix-free, the Schur-Jacobi preconditioner blocks and their application
 void launch_implicit_matvec(int dc, const BAView& v, const int* cam_ptr, const double* hinv, double* lmu, const double* x,
-                            double lambda, double* y, hipStream_t s, const double* orec = nullptr);
+                            double lambda, double* y, hipStream_t s, const double* orec = nullptr, const PgLoss* loss = nullptr);
 void launch_clear3(double* a, double* b, int64_t n, int* f, int nf, hipStream_t s);   // a[0..n) = b[0..n) = 0, f[0..nf) = 0: one launch
 void launch_gather_uv(int64_t n, const int* idx, const double* src, double* dst, hipStream_t s);          // dst[k] = src[idx[k]] (double2)
 void launch_gather_u32(int64_t n, const int* idx, const uint32_t* src, uint32_t* dst, hipStream_t s);
@@ -89,18 +93,19 @@ void launch_prepare_cams(int64_t n_cam, const double* poses, const double* intr,
 // orec: the projection records of the same linearisation (k_landmark_reduce) or NULL -- the record form of the kernel
 void launch_back_substitute(int dc, const BAView& v, const double* hinv, const double* g_l, const double* dcam,
                             double* dl, hipStream_t s, const double* orec = nullptr, const uint8_t* fix_pt = nullptr,
-                            double* pts_trial = nullptr /* with fix_pt: the trial points p (+) dl are written too */);
+                            double* pts_trial = nullptr /* with fix_pt: the trial points p (+) dl are written too */,
+                            const PgLoss* loss = nullptr);
 void launch_retract(int dc, int64_t n_cam, int64_t n_pt, const double* poses, const double* intr, const double* pts,
                     const double* dcam, const double* dl, double sign, const uint8_t* fix_pose,
                     const uint8_t* fix_intr, const uint8_t* fix_pt, double* poses_out, double* intr_out,
                     double* pts_out, hipStream_t s);
-void launch_cost(const BAView& v, double* partial, int n_partial, double* out_sumsq, hipStream_t s);
+void launch_cost(const BAView& v, double* partial, int n_partial, double* out_sumsq, hipStream_t s, const PgLoss* loss = nullptr);
 // gscale (may be NULL): the gradient the statistics use is g .* gscale (the scaled gradient of Jacobi scaling)
 void launch_step_stats(int64_t n, const double* g, const double* d, double lambda, const double* gscale, double* partial,
                        int n_partial, double* out3, hipStream_t s);
 // Jacobi scaling: n2_cam[c][d_c], n2_pt[l][3] += squared entries of the corrected Jacobian's columns (atomics; a
 // one-off per optimize), and s = 1 / (1 + sqrt(n2)) (process_jacobian_generic, optimizer/mod.rs:754-757)
-void launch_column_norms_sq(int dc, const BAView& v, double* n2_cam, double* n2_pt, hipStream_t s);
+void launch_column_norms_sq(int dc, const BAView& v, double* n2_cam, double* n2_pt, hipStream_t s, const PgLoss* loss = nullptr);
 void launch_scaling_from_norms_sq(int64_t n, const double* n2, double* scale, hipStream_t s);
 void launch_vec_mul(int64_t n, const double* a, const double* b, double* out, hipStream_t s);  // out = a .* b (in place ok)
 void launch_vec_add(int64_t n, const double* a, const double* b, double* out, hipStream_t s);  // out = a + b (in place ok)
@@ -119,8 +124,8 @@ void launch_debug_invert_blocks(int64_t n, const double* in, double* out, int* o
 // camera pair fell outside z's tile pattern.
 constexpr int kLcSmallK = 8, kLcChunk = 32;
 void launch_landmark_cov(int dc, const BAView& v, const double* hinv, const TileMap& z, const int* small_list, int n_small,
-                         const int* large_list, int n_large, double* out, int* err, hipStream_t s);
+                         const int* large_list, int n_large, double* out, int* err, hipStream_t s, const PgLoss* loss = nullptr);
 void launch_export_linearization(int dc, const BAView& v, const int* o_orig, double* r_out, double* jc_out,
-                                 double* jl_out, hipStream_t s);
+                                 double* jl_out, hipStream_t s, const PgLoss* loss = nullptr);
 
 }  // namespace apex

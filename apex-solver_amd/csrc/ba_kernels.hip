@@ -55,8 +55,10 @@ __device__ __forceinline__ double* s_block_ptr(const TileMap& tm, uint32_t row_c
 // (+lambda on the diagonal when add_lambda), g_c and g_red := -g_c.
 // ------------------------------------------------------------------------------------------
 constexpr int kCamThreads = 64;  // one wave per camera: ~30 observations per lane amortise the 63-value reduction
-template <int DC, bool MASKED, bool WITH_SELF>
-__global__ __launch_bounds__(kCamThreads, 2) void k_cam_reduce(BAView v, TileMap tm, const int* __restrict__ cam_ptr,
+// LOSS: empty, or PgLoss -- the general-loss instantiation, with the loss as an argument of its own (ba_device.hpp, loss_arg;
+// DESIGN.md §12).  The general form does not pin two waves per SIMD: see the register table there.
+template <int DC, bool MASKED, bool WITH_SELF, class... LOSS>
+__global__ __launch_bounds__(kCamThreads, sizeof...(LOSS) ? 1 : 2) void k_cam_reduce(BAView v, LOSS... loss, TileMap tm, const int* __restrict__ cam_ptr,
                                                       const int* __restrict__ cam_obs, double lambda,
                                                       int add_lambda, const double* __restrict__ hinv,
                                                       const double* __restrict__ g_l,
@@ -100,7 +102,10 @@ __global__ __launch_bounds__(kCamThreads, 2) void k_cam_reduce(BAView v, TileMap
         }
         const double pw[3] = {rec[kLmPt], rec[kLmPt + 1], rec[kLmPt + 2]};
         double r[2], Jc[2][DC], Jl[2][3];
-        linearize_obs<DC, MASKED>(cam, pw, uv.x, uv.y, v.huber_delta, r, Jc, Jl);
+        // (v.huber_delta is named here, not fetched through loss_arg as in the other kernels: this kernel's register
+        // allocation -- not its instructions -- came out different from the one before the loss family otherwise)
+        if constexpr (sizeof...(LOSS) == 0) linearize_obs<DC, MASKED>(cam, pw, uv.x, uv.y, v.huber_delta, r, Jc, Jl);
+        else linearize_obs<DC, MASKED>(cam, pw, uv.x, uv.y, loss..., r, Jc, Jl);
 #pragma unroll
         for (int a = 0; a < DC; ++a) acc[NH + a] += Jc[0][a] * r[0] + Jc[1][a] * r[1];
         if (WITH_SELF) {
@@ -225,8 +230,8 @@ constexpr int kLmLanes = 4;   // lanes per landmark in the landmark-major kernel
                               // 0.75 + 0.73; 4 keeps the tail of a landmark with a thousand observations at a few hundred microseconds
 // (occupancy: 114 VGPRs = 4 waves per SIMD.  Forcing 5 / 6 with amdgpu_waves_per_eu spills 124 / 180 bytes per lane and the
 // kernel goes from 0.78 to 1.94 / 3.10 ms -- k_back_substitute likewise 0.48 -> 0.85 / 2.12: profiles/r05_ab_waves_per_eu.txt)
-template <int DC>
-__global__ __launch_bounds__(kLmWg * kLmLanes) void k_landmark_reduce(BAView v, double lambda, double* __restrict__ hinv,
+template <int DC, class... LOSS>
+__global__ __launch_bounds__(kLmWg * kLmLanes) void k_landmark_reduce(BAView v, LOSS... loss, double lambda, double* __restrict__ hinv,
                                                            double* __restrict__ g_l, int* __restrict__ err_flag,
                                                            double* __restrict__ lmu, double* __restrict__ orec) {
     static_assert(kLmWg * kLmLanes <= 1024 && kLmWg * kBsLanes <= 1024, "a workgroup is kLmWg landmarks (the camera staging lists are built per kLmWg landmarks)");
@@ -260,11 +265,11 @@ __global__ __launch_bounds__(kLmWg * kLmLanes) void k_landmark_reduce(BAView v, 
             double r[2], Jc[2][DC], Jl[2][3];
             if (orec) {   // record form of the pair kernel: the observation's projection record, 32 bytes, landmark-major
                 double rec[4];
-                linearize_obs<DC>(cam, pw, uv.x, uv.y, v.huber_delta, r, Jc, Jl, rec);
+                linearize_obs<DC>(cam, pw, uv.x, uv.y, loss_arg(v, loss...), r, Jc, Jl, rec);
                 double2* q = reinterpret_cast<double2*>(orec + 4 * (size_t)i);
                 q[0] = make_double2(rec[0], rec[1]); q[1] = make_double2(rec[2], rec[3]);
             } else {
-                linearize_obs<DC>(cam, pw, uv.x, uv.y, v.huber_delta, r, Jc, Jl);
+                linearize_obs<DC>(cam, pw, uv.x, uv.y, loss_arg(v, loss...), r, Jc, Jl);
             }
             h[0] += Jl[0][0] * Jl[0][0] + Jl[1][0] * Jl[1][0];
             h[1] += Jl[0][1] * Jl[0][0] + Jl[1][1] * Jl[1][0];
@@ -349,8 +354,10 @@ __global__ __launch_bounds__(256) void k_prepare_cams(int64_t n_cam, const doubl
 // LANES per landmark (round 5): 2 here against k_landmark_reduce's 4 -- 0.39 against 0.48 ms on final-13682 (the A/B with every
 // landmark-major kernel at 2 lanes: this kernel -0.09, k_landmark_reduce +0.03); a workgroup is kLmWg landmarks either way (the
 // camera staging lists are built per kLmWg landmarks), i.e. 128 threads here.
-template <int DC, bool MATVEC, bool REC, int LANES = kBsLanes>
-__global__ __launch_bounds__(kLmWg * LANES) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_back_substitute(BAView v, const double* __restrict__ hinv,
+// LOSS (see k_cam_reduce): only with REC = false -- the record form evaluates no loss, its w is in the record.  The general form
+// does not pin four waves per SIMD (the register table of DESIGN.md §12).
+template <int DC, bool MATVEC, bool REC, int LANES = kBsLanes, class... LOSS>
+__global__ __launch_bounds__(kLmWg * LANES) __attribute__((amdgpu_waves_per_eu(sizeof...(LOSS) ? 1 : 4, 4))) void k_back_substitute(BAView v, LOSS... loss, const double* __restrict__ hinv,
                                                            const double* __restrict__ g_l,
                                                            const double* __restrict__ dc,
                                                            double* __restrict__ dl,
@@ -437,7 +444,7 @@ __global__ __launch_bounds__(kLmWg * LANES) __attribute__((amdgpu_waves_per_eu(4
                 for (int a = 0; a < DC; ++a) dcv[a] = dc[(size_t)c * DC + a];
             }
             double r[2], Jc[2][DC], Jl[2][3];
-            linearize_obs<DC>(cam, pw, uv.x, uv.y, v.huber_delta, r, Jc, Jl);
+            linearize_obs<DC>(cam, pw, uv.x, uv.y, loss_arg(v, loss...), r, Jc, Jl);
             double s0 = 0.0, s1 = 0.0;
 #pragma unroll
             for (int a = 0; a < DC; ++a) {
@@ -479,8 +486,8 @@ __global__ __launch_bounds__(kLmWg * LANES) __attribute__((amdgpu_waves_per_eu(4
 // A18 camera half of the matrix-free Schur operator, one wave per camera:
 //   y_c = lambda x_c + sum_i Jc_i^T (Jc_i x_c - Jl_i u_l)      (= H_cc x - H_cl Hll^-1 H_cl^T x)
 // ------------------------------------------------------------------------------------------
-template <int DC>
-__global__ __launch_bounds__(64) void k_implicit_cam(BAView v, const int* __restrict__ cam_ptr,
+template <int DC, class... LOSS>
+__global__ __launch_bounds__(64) void k_implicit_cam(BAView v, LOSS... loss, const int* __restrict__ cam_ptr,
                                                        const double* __restrict__ lmu, const double* __restrict__ x,
                                                        double lambda, double* __restrict__ y) {
     const uint32_t c = blockIdx.x;
@@ -510,7 +517,7 @@ __global__ __launch_bounds__(64) void k_implicit_cam(BAView v, const int* __rest
         }
         const double pw[3] = {q0.x, q0.y, q1.x}, u[3] = {q2.x, q2.y, q3.x};
         double r[2], Jc[2][DC], Jl[2][3];
-        linearize_obs<DC>(cam, pw, uv.x, uv.y, v.huber_delta, r, Jc, Jl);
+        linearize_obs<DC>(cam, pw, uv.x, uv.y, loss_arg(v, loss...), r, Jc, Jl);
         double s0 = -(Jl[0][0] * u[0] + Jl[0][1] * u[1] + Jl[0][2] * u[2]);
         double s1 = -(Jl[1][0] * u[0] + Jl[1][1] * u[1] + Jl[1][2] * u[2]);
 #pragma unroll
@@ -715,7 +722,8 @@ __device__ __forceinline__ void cam_cache_get(CamCache& cc, const double* __rest
     for (int k = 0; k < kCamQStride / 2; ++k) { q[2 * k] = t[k].x; q[2 * k + 1] = t[k].y; }
 }
 
-__global__ __launch_bounds__(256) void k_cost_partial(BAView v, double* __restrict__ partial) {
+template <class... LOSS>
+__global__ __launch_bounds__(256) void k_cost_partial(BAView v, LOSS... loss, double* __restrict__ partial) {
     __shared__ double scratch[4];
     __shared__ CamCache cache[4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -749,7 +757,7 @@ __global__ __launch_bounds__(256) void k_cost_partial(BAView v, double* __restri
         load_cam_q(q, v.mask_code, cam);
         const double pw[3] = {v.pts[3 * (size_t)l], v.pts[3 * (size_t)l + 1], v.pts[3 * (size_t)l + 2]};
         double r[2];
-        residual_obs(cam, pw, uv.x, uv.y, v.huber_delta, r);
+        residual_obs(cam, pw, uv.x, uv.y, loss_arg(v, loss...), r);
         s += active ? r[0] * r[0] + r[1] * r[1] : 0.0;
     }
     s = block_sum_256(s, scratch);
@@ -802,8 +810,8 @@ __global__ __launch_bounds__(256) void k_sumsq_partial(int64_t n, const double* 
 // Jacobi column scaling (process_jacobian_generic, optimizer/mod.rs:749-763): squared column norms of the
 // corrected Jacobian (compute_column_norms, linearizer/mod.rs:229-239).  Runs once per optimize.
 // ------------------------------------------------------------------------------------------
-template <int DC>
-__global__ __launch_bounds__(256) void k_column_norms_sq(BAView v, double* __restrict__ n2_cam, double* __restrict__ n2_pt) {
+template <int DC, class... LOSS>
+__global__ __launch_bounds__(256) void k_column_norms_sq(BAView v, LOSS... loss, double* __restrict__ n2_cam, double* __restrict__ n2_pt) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= v.n_obs) return;
     const uint32_t c = v.o_cam[i], l = v.o_pt[i];
@@ -812,7 +820,7 @@ __global__ __launch_bounds__(256) void k_column_norms_sq(BAView v, double* __res
     load_cam_prepared(v.camp + kCamStride * (size_t)c, cam);
     const double pw[3] = {v.pts[3 * (size_t)l], v.pts[3 * (size_t)l + 1], v.pts[3 * (size_t)l + 2]};
     double r[2], Jc[2][DC], Jl[2][3];
-    linearize_obs<DC>(cam, pw, uv.x, uv.y, v.huber_delta, r, Jc, Jl);
+    linearize_obs<DC>(cam, pw, uv.x, uv.y, loss_arg(v, loss...), r, Jc, Jl);
 #pragma unroll
     for (int a = 0; a < DC; ++a) atomicAdd(n2_cam + (size_t)c * DC + a, Jc[0][a] * Jc[0][a] + Jc[1][a] * Jc[1][a]);
 #pragma unroll
@@ -845,8 +853,8 @@ __global__ __launch_bounds__(256) void k_scale_diag_blocks(int64_t n_cam, const 
 
 // per-observation corrected residual and Jacobian blocks in the CALLER's observation order
 // (parity/debug export: apexgpu_get_residual / apexgpu_get_jacobian_blocks)
-template <int DC>
-__global__ __launch_bounds__(256) void k_export_linearization(BAView v, const int* __restrict__ o_orig,
+template <int DC, class... LOSS>
+__global__ __launch_bounds__(256) void k_export_linearization(BAView v, LOSS... loss, const int* __restrict__ o_orig,
                                                                 double* __restrict__ r_out,
                                                                 double* __restrict__ jc_out,
                                                                 double* __restrict__ jl_out) {
@@ -858,7 +866,7 @@ __global__ __launch_bounds__(256) void k_export_linearization(BAView v, const in
     load_cam_prepared(v.camp + kCamStride * (size_t)c, cam);
     const double pw[3] = {v.pts[3 * (size_t)l], v.pts[3 * (size_t)l + 1], v.pts[3 * (size_t)l + 2]};
     double r[2], Jc[2][DC], Jl[2][3];
-    linearize_obs<DC>(cam, pw, uv.x, uv.y, v.huber_delta, r, Jc, Jl);
+    linearize_obs<DC>(cam, pw, uv.x, uv.y, loss_arg(v, loss...), r, Jc, Jl);
     const int64_t o = o_orig[i];
     if (r_out) { r_out[2 * o] = r[0]; r_out[2 * o + 1] = r[1]; }
     if (jc_out)
@@ -887,10 +895,14 @@ static inline int grid_for(int64_t n, int per_block, int cap) {
 
 void launch_cam_reduce(int dc, const BAView& v, const TileMap& tm, const int* cam_ptr, const int* cam_obs,
                        double lambda, int add_lambda, const double* hinv, const double* g_l, int with_self, double* g_c,
-                       double* g_red, hipStream_t s) {
+                       double* g_red, hipStream_t s, const PgLoss* loss) {
     if (v.n_cam == 0) return;
     const bool masked = !(v.mask_code == 7 || (dc == 6 && v.mask_code == 6));   // (the masked form costs a wave per SIMD at d_c = 9)
-#define CAM_REDUCE(DCV, MK, WS) hipLaunchKernelGGL((k_cam_reduce<DCV, MK, WS>), dim3((unsigned)v.n_cam), dim3(kCamThreads), 0, s, v, tm, cam_ptr, cam_obs, lambda, add_lambda, hinv, g_l, g_c, g_red)
+#define CAM_REDUCE(DCV, MK, WS)                                                                                                                            \
+    do {                                                                                                                                                   \
+        if (loss) hipLaunchKernelGGL((k_cam_reduce<DCV, MK, WS, PgLoss>), dim3((unsigned)v.n_cam), dim3(kCamThreads), 0, s, v, *loss, tm, cam_ptr, cam_obs, lambda, add_lambda, hinv, g_l, g_c, g_red); \
+        else hipLaunchKernelGGL((k_cam_reduce<DCV, MK, WS>), dim3((unsigned)v.n_cam), dim3(kCamThreads), 0, s, v, tm, cam_ptr, cam_obs, lambda, add_lambda, hinv, g_l, g_c, g_red);                    \
+    } while (0)
     if (with_self) {
         if (dc == 9 && !masked) CAM_REDUCE(9, false, true); else if (dc == 9) CAM_REDUCE(9, true, true);
         else if (!masked) CAM_REDUCE(6, false, true); else CAM_REDUCE(6, true, true);
@@ -902,9 +914,14 @@ void launch_cam_reduce(int dc, const BAView& v, const TileMap& tm, const int* ca
 }
 
 void launch_landmark_reduce(int dc, const BAView& v, double lambda, double* hinv, double* g_l, int* err_flag, double* lmu,
-                            hipStream_t s, double* orec) {
+                            hipStream_t s, double* orec, const PgLoss* loss) {
     if (v.n_pt == 0) return;
     const int grid = lm_grid(v);
+    if (loss) {
+        if (dc == 9) hipLaunchKernelGGL((k_landmark_reduce<9, PgLoss>), dim3(grid), dim3(kLmWg * kLmLanes), 0, s, v, *loss, lambda, hinv, g_l, err_flag, lmu, orec);
+        else hipLaunchKernelGGL((k_landmark_reduce<6, PgLoss>), dim3(grid), dim3(kLmWg * kLmLanes), 0, s, v, *loss, lambda, hinv, g_l, err_flag, lmu, orec);
+        return;
+    }
     if (dc == 9) hipLaunchKernelGGL(k_landmark_reduce<9>, dim3(grid), dim3(kLmWg * kLmLanes), 0, s, v, lambda, hinv, g_l, err_flag, lmu, orec);
     else hipLaunchKernelGGL(k_landmark_reduce<6>, dim3(grid), dim3(kLmWg * kLmLanes), 0, s, v, lambda, hinv, g_l, err_flag, lmu, orec);
 }
@@ -917,12 +934,17 @@ void launch_prepare_cams(int64_t n_cam, const double* poses, const double* intr,
 // orec != nullptr: the record form (the records of THIS linearisation, k_landmark_reduce); ignored in the masked modes
 static bool rec_form_ok(int dc, const BAView& v, const double* orec) { return orec != nullptr && v.mask_code == (dc == 9 ? 7 : 6); }
 void launch_back_substitute(int dc, const BAView& v, const double* hinv, const double* g_l, const double* dcam,
-                            double* dl, hipStream_t s, const double* orec, const uint8_t* fix_pt, double* pts_trial) {
+                            double* dl, hipStream_t s, const double* orec, const uint8_t* fix_pt, double* pts_trial, const PgLoss* loss) {
     if (v.n_pt == 0) return;
     const int grid = lm_grid(v);
-    if (rec_form_ok(dc, v, orec)) {
+    if (rec_form_ok(dc, v, orec)) {   // (the record carries sqrt(rho') of whichever loss wrote it: one form for every loss)
         if (dc == 9) hipLaunchKernelGGL((k_back_substitute<9, false, true>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, g_l, dcam, dl, orec, fix_pt, pts_trial);
         else hipLaunchKernelGGL((k_back_substitute<6, false, true>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, g_l, dcam, dl, orec, fix_pt, pts_trial);
+        return;
+    }
+    if (loss) {
+        if (dc == 9) hipLaunchKernelGGL((k_back_substitute<9, false, false, kBsLanes, PgLoss>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, *loss, hinv, g_l, dcam, dl, nullptr, fix_pt, pts_trial);
+        else hipLaunchKernelGGL((k_back_substitute<6, false, false, kBsLanes, PgLoss>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, *loss, hinv, g_l, dcam, dl, nullptr, fix_pt, pts_trial);
         return;
     }
     if (dc == 9) hipLaunchKernelGGL((k_back_substitute<9, false, false>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, g_l, dcam, dl, nullptr, fix_pt, pts_trial);
@@ -942,8 +964,9 @@ void launch_retract(int dc, int64_t n_cam, int64_t n_pt, const double* poses, co
         hipLaunchKernelGGL(k_retract_points, dim3(grid_for(3 * n_pt, 256, 0)), dim3(256), 0, s, 3 * n_pt, pts, dl, sign, fix_pt, pts_out);
 }
 
-void launch_cost(const BAView& v, double* partial, int n_partial, double* out_sumsq, hipStream_t s) {
-    hipLaunchKernelGGL(k_cost_partial, dim3(n_partial), dim3(256), 0, s, v, partial);
+void launch_cost(const BAView& v, double* partial, int n_partial, double* out_sumsq, hipStream_t s, const PgLoss* loss) {
+    if (loss) hipLaunchKernelGGL(k_cost_partial<PgLoss>, dim3(n_partial), dim3(256), 0, s, v, *loss, partial);
+    else hipLaunchKernelGGL(k_cost_partial<>, dim3(n_partial), dim3(256), 0, s, v, partial);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, partial, n_partial, 1, out_sumsq);
 }
 
@@ -953,9 +976,14 @@ void launch_step_stats(int64_t n, const double* g, const double* d, double lambd
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, partial, n_partial, 3, out3);
 }
 
-void launch_column_norms_sq(int dc, const BAView& v, double* n2_cam, double* n2_pt, hipStream_t s) {
+void launch_column_norms_sq(int dc, const BAView& v, double* n2_cam, double* n2_pt, hipStream_t s, const PgLoss* loss) {
     if (v.n_obs == 0) return;
     const unsigned grid = (unsigned)((v.n_obs + 255) / 256);
+    if (loss) {
+        if (dc == 9) hipLaunchKernelGGL((k_column_norms_sq<9, PgLoss>), dim3(grid), dim3(256), 0, s, v, *loss, n2_cam, n2_pt);
+        else hipLaunchKernelGGL((k_column_norms_sq<6, PgLoss>), dim3(grid), dim3(256), 0, s, v, *loss, n2_cam, n2_pt);
+        return;
+    }
     if (dc == 9) hipLaunchKernelGGL(k_column_norms_sq<9>, dim3(grid), dim3(256), 0, s, v, n2_cam, n2_pt);
     else hipLaunchKernelGGL(k_column_norms_sq<6>, dim3(grid), dim3(256), 0, s, v, n2_cam, n2_pt);
 }
@@ -1006,16 +1034,24 @@ void launch_gather_u32(int64_t n, const int* idx, const uint32_t* src, uint32_t*
 }
 // y = S x without S: landmark half (u_l into lmu), then camera half
 void launch_implicit_matvec(int dc, const BAView& v, const int* cam_ptr, const double* hinv, double* lmu, const double* x,
-                            double lambda, double* y, hipStream_t s, const double* orec) {
+                            double lambda, double* y, hipStream_t s, const double* orec, const PgLoss* loss) {
     if (v.n_pt > 0) {
         const int grid = lm_grid(v);
         if (rec_form_ok(dc, v, orec)) {
             if (dc == 9) hipLaunchKernelGGL((k_back_substitute<9, true, true>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, nullptr, x, lmu, orec, nullptr, nullptr);
             else hipLaunchKernelGGL((k_back_substitute<6, true, true>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, nullptr, x, lmu, orec, nullptr, nullptr);
+        } else if (loss) {
+            if (dc == 9) hipLaunchKernelGGL((k_back_substitute<9, true, false, kBsLanes, PgLoss>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, *loss, hinv, nullptr, x, lmu, nullptr, nullptr, nullptr);
+            else hipLaunchKernelGGL((k_back_substitute<6, true, false, kBsLanes, PgLoss>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, *loss, hinv, nullptr, x, lmu, nullptr, nullptr, nullptr);
         } else {
             if (dc == 9) hipLaunchKernelGGL((k_back_substitute<9, true, false>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, nullptr, x, lmu, nullptr, nullptr, nullptr);
             else hipLaunchKernelGGL((k_back_substitute<6, true, false>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, nullptr, x, lmu, nullptr, nullptr, nullptr);
         }
+    }
+    if (loss) {
+        if (dc == 9) hipLaunchKernelGGL((k_implicit_cam<9, PgLoss>), dim3((unsigned)v.n_cam), dim3(64), 0, s, v, *loss, cam_ptr, lmu, x, lambda, y);
+        else hipLaunchKernelGGL((k_implicit_cam<6, PgLoss>), dim3((unsigned)v.n_cam), dim3(64), 0, s, v, *loss, cam_ptr, lmu, x, lambda, y);
+        return;
     }
     if (dc == 9) hipLaunchKernelGGL(k_implicit_cam<9>, dim3((unsigned)v.n_cam), dim3(64), 0, s, v, cam_ptr, lmu, x, lambda, y);
     else hipLaunchKernelGGL(k_implicit_cam<6>, dim3((unsigned)v.n_cam), dim3(64), 0, s, v, cam_ptr, lmu, x, lambda, y);
@@ -1082,9 +1118,14 @@ void launch_debug_invert_blocks(int64_t n, const double* in, double* out, int* o
 }
 
 void launch_export_linearization(int dc, const BAView& v, const int* o_orig, double* r_out, double* jc_out,
-                                 double* jl_out, hipStream_t s) {
+                                 double* jl_out, hipStream_t s, const PgLoss* loss) {
     if (v.n_obs == 0) return;
     const int grid = grid_for(v.n_obs, 256, 0);
+    if (loss) {
+        if (dc == 9) hipLaunchKernelGGL((k_export_linearization<9, PgLoss>), dim3(grid), dim3(256), 0, s, v, *loss, o_orig, r_out, jc_out, jl_out);
+        else hipLaunchKernelGGL((k_export_linearization<6, PgLoss>), dim3(grid), dim3(256), 0, s, v, *loss, o_orig, r_out, jc_out, jl_out);
+        return;
+    }
     if (dc == 9) hipLaunchKernelGGL(k_export_linearization<9>, dim3(grid), dim3(256), 0, s, v, o_orig, r_out, jc_out, jl_out);
     else hipLaunchKernelGGL(k_export_linearization<6>, dim3(grid), dim3(256), 0, s, v, o_orig, r_out, jc_out, jl_out);
 }

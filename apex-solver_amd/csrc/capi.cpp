@@ -172,6 +172,16 @@ int apexgpu_set_params(apexgpu_solver* h, const double* poses, const double* int
     if (!poses || !intr || !points) return APEXGPU_ERR_INVALID_INPUT;
     return guarded([&] { return h->s->set_params(poses, intr, points); });
 }
+int apexgpu_set_loss(apexgpu_solver* h, int kind, double p0, double p1) {
+    H_OR_FAIL;
+    return guarded([&] { return h->s->set_loss(kind, p0, p1); });
+}
+int apexgpu_get_loss(const apexgpu_solver* h, int* kind, double out2[2]) {
+    H_OR_FAIL;
+    if (!kind || !out2) return APEXGPU_ERR_INVALID_INPUT;
+    h->s->get_loss(kind, out2);
+    return APEXGPU_OK;
+}
 int apexgpu_get_params(apexgpu_solver* h, double* poses, double* intr, double* points) {
     H_OR_FAIL;
     if (!poses || !intr || !points) return APEXGPU_ERR_INVALID_INPUT;

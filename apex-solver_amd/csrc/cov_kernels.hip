@@ -37,14 +37,14 @@ __device__ __forceinline__ void load_hinv_point(const double* __restrict__ rec, 
 }
 
 // U = D_c (Jc^T Jl) Hinv of observation i (DC x 3, row-major) and its camera
-template <int DC>
-__device__ __forceinline__ uint32_t obs_u(const BAView& v, int64_t i, const double H[9], const double pw[3], double* __restrict__ U) {
+template <int DC, class LOSS>
+__device__ __forceinline__ uint32_t obs_u(const BAView& v, LOSS loss, int64_t i, const double H[9], const double pw[3], double* __restrict__ U) {
     const uint32_t c = v.o_cam[i];
     Cam cam;
     load_cam_q(v.camq + kCamQStride * (size_t)c, v.mask_code, cam);
     const double2 uv = v.o_uv[i];
     double r[2], Jc[2][DC], Jl[2][3];
-    linearize_obs<DC>(cam, pw, uv.x, uv.y, v.huber_delta, r, Jc, Jl);
+    linearize_obs<DC>(cam, pw, uv.x, uv.y, loss, r, Jc, Jl);
 #pragma unroll
     for (int a = 0; a < DC; ++a) {
         const double s = v.cam_scale ? v.cam_scale[(size_t)c * DC + a] : 1.0;
@@ -88,8 +88,9 @@ __device__ __forceinline__ void pair_term(const TileMap& z, const double* Ui, ui
 
 // G lanes per landmark, NT threads per workgroup; chunks of CH observations.  G == NT when CH chunks may repeat (k > CH): the
 // chunk loop then runs uniformly over the workgroup and may synchronise.
-template <int DC, int G, int NT, int CH>
-__global__ __launch_bounds__(NT) void k_landmark_cov(BAView v, const double* __restrict__ hinv, TileMap z, const int* __restrict__ list,
+// LOSS: empty (v.huber_delta) or PgLoss, a kernel argument of its own, as in ba_kernels.hip (ba_device.hpp, loss_arg)
+template <int DC, int G, int NT, int CH, class... LOSS>
+__global__ __launch_bounds__(NT) void k_landmark_cov(BAView v, LOSS... loss, const double* __restrict__ hinv, TileMap z, const int* __restrict__ list,
                                                      int n_list, double* __restrict__ out, int* __restrict__ err) {
     static_assert(NT % G == 0 && G <= 64, "groups inside a wave");
     constexpr int NGRP = NT / G, US = 3 * DC;
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(NT) void k_landmark_cov(BAView v, const double* __r
             if (MULTI) __syncthreads();   // (the previous chunk pair's reads are done)
             for (int q = t; q < two * CH; q += G) {
                 const int s = q / CH, o = q - s * CH, idx = (s == 0 ? ca : cb) * CH + o;
-                if (idx < k) sC[grp][s][o] = obs_u<DC>(v, b + idx, H, pw, &sU[grp][s][o * US]);
+                if (idx < k) sC[grp][s][o] = obs_u<DC>(v, loss_arg(v, loss...), b + idx, H, pw, &sU[grp][s][o * US]);
             }
             __syncthreads();
             const int na = min(CH, k - ca * CH), nb = min(CH, k - cb * CH);
@@ -161,9 +162,21 @@ __global__ __launch_bounds__(NT) void k_landmark_cov(BAView v, const double* __r
 }  // namespace
 
 void launch_landmark_cov(int dc, const BAView& v, const double* hinv, const TileMap& z, const int* small_list, int n_small,
-                         const int* large_list, int n_large, double* out, int* err, hipStream_t s) {
+                         const int* large_list, int n_large, double* out, int* err, hipStream_t s, const PgLoss* loss) {
     constexpr int NT = 128, G = 8;
     static_assert(kLcSmallK <= G, "a small landmark is one chunk of its group");
+    if (loss) {
+        if (n_large > 0) {
+            if (dc == 9) hipLaunchKernelGGL((k_landmark_cov<9, 64, 64, kLcChunk, PgLoss>), dim3(n_large), dim3(64), 0, s, v, *loss, hinv, z, large_list, n_large, out, err);
+            else hipLaunchKernelGGL((k_landmark_cov<6, 64, 64, kLcChunk, PgLoss>), dim3(n_large), dim3(64), 0, s, v, *loss, hinv, z, large_list, n_large, out, err);
+        }
+        if (n_small > 0) {
+            const int grid = (n_small + NT / G - 1) / (NT / G);
+            if (dc == 9) hipLaunchKernelGGL((k_landmark_cov<9, G, NT, kLcSmallK, PgLoss>), dim3(grid), dim3(NT), 0, s, v, *loss, hinv, z, small_list, n_small, out, err);
+            else hipLaunchKernelGGL((k_landmark_cov<6, G, NT, kLcSmallK, PgLoss>), dim3(grid), dim3(NT), 0, s, v, *loss, hinv, z, small_list, n_small, out, err);
+        }
+        return;
+    }
     if (n_large > 0) {   // first: the long ones start early and the short ones fill in behind them
         if (dc == 9) hipLaunchKernelGGL((k_landmark_cov<9, 64, 64, kLcChunk>), dim3(n_large), dim3(64), 0, s, v, hinv, z, large_list, n_large, out, err);
         else hipLaunchKernelGGL((k_landmark_cov<6, 64, 64, kLcChunk>), dim3(n_large), dim3(64), 0, s, v, hinv, z, large_list, n_large, out, err);

@@ -76,6 +76,24 @@ inline bool pg_loss_make(int kind, double p0, double p1, PgLoss* out) {
     return true;
 }
 
+// True where pg_loss_evaluate returns rho'' > 0 for no s >= 0, so that pg_corrector always takes its first arm (alpha = 0,
+// residual_scaling = sqrt(rho')): the losses one scalar per residual block expresses, the only ones the bundle-adjustment
+// kernels run.  Read off pg_loss_evaluate kind by kind: every rho'' there is minus a product of non-negative
+// factors, 0, or the L2 fall-back, except
+//   Andrews   (0.25 / scale) cos(x / scale) / x is positive for x < pi scale / 2, whatever the scale;
+//   Lp norm   e0 e1 s^e2 with e0 = p / 2 > 0, e1 = e0 - 1: positive exactly when p > 2;
+//   Barron    (alpha - 2) / (4 scale^2) inner^(alpha / 2 - 2) outside its two special cases: positive exactly when alpha > 2
+//             (alpha within 1e-6 of 2 is the L2 special case, within 1e-6 of 0 the Cauchy one; a NaN alpha fails both tests
+//             below and is refused with the rest).
+inline bool pg_loss_first_arm_only(const PgLoss& l) {
+    switch (l.kind) {
+        case kLossAndrews: return false;
+        case kLossLpNorm: return l.p0 <= 2.0;
+        case kLossBarron: return fabs(l.p0 - 2.0) < 1e-6 || l.p0 < 2.0;
+        default: return true;
+    }
+}
+
 APEX_LOSS_HD void pg_loss_set(double rho[3], double a, double b, double c) { rho[0] = a; rho[1] = b; rho[2] = c; }
 
 // rho = {rho(s), rho'(s), rho''(s)} at the squared norm s.  The kind is uniform over a launch: no divergence.

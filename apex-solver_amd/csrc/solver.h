@@ -35,6 +35,12 @@ class Solver : public TileBackend {
     int set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const double* obs_uv, const int64_t* intr_col,
                       const int64_t* pose_col, const int64_t* pt_col, const uint8_t* fix_pose, const uint8_t* fix_intr,
                       const uint8_t* fix_pt, double huber_delta);
+    // The loss of every ProjectionFactor block (pg_loss.hpp), in place of set_structure's huber_delta until the next
+    // set_structure.  kInvalidInput, and nothing changes: a kind or parameter pg_loss_make refuses, and a loss whose corrector
+    // can take its second arm (pg_loss_first_arm_only).  Voids a pending trial step, the projection records and
+    // the landmark covariance's linearisation, as set_params does.
+    int set_loss(int kind, double p0, double p1);
+    void get_loss(int* kind, double out2[2]) const;
     int set_params(const double* poses, const double* intr, const double* points);
     int get_params(double* poses, double* intr, double* points);
     void set_cg_params(int max_iter, double tol) { cg_max_iter_ = max_iter; cg_tol_ = tol; }
@@ -199,6 +205,13 @@ class Solver : public TileBackend {
     int64_t n_c_ = 0, n_c_pad_ = 0;
     int nt_ = 0;
     double huber_delta_ = 1.0;
+    PgLoss loss_;
+    bool loss_set_ = false;   // set_loss has replaced huber_delta_ (until the next set_structure)
+    // what the launchers of the linearising kernels take: the loss of the general instantiations, or NULL where the
+    // huber_delta kernels compute it (no set_loss; no loss, L2 and Huber given through set_loss: view())
+    const PgLoss* general_loss() const {
+        return loss_set_ && loss_.kind != kLossNone && loss_.kind != kLossL2 && loss_.kind != kLossHuber ? &loss_ : nullptr;
+    }
     bool have_structure_ = false, have_params_ = false;
     double last_reg_ = 0.0;
     int last_pcg_iters_ = 0;

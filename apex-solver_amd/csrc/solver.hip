@@ -77,7 +77,9 @@ BAView Solver::view(int which) const {
     v.n_cam = n_cam_; v.n_pt = n_pt_; v.n_obs = (int64_t)o_orig_h_.size();
     v.camp = camp_[which]; v.camq = camp_[which] + (size_t)kCamStride * n_cam_; v.pts = pts_[which];
     v.o_cam = o_cam_; v.o_pt = o_pt_; v.o_uv = reinterpret_cast<const double2*>(o_uv_.get()); v.pt_ptr = pt_ptr_;
-    v.huber_delta = huber_delta_;
+    // set_loss: no loss, L2 and Huber are what the huber_delta kernels compute, so they run there (the same bits as a delta given
+    // to set_structure); every other kind runs the general instantiations, which take general_loss() and do not read this
+    v.huber_delta = !loss_set_ ? huber_delta_ : (loss_.kind == kLossHuber ? loss_.p0 : -1.0);
     v.mask_code = mode_mask(mode_);
     v.co_pt = co_pt_; v.co_uv = reinterpret_cast<const double2*>(co_uv_.get()); v.co_rank = co_rank_;
     v.cam_scale = scaled_ ? cam_scale_ : nullptr;
@@ -481,6 +483,8 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     { const int rc = validate_indices(su); if (rc != kOk) return rc; }
     su.release_device_thread(true);
     huber_delta_ = huber_delta;
+    loss_set_ = false;
+    loss_ = PgLoss{};
     intr_col_.assign(intr_col, intr_col + n_cam_);
     pose_col_.assign(pose_col, pose_col + n_cam_);
     pt_col_.assign(pt_col, pt_col + n_pt_);
@@ -584,6 +588,32 @@ int Solver::set_params(const double* poses, const double* intr, const double* po
     return kOk;
 }
 
+int Solver::set_loss(int kind, double p0, double p1) {
+    if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
+    PgLoss l;
+    if (!pg_loss_make(kind, p0, p1, &l)) return fail(kInvalidInput, "set_loss: unknown loss kind or a parameter its constructor refuses");
+    if (!pg_loss_first_arm_only(l)) {
+        const char* name = kind == kLossAndrews ? "Andrews" : kind == kLossLpNorm ? "LpNorm with p > 2" : "Barron with alpha > 2";
+        return fail(kInvalidInput, std::string("set_loss: ") + name + " has rho'' > 0 for some residuals; the corrector's rank-one "
+                    "Jacobian term does not fit the one weight per observation of the bundle-adjustment kernels");
+    }
+    HIP_TRY(hipSetDevice(device_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    st_.invalidate(); orec_fresh_ = false;
+    factor_lin_ = -1;   // (the factor was linearised under the old loss)
+    loss_ = l;
+    loss_set_ = true;
+    return kOk;
+}
+
+// what the observations carry: the loss of set_loss, else set_structure's Huber delta (or none)
+void Solver::get_loss(int* kind, double out2[2]) const {
+    out2[0] = out2[1] = 0.0;
+    if (loss_set_) { *kind = loss_.kind; out2[0] = loss_.p0; out2[1] = loss_.p1; }
+    else if (huber_delta_ > 0.0) { *kind = kLossHuber; out2[0] = huber_delta_; }
+    else *kind = kLossNone;
+}
+
 int Solver::get_params(double* poses, double* intr, double* points) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
@@ -627,7 +657,7 @@ int Solver::cost(double* out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
     stage_begin(kStCost);
-    launch_cost(view(st_.cur), partial_, n_partial_, scal_, stream_);
+    launch_cost(view(st_.cur), partial_, n_partial_, scal_, stream_, general_loss());
     if (comm_ && world_ > 1)
         COMM_TRY(comm_->all_reduce_sum(scal_, 1, stream_));
     stage_end(kStCost);
@@ -686,12 +716,12 @@ int Solver::assemble_local(double lambda, double diag_extra, bool for_factor) {
     tp_.add_diag((int)n_c_, 0.0, rank_ == pad_rank_ ? 1.0 : 0.0);
     stage_end(kStAssembleCam);
     stage_begin(kStAssembleLm);
-    launch_landmark_reduce(dc_, v, lambda, hinv_, g_l_, flags_, nullptr, stream_, orec_);   // (the pair kernel and the back-substitution read the projection records)
+    launch_landmark_reduce(dc_, v, lambda, hinv_, g_l_, flags_, nullptr, stream_, orec_, general_loss());   // (the pair kernel and the back-substitution read the projection records)
     orec_fresh_ = true;
     stage_end(kStAssembleLm);
     stage_begin(kStAssembleCam);
     launch_cam_reduce(dc_, v, tm, cam_ptr_, cam_obs_, lambda + diag_extra, rank_ == 0 ? 1 : 0, hinv_, g_l_, 1,
-                      g_c_, g_red_, stream_);
+                      g_c_, g_red_, stream_, general_loss());
     stage_end(kStAssembleCam);
     stage_begin(kStScatter);
     launch_schur_pairs(dc_, v, tp_.tiles(), ptasks_, n_ptasks_, pchunks_, pblocks_, precs_, hinv_, stream_, orec_, pqdesc_);
@@ -797,11 +827,11 @@ int Solver::assemble_implicit(double lambda) {
     const BAView v = view(st_.cur);
     stage_begin(kStAssembleLm);
     HIP_TRY(hipMemsetAsync(flags_, 0, 4 * sizeof(int), stream_));
-    launch_landmark_reduce(dc_, v, lambda, hinv_, g_l_, flags_, lmu_, stream_, orec_);
+    launch_landmark_reduce(dc_, v, lambda, hinv_, g_l_, flags_, lmu_, stream_, orec_, general_loss());
     orec_fresh_ = orec_ != nullptr;
     stage_end(kStAssembleLm);
     stage_begin(kStAssembleCam);
-    launch_cam_reduce(dc_, v, tilemap(), cam_ptr_, cam_obs_, lambda, rank_ == 0 ? 1 : 0, hinv_, g_l_, 1, g_c_, g_red_, stream_);
+    launch_cam_reduce(dc_, v, tilemap(), cam_ptr_, cam_obs_, lambda, rank_ == 0 ? 1 : 0, hinv_, g_l_, 1, g_c_, g_red_, stream_, general_loss());
     launch_extract_diag_blocks(dc_, n_cam_, tilemap(), sd_, stream_);
     stage_end(kStAssembleCam);
     if (comm_ && world_ > 1) {
@@ -833,7 +863,7 @@ int Solver::implicit_matvec(const double* x, double lam_local, double* y, bool r
         launch_vec_mul(n_c_, x, cam_scale_, t, stream_);
         xin = t;
     }
-    launch_implicit_matvec(dc_, view(st_.cur), cam_ptr_, hinv_, lmu_, xin, lam_local, y, stream_, backsub_records());
+    launch_implicit_matvec(dc_, view(st_.cur), cam_ptr_, hinv_, lmu_, xin, lam_local, y, stream_, backsub_records(), general_loss());
     if (reduce && comm_ && world_ > 1)
         COMM_TRY(comm_->all_reduce_sum(y, (size_t)n_c_, stream_));
     if (scaled_) launch_vec_mul(n_c_, y, cam_scale_, y, stream_);
@@ -934,7 +964,7 @@ int Solver::finish_step(double* step_out, double* grad_out) {
     const bool eager = eager_eval_ && !(comm_ && world_ > 1);
     trial_pts_written_ = eager && fix_pt_ != nullptr;
     launch_back_substitute(dc_, view(st_.cur), hinv_, g_l_, dcam_, dl_, stream_, backsub_records(), trial_pts_written_ ? fix_pt_ : nullptr,
-                           trial_pts_written_ ? pts_[st_.cur ^ 1] : nullptr);
+                           trial_pts_written_ ? pts_[st_.cur ^ 1] : nullptr, general_loss());
     stage_end(kStBackSub);
     HIP_TRY(hipGetLastError());
     st_.step_computed();
@@ -1028,7 +1058,7 @@ int Solver::dist_phase(int phase, double lambda) {
         case 5:
             tp_.solve_phase(2, g_red_, dcam_, pcg_buf_);
             if (scaled_) launch_vec_mul(n_c_, dcam_, cam_scale_, dcam_, stream_);
-            launch_back_substitute(dc_, view(st_.cur), hinv_, g_l_, dcam_, dl_, stream_, backsub_records());
+            launch_back_substitute(dc_, view(st_.cur), hinv_, g_l_, dcam_, dl_, stream_, backsub_records(), nullptr, nullptr, general_loss());
             HIP_TRY(hipStreamSynchronize(stream_));
             st_.step_computed();
             return kOk;
@@ -1095,7 +1125,7 @@ int Solver::enqueue_trial_point(double* sumsq_out) {
     retract_sets(st_.cur, 1.0, t, trial_pts_written_ ? 0 : n_pt_);   // (the points: by k_back_substitute when trial_pts_written_)
     trial_pts_written_ = false;
     stage_begin(kStCost);
-    launch_cost(view(t), partial_, n_partial_, sumsq_out, stream_);
+    launch_cost(view(t), partial_, n_partial_, sumsq_out, stream_, general_loss());
     if (comm_ && world_ > 1)
         COMM_TRY(comm_->all_reduce_sum(sumsq_out, 1, stream_));
     stage_end(kStCost);
@@ -1138,7 +1168,7 @@ int Solver::column_norms_sq_device() {
     scaled_ = was;
     HIP_TRY(hipMemsetAsync(cam_scale_, 0, n_c_pad_ * sizeof(double), stream_));
     HIP_TRY(hipMemsetAsync(pt_scale_, 0, std::max<int64_t>(3 * n_pt_, 1) * sizeof(double), stream_));
-    launch_column_norms_sq(dc_, v, cam_scale_, pt_scale_, stream_);
+    launch_column_norms_sq(dc_, v, cam_scale_, pt_scale_, stream_, general_loss());
     if (comm_ && world_ > 1)  // every rank sees all cameras but only its own landmarks
         COMM_TRY(comm_->all_reduce_sum(cam_scale_, (size_t)n_c_, stream_));
     return kOk;
@@ -1237,7 +1267,7 @@ int Solver::get_residual(double* r_out) {
     DeviceBuffer<double> d;
     HIP_TRY(d.alloc(2 * n_obs_));
     hipMemsetAsync(d, 0, 2 * n_obs_ * sizeof(double), stream_);
-    launch_export_linearization(dc_, view(st_.cur), o_orig_, d, nullptr, nullptr, stream_);
+    launch_export_linearization(dc_, view(st_.cur), o_orig_, d, nullptr, nullptr, stream_, general_loss());
     hipError_t e = hipMemcpyAsync(r_out, d, 2 * n_obs_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     hipStreamSynchronize(stream_);
     return check_hip(e, "get_residual");
@@ -1251,7 +1281,7 @@ int Solver::get_jacobian_blocks(double* jc_out, double* jl_out) {
     HIP_TRY(dl.alloc(6 * n_obs_));
     hipMemsetAsync(dj, 0, 2 * dc_ * n_obs_ * sizeof(double), stream_);
     hipMemsetAsync(dl, 0, 6 * n_obs_ * sizeof(double), stream_);
-    launch_export_linearization(dc_, view(st_.cur), o_orig_, nullptr, dj, dl, stream_);
+    launch_export_linearization(dc_, view(st_.cur), o_orig_, nullptr, dj, dl, stream_, general_loss());
     hipError_t e1 = hipMemcpyAsync(jc_out, dj, 2 * dc_ * n_obs_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     hipError_t e2 = hipMemcpyAsync(jl_out, dl, 6 * n_obs_ * sizeof(double), hipMemcpyDeviceToHost, stream_);
     hipStreamSynchronize(stream_);
@@ -1575,7 +1605,7 @@ int Solver::landmark_covariance(double* out) {
     }
     HIP_TRY(hipMemsetAsync(lc_err_, 0, sizeof(int), stream_));
     if (timed) HIP_TRY(hipEventRecord(ev[0], stream_));
-    launch_landmark_cov(dc_, v, hinv_, tp_.inverse().map(), lc_lists_, lc_n_small_, lc_lists_ + lc_n_small_, lc_n_large_, lc_out_, lc_err_, stream_);
+    launch_landmark_cov(dc_, v, hinv_, tp_.inverse().map(), lc_lists_, lc_n_small_, lc_lists_ + lc_n_small_, lc_n_large_, lc_out_, lc_err_, stream_, general_loss());
     if (timed) HIP_TRY(hipEventRecord(ev[1], stream_));
     hipError_t e = hipGetLastError();
     std::vector<double> blk(9 * (size_t)n_pt_);

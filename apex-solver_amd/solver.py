@@ -27,6 +27,7 @@ import numpy as np
 
 from . import capi
 from .layout import ColumnLayout, reference_column_layout
+from .loss import Loss, create_loss_function  # noqa: F401
 from .synthetic import BAProblemData
 
 
@@ -163,6 +164,7 @@ class Problem:
     fix_pose: np.ndarray = field(default=None)
     fix_intr: np.ndarray = field(default=None)
     fix_pt: np.ndarray = field(default=None)
+    loss: Loss | None = None   # the loss of every ProjectionFactor block; takes precedence over huber_delta
 
     def __post_init__(self):
         d = self.data
@@ -176,10 +178,10 @@ class Problem:
 
     @classmethod
     def bundle_adjustment(cls, data: BAProblemData, optimization_type=OptimizationType.SelfCalibration,
-                          huber_delta: float | None = 1.0) -> "Problem":
+                          huber_delta: float | None = 1.0, loss: Loss | None = None) -> "Problem":
         """run_bundle_adjustment (bin/bundle_adjustment.rs:211-298): gauge fixed by all six DOF of
-        pose_0000."""
-        p = cls(data, optimization_type, huber_delta)
+        pose_0000.  loss (loss.create_loss_function), when given, replaces HuberLoss(huber_delta) on every block."""
+        p = cls(data, optimization_type, huber_delta, loss=loss)
         for dof in range(6):
             p.fix_variable("pose_0000", dof)
         return p
@@ -273,6 +275,8 @@ class GpuSchurComplementSolver:
         t3 = time.perf_counter()
         h.check(h.L.apexgpu_set_cg_params(h.h, self.cg_max_iterations, self.cg_tolerance))
         self._problem = problem
+        if problem.loss is not None:
+            self.set_loss(problem.loss)
         # wall time of this call by piece (seconds): handle + communicator, host-side argument arrays, apexgpu_set_structure
         self.setup_wall = dict(create_handle=t1 - t0, host_arrays=t2 - t1, set_structure=t3 - t2)
         return self
@@ -293,7 +297,24 @@ class GpuSchurComplementSolver:
         h.check(h.L.apexgpu_set_structure(h.h, *[capi.ptr(a) for a in self._keep], hd))
         h.check(h.L.apexgpu_set_cg_params(h.h, self.cg_max_iterations, self.cg_tolerance))
         self._problem = problem
+        if problem.loss is not None:
+            self.set_loss(problem.loss)
         return self
+
+    def set_loss(self, loss: Loss | None):
+        """The loss of every ProjectionFactor block from here on (None: no loss); replaces the problem's huber_delta until the
+        next initialize_structure.  InvalidInput for the kinds whose corrector needs more than one weight per observation
+        (Andrews, lp with p > 2, Barron with alpha > 2).  With several ranks every rank sets the same loss."""
+        h = self._need()
+        if loss is None:
+            loss = Loss(capi.LOSS_NONE)
+        h.check(h.L.apexgpu_set_loss(h.h, int(loss.kind), float(loss.p0), float(loss.p1)))
+
+    def get_loss(self) -> Loss:
+        h = self._need()
+        k = C.c_int(); p = (C.c_double * 2)()
+        h.check(h.L.apexgpu_get_loss(h.h, C.byref(k), C.byref(p)))
+        return Loss(k.value, p[0], p[1])
 
     def _need(self) -> capi.Handle:
         if self._h is None:

@@ -106,6 +106,24 @@ int apexgpu_set_cg_params(apexgpu_solver* h, int max_iterations, double toleranc
  * Replaces Problem::initialize_variables (src/core/problem.rs:686-808) / reading
  * SolverResult.parameters back (src/optimizer/mod.rs:250-273). */
 int apexgpu_set_params(apexgpu_solver* h, const double* poses, const double* intr, const double* points);
+/* The loss of every ProjectionFactor block (Problem::add_residual_block takes any LossFunction; src/core/loss_functions.rs):
+ * kind is an APEXGPU_LOSS_* value and p0, p1 its parameters, as for apexgpu_pg_set_loss below.  After apexgpu_set_structure;
+ * replaces huber_delta's loss until the next set_structure.  Voids a pending step (apexgpu_commit_step then answers
+ * APEXGPU_ERR_INVALID_STATE) like apexgpu_set_params, and the linearisation apexgpu_landmark_covariance relies on.  Every
+ * variant, the LM loop, Jacobi scaling, the covariances and the exports use it.  NONE, L2 and HUBER run the kernels
+ * huber_delta runs, bit for bit; an observation whose rho' is 0 (TUKEY, TRIMMED_MEAN beyond their cut) contributes nothing,
+ * and a landmark all of whose observations are cut gets a zero step.
+ * The bundle-adjustment kernels apply a loss as one weight sqrt(rho') per observation, which is the whole corrector
+ * (src/core/corrector.rs:143-181) exactly where rho'' <= 0 everywhere.  The kinds that can have rho'' > 0 are refused:
+ * ANDREWS, LP_NORM with p > 2, BARRON with alpha - 2 >= 1e-6.
+ * APEXGPU_ERR_INVALID_INPUT for those (apexgpu_last_error names the kind), where the reference's new() fails (scale <= 0,
+ * p <= 0, nu <= 0), for a NaN parameter or an unknown kind -- the handle's loss is then unchanged;
+ * APEXGPU_ERR_INVALID_STATE before set_structure.
+ * Several ranks (apexgpu_create_with_shard, shm or RCCL communicator): every rank sets the same loss, like every other
+ * per-handle setting. */
+int apexgpu_set_loss(apexgpu_solver* h, int kind, double p0, double p1);
+/* what the observations carry: the loss of set_loss, else HUBER with set_structure's delta, else NONE; out2 = {p0, p1} */
+int apexgpu_get_loss(const apexgpu_solver* h, int* kind, double out2[2]);
 int apexgpu_get_params(apexgpu_solver* h, double* poses, double* intr, double* points);
 
 /* ---- hot path --------------------------------------------------------------------------------*/

@@ -78,6 +78,7 @@ impl GpuSchurComplementSolver {
         let (mut cam_idx, mut pt_idx, mut uv) = (Vec::with_capacity(n_obs), Vec::with_capacity(n_obs), Vec::with_capacity(2 * n_obs));
         let mut mode: Option<i32> = None;
         let mut huber: Option<f64> = None; // Some(-1.0): no loss function on any block
+        let mut family: Option<DeviceLossDesc> = None; // a loss other than Huber on every block: apexgpu_set_loss
         for b in &blocks {
             let d = b.factor.device_descriptor().ok_or_else(|| bad("a factor has no device descriptor".into()))?;
             let m = d.device_mode().ok_or_else(|| bad("a projection factor that optimises nothing".into()))?;
@@ -98,14 +99,16 @@ impl GpuSchurComplementSolver {
             } else {
                 fixed_intr[ci] = d.intrinsics;
             }
-            let scale = match &b.loss_func {
-                None => -1.0,
-                Some(l) => match l.device_descriptor() {
-                    Some(DeviceLossDesc::Huber { scale }) => scale,
-                    None => return Err(bad("a loss function has no device descriptor".into())),
-                },
+            let desc = match &b.loss_func {
+                None => None,
+                Some(l) => Some(l.device_descriptor().ok_or_else(|| bad("a loss function has no device descriptor".into()))?),
             };
-            if *huber.get_or_insert(scale) != scale { return Err(bad("mixed loss functions".into())); }
+            let scale = match desc {
+                None | Some(DeviceLossDesc::Family { .. }) => -1.0,
+                Some(DeviceLossDesc::Huber { scale }) => scale,
+            };
+            let fam = match desc { Some(f @ DeviceLossDesc::Family { .. }) => f, _ => DeviceLossDesc::Huber { scale } };
+            if *huber.get_or_insert(scale) != scale || *family.get_or_insert(fam) != fam { return Err(bad("mixed loss functions".into())); }
             cam_idx.push(ci as u32); pt_idx.push(pi as u32); uv.extend_from_slice(&d.uv);
         }
         let mode = mode.unwrap_or(APEXGPU_MODE_SELF_CALIBRATION);
@@ -145,6 +148,9 @@ impl GpuSchurComplementSolver {
         check(h, unsafe { apexgpu_set_option(h, b"eager_step_eval\0".as_ptr() as *const c_char, 0) })?;
         check(h, unsafe { apexgpu_set_structure(h, cam_idx.as_ptr(), pt_idx.as_ptr(), uv.as_ptr(), intr_col.as_ptr(), pose_col.as_ptr(),
                                                  pt_col.as_ptr(), fix_pose.as_ptr(), fix_intr.as_ptr(), fix_pt.as_ptr(), huber.unwrap_or(-1.0)) })?;
+        // a loss of the family other than Huber: the device refuses (InvalidInput, named) the kinds its one weight per observation
+        // cannot express; the LM dispatch arm then falls back to the CPU Schur solver like for a factor without a descriptor
+        if let Some(DeviceLossDesc::Family { kind, p0, p1 }) = family { check(h, unsafe { apexgpu_set_loss(h, kind, p0, p1) })?; }
         check(h, unsafe { apexgpu_set_cg_params(h, self.cg.0, self.cg.1) })?;
         {
             // A structure whose direct factorisation the backend refuses (S dense at tile granularity) does not fail: the handle

@@ -57,6 +57,10 @@ extern "C" {
     pub fn apexgpu_trim_host_cache(released_bytes: *mut i64) -> c_int;
     pub fn apexgpu_host_cache_bytes() -> i64;
     pub fn apexgpu_set_params(h: *mut ApexGpuSolver, poses: *const f64, intr: *const f64, points: *const f64) -> c_int;
+    /// the loss of every projection block (`APEXGPU_LOSS_*`), after `apexgpu_set_structure`, in place of its `huber_delta`;
+    /// `InvalidInput` for the kinds whose corrector can take its second arm (Andrews, Lp with p > 2, Barron with alpha > 2)
+    pub fn apexgpu_set_loss(h: *mut ApexGpuSolver, kind: c_int, p0: f64, p1: f64) -> c_int;
+    pub fn apexgpu_get_loss(h: *const ApexGpuSolver, kind: *mut c_int, out2: *mut f64) -> c_int;
     pub fn apexgpu_solve_augmented(h: *mut ApexGpuSolver, lambda: f64, variant: c_int, step_out: *mut f64, grad_out: *mut f64) -> c_int;
     pub fn apexgpu_column_norms(h: *mut ApexGpuSolver, norms_out: *mut f64) -> c_int;
     pub fn apexgpu_set_column_scaling(h: *mut ApexGpuSolver, scaling: *const f64) -> c_int;
@@ -121,10 +125,13 @@ impl DeviceFactorDesc {
         }
     }
 }
-/// Returned by `LossFunction::device_descriptor()`; `HuberLoss` answers `Some(Huber { scale })`.
+/// Returned by `LossFunction::device_descriptor()`; `HuberLoss` answers `Some(Huber { scale })`, every other loss of
+/// src/core/loss_functions.rs `Some(Family { kind, p0, p1 })` with `kind` an `APEXGPU_LOSS_*` value of include/apexgpu.h and
+/// (p0, p1) its parameters as `apexgpu_set_loss` takes them (scale | p | nu | Barron's alpha, Barron's scale).
 #[derive(Clone, Copy, Debug, PartialEq)]
 pub enum DeviceLossDesc {
     Huber { scale: f64 },
+    Family { kind: i32, p0: f64, p1: f64 },
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
