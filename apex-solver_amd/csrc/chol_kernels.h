@@ -1,4 +1,4 @@
-// chol_kernels.h -- launchers of the tile Cholesky / triangular-solve / PCG kernels.
+// chol_kernels.h -- launchers of the tile Cholesky / triangular-solve kernels and of the small operations on a plan's tiles.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,13 +8,6 @@
 
 namespace apex {
 
-void launch_sym_tile_products(const SymTile* list, int n, const double* tiles, const double* x, double* part, hipStream_t s);
-void launch_sym_tile_gather(int nt, const int* row_ptr, const SymEntry* entries, const double* part, const double* p,
-                            double* y, double* row_dot, hipStream_t s);
-void launch_pcg_step1(int n, int nt, const double* scal, const double* row_dot, const double* p, const double* ap,
-                      const double* pre, double* x, double* r, double* blk_part, double* out_pap, hipStream_t s);
-void launch_pcg_step2(int n, double* scal, const double* blk_part, const double* pre, const double* r, double* p,
-                      double* out2, double abs_tol, hipStream_t s);
 void launch_potrf_inv(const PotrfTask* tasks, int n, int* fail, hipStream_t s, int* arrived = nullptr);
 void launch_gate(const int* arrived, int expected, int max_micros, hipStream_t s);
 // the dataflow factorisation: one workgroup per unit, dispatched in list order; ver[] must be zero; err: error word (time-out)
@@ -41,13 +34,5 @@ void launch_tile_add_diag(double* tiles, const int* diag_slot, int n_valid, int 
 void launch_vec_select(int n, const double* in, const int* cls, int mask, double* out, hipStream_t s);
 void launch_vec_merge(int n, const double* src, const int* cls, int mask, double* dst, hipStream_t s);
 void launch_tile_scale_sym(const SymTile* list, int n, double* tiles, const double* scale /* n_pad */, hipStream_t s);
-void launch_pcg_init(int n, const double* diag, const double* b, double* pre, double* x, double* r, double* z, double* p,
-                     hipStream_t s);
-void launch_dot(int n, const double* a, const double* b, double* out, hipStream_t s);
-// the matrix-free PCG's scalars on the device (sc: [0] r.r [1] r.z [2] p.Ap [4] rz_old [5] frozen [6] beta): see k_pcg_implicit_close
-void launch_pcg_implicit_begin(double* sc, hipStream_t s);
-void launch_pcg_update_xr_sc(int n, const double* sc, const double* p, const double* ap, double* x, double* r, hipStream_t s);
-void launch_pcg_implicit_close(double* sc, double abs_tol, hipStream_t s);
-void launch_pcg_update_p_sc(int n, const double* sc, const double* z, double* p, hipStream_t s);
 
 }  // namespace apex

@@ -14,6 +14,8 @@
 
 #include "ba_kernels.h"
 #include "chol_kernels.h"
+#include "pcg_kernels.h"
+#include "pcg_readback.h"
 #include "schur_pairs.h"
 #include "comm.h"
 #include "tile_backend.h"
@@ -249,8 +251,7 @@ class Solver : public TileBackend {
     bool matrix_free_only_opt_ = false;   // the caller's option ("matrix_free_only")
     bool matrix_free_only_ = false;       // the effective state of the structure that is built: the option, or the automatic selection
     bool trial_pts_written_ = false;   // the back-substitution of this solve has written the trial points (enqueue_trial_point skips them)
-    PinnedBuffer<double> pcg_host_;              // two slots of the matrix-free PCG's scalars (read one iteration behind)
-    hipEvent_t pcg_ev_[2] = {nullptr, nullptr};
+    PcgReadback<ImplicitPcgScalars> pcg_readback_;   // the matrix-free PCG's scalars, read one iteration behind
     bool device_pair_recs_ = true;   // queued layout: the pair records are written by the device (k_build_pair_recs_q), not built on the host and copied
     bool auto_variant_ = true, auto_fallback_ = false;   // see set_auto_variant
     int variant_cost_permille_ = 1000, variant_choice_ = 0;

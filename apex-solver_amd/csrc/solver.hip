@@ -2,6 +2,7 @@
 #include "solver.h"
 #include "ba_device.hpp"
 #include "ba_structure.h"
+#include "pcg_loop.h"
 
 #include <math.h>
 #include <string.h>
@@ -17,6 +18,7 @@ namespace apex {
 void warm_ba_kernels(hipStream_t s);
 void warm_schur_pairs(hipStream_t s);
 void warm_chol_kernels(hipStream_t s);
+void warm_pcg_kernels(hipStream_t s);
 
 // every collective's result is surfaced as APEXGPU_ERR_DEVICE with the transport's own text (comm.h)
 #define COMM_TRY(expr)                                                                  \
@@ -43,7 +45,6 @@ Solver::~Solver() {
     hipSetDevice(device_);
     if (stream_) hipStreamSynchronize(stream_);   // (and the join above) before any buffer is freed; stream_last_ destroys the stream after them
     comm_.reset();
-    for (hipEvent_t e : pcg_ev_) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : pin_ev_) if (e) (void)hipEventDestroy(e);
 }
 
@@ -230,7 +231,7 @@ void Solver::device_thread_body(Setup& su) {
     }
     hipStream_t ws = nullptr;
     if (hipStreamCreateWithFlags(&ws, hipStreamNonBlocking) != hipSuccess) return;
-    warm_ba_kernels(ws); warm_schur_pairs(ws); warm_chol_kernels(ws);
+    warm_ba_kernels(ws); warm_schur_pairs(ws); warm_chol_kernels(ws); warm_pcg_kernels(ws);
     (void)hipStreamSynchronize(ws);
     (void)hipStreamDestroy(ws);
     wt.mark("device thread: code objects");
@@ -874,27 +875,23 @@ int Solver::implicit_pcg_solve(double lambda, int max_iter, double tol) {
     stage_begin(kStFactor);
     const int n = (int)n_c_;
     double *x = dcam_, *r = pcg_buf_, *z = pcg_buf_ + n_c_pad_, *p = pcg_buf_ + 2 * n_c_pad_, *ap = pcg_buf_ + 3 * n_c_pad_;
-    double* sc = scal_ + 16;   // [0] r.r  [1] r.z  [2] p.Ap  [4] rz_old  [5] frozen  [6] beta (chol_kernels.h)
-    if (!pcg_host_) {
-        HIP_TRY(pcg_host_.alloc(16));
-        for (hipEvent_t& ev : pcg_ev_) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    }
+    double* sc = scal_ + 16;   // ImplicitPcgScalars (pcg_kernels.h)
+    HIP_TRY(pcg_readback_.ensure());
     HIP_TRY(hipMemsetAsync(x, 0, n_c_pad_ * sizeof(double), stream_));
     HIP_TRY(hipMemcpyAsync(r, g_red_, n_c_pad_ * sizeof(double), hipMemcpyDeviceToDevice, stream_));
     launch_precond_apply(dc_, n_cam_, minv_, r, z, stream_);
     HIP_TRY(hipMemcpyAsync(p, z, n_c_pad_ * sizeof(double), hipMemcpyDeviceToDevice, stream_));
     launch_dot2(n, r, z, r, r, partial_, n_partial_, sc, stream_);
     launch_pcg_implicit_begin(sc, stream_);   // rz_old := r.z, not frozen
-    double* h = pcg_host_;
-    HIP_TRY(hipMemcpyAsync(h, sc, 2 * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(&pcg_readback_.host(0), sc, 2 * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    const double abs_tol = tol * std::max(sqrt(h[1]), 1.0);
+    ImplicitPcgStart start;
+    memcpy(&start, &pcg_readback_.host(0), sizeof start);
+    const double abs_tol = tol * std::max(sqrt(start.rr), 1.0);
     const double lam_local = (rank_ == 0) ? lambda : 0.0;  // the all-reduce sums the ranks' partial S p
     // Every scalar of the iteration stays on the device (alpha, beta, the reference's three termination tests:
-    // k_pcg_implicit_close), and the host reads {r.r, r.z, p.Ap, frozen} ONE ITERATION BEHIND: iteration k + 1 is enqueued
-    // before the host waits for iteration k, so the device never idles through a host round trip (round 5; two round trips per
-    // iteration before).  An iteration enqueued behind a met test changes nothing: x, r, p and the iteration count are those of
-    // the loop that waited every time.  (Sharded: every rank reads the same scalars and enqueues the same iterations.)
+    // k_pcg_implicit_close), and the host reads {r.r, r.z, p.Ap, frozen} one iteration behind (pcg_loop.h).  (Sharded: every rank
+    // reads the same scalars and enqueues the same iterations.)
     auto enqueue_iteration = [&](int slot) -> int {
         const int mrc = implicit_matvec(p, lam_local, ap, true);
         if (mrc != kOk) return mrc;
@@ -904,21 +901,18 @@ int Solver::implicit_pcg_solve(double lambda, int max_iter, double tol) {
         launch_dot2(n, r, r, r, z, partial_, n_partial_, sc, stream_);
         launch_pcg_implicit_close(sc, abs_tol, stream_);               // :634-641, :652-654, else beta and rz_old
         launch_pcg_update_p_sc(n, sc, z, p, stream_);
-        HIP_TRY(hipMemcpyAsync(pcg_host_ + 8 * slot, sc, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipEventRecord(pcg_ev_[slot], stream_));
-        return kOk;
+        return check_hip(pcg_readback_.post(slot, sc, 6, stream_), "pcg_readback_.post");
     };
-    int it = 0;
-    if (max_iter > 0) { const int rc = enqueue_iteration(0); if (rc != kOk) return rc; }
-    for (; it < max_iter; ++it) {
-        if (it + 1 < max_iter) { const int rc = enqueue_iteration((it + 1) & 1); if (rc != kOk) return rc; }   // on speculation
-        HIP_TRY(hipEventSynchronize(pcg_ev_[it & 1]));
-        h = pcg_host_ + 8 * (it & 1);
-        if (fabs(h[2]) < 1e-20) break;           // :610-613 (x, r untouched)
-        if (h[5] != 0.0) { ++it; break; }        // the device's verdict: |r| < tol (:634-641) or rz_old ~ 0 (:652-654)
-    }
+    const PcgLoopResult res = pcg_loop_one_behind(
+        max_iter, enqueue_iteration, [&](int slot) -> int { return check_hip(pcg_readback_.wait(slot), "pcg_readback_.wait"); },
+        [&](int slot) {
+            const ImplicitPcgScalars& h = pcg_readback_.host(slot);
+            if (fabs(h.p_ap) < 1e-20) return PcgVerdict::kStopUncounted;               // :610-613 (x, r untouched)
+            return h.frozen != 0.0 ? PcgVerdict::kStopCounted : PcgVerdict::kGoOn;   // the device's verdict: |r| < tol (:634-641) or rz_old ~ 0 (:652-654)
+        });
+    if (res.status != kOk) return res.status;   // (a failed collective of the matvec included: its status, its text in err_)
     HIP_TRY(hipStreamSynchronize(stream_));      // (the speculative iteration, if any, has drained)
-    last_pcg_iters_ = it;
+    last_pcg_iters_ = res.iterations;
     stage_end(kStFactor);
     return kOk;
 }

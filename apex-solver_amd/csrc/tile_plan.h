@@ -6,7 +6,7 @@
 //             slot map, level groups, batched task lists -- is a host value (plan_lists.h: PlanStructure, PlanLists) that
 //             build() has made, allocates the tiles for and uploads; the plan keeps both and never writes them again
 //   factor() / solve()   level-scheduled tile Cholesky and triangular solves, replayed as hipGraphs
-//   pcg()     Jacobi-preconditioned CG on the unfactored tiles (solve_with_pcg, explicit_schur.rs:639-756)
+//   pcg()     Jacobi-preconditioned CG on the unfactored tiles: a class of its own, tile_pcg.h
 //   inverse() the selected inversion of the held factor (marginal covariances): a class of its own, tile_sinv.h
 //
 // Distributed factorisation (set_partition(rank, world) before build()): the elimination tree is cut below its top
@@ -31,6 +31,7 @@
 #include "device_buffer.h"
 #include "factor_schedule.h"
 #include "plan_lists.h"
+#include "tile_pcg.h"
 #include "tile_sinv.h"
 
 namespace apex {
@@ -49,15 +50,11 @@ struct TilePlanMemory {
     DeviceBuffer<FlowTask> flow_fwd_, flow_bwd_;   // dataflow triangular sweeps (single-GPU plans)
     DeviceBuffer<double> flow_part_;               // one 144-vector per off-diagonal tile
     DeviceBuffer<int> flow_flags_;                 // cnt[nt] | done[nt] | error word
-    PinnedBuffer<double> pcg_host_;                // two slots of PCG scalars (pcg(): read one iteration behind)
     PinnedBuffer<int> flow_err_host_;              // [0] the error word behind the last solve(), [1..2] debug_occupy_cus
     DeviceBuffer<FactorUnit> flow_units_;          // dataflow factorisation of the top groups: [phase 0 units | phase 1 units]
     DeviceBuffer<int> flow_ver_;                   // per tile slot: finished strips of in-launch writers
     DeviceBuffer<unsigned long long> flow_trace_;
-    DeviceBuffer<SymTile> sym_tiles_;
-    DeviceBuffer<int> sym_row_ptr_;
-    DeviceBuffer<SymEntry> sym_entries_;
-    DeviceBuffer<double> sym_part_, row_dot_, blk_part_, scal_;
+    DeviceBuffer<SymTile> sym_tiles_;              // the tiles non-zero before fill (scale_sym, TilePcg)
 };
 
 class TilePlan : private TilePlanMemory {
@@ -176,10 +173,10 @@ class TilePlan : private TilePlanMemory {
     // the distributed sweeps failed (the communicator's own message is with the caller)
     hipError_t solve(const double* rhs, double* x, double* work);
     // y = A x on the UNFACTORED tiles (deterministic two-pass symmetric product), no sync
-    void sym_matvec(const double* x, double* y);
+    void sym_matvec(const double* x, double* y) { pcg_.matvec(x, y); }
     // Jacobi-PCG on the UNFACTORED tiles; work: 6*n_pad doubles; syncs once per iteration
-    hipError_t pcg(const double* rhs, double* x, double* work, int max_iter, double tol, int* iters);
-    const double* pcg_scalars() const { return scal_; }   // device: {rz_old, p.Ap, r.r, r.z, frozen} as the last pcg() left them (tests)
+    hipError_t pcg(const double* rhs, double* x, double* work, int max_iter, double tol, int* iters) { tiles_written(); return pcg_.solve(rhs, x, work, max_iter, tol, iters); }
+    const double* pcg_scalars() const { return pcg_.scalars(); }   // device: ExplicitPcgScalars as the last pcg() left them (tests)
 
     // The tiles hold a valid factor L only between a successful single-rank factorisation + sweeps (the CALLER says so with
     // set_factor_valid(true) once it has read the pivot flags) and the next write of the tiles: zero_tiles, add_diag,
@@ -218,7 +215,6 @@ class TilePlan : private TilePlanMemory {
     // the handles behind the schedule's stream and event ids (issue)
     hipStream_t stream_of(uintptr_t s) const { return s == kMain ? stream_ : s == kSide ? side_ : s == kSide2 ? side2_ : so_; }
     std::vector<std::array<hipEvent_t, kLevelEvents>> ev_;
-    hipEvent_t pcg_ev_[2] = {nullptr, nullptr};
     int* flow_err_host_dev_ = nullptr;                     // the device address of flow_err_host_ (mapped pinned memory)
     int n_sweep_timeouts_ = 0;
     int poison_ = 0;
@@ -237,6 +233,7 @@ class TilePlan : private TilePlanMemory {
     bool factor_valid_{false};
     uint64_t factor_epoch_ = 0;
     SelectedInverse inverse_;
+    TilePcg pcg_;
     bool use_graphs_ = true;
 };
 

@@ -7,8 +7,6 @@
 
 #include <stdlib.h>
 
-#include <math.h>
-
 #include <algorithm>
 
 namespace apex {
@@ -19,11 +17,11 @@ void TilePlan::release() {
         graph_failed_[i] = false;
     }
     inverse_.release();
+    pcg_.release();
     tiles_written();
     static_cast<TilePlanMemory&>(*this) = TilePlanMemory();   // frees every device and pinned block of the plan
     lists_ = PlanLists(); sw_.flow_on = true; flow_gave_up_ = false;
     flow_err_host_dev_ = nullptr;
-    for (hipEvent_t& ev : pcg_ev_) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
     if (occ_stream_) { (void)hipStreamSynchronize(occ_stream_); (void)hipStreamDestroy(occ_stream_); occ_stream_ = nullptr; }
     for (const auto& evs : ev_) for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
     ev_.clear();
@@ -76,10 +74,7 @@ std::string TilePlan::upload() {
     TP_TRY(flow_units_.upload(lists_.units));
     TP_TRY(flow_ver_.alloc_zero((size_t)structure_.n_slots));
     TP_TRY(sym_tiles_.upload(lists_.sym_tiles));
-    TP_TRY(sym_part_.alloc_zero((size_t)structure_.n_slots * 2 * kNB));
-    TP_TRY(row_dot_.alloc_zero((size_t)structure_.nt));
-    TP_TRY(blk_part_.alloc_zero(2 * (size_t)((n_pad() + 255) / 256)));
-    TP_TRY(scal_.alloc_zero(8));
+    TP_TRY(pcg_.setup(PcgPlanView{tiles_, diag_slot_, sym_tiles_, n_sym_tiles(), structure_.nt, n_pad(), stream_}, lists_, structure_.n_slots));
     TP_TRY(tri_fwd_.upload(lists_.fwd));
     TP_TRY(tri_bwd_.upload(lists_.bwd));
     TP_TRY(flow_fwd_.upload(lists_.flow_fwd));
@@ -96,10 +91,8 @@ std::string TilePlan::upload() {
     TP_TRY(potrf_tasks_.upload(lists_.potrf));
     TP_TRY(trsm_tasks_.upload(lists_.panel));
     TP_TRY(upd_tasks_.upload(lists_.upd));
-    TP_TRY(sym_row_ptr_.upload(lists_.sym_row_ptr));
     TP_TRY(cls_.upload(structure_.cls));
     TP_TRY(exch_.alloc_zero((size_t)n_pad()));
-    TP_TRY(sym_entries_.upload(lists_.sym_entries));
     // (a lowest-priority side stream was tried: no gain without graphs, +2.7 ms with them)
     // (and so was a CU-masked one that leaves 1 CU in 8 / 4 / 2 to the critical path: the same, either way)
     for (hipStream_t* s : {&side_, &so_, &side2_})
@@ -406,60 +399,6 @@ hipError_t TilePlan::solve(const double* rhs, double* x, double* work) {
     } else if (!run_graph(kGraphSweeps, rhs, x, work)) enqueue_solve(rhs, x, work);
     if (tri_flow_ && n_flow_fwd() > 0) (void)post_sweep_status(false);
     return hipGetLastError();
-}
-
-void TilePlan::sym_matvec(const double* x, double* y) {
-    launch_sym_tile_products(sym_tiles_, n_sym_tiles(), tiles_, x, sym_part_, stream_);
-    launch_sym_tile_gather(structure_.nt, sym_row_ptr_, sym_entries_, sym_part_, x, y, row_dot_, stream_);
-}
-
-// solve_with_pcg (explicit_schur.rs:639-756).  Per iteration: one pass over the non-zero tiles
-// (k_sym_tile_products + k_sym_tile_gather, which also yields p.Ap), two fused vector kernels that keep
-// alpha/beta on the device, and ONE host read-back of {p.Ap, r.r, r.z} for the reference's three
-// termination tests -- read ONE ITERATION BEHIND (round 5): iteration k + 1 is enqueued before the host waits for the
-// scalars of iteration k, so the device never idles through a host round trip (25 us of a 185-us iteration).  The tests are
-// also made on the device (k_pcg_close_iteration): the speculative iteration behind a met test changes nothing, and x, the
-// iteration count and every scalar are those of the loop that waited every time.
-hipError_t TilePlan::pcg(const double* rhs, double* x, double* work, int max_iter, double tol, int* iters) {
-    tiles_written();
-    const int n = (int)n_pad();
-    double *dg = work, *pre = work + n, *r = work + 2 * (size_t)n, *z = work + 3 * (size_t)n, *p = work + 4 * (size_t)n,
-           *ap = work + 5 * (size_t)n;
-    double* sc = scal_;  // [0] rz_old  [1] p.Ap  [2] r.r  [3] r.z  [4] frozen
-    hipError_t e;
-    if (!pcg_host_) {
-        if ((e = pcg_host_.alloc(16)) != hipSuccess) return e;
-        for (hipEvent_t& ev : pcg_ev_) if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
-    }
-    launch_tile_diag(tiles_, diag_slot_, structure_.nt, dg, stream_);
-    launch_pcg_init(n, dg, rhs, pre, x, r, z, p, stream_);
-    if ((e = hipMemsetAsync(sc, 0, 8 * sizeof(double), stream_)) != hipSuccess) return e;
-    launch_dot(n, r, z, sc, stream_);
-    launch_dot(n, r, r, sc + 2, stream_);
-    double* h = pcg_host_;
-    if ((e = hipMemcpyAsync(h, sc, 4 * sizeof(double), hipMemcpyDeviceToHost, stream_)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(stream_)) != hipSuccess) return e;
-    const double abs_tol = tol * std::max(sqrt(h[2]), 1.0);
-    auto enqueue_iteration = [&](int slot) -> hipError_t {
-        launch_sym_tile_products(sym_tiles_, n_sym_tiles(), tiles_, p, sym_part_, stream_);
-        launch_sym_tile_gather(structure_.nt, sym_row_ptr_, sym_entries_, sym_part_, p, ap, row_dot_, stream_);
-        launch_pcg_step1(n, structure_.nt, sc, row_dot_, p, ap, pre, x, r, blk_part_, sc + 1, stream_);
-        launch_pcg_step2(n, sc, blk_part_, pre, r, p, sc + 2, abs_tol, stream_);
-        const hipError_t ce = hipMemcpyAsync(pcg_host_ + 8 * slot, sc, 5 * sizeof(double), hipMemcpyDeviceToHost, stream_);
-        return ce != hipSuccess ? ce : hipEventRecord(pcg_ev_[slot], stream_);
-    };
-    int it = 0;
-    if (max_iter > 0 && (e = enqueue_iteration(0)) != hipSuccess) return e;
-    for (; it < max_iter; ++it) {
-        if (it + 1 < max_iter && (e = enqueue_iteration((it + 1) & 1)) != hipSuccess) return e;   // on speculation
-        if ((e = hipEventSynchronize(pcg_ev_[it & 1])) != hipSuccess) return e;
-        h = pcg_host_ + 8 * (it & 1);
-        // the device's verdict (h[4], k_pcg_close_iteration) decides -- the speculative iteration obeys the same word
-        if (fabs(h[1]) < 1e-30) break;                       // p.Ap (:703-705); x was left untouched
-        if (h[4] != 0.0) { ++it; break; }                    // |r| < tol (:726-728) or rz_old ~ 0 (:741-743)
-    }
-    *iters = it;
-    return hipStreamSynchronize(stream_);   // (the speculative iteration, if any, has drained: x is final)
 }
 
 SelectedInverse& TilePlan::inverse() {

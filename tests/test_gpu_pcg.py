@@ -1,6 +1,6 @@
-"""The device conjugate-gradient loop of the explicit Schur variants (TilePlan::pcg: k_pcg_init, k_sym_tile_products,
-k_sym_tile_gather, k_pcg_step1, k_pcg_step2, k_pcg_close_iteration, the host loop that reads the scalars one iteration behind
-and enqueues the next iteration on speculation) on systems the test chooses, through the hook apexgpu_debug_tiles_pcg
+"""The device conjugate-gradient loop of the explicit Schur variants (TilePcg::solve behind TilePlan::pcg, csrc/tile_pcg.hip; csrc/pcg_kernels.hip:
+k_pcg_init, k_sym_tile_products, k_sym_tile_gather, k_pcg_step1, k_pcg_step2, k_pcg_close_iteration; csrc/pcg_loop.h: the host
+loop that reads the scalars one iteration behind and enqueues the next iteration on speculation) on systems the test chooses, through the hook apexgpu_debug_tiles_pcg
 (capi.TileCholesky.pcg), against the long double restatement of the reference's loop (tests/pcg_ref.py):
   - every iterate x_k (the loop capped at k), by the referee rule e_gpu <= max(8 e_np, 8 n u max(1, kappa_J)) with e_np numpy
     fp64's distance from the same long double iterate, and the iteration count, exactly;

@@ -1,4 +1,4 @@
-"""Both device conjugate-gradient loops through the C ABI -- TilePlan::pcg behind SchurVariant.Iterative and
+"""Both device conjugate-gradient loops through the C ABI -- TilePcg::solve (csrc/tile_pcg.hip) behind SchurVariant.Iterative and
 Solver::implicit_pcg_solve behind SchurVariant.Implicit -- capped before convergence, at it and past it, against the oracle
 under the same cap (tests/test_gpu_pcg.py runs the explicit loop on crafted tiles; tests/test_pcg_ref_host.py pins the
 oracle's two loops to a plain long double restatement).
@@ -149,3 +149,61 @@ def test_noise_free_problem_at_its_ground_truth(mode, variant, scaled):
         assert np.isfinite(step).all() and np.isfinite(grad).all() and np.isfinite(trial)
         assert np.linalg.norm(plain) <= 1e-6 * x_norm
     s.close()
+
+
+def _two_islands(d, seed):
+    """The counts of d with another plan: the landmarks alternate between cameras 0..15 (one tile at d_c = 9) and the rest,
+    every landmark keeps its number of observations, drawn inside its island, so S is block diagonal -- two tile rows, no
+    off-diagonal tile -- and every list and work array of the plan and of its PCG has another size."""
+    import dataclasses
+
+    rng = np.random.default_rng(seed)
+    islands = (np.arange(0, 16), np.arange(16, d.n_cam))
+    cam = d.cam_idx.copy()
+    order = np.argsort(d.pt_idx, kind="stable")
+    pts, first = np.unique(d.pt_idx[order], return_index=True)
+    for l, a, b in zip(pts, first, list(first[1:]) + [len(order)]):
+        cam[order[a:b]] = rng.choice(islands[int(l) % 2], size=b - a, replace=False)
+    uv = pkg.synthetic.project_bal(d.truth_poses[cam], d.truth_intr[cam], d.truth_points[d.pt_idx]) + rng.normal(0, 0.7, (len(cam), 2))
+    return dataclasses.replace(d, cam_idx=cam.astype(d.cam_idx.dtype), obs_uv=np.ascontiguousarray(uv))
+
+
+def _both_variants(s, d, tiles):
+    """Parameters set, then one solve per PCG variant: (step bytes, pcg_iterations) each."""
+    s.set_parameters(d.poses, d.intr, d.points)
+    s.with_cg_params(5000, TOL)
+    out = []
+    for variant in (SchurVariant.Iterative, SchurVariant.Implicit):
+        step = s.with_variant(variant).solve_augmented_equation(LAM)
+        assert np.isfinite(step).all() and s.info()["pcg_iterations"] > 1
+        out.append((step.tobytes(), s.info()["pcg_iterations"]))
+    info = s.info()
+    assert info["tile_rows"] == 2 and info["tiles"] == tiles, info
+    return out
+
+
+def test_pcg_survives_a_rebuild():
+    """A handle that has run both PCG loops is given another structure (reinitialize_structure: the same library handle, the
+    plan released and built again over the PCG's lists, work arrays, pinned slots and events) and runs them again: every step
+    and every pcg_iterations equal, byte for byte, those of a fresh handle given only the second problem.  A library handle
+    keeps the counts it was created with, so the second problem cannot have fewer cameras: it has the first one's counts and a
+    smaller plan instead -- two tiles (block diagonal) after three (two tile rows with their off-diagonal tile, which the
+    gather needs).  Then back to the first structure on the same handle: the bytes of its first, fresh, run."""
+    dA = pkg.synthetic.make_problem(30, 1500, 3, 7, config_id=77)
+    dB = _two_islands(dA, 5)
+    assert (dB.n_cam, dB.n_pt, dB.n_obs) == (dA.n_cam, dA.n_pt, dA.n_obs)
+    problem = lambda d: Problem.bundle_adjustment(d, OptimizationType.SelfCalibration, 1.0)
+    f = GpuSchurComplementSolver(0).initialize_structure(problem(dB))
+    fresh = _both_variants(f, dB, 2)
+    f.close()
+    s = GpuSchurComplementSolver(0).initialize_structure(problem(dA))
+    first = _both_variants(s, dA, 3)
+    s.reinitialize_structure(problem(dB))
+    again = _both_variants(s, dB, 2)
+    s.reinitialize_structure(problem(dA))
+    back = _both_variants(s, dA, 3)
+    s.close()
+    print(f"PCGCASE abi rebuild: iterations (Iterative, Implicit) three tiles {[i for _, i in first]}, two tiles on the same handle "
+          f"{[i for _, i in again]} (fresh handle {[i for _, i in fresh]}), three tiles again {[i for _, i in back]}")
+    assert again == fresh
+    assert back == first
