@@ -96,7 +96,6 @@ class PoseGraphSolver : public TileBackend, public TrBackend {
     double* step_sums(int* n) override { *n = 3; return scal_ + 1; }
     StepAnswers answers_from_sums(const double* h) const override { return {sqrt(h[0]), sqrt(h[1]), 0.5 * h[2], h[3]}; }
     int assemble(double lambda);
-    int ensure_scale_buffer();
     int solve_damped(double lambda, double* step_out, double* grad_out);   // solve_augmented behind its checks; the fresh Dog-Leg solve
     int enqueue_dogleg_tail(bool fresh);   // everything of a Dog-Leg step behind the sweeps, up to the copy to dl_host_
     void drop_dogleg_cache() { have_dl_cache_ = false; }
@@ -108,8 +107,8 @@ class PoseGraphSolver : public TileBackend, public TrBackend {
     bool loss_set_ = false;   // set_loss has replaced huber_delta_ (until the next set_structure)
     PgLoss loss_;             // kLossNone unless loss_set_
     bool have_structure_ = false, have_params_ = false;
-    std::vector<int64_t> pose_col_;
     std::vector<int> vmap_;  // caller's vertex -> internal vertex
+    ColumnMap map_;          // ... and per tangent column: the caller's pose_col against the internal order (column_map.h)
     DeviceBuffer<double> poses_[2], posep_[2];
     DeviceBuffer<uint32_t> e_from_, e_to_;
     int n_prior_ = 0;
@@ -121,9 +120,7 @@ class PoseGraphSolver : public TileBackend, public TrBackend {
     DeviceBuffer<double> meas_;
     DeviceBuffer<uint8_t> fix_;
     DeviceBuffer<double> g_, rhs_, d_, work_, partial_, scal_;
-    DeviceBuffer<double> scale_;       // Jacobi scaling, internal order, [n_pad] with 1 on the padding
-    std::vector<double> scale_h_;
-    bool scaled_ = false;
+    JacobiScaling scale_;              // Jacobi scaling, internal order, [n_pad] with 1 on the padding; on: TileBackend::scaled_
     int n_partial_ = 256;
     // Dog-Leg state.  dls_: [0..5] the six sums of dogleg_combine.hpp (kept from the last fresh solve), [6..12] the combine's
     // answer, [13] |step|^2, [14] the trial point's sum of squares; dl_host_ is its pinned copy.

@@ -138,7 +138,6 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
     huber_delta_ = huber_delta;
     loss_set_ = false;
     loss_ = PgLoss{};
-    pose_col_.assign(pose_col, pose_col + n_v_);
     n_ = dof_ * n_v_;
     const int nt = (int)((n_ + kNB - 1) / kNB);
     n_pad_ = (int64_t)nt * kNB;
@@ -153,6 +152,8 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
     const std::vector<int> tperm = tile_order(nt, adjm, use_nd_, nd_leaf_);
     vmap_.resize(n_v_);
     for (int64_t v = 0; v < n_v_; ++v) vmap_[v] = (int)((int64_t)tperm[v / vpt_] * vpt_ + v % vpt_);
+    map_ = block_column_map(std::vector<int64_t>(pose_col, pose_col + n_v_), vmap_, dof_);
+    scale_.set_size(n_, n_pad_);
     std::vector<uint8_t> present((size_t)nt * nt, 0);
     for (int I = 0; I < nt; ++I) present[(size_t)I * nt + I] = 1;
     std::vector<uint32_t> ef(n_e_), et(n_e_);
@@ -174,8 +175,7 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
         else pose_normalise(meas7 + 7 * e, mp.data() + (size_t)stride_ * e);
     }
     std::vector<uint8_t> fx((size_t)dof_ * n_v_, 0);
-    if (fix6)
-        for (int64_t v = 0; v < n_v_; ++v) memcpy(fx.data() + dof_ * (size_t)vmap_[v], fix6 + (size_t)dof_ * v, dof_);
+    if (fix6) blocks_to_internal(vmap_, dof_, fix6, fx.data());
     if (manifold_ == kManifoldSE2) {   // the row-owned assembly walks each vertex's incident edges
         IncidentLists inc;
         if (!build_incident_lists(n_v_, n_e_, ef.data(), et.data(), &inc)) return fail(kInvalidInput, "incident-edge lists: out of range");
@@ -209,7 +209,7 @@ int PoseGraphSolver::set_params(const double* poses7) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
     HIP_TRY(hipSetDevice(device_));
     std::vector<double> hp(amb_ * (size_t)n_v_);
-    for (int64_t v = 0; v < n_v_; ++v) memcpy(hp.data() + amb_ * (size_t)vmap_[v], poses7 + (size_t)amb_ * v, amb_ * sizeof(double));
+    blocks_to_internal(vmap_, amb_, poses7, hp.data());
     if (manifold_ == kManifoldSE2)   // the variable is held as SE2 -> DVector gives it: theta in (-pi, pi] (se2.rs:55-63)
         for (int64_t v = 0; v < n_v_; ++v) hp[3 * (size_t)v + 2] = se2_wrap_angle(hp[3 * (size_t)v + 2]);
     HIP_TRY(hipMemcpyAsync(poses_[st_.cur], hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
@@ -226,7 +226,7 @@ int PoseGraphSolver::get_params(double* poses7) {
     std::vector<double> hp(amb_ * (size_t)n_v_);
     HIP_TRY(hipMemcpyAsync(hp.data(), poses_[st_.cur], hp.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    for (int64_t v = 0; v < n_v_; ++v) memcpy(poses7 + (size_t)amb_ * v, hp.data() + amb_ * (size_t)vmap_[v], amb_ * sizeof(double));
+    blocks_to_caller(vmap_, amb_, hp.data(), poses7);
     return kOk;
 }
 
@@ -252,7 +252,7 @@ int PoseGraphSolver::assemble(double lambda) {
     tp_.add_diag((int)n_, scaled_ ? 0.0 : lambda, 1.0);  // lambda on the real rows, identity on the padding rows
     launch_pg_assemble(manifold_, view(st_.cur), tp_.tilemap(), g_, stream_);
     if (scaled_) {  // Jacobi scaling: H := D H D, then the damping of the scaled system
-        tp_.scale_sym(scale_);
+        tp_.scale_sym(scale_.dev);
         tp_.add_diag((int)n_, lambda, 1.0);
     }
     timer_.end(kPgAssemble, stream_);
@@ -264,7 +264,7 @@ int PoseGraphSolver::rebuild_system(double lambda, double) {
     const int rc = assemble(lambda);
     if (rc != kOk) return rc;
     launch_pg_negate(n_pad_, g_, rhs_, stream_);
-    if (scaled_) launch_vec_mul(n_pad_, rhs_, scale_, rhs_, stream_);  // -D g
+    if (scaled_) launch_vec_mul(n_pad_, rhs_, scale_.dev, rhs_, stream_);  // -D g
     return kOk;
 }
 
@@ -305,7 +305,7 @@ int PoseGraphSolver::solve_damped(double lambda, double* step_out, double* grad_
 int PoseGraphSolver::enqueue_sweeps() {
     timer_.begin(kPgTriSolve, stream_);
     HIP_TRY(tp_.solve(rhs_, d_, work_));
-    if (scaled_) launch_vec_mul(n_pad_, d_, scale_, d_, stream_);  // apply_inverse_scaling: step = D y
+    if (scaled_) launch_vec_mul(n_pad_, d_, scale_.dev, d_, stream_);  // apply_inverse_scaling: step = D y
     timer_.end(kPgTriSolve, stream_);
     return kOk;
 }
@@ -319,28 +319,16 @@ int PoseGraphSolver::finish_step(double* step_out, double* grad_out) {
         return kOk;
     }
     if (eager_eval_) { const int rc = enqueue_eager_eval(); if (rc != kOk) return rc; }   // what the LM loop asks next rides on this solve's wait
-    if (step_out || grad_out) {
-        std::vector<double> h(n_);
-        for (int pass = 0; pass < 2; ++pass) {
-            double* out = pass == 0 ? step_out : grad_out;
-            if (!out) continue;
-            HIP_TRY(hipMemcpyAsync(h.data(), pass == 0 ? d_ : g_, n_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
-            HIP_TRY(hipStreamSynchronize(stream_));
-            if (scaled_)  // the caller's variables are the scaled ones: y = step / s, gradient = s g
-                for (int64_t i = 0; i < n_; ++i) h[i] = pass == 0 ? h[i] / scale_h_[i] : h[i] * scale_h_[i];
-            for (int64_t v = 0; v < n_v_; ++v)
-                for (int a = 0; a < dof_; ++a) out[pose_col_[v] + a] = h[dof_ * (size_t)vmap_[v] + a];
-        }
-    } else {
-        HIP_TRY(hipStreamSynchronize(stream_));
-    }
+    if (step_out) { const int rc = export_columns({{d_, &map_, &scale_}}, ExportAs::kStep, step_out); if (rc != kOk) return rc; }
+    if (grad_out) { const int rc = export_columns({{g_, &map_, &scale_}}, ExportAs::kGradient, grad_out); if (rc != kOk) return rc; }
+    if (!step_out && !grad_out) HIP_TRY(hipStreamSynchronize(stream_));
     if (eager_eval_) post_eager_answers();
     return kOk;
 }
 
 int PoseGraphSolver::enqueue_step_stats() {
     timer_.begin(kPgStats, stream_);
-    launch_step_stats(n_, g_, d_, last_lambda_, scaled_ ? scale_ : nullptr, partial_, n_partial_, scal_ + 1, stream_);
+    launch_step_stats(n_, g_, d_, last_lambda_, scaled_ ? scale_.dev.get() : nullptr, partial_, n_partial_, scal_ + 1, stream_);
     timer_.end(kPgStats, stream_);
     return kOk;
 }
@@ -365,14 +353,6 @@ int PoseGraphSolver::parameter_norm(double* out) {
 }
 
 // ---- Jacobi column scaling (process_jacobian_generic, optimizer/mod.rs:749-763) -------------------
-int PoseGraphSolver::ensure_scale_buffer() {
-    if (scale_) return kOk;
-    HIP_TRY(scale_.alloc((size_t)n_pad_));
-    std::vector<double> ones(n_pad_, 1.0);
-    HIP_TRY(hipMemcpy(scale_, ones.data(), n_pad_ * sizeof(double), hipMemcpyHostToDevice));
-    return kOk;
-}
-
 // compute_column_norms (linearizer/mod.rs:229-239): the squared column norms of the corrected Jacobian are the
 // diagonal of J^T J, which the edge kernel already assembles.
 int PoseGraphSolver::column_norms(double* norms_out) {
@@ -388,8 +368,7 @@ int PoseGraphSolver::column_norms(double* norms_out) {
     std::vector<double> h(n_);
     HIP_TRY(hipMemcpyAsync(h.data(), work_, n_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    for (int64_t v = 0; v < n_v_; ++v)
-        for (int a = 0; a < dof_; ++a) norms_out[pose_col_[v] + a] = sqrt(h[dof_ * (size_t)vmap_[v] + a]);
+    map_.scatter(h.data(), norms_out, 0.0, [](double n2, int64_t) { return sqrt(n2); });
     return kOk;
 }
 
@@ -399,13 +378,10 @@ int PoseGraphSolver::set_column_scaling(const double* scaling) {
     st_.invalidate_step();
     drop_dogleg_cache();
     if (!scaling) { scaled_ = false; return kOk; }
-    int rc = ensure_scale_buffer();
-    if (rc != kOk) return rc;
-    scale_h_.assign(n_, 1.0);
-    for (int64_t v = 0; v < n_v_; ++v)
-        for (int a = 0; a < dof_; ++a) scale_h_[dof_ * (size_t)vmap_[v] + a] = scaling[pose_col_[v] + a];
-    for (double v : scale_h_) if (!(v > 0.0) || !std::isfinite(v)) return fail(kInvalidInput, "column scaling must be positive and finite");
-    HIP_TRY(hipMemcpyAsync(scale_, scale_h_.data(), n_ * sizeof(double), hipMemcpyHostToDevice, stream_));
+    HIP_TRY(scale_.ensure());
+    std::vector<double> staged;
+    if (!scale_.accepts(map_, scaling, &staged)) return fail(kInvalidInput, JacobiScaling::kRefused);
+    HIP_TRY(scale_.set_from_caller(std::move(staged), stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     scaled_ = true;
     return kOk;
@@ -415,15 +391,12 @@ int PoseGraphSolver::set_jacobi_scaling(bool on) {
     if (!on) { scaled_ = false; st_.invalidate_step(); drop_dogleg_cache(); return kOk; }
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    int rc = ensure_scale_buffer();
-    if (rc != kOk) return rc;
+    HIP_TRY(scale_.ensure());
     scaled_ = false;
-    rc = assemble(0.0);
+    const int rc = assemble(0.0);
     if (rc != kOk) return rc;
     tp_.diag(work_);
-    launch_scaling_from_norms_sq(n_, work_, scale_, stream_);  // the padding keeps its 1
-    scale_h_.resize(n_);
-    HIP_TRY(hipMemcpyAsync(scale_h_.data(), scale_, n_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(scale_.from_norms_sq(work_, n_, stream_));  // the padding keeps its 1
     HIP_TRY(hipStreamSynchronize(stream_));
     scaled_ = true; st_.invalidate_step();
     return kOk;
@@ -436,7 +409,7 @@ int PoseGraphSolver::lm_optimize(LmConfig* cfg, LmResult* res, LmIterRecord* his
 
 // ---- Gauss-Newton and Dog-Leg (tr_loop.h) -------------------------------------------------------------------------
 int PoseGraphSolver::enqueue_dogleg_tail(bool fresh) {
-    const double* sc = scaled_ ? scale_.get() : nullptr;
+    const double* sc = scaled_ ? scale_.dev.get() : nullptr;
     timer_.begin(kPgStats, stream_);
     if (fresh) {
         // g_s = D g, y = D^-1 d: g_s.g_s, y.y, g_s.y; then g_s.H_s g_s = |J D g_s|^2, g_s.H_s y = (J D g_s).(J D y), y.H_s y = |J D y|^2 with
@@ -504,11 +477,8 @@ int PoseGraphSolver::jv_gram(const double* a, const double* b, double out3[3]) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
     std::vector<double> ha(n_pad_, 0.0), hb(n_pad_, 0.0);
-    for (int64_t v = 0; v < n_v_; ++v)
-        for (int k = 0; k < dof_; ++k) {
-            ha[dof_ * (size_t)vmap_[v] + k] = a[pose_col_[v] + k];
-            hb[dof_ * (size_t)vmap_[v] + k] = b[pose_col_[v] + k];
-        }
+    map_.gather(a, ha.data());
+    map_.gather(b, hb.data());
     DeviceBuffer<double> da, db;
     HIP_TRY(hipStreamSynchronize(stream_));
     HIP_TRY(da.upload(ha));
@@ -549,35 +519,10 @@ int PoseGraphSolver::get_hessian(double lambda, double* H_out, double* g_out) {
     int rc = assemble(lambda);
     if (rc != kOk) return rc;
     st_.invalidate_step();
-    const size_t tile_elems = (size_t)kNB * kNB;
-    std::vector<int64_t> col(n_, -1);
-    for (int64_t v = 0; v < n_v_; ++v)
-        for (int a = 0; a < dof_; ++a) col[dof_ * (size_t)vmap_[v] + a] = pose_col_[v] + a;
-    if (g_out) {
-        std::vector<double> h(n_);
-        HIP_TRY(hipMemcpyAsync(h.data(), g_, n_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
-        for (int64_t i = 0; i < n_; ++i) g_out[col[i]] = scaled_ ? h[i] * scale_h_[i] : h[i];
-    }
+    if (g_out) { rc = export_columns({{g_, &map_, &scale_}}, ExportAs::kGradient, g_out); if (rc != kOk) return rc; }
     if (H_out) {
         memset(H_out, 0, (size_t)n_ * (size_t)n_ * sizeof(double));
-        std::vector<double> t(tile_elems);
-        const int nt = tp_.nt();
-        for (int I = 0; I < nt; ++I)
-            for (int J = 0; J <= I; ++J) {
-                const int s = tp_.slot(I, J);
-                if (s < 0 || s >= tp_.n_touched_slots()) continue;
-                HIP_TRY(hipMemcpyAsync(t.data(), tp_.tiles() + (size_t)s * tile_elems, tile_elems * sizeof(double), hipMemcpyDeviceToHost, stream_));
-                HIP_TRY(hipStreamSynchronize(stream_));
-                for (int r = 0; r < kNB; ++r)
-                    for (int c = 0; c < kNB; ++c) {
-                        const int64_t gi = (int64_t)I * kNB + r, gj = (int64_t)J * kNB + c;
-                        if (gi >= n_ || gj >= n_ || gj > gi) continue;
-                        const double val = t[(size_t)r * kNB + c];
-                        H_out[col[gi] * n_ + col[gj]] = val;
-                        H_out[col[gj] * n_ + col[gi]] = val;
-                    }
-            }
+        return export_tiles_dense(map_, n_, tp_.n_touched_slots(), H_out);
     }
     return kOk;
 }
@@ -586,10 +531,8 @@ int PoseGraphSolver::covariance(double* out) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
     if (!out) return fail(kInvalidInput, "cov_out is NULL");
     HIP_TRY(hipSetDevice(device_));
-    std::vector<int64_t> pos(n_v_);
-    for (int64_t v = 0; v < n_v_; ++v) pos[v] = dof_ * (int64_t)vmap_[v];
     std::string err;
-    const int rc = tp_.inverse().blocks(pos.data(), n_v_, dof_, out, &err);
+    const int rc = tp_.inverse().blocks(map_.pos.data(), n_v_, dof_, out, &err);
     if (rc == 1) return fail(kInvalidState, "covariance: " + err);
     if (rc != 0) return fail(kDeviceError, "covariance: " + err);
     return kOk;

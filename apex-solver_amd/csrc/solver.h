@@ -178,8 +178,7 @@ class Solver : public TileBackend {
     int assemble_implicit(double lambda);
     int implicit_pcg_solve(double lambda, int max_iter, double tol);
     int implicit_matvec(const double* x, double lam_local, double* y, bool reduce);
-    int ensure_scale_buffers();
-    int column_norms_sq_device();   // -> n2 in cam_scale_ / pt_scale_ (camera part all-reduced over the shards)
+    int column_norms_sq_device();   // -> n2 in cam_scale_.dev / pt_scale_.dev (camera part all-reduced over the shards)
     int factor_with_ladder(double lambda);
     int ladder(double lambda);
     int pcg_solve();
@@ -196,6 +195,7 @@ class Solver : public TileBackend {
     int adopt_host_structure(Setup& su);
     void uploader_body(Setup& su);
     int upload_observation_lists(Setup& su, std::string* err);
+    void build_column_maps(const Setup& su);
     int upload_fixed_masks(const Setup& su, std::string* err);
     int alloc_work_arrays(std::string* err);
     int upload_pair_lists(Setup& su, const PairDeviceTables& dtab, bool recs_on_device);
@@ -229,7 +229,6 @@ class Solver : public TileBackend {
     int adopt_comm(std::unique_ptr<Communicator> c, const std::string& err);
 
     // host copies
-    std::vector<int64_t> intr_col_, pose_col_, pt_col_;
     std::vector<int> o_orig_h_;
     std::thread free_thread_;   // unmaps the set-up's host lists off the caller's path
 
@@ -298,12 +297,17 @@ class Solver : public TileBackend {
     bool tree_shard_ = false;   // what set_structure arrived at
     int dist_selftest_ = 0;
     std::vector<int> lmap_;     // external landmark -> internal landmark (identity unless tree sharded)
+    // The caller's global columns against the internal order (column_map.h), built by set_structure: the camera side (n_c_ entries;
+    // six-column cameras leave their intrinsic columns untouched) and the landmarks (3 n_pt).  Every export scatters ALL 3 n_pt
+    // landmark entries, a sharded rank's too.  Invariant: the entries of dl_ / g_l_ / hinv_ (and lmu_) of landmarks this rank does
+    // not own, outside [lm_lo_, lm_hi_), are zero -- alloc_work_arrays zeroed them and nothing else writes them: the landmark-major
+    // kernels run over the rank's own workgroups only and there is no collective over these buffers.  Whatever writes them whole
+    // (an in-place all-gather, a debug import) breaks what export_step, step_stats and retract read.
+    ColumnMap cam_map_, pt_map_;
     DeviceBuffer<uint8_t> lam_mask_;  // tree sharding: cameras whose diagonal block gets lambda on this rank
     DeviceBuffer<double> pcg_buf_;                 // 7 vectors of n_c_pad
     DeviceBuffer<double> lmu_, sd_, minv_;  // matrix-free variant: {pt, u_l} records, diag blocks of S, their inverses
-    DeviceBuffer<double> cam_scale_, pt_scale_;   // Jacobi scaling, internal order ([n_c_pad] with 1 on the padding, [3 n_pt])
-    std::vector<double> cam_scale_h_, pt_scale_h_;
-    bool scaled_ = false;
+    JacobiScaling cam_scale_, pt_scale_;   // Jacobi scaling, internal order ([n_c_pad] with 1 on the padding, [3 n_pt]); on: TileBackend::scaled_
     int n_partial_ = 1024;
 
     bool use_graphs_ = true;

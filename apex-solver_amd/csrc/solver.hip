@@ -83,8 +83,8 @@ BAView Solver::view(int which) const {
     v.huber_delta = !loss_set_ ? huber_delta_ : (loss_.kind == kLossHuber ? loss_.p0 : -1.0);
     v.mask_code = mode_mask(mode_);
     v.co_pt = co_pt_; v.co_uv = reinterpret_cast<const double2*>(co_uv_.get()); v.co_rank = co_rank_;
-    v.cam_scale = scaled_ ? cam_scale_ : nullptr;
-    v.pt_scale = scaled_ ? pt_scale_ : nullptr;
+    v.cam_scale = scaled_ ? cam_scale_.dev.get() : nullptr;
+    v.pt_scale = scaled_ ? pt_scale_.dev.get() : nullptr;
     v.lam_mask = tree_shard_ ? lam_mask_ : nullptr;
     v.o_slot = o_slot_; v.wg_cam_n = wg_cam_n_; v.wg_cam_list = wg_cam_list_;
     if (world_ > 1 && lm_hi_ > lm_lo_) {   // the rank's own landmark range, in whole workgroups of kLmWg
@@ -164,6 +164,7 @@ struct Solver::Setup {
     // the caller's arguments: set before any thread starts, read-only afterwards
     const uint32_t *cam_idx = nullptr, *pt_idx = nullptr;
     const double* obs_uv = nullptr;
+    const int64_t *intr_col = nullptr, *pose_col = nullptr, *pt_col = nullptr;
     const uint8_t *fix_pose = nullptr, *fix_intr = nullptr, *fix_pt = nullptr;
     bool raw_uv_wanted = false;   // single rank: the device thread copies the measurements as they are
     // calling thread, before the planner and the uploader start; schur_form alone is rewritten later (after the planner is
@@ -177,7 +178,8 @@ struct Solver::Setup {
     std::string plan_err;
     double plan_seconds = 0.0;
     // uploader, which keeps its own error text (err_ belongs to the calling thread): read after uploader.join().  The
-    // calling thread then adds the pair lists' copy time to up_seconds
+    // calling thread then adds the pair lists' copy time to up_seconds.  (The uploader also writes the solver's two column
+    // maps, from the caller's column lists above and cmap_ / lmap_: nothing reads them before set_structure has returned)
     std::string up_err;
     int up_rc = kOk;
     double up_seconds = 0.0;
@@ -315,6 +317,8 @@ int Solver::adopt_host_structure(Setup& su) {
     cmap_ = hs.cmap; cinv_ = hs.cinv; lmap_ = hs.lmap;
     lm_lo_ = hs.lm_lo; lm_hi_ = hs.lm_hi; tree_shard_ = hs.tree_shard; pad_rank_ = hs.pad_rank;
     n_hubs_ = hs.n_hubs; n_border_tiles_ = hs.n_border_tiles;
+    cam_scale_.set_size(n_c_, n_c_pad_);
+    pt_scale_.set_size(3 * n_pt_, 3 * n_pt_);
     o_orig_h_.assign(hs.o_orig.begin(), hs.o_orig.end());
     n_pairs_ = hs.n_pairs; n_present_ = hs.n_present;
     lam_mask_.reset();
@@ -329,6 +333,7 @@ void Solver::uploader_body(Setup& su) {   // (nothing may escape a thread: an al
     try {
         const auto t0 = std::chrono::steady_clock::now();
         int rc = upload_observation_lists(su, &su.up_err);
+        build_column_maps(su);   // (host only; on this thread because it has the slack: 3 n_pt columns)
         if (rc == kOk) rc = upload_fixed_masks(su, &su.up_err);
         if (rc == kOk) rc = alloc_work_arrays(&su.up_err);
         if (rc == kOk) su.up_seconds = seconds_since(t0);
@@ -384,14 +389,18 @@ int Solver::upload_observation_lists(Setup& su, std::string* err) {
     return kOk;
 }
 
+// The caller's columns against the internal order (column_map.h): cmap_ and lmap_ are known, every export from here on goes
+// through these two
+void Solver::build_column_maps(const Setup& su) {
+    cam_map_ = camera_column_map(std::vector<int64_t>(su.pose_col, su.pose_col + n_cam_), std::vector<int64_t>(su.intr_col, su.intr_col + n_cam_), cmap_, dc_);
+    pt_map_ = block_column_map(std::vector<int64_t>(su.pt_col, su.pt_col + n_pt_), lmap_, 3);
+}
+
 int Solver::upload_fixed_masks(const Setup& su, std::string* err) {
     std::vector<uint8_t> fp(6 * n_cam_, 0), fi(3 * n_cam_, 0), fl(3 * n_pt_, 0);
-    for (int64_t c = 0; c < n_cam_; ++c) {
-        if (su.fix_pose) memcpy(fp.data() + 6 * (size_t)cmap_[c], su.fix_pose + 6 * c, 6);
-        if (su.fix_intr) memcpy(fi.data() + 3 * (size_t)cmap_[c], su.fix_intr + 3 * c, 3);
-    }
-    if (su.fix_pt)
-        for (int64_t l = 0; l < n_pt_; ++l) memcpy(fl.data() + 3 * (size_t)lmap_[l], su.fix_pt + 3 * l, 3);
+    if (su.fix_pose) blocks_to_internal(cmap_, 6, su.fix_pose, fp.data());
+    if (su.fix_intr) blocks_to_internal(cmap_, 3, su.fix_intr, fi.data());
+    if (su.fix_pt) blocks_to_internal(lmap_, 3, su.fix_pt, fl.data());
     HIP_TRY(fix_pose_.upload(fp), err);
     HIP_TRY(fix_intr_.upload(fi), err);
     HIP_TRY(fix_pt_.upload(fl), err);
@@ -478,6 +487,7 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     lc_release();   // (the landmark covariance lists belong to the old structure)
     Setup su;   // (its destructor releases and joins whatever thread is still out, on every return below)
     su.cam_idx = cam_idx; su.pt_idx = pt_idx; su.obs_uv = obs_uv;
+    su.intr_col = intr_col; su.pose_col = pose_col; su.pt_col = pt_col;
     su.fix_pose = fix_pose; su.fix_intr = fix_intr; su.fix_pt = fix_pt;
     su.raw_uv_wanted = world_ == 1;
     su.device_thread = std::thread(&Solver::device_thread_body, this, std::ref(su));
@@ -486,9 +496,6 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     huber_delta_ = huber_delta;
     loss_set_ = false;
     loss_ = PgLoss{};
-    intr_col_.assign(intr_col, intr_col + n_cam_);
-    pose_col_.assign(pose_col, pose_col + n_cam_);
-    pt_col_.assign(pt_col, pt_col + n_pt_);
     // (the caller's factor list is NOT kept: get_hessian_csc, the one reader, rebuilds it from the device's observation
     // lists on demand -- 0.1 s of set-up on final-13682 for an export the LM loop never calls)
     su.tr.mark("validate the index lists");
@@ -568,17 +575,15 @@ int Solver::set_params(const double* poses, const double* intr, const double* po
     if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
     HIP_TRY(hipSetDevice(device_));
     std::vector<double> hp(7 * n_cam_), hi(3 * n_cam_);
-    for (int64_t c = 0; c < n_cam_; ++c) {
-        memcpy(hp.data() + 7 * (size_t)cmap_[c], poses + 7 * c, 7 * sizeof(double));
-        memcpy(hi.data() + 3 * (size_t)cmap_[c], intr + 3 * c, 3 * sizeof(double));
-    }
+    blocks_to_internal(cmap_, 7, poses, hp.data());
+    blocks_to_internal(cmap_, 3, intr, hi.data());
     HIP_TRY(hipMemcpyAsync(poses_[st_.cur], hp.data(), 7 * n_cam_ * sizeof(double), hipMemcpyHostToDevice, stream_));
     HIP_TRY(hipMemcpyAsync(intr_[st_.cur], hi.data(), 3 * n_cam_ * sizeof(double), hipMemcpyHostToDevice, stream_));
     std::vector<double> hpt;
     const double* src_pts = points;
     if (tree_shard_) {  // landmarks are renumbered so that every rank's set is one internal range
         hpt.resize(3 * n_pt_);
-        for (int64_t l = 0; l < n_pt_; ++l) memcpy(hpt.data() + 3 * (size_t)lmap_[l], points + 3 * l, 3 * sizeof(double));
+        blocks_to_internal(lmap_, 3, points, hpt.data());
         src_pts = hpt.data();
     }
     { const int rc = upload_staged(pts_[st_.cur], src_pts, 3 * (size_t)n_pt_ * sizeof(double)); if (rc != kOk) return rc; }
@@ -642,12 +647,9 @@ int Solver::get_params(double* poses, double* intr, double* points) {
     std::vector<double> hpt(tree_shard_ ? 3 * n_pt_ : 0);
     HIP_TRY(hipMemcpyAsync(tree_shard_ ? hpt.data() : points, pts_[st_.cur], 3 * n_pt_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    if (tree_shard_)
-        for (int64_t l = 0; l < n_pt_; ++l) memcpy(points + 3 * l, hpt.data() + 3 * (size_t)lmap_[l], 3 * sizeof(double));
-    for (int64_t c = 0; c < n_cam_; ++c) {
-        memcpy(poses + 7 * c, hp.data() + 7 * (size_t)cmap_[c], 7 * sizeof(double));
-        memcpy(intr + 3 * c, hi.data() + 3 * (size_t)cmap_[c], 3 * sizeof(double));
-    }
+    if (tree_shard_) blocks_to_caller(lmap_, 3, hpt.data(), points);
+    blocks_to_caller(cmap_, 7, hp.data(), poses);
+    blocks_to_caller(cmap_, 3, hi.data(), intr);
     return kOk;
 }
 
@@ -735,8 +737,8 @@ int Solver::assemble_local(double lambda, double diag_extra, bool for_factor) {
 int Solver::assemble_finish() {
     if (scaled_) {  // the reduced system in the scaled variables: S := D_c S D_c, g_red := D_c g_red
         stage_begin(kStAssembleCam);
-        tp_.scale_sym(cam_scale_);
-        launch_vec_mul(n_c_pad_, g_red_, cam_scale_, g_red_, stream_);
+        tp_.scale_sym(cam_scale_.dev);
+        launch_vec_mul(n_c_pad_, g_red_, cam_scale_.dev, g_red_, stream_);
         stage_end(kStAssembleCam);
     }
     return kOk;
@@ -847,8 +849,8 @@ int Solver::assemble_implicit(double lambda) {
     }
     stage_begin(kStAssembleCam);
     if (scaled_) {
-        launch_scale_diag_blocks(dc_, n_cam_, cam_scale_, sd_, stream_);
-        launch_vec_mul(n_c_pad_, g_red_, cam_scale_, g_red_, stream_);
+        launch_scale_diag_blocks(dc_, n_cam_, cam_scale_.dev, sd_, stream_);
+        launch_vec_mul(n_c_pad_, g_red_, cam_scale_.dev, g_red_, stream_);
     }
     launch_precond_blocks(dc_, n_cam_, sd_, minv_, stream_);
     stage_end(kStAssembleCam);
@@ -861,13 +863,13 @@ int Solver::implicit_matvec(const double* x, double lam_local, double* y, bool r
     const double* xin = x;
     if (scaled_) {
         double* t = pcg_buf_ + 4 * n_c_pad_;
-        launch_vec_mul(n_c_, x, cam_scale_, t, stream_);
+        launch_vec_mul(n_c_, x, cam_scale_.dev, t, stream_);
         xin = t;
     }
     launch_implicit_matvec(dc_, view(st_.cur), cam_ptr_, hinv_, lmu_, xin, lam_local, y, stream_, backsub_records(), general_loss());
     if (reduce && comm_ && world_ > 1)
         COMM_TRY(comm_->all_reduce_sum(y, (size_t)n_c_, stream_));
-    if (scaled_) launch_vec_mul(n_c_, y, cam_scale_, y, stream_);
+    if (scaled_) launch_vec_mul(n_c_, y, cam_scale_.dev, y, stream_);
     return check_hip(hipGetLastError(), "implicit_matvec");
 }
 
@@ -952,7 +954,7 @@ int Solver::solve_augmented(double lambda, int variant, double* step_out, double
 // the camera step is in dcam_: scaling back, back-substitution, the eager evaluation, the export and its wait
 int Solver::finish_step(double* step_out, double* grad_out) {
     stage_begin(kStBackSub);
-    if (scaled_) launch_vec_mul(n_c_, dcam_, cam_scale_, dcam_, stream_);  // apply_inverse_scaling: dc = D_c y
+    if (scaled_) launch_vec_mul(n_c_, dcam_, cam_scale_.dev, dcam_, stream_);  // apply_inverse_scaling: dc = D_c y
     // what the LM loop asks next (step statistics, trial cost) rides on this solve's wait (tile_backend.h, eager_eval_; single
     // rank); the trial POINTS are written by the back-substitution itself
     const bool eager = eager_eval_ && !(comm_ && world_ > 1);
@@ -978,29 +980,9 @@ void Solver::keep_factor() {
 
 // the last step / gradient in the reference's global column order (syncs)
 int Solver::export_step(double* step_out, double* grad_out) {
-    if (step_out || grad_out) {
-        std::vector<double> hc(n_c_), hl(3 * n_pt_);
-        for (int pass = 0; pass < 2; ++pass) {
-            double* out = pass == 0 ? step_out : grad_out;
-            if (!out) continue;
-            HIP_TRY(hipMemcpyAsync(hc.data(), pass == 0 ? dcam_ : g_c_, n_c_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
-            HIP_TRY(hipMemcpyAsync(hl.data(), pass == 0 ? dl_ : g_l_, 3 * n_pt_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
-            HIP_TRY(hipStreamSynchronize(stream_));
-            if (scaled_) {  // the caller's variables are the scaled ones: y = step / s, gradient = s g
-                for (int64_t i = 0; i < n_c_; ++i) hc[i] = pass == 0 ? hc[i] / cam_scale_h_[i] : hc[i] * cam_scale_h_[i];
-                for (int64_t i = 0; i < 3 * n_pt_; ++i) hl[i] = pass == 0 ? hl[i] / pt_scale_h_[i] : hl[i] * pt_scale_h_[i];
-            }
-            for (int64_t c = 0; c < n_cam_; ++c) {
-                const int64_t ci = cmap_[c];
-                for (int a = 0; a < 6; ++a) out[pose_col_[c] + a] = hc[ci * dc_ + a];
-                for (int a = 0; a < 3; ++a) out[intr_col_[c] + a] = (dc_ == 9) ? hc[ci * dc_ + 6 + a] : 0.0;
-            }
-            for (int64_t l = 0; l < n_pt_; ++l)
-                for (int a = 0; a < 3; ++a) out[pt_col_[l] + a] = hl[3 * (size_t)lmap_[l] + a];
-        }
-    } else {
-        HIP_TRY(hipStreamSynchronize(stream_));
-    }
+    if (step_out) { const int rc = export_columns({{dcam_, &cam_map_, &cam_scale_}, {dl_, &pt_map_, &pt_scale_}}, ExportAs::kStep, step_out); if (rc != kOk) return rc; }
+    if (grad_out) { const int rc = export_columns({{g_c_, &cam_map_, &cam_scale_}, {g_l_, &pt_map_, &pt_scale_}}, ExportAs::kGradient, grad_out); if (rc != kOk) return rc; }
+    if (!step_out && !grad_out) HIP_TRY(hipStreamSynchronize(stream_));
     return kOk;
 }
 
@@ -1051,7 +1033,7 @@ int Solver::dist_phase(int phase, double lambda) {
             return kOk;
         case 5:
             tp_.solve_phase(2, g_red_, dcam_, pcg_buf_);
-            if (scaled_) launch_vec_mul(n_c_, dcam_, cam_scale_, dcam_, stream_);
+            if (scaled_) launch_vec_mul(n_c_, dcam_, cam_scale_.dev, dcam_, stream_);
             launch_back_substitute(dc_, view(st_.cur), hinv_, g_l_, dcam_, dl_, stream_, backsub_records(), nullptr, nullptr, general_loss());
             HIP_TRY(hipStreamSynchronize(stream_));
             st_.step_computed();
@@ -1098,8 +1080,8 @@ int Solver::assemble_only(double lambda) {
 
 int Solver::enqueue_step_stats() {
     stage_begin(kStStats);
-    launch_step_stats(n_c_, g_c_, dcam_, last_lambda_, scaled_ ? cam_scale_ : nullptr, partial_, n_partial_, scal_, stream_);
-    launch_step_stats(3 * n_pt_, g_l_, dl_, last_lambda_, scaled_ ? pt_scale_ : nullptr, partial_, n_partial_, scal_ + 3, stream_);
+    launch_step_stats(n_c_, g_c_, dcam_, last_lambda_, scaled_ ? cam_scale_.dev.get() : nullptr, partial_, n_partial_, scal_, stream_);
+    launch_step_stats(3 * n_pt_, g_l_, dl_, last_lambda_, scaled_ ? pt_scale_.dev.get() : nullptr, partial_, n_partial_, scal_ + 3, stream_);
     if (comm_ && world_ > 1)  // landmark part is sharded, camera part replicated
         COMM_TRY(comm_->all_reduce_sum(scal_ + 3, 3, stream_));
     stage_end(kStStats);
@@ -1145,53 +1127,37 @@ int Solver::parameter_norm(double* out) {
 // ---------------------------------------------------------------------------------------------
 // Jacobi column scaling (process_jacobian_generic, optimizer/mod.rs:749-763)
 // ---------------------------------------------------------------------------------------------
-int Solver::ensure_scale_buffers() {
-    if (cam_scale_) return kOk;
-    HIP_TRY(cam_scale_.alloc((size_t)n_c_pad_));
-    HIP_TRY(pt_scale_.alloc((size_t)(3 * n_pt_)));
-    return kOk;
-}
-
-// squared column norms of the corrected Jacobian at the current parameters, left in cam_scale_ / pt_scale_
+// squared column norms of the corrected Jacobian at the current parameters, left in the two holders' device vectors
 int Solver::column_norms_sq_device() {
-    int rc = ensure_scale_buffers();
-    if (rc != kOk) return rc;
+    HIP_TRY(cam_scale_.ensure());
+    HIP_TRY(pt_scale_.ensure());
     const bool was = scaled_;
     scaled_ = false;
     const BAView v = view(st_.cur);
     scaled_ = was;
-    HIP_TRY(hipMemsetAsync(cam_scale_, 0, n_c_pad_ * sizeof(double), stream_));
-    HIP_TRY(hipMemsetAsync(pt_scale_, 0, std::max<int64_t>(3 * n_pt_, 1) * sizeof(double), stream_));
-    launch_column_norms_sq(dc_, v, cam_scale_, pt_scale_, stream_, general_loss());
+    HIP_TRY(hipMemsetAsync(cam_scale_.dev, 0, n_c_pad_ * sizeof(double), stream_));
+    HIP_TRY(hipMemsetAsync(pt_scale_.dev, 0, std::max<int64_t>(3 * n_pt_, 1) * sizeof(double), stream_));
+    launch_column_norms_sq(dc_, v, cam_scale_.dev, pt_scale_.dev, stream_, general_loss());
     if (comm_ && world_ > 1)  // every rank sees all cameras but only its own landmarks
-        COMM_TRY(comm_->all_reduce_sum(cam_scale_, (size_t)n_c_, stream_));
+        COMM_TRY(comm_->all_reduce_sum(cam_scale_.dev, (size_t)n_c_, stream_));
     return kOk;
 }
 
 int Solver::column_norms(double* norms_out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    const bool was = scaled_;
-    std::vector<double> keep_c, keep_p;
-    if (was) { keep_c = cam_scale_h_; keep_p = pt_scale_h_; }
     int rc = column_norms_sq_device();
     if (rc != kOk) return rc;
     std::vector<double> hc(n_c_), hl(3 * n_pt_);
-    HIP_TRY(hipMemcpyAsync(hc.data(), cam_scale_, n_c_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipMemcpyAsync(hl.data(), pt_scale_, 3 * n_pt_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(hc.data(), cam_scale_.dev, n_c_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(hl.data(), pt_scale_.dev, 3 * n_pt_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    for (int64_t c = 0; c < n_cam_; ++c) {
-        const int64_t ci = cmap_[c];
-        for (int a = 0; a < 6; ++a) norms_out[pose_col_[c] + a] = sqrt(hc[ci * dc_ + a]);
-        for (int a = 0; a < 3; ++a) norms_out[intr_col_[c] + a] = (dc_ == 9) ? sqrt(hc[ci * dc_ + 6 + a]) : 0.0;
-    }
-    for (int64_t l = 0; l < n_pt_; ++l)
-        for (int a = 0; a < 3; ++a) norms_out[pt_col_[l] + a] = sqrt(hl[3 * (size_t)lmap_[l] + a]);
-    if (was) {  // the buffers held the active scaling: put it back
-        std::vector<double> pad(n_c_pad_, 1.0);
-        std::copy(keep_c.begin(), keep_c.end(), pad.begin());
-        HIP_TRY(hipMemcpyAsync(cam_scale_, pad.data(), n_c_pad_ * sizeof(double), hipMemcpyHostToDevice, stream_));
-        HIP_TRY(hipMemcpyAsync(pt_scale_, keep_p.data(), 3 * n_pt_ * sizeof(double), hipMemcpyHostToDevice, stream_));
+    const auto root = [](double n2, int64_t) { return sqrt(n2); };
+    cam_map_.scatter(hc.data(), norms_out, 0.0, root);
+    pt_map_.scatter(hl.data(), norms_out, 0.0, root);
+    if (scaled_) {  // the device vectors held the active scaling: put it back
+        HIP_TRY(cam_scale_.reupload(stream_));
+        HIP_TRY(pt_scale_.reupload(stream_));
         HIP_TRY(hipStreamSynchronize(stream_));
     }
     return kOk;
@@ -1203,24 +1169,12 @@ int Solver::set_column_scaling(const double* scaling) {
     st_.invalidate_step();
     if (!scaling) { scaled_ = false; return kOk; }
     if (factor_scaled_) factor_lin_ = -1;   // (the factor's scale vectors are overwritten below)
-    int rc = ensure_scale_buffers();
-    if (rc != kOk) return rc;
-    cam_scale_h_.assign(n_c_, 1.0);
-    pt_scale_h_.assign(3 * n_pt_, 1.0);
-    for (int64_t c = 0; c < n_cam_; ++c) {
-        const int64_t ci = cmap_[c];
-        for (int a = 0; a < 6; ++a) cam_scale_h_[ci * dc_ + a] = scaling[pose_col_[c] + a];
-        if (dc_ == 9)
-            for (int a = 0; a < 3; ++a) cam_scale_h_[ci * dc_ + 6 + a] = scaling[intr_col_[c] + a];
-    }
-    for (int64_t l = 0; l < n_pt_; ++l)
-        for (int a = 0; a < 3; ++a) pt_scale_h_[3 * (size_t)lmap_[l] + a] = scaling[pt_col_[l] + a];
-    for (double v : cam_scale_h_) if (!(v > 0.0) || !std::isfinite(v)) return fail(kInvalidInput, "column scaling must be positive and finite");
-    for (double v : pt_scale_h_) if (!(v > 0.0) || !std::isfinite(v)) return fail(kInvalidInput, "column scaling must be positive and finite");
-    std::vector<double> pad(n_c_pad_, 1.0);
-    std::copy(cam_scale_h_.begin(), cam_scale_h_.end(), pad.begin());
-    HIP_TRY(hipMemcpyAsync(cam_scale_, pad.data(), n_c_pad_ * sizeof(double), hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipMemcpyAsync(pt_scale_, pt_scale_h_.data(), 3 * n_pt_ * sizeof(double), hipMemcpyHostToDevice, stream_));
+    HIP_TRY(cam_scale_.ensure());
+    HIP_TRY(pt_scale_.ensure());
+    std::vector<double> hc, hl;
+    if (!cam_scale_.accepts(cam_map_, scaling, &hc) || !pt_scale_.accepts(pt_map_, scaling, &hl)) return fail(kInvalidInput, JacobiScaling::kRefused);
+    HIP_TRY(cam_scale_.set_from_caller(std::move(hc), stream_));
+    HIP_TRY(pt_scale_.set_from_caller(std::move(hl), stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     scaled_ = true;
     return kOk;
@@ -1234,11 +1188,8 @@ int Solver::set_jacobi_scaling(bool on) {
     if (factor_scaled_) factor_lin_ = -1;   // (the factor's scale vectors are overwritten below)
     int rc = column_norms_sq_device();
     if (rc != kOk) return rc;
-    launch_scaling_from_norms_sq(n_c_pad_, cam_scale_, cam_scale_, stream_);  // padding: n2 = 0 -> 1
-    launch_scaling_from_norms_sq(3 * n_pt_, pt_scale_, pt_scale_, stream_);
-    cam_scale_h_.resize(n_c_); pt_scale_h_.resize(3 * n_pt_);
-    HIP_TRY(hipMemcpyAsync(cam_scale_h_.data(), cam_scale_, n_c_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipMemcpyAsync(pt_scale_h_.data(), pt_scale_, 3 * n_pt_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(cam_scale_.from_norms_sq(cam_scale_.dev, n_c_pad_, stream_));  // padding: n2 = 0 -> 1
+    HIP_TRY(pt_scale_.from_norms_sq(pt_scale_.dev, 3 * n_pt_, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     scaled_ = true; st_.invalidate_step();
     return kOk;
@@ -1290,42 +1241,16 @@ int Solver::get_schur(double* S_out, double* gred_out) {
     HIP_TRY(hipSetDevice(device_));
     int rc = assemble(last_lambda_, 0.0);
     if (rc != kOk) return rc;
-    const size_t tile_elems = (size_t)kNB * kNB;
     const int64_t nref = 9 * n_cam_;
-    auto ref_row = [&](int64_t i) -> int64_t {
-        const int64_t ci = i / dc_; const int a = (int)(i - ci * dc_);
-        const int64_t c = cinv_[ci];
-        return a < 6 ? pose_col_[c] + a : intr_col_[c] + (a - 6);
-    };
-    if (gred_out) {
-        std::vector<double> h(n_c_);
-        HIP_TRY(hipMemcpyAsync(h.data(), g_red_, n_c_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
+    if (gred_out) {   // (g_red as the solver sees it: of the scaled system when scaling is on)
         std::fill(gred_out, gred_out + nref, 0.0);
-        for (int64_t i = 0; i < n_c_; ++i) gred_out[ref_row(i)] = h[i];
+        rc = export_columns({{g_red_, &cam_map_, &cam_scale_}}, ExportAs::kPlain, gred_out);
+        if (rc != kOk) return rc;
     }
     if (S_out) {
         std::fill(S_out, S_out + nref * nref, 0.0);
-        if (dc_ == 6)  // intrinsic variables exist but no factor touches them: S_ii = lambda
-            for (int64_t c = 0; c < n_cam_; ++c)
-                for (int a = 0; a < 3; ++a) S_out[(intr_col_[c] + a) * nref + intr_col_[c] + a] = last_lambda_;
-        std::vector<double> t(tile_elems);
-        for (int I = 0; I < nt_; ++I)
-            for (int J = 0; J <= I; ++J) {
-                const int s = tp_.slot(I, J);
-                if (s < 0) continue;
-                HIP_TRY(hipMemcpyAsync(t.data(), tp_.tiles() + (size_t)s * tile_elems, tile_elems * sizeof(double), hipMemcpyDeviceToHost, stream_));
-                HIP_TRY(hipStreamSynchronize(stream_));
-                for (int r = 0; r < kNB; ++r)
-                    for (int c = 0; c < kNB; ++c) {
-                        const int64_t gi = (int64_t)I * kNB + r, gj = (int64_t)J * kNB + c;
-                        if (gi >= n_c_ || gj >= n_c_ || gj > gi) continue;
-                        const double val = t[(size_t)r * kNB + c];
-                        const int64_t ri = ref_row(gi), rj = ref_row(gj);
-                        S_out[ri * nref + rj] = val;
-                        S_out[rj * nref + ri] = val;
-                    }
-            }
+        for (int64_t u : cam_map_.untouched) S_out[u * nref + u] = last_lambda_;   // intrinsic variables exist but no factor touches them: S_ii = lambda
+        return export_tiles_dense(cam_map_, nref, tp_.n_slots(), S_out);
     }
     return kOk;
 }
@@ -1339,13 +1264,8 @@ int Solver::schur_matvec(double lambda, const double* x_in, double* y_explicit, 
     HIP_TRY(hipSetDevice(device_));
     st_.invalidate_step();
     const int64_t nref = 9 * n_cam_;
-    auto ref_row = [&](int64_t i) -> int64_t {
-        const int64_t ci = i / dc_; const int a = (int)(i - ci * dc_);
-        const int64_t c = cinv_[ci];
-        return a < 6 ? pose_col_[c] + a : intr_col_[c] + (a - 6);
-    };
     std::vector<double> h(n_c_pad_, 0.0);
-    for (int64_t i = 0; i < n_c_; ++i) h[i] = x_in[ref_row(i)];
+    cam_map_.gather(x_in, h.data());
     double *xd = pcg_buf_, *yd = pcg_buf_ + n_c_pad_;
     HIP_TRY(hipMemcpyAsync(xd, h.data(), n_c_pad_ * sizeof(double), hipMemcpyHostToDevice, stream_));
     for (int pass = 0; pass < 2; ++pass) {
@@ -1358,10 +1278,9 @@ int Solver::schur_matvec(double lambda, const double* x_in, double* y_explicit, 
         HIP_TRY(hipMemcpyAsync(h.data(), yd, n_c_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
         HIP_TRY(hipStreamSynchronize(stream_));
         std::fill(out, out + nref, 0.0);
-        for (int64_t i = 0; i < n_c_; ++i) out[ref_row(i)] = h[i];
-        if (dc_ == 6 && rank_ == 0)  // intrinsic variables exist but no factor touches them: S_ii = lambda
-            for (int64_t c = 0; c < n_cam_; ++c)
-                for (int a = 0; a < 3; ++a) out[intr_col_[c] + a] = lambda * x_in[intr_col_[c] + a];
+        cam_map_.scatter(h.data(), out, 0.0);
+        if (rank_ == 0)  // intrinsic variables exist but no factor touches them: S_ii = lambda
+            for (int64_t u : cam_map_.untouched) out[u] = lambda * x_in[u];
     }
     return kOk;
 }
@@ -1415,7 +1334,8 @@ int Solver::get_hessian_csc(int64_t* nnz_out, int64_t* colptr, int64_t* rowidx, 
     std::vector<double> jc((size_t)2 * dc_ * n_obs_), jl((size_t)6 * n_obs_);
     int rc = get_jacobian_blocks(jc.data(), jl.data());
     if (rc != kOk) return rc;
-    auto cam_col = [&](int64_t c, int a) -> int64_t { return a < 6 ? pose_col_[c] + a : intr_col_[c] + (a - 6); };
+    // column a of the caller's camera c: cc[cp[c] + a]; column b of its landmark l: pc[pp[l] + b]
+    const std::vector<int64_t>&cc = cam_map_.col, &cp = cam_map_.pos, &pc = pt_map_.col, &pp = pt_map_.pos;
     struct Trip { int64_t col, row; double v; };
     std::vector<Trip> t;
     t.reserve((size_t)nnz);
@@ -1430,7 +1350,7 @@ int Solver::get_hessian_csc(int64_t* nnz_out, int64_t* colptr, int64_t* rowidx, 
         for (int64_t c = 0; c < n_cam_; ++c)
             if (cam_seen[c])
                 for (int a = 0; a < dc_; ++a)
-                    for (int b = 0; b < dc_; ++b) t.push_back({cam_col(c, b), cam_col(c, a), hcc[(size_t)c * dc_ * dc_ + a * dc_ + b]});
+                    for (int b = 0; b < dc_; ++b) t.push_back({cc[cp[c] + b], cc[cp[c] + a], hcc[(size_t)c * dc_ * dc_ + a * dc_ + b]});
     }
     {   // landmark blocks
         std::vector<double> hll((size_t)n_pt_ * 9, 0.0);
@@ -1443,7 +1363,7 @@ int Solver::get_hessian_csc(int64_t* nnz_out, int64_t* colptr, int64_t* rowidx, 
         for (int64_t l = 0; l < n_pt_; ++l)
             if (pt_seen[l])
                 for (int a = 0; a < 3; ++a)
-                    for (int b = 0; b < 3; ++b) t.push_back({pt_col_[l] + b, pt_col_[l] + a, hll[(size_t)l * 9 + 3 * a + b]});
+                    for (int b = 0; b < 3; ++b) t.push_back({pc[pp[l] + b], pc[pp[l] + a], hll[(size_t)l * 9 + 3 * a + b]});
     }
     {   // couplings, duplicated (camera, landmark) factors merged
         std::vector<double> w((size_t)dc_ * 3);
@@ -1459,8 +1379,8 @@ int Solver::get_hessian_csc(int64_t* nnz_out, int64_t* colptr, int64_t* rowidx, 
             }
             for (int a = 0; a < dc_; ++a)
                 for (int b = 0; b < 3; ++b) {
-                    t.push_back({pt_col_[l] + b, cam_col(c, a), w[a * 3 + b]});
-                    t.push_back({cam_col(c, a), pt_col_[l] + b, w[a * 3 + b]});
+                    t.push_back({pc[pp[l] + b], cc[cp[c] + a], w[a * 3 + b]});
+                    t.push_back({cc[cp[c] + a], pc[pp[l] + b], w[a * 3 + b]});
                 }
         }
     }
@@ -1504,8 +1424,8 @@ int Solver::get_landmark_blocks(double* hinv_out, double* gl_out) {
         }
     if (tree_shard_) {  // back to the caller's landmark order
         std::vector<double> t;
-        if (hinv_out) { t.assign(hinv_out, hinv_out + 9 * n_pt_); for (int64_t l = 0; l < n_pt_; ++l) memcpy(hinv_out + 9 * l, t.data() + 9 * (size_t)lmap_[l], 9 * sizeof(double)); }
-        if (gl_out) { t.assign(gl_out, gl_out + 3 * n_pt_); for (int64_t l = 0; l < n_pt_; ++l) memcpy(gl_out + 3 * l, t.data() + 3 * (size_t)lmap_[l], 3 * sizeof(double)); }
+        if (hinv_out) { t.assign(hinv_out, hinv_out + 9 * n_pt_); blocks_to_caller(lmap_, 9, t.data(), hinv_out); }
+        if (gl_out) { t.assign(gl_out, gl_out + 3 * n_pt_); blocks_to_caller(lmap_, 3, t.data(), gl_out); }
     }
     return kOk;
 }
@@ -1519,11 +1439,9 @@ int Solver::camera_covariance(double* out) {
         return fail(kInvalidState, auto_fallback_ ? "covariance: the automatic variant selection chose the matrix-free PCG for this handle: there is no factor to invert"
                                                   : "covariance: this handle was built matrix-free only: there is no factor to invert");
     HIP_TRY(hipSetDevice(device_));
-    std::vector<int64_t> pos(n_cam_);
-    for (int64_t c = 0; c < n_cam_; ++c) pos[c] = (int64_t)cmap_[c] * dc_;
     std::vector<double> blk((size_t)n_cam_ * dc_ * dc_);
     std::string err;
-    const int rc = tp_.inverse().blocks(pos.data(), n_cam_, dc_, blk.data(), &err);
+    const int rc = tp_.inverse().blocks(cam_map_.pos.data(), n_cam_, dc_, blk.data(), &err);
     if (rc == 1) return fail(kInvalidState, "covariance: " + err + " (the Iterative and matrix-free variants have no factor)");
     if (rc != 0) return fail(kDeviceError, "covariance: " + err);
     for (int64_t c = 0; c < n_cam_; ++c) {
@@ -1589,8 +1507,8 @@ int Solver::landmark_covariance(double* out) {
     lc_recomputed_ = recomputed;
     lc_ms_ = 0.0;
     BAView v = view(factor_lin_);   // the cameras the factor was linearised at; the points come from the landmark records
-    v.cam_scale = factor_scaled_ ? cam_scale_ : nullptr;
-    v.pt_scale = factor_scaled_ ? pt_scale_ : nullptr;
+    v.cam_scale = factor_scaled_ ? cam_scale_.dev.get() : nullptr;
+    v.pt_scale = factor_scaled_ ? pt_scale_.dev.get() : nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
     const bool timed = tp_.inverse().timing();
     if (timed) {
@@ -1615,7 +1533,7 @@ int Solver::landmark_covariance(double* out) {
     }
     if (e != hipSuccess) return check_hip(e, "landmark covariance");
     if (kerr) return fail(kDeviceError, "landmark covariance: a covisible camera pair is not in the factor's tile pattern");
-    for (int64_t l = 0; l < n_pt_; ++l) memcpy(out + 9 * l, blk.data() + 9 * (size_t)lmap_[l], 9 * sizeof(double));
+    blocks_to_caller(lmap_, 9, blk.data(), out);
     return kOk;
 }
 

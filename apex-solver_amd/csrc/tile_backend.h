@@ -5,9 +5,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <string>
 
+#include "column_map.h"
 #include "device_buffer.h"
+#include "jacobi_scaling.h"
 #include "lm_loop.h"
 #include "stage_timer.h"
 #include "step_state.h"
@@ -72,6 +75,15 @@ class TileBackend : public virtual LmBackend {   // (virtual: a solver may also 
     int direct_solve(bool speculative, double lambda, double* step_out, double* grad_out);
     int factor_fresh(double lambda, double reg, int* failed);   // factor_now on the system rebuild_system(lambda, reg) has just built, flags waited for; a give-up is repaired
     int factor_again(double lambda, double reg, int* failed);   // after a dataflow factorisation that gave up
+    // Device vectors in internal order to the caller's columns of `out`, with ONE host wait for all segments: each is copied to the
+    // host, unscaled when Jacobi scaling is on -- the caller's variables are the scaled ones: a step is divided by s, a gradient
+    // multiplied by it, kPlain is left as it is -- and scattered by its map, 0 to the map's untouched columns.
+    enum class ExportAs { kPlain, kStep, kGradient };
+    struct ExportSegment { const double* dev; const ColumnMap* map; const JacobiScaling* scale; };
+    int export_columns(std::initializer_list<ExportSegment> segs, ExportAs as, double* out);
+    // Every lower tile whose slot is below slot_bound to the host (a wait per tile) and, by the map, into both triangles of the
+    // dense row-major matrix `out` of leading dimension ld.  The padding rows are not in the map and stay out.
+    int export_tiles_dense(const ColumnMap& map, int64_t ld, int64_t slot_bound, double* out);
 
     // What the protocol asks of a solver ("The direct solve's hooks, by name").
     virtual int rebuild_system(double lambda, double reg) = 0;            // the matrix (diagonal + reg) and right-hand side, ready to factorise
@@ -94,6 +106,7 @@ class TileBackend : public virtual LmBackend {   // (virtual: a solver may also 
     StepState st_;
     double last_lambda_ = 0.0;
     bool one_wait_ = true, eager_eval_ = true;
+    bool scaled_ = false;   // Jacobi column scaling is on: the solver's JacobiScaling holders are what the system is scaled by
     int n_factor_flow_timeouts_ = 0;
     bool use_nd_ = true;
     int nd_leaf_;

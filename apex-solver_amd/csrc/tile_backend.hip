@@ -1,6 +1,8 @@
 // tile_backend.hip -- see tile_backend.h
 #include "tile_backend.h"
 
+#include <vector>
+
 namespace apex {
 
 int TileBackend::check_hip(hipError_t e, const char* what, std::string* err) {
@@ -59,6 +61,47 @@ int TileBackend::direct_solve(bool speculative, double lambda, double* step_out,
         tp_.enable_tri_flow(false);
     }
     return rc;
+}
+
+// ---- exports in the caller's column order (column_map.h) ---------------------------------------------------------------------
+int TileBackend::export_columns(std::initializer_list<ExportSegment> segs, ExportAs as, double* out) {
+    std::vector<std::vector<double>> h;
+    for (const ExportSegment& sg : segs) {
+        h.emplace_back((size_t)sg.map->size());
+        HIP_TRY(hipMemcpyAsync(h.back().data(), sg.dev, h.back().size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    }
+    HIP_TRY(hipStreamSynchronize(stream_));
+    size_t k = 0;
+    for (const ExportSegment& sg : segs) {
+        const double* v = h[k++].data();
+        const double* s = (scaled_ && as != ExportAs::kPlain) ? sg.scale->host.data() : nullptr;
+        if (!s) sg.map->scatter(v, out, 0.0);
+        else if (as == ExportAs::kStep) sg.map->scatter(v, out, 0.0, [s](double x, int64_t i) { return x / s[i]; });
+        else sg.map->scatter(v, out, 0.0, [s](double x, int64_t i) { return x * s[i]; });
+    }
+    return kOk;
+}
+
+int TileBackend::export_tiles_dense(const ColumnMap& map, int64_t ld, int64_t slot_bound, double* out) {
+    const size_t tile_elems = (size_t)kNB * kNB;
+    const int64_t n = map.size();
+    std::vector<double> t(tile_elems);
+    for (int I = 0; I < tp_.nt(); ++I)
+        for (int J = 0; J <= I; ++J) {
+            const int s = tp_.slot(I, J);
+            if (s < 0 || s >= slot_bound) continue;
+            HIP_TRY(hipMemcpyAsync(t.data(), tp_.tiles() + (size_t)s * tile_elems, tile_elems * sizeof(double), hipMemcpyDeviceToHost, stream_));
+            HIP_TRY(hipStreamSynchronize(stream_));
+            for (int r = 0; r < kNB; ++r)
+                for (int c = 0; c < kNB; ++c) {
+                    const int64_t gi = (int64_t)I * kNB + r, gj = (int64_t)J * kNB + c;
+                    if (gi >= n || gj >= n || gj > gi) continue;
+                    const double val = t[(size_t)r * kNB + c];
+                    out[map.col[gi] * ld + map.col[gj]] = val;
+                    out[map.col[gj] * ld + map.col[gi]] = val;
+                }
+        }
+    return kOk;
 }
 
 // ---- the trial-step protocol (lm_loop.h) ---------------------------------------------------------------------------------
