@@ -49,6 +49,8 @@ SYMBOLS = (
     "apexgpu_pg_jv_gram", "apexgpu_pg_dogleg_step", "apexgpu_pg_gn_optimize", "apexgpu_pg_dogleg_optimize",
     # the robust loss family on pose graphs
     "apexgpu_pg_set_loss", "apexgpu_pg_get_loss", "apexgpu_loss_evaluate", "apexgpu_set_loss", "apexgpu_get_loss",
+    # edge information matrices on pose graphs
+    "apexgpu_pg_set_information", "apexgpu_pg_get_information", "apexgpu_g2o_problem_information",
 )
 MANIFOLD_SE3, MANIFOLD_SE2 = 0, 1
 # APEXGPU_LOSS_* of include/apexgpu.h, in value order
@@ -270,6 +272,9 @@ def load() -> C.CDLL:
     L.apexgpu_pg_manifold.argtypes = [vp, C.POINTER(C.c_int * 3)]
     L.apexgpu_g2o_raw_se2.argtypes = [vp] * 7
     L.apexgpu_g2o_problem_se2.argtypes = [vp] * 8
+    L.apexgpu_g2o_problem_information.argtypes = [vp, C.c_int, vp]
+    L.apexgpu_pg_set_information.argtypes = [vp, vp]
+    L.apexgpu_pg_get_information.argtypes = [vp, C.POINTER(C.c_int), vp]
     L.apexgpu_pose_graph_columns_se2.argtypes = [i64, vp, vp]
     for name in SYMBOLS:
         f = getattr(L, name)

@@ -891,6 +891,15 @@ int apexgpu_pg_get_loss(const apexgpu_pg_solver* h, int* kind, double out2[2]) {
     h->s->get_loss(kind, out2);
     return APEXGPU_OK;
 }
+int apexgpu_pg_set_information(apexgpu_pg_solver* h, const double* info) {
+    PG_OR_FAIL;
+    return guarded([&] { return h->s->set_information(info); });
+}
+int apexgpu_pg_get_information(apexgpu_pg_solver* h, int* present, double* info_out) {
+    PG_OR_FAIL;
+    if (!present) return APEXGPU_ERR_INVALID_INPUT;
+    return h->s->get_information(present, info_out);
+}
 int apexgpu_loss_evaluate(int kind, double p0, double p1, double s, double out6[6]) {
     apex::PgLoss l;
     if (!out6 || !apex::pg_loss_make(kind, p0, p1, &l)) return APEXGPU_ERR_INVALID_INPUT;

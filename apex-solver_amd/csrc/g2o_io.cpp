@@ -367,6 +367,16 @@ int apexgpu_g2o_problem_se2(const apexgpu_g2o* g, int64_t* sorted_ids, double* p
     return 0;
 }
 
+/* The file's edge information matrices in the edge order of apexgpu_g2o_problem / apexgpu_g2o_problem_se2 (the file's edge
+ * order): info_out [n_e][36] (manifold 0, SE3) | [n_e][9] (manifold 1, SE2), row-major, full and symmetric.  Host only. */
+int apexgpu_g2o_problem_information(const apexgpu_g2o* g, int manifold, double* info_out) {
+    if (!g) return g2o_fail(APEXGPU_G2O_ERR_IO, "null handle");
+    if (manifold != 0 && manifold != 1) return g2o_fail(APEXGPU_G2O_ERR_PARSE, "manifold must be 0 (SE3) or 1 (SE2)");
+    const std::vector<double>& src = manifold == 1 ? g->info2 : g->info;
+    if (info_out && !src.empty()) memcpy(info_out, src.data(), src.size() * sizeof(double));
+    return 0;
+}
+
 /* First global column of "x{id}" in the sorted-name order of src/optimizer/mod.rs:530-536
  * (names compare as strings: x0, x1, x10, x100, ..., x2, ...). */
 static int pose_graph_columns(int64_t n_v, const int64_t* ids, int64_t* pose_col, int dof) {

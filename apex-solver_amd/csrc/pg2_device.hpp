@@ -299,6 +299,97 @@ APEX_HD void pg2_assemble_row(uint32_t v, const double* __restrict__ posep, cons
     }
 }
 
+// ---- edge information matrices ------------------------------------------------------------------------
+// One SE2 edge with Omega = U^T U under the general corrector, corrected but NOT whitened:
+//     r^ = residual_scaling r,   J^ = sqrt(rho') (J - a r (Omega r)^T J),   s = r^T Omega r
+// so that the whitened block is r~ = U r^, J~ = U J^ and every product closes with Omega: J~_a^T J~_b = J^_a^T Omega J^_b,
+// J~_v^T r~ = J^_v^T Omega r^.  The hot kernels need Omega only.  false: rho' = 0, the edge contributes nothing; r, J0, J1 are zero.
+APEX_HD bool between2_weighted(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                               const PgLoss& loss, const double* __restrict__ W, double r[3], double J0[9], double J1[9]) {
+    between2_linearize(k0, k1, m, r, J0, J1);
+    double Wr[3];
+    info_mv<3>(W, r, Wr);
+    const PgCorrector c = pg_loss_corrector(loss, fmax(dotn<3>(r, Wr), 0.0));
+    const double sc = c.sqrt_rho1;
+    if (sc == 0.0) {
+        r[0] = r[1] = r[2] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { J0[i] = 0.0; J1[i] = 0.0; }
+        return false;
+    }
+    const double a = c.alpha_sq_norm;
+    if (a != 0.0) {
+        double w0[3], w1[3];   // a (Omega r)^T J
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            w0[j] = a * (Wr[0] * J0[j] + Wr[1] * J0[3 + j] + Wr[2] * J0[6 + j]);
+            w1[j] = a * (Wr[0] * J1[j] + Wr[1] * J1[3 + j] + Wr[2] * J1[6 + j]);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { J0[3 * i + j] -= r[i] * w0[j]; J1[3 * i + j] -= r[i] * w1[j]; }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { J0[i] *= sc; J1[i] *= sc; }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) r[i] *= c.residual_scaling;
+    return true;
+}
+
+// M = Omega J (3 x 3 row-major)
+APEX_HD void info_mul3(const double* __restrict__ W, const double* __restrict__ J, double* __restrict__ M) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) M[3 * i + j] = W[3 * i] * J[j] + W[3 * i + 1] * J[3 + j] + W[3 * i + 2] * J[6 + j];
+}
+
+// pg2_assemble_row with information: info holds the packed upper triangle of every edge's Omega (InfoPack<3>: six doubles, the
+// caller's edge order).  Row-owned like pg2_assemble_row: the same lists, the same order of summation, no atomics.  The block
+// of row v and column u is J^_v^T (Omega J^_u) -- Omega sits between the two Jacobians, so the block of (u, v) is its transpose
+// and not the same product with the roles swapped.
+template <typename AddOff>
+APEX_HD void pg2_assemble_row_info(uint32_t v, const double* __restrict__ posep, const double* __restrict__ meas,
+                                   const uint32_t* __restrict__ e_from, const uint32_t* __restrict__ e_to,
+                                   const int* __restrict__ inc_ptr, const uint32_t* __restrict__ inc_edge,
+                                   const double* __restrict__ info, const PgLoss& loss, double Hvv[9], double gv[3], AddOff add_off) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Hvv[i] = 0.0;
+    gv[0] = gv[1] = gv[2] = 0.0;
+    for (int k = inc_ptr[v]; k < inc_ptr[v + 1]; ++k) {
+        const uint32_t e = inc_edge[k], a = e_from[e], b = e_to[e];
+        double W[9], r[3], Wr[3], J0[9], J1[9];
+        info_unpack<3>(info + InfoPack<3>::kStride * (size_t)e, W);
+        if (!between2_weighted(posep + kPose2Stride * (size_t)a, posep + kPose2Stride * (size_t)b, meas + kPose2Stride * (size_t)e,
+                               loss, W, r, J0, J1)) continue;
+        info_mv<3>(W, r, Wr);
+        double M[9];
+        if (a == b) {   // self-loop: both Jacobians hit the same columns
+#pragma unroll
+            for (int i = 0; i < 9; ++i) J0[i] += J1[i];
+            info_mul3(W, J0, M);
+            jtj3_acc(J0, M, Hvv);
+            jtr3_acc(J0, Wr, gv);
+            continue;
+        }
+        const bool first = a == v;   // (selects, not pointers into the register arrays: no scratch)
+        const uint32_t u = first ? b : a;
+        double Jv[9], Ju[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { Jv[i] = first ? J0[i] : J1[i]; Ju[i] = first ? J1[i] : J0[i]; }
+        info_mul3(W, Jv, M);
+        jtj3_acc(Jv, M, Hvv);
+        jtr3_acc(Jv, Wr, gv);
+        if (u < v) {
+            double B[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            info_mul3(W, Ju, M);
+            jtj3_acc(Jv, M, B);
+            add_off(u, B);
+        }
+    }
+}
+
 // The SE2 side of the trait pg_device.hpp describes at Se3Manifold.
 struct Se2Manifold {
     static constexpr int kDof = 3;                 // tangent columns per vertex
@@ -330,6 +421,28 @@ struct Se2Manifold {
             u[i] = (J0[3 * i] * a0[0] + J0[3 * i + 1] * a0[1] + J0[3 * i + 2] * a0[2]) + (J1[3 * i] * a1[0] + J1[3 * i + 1] * a1[1] + J1[3 * i + 2] * a1[2]);
             w[i] = (J0[3 * i] * b0[0] + J0[3 * i + 1] * b0[1] + J0[3 * i + 2] * b0[2]) + (J1[3 * i] * b1[0] + J1[3 * i + 1] * b1[1] + J1[3 * i + 2] * b1[2]);
         }
+    }
+    // With Omega (LossWeighted): u = J^0 a0 + J^1 a1, w = J^0 b0 + J^1 b1 for the corrected, not whitened Jacobians of
+    // between2_weighted; the caller closes the products with Omega: (J~ a).(J~ b) = u^T Omega w.
+    static APEX_HD void edge_jv_info(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m, const PgLoss& loss,
+                                     const double* __restrict__ W, const double a0[3], const double a1[3], const double b0[3], const double b1[3],
+                                     double u[3], double w[3]) {
+        double r[3], J0[9], J1[9];
+        (void)between2_weighted(k0, k1, m, loss, W, r, J0, J1);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            u[i] = (J0[3 * i] * a0[0] + J0[3 * i + 1] * a0[1] + J0[3 * i + 2] * a0[2]) + (J1[3 * i] * a1[0] + J1[3 * i + 1] * a1[1] + J1[3 * i + 2] * a1[2]);
+            w[i] = (J0[3 * i] * b0[0] + J0[3 * i + 1] * b0[1] + J0[3 * i + 2] * b0[2]) + (J1[3 * i] * b1[0] + J1[3 * i + 1] * b1[1] + J1[3 * i + 2] * b1[2]);
+        }
+    }
+    // the literal whitened, corrected residual [3] and Jacobian [3][6] of one edge (info_export_block: factors Omega here)
+    static APEX_HD void export_edge_info(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                                         const PgLoss& loss, const double* __restrict__ W, double* __restrict__ r_out, double* __restrict__ j_out) {
+        double r[3], J0[9], J1[9], Jd[18];
+        between2_linearize(k0, k1, m, r, J0, J1);
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) { Jd[6 * i + j] = J0[3 * i + j]; Jd[6 * i + 3 + j] = J1[3 * i + j]; }
+        info_export_block<3>(W, loss, r, Jd, r_out, j_out);
     }
     // corrected residual [3] and Jacobian [3][6] = [dr/dk0 | dr/dk1] of one edge (either may be null); sqrt(rho') is
     // applied inside between2_corrected

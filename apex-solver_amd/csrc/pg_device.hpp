@@ -293,6 +293,144 @@ APEX_HD bool between_linearize_general(const double* __restrict__ k0, const doub
     return true;
 }
 
+// ---- edge information matrices ------------------------------------------------------------------------
+// Edge e may carry a symmetric positive-definite D x D matrix Omega = U^T U in the tangent order of the residual.  The block
+// is the reference's block whitened, r_w = U r, J_w = U J, and the loss acts on (r_w, J_w, s = r^T Omega r) through the same
+// corrector.  The third loss policy: the general corrector plus Omega.  Its instantiations are the only code that reads
+// PGView::info; no loss, L2 and Huber run through it too (as a PgLoss of that kind) when information is set.
+struct LossWeighted { using Param = PgLoss; static constexpr bool kGeneral = true; };
+
+// Omega travels packed: the upper triangle row-major, D (D + 1) / 2 doubles padded to an even count (16-byte loads)
+template <int D>
+struct InfoPack {
+    static constexpr int kPacked = D * (D + 1) / 2;
+    static constexpr int kStride = (kPacked + 1) & ~1;   // 22 | 6
+};
+template <int D>
+APEX_HD void info_unpack(const double* __restrict__ p, double* __restrict__ W) {   // -> full, row-major
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) { W[D * i + j] = p[k]; W[D * j + i] = p[k]; ++k; }
+}
+// y = Omega x
+template <int D>
+APEX_HD void info_mv(const double* __restrict__ W, const double* __restrict__ x, double* __restrict__ y) {
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        double acc = W[D * i] * x[0];
+#pragma unroll
+        for (int j = 1; j < D; ++j) acc += W[D * i + j] * x[j];
+        y[i] = acc;
+    }
+}
+template <int D>
+APEX_HD double dotn(const double* __restrict__ x, const double* __restrict__ y) {
+    double acc = x[0] * y[0];
+#pragma unroll
+    for (int i = 1; i < D; ++i) acc += x[i] * y[i];
+    return acc;
+}
+// s = r^T Omega r (never negative: a rounding residue below zero would send sqrt(s) of a loss to NaN)
+template <int D>
+APEX_HD double info_sqnorm(const double* __restrict__ W, const double* __restrict__ r) {
+    double Wr[D];
+    info_mv<D>(W, r, Wr);
+    return fmax(dotn<D>(r, Wr), 0.0);
+}
+// U upper-triangular with Omega = U^T U (the transpose of the Cholesky factor); Omega is positive definite (the host checks)
+template <int D>
+APEX_HD void info_chol_upper(const double* __restrict__ W, double* __restrict__ U) {
+    for (int i = 0; i < D * D; ++i) U[i] = 0.0;
+    for (int i = 0; i < D; ++i)
+        for (int j = i; j < D; ++j) {
+            double acc = W[D * i + j];
+            for (int k = 0; k < i; ++k) acc -= U[D * k + i] * U[D * k + j];
+            U[D * i + j] = i == j ? sqrt(acc) : acc / U[D * i + i];
+        }
+}
+// The literal whitened and corrected block of one edge, for the exports (not hot): r~ = residual_scaling U r,
+// J~ = sqrt(rho') U (J - a r (Omega r)^T J); r [D], J [D][2 D] uncorrected.  An edge with rho' = 0 is written as zeros.
+template <int D>
+APEX_HD void info_export_block(const double* __restrict__ W, const PgLoss& loss, const double* __restrict__ r, const double* __restrict__ J,
+                               double* __restrict__ r_out, double* __restrict__ j_out) {
+    double Wr[D], w[2 * D], U[D * D];
+    info_mv<D>(W, r, Wr);
+    const double s = fmax(dotn<D>(r, Wr), 0.0);
+    const PgCorrector c = pg_loss_corrector(loss, s);
+    if (c.sqrt_rho1 == 0.0) {
+        if (r_out) for (int i = 0; i < D; ++i) r_out[i] = 0.0;
+        if (j_out) for (int i = 0; i < 2 * D * D; ++i) j_out[i] = 0.0;
+        return;
+    }
+    info_chol_upper<D>(W, U);
+    if (r_out)
+        for (int i = 0; i < D; ++i) {
+            double acc = 0.0;
+            for (int k = i; k < D; ++k) acc += U[D * i + k] * r[k];
+            r_out[i] = c.residual_scaling * acc;
+        }
+    if (!j_out) return;
+    for (int j = 0; j < 2 * D; ++j) {
+        double acc = 0.0;
+        for (int k = 0; k < D; ++k) acc += Wr[k] * J[2 * D * k + j];
+        w[j] = c.alpha_sq_norm * acc;   // a (Omega r)^T J
+    }
+    for (int i = 0; i < D; ++i)
+        for (int j = 0; j < 2 * D; ++j) {
+            double acc = 0.0;
+            for (int k = i; k < D; ++k) acc += U[D * i + k] * (J[2 * D * k + j] - r[k] * w[j]);
+            j_out[2 * D * i + j] = c.sqrt_rho1 * acc;
+        }
+}
+
+// M = Omega J for J = [P T; 0 P]: dense 6 x 6, formed once per Jacobian and used by every block that has it on the right
+APEX_HD void info_mul_jac(const double* __restrict__ W, const Jac6& J, double* __restrict__ M) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            M[6 * i + j] = W[6 * i] * J.P[j] + W[6 * i + 1] * J.P[3 + j] + W[6 * i + 2] * J.P[6 + j];
+            M[6 * i + 3 + j] = (W[6 * i] * J.T[j] + W[6 * i + 1] * J.T[3 + j] + W[6 * i + 2] * J.T[6 + j]) +
+                               (W[6 * i + 3] * J.P[j] + W[6 * i + 4] * J.P[3 + j] + W[6 * i + 5] * J.P[6 + j]);
+        }
+}
+// G = A^T M for A = [P T; 0 P]: with M = Omega J_b this is G_ab = J_a^T Omega J_b.  Not symmetric in (a, b) unless Omega is
+// a multiple of I: the block of row vertex a and column vertex b is G_ab, the transposed one is G_ba.
+APEX_HD void jt_mul(const Jac6& A, const double* __restrict__ M, double* __restrict__ G) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            G[6 * i + j] = A.P[i] * M[j] + A.P[3 + i] * M[6 + j] + A.P[6 + i] * M[12 + j];
+            G[6 * (i + 3) + j] = (A.T[i] * M[j] + A.T[3 + i] * M[6 + j] + A.T[6 + i] * M[12 + j]) +
+                                 (A.P[i] * M[18 + j] + A.P[3 + i] * M[24 + j] + A.P[6 + i] * M[30 + j]);
+        }
+}
+
+// between_linearize_general with Omega: s = r^T Omega r and w_v = J_v^T (Omega r).  With those, EdgeNormal6 corrects
+// G_ab = J_a^T Omega J_b exactly as it corrects J_a^T J_b:
+//     J~_a^T J~_b = rho' (G_ab - a (2 - a s) w_a w_b^T),   J~_v^T r~ = sqrt(rho') residual_scaling (1 - a s) w_v,
+//     (J~ x).(J~ y) = rho' z_x^T Omega z_y with z_x = J x - a r (w . x)
+// so the hot kernels need Omega only, never U.
+APEX_HD bool between_linearize_weighted(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                                        const PgLoss& loss, const double* __restrict__ W, double r[6], Jac6& J0, Jac6& J1, EdgeNormal6& n) {
+    between_linearize(k0, k1, m, r, J0, J1);
+    double Wr[6];
+    info_mv<6>(W, r, Wr);
+    n.s = fmax(dotn<6>(r, Wr), 0.0);
+    n.c = pg_loss_corrector(loss, n.s);
+    if (n.c.sqrt_rho1 == 0.0) return false;
+    const double as = n.c.alpha_sq_norm * n.s;
+    n.rho1 = n.c.sqrt_rho1 * n.c.sqrt_rho1;
+    n.kap = n.c.alpha_sq_norm * (2.0 - as);
+    n.gsc = n.c.sqrt_rho1 * n.c.residual_scaling * (1.0 - as);
+    jtr(J0, Wr, n.w0);
+    jtr(J1, Wr, n.w1);
+    return true;
+}
+
 // PriorFactor on an SE3 variable (prior_factor.rs:96-108): r = to_vector(x) - data over the 7 stored doubles of the prepared
 // pose (SE3::from(DVector).to_vector(), unit quaternion), J = the first six columns of I7; returns sqrt(rho') of the
 // block's Huber loss
@@ -417,6 +555,56 @@ struct Se3Manifold {
                         o[12 * (i + 3) + 3 + j] = sc * (J[w].P[3 * i + j] - a * r[3 + i] * wh);
                     }
                 }
+    }
+    // With Omega (LossWeighted): u = sqrt(rho') z_a, w = sqrt(rho') z_b, z_x = J x - a r (w . x) -- corrected, not whitened; the
+    // caller closes the products with Omega: (J~ a).(J~ b) = u^T Omega w.
+    static APEX_HD void edge_jv_info(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m, const PgLoss& loss,
+                                     const double* __restrict__ W, const double a0[6], const double a1[6], const double b0[6], const double b1[6],
+                                     double u[6], double w[6]) {
+        double r[6];
+        Jac6 J0, J1;
+        EdgeNormal6 n;
+        if (!between_linearize_weighted(k0, k1, m, loss, W, r, J0, J1, n)) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) { u[i] = 0.0; w[i] = 0.0; }
+            return;
+        }
+        double wa = 0.0, wb = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) { wa += n.w0[i] * a0[i] + n.w1[i] * a1[i]; wb += n.w0[i] * b0[i] + n.w1[i] * b1[i]; }
+        const double sc = n.c.sqrt_rho1;
+        wa *= n.c.alpha_sq_norm; wb *= n.c.alpha_sq_norm;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            double ut = 0.0, ur = 0.0, wt = 0.0, wr = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double p0 = J0.P[3 * i + j], t0 = J0.T[3 * i + j], p1 = J1.P[3 * i + j], t1 = J1.T[3 * i + j];
+                ut += (p0 * a0[j] + t0 * a0[3 + j]) + (p1 * a1[j] + t1 * a1[3 + j]);
+                ur += p0 * a0[3 + j] + p1 * a1[3 + j];
+                wt += (p0 * b0[j] + t0 * b0[3 + j]) + (p1 * b1[j] + t1 * b1[3 + j]);
+                wr += p0 * b0[3 + j] + p1 * b1[3 + j];
+            }
+            u[i] = sc * (ut - r[i] * wa); u[3 + i] = sc * (ur - r[3 + i] * wa);
+            w[i] = sc * (wt - r[i] * wb); w[3 + i] = sc * (wr - r[3 + i] * wb);
+        }
+    }
+    // the literal whitened, corrected residual [6] and Jacobian [6][12] of one edge (info_export_block: factors Omega here)
+    static APEX_HD void export_edge_info(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                                         const PgLoss& loss, const double* __restrict__ W, double* __restrict__ r_out, double* __restrict__ j_out) {
+        double r[6], Jd[72];
+        Jac6 J[2];
+        between_linearize(k0, k1, m, r, J[0], J[1]);
+        for (int w = 0; w < 2; ++w)
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    double* o = Jd + 6 * w;
+                    o[12 * i + j] = J[w].P[3 * i + j];
+                    o[12 * i + 3 + j] = J[w].T[3 * i + j];
+                    o[12 * (i + 3) + j] = 0.0;
+                    o[12 * (i + 3) + 3 + j] = J[w].P[3 * i + j];
+                }
+        info_export_block<6>(W, loss, r, Jd, r_out, j_out);
     }
     // corrected residual [6] and Jacobian [6][12] = [dr/dk0 | dr/dk1] of one edge (either may be null); sqrt(rho') is
     // applied at the store

@@ -30,6 +30,12 @@ struct PGView {
     const int* inc_ptr = nullptr;         // [n_v + 1] incident-edge CSR of the row-owned assembly (pg2_lists.h)
     const uint32_t* inc_edge = nullptr;
     const int* prior_slot = nullptr;      // [n_prior] the caller's index of the block (export order)
+    // Edge information matrices (apexgpu_pg_set_information): [n_e][InfoPack<dof>::kStride] the packed upper
+    // triangle of every edge's Omega, the caller's edge order; null: none.  Non-null selects the LossWeighted instantiations,
+    // which read the loss from `loss` below whatever its kind (PoseGraphSolver::view puts no loss, L2 and Huber there as well).
+    // (Ahead of `loss`: the struct's tail keeps its layout against the kernel arguments behind it, and the instruction stream
+    // of the other instantiations differs from what it was in kernel-argument offsets only.)
+    const double* info = nullptr;
     // The loss of every BetweenFactor block when apexgpu_pg_set_loss gave one that huber_delta cannot express
     // (kind != kLossNone): the launchers below then run the general-loss instantiation of every per-edge kernel and
     // huber_delta is not read for the edges.  kLossNone: the instantiations that know huber_delta only -- the code and the
@@ -37,8 +43,8 @@ struct PGView {
     PgLoss loss;
 };
 
-// Every launcher below that linearises edges (assemble, cost, export, jv_gram) also picks the loss policy (LossLegacy |
-// LossGeneral, pg_device.hpp) from v.loss.kind.
+// Every launcher below that linearises edges (assemble, cost, export, jv_gram) also picks the loss policy (pg_device.hpp):
+// LossWeighted when v.info is set, else LossLegacy | LossGeneral from v.loss.kind.
 void launch_pg_prepare(int manifold, int64_t n, const double* poses, double* posep, hipStream_t s);
 // H (tiles, lower triangle) += J^T J, g += J^T r over the edges, then the prior blocks' J^T J (sc^2 on the diagonal entries
 // of the vertex) and J^T r; tiles and g zeroed by the caller.  Two launches, and two algorithms:

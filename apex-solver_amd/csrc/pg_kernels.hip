@@ -21,6 +21,8 @@
 //                                      assemblies of one state are bit-identical.  An edge is linearised by both of its
 //                                      endpoints (a few dozen flops) instead of scattering 24-byte segments atomically.
 //   k_pg2_priors    SE2  one lane per run of prior blocks on one vertex (the blocks arrive sorted by vertex)
+// Every kernel that linearises edges is instantiated per loss policy (pg_device.hpp): LossLegacy (huber_delta), LossGeneral
+// (PgLoss), LossWeighted (PgLoss and the edge information matrices of PGView::info).
 //
 // HBM-bound and tiny next to the factorisation: per SE3 edge 2 x 64 B poses + 64 B measurement in,
 // 3 x 288 B + 2 x 48 B of atomics out.
@@ -70,6 +72,24 @@ __device__ __forceinline__ double sumsq(const double r[N]) {
     return s;
 }
 
+// LossWeighted: the instantiation that reads v.info
+template <class LP>
+constexpr bool kWeighted = std::is_same<LP, LossWeighted>::value;
+
+// edge e's Omega, unpacked to full row-major D x D: InfoPack<D>::kStride doubles by 16-byte loads
+template <int D>
+__device__ __forceinline__ void load_info(const double* __restrict__ base, int64_t e, double W[D * D]) {
+    constexpr int S = InfoPack<D>::kStride;
+    double p[S];
+    const double2* q = reinterpret_cast<const double2*>(base + S * e);
+#pragma unroll
+    for (int a = 0; a < S / 2; ++a) {
+        const double2 t = q[a];
+        p[2 * a] = t.x; p[2 * a + 1] = t.y;
+    }
+    info_unpack<D>(p, W);
+}
+
 // One prior block: the corrected residual (M::kAmb rows); returns sqrt(rho')
 template <class M>
 __device__ __forceinline__ double prior_at(const PGView& v, int k, double r[M::kAmb]) {
@@ -99,6 +119,65 @@ __global__ __launch_bounds__(256) void k_pg_prepare(int64_t n, const double* __r
 }
 
 // ---- SE3 assembly: edge-major, fp64 atomics ------------------------------------------------------------------------
+__device__ __forceinline__ void atomic_add_lower6(double* blk, const double H[36]) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) unsafeAtomicAdd(blk + i * kNB + j, H[6 * i + j]);
+}
+__device__ __forceinline__ void atomic_add_full6(double* blk, const double H[36]) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) unsafeAtomicAdd(blk + i * kNB + j, H[6 * i + j]);
+}
+
+// The body of k_pg_edges<LossWeighted>: every block is G_ab = J_a^T Omega J_b under EdgeNormal6's correction.  Omega J_b is
+// formed once per Jacobian (M) and serves the diagonal block and the cross block that has J_b on the right; the cross block
+// of row vertex hi and column vertex lo is J_hi^T Omega J_lo -- G_ab is not symmetric in (a, b), so which Jacobian is
+// transposed is decided by the vertex order, not by the edge's direction.
+__device__ __forceinline__ void pg_edge_weighted(const PGView& v, const TileMap& tm, double* __restrict__ g, int64_t e, uint32_t a,
+                                                 uint32_t b, const double k0[8], const double k1[8], const double m[8]) {
+    double W[36], r[6];
+    load_info<6>(v.info, e, W);
+    Jac6 J0, J1;
+    EdgeNormal6 nf;
+    if (!between_linearize_weighted(k0, k1, m, v.loss, W, r, J0, J1, nf)) return;
+    double M[36], H[36], gv[6];
+    info_mul_jac(W, J0, M);   // Omega J0
+    jt_mul(J0, M, H);
+    nf.correct(H, nf.w0, nf.w0);
+    atomic_add_lower6(h_block_ptr<6>(tm, a, a), H);
+    if (a < b) {   // row b, column a: J1^T Omega J0
+        jt_mul(J1, M, H);
+        nf.correct(H, nf.w1, nf.w0);
+        atomic_add_full6(h_block_ptr<6>(tm, b, a), H);
+    }
+    info_mul_jac(W, J1, M);   // Omega J1
+    jt_mul(J1, M, H);
+    nf.correct(H, nf.w1, nf.w1);
+    atomic_add_lower6(h_block_ptr<6>(tm, b, b), H);
+    if (a > b) {   // row a, column b: J0^T Omega J1
+        jt_mul(J0, M, H);
+        nf.correct(H, nf.w0, nf.w1);
+        atomic_add_full6(h_block_ptr<6>(tm, a, b), H);
+    } else if (a == b) {   // self-loop: the two cross terms G_01 + G_10 = G_01 + G_01^T land on the diagonal block
+        jt_mul(J0, M, H);
+        nf.correct(H, nf.w0, nf.w1);
+        double* blk = h_block_ptr<6>(tm, a, a);
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) unsafeAtomicAdd(blk + i * kNB + j, H[6 * i + j] + H[6 * j + i]);
+    }
+    nf.grad(nf.w0, gv);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) unsafeAtomicAdd(g + (size_t)a * 6 + i, gv[i]);
+    nf.grad(nf.w1, gv);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) unsafeAtomicAdd(g + (size_t)b * 6 + i, gv[i]);
+}
+
 // LP = LossGeneral: J0, J1, r stay uncorrected and every block and gradient segment is corrected as it is formed
 // (EdgeNormal6, pg_device.hpp); an edge whose rho' is 0 leaves before any block is formed.
 template <class LP>
@@ -110,6 +189,7 @@ __global__ __launch_bounds__(256) void k_pg_edges(PGView v, TileMap tm, double* 
     load_pose<Se3Manifold>(v.posep, a, k0);
     load_pose<Se3Manifold>(v.posep, b, k1);
     load_pose<Se3Manifold>(v.meas, e, m);
+    if constexpr (kWeighted<LP>) { pg_edge_weighted(v, tm, g, e, a, b, k0, k1, m); return; }
     Jac6 J0, J1;
     [[maybe_unused]] EdgeNormal6 nf;
     if constexpr (LP::kGeneral) {
@@ -197,14 +277,17 @@ __global__ __launch_bounds__(256) void k_pg2_assemble(PGView v, TileMap tm, doub
     if (i >= v.n_v) return;
     const uint32_t row = (uint32_t)i;
     double H[9], gv[3];
-    pg2_assemble_row(row, v.posep, v.meas, v.e_from, v.e_to, v.inc_ptr, v.inc_edge, loss_param<LP>(v), H, gv,
-                     [&](uint32_t u, const double* B) {
-                         double* blk = h_block_ptr<3>(tm, row, u);
+    const auto add_off = [&](uint32_t u, const double* B) {
+        double* blk = h_block_ptr<3>(tm, row, u);
 #pragma unroll
-                         for (int a = 0; a < 3; ++a)
+        for (int a = 0; a < 3; ++a)
 #pragma unroll
-                             for (int b = 0; b < 3; ++b) blk[a * kNB + b] += B[3 * a + b];
-                     });
+            for (int b = 0; b < 3; ++b) blk[a * kNB + b] += B[3 * a + b];
+    };
+    if constexpr (kWeighted<LP>)
+        pg2_assemble_row_info(row, v.posep, v.meas, v.e_from, v.e_to, v.inc_ptr, v.inc_edge, v.info, v.loss, H, gv, add_off);
+    else
+        pg2_assemble_row(row, v.posep, v.meas, v.e_from, v.e_to, v.inc_ptr, v.inc_edge, loss_param<LP>(v), H, gv, add_off);
     double* blk = h_block_ptr<3>(tm, row, row);   // (on top of the damping add_diag has put there)
 #pragma unroll
     for (int a = 0; a < 3; ++a)
@@ -262,7 +345,12 @@ __global__ __launch_bounds__(256) void k_pg_cost_partial(PGView v, double* __res
         load_pose<M>(v.posep, v.e_to[e], k1);
         load_pose<M>(v.meas, e, m);
         M::residual(k0, k1, m, r);
-        const double s = sumsq<M::kDof>(r);
+        double s = sumsq<M::kDof>(r);
+        if constexpr (kWeighted<LP>) {   // s = r^T Omega r
+            double W[M::kDof * M::kDof];
+            load_info<M::kDof>(v.info, e, W);
+            s = info_sqnorm<M::kDof>(W, r);
+        }
         if constexpr (LP::kGeneral) {   // |r~|^2 = residual_scaling^2 s: in the second arm that is not rho' s
             const double sc = pg_loss_corrector(v.loss, s).residual_scaling;
             acc += (sc * sc) * s;
@@ -304,6 +392,12 @@ __global__ __launch_bounds__(256) void k_pg_export(PGView v, double* __restrict_
     load_pose<M>(v.posep, v.e_from[e], k0);
     load_pose<M>(v.posep, v.e_to[e], k1);
     load_pose<M>(v.meas, e, m);
+    if constexpr (kWeighted<LP>) {
+        double W[M::kDof * M::kDof];
+        load_info<M::kDof>(v.info, e, W);
+        M::export_edge_info(k0, k1, m, v.loss, W, r_out ? r_out + M::kDof * e : nullptr, j_out ? j_out + 2 * M::kDof * M::kDof * e : nullptr);
+        return;
+    }
     M::export_edge(k0, k1, m, loss_param<LP>(v), r_out ? r_out + M::kDof * e : nullptr,
                    j_out ? j_out + 2 * M::kDof * M::kDof * e : nullptr);
 }
@@ -345,10 +439,19 @@ __global__ __launch_bounds__(256) void k_pg_jv_gram(PGView v, const double* __re
             a0[i] = a[(size_t)D * from + i]; a1[i] = a[(size_t)D * to + i];
             b0[i] = b[(size_t)D * from + i]; b1[i] = b[(size_t)D * to + i];
         }
-        M::edge_jv(k0, k1, m, loss_param<LP>(v), a0, a1, b0, b1, u, w);
         double su = 0.0, sx = 0.0, sw = 0.0;
+        if constexpr (kWeighted<LP>) {   // u, w corrected but not whitened: the products close with Omega
+            double W[D * D], Wu[D], Ww[D];
+            load_info<D>(v.info, e, W);
+            M::edge_jv_info(k0, k1, m, v.loss, W, a0, a1, b0, b1, u, w);
+            info_mv<D>(W, u, Wu);
+            info_mv<D>(W, w, Ww);
+            su = dotn<D>(u, Wu); sx = dotn<D>(u, Ww); sw = dotn<D>(w, Ww);
+        } else {
+            M::edge_jv(k0, k1, m, loss_param<LP>(v), a0, a1, b0, b1, u, w);
 #pragma unroll
-        for (int i = 0; i < D; ++i) { su += u[i] * u[i]; sx += u[i] * w[i]; sw += w[i] * w[i]; }
+            for (int i = 0; i < D; ++i) { su += u[i] * u[i]; sx += u[i] * w[i]; sw += w[i] * w[i]; }
+        }
         uu += su; uw += sx; ww += sw;
     }
     uu = block_sum_256(uu, scratch);
@@ -413,10 +516,12 @@ static inline void with_manifold(int manifold, F f) {
     if (manifold == kManifoldSE2) f(Se2Manifold{});
     else f(Se3Manifold{});
 }
-// the one place a view's loss becomes a policy type: the legacy instantiation unless a loss was set through apexgpu_pg_set_loss
+// the one place a view's loss becomes a policy type: the weighted instantiation when the view carries information matrices,
+// else the legacy instantiation unless a loss was set through apexgpu_pg_set_loss
 template <class F>
 static inline void with_loss(const PGView& v, F f) {
-    if (v.loss.kind != kLossNone) f(LossGeneral{});
+    if (v.info) f(LossWeighted{});
+    else if (v.loss.kind != kLossNone) f(LossGeneral{});
     else f(LossLegacy{});
 }
 

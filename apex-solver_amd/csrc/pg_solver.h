@@ -40,6 +40,11 @@ class PoseGraphSolver : public TileBackend, public TrBackend {
     // Priors keep their per-block Huber delta.  Drops a pending step and the Dog-Leg cache like set_priors.
     int set_loss(int kind, double p0, double p1);
     void get_loss(int* kind, double out2[2]) const;
+    // Edge information matrices: info [n_e][dof * dof] row-major, the caller's edge order; NULL: none.  Every
+    // matrix is checked on the host (finite, symmetric to 1e-12 max|Omega|, positive definite) before anything changes; the
+    // upper triangle is what is stored.  Drops a pending step and the Dog-Leg cache like set_loss; set_structure clears it.
+    int set_information(const double* info);
+    int get_information(int* present, double* info_out) const;   // info_out [n_e][dof * dof], full and symmetric; may be NULL
     int get_prior_residual(double* r7_out);
     int get_params(double* poses7);
 
@@ -118,6 +123,8 @@ class PoseGraphSolver : public TileBackend, public TrBackend {
     DeviceBuffer<double> prior_data_;
     DeviceBuffer<double> prior_res_;   // staging of get_prior_residual
     DeviceBuffer<double> meas_;
+    DeviceBuffer<double> info_;        // [n_e][InfoPack<dof>::kStride] packed upper triangles; empty: no information
+    std::vector<double> info_host_;    // the same on the host (get_information)
     DeviceBuffer<uint8_t> fix_;
     DeviceBuffer<double> g_, rhs_, d_, work_, partial_, scal_;
     JacobiScaling scale_;              // Jacobi scaling, internal order, [n_pad] with 1 on the padding; on: TileBackend::scaled_

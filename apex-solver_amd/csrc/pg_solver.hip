@@ -37,6 +37,12 @@ PGView PoseGraphSolver::view(int which) const {
         v.huber_delta = loss_.kind == kLossHuber ? loss_.p0 : -1.0;
         if (!legacy) v.loss = loss_;
     }
+    // information matrices: the weighted instantiations take every loss as a PgLoss, no loss, L2 and Huber included
+    if (info_) {
+        v.info = info_;
+        if (loss_set_) v.loss = loss_;
+        else if (huber_delta_ > 0.0) (void)pg_loss_make(kLossHuber, huber_delta_, 0.0, &v.loss);
+    }
     v.n_prior = n_prior_; v.prior_v = prior_v_; v.prior_data = prior_data_;
     if (manifold_ == kManifoldSE2) {
         v.poses = poses_[which]; v.inc_ptr = inc_ptr_; v.inc_edge = inc_edge_; v.prior_slot = prior_slot_;
@@ -107,6 +113,65 @@ int PoseGraphSolver::set_loss(int kind, double p0, double p1) {
     return kOk;
 }
 
+int PoseGraphSolver::set_information(const double* info) {
+    if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
+    const int D = dof_, S = (D * (D + 1) / 2 + 1) & ~1;
+    std::vector<double> packed;
+    if (info) {
+        packed.assign((size_t)n_e_ * S, 0.0);
+        for (int64_t e = 0; e < n_e_; ++e) {
+            const double* W = info + (size_t)e * D * D;
+            const std::string who = "set_information: edge " + std::to_string(e);
+            double big = 0.0;
+            for (int i = 0; i < D * D; ++i) {
+                if (!std::isfinite(W[i])) return fail(kInvalidInput, who + " has an entry that is not finite");
+                big = std::max(big, fabs(W[i]));
+            }
+            for (int i = 0; i < D; ++i)
+                for (int j = i + 1; j < D; ++j)
+                    if (fabs(W[D * i + j] - W[D * j + i]) > 1e-12 * big) return fail(kInvalidInput, who + " is not symmetric");
+            double U[36];   // Omega = U^T U from the upper triangle
+            for (int i = 0; i < D; ++i)
+                for (int j = i; j < D; ++j) {
+                    double acc = W[D * i + j];
+                    for (int k = 0; k < i; ++k) acc -= U[D * k + i] * U[D * k + j];
+                    if (i == j) {
+                        if (!(acc > 0.0)) return fail(kInvalidInput, who + " is not positive definite (Cholesky pivot " + std::to_string(i) + " <= 0)");
+                        U[D * i + i] = sqrt(acc);
+                    } else {
+                        U[D * i + j] = acc / U[D * i + i];
+                    }
+                }
+            double* p = packed.data() + (size_t)e * S;
+            for (int i = 0; i < D; ++i)
+                for (int j = i; j < D; ++j) *p++ = W[D * i + j];
+        }
+    }
+    HIP_TRY(hipSetDevice(device_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    DeviceBuffer<double> fresh;   // the members change only when the upload has succeeded
+    if (info && n_e_ > 0) HIP_TRY(fresh.upload(packed));
+    st_.invalidate();
+    drop_dogleg_cache();
+    info_ = std::move(fresh);
+    info_host_ = std::move(packed);
+    return kOk;
+}
+
+int PoseGraphSolver::get_information(int* present, double* info_out) const {
+    const int D = dof_, S = (D * (D + 1) / 2 + 1) & ~1;
+    const bool have = !info_host_.empty();
+    if (present) *present = have ? 1 : 0;
+    if (!have || !info_out) return kOk;
+    for (int64_t e = 0; e < n_e_; ++e) {
+        const double* p = info_host_.data() + (size_t)e * S;
+        double* W = info_out + (size_t)e * D * D;
+        for (int i = 0; i < D; ++i)
+            for (int j = i; j < D; ++j) { W[D * i + j] = *p; W[D * j + i] = *p; ++p; }
+    }
+    return kOk;
+}
+
 // what the edges carry: the loss of set_loss, else set_structure's Huber delta (or none)
 void PoseGraphSolver::get_loss(int* kind, double out2[2]) const {
     out2[0] = out2[1] = 0.0;
@@ -138,6 +203,7 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
     huber_delta_ = huber_delta;
     loss_set_ = false;
     loss_ = PgLoss{};
+    info_.reset(); info_host_.clear();
     n_ = dof_ * n_v_;
     const int nt = (int)((n_ + kNB - 1) / kNB);
     n_pad_ = (int64_t)nt * kNB;

@@ -59,8 +59,9 @@ class G2oGraph:
     def edge_count(self) -> int:
         return int(self.edge_from.shape[0]) + self.n_edges_se2
 
-    def to_problem_data(self, name: str = "g2o", manifold: str | None = None) -> PoseGraphData:
-        """manifold "se3" | "se2"; None: "se2" for a file with SE2 content only, else "se3"."""
+    def to_problem_data(self, name: str = "g2o", manifold: str | None = None, use_information: bool = False) -> PoseGraphData:
+        """manifold "se3" | "se2"; None: "se2" for a file with SE2 content only, else "se3".  use_information: the file's edge
+        information matrices go along as `information`, in the problem's edge order (default: None, they are not used)."""
         if manifold is None:
             manifold = "se2" if (self.vertex_ids.shape[0] == 0 and self.n_vertices_se2 > 0) else "se3"
         if manifold not in ("se3", "se2"):
@@ -71,8 +72,9 @@ class G2oGraph:
             raise G2oError(*self._problem_se2_error)
         p = self._problem_se2 if manifold == "se2" else self._problem
         assert p is not None
+        info = None if (not use_information or p.information is None) else p.information.copy()
         return PoseGraphData(ids=p.ids.copy(), poses=p.poses.copy(), e_from=p.e_from.copy(), e_to=p.e_to.copy(),
-                             meas=p.meas.copy(), name=name)
+                             meas=p.meas.copy(), name=name, information=info)
 
 
 class G2oLoader:
@@ -95,7 +97,9 @@ class G2oLoader:
             rc = L.apexgpu_g2o_problem(h, capi.ptr(sid), capi.ptr(sp), capi.ptr(pf), capi.ptr(pt), capi.ptr(pm), None, None)
             if rc != 0:
                 raise G2oError(rc, L.apexgpu_g2o_last_error().decode())
-            prob = PoseGraphData(ids=sid, poses=sp, e_from=pf, e_to=pt, meas=pm)
+            pi = np.zeros((ne, 6, 6))
+            L.apexgpu_g2o_problem_information(h, capi.MANIFOLD_SE3, capi.ptr(pi))
+            prob = PoseGraphData(ids=sid, poses=sp, e_from=pf, e_to=pt, meas=pm, information=pi)
             nv2, ne2 = nv2.value, ne2.value
             ids2 = np.zeros(nv2, np.int64); poses2 = np.zeros((nv2, 3)); ef2 = np.zeros(ne2, np.int64); et2 = np.zeros(ne2, np.int64)
             meas2 = np.zeros((ne2, 3)); info2 = np.zeros((ne2, 3, 3))
@@ -104,7 +108,9 @@ class G2oLoader:
             pm2 = np.zeros((ne2, 3))
             rc = L.apexgpu_g2o_problem_se2(h, capi.ptr(sid2), capi.ptr(sp2), capi.ptr(pf2), capi.ptr(pt2), capi.ptr(pm2), None, None)
             err2 = (rc, L.apexgpu_g2o_last_error().decode()) if rc != 0 else None
-            prob2 = None if err2 else PoseGraphData(ids=sid2, poses=sp2, e_from=pf2, e_to=pt2, meas=pm2)
+            pi2 = np.zeros((ne2, 3, 3))
+            L.apexgpu_g2o_problem_information(h, capi.MANIFOLD_SE2, capi.ptr(pi2))
+            prob2 = None if err2 else PoseGraphData(ids=sid2, poses=sp2, e_from=pf2, e_to=pt2, meas=pm2, information=pi2)
             return G2oGraph(ids, poses, ef, et, meas, info, nv2, ne2, prob, ids2, poses2, ef2, et2, meas2, info2, prob2, err2)
         finally:
             L.apexgpu_g2o_close(h)
@@ -183,12 +189,19 @@ class PoseGraphProblem:
     fix: np.ndarray = field(default=None)
     priors: list = field(default_factory=list)   # (vertex index, data[7], huber delta or None) per PriorFactor block
     loss: Loss | None = None   # the loss of every BetweenFactor block; mutually exclusive with huber_delta
+    information: np.ndarray | None = None   # (n_e, dof, dof) edge information matrices; None: data.information (None: not used)
 
     def __post_init__(self):
         if self.loss is not None and self.huber_delta is not None:
             raise ValueError("PoseGraphProblem: give either loss or huber_delta, not both")
         self.manifold = self.data.manifold
         self.dof, self.ambient = (3, 3) if self.manifold == "se2" else (6, 7)
+        if self.information is None:
+            self.information = self.data.information
+        if self.information is not None:
+            self.information = np.ascontiguousarray(self.information, dtype=np.float64)
+            if self.information.shape != (self.data.n_e, self.dof, self.dof):
+                raise ValueError(f"information must be ({self.data.n_e}, {self.dof}, {self.dof})")
         if self.fix is None:
             self.fix = np.zeros((self.data.n_v, self.dof), dtype=np.uint8)
         self.pose_col = pose_graph_columns(self.data.ids, self.dof)
@@ -212,9 +225,11 @@ class PoseGraphProblem:
         return self
 
     @classmethod
-    def pose_graph(cls, data: PoseGraphData, huber_delta: float | None = None, loss: Loss | None = None) -> "PoseGraphProblem":
-        """The LM set-up: all six DOF of the first vertex fixed (pose_graph_g2o.rs:790-797)."""
-        p = cls(data, huber_delta, loss=loss)
+    def pose_graph(cls, data: PoseGraphData, huber_delta: float | None = None, loss: Loss | None = None,
+                   information: np.ndarray | None = None) -> "PoseGraphProblem":
+        """The LM set-up: all six DOF of the first vertex fixed (pose_graph_g2o.rs:790-797).  information: the edges'
+        information matrices (n_e, dof, dof); None: data.information."""
+        p = cls(data, huber_delta, loss=loss, information=information)
         for dof in range(p.dof):
             p.fix_variable(f"x{int(data.ids[0])}", dof)
         return p
@@ -324,7 +339,29 @@ class GpuSparseCholeskySolver:
             self.set_loss(problem.loss)
         if problem.priors:
             self.set_priors(problem.priors)
+        if problem.information is not None:
+            self.set_information(problem.information)
         return self
+
+    def set_information(self, information):
+        """The information matrix of every BetweenFactor block, (n_e, dof, dof) in the problem's edge order: the block is
+        whitened by it before the loss acts.  None: none, the handle is what it was before.  Raises LinAlgError (InvalidInput,
+        naming the edge) for a matrix that is not finite, not symmetric or not positive definite; the handle keeps what it had."""
+        h = self._need()
+        a = None
+        if information is not None:
+            a = np.ascontiguousarray(information, dtype=np.float64)
+            if a.shape != (h.n_edges, h.dof, h.dof):
+                raise ValueError(f"information must be ({h.n_edges}, {h.dof}, {h.dof})")
+        h.check(h.L.apexgpu_pg_set_information(h.h, capi.ptr(a)))
+
+    def get_information(self):
+        """The stored information matrices (n_e, dof, dof), full and symmetric; None when the handle has none."""
+        h = self._need()
+        present = C.c_int(0)
+        out = np.zeros((h.n_edges, h.dof, h.dof))
+        h.check(h.L.apexgpu_pg_get_information(h.h, C.byref(present), capi.ptr(out)))
+        return out if present.value else None
 
     def set_loss(self, loss: Loss | None):
         """The loss of every BetweenFactor block from here on (None: no loss); replaces the problem's huber_delta."""

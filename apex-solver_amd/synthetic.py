@@ -364,6 +364,7 @@ class PoseGraphData:
     meas: np.ndarray      # (n_e, 7)
     truth: np.ndarray | None = None
     name: str = "pose-graph"
+    information: np.ndarray | None = None   # (n_e, D, D) edge information matrices, D = 6 | 3; None: not used
 
     @property
     def n_v(self) -> int:

@@ -570,8 +570,8 @@ int apexgpu_reference_columns(int64_t n_cam, int64_t n_pt, int64_t* intr_col, in
  *   BetweenFactor<SE3>::linearize                         src/factors/between_factor.rs:268-322
  *   SparseCholeskySolver::solve_augmented_equation        src/linalg/sparse/cholesky.rs:159-230
  *   the LM loop around them                               src/optimizer/levenberg_marquardt.rs:823-1031
- * Edge information matrices are NOT used (the reference passes only edge.measurement,
- * bin/pose_graph_g2o.rs:805-826).  Vertices are numbered by the caller 0..n_v-1 (the reference sorts
+ * Edge information matrices are opt-in: a handle uses them once apexgpu_pg_set_information has given them, and is the
+ * reference's problem (which passes only edge.measurement, bin/pose_graph_g2o.rs:805-826) until then.  Vertices are numbered by the caller 0..n_v-1 (the reference sorts
  * the vertex ids); pose_col[v] is the first global column of variable "x{id_v}" in the sorted-name order
  * (apexgpu_pose_graph_columns); tangent order [rho(3); theta(3)], right-plus retraction as above.
  * The same status codes; messages via apexgpu_pg_last_error().
@@ -648,6 +648,20 @@ int apexgpu_pg_get_prior_residual(apexgpu_pg_solver* h, double* r7_out);
 int apexgpu_pg_set_loss(apexgpu_pg_solver* h, int kind, double p0, double p1);
 /* what the edges carry: the loss of set_loss, else HUBER with set_structure's delta, else NONE; out2 = {p0, p1} */
 int apexgpu_pg_get_loss(const apexgpu_pg_solver* h, int* kind, double out2[2]);
+/* ---- edge information matrices -------------------------------------------------------------------------------------------
+ * info[e] is the symmetric positive-definite D x D matrix Omega_e of BetweenFactor e (D = 6 | 3), row-major, in the tangent
+ * order of the residual ([rho; theta] | [x, y, theta] -- the order of a G2O file), the caller's edge order; NULL: none, the
+ * handle is again what it was before the first call.  With Omega = U^T U (U upper-triangular) the block is the reference's
+ * block whitened, r_w = U r, J_w = U J, and the loss (huber_delta or apexgpu_pg_set_loss) acts on (r_w, J_w,
+ * s = r^T Omega r) through the same corrector: whiten, then robustify.  The cost is 1/2 sum rho(r^T Omega r), H = J^T Omega J
+ * without a loss; apexgpu_pg_covariance is then a covariance in the units of Omega^-1.  Prior blocks carry no information
+ * matrix.  After apexgpu_pg_set_structure (which clears it), else APEXGPU_ERR_INVALID_STATE.  APEXGPU_ERR_INVALID_INPUT, with
+ * the first offending edge named in apexgpu_pg_last_error and the handle unchanged, when an entry is not finite, when
+ * |Omega_ij - Omega_ji| > 1e-12 max|Omega|, or when the Cholesky factorisation meets a pivot <= 0.  The upper triangle is what
+ * is stored.  Invalidates a pending step and a cached Dog-Leg solve like apexgpu_pg_set_loss.
+ * apexgpu_pg_get_information: *present = 1 when matrices are held; info_out (may be NULL) receives them, full and symmetric. */
+int apexgpu_pg_set_information(apexgpu_pg_solver* h, const double* info);
+int apexgpu_pg_get_information(apexgpu_pg_solver* h, int* present, double* info_out);
 /* host only, no device: out6 = { rho, rho', rho'', sqrt_rho1, residual_scaling, alpha_sq_norm } at squared norm s */
 int apexgpu_loss_evaluate(int kind, double p0, double p1, double s, double out6[6]);
 int apexgpu_pg_set_params(apexgpu_pg_solver* h, const double* poses7);
@@ -791,12 +805,16 @@ int apexgpu_pose_graph_columns(int64_t n_vertices, const int64_t* ids, int64_t* 
 /* the SE2 content of the file.  raw: file order; poses3 / meas3 = [x, y, theta]; e_from / e_to are vertex IDS; info9 row-major
  * symmetric; any may be NULL.  problem: what bin/pose_graph_g2o.rs:366-437 builds for the LM optimiser -- vertices sorted by
  * id, variables x{id} in sorted-name order with 3 columns each (apexgpu_pose_graph_columns_se2), the three DOF of the first
- * vertex fixed, one BetweenFactor per EDGE_SE2 with edge.measurement only (the information matrix is not used by the factor). */
+ * vertex fixed, one BetweenFactor per EDGE_SE2 with edge.measurement (the information matrices come from apexgpu_g2o_problem_information and
+ * reach the factor through apexgpu_pg_set_information only). */
 int apexgpu_g2o_raw_se2(const apexgpu_g2o* g, int64_t* ids, double* poses3, int64_t* e_from, int64_t* e_to, double* meas3,
                         double* info9);
 int apexgpu_g2o_problem_se2(const apexgpu_g2o* g, int64_t* sorted_ids, double* poses3, uint32_t* e_from, uint32_t* e_to,
                             double* meas3, int64_t* pose_col, uint8_t* fix3);
 int apexgpu_pose_graph_columns_se2(int64_t n_vertices, const int64_t* ids, int64_t* pose_col);
+/* host only: the file's edge information matrices in the edge order of apexgpu_g2o_problem (manifold APEXGPU_MANIFOLD_SE3:
+ * info_out [n_e][36]) or apexgpu_g2o_problem_se2 (APEXGPU_MANIFOLD_SE2: [n_e][9]), row-major, full and symmetric */
+int apexgpu_g2o_problem_information(const apexgpu_g2o* g, int manifold, double* info_out);
 
 #ifdef __cplusplus
 }
