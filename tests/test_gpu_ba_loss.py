@@ -11,6 +11,7 @@ import ba_loss_cases as bc
 import np_ref_ba_loss as nb
 import referee
 from apex_solver_amd import capi
+from ba_custom import custom_problem
 from apex_solver_amd.loss import Loss, create_loss_function
 from apex_solver_amd.solver import (GpuSchurComplementSolver, LevenbergMarquardtConfig, OptimizationType, Problem, SchurVariant)
 
@@ -117,19 +118,8 @@ def test_legacy_kinds_through_set_loss_are_the_huber_delta_kernels_bit_for_bit(c
 
 
 def _custom(n_cam, cam_lists, seed=5):
-    """tests/test_gpu_parity.py's construction: explicit per-landmark camera lists (duplicates allowed), shuffled"""
-    base = pkg.synthetic.make_problem(n_cam, len(cam_lists), 3, 3, config_id=seed)
-    cam_idx, pt_idx = [], []
-    for l, cams in enumerate(cam_lists):
-        cam_idx += list(cams); pt_idx += [l] * len(cams)
-    cam_idx = np.asarray(cam_idx, dtype=np.uint32); pt_idx = np.asarray(pt_idx, dtype=np.uint32)
-    rng = np.random.default_rng(seed)
-    perm = rng.permutation(len(cam_idx))
-    cam_idx, pt_idx = cam_idx[perm], pt_idx[perm]
-    uv = pkg.synthetic.project_bal(base.truth_poses[cam_idx], base.truth_intr[cam_idx], base.truth_points[pt_idx])
-    uv = uv + rng.normal(0, 0.7, uv.shape)
-    uv[::5] += rng.normal(0, 25.0, uv[::5].shape)
-    return pkg.synthetic.BAProblemData(base.poses, base.intr, base.points, cam_idx, pt_idx, np.ascontiguousarray(uv))
+    """tests/ba_custom.py: explicit per-landmark camera lists (duplicates allowed), shuffled, every fifth factor an outlier"""
+    return custom_problem(n_cam, cam_lists, seed=seed, outlier_every=5)
 
 
 @pytest.mark.parametrize("mode", ["selfcal", "ba"])

@@ -11,6 +11,7 @@ import pytest
 import apex_solver_amd as pkg
 import np_ref
 import referee
+from ba_custom import custom_problem
 from apex_solver_amd.solver import (GpuSchurComplementSolver, LevenbergMarquardt, LevenbergMarquardtConfig,
                                     OptimizationStatus, OptimizationType, Problem, SchurVariant)
 
@@ -326,21 +327,8 @@ def test_full_normal_equations_from_exported_blocks():
 
 # ---- edge cases -----------------------------------------------------------------------------------
 def _custom(n_cam, n_pt, cam_lists, seed=5):
-    """A problem with explicit per-landmark camera lists (duplicates allowed)."""
-    base = pkg.synthetic.make_problem(n_cam, n_pt, 3, 3, config_id=seed)
-    cam_idx, pt_idx = [], []
-    for l, cams in enumerate(cam_lists):
-        cam_idx += list(cams); pt_idx += [l] * len(cams)
-    cam_idx = np.asarray(cam_idx, dtype=np.uint32); pt_idx = np.asarray(pt_idx, dtype=np.uint32)
-    rng = np.random.default_rng(seed)
-    # shuffle the factor order: the caller's order is arbitrary, the library sorts by landmark
-    perm = rng.permutation(len(cam_idx))
-    cam_idx, pt_idx = cam_idx[perm], pt_idx[perm]
-    uv = pkg.synthetic.project_bal(base.truth_poses[cam_idx], base.truth_intr[cam_idx], base.truth_points[pt_idx])
-    uv = uv + rng.normal(0, 0.7, uv.shape)
-    from apex_solver_amd.synthetic import BAProblemData
-
-    return BAProblemData(base.poses, base.intr, base.points, cam_idx, pt_idx, np.ascontiguousarray(uv))
+    """A problem with explicit per-landmark camera lists (duplicates allowed): tests/ba_custom.py."""
+    return custom_problem(n_cam, cam_lists, seed=seed, n_pt=n_pt)
 
 
 @pytest.mark.parametrize("mode", ["selfcal", "ba"])
