@@ -16,5 +16,5 @@ __all__ = ["layout", "synthetic"]
 from . import bal, capi, datasets, loss, pose_graph, solver  # noqa: F401,E402
 from .pose_graph import (DogLegConfig, G2oLoader, GaussNewtonConfig, GpuSparseCholeskySolver,  # noqa: F401,E402
                          PoseGraphProblem)
-from .solver import (GpuSchurComplementSolver, LevenbergMarquardt, LevenbergMarquardtConfig,  # noqa: F401,E402
+from .solver import (DogLeg, GpuSchurComplementSolver, LevenbergMarquardt, LevenbergMarquardtConfig,  # noqa: F401,E402
                      LinearSolverType, OptimizationStatus, OptimizationType, Problem, SchurVariant, SolverResult)

@@ -47,6 +47,8 @@ SYMBOLS = (
     "apexgpu_pose_graph_columns_se2",
     # Gauss-Newton and Dog-Leg on pose graphs
     "apexgpu_pg_jv_gram", "apexgpu_pg_dogleg_step", "apexgpu_pg_gn_optimize", "apexgpu_pg_dogleg_optimize",
+    # Dog-Leg on bundle adjustment
+    "apexgpu_jv_gram", "apexgpu_dogleg_step", "apexgpu_dogleg_optimize",
     # the robust loss family on pose graphs
     "apexgpu_pg_set_loss", "apexgpu_pg_get_loss", "apexgpu_loss_evaluate", "apexgpu_set_loss", "apexgpu_get_loss",
     # edge information matrices on pose graphs
@@ -245,6 +247,9 @@ def load() -> C.CDLL:
     L.apexgpu_pg_column_norms.argtypes = [vp, vp]
     L.apexgpu_pg_set_column_scaling.argtypes = [vp, vp]
     L.apexgpu_pg_lm_optimize.argtypes = [vp, C.POINTER(LmConfigC), C.POINTER(LmResultC), vp, C.c_int]
+    L.apexgpu_jv_gram.argtypes = [vp, vp, vp, C.POINTER(dbl * 3)]
+    L.apexgpu_dogleg_step.argtypes = [vp, dbl, dbl, C.c_int, C.POINTER(dbl * 8)]
+    L.apexgpu_dogleg_optimize.argtypes = [vp, C.POINTER(DlConfigC), C.POINTER(LmResultC), vp, C.c_int]
     L.apexgpu_pg_jv_gram.argtypes = [vp, vp, vp, C.POINTER(dbl * 3)]
     L.apexgpu_pg_dogleg_step.argtypes = [vp, dbl, dbl, C.c_int, C.POINTER(dbl * 8)]
     L.apexgpu_pg_gn_optimize.argtypes = [vp, C.POINTER(GnConfigC), C.POINTER(LmResultC), vp, C.c_int]

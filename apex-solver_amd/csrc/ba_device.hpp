@@ -302,6 +302,67 @@ APEX_HD bool linearize_obs(const Cam& c, const double pw[3], double u_obs, doubl
     return true;
 }
 
+// u = J_o a, w = J_o b for the CORRECTED 2 x (DC + 3) Jacobian [Jc | Jl] of one observation (the Gram pass of the Dog-Leg
+// step, k_ba_jv_gram): ac / bc are the camera's DC entries, al / bl the landmark's three.  Every entry of J is formed by
+// linearize_obs' own operations on the same operands -- the same bits as the blocks the assembly built, masks, zero rows behind
+// the camera and sqrt(rho') included -- and goes straight into the two 2-vectors: J is never held.  Order of the sums: the
+// camera columns 0 .. DC - 1, then the landmark's.
+template <int DC, bool MASKED = true, class LOSS = double>
+APEX_HD bool jv_obs(const Cam& c, const double pw[3], double u_obs, double v_obs, LOSS loss, const double* ac,
+                    const double al[3], const double* bc, const double bl[3], double u[2], double w2[2]) {
+    APEX_FP_EXACT
+    u[0] = 0.0; u[1] = 0.0; w2[0] = 0.0; w2[1] = 0.0;
+    double pc[3];
+    cam_transform(c, pw, pc);
+    if (!(pc[2] < -kMinDepth)) return false;
+    const double f = c.f, k1 = c.k1, k2 = c.k2;
+    double inz = -apex_rcp(pc[2]);
+    double xn = pc[0] * inz, yn = pc[1] * inz;
+    double r2 = fma(xn, xn, yn * yn), r4 = r2 * r2;
+    double dist = fma(k2, r4, fma(k1, r2, 1.0));
+    double r0 = fma(f, xn * dist, -u_obs);
+    double r1 = fma(f, yn * dist, -v_obs);
+    double dd = fma(2.0 * k2, r2, k1);
+    double dxn_dz = xn * inz, dyn_dz = yn * inz;
+    const double tx = (xn * dd) * 2.0, ty = (yn * dd) * 2.0;
+    double dxd_dxn = fma(tx, xn, dist);
+    double dxd_dyn = tx * yn;
+    double dyd_dxn = ty * xn;
+    double dyd_dyn = fma(ty, yn, dist);
+    double Jp[2][3];
+    Jp[0][0] = f * (dxd_dxn * inz);
+    Jp[0][1] = f * (dxd_dyn * inz);
+    Jp[0][2] = f * fma(dxd_dxn, dxn_dz, dxd_dyn * dyn_dz);
+    Jp[1][0] = f * (dyd_dxn * inz);
+    Jp[1][1] = f * (dyd_dyn * inz);
+    Jp[1][2] = f * fma(dyd_dxn, dxn_dz, dyd_dyn * dyn_dz);
+    const double* R = c.R;
+    const double w = loss_sqrt_rho1(loss, fma(r0, r0, r1 * r1));
+    const double wl = MASKED ? w * c.m_lm : w, wp = MASKED ? w * c.m_pose : w;
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+        double a0 = fma(Jp[rr][0], R[0], fma(Jp[rr][1], R[3], Jp[rr][2] * R[6]));
+        double a1 = fma(Jp[rr][0], R[1], fma(Jp[rr][1], R[4], Jp[rr][2] * R[7]));
+        double a2 = fma(Jp[rr][0], R[2], fma(Jp[rr][1], R[5], Jp[rr][2] * R[8]));
+        const double jc[6] = {a0 * wp, a1 * wp, a2 * wp, fma(a2, pw[1], -(a1 * pw[2])) * wp, fma(a0, pw[2], -(a2 * pw[0])) * wp,
+                              fma(a1, pw[0], -(a0 * pw[1])) * wp};
+        double su = 0.0, sw = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { su = fma(jc[k], ac[k], su); sw = fma(jc[k], bc[k], sw); }
+        if (DC == 9) {   // d(u,v)/d(f,k1,k2)
+            const double wi = MASKED ? w * c.m_intr : w, n = rr == 0 ? xn : yn;
+            const double ji[3] = {(n * dist) * wi, (f * n * r2) * wi, (f * n * r4) * wi};
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { su = fma(ji[k], ac[DC - 3 + k], su); sw = fma(ji[k], bc[DC - 3 + k], sw); }
+        }
+        const double jl[3] = {a0 * wl, a1 * wl, a2 * wl};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { su = fma(jl[k], al[k], su); sw = fma(jl[k], bl[k], sw); }
+        u[rr] = su; w2[rr] = sw;
+    }
+    return true;
+}
+
 // ---- the Jacobian of one observation from its projection record (device code only) ---------------------------------
 // J follows from the record and the camera without the projection:
 //     Jl = a = (f w inz) [dxx dxy .; dxy dyy .] R      (2 x 3, corrected)

@@ -100,6 +100,12 @@ void launch_retract(int dc, int64_t n_cam, int64_t n_pt, const double* poses, co
                     const uint8_t* fix_intr, const uint8_t* fix_pt, double* poses_out, double* intr_out,
                     double* pts_out, hipStream_t s);
 void launch_cost(const BAView& v, double* partial, int n_partial, double* out_sumsq, hipStream_t s, const PgLoss* loss = nullptr);
+// Dog-Leg's products with H = J^T J (k_ba_jv_gram): out3 = { sum |J_o a|^2, sum (J_o a).(J_o b), sum |J_o b|^2 } over the local
+// observations, J_o the corrected Jacobian at v's parameters as the assembly builds it (masks, zero rows behind the camera,
+// sqrt(rho')).  a_cam / b_cam [n_cam][dc], a_pt / b_pt [n_pt][3] in internal order (dcam_ / dl_), taken as given: v's scaling
+// is not read.  partial[n_partial * 3], fixed order of summation, no atomics.
+void launch_ba_jv_gram(int dc, const BAView& v, const double* a_cam, const double* a_pt, const double* b_cam, const double* b_pt,
+                       double* partial, int n_partial, double* out3, hipStream_t s, const PgLoss* loss = nullptr);
 // gscale (may be NULL): the gradient the statistics use is g .* gscale (the scaled gradient of Jacobi scaling)
 void launch_step_stats(int64_t n, const double* g, const double* d, double lambda, const double* gscale, double* partial,
                        int n_partial, double* out3, hipStream_t s);

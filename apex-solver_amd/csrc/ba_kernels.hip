@@ -764,6 +764,74 @@ __global__ __launch_bounds__(256) void k_cost_partial(BAView v, LOSS... loss, do
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
+// ------------------------------------------------------------------------------------------
+// Dog-Leg: a.Ha, a.Hb, b.Hb for H = J^T J without H -- with u = J a, w = J b they are sum |u_o|^2, sum u_o.w_o, sum |w_o|^2
+// over the observations (dogleg_combine.hpp; the pose graphs' k_pg_jv_gram).  One lane per observation over the landmark-major
+// stream in k_cost_partial's form (a contiguous range of whole 64-observation steps per wave, the next step's record in
+// flight, the cameras through the wave's cache): the landmark reads of a_pt / b_pt run with the points', the camera vectors
+// (at most 1 MB) are gathered.  jv_obs (ba_device.hpp) prices the Jacobian the assembly built, entry for entry, and holds no
+// J.  a_cam / b_cam [n_cam][DC], a_pt / b_pt [n_pt][3], internal order, as given: the kernel knows no scaling.  No atomics:
+// lane, wave, workgroup into partial[3 block + k], then k_sum_partials in index order -- the same bits on every call.
+// ------------------------------------------------------------------------------------------
+template <int DC, class... LOSS>
+__global__ __launch_bounds__(256) void k_ba_jv_gram(BAView v, LOSS... loss, const double* __restrict__ a_cam,
+                                                     const double* __restrict__ a_pt, const double* __restrict__ b_cam,
+                                                     const double* __restrict__ b_pt, double* __restrict__ partial) {
+    __shared__ double scratch[4];
+    __shared__ CamCache cache[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    CamCache& cc = cache[w];
+    cam_cache_reset(cc, lane);
+    // The general form reads its loss from LDS: as a kernel argument the loss and the constants the compiler derives from it sit
+    // in scalar registers beside the view and the four vectors, a few more than there are; from LDS they are vector registers.
+    __shared__ double loss_lds[sizeof(PgLoss) / sizeof(double)];   // (raw: a type with member initialisers cannot be __shared__)
+    if constexpr (sizeof...(LOSS) > 0) {
+        if (threadIdx.x == 0) *reinterpret_cast<PgLoss*>(loss_lds) = (loss, ...);
+        __syncthreads();
+    }
+    // (n_obs <= 2e9, set_structure: the step counts fit 32 bits, which keeps the loop's uniform state in few scalar registers)
+    const int n_waves = (int)gridDim.x * 4, wave = (int)blockIdx.x * 4 + w;
+    const int steps = (int)((v.n_obs + 63) / 64), per = (steps + n_waves - 1) / n_waves;
+    const int s0 = min(steps, wave * per), s1 = min(steps, s0 + per);
+    double uu = 0.0, uw = 0.0, ww = 0.0;
+    uint32_t c_next = 0, l_next = 0;
+    double2 uv_next = make_double2(0.0, 0.0);
+    if (s0 < s1) {
+        const int64_t i0 = min((int64_t)s0 * 64 + lane, v.n_obs - 1);
+        c_next = v.o_cam[i0]; l_next = v.o_pt[i0]; uv_next = v.o_uv[i0];
+    }
+    for (int st = s0; st < s1; ++st) {
+        const int64_t i = (int64_t)st * 64 + lane;
+        const bool active = i < v.n_obs;   // (a lane past the end re-reads the last observation and adds nothing)
+        const uint32_t c = c_next, l = l_next;
+        const double2 uv = uv_next;
+        if (st + 1 < s1) {
+            const int64_t in = min(i + 64, v.n_obs - 1);
+            c_next = v.o_cam[in]; l_next = v.o_pt[in]; uv_next = v.o_uv[in];
+        }
+        double q[kCamQStride];
+        cam_cache_get(cc, v.camq, c, active, q);
+        Cam cam;
+        load_cam_q(q, v.mask_code, cam);
+        const size_t lo = 3 * (size_t)l, co = (size_t)DC * c;
+        const double pw[3] = {v.pts[lo], v.pts[lo + 1], v.pts[lo + 2]};
+        const double al[3] = {a_pt[lo], a_pt[lo + 1], a_pt[lo + 2]}, bl[3] = {b_pt[lo], b_pt[lo + 1], b_pt[lo + 2]};
+        double ac[DC], bc[DC];
+#pragma unroll
+        for (int k = 0; k < DC; ++k) { ac[k] = a_cam[co + k]; bc[k] = b_cam[co + k]; }
+        double u[2], x[2];
+        if constexpr (sizeof...(LOSS) > 0) jv_obs<DC>(cam, pw, uv.x, uv.y, *reinterpret_cast<const PgLoss*>(loss_lds), ac, al, bc, bl, u, x);
+        else jv_obs<DC>(cam, pw, uv.x, uv.y, v.huber_delta, ac, al, bc, bl, u, x);
+        uu += active ? u[0] * u[0] + u[1] * u[1] : 0.0;
+        uw += active ? u[0] * x[0] + u[1] * x[1] : 0.0;
+        ww += active ? x[0] * x[0] + x[1] * x[1] : 0.0;
+    }
+    uu = block_sum_256(uu, scratch);
+    uw = block_sum_256(uw, scratch);
+    ww = block_sum_256(ww, scratch);
+    if (threadIdx.x == 0) { partial[3 * blockIdx.x] = uu; partial[3 * blockIdx.x + 1] = uw; partial[3 * blockIdx.x + 2] = ww; }
+}
+
 // out[k] = sum_i partial[i*stride + k], k < nk, in index order (single block, reproducible)
 __global__ __launch_bounds__(256) void k_sum_partials(const double* __restrict__ partial, int n, int nk,
                                                         double* __restrict__ out) {
@@ -968,6 +1036,19 @@ void launch_cost(const BAView& v, double* partial, int n_partial, double* out_su
     if (loss) hipLaunchKernelGGL(k_cost_partial<PgLoss>, dim3(n_partial), dim3(256), 0, s, v, *loss, partial);
     else hipLaunchKernelGGL(k_cost_partial<>, dim3(n_partial), dim3(256), 0, s, v, partial);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, partial, n_partial, 1, out_sumsq);
+}
+
+void launch_ba_jv_gram(int dc, const BAView& v, const double* a_cam, const double* a_pt, const double* b_cam, const double* b_pt,
+                       double* partial, int n_partial, double* out3, hipStream_t s, const PgLoss* loss) {
+    const dim3 grid(n_partial), block(256);
+    if (loss) {
+        if (dc == 9) hipLaunchKernelGGL((k_ba_jv_gram<9, PgLoss>), grid, block, 0, s, v, *loss, a_cam, a_pt, b_cam, b_pt, partial);
+        else hipLaunchKernelGGL((k_ba_jv_gram<6, PgLoss>), grid, block, 0, s, v, *loss, a_cam, a_pt, b_cam, b_pt, partial);
+    } else {
+        if (dc == 9) hipLaunchKernelGGL(k_ba_jv_gram<9>, grid, block, 0, s, v, a_cam, a_pt, b_cam, b_pt, partial);
+        else hipLaunchKernelGGL(k_ba_jv_gram<6>, grid, block, 0, s, v, a_cam, a_pt, b_cam, b_pt, partial);
+    }
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, partial, n_partial, 3, out3);
 }
 
 void launch_step_stats(int64_t n, const double* g, const double* d, double lambda, const double* gscale, double* partial,

@@ -874,6 +874,24 @@ int apexgpu_pg_dogleg_optimize(apexgpu_pg_solver* h, apexgpu_dl_config* cfg, ape
     return h->s->dogleg_optimize(reinterpret_cast<apex::DlConfig*>(cfg), reinterpret_cast<apex::LmResult*>(result),
                                  reinterpret_cast<apex::DlIterRecord*>(history), history ? history_capacity : 0);
 }
+int apexgpu_jv_gram(apexgpu_solver* h, const double* a, const double* b, double out3[3]) {
+    H_OR_FAIL;
+    if (!a || !b || !out3) return APEXGPU_ERR_INVALID_INPUT;
+    return guarded([&] { return h->s->jv_gram(a, b, out3); });
+}
+int apexgpu_dogleg_step(apexgpu_solver* h, double mu, double radius, int reuse, double out8[8]) {
+    H_OR_FAIL;
+    return guarded([&] { return h->s->dogleg_step(mu, radius, reuse, reinterpret_cast<apex::DoglegStepInfo*>(out8)); });
+}
+int apexgpu_dogleg_optimize(apexgpu_solver* h, apexgpu_dl_config* cfg, apexgpu_lm_result* result, apexgpu_dl_iter* history,
+                            int history_capacity) {
+    H_OR_FAIL;
+    if (!cfg || !result) return APEXGPU_ERR_INVALID_INPUT;
+    return guarded([&] {
+        return h->s->dogleg_optimize(reinterpret_cast<apex::DlConfig*>(cfg), reinterpret_cast<apex::LmResult*>(result),
+                                     reinterpret_cast<apex::DlIterRecord*>(history), history ? history_capacity : 0);
+    });
+}
 int apexgpu_pg_get_residual(apexgpu_pg_solver* h, double* r_out) { PG_OR_FAIL; return h->s->get_residual(r_out); }
 int apexgpu_pg_get_jacobian_blocks(apexgpu_pg_solver* h, double* j_out) { PG_OR_FAIL; return h->s->get_jacobian_blocks(j_out); }
 int apexgpu_pg_set_priors(apexgpu_pg_solver* h, int64_t n, const uint32_t* vertex, const double* data7, const double* huber_delta) {

@@ -594,6 +594,21 @@ void launch_dl_dots(int64_t n, const double* g, const double* d, const double* s
     hipLaunchKernelGGL(k_dl_dots, dim3(n_partial), dim3(256), 0, s, n, g, d, scale, a_out, h_out, partial);
     launch_sum_partials(partial, n_partial, 3, out3, s);
 }
+// Two segments (bundle adjustment: cameras, landmarks): each runs the one-segment kernel over its own half of the partials, the
+// first segment's blocks ahead of the second's, then ONE sum in index order.
+void launch_dl_dots2(const DlSegment& s0, const DlSegment& s1, double* partial, int n_partial, double* out3, hipStream_t s) {
+    const int half = n_partial / 2;   // (an odd n_partial leaves its last slot unused: 2 * half are written and summed)
+    hipLaunchKernelGGL(k_dl_dots, dim3(half), dim3(256), 0, s, s0.n, s0.g, s0.d, s0.scale, s0.a, s0.h, partial);
+    hipLaunchKernelGGL(k_dl_dots, dim3(half), dim3(256), 0, s, s1.n, s1.g, s1.d, s1.scale, s1.a, s1.h, partial + 3 * (size_t)half);
+    launch_sum_partials(partial, 2 * half, 3, out3, s);
+}
+void launch_dl_blend2(const DlSegment& s0, const DlSegment& s1, const double* coef, double* partial, int n_partial,
+                      double* out_sumsq, hipStream_t s) {
+    const int half = n_partial / 2;
+    hipLaunchKernelGGL(k_dl_blend, dim3(half), dim3(256), 0, s, s0.n, s0.g, s0.scale, s0.h, coef, s0.d, partial);
+    hipLaunchKernelGGL(k_dl_blend, dim3(half), dim3(256), 0, s, s1.n, s1.g, s1.scale, s1.h, coef, s1.d, partial + half);
+    launch_sum_partials(partial, 2 * half, 1, out_sumsq, s);
+}
 void launch_dl_combine(const double* sums6, double delta, double* out7, hipStream_t s) {
     hipLaunchKernelGGL(k_dl_combine, dim3(1), dim3(64), 0, s, sums6, delta, out7);
 }

@@ -511,9 +511,11 @@ int PoseGraphSolver::dogleg_step(double mu, double radius, int reuse, DoglegStep
         if (rc == kOk) rc = check_hip(hipStreamSynchronize(stream_), "dogleg_step");
         if (rc == kOk) st_.step_computed();
     } else {
-        dl_mode_ = true;
-        rc = solve_damped(mu, nullptr, nullptr);
-        dl_mode_ = false;
+        struct ModeGuard { bool& on; explicit ModeGuard(bool& f) : on(f) { on = true; } ~ModeGuard() { on = false; } };   // (cleared on every way out)
+        {
+            ModeGuard in_dogleg(dl_mode_);
+            rc = solve_damped(mu, nullptr, nullptr);
+        }
         if (rc == kOk) have_dl_cache_ = true;
     }
     if (rc != kOk) return rc;

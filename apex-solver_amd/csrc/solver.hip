@@ -567,6 +567,8 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
 
     have_structure_ = true;
     have_params_ = false; st_.invalidate();
+    drop_dogleg_cache();
+    hgn_c_.reset(); hgn_l_.reset(); dla_c_.reset(); dla_l_.reset(); dls_.reset();   // (dogleg_step allocates them again)
     st_.cur = 0;
     return kOk;
 }
@@ -590,6 +592,7 @@ int Solver::set_params(const double* poses, const double* intr, const double* po
     launch_prepare_cams(n_cam_, poses_[st_.cur], intr_[st_.cur], camp_[st_.cur], mode_mask(mode_), stream_);
     HIP_TRY(hipStreamSynchronize(stream_));
     have_params_ = true; st_.invalidate(); orec_fresh_ = false;
+    drop_dogleg_cache();
     factor_lin_ = -1;   // (the current set is overwritten: the factor's linearisation is no longer known)
     return kOk;
 }
@@ -606,6 +609,7 @@ int Solver::set_loss(int kind, double p0, double p1) {
     HIP_TRY(hipSetDevice(device_));
     HIP_TRY(hipStreamSynchronize(stream_));
     st_.invalidate(); orec_fresh_ = false;
+    drop_dogleg_cache();
     factor_lin_ = -1;   // (the factor was linearised under the old loss)
     loss_ = l;
     loss_set_ = true;
@@ -707,6 +711,7 @@ int Solver::assemble(double lambda, double diag_extra, bool for_factor) {
 
 // this rank's part of S, g_red, g_c (its landmarks), before any exchange
 int Solver::assemble_local(double lambda, double diag_extra, bool for_factor) {
+    drop_dogleg_cache();   // (g_c_ / g_l_ are overwritten)
     const BAView v = view(st_.cur);
     const TileMap tm = tilemap();
     stage_begin(kStAssembleCam);
@@ -773,6 +778,10 @@ int Solver::factor_with_ladder(double lambda) {
 // A speculative factorisation went wrong: what was enqueued behind it is void.  A failed pivot takes the waited-for path from
 // the top (S again, the factorisation, the ladder); after a give-up the repaired factorisation stands in for that path's first.
 int Solver::recover_factor(double lambda, int failed, bool gave_up) {
+    if (dl_mode_) {   // Dog-Leg: no ladder -- a regularised h would not solve the system whose products are priced; the loop raises mu
+        if (gave_up) { const int rc = factor_again(lambda, 0.0, &failed); if (rc != kOk) return rc; }
+        return failed ? fail(kFactorizationFailed, "non-positive pivot in tile column " + std::to_string(failed - 1) + " of S") : kOk;
+    }
     if (!gave_up) {
         const int rc = assemble(lambda, 0.0, true);
         return rc != kOk ? rc : factor_with_ladder(lambda);
@@ -826,6 +835,7 @@ int Solver::pcg_solve() {
 // Sharded: g_red, g_c and the diagonal blocks are all-reduced once, every S p once per iteration.
 // ---------------------------------------------------------------------------------------------
 int Solver::assemble_implicit(double lambda) {
+    drop_dogleg_cache();   // (g_c_ / g_l_ are overwritten)
     tp_.set_factor_valid(false);   // (the camera reduction adds to the diagonal tiles)
     const BAView v = view(st_.cur);
     stage_begin(kStAssembleLm);
@@ -923,6 +933,7 @@ int Solver::solve_augmented(double lambda, int variant, double* step_out, double
     if (!have_params_) return fail(kInvalidState, "Block structure not built or parameters not set");
     HIP_TRY(hipSetDevice(device_));
     begin_solve(lambda);
+    drop_dogleg_cache();
     last_pcg_iters_ = 0;   // (the PCG variants set it: apexgpu_info[5] is about THIS solve)
     tp_.set_factor_valid(false);   // (every variant writes the tiles or leaves them stale for this point)
     int pcg_max = cg_max_iter_;
@@ -957,13 +968,20 @@ int Solver::finish_step(double* step_out, double* grad_out) {
     if (scaled_) launch_vec_mul(n_c_, dcam_, cam_scale_.dev, dcam_, stream_);  // apply_inverse_scaling: dc = D_c y
     // what the LM loop asks next (step statistics, trial cost) rides on this solve's wait (tile_backend.h, eager_eval_; single
     // rank); the trial POINTS are written by the back-substitution itself
-    const bool eager = eager_eval_ && !(comm_ && world_ > 1);
+    // (a Dog-Leg solve evaluates the BLENDED step behind its tail, not the Gauss-Newton step these sweeps left)
+    const bool eager = eager_eval_ && !(comm_ && world_ > 1) && !dl_mode_;
     trial_pts_written_ = eager && fix_pt_ != nullptr;
     launch_back_substitute(dc_, view(st_.cur), hinv_, g_l_, dcam_, dl_, stream_, backsub_records(), trial_pts_written_ ? fix_pt_ : nullptr,
                            trial_pts_written_ ? pts_[st_.cur ^ 1] : nullptr, general_loss());
     stage_end(kStBackSub);
     HIP_TRY(hipGetLastError());
     st_.step_computed();
+    if (dl_mode_) {
+        const int rc = enqueue_dogleg_tail(true);
+        if (rc != kOk) return rc;
+        HIP_TRY(hipStreamSynchronize(stream_));
+        return kOk;
+    }
     if (eager) { const int rc = enqueue_eager_eval(); if (rc != kOk) return rc; }
     const int rc = export_step(step_out, grad_out);   // (synchronises)
     if (rc == kOk && eager) post_eager_answers();
@@ -1068,6 +1086,7 @@ int Solver::assemble_only(double lambda) {
     if (!have_params_) return fail(kInvalidState, "Block structure not built or parameters not set");
     HIP_TRY(hipSetDevice(device_));
     st_.invalidate_step();
+    drop_dogleg_cache();
     last_lambda_ = lambda;
     int rc = assemble(lambda, 0.0);
     if (rc != kOk) return rc;
@@ -1146,6 +1165,7 @@ int Solver::column_norms_sq_device() {
 int Solver::column_norms(double* norms_out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
+    drop_dogleg_cache();
     int rc = column_norms_sq_device();
     if (rc != kOk) return rc;
     std::vector<double> hc(n_c_), hl(3 * n_pt_);
@@ -1167,6 +1187,7 @@ int Solver::set_column_scaling(const double* scaling) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built");
     HIP_TRY(hipSetDevice(device_));
     st_.invalidate_step();
+    drop_dogleg_cache();
     if (!scaling) { scaled_ = false; return kOk; }
     if (factor_scaled_) factor_lin_ = -1;   // (the factor's scale vectors are overwritten below)
     HIP_TRY(cam_scale_.ensure());
@@ -1182,6 +1203,7 @@ int Solver::set_column_scaling(const double* scaling) {
 
 // iteration 0 of the reference's loop: norms of the current Jacobian -> s = 1 / (1 + norm), kept for the whole optimize
 int Solver::set_jacobi_scaling(bool on) {
+    drop_dogleg_cache();
     if (!on) { scaled_ = false; st_.invalidate_step(); return kOk; }
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
@@ -1201,6 +1223,132 @@ int Solver::set_jacobi_scaling(bool on) {
 int Solver::lm_optimize(LmConfig* cfg, LmResult* res, LmIterRecord* hist, int hist_cap) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     return run_lm(*this, cfg, res, hist, hist_cap);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Dog-Leg (tr_loop.h).  Everything is in the SCALED variables when Jacobi scaling is on: g_s = D g, y = D^-1 d with
+// d the unscaled step the back-substitution left; g_s.H_s g_s = |J D g_s|^2, g_s.H_s y = (J D g_s).(J d), y.H_s y = |J d|^2 --
+// the Gram kernel is handed D^2 g and d and never sees D.
+// ---------------------------------------------------------------------------------------------
+int Solver::dogleg_refusal() {
+    if (matrix_free_only_ || auto_fallback_)
+        return fail(kInvalidState, "Dog-Leg needs the direct solve: this handle is matrix-free only (the PCG step is inexact and S is never factorised)");
+    if (world_ > 1 || tp_.distributed()) return fail(kInvalidState, "Dog-Leg: single rank only");
+    return kOk;
+}
+
+int Solver::enqueue_dogleg_tail(bool fresh) {
+    const double* sc_c = scaled_ ? cam_scale_.dev.get() : nullptr;
+    const double* sc_l = scaled_ ? pt_scale_.dev.get() : nullptr;
+    const DlSegment cams{n_c_, g_c_, dcam_, sc_c, scaled_ ? dla_c_.get() : nullptr, hgn_c_};
+    const DlSegment lms{3 * n_pt_, g_l_, dl_, sc_l, scaled_ ? dla_l_.get() : nullptr, hgn_l_};
+    stage_begin(kStStats);
+    if (fresh) {
+        launch_dl_dots2(cams, lms, partial_, n_partial_, dls_, stream_);
+        launch_ba_jv_gram(dc_, view(st_.cur), scaled_ ? dla_c_.get() : g_c_.get(), scaled_ ? dla_l_.get() : g_l_.get(), dcam_, dl_,
+                          partial_, n_partial_, dls_ + 3, stream_, general_loss());
+    }
+    launch_dl_combine(dls_, dl_radius_, dls_ + 6, stream_);
+    launch_dl_blend2(cams, lms, dls_ + 8, partial_, n_partial_, dls_ + 13, stream_);
+    stage_end(kStStats);
+    trial_pts_written_ = false;   // (the trial point belongs to the blended step: the retraction writes all of it)
+    const int rc = enqueue_trial_point(dls_ + 14);
+    if (rc != kOk) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(dl_host_, dls_, 16 * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    return kOk;
+}
+
+// solve_augmented(mu, 0) on a single rank, with dl_mode_ on: finish_step runs the tail, recover_factor leaves the ladder out
+int Solver::solve_dogleg(double mu) {
+    begin_solve(mu);
+    last_pcg_iters_ = 0;
+    last_reg_ = 0.0;
+    tp_.set_factor_valid(false);
+    int rc = assemble(mu, 0.0, true);   // (drops the Dog-Leg cache)
+    if (rc != kOk) return rc;
+    if (!one_wait_) {   // the flags are waited for where they are raised
+        int lm_err = 0, failed = 0;
+        HIP_TRY(hipMemcpyAsync(&lm_err, flags_, sizeof(int), hipMemcpyDeviceToHost, stream_));
+        HIP_TRY(hipStreamSynchronize(stream_));
+        if (lm_err) return own_flag_raised();
+        rc = factor_fresh(mu, 0.0, &failed);
+        if (rc == kOk) rc = recover_factor(mu, failed, false);   // (a failed pivot: the error)
+        if (rc != kOk) return rc;
+    }
+    return direct_solve(one_wait_, mu, nullptr, nullptr);
+}
+
+int Solver::dogleg_step(double mu, double radius, int reuse, DoglegStepInfo* out) {
+    if (!have_params_) return fail(kInvalidState, "Block structure not built or parameters not set");
+    { const int rc = dogleg_refusal(); if (rc != kOk) return rc; }
+    if (!(radius > 0.0) || !(mu >= 0.0)) return fail(kInvalidInput, "dogleg_step: the radius must be positive and mu non-negative");
+    if (reuse && !have_dl_cache_) return fail(kInvalidState, "no cached Dog-Leg solve to reuse");
+    HIP_TRY(hipSetDevice(device_));
+    if (!dls_) {
+        HIP_TRY(hgn_c_.alloc_zero(n_c_pad_));
+        HIP_TRY(hgn_l_.alloc_zero(3 * n_pt_));
+        HIP_TRY(dla_c_.alloc_zero(n_c_pad_));
+        HIP_TRY(dla_l_.alloc_zero(3 * n_pt_));
+        HIP_TRY(dls_.alloc_zero(16));
+        HIP_TRY(hipDeviceSynchronize());   // (null-stream memsets ahead of the work on stream_)
+    }
+    if (!dl_host_) HIP_TRY(dl_host_.alloc(16));
+    static_assert(sizeof(PgLoss) % sizeof(double) == 0, "k_ba_jv_gram keeps the loss in doubles of LDS");
+    if (n_partial_ < 2) return fail(kInvalidState, "Dog-Leg: the two-segment reductions need two partial slots");
+    dl_radius_ = radius;
+    int rc;
+    if (reuse) {
+        begin_solve(last_lambda_);
+        rc = enqueue_dogleg_tail(false);
+        if (rc == kOk) rc = check_hip(hipStreamSynchronize(stream_), "dogleg_step");
+        if (rc == kOk) st_.step_computed();
+    } else {
+        // (cleared on every way out, an exception caught at the C boundary included: a flag left on would take the ladder, the
+        // export and the eager evaluation away from every later solve_augmented)
+        struct ModeGuard { bool& on; explicit ModeGuard(bool& f) : on(f) { on = true; } ~ModeGuard() { on = false; } };
+        {
+            ModeGuard in_dogleg(dl_mode_);
+            rc = solve_dogleg(mu);
+        }
+        if (rc == kOk) have_dl_cache_ = true;
+    }
+    if (rc != kOk) return rc;
+    const double* h = dl_host_;   // |g_s|, |step|, -s.g - 1/2 s.Hs (dog_leg.rs:1046, 1222, 948-960); the trial point is in place
+    st_.post_answers({sqrt(h[0]), sqrt(h[13]), h[11], h[14]});
+    if (out) {
+        out->gradient_norm = sqrt(h[0]); out->step_norm = sqrt(h[13]); out->predicted_reduction = h[11]; out->step_type = h[12];
+        out->alpha = h[6]; out->beta = h[7]; out->scaled_step_norm = h[10]; out->reused = reuse ? 1.0 : 0.0;
+    }
+    return kOk;
+}
+
+int Solver::dogleg_optimize(DlConfig* cfg, LmResult* res, DlIterRecord* hist, int hist_cap) {
+    if (!have_params_) return fail(kInvalidState, "no parameters set");
+    if (cfg->variant != 0) return fail(kInvalidInput, "Dog-Leg runs on the sparse Cholesky variant (0) only");
+    { const int rc = dogleg_refusal(); if (rc != kOk) return rc; }
+    if (!(cfg->trust_region_radius > 0.0) || !(cfg->mu >= 0.0)) return fail(kInvalidInput, "Dog-Leg: the radius must be positive and mu non-negative");
+    return run_dogleg(*this, cfg, res, hist, hist_cap);
+}
+
+int Solver::jv_gram(const double* a, const double* b, double out3[3]) {
+    if (!have_params_) return fail(kInvalidState, "no parameters set");
+    if (world_ > 1) return fail(kInvalidState, "jv_gram: single rank only");
+    HIP_TRY(hipSetDevice(device_));
+    std::vector<double> hac(n_c_pad_, 0.0), hbc(n_c_pad_, 0.0), hal(3 * n_pt_), hbl(3 * n_pt_);
+    cam_map_.gather(a, hac.data()); cam_map_.gather(b, hbc.data());
+    pt_map_.gather(a, hal.data()); pt_map_.gather(b, hbl.data());
+    DeviceBuffer<double> dac, dbc, dal, dbl;
+    HIP_TRY(hipStreamSynchronize(stream_));
+    HIP_TRY(dac.upload(hac)); HIP_TRY(dbc.upload(hbc)); HIP_TRY(dal.upload(hal)); HIP_TRY(dbl.upload(hbl));
+    // scal_ [12..14]: clear of the step's sums, the trial slot, parameter_norm's and the PCG's scalars
+    stage_begin(kStStats);   // (with stage timing on, this call's step_stats time is the Gram pass alone: tools/ba_trust_region_bench.py)
+    launch_ba_jv_gram(dc_, view(st_.cur), dac, dal, dbc, dbl, partial_, n_partial_, scal_ + 12, stream_, general_loss());
+    stage_end(kStStats);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out3, scal_ + 12, 3 * sizeof(double), hipMemcpyDeviceToHost, stream_);
+    (void)hipStreamSynchronize(stream_);   // (before the staging buffers are freed)
+    return check_hip(e, "jv_gram");
 }
 
 // ---------------------------------------------------------------------------------------------

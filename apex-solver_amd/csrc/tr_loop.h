@@ -4,8 +4,9 @@
 //   GaussNewton::optimize_with_mode   src/optimizer/gauss_newton.rs:559-720   (defaults :236-255)
 //   DogLeg::optimize_with_mode        src/optimizer/dog_leg.rs:1143-1354      (defaults :353-399, state :725-745)
 // Gauss-Newton needs nothing LmBackend does not have: it is solve_augmented(0) (solve_normal_equation) with every step kept.
-// Dog-Leg needs one call more, dogleg_step; TrBackend adds it.  The pose-graph backend (pg_solver.h) implements it, the
-// bundle-adjustment backend does not: the reference's Dog-Leg never runs on a Schur solver (optimizer/mod.rs:681-693).
+// Dog-Leg needs one call more, dogleg_step; TrBackend adds it.  Both backends implement it: the pose-graph one (pg_solver.h) on
+// its sparse Cholesky, the bundle-adjustment one (solver.h) on the Schur solver -- the reference hands a DogLeg configured with
+// SparseSchurComplement a sparse Cholesky of the whole H + mu I (optimizer/mod.rs:681-693), which computes the same step.
 #pragma once
 #include "lm_loop.h"
 

@@ -10,6 +10,9 @@ read like the reference's own tests:
   LevenbergMarquardtConfig             src/optimizer/levenberg_marquardt.rs:213-530
   LevenbergMarquardt.optimize          :1034-1083 (dispatch) and :823-1031 (loop; the loop itself
                                        runs in the library's C++ twin, apexgpu_lm_optimize)
+  DogLeg.optimize                      src/optimizer/dog_leg.rs:1143-1354 (the loop runs in apexgpu_dogleg_optimize; on a
+                                       Schur solver the reference solves by a sparse Cholesky of H + mu I,
+                                       optimizer/mod.rs:681-693 -- the same step)
   GpuSchurComplementSolver             LinearSolver<M> + StructureAware (src/linalg/mod.rs:116-180)
                                        as SparseSchurComplementSolver implements them
                                        (explicit_schur.rs:1038-1243)
@@ -28,6 +31,7 @@ import numpy as np
 from . import capi
 from .layout import ColumnLayout, reference_column_layout
 from .loss import Loss, create_loss_function  # noqa: F401
+from .pose_graph import DogLegConfig
 from .synthetic import BAProblemData
 
 
@@ -582,6 +586,41 @@ class GpuSchurComplementSolver:
         H = np.array([[getattr(hist[i], f) for f, _ in capi.LmIterC._fields_] for i in range(min(n, cap))])
         return res, H.reshape(-1, 8), c
 
+    # ---- Dog-Leg (dog_leg.rs): mirrors of GpuSparseCholeskySolver's three calls ----
+    def dogleg_optimize(self, cfg: DogLegConfig):
+        """DogLeg::optimize (dog_leg.rs:1143-1354) on the device: (result, history (n, 12) in DlIterC's columns, the config as
+        the loop left it -- trust_region_radius and mu hold their final values).  LinAlgError: InvalidInput for cfg.variant != 0,
+        InvalidState on a matrix-free or a sharded handle."""
+        h = self._need()
+        c = cfg.to_c()
+        res = capi.LmResultC()
+        cap = cfg.max_iterations + 2
+        hist = (capi.DlIterC * cap)()
+        h.check(h.L.apexgpu_dogleg_optimize(h.h, C.byref(c), C.byref(res), C.cast(hist, C.c_void_p), cap))
+        H = np.array([[getattr(hist[i], f) for f, _ in capi.DlIterC._fields_] for i in range(min(res.iterations, cap))])
+        return res, H.reshape(-1, 12), c
+
+    def dogleg_step(self, mu: float, radius: float, reuse: bool = False) -> dict:
+        """One Dog-Leg step and its trial point at the current parameters; eval_step / commit_step / discard_step follow.
+        reuse: rebuild the step from the cached solve at the new radius (no assembly, factorisation, sweeps or
+        back-substitution).  A failed factorisation raises FactorizationFailed / SingularMatrix without the ladder."""
+        h = self._need()
+        o = (C.c_double * 8)()
+        h.check(h.L.apexgpu_dogleg_step(h.h, float(mu), float(radius), 1 if reuse else 0, C.byref(o)))
+        return dict(gradient_norm=o[0], step_norm=o[1], predicted_reduction=o[2], step_type=int(o[3]), alpha=o[4], beta=o[5],
+                    scaled_step_norm=o[6], reused=bool(o[7]))
+
+    def jv_gram(self, a, b):
+        """(|J a|^2, (J a).(J b), |J b|^2) at the current parameters, matrix-free; a, b in the global column order."""
+        h = self._need()
+        n = self._problem.total_dof
+        a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
+        if a.shape != (n,) or b.shape != (n,):
+            raise ValueError("a and b must have total_dof entries")
+        o = (C.c_double * 3)()
+        h.check(h.L.apexgpu_jv_gram(h.h, capi.ptr(a), capi.ptr(b), C.byref(o)))
+        return o[0], o[1], o[2]
+
     def close(self):
         if self._h is not None:
             self._h.close()
@@ -702,3 +741,46 @@ class LevenbergMarquardt:
             cost_evaluations=res.cost_evaluations, jacobian_evaluations=res.jacobian_evaluations,
             successful_steps=res.successful_steps, unsuccessful_steps=res.unsuccessful_steps, history=hist,
             final_damping=c.damping, covariances=cov)
+
+
+@dataclass
+class DogLegResult(SolverResult):
+    """SolverResult of a Dog-Leg run: history has DlIterC's twelve columns (cost, radius, mu, rho, accepted, |g|, |step|,
+    predicted, trial cost, step type, beta, reused); where the loop left the trust region and mu."""
+
+    final_radius: float = 0.0
+    final_mu: float = 0.0
+
+
+class DogLeg:
+    """DogLeg (src/optimizer/dog_leg.rs) beside LevenbergMarquardt, for bundle adjustment on GpuSchurComplementSolver (pose graphs:
+    GpuSparseCholeskySolver.dogleg_optimize).  The config is pose_graph.DogLegConfig, the one both take."""
+
+    def __init__(self, config: DogLegConfig | None = None, device: int = 0):
+        self.config = config or DogLegConfig()
+        self.device = device
+        self.linear_solver = None
+
+    @classmethod
+    def new(cls): return cls()
+
+    @classmethod
+    def with_config(cls, config: DogLegConfig, device: int = 0): return cls(config, device)
+
+    def optimize(self, problem, initial_values=None, solver=None) -> DogLegResult:
+        """DogLeg::optimize (dog_leg.rs:1143-1354): builds the solver unless one is given, uploads the initial values and runs
+        the loop on the device."""
+        d = problem.data
+        s = solver or GpuSchurComplementSolver(self.device)
+        if s._h is None:
+            s.initialize_structure(problem)
+        s.set_parameters(*(initial_values if initial_values is not None else (d.poses, d.intr, d.points)))
+        self.linear_solver = s
+        res, hist, c = s.dogleg_optimize(self.config)
+        return DogLegResult(
+            status=OptimizationStatus(res.status), iterations=res.iterations, initial_cost=res.initial_cost,
+            final_cost=res.final_cost, parameters=s.get_parameters(), elapsed_time=res.elapsed_s,
+            final_gradient_norm=res.final_gradient_norm, final_parameter_update_norm=res.final_step_norm,
+            cost_evaluations=res.cost_evaluations, jacobian_evaluations=res.jacobian_evaluations,
+            successful_steps=res.successful_steps, unsuccessful_steps=res.unsuccessful_steps, history=hist,
+            final_radius=c.trust_region_radius, final_mu=c.mu)

@@ -748,6 +748,34 @@ int apexgpu_pg_gn_optimize(apexgpu_pg_solver* h, apexgpu_gn_config* cfg, apexgpu
 int apexgpu_pg_dogleg_optimize(apexgpu_pg_solver* h, apexgpu_dl_config* cfg, apexgpu_lm_result* result, apexgpu_dl_iter* history,
                                int history_capacity);
 
+/* ---- Dog-Leg on bundle adjustment (DogLeg::optimize_with_mode, dog_leg.rs:1143-1354, on an apexgpu_solver) ----------------
+ * A reference DogLeg configured with SparseSchurComplement runs on a sparse Cholesky of the whole H + mu I
+ * (create_linear_solver, optimizer/mod.rs:681-693): the step it computes is the step of the Schur path with identity damping on
+ * the camera and the landmark blocks, which is what these three entries solve for (apexgpu_solve_augmented(mu), variant 0).
+ * Refused by all three, the state of the handle unchanged: APEXGPU_ERR_INVALID_STATE on a handle that is matrix-free only
+ * ("matrix_free_only", or the automatic selection of "auto_variant": the PCG step is inexact and S is never factorised) and
+ * on a sharded handle (single rank only); apexgpu_dogleg_step / apexgpu_dogleg_optimize also APEXGPU_ERR_INVALID_INPUT for a
+ * radius <= 0 or mu < 0, apexgpu_dogleg_optimize for cfg->variant != 0.
+ *
+ * out3 = { |J a|^2, (J a).(J b), |J b|^2 } = { a.Ha, a.Hb, b.Hb } for H = J^T J of the corrected Jacobian at the current
+ * parameters (what get_hessian returns, explicit_schur.rs:1236-1238; the products of dog_leg.rs:776-803 and :948-960), in one
+ * pass over the observations -- no matrix is built.  a, b: total-dof entries in the global column order, taken as given (no
+ * scaling); the intrinsic columns of a BundleAdjustment-mode handle are not read. */
+int apexgpu_jv_gram(apexgpu_solver* h, const double* a, const double* b, double out3[3]);
+/* One Dog-Leg step at the current parameters (compute_optimization_step_generic, dog_leg.rs:963-1089) and its trial point:
+ * apexgpu_step_stats / eval_step / commit_step / discard_step follow as after apexgpu_solve_augmented.
+ * reuse = 0: solves (H + mu I) h = -g.  A factorisation that fails is APEXGPU_ERR_FACTORIZATION_FAILED, a singular landmark
+ * block APEXGPU_ERR_SINGULAR_MATRIX -- WITHOUT the regularisation ladder of apexgpu_solve_augmented: the caller raises mu
+ * (dog_leg.rs:1026-1039).  reuse = 1: the step from the cached h, g, Cauchy point of the last reuse = 0 call at the new radius
+ * (dog_leg.rs:969-1017), without assembly, factorisation, sweeps or back-substitution; APEXGPU_ERR_INVALID_STATE when there is
+ * none (or parameters, loss, structure or scaling were set, or another solve, assembly, column-norm call or export of S ran
+ * since).  out8 as apexgpu_pg_dogleg_step's. */
+int apexgpu_dogleg_step(apexgpu_solver* h, double mu, double radius, int reuse, double out8[8]);
+/* cfg->trust_region_radius and cfg->mu hold their final values on return; use_jacobi_scaling defaults to 1 in the reference
+ * (dog_leg.rs:378). */
+int apexgpu_dogleg_optimize(apexgpu_solver* h, apexgpu_dl_config* cfg, apexgpu_lm_result* result, apexgpu_dl_iter* history,
+                            int history_capacity);
+
 /* parity / debug exports: loss-corrected residuals [n_edges][6], Jacobians [n_edges][6][12] = [dr/dk0 | dr/dk1]
  * in residual-block order; dense H = J^T J + lambda I ([6 n_v]^2 row-major) and g = J^T r in the global column order.
  * SE2 handle: residuals [n_edges][3], Jacobians [n_edges][3][6], H (3 n_v)^2, g 3 n_v. */
