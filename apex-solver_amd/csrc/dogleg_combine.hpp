@@ -1,5 +1,5 @@
 // dogleg_combine.hpp -- Powell's dog leg as plain arithmetic on seven scalars, shared by the host (tr_loop's test harness) and
-// the device (k_dl_combine, pg_kernels.hip).
+// the device (k_dl_combine, dogleg_kernels.hip).
 //
 // Reference semantics (file:line under the apex-solver tree), everything in the SCALED variables (g = g_s, h = h_s, H = D J^T J D):
 //   compute_cauchy_point_and_alpha   src/optimizer/dog_leg.rs:776-803   alpha = g.g / g.Hg when |g.Hg| > 1e-15, else 1; p_c = -alpha g

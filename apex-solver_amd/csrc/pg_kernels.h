@@ -59,26 +59,9 @@ void launch_pg_retract(int manifold, int64_t n_v, const double* poses, const dou
 void launch_pg_negate(int64_t n, const double* x, double* y, hipStream_t s);
 // corrected residuals [n_e][dof] and Jacobians [n_e][dof][2 dof] = [dr/dk0 | dr/dk1] in the kernel's edge order
 void launch_pg_export(int manifold, const PGView& v, double* r_out, double* j_out, hipStream_t s);
-// Dog-Leg (dog_leg.rs:776-803, 818-902, 948-960; dogleg_combine.hpp).  All reductions: partial[n_partial * 3], fixed order.
+// Dog-Leg's products with H = J^T J (dog_leg.rs:776-803, 948-960): partial[n_partial * 3], fixed order.
 // out3 = {|J a|^2, (J a).(J b), |J b|^2} over the edges and priors of v; a, b [dof n_v] in internal column order
 void launch_pg_jv_gram(int manifold, const PGView& v, const double* a, const double* b, double* partial, int n_partial,
                        double* out3, hipStream_t s);
-// out3 = {g_s.g_s, y.y, g_s.y} for g_s = scale g, y = d / scale (scale may be NULL: 1); a_out = scale^2 g (may be NULL), h_out = d
-void launch_dl_dots(int64_t n, const double* g, const double* d, const double* scale, double* a_out, double* h_out,
-                    double* partial, int n_partial, double* out3, hipStream_t s);
-// The same two passes over a vector that lives in TWO buffers (bundle adjustment: the camera and the landmark half of the
-// gradient and the step): g the gradient, d the step (read by the dots, written by the blend), scale (may be NULL), a = scale^2 g
-// (written by the dots; may be NULL), h the cached Gauss-Newton step (written by the dots, read by the blend).  Each segment
-// takes n_partial / 2 blocks (n_partial >= 2; partial holds 3 n_partial doubles for the dots, n_partial for the blend; an odd
-// n_partial leaves its last slot unused), the partials are summed once in index order -- first segment first.
-struct DlSegment { int64_t n; const double* g; double* d; const double* scale; double* a; double* h; };
-void launch_dl_dots2(const DlSegment& s0, const DlSegment& s1, double* partial, int n_partial, double* out3, hipStream_t s);
-void launch_dl_blend2(const DlSegment& s0, const DlSegment& s1, const double* coef, double* partial, int n_partial,
-                      double* out_sumsq, hipStream_t s);
-// out7 = {alpha, beta, c_g, c_h, |step_s|, predicted reduction, type} from sums6 = {g.g, h.h, g.h, g.Hg, g.Hh, h.Hh} (device) and the radius
-void launch_dl_combine(const double* sums6, double delta, double* out7, hipStream_t s);
-// d_out = coef[1] h - coef[0] scale^2 g (coef on the device), out_sumsq = |d_out|^2
-void launch_dl_blend(int64_t n, const double* g, const double* scale, const double* h, const double* coef, double* d_out,
-                     double* partial, int n_partial, double* out_sumsq, hipStream_t s);
 
 }  // namespace apex

@@ -7,8 +7,8 @@
 //   k_pg_retract<M>       vertex-major  x (+) d with the fixed-DOF mask (src/core/problem.rs:185-197)
 //   k_pg_prior_export<M>, k_pg_export<M>  parity exports
 //   k_pg_jv_gram<M>       edge-major    |J a|^2, (J a).(J b), |J b|^2 matrix-free: the products with H = J^T J the Dog-Leg step needs
-//                                       (dog_leg.rs:776-803, 948-960) once the tiles hold L instead of H
-//   k_dl_dots, k_dl_combine, k_dl_blend  the rest of a Dog-Leg step on plain vectors (dogleg_combine.hpp)
+//                                       (dog_leg.rs:776-803, 948-960) once the tiles hold L instead of H; the rest of a Dog-Leg
+//                                       step runs on plain vectors and lives in dogleg_kernels.hip
 // The assembly is one algorithm per manifold:
 //   k_pg_edges      SE3  edge-major    r, dr/dk0, dr/dk1 per edge in registers (never written to memory), loss correction,
 //                                      then H_aa += Ja^T Ja, H_bb += Jb^T Jb, H_(hi,lo) += J_hi^T J_lo, g_a += Ja^T r,
@@ -29,7 +29,6 @@
 #include <hip/hip_runtime.h>
 
 #include "device_reduce.hpp"
-#include "dogleg_combine.hpp"
 #include "pg2_device.hpp"
 #include "pg_device.hpp"
 #include "pg_kernels.h"
@@ -460,53 +459,6 @@ __global__ __launch_bounds__(256) void k_pg_jv_gram(PGView v, const double* __re
     if (threadIdx.x == 0) { partial[3 * blockIdx.x] = uu; partial[3 * blockIdx.x + 1] = uw; partial[3 * blockIdx.x + 2] = ww; }
 }
 
-// The inner products of the scaled gradient g_s = D g and the scaled Gauss-Newton step y = D^-1 d (d: the unscaled step the
-// sweeps leave): partial = {g_s.g_s, y.y, g_s.y}.  On the way: a_out = D g_s (the direction k_pg_jv_gram prices g_s with; may be
-// null without scaling, where it is g itself) and h_out = d (the cached step: d is overwritten by the blended step).
-__global__ __launch_bounds__(256) void k_dl_dots(int64_t n, const double* __restrict__ g, const double* __restrict__ d,
-                                                   const double* __restrict__ scale, double* __restrict__ a_out,
-                                                   double* __restrict__ h_out, double* __restrict__ partial) {
-    __shared__ double scratch[4];
-    double gg = 0.0, hh = 0.0, gh = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const double s = scale ? scale[i] : 1.0, di = d[i];
-        const double gs = g[i] * s, y = scale ? di / s : di;
-        gg += gs * gs; hh += y * y; gh += gs * y;
-        if (a_out) a_out[i] = gs * s;
-        h_out[i] = di;
-    }
-    gg = block_sum_256(gg, scratch);
-    hh = block_sum_256(hh, scratch);
-    gh = block_sum_256(gh, scratch);
-    if (threadIdx.x == 0) { partial[3 * blockIdx.x] = gg; partial[3 * blockIdx.x + 1] = hh; partial[3 * blockIdx.x + 2] = gh; }
-}
-
-// one lane: the six sums and the radius -> {alpha, beta, c_g, c_h, |step_s|, predicted reduction, type}
-__global__ void k_dl_combine(const double* __restrict__ sums6, double delta, double* __restrict__ out7) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const DoglegSums s{sums6[0], sums6[1], sums6[2], sums6[3], sums6[4], sums6[5]};
-    const DoglegStep o = dogleg_combine(s, delta);
-    out7[0] = o.alpha; out7[1] = o.beta; out7[2] = o.c_g; out7[3] = o.c_h; out7[4] = o.step_norm; out7[5] = o.predicted_reduction;
-    out7[6] = (double)o.type;
-}
-
-// step = D (c_g (-g_s) + c_h y) = c_h h - c_g D^2 g into d_out, and the partial sums of |step|^2.  coef = {c_g, c_h} on the device.
-__global__ __launch_bounds__(256) void k_dl_blend(int64_t n, const double* __restrict__ g, const double* __restrict__ scale,
-                                                    const double* __restrict__ h, const double* __restrict__ coef,
-                                                    double* __restrict__ d_out, double* __restrict__ partial) {
-    __shared__ double scratch[4];
-    const double cg = coef[0], ch = coef[1];
-    double acc = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const double s = scale ? scale[i] : 1.0;
-        const double st = ch * h[i] - cg * ((g[i] * s) * s);
-        d_out[i] = st;
-        acc += st * st;
-    }
-    acc = block_sum_256(acc, scratch);
-    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-
 // ---- launchers -----------------------------------------------------------------------------------------------------
 static inline int grid256(int64_t n) { return (int)((n + 255) / 256); }
 
@@ -588,34 +540,6 @@ void launch_pg_jv_gram(int manifold, const PGView& v, const double* a, const dou
         });
     });
     launch_sum_partials(partial, n_partial, 3, out3, s);
-}
-void launch_dl_dots(int64_t n, const double* g, const double* d, const double* scale, double* a_out, double* h_out,
-                    double* partial, int n_partial, double* out3, hipStream_t s) {
-    hipLaunchKernelGGL(k_dl_dots, dim3(n_partial), dim3(256), 0, s, n, g, d, scale, a_out, h_out, partial);
-    launch_sum_partials(partial, n_partial, 3, out3, s);
-}
-// Two segments (bundle adjustment: cameras, landmarks): each runs the one-segment kernel over its own half of the partials, the
-// first segment's blocks ahead of the second's, then ONE sum in index order.
-void launch_dl_dots2(const DlSegment& s0, const DlSegment& s1, double* partial, int n_partial, double* out3, hipStream_t s) {
-    const int half = n_partial / 2;   // (an odd n_partial leaves its last slot unused: 2 * half are written and summed)
-    hipLaunchKernelGGL(k_dl_dots, dim3(half), dim3(256), 0, s, s0.n, s0.g, s0.d, s0.scale, s0.a, s0.h, partial);
-    hipLaunchKernelGGL(k_dl_dots, dim3(half), dim3(256), 0, s, s1.n, s1.g, s1.d, s1.scale, s1.a, s1.h, partial + 3 * (size_t)half);
-    launch_sum_partials(partial, 2 * half, 3, out3, s);
-}
-void launch_dl_blend2(const DlSegment& s0, const DlSegment& s1, const double* coef, double* partial, int n_partial,
-                      double* out_sumsq, hipStream_t s) {
-    const int half = n_partial / 2;
-    hipLaunchKernelGGL(k_dl_blend, dim3(half), dim3(256), 0, s, s0.n, s0.g, s0.scale, s0.h, coef, s0.d, partial);
-    hipLaunchKernelGGL(k_dl_blend, dim3(half), dim3(256), 0, s, s1.n, s1.g, s1.scale, s1.h, coef, s1.d, partial + half);
-    launch_sum_partials(partial, 2 * half, 1, out_sumsq, s);
-}
-void launch_dl_combine(const double* sums6, double delta, double* out7, hipStream_t s) {
-    hipLaunchKernelGGL(k_dl_combine, dim3(1), dim3(64), 0, s, sums6, delta, out7);
-}
-void launch_dl_blend(int64_t n, const double* g, const double* scale, const double* h, const double* coef, double* d_out,
-                     double* partial, int n_partial, double* out_sumsq, hipStream_t s) {
-    hipLaunchKernelGGL(k_dl_blend, dim3(n_partial), dim3(256), 0, s, n, g, scale, h, coef, d_out, partial);
-    launch_sum_partials(partial, n_partial, 1, out_sumsq, s);
 }
 
 }  // namespace apex

@@ -21,13 +21,12 @@
 
 #include "pg_kernels.h"
 #include "tile_backend.h"
-#include "tr_loop.h"
 
 namespace apex {
 
 enum PgStage { kPgAssemble = 0, kPgFactor, kPgTriSolve, kPgStats, kPgRetract, kPgCost, kPgNumStages };
 
-class PoseGraphSolver : public TileBackend, public TrBackend {
+class PoseGraphSolver : public TileBackend {
    public:
     PoseGraphSolver(int64_t n_v, int64_t n_e, int device, int manifold = kManifoldSE3);
     ~PoseGraphSolver() override;
@@ -52,11 +51,8 @@ class PoseGraphSolver : public TileBackend, public TrBackend {
     int solve_augmented(double lambda, int variant, double* step_out, double* grad_out) override;
     int parameter_norm(double* out) override;
     int lm_optimize(LmConfig* cfg, LmResult* res, LmIterRecord* hist, int hist_cap);
-    // Gauss-Newton and Dog-Leg (tr_loop.h).  dogleg_step runs to ONE host wait, fresh or reused: behind the sweeps come the inner
-    // products, the Gram pass over the edges (k_pg_jv_gram), the combine (one lane), the blended step into d_, the trial point
-    // and its cost, posted as this solve's answers: step_stats / eval_step then answer from the host.  A reused step starts at the combine: the six sums of
-    // the last fresh solve, g_ and the cached Gauss-Newton step (hgn_) are all it reads.
-    int dogleg_step(double mu, double radius, int reuse, DoglegStepInfo* out) override;
+    // Gauss-Newton and Dog-Leg (tr_loop.h).  dogleg_step is TileBackend's; what this solver puts in are the hooks below: one
+    // segment (g_, d_), the Gram pass over the edges (k_pg_jv_gram) and solve_damped as the fresh solve.
     int gn_optimize(GnConfig* cfg, LmResult* res, LmIterRecord* hist, int hist_cap);
     int dogleg_optimize(DlConfig* cfg, LmResult* res, DlIterRecord* hist, int hist_cap);
     // parity export: {|J a|^2, (J a).(J b), |J b|^2} at the current parameters; a, b in the caller's column order, as given
@@ -102,8 +98,11 @@ class PoseGraphSolver : public TileBackend, public TrBackend {
     StepAnswers answers_from_sums(const double* h) const override { return {sqrt(h[0]), sqrt(h[1]), 0.5 * h[2], h[3]}; }
     int assemble(double lambda);
     int solve_damped(double lambda, double* step_out, double* grad_out);   // solve_augmented behind its checks; the fresh Dog-Leg solve
-    int enqueue_dogleg_tail(bool fresh);   // everything of a Dog-Leg step behind the sweeps, up to the copy to dl_host_
-    void drop_dogleg_cache() { have_dl_cache_ = false; }
+    // the Dog-Leg hooks (tile_backend.h)
+    int dogleg_refusal() override { return have_params_ ? kOk : fail(kInvalidState, "Block structure not built or parameters not set"); }
+    int dogleg_segments(DlSegment out[2]) override;
+    void enqueue_jv_gram(const double* const a[2], const double* const b[2], double* out3) override;
+    int solve_for_dogleg(double mu) override { return solve_damped(mu, nullptr, nullptr); }
 
     int64_t n_v_, n_e_;
     int manifold_, dof_, amb_, stride_, vpt_;   // vpt_: vertices per tile = kNB / dof_
@@ -126,16 +125,8 @@ class PoseGraphSolver : public TileBackend, public TrBackend {
     DeviceBuffer<double> info_;        // [n_e][InfoPack<dof>::kStride] packed upper triangles; empty: no information
     std::vector<double> info_host_;    // the same on the host (get_information)
     DeviceBuffer<uint8_t> fix_;
-    DeviceBuffer<double> g_, rhs_, d_, work_, partial_, scal_;
+    DeviceBuffer<double> g_, rhs_, d_, work_, scal_;   // (the reduction scratch partial_ is TileBackend's)
     JacobiScaling scale_;              // Jacobi scaling, internal order, [n_pad] with 1 on the padding; on: TileBackend::scaled_
-    int n_partial_ = 256;
-    // Dog-Leg state.  dls_: [0..5] the six sums of dogleg_combine.hpp (kept from the last fresh solve), [6..12] the combine's
-    // answer, [13] |step|^2, [14] the trial point's sum of squares; dl_host_ is its pinned copy.
-    DeviceBuffer<double> hgn_, dl_a_, dls_;   // the cached (unscaled) Gauss-Newton step; D^2 g; the scalars
-    PinnedBuffer<double> dl_host_;
-    double dl_radius_ = 0.0;
-    bool dl_mode_ = false;         // finish_step: the Dog-Leg tail instead of the LM statistics
-    bool have_dl_cache_ = false;   // g_, hgn_, dls_[0..5] belong to one solve and scale_ is what it was then
 };
 
 }  // namespace apex

@@ -14,7 +14,7 @@
 namespace apex {
 
 PoseGraphSolver::PoseGraphSolver(int64_t n_v, int64_t n_e, int device, int manifold)
-    : TileBackend(device, kPgNumStages, /*nd_leaf=*/2), n_v_(n_v), n_e_(n_e), manifold_(manifold == kManifoldSE2 ? kManifoldSE2 : kManifoldSE3),
+    : TileBackend(device, kPgNumStages, /*nd_leaf=*/2, kPgStats, /*n_partial=*/256), n_v_(n_v), n_e_(n_e), manifold_(manifold == kManifoldSE2 ? kManifoldSE2 : kManifoldSE3),
       dof_(manifold_ == kManifoldSE2 ? Se2Manifold::kDof : Se3Manifold::kDof),
       amb_(manifold_ == kManifoldSE2 ? Se2Manifold::kAmb : Se3Manifold::kAmb),
       stride_(manifold_ == kManifoldSE2 ? Se2Manifold::kStride : Se3Manifold::kStride), vpt_(kNB / dof_) {}
@@ -266,7 +266,7 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
     have_structure_ = true;
     have_params_ = false; st_.invalidate();
     drop_dogleg_cache();
-    hgn_.reset(); dl_a_.reset(); dls_.reset();   // (sized by the old structure: dogleg_step allocates them again)
+    release_dogleg_buffers();
     st_.cur = 0;
     return kOk;
 }
@@ -378,7 +378,7 @@ int PoseGraphSolver::enqueue_sweeps() {
 
 int PoseGraphSolver::finish_step(double* step_out, double* grad_out) {
     st_.step_computed();
-    if (dl_mode_) {   // dogleg_step: the sweeps have left the Gauss-Newton step in d_
+    if (dl_mode_) {   // TileBackend::dogleg_step: the sweeps have left the Gauss-Newton step in d_
         const int rc = enqueue_dogleg_tail(true);
         if (rc != kOk) return rc;
         HIP_TRY(hipStreamSynchronize(stream_));
@@ -474,58 +474,13 @@ int PoseGraphSolver::lm_optimize(LmConfig* cfg, LmResult* res, LmIterRecord* his
 }
 
 // ---- Gauss-Newton and Dog-Leg (tr_loop.h) -------------------------------------------------------------------------
-int PoseGraphSolver::enqueue_dogleg_tail(bool fresh) {
-    const double* sc = scaled_ ? scale_.dev.get() : nullptr;
-    timer_.begin(kPgStats, stream_);
-    if (fresh) {
-        // g_s = D g, y = D^-1 d: g_s.g_s, y.y, g_s.y; then g_s.H_s g_s = |J D g_s|^2, g_s.H_s y = (J D g_s).(J D y), y.H_s y = |J D y|^2 with
-        // D y = d, the unscaled step the sweeps left -- the Gram kernel never sees D
-        launch_dl_dots(n_, g_, d_, sc, scaled_ ? dl_a_.get() : nullptr, hgn_, partial_, n_partial_, dls_, stream_);
-        launch_pg_jv_gram(manifold_, view(st_.cur), scaled_ ? dl_a_.get() : g_.get(), d_, partial_, n_partial_, dls_ + 3, stream_);
-    }
-    launch_dl_combine(dls_, dl_radius_, dls_ + 6, stream_);
-    launch_dl_blend(n_, g_, sc, hgn_, dls_ + 8, d_, partial_, n_partial_, dls_ + 13, stream_);
-    timer_.end(kPgStats, stream_);
-    enqueue_trial_point(dls_ + 14);
-    HIP_TRY(hipMemcpyAsync(dl_host_, dls_, 16 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    return kOk;
+int PoseGraphSolver::dogleg_segments(DlSegment out[2]) {
+    out[0] = DlSegment{n_, g_, d_, scaled_ ? scale_.dev.get() : nullptr, nullptr, nullptr, n_pad_, &map_};
+    return 1;
 }
 
-int PoseGraphSolver::dogleg_step(double mu, double radius, int reuse, DoglegStepInfo* out) {
-    if (!have_params_) return fail(kInvalidState, "Block structure not built or parameters not set");
-    if (!(radius > 0.0) || !(mu >= 0.0)) return fail(kInvalidInput, "dogleg_step: the radius must be positive and mu non-negative");
-    HIP_TRY(hipSetDevice(device_));
-    if (!dls_) {
-        HIP_TRY(hgn_.alloc_zero(n_pad_));
-        HIP_TRY(dl_a_.alloc_zero(n_pad_));
-        HIP_TRY(dls_.alloc_zero(16));
-        HIP_TRY(hipDeviceSynchronize());
-    }
-    if (!dl_host_) HIP_TRY(dl_host_.alloc(16));
-    dl_radius_ = radius;
-    int rc;
-    if (reuse) {
-        if (!have_dl_cache_) return fail(kInvalidState, "no cached Dog-Leg solve to reuse");
-        begin_solve(last_lambda_);
-        rc = enqueue_dogleg_tail(false);
-        if (rc == kOk) rc = check_hip(hipStreamSynchronize(stream_), "dogleg_step");
-        if (rc == kOk) st_.step_computed();
-    } else {
-        struct ModeGuard { bool& on; explicit ModeGuard(bool& f) : on(f) { on = true; } ~ModeGuard() { on = false; } };   // (cleared on every way out)
-        {
-            ModeGuard in_dogleg(dl_mode_);
-            rc = solve_damped(mu, nullptr, nullptr);
-        }
-        if (rc == kOk) have_dl_cache_ = true;
-    }
-    if (rc != kOk) return rc;
-    const double* h = dl_host_;   // |g_s|, |step|, -s.g - 1/2 s.Hs (dog_leg.rs:1046, 1222, 948-960); the trial point is in place
-    st_.post_answers({sqrt(h[0]), sqrt(h[13]), h[11], h[14]});
-    if (out) {
-        out->gradient_norm = sqrt(h[0]); out->step_norm = sqrt(h[13]); out->predicted_reduction = h[11]; out->step_type = h[12];
-        out->alpha = h[6]; out->beta = h[7]; out->scaled_step_norm = h[10]; out->reused = reuse ? 1.0 : 0.0;
-    }
-    return kOk;
+void PoseGraphSolver::enqueue_jv_gram(const double* const a[2], const double* const b[2], double* out3) {
+    launch_pg_jv_gram(manifold_, view(st_.cur), a[0], b[0], partial_, n_partial_, out3, stream_);
 }
 
 int PoseGraphSolver::gn_optimize(GnConfig* cfg, LmResult* res, LmIterRecord* hist, int hist_cap) {
@@ -543,18 +498,7 @@ int PoseGraphSolver::dogleg_optimize(DlConfig* cfg, LmResult* res, DlIterRecord*
 
 int PoseGraphSolver::jv_gram(const double* a, const double* b, double out3[3]) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
-    HIP_TRY(hipSetDevice(device_));
-    std::vector<double> ha(n_pad_, 0.0), hb(n_pad_, 0.0);
-    map_.gather(a, ha.data());
-    map_.gather(b, hb.data());
-    DeviceBuffer<double> da, db;
-    HIP_TRY(hipStreamSynchronize(stream_));
-    HIP_TRY(da.upload(ha));
-    HIP_TRY(db.upload(hb));
-    launch_pg_jv_gram(manifold_, view(st_.cur), da, db, partial_, n_partial_, scal_ + 5, stream_);
-    hipError_t e = hipMemcpyAsync(out3, scal_ + 5, 3 * sizeof(double), hipMemcpyDeviceToHost, stream_);
-    (void)hipStreamSynchronize(stream_);   // (before da / db are freed)
-    return check_hip(e, "jv_gram");
+    return jv_gram_columns(a, b, out3);
 }
 
 // ---- parity / debug exports ------------------------------------------------------------------

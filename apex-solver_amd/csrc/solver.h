@@ -16,12 +16,9 @@
 #include "chol_kernels.h"
 #include "pcg_kernels.h"
 #include "pcg_readback.h"
-#include "pg_kernels.h"   // the Dog-Leg vector kernels (launch_dl_*): manifold-agnostic
 #include "schur_pairs.h"
 #include "comm.h"
 #include "tile_backend.h"
-#include "tr_loop.h"
-
 
 namespace apex {
 
@@ -31,7 +28,7 @@ enum Stage { kStAssembleCam = 0, kStAssembleLm, kStScatter, kStAllReduce, kStFac
 int mode_mask(int mode);  // 4 POSE + 2 LANDMARK + INTRINSIC of an APEXGPU_MODE_*
 void shard_range(int64_t n_pt, const int64_t* ptr, int rank, int world, int64_t* lo, int64_t* hi);
 
-class Solver : public TileBackend, public TrBackend {
+class Solver : public TileBackend {
    public:
     Solver(int64_t n_cam, int64_t n_pt, int64_t n_obs, int mode, int device);
     ~Solver();
@@ -57,13 +54,11 @@ class Solver : public TileBackend, public TrBackend {
     int lm_optimize(LmConfig* cfg, LmResult* res, LmIterRecord* hist, int hist_cap);
     // Dog-Leg (tr_loop.h): what the reference's DogLeg computes on a bundle-adjustment problem -- there on a sparse
     // Cholesky of the whole H + mu I (optimizer/mod.rs:681-693), here on the Schur path: solve_augmented(mu, 0) damps Hcc and Hll by
-    // the identity.  dogleg_step runs to ONE host wait, fresh or reused: behind the back-substitution come the inner products over
-    // the two halves of g and h, the Gram pass over the observations (k_ba_jv_gram), the combine, the blended step into dcam_ /
-    // dl_, the trial point and its cost, posted as the solve's answers.  A reused step starts at the combine.  A failed
-    // factorisation is kFactorizationFailed (a raised landmark flag kSingularMatrix) WITHOUT the regularisation ladder: the loop
-    // raises mu.  Refused, nothing changing: kInvalidState on a matrix-free handle (the option or the automatic fallback: the
-    // PCG step is inexact, S is never factorised) and on several ranks; kInvalidInput for radius <= 0 or mu < 0.
-    int dogleg_step(double mu, double radius, int reuse, DoglegStepInfo* out) override;
+    // the identity.  dogleg_step is TileBackend's; what this solver puts in are the hooks below: two segments (the camera and the
+    // landmark half of g and the step, blended into dcam_ / dl_), the Gram pass over the observations (k_ba_jv_gram) and
+    // solve_for_dogleg.  A failed factorisation is kFactorizationFailed (a raised landmark flag kSingularMatrix) WITHOUT the
+    // regularisation ladder: the loop raises mu.  Refused, nothing changing: kInvalidState on a matrix-free handle (the option or
+    // the automatic fallback: the PCG step is inexact, S is never factorised) and on several ranks.
     int dogleg_optimize(DlConfig* cfg, LmResult* res, DlIterRecord* hist, int hist_cap);   // variant != 0: kInvalidInput
     // parity export: {|J a|^2, (J a).(J b), |J b|^2} at the current parameters; a, b total-dof entries in the caller's column
     // order, as given (no scaling); single rank
@@ -197,10 +192,12 @@ class Solver : public TileBackend, public TrBackend {
     int factor_with_ladder(double lambda);
     int ladder(double lambda);
     int pcg_solve();
-    int dogleg_refusal();                  // kOk, or the refusal of a Dog-Leg call on this handle (its text in err_)
-    int solve_dogleg(double mu);           // the fresh Dog-Leg solve: solve_augmented(mu, 0) without the ladder, finish_step in dl_mode_
-    int enqueue_dogleg_tail(bool fresh);   // everything of a Dog-Leg step behind the back-substitution, up to the copy to dl_host_
-    void drop_dogleg_cache() { have_dl_cache_ = false; }
+    // the Dog-Leg hooks (tile_backend.h)
+    int dogleg_refusal() override;                 // no parameters, a matrix-free handle, several ranks
+    int dogleg_segments(DlSegment out[2]) override;
+    void enqueue_jv_gram(const double* const a[2], const double* const b[2], double* out3) override;
+    int solve_for_dogleg(double mu) override;      // solve_augmented(mu, 0) without the ladder, finish_step in dl_mode_
+    void dogleg_trial_begins() override { trial_pts_written_ = false; }   // (the retraction writes all of the blended step's trial point)
     void stage_begin(int st);
     void stage_end(int st);
     // The steps of set_structure in the order it runs them (solver.hip).  Setup is the state of one call, its comments say
@@ -306,7 +303,7 @@ class Solver : public TileBackend, public TrBackend {
     DeviceBuffer<int> o_orig_, pt_ptr_, cam_ptr_, cam_obs_;
     DeviceBuffer<uint8_t> fix_pose_, fix_intr_, fix_pt_;
     DeviceBuffer<double> g_c_, g_red_, dcam_, hinv_, g_l_, dl_;
-    DeviceBuffer<double> partial_, scal_;  // reduction scratch, scalar outputs
+    DeviceBuffer<double> scal_;            // scalar outputs (the reduction scratch partial_ is TileBackend's)
     DeviceBuffer<int> flags_;              // [0] landmark inversion error
     std::vector<int> cmap_, cinv_;   // external camera -> internal camera and back
     bool hubs_last_ = true;     // order cameras covisible with > max(16, 10 sqrt(n_cam)) others last (ba_structure.h)
@@ -327,17 +324,6 @@ class Solver : public TileBackend, public TrBackend {
     DeviceBuffer<double> pcg_buf_;                 // 7 vectors of n_c_pad
     DeviceBuffer<double> lmu_, sd_, minv_;  // matrix-free variant: {pt, u_l} records, diag blocks of S, their inverses
     JacobiScaling cam_scale_, pt_scale_;   // Jacobi scaling, internal order ([n_c_pad] with 1 on the padding, [3 n_pt]); on: TileBackend::scaled_
-    int n_partial_ = 1024;
-    // Dog-Leg state, allocated by the first dogleg_step.  dls_: [0..5] the six sums of dogleg_combine.hpp (kept from the last fresh
-    // solve), [6..12] the combine's answer, [13] |step|^2, [14] the trial point's sum of squares; dl_host_ is its pinned copy.
-    DeviceBuffer<double> hgn_c_, hgn_l_;   // the cached (unscaled) Gauss-Newton step, camera and landmark half
-    DeviceBuffer<double> dla_c_, dla_l_;   // D^2 g: the direction the Gram pass prices g_s with
-    DeviceBuffer<double> dls_;
-    PinnedBuffer<double> dl_host_;
-    double dl_radius_ = 0.0;
-    bool dl_mode_ = false;         // finish_step: the Dog-Leg tail instead of the eager LM evaluation; recover_factor: no ladder
-    bool have_dl_cache_ = false;   // g_c_ / g_l_, hgn_*, dls_[0..5] belong to one solve and the scaling is what it was then
-
     bool use_graphs_ = true;
     double setup_s_[6] = {0, 0, 0, 0, 0, 0};  // set_structure by phase: order + tile structure, landmark / camera lists, tile plan, Schur lists, uploads, total
 };

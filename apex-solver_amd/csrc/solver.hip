@@ -34,7 +34,7 @@ int mode_mask(int mode) {
 }
 
 Solver::Solver(int64_t n_cam, int64_t n_pt, int64_t n_obs, int mode, int device)
-    : TileBackend(device, kNumStages, /*nd_leaf=*/16), n_cam_(n_cam), n_pt_(n_pt), n_obs_(n_obs), mode_(mode), dc_(mode_mask(mode) & 1 ? 9 : 6) {
+    : TileBackend(device, kNumStages, /*nd_leaf=*/16, kStStats, /*n_partial=*/1024), n_cam_(n_cam), n_pt_(n_pt), n_obs_(n_obs), mode_(mode), dc_(mode_mask(mode) & 1 ? 9 : 6) {
     lm_lo_ = 0; lm_hi_ = n_pt;
     HostBlockCache::get().retain();   // (the set-up's host blocks are cached only while a handle is alive: host_parallel.h)
 }
@@ -568,7 +568,7 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     have_structure_ = true;
     have_params_ = false; st_.invalidate();
     drop_dogleg_cache();
-    hgn_c_.reset(); hgn_l_.reset(); dla_c_.reset(); dla_l_.reset(); dls_.reset();   // (dogleg_step allocates them again)
+    release_dogleg_buffers();
     st_.cur = 0;
     return kOk;
 }
@@ -1226,41 +1226,30 @@ int Solver::lm_optimize(LmConfig* cfg, LmResult* res, LmIterRecord* hist, int hi
 }
 
 // ---------------------------------------------------------------------------------------------
-// Dog-Leg (tr_loop.h).  Everything is in the SCALED variables when Jacobi scaling is on: g_s = D g, y = D^-1 d with
-// d the unscaled step the back-substitution left; g_s.H_s g_s = |J D g_s|^2, g_s.H_s y = (J D g_s).(J d), y.H_s y = |J d|^2 --
-// the Gram kernel is handed D^2 g and d and never sees D.
+// Dog-Leg (tr_loop.h): what this solver puts into TileBackend::dogleg_step.  d is the unscaled step the
+// back-substitution left; the Gram kernel is handed D^2 g and d and never sees D (tile_backend.hip).
 // ---------------------------------------------------------------------------------------------
 int Solver::dogleg_refusal() {
+    if (!have_params_) return fail(kInvalidState, "Block structure not built or parameters not set");
     if (matrix_free_only_ || auto_fallback_)
         return fail(kInvalidState, "Dog-Leg needs the direct solve: this handle is matrix-free only (the PCG step is inexact and S is never factorised)");
     if (world_ > 1 || tp_.distributed()) return fail(kInvalidState, "Dog-Leg: single rank only");
     return kOk;
 }
 
-int Solver::enqueue_dogleg_tail(bool fresh) {
-    const double* sc_c = scaled_ ? cam_scale_.dev.get() : nullptr;
-    const double* sc_l = scaled_ ? pt_scale_.dev.get() : nullptr;
-    const DlSegment cams{n_c_, g_c_, dcam_, sc_c, scaled_ ? dla_c_.get() : nullptr, hgn_c_};
-    const DlSegment lms{3 * n_pt_, g_l_, dl_, sc_l, scaled_ ? dla_l_.get() : nullptr, hgn_l_};
-    stage_begin(kStStats);
-    if (fresh) {
-        launch_dl_dots2(cams, lms, partial_, n_partial_, dls_, stream_);
-        launch_ba_jv_gram(dc_, view(st_.cur), scaled_ ? dla_c_.get() : g_c_.get(), scaled_ ? dla_l_.get() : g_l_.get(), dcam_, dl_,
-                          partial_, n_partial_, dls_ + 3, stream_, general_loss());
-    }
-    launch_dl_combine(dls_, dl_radius_, dls_ + 6, stream_);
-    launch_dl_blend2(cams, lms, dls_ + 8, partial_, n_partial_, dls_ + 13, stream_);
-    stage_end(kStStats);
-    trial_pts_written_ = false;   // (the trial point belongs to the blended step: the retraction writes all of it)
-    const int rc = enqueue_trial_point(dls_ + 14);
-    if (rc != kOk) return rc;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(dl_host_, dls_, 16 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    return kOk;
+int Solver::dogleg_segments(DlSegment out[2]) {
+    out[0] = DlSegment{n_c_, g_c_, dcam_, scaled_ ? cam_scale_.dev.get() : nullptr, nullptr, nullptr, n_c_pad_, &cam_map_};
+    out[1] = DlSegment{3 * n_pt_, g_l_, dl_, scaled_ ? pt_scale_.dev.get() : nullptr, nullptr, nullptr, 3 * n_pt_, &pt_map_};
+    return 2;
+}
+
+void Solver::enqueue_jv_gram(const double* const a[2], const double* const b[2], double* out3) {
+    static_assert(sizeof(PgLoss) % sizeof(double) == 0, "k_ba_jv_gram keeps the loss in doubles of LDS");
+    launch_ba_jv_gram(dc_, view(st_.cur), a[0], a[1], b[0], b[1], partial_, n_partial_, out3, stream_, general_loss());
 }
 
 // solve_augmented(mu, 0) on a single rank, with dl_mode_ on: finish_step runs the tail, recover_factor leaves the ladder out
-int Solver::solve_dogleg(double mu) {
+int Solver::solve_for_dogleg(double mu) {
     begin_solve(mu);
     last_pcg_iters_ = 0;
     last_reg_ = 0.0;
@@ -1279,50 +1268,6 @@ int Solver::solve_dogleg(double mu) {
     return direct_solve(one_wait_, mu, nullptr, nullptr);
 }
 
-int Solver::dogleg_step(double mu, double radius, int reuse, DoglegStepInfo* out) {
-    if (!have_params_) return fail(kInvalidState, "Block structure not built or parameters not set");
-    { const int rc = dogleg_refusal(); if (rc != kOk) return rc; }
-    if (!(radius > 0.0) || !(mu >= 0.0)) return fail(kInvalidInput, "dogleg_step: the radius must be positive and mu non-negative");
-    if (reuse && !have_dl_cache_) return fail(kInvalidState, "no cached Dog-Leg solve to reuse");
-    HIP_TRY(hipSetDevice(device_));
-    if (!dls_) {
-        HIP_TRY(hgn_c_.alloc_zero(n_c_pad_));
-        HIP_TRY(hgn_l_.alloc_zero(3 * n_pt_));
-        HIP_TRY(dla_c_.alloc_zero(n_c_pad_));
-        HIP_TRY(dla_l_.alloc_zero(3 * n_pt_));
-        HIP_TRY(dls_.alloc_zero(16));
-        HIP_TRY(hipDeviceSynchronize());   // (null-stream memsets ahead of the work on stream_)
-    }
-    if (!dl_host_) HIP_TRY(dl_host_.alloc(16));
-    static_assert(sizeof(PgLoss) % sizeof(double) == 0, "k_ba_jv_gram keeps the loss in doubles of LDS");
-    if (n_partial_ < 2) return fail(kInvalidState, "Dog-Leg: the two-segment reductions need two partial slots");
-    dl_radius_ = radius;
-    int rc;
-    if (reuse) {
-        begin_solve(last_lambda_);
-        rc = enqueue_dogleg_tail(false);
-        if (rc == kOk) rc = check_hip(hipStreamSynchronize(stream_), "dogleg_step");
-        if (rc == kOk) st_.step_computed();
-    } else {
-        // (cleared on every way out, an exception caught at the C boundary included: a flag left on would take the ladder, the
-        // export and the eager evaluation away from every later solve_augmented)
-        struct ModeGuard { bool& on; explicit ModeGuard(bool& f) : on(f) { on = true; } ~ModeGuard() { on = false; } };
-        {
-            ModeGuard in_dogleg(dl_mode_);
-            rc = solve_dogleg(mu);
-        }
-        if (rc == kOk) have_dl_cache_ = true;
-    }
-    if (rc != kOk) return rc;
-    const double* h = dl_host_;   // |g_s|, |step|, -s.g - 1/2 s.Hs (dog_leg.rs:1046, 1222, 948-960); the trial point is in place
-    st_.post_answers({sqrt(h[0]), sqrt(h[13]), h[11], h[14]});
-    if (out) {
-        out->gradient_norm = sqrt(h[0]); out->step_norm = sqrt(h[13]); out->predicted_reduction = h[11]; out->step_type = h[12];
-        out->alpha = h[6]; out->beta = h[7]; out->scaled_step_norm = h[10]; out->reused = reuse ? 1.0 : 0.0;
-    }
-    return kOk;
-}
-
 int Solver::dogleg_optimize(DlConfig* cfg, LmResult* res, DlIterRecord* hist, int hist_cap) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     if (cfg->variant != 0) return fail(kInvalidInput, "Dog-Leg runs on the sparse Cholesky variant (0) only");
@@ -1334,21 +1279,7 @@ int Solver::dogleg_optimize(DlConfig* cfg, LmResult* res, DlIterRecord* hist, in
 int Solver::jv_gram(const double* a, const double* b, double out3[3]) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     if (world_ > 1) return fail(kInvalidState, "jv_gram: single rank only");
-    HIP_TRY(hipSetDevice(device_));
-    std::vector<double> hac(n_c_pad_, 0.0), hbc(n_c_pad_, 0.0), hal(3 * n_pt_), hbl(3 * n_pt_);
-    cam_map_.gather(a, hac.data()); cam_map_.gather(b, hbc.data());
-    pt_map_.gather(a, hal.data()); pt_map_.gather(b, hbl.data());
-    DeviceBuffer<double> dac, dbc, dal, dbl;
-    HIP_TRY(hipStreamSynchronize(stream_));
-    HIP_TRY(dac.upload(hac)); HIP_TRY(dbc.upload(hbc)); HIP_TRY(dal.upload(hal)); HIP_TRY(dbl.upload(hbl));
-    // scal_ [12..14]: clear of the step's sums, the trial slot, parameter_norm's and the PCG's scalars
-    stage_begin(kStStats);   // (with stage timing on, this call's step_stats time is the Gram pass alone: tools/ba_trust_region_bench.py)
-    launch_ba_jv_gram(dc_, view(st_.cur), dac, dal, dbc, dbl, partial_, n_partial_, scal_ + 12, stream_, general_loss());
-    stage_end(kStStats);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out3, scal_ + 12, 3 * sizeof(double), hipMemcpyDeviceToHost, stream_);
-    (void)hipStreamSynchronize(stream_);   // (before the staging buffers are freed)
-    return check_hip(e, "jv_gram");
+    return jv_gram_columns(a, b, out3);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // tile_backend.h -- what the two backends that factorise on a TilePlan share (solver.h: S of bundle adjustment, pg_solver.h: H of a
-// pose graph): the plan, the stream and their order of destruction, the state of one solve and the trial-step protocol on it, the switches that go to the plan, and
-// the protocol around one direct solve -- speculative factorisation, one host wait, the repairs of a dataflow launch that gave up.
+// pose graph): the plan, the stream and their order of destruction, the state of one solve and the trial-step protocol on it, the switches that go to the plan,
+// the protocol around one direct solve -- speculative factorisation, one host wait, the repairs of a dataflow launch that gave up --
+// and the Dog-Leg step on that solve (TrBackend, tr_loop.h): its state, its host protocol and its tail of vector kernels, once.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,11 +11,14 @@
 
 #include "column_map.h"
 #include "device_buffer.h"
+#include "dogleg_kernels.h"
+#include "dogleg_scalars.hpp"
 #include "jacobi_scaling.h"
 #include "lm_loop.h"
 #include "stage_timer.h"
 #include "step_state.h"
 #include "tile_plan.h"
+#include "tr_loop.h"
 
 namespace apex {
 
@@ -25,7 +29,7 @@ namespace apex {
         if (_rc != kOk) return _rc;                           \
     } while (0)
 
-class TileBackend : public virtual LmBackend {   // (virtual: a solver may also be a TrBackend, tr_loop.h)
+class TileBackend : public TrBackend {
    public:
     void enable_graphs(bool on) { tp_.enable_graphs(on); }
     void enable_overlap(bool on) { tp_.enable_overlap(on); }
@@ -60,9 +64,18 @@ class TileBackend : public virtual LmBackend {   // (virtual: a solver may also 
     int eval_step(double* trial_cost) final;    // x (+) step into the trial set, its cost
     int commit_step() final;
     int discard_step() final;                   // reference semantics: trial (+) (-step), not a snapshot
+    // The Dog-Leg step (tr_loop.h), to ONE host wait, fresh or reused.  Fresh: solve_for_dogleg with dl_mode_ on, whose finish_step
+    // runs enqueue_dogleg_tail behind the step: the inner products, the Gram pass, the combine (one lane), the blended step into
+    // the step vector, the trial point and its cost, one copy of DoglegScalars -- posted as the solve's answers, so step_stats /
+    // eval_step answer from the host.  Reused: the tail from the combine on; the six sums of the last fresh solve, the gradient
+    // and the cached Gauss-Newton step are all it reads.  Checked in this order: the solver's refusal, radius and mu
+    // (kInvalidInput), reuse without a cache (kInvalidState); only then is anything allocated.
+    int dogleg_step(double mu, double radius, int reuse, DoglegStepInfo* out) final;
 
    protected:
-    TileBackend(int device, int n_stages, int nd_leaf) : device_(device), nd_leaf_(nd_leaf), timer_(n_stages) {}
+    // stats_stage: the solver's stage the Dog-Leg tail and the Gram pass are booked under; n_partial: the blocks of a reduction
+    TileBackend(int device, int n_stages, int nd_leaf, int stats_stage, int n_partial)
+        : device_(device), nd_leaf_(nd_leaf), timer_(n_stages), n_partial_(n_partial), stats_stage_(stats_stage) {}
     int fail(int code, const std::string& msg) { err_ = msg; return code; }
     int check_hip(hipError_t e, const char* what, std::string* err = nullptr);   // err: where the text goes instead of err_
     void begin_solve(double lambda) { st_.begin_solve(); last_lambda_ = lambda; }
@@ -101,6 +114,21 @@ class TileBackend : public virtual LmBackend {   // (virtual: a solver may also 
     virtual double* step_sums(int* n) = 0;                                // device: the *n sums of enqueue_step_stats, the trial point's slot behind them
     virtual StepAnswers answers_from_sums(const double* h) const = 0;     // a host copy of those *n + 1 doubles as named answers
     virtual void params_moved() {}                                        // the current parameters are other ones now (commit, discard)
+    // ... and the Dog-Leg step (same section)
+    virtual int dogleg_refusal() = 0;                                     // kOk, or why this handle takes no Dog-Leg call now (its text in err_)
+    virtual int dogleg_segments(DlSegment out[2]) = 0;                    // the pieces of gradient and step (1 | 2), a and h left out
+    virtual void enqueue_jv_gram(const double* const a[2], const double* const b[2], double* out3) = 0;   // {|J a|^2, (J a).(J b), |J b|^2}, a and b per segment
+    virtual int solve_for_dogleg(double mu) = 0;                          // the solver's solve_augmented(mu) behind its checks, no export; dl_mode_ is on
+    virtual void dogleg_trial_begins() {}                                 // the tail is about to write the trial point of the BLENDED step, all of it
+
+    // everything of a Dog-Leg step behind the solve, up to the copy to dl_host_: a finish_step in dl_mode_ calls it with fresh
+    int enqueue_dogleg_tail(bool fresh);
+    // The solvers' parity export jv_gram behind their own refusals: a, b in the caller's columns, gathered through the segments'
+    // maps and zero-padded, to out3.  One wait; booked under the stats stage; the Dog-Leg cache stays.
+    int jv_gram_columns(const double* a, const double* b, double out3[3]);
+    void drop_dogleg_cache() { have_dl_cache_ = false; }
+    // set_structure: they are sized by the old structure, dogleg_step allocates them again
+    void release_dogleg_buffers() { for (int k = 0; k < 2; ++k) { dl_h_[k].reset(); dl_a_[k].reset(); } dls_.reset(); }
 
     int device_;
     StepState st_;
@@ -118,6 +146,19 @@ class TileBackend : public virtual LmBackend {   // (virtual: a solver may also 
     TilePlan tp_;   // the tiles, their factorisation and solves
     StageTimer timer_;
     PinnedBuffer<double> eager_host_;   // the eager evaluation's sums as step_sums() lays them out: read by answers_from_sums only
+    DeviceBuffer<double> partial_;   // reduction scratch of the solver's kernels and the tail's: the solver allocates 3 n_partial_ or more
+    const int n_partial_;
+    bool dl_mode_ = false;   // inside a fresh dogleg_step: finish_step runs the tail instead of the LM evaluation and the export
+
+   private:
+    // Dog-Leg state, allocated by the first dogleg_step
+    const int stats_stage_;
+    DeviceBuffer<double> dl_h_[2], dl_a_[2];   // per segment: the cached (unscaled) Gauss-Newton step; D^2 g, the direction the Gram pass prices g_s with
+    DeviceBuffer<DoglegScalars> dls_;          // sums[] is kept from the last fresh solve
+    PinnedBuffer<DoglegScalars> dl_host_;
+    DeviceBuffer<double> jv_out_;              // jv_gram_columns' three sums
+    double dl_radius_ = 0.0;
+    bool have_dl_cache_ = false;   // the gradient, dl_h_, dls_->sums belong to one solve and the scaling is what it was then
 };
 
 }  // namespace apex

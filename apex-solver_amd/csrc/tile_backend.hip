@@ -1,6 +1,8 @@
 // tile_backend.hip -- see tile_backend.h
 #include "tile_backend.h"
 
+#include <stddef.h>
+
 #include <vector>
 
 namespace apex {
@@ -163,6 +165,97 @@ int TileBackend::discard_step() {
     (void)st_.finish_discard();
     params_moved();
     return kOk;
+}
+
+// ---- the Dog-Leg step (tr_loop.h; DESIGN.md §5, "The Dog-Leg step, held once") ------------------------------------------------
+// Everything is in the SCALED variables when Jacobi scaling is on: g_s = D g, y = D^-1 d with d the unscaled step the solve left;
+// g_s.H_s g_s = |J D g_s|^2, g_s.H_s y = (J D g_s).(J d), y.H_s y = |J d|^2 -- the Gram pass is handed D^2 g and d and never sees D.
+int TileBackend::enqueue_dogleg_tail(bool fresh) {
+    constexpr size_t kSums = offsetof(DoglegScalars, sums) / sizeof(double), kCombined = offsetof(DoglegScalars, alpha) / sizeof(double),
+                     kCoef = offsetof(DoglegScalars, c_g) / sizeof(double), kStep = offsetof(DoglegScalars, step_sumsq) / sizeof(double),
+                     kTrial = offsetof(DoglegScalars, trial_sumsq) / sizeof(double);
+    static_assert(offsetof(DoglegScalars, c_h) == offsetof(DoglegScalars, c_g) + sizeof(double), "k_dl_blend reads {c_g, c_h}");
+    double* const s = reinterpret_cast<double*>(dls_.get());
+    DlSegment segs[2];
+    const int n_seg = dogleg_segments(segs);
+    const double *a[2] = {}, *b[2] = {};   // what the Gram pass prices: D^2 g (g itself without scaling) and the step
+    for (int k = 0; k < n_seg; ++k) {
+        segs[k].a = scaled_ ? dl_a_[k].get() : nullptr; segs[k].h = dl_h_[k];
+        a[k] = scaled_ ? segs[k].a : segs[k].g; b[k] = segs[k].d;
+    }
+    timer_.begin(stats_stage_, stream_);
+    if (fresh) {
+        launch_dl_dots(segs, n_seg, partial_, n_partial_, s + kSums, stream_);
+        enqueue_jv_gram(a, b, s + kSums + 3);
+    }
+    launch_dl_combine(s + kSums, dl_radius_, s + kCombined, stream_);
+    launch_dl_blend(segs, n_seg, s + kCoef, partial_, n_partial_, s + kStep, stream_);
+    timer_.end(stats_stage_, stream_);
+    dogleg_trial_begins();
+    const int rc = enqueue_trial_point(s + kTrial);
+    if (rc != kOk) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(dl_host_, dls_, sizeof(DoglegScalars), hipMemcpyDeviceToHost, stream_));
+    return kOk;
+}
+
+int TileBackend::dogleg_step(double mu, double radius, int reuse, DoglegStepInfo* out) {
+    { const int rc = dogleg_refusal(); if (rc != kOk) return rc; }
+    if (!(radius > 0.0) || !(mu >= 0.0)) return fail(kInvalidInput, "dogleg_step: the radius must be positive and mu non-negative");
+    if (reuse && !have_dl_cache_) return fail(kInvalidState, "no cached Dog-Leg solve to reuse");
+    HIP_TRY(hipSetDevice(device_));
+    DlSegment segs[2];
+    const int n_seg = dogleg_segments(segs);
+    if (n_partial_ < n_seg) return fail(kInvalidState, "Dog-Leg: the reductions need a partial slot per segment");
+    if (!dls_) {
+        for (int k = 0; k < n_seg; ++k) { HIP_TRY(dl_h_[k].alloc_zero(segs[k].n_alloc)); HIP_TRY(dl_a_[k].alloc_zero(segs[k].n_alloc)); }
+        HIP_TRY(dls_.alloc_zero(1));
+        HIP_TRY(hipDeviceSynchronize());   // (null-stream memsets ahead of the work on stream_)
+    }
+    if (!dl_host_) HIP_TRY(dl_host_.alloc(1));
+    dl_radius_ = radius;
+    int rc;
+    if (reuse) {
+        begin_solve(last_lambda_);
+        rc = enqueue_dogleg_tail(false);
+        if (rc == kOk) rc = check_hip(hipStreamSynchronize(stream_), "dogleg_step");
+        if (rc == kOk) st_.step_computed();
+    } else {
+        // (cleared on every way out, an exception caught at the C boundary included: a flag left on would take the ladder, the
+        // export and the eager evaluation away from every later solve_augmented)
+        struct ModeGuard { bool& on; explicit ModeGuard(bool& f) : on(f) { on = true; } ~ModeGuard() { on = false; } };
+        { ModeGuard in_dogleg(dl_mode_); rc = solve_for_dogleg(mu); }
+        if (rc == kOk) have_dl_cache_ = true;
+    }
+    if (rc != kOk) return rc;
+    st_.post_answers(dogleg_answers(*dl_host_));   // (the trial point is in place)
+    if (out) *out = dogleg_step_info(*dl_host_, reuse != 0);
+    return kOk;
+}
+
+int TileBackend::jv_gram_columns(const double* a, const double* b, double out3[3]) {
+    HIP_TRY(hipSetDevice(device_));
+    DlSegment segs[2];
+    const int n_seg = dogleg_segments(segs);
+    DeviceBuffer<double> da[2], db[2];
+    HIP_TRY(hipStreamSynchronize(stream_));
+    for (int k = 0; k < n_seg; ++k) {
+        std::vector<double> ha((size_t)segs[k].n_alloc, 0.0), hb((size_t)segs[k].n_alloc, 0.0);
+        segs[k].map->gather(a, ha.data());
+        segs[k].map->gather(b, hb.data());
+        HIP_TRY(da[k].upload(ha));
+        HIP_TRY(db[k].upload(hb));
+    }
+    if (!jv_out_) HIP_TRY(jv_out_.alloc(3));
+    const double* const pa[2] = {da[0], da[1]};
+    const double* const pb[2] = {db[0], db[1]};
+    timer_.begin(stats_stage_, stream_);   // (with stage timing on, this call's time under the stage is the Gram pass alone)
+    enqueue_jv_gram(pa, pb, jv_out_);
+    timer_.end(stats_stage_, stream_);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out3, jv_out_, 3 * sizeof(double), hipMemcpyDeviceToHost, stream_);
+    (void)hipStreamSynchronize(stream_);   // (before the staging buffers are freed)
+    return check_hip(e, "jv_gram");
 }
 
 }  // namespace apex

@@ -4,9 +4,10 @@
 //   GaussNewton::optimize_with_mode   src/optimizer/gauss_newton.rs:559-720   (defaults :236-255)
 //   DogLeg::optimize_with_mode        src/optimizer/dog_leg.rs:1143-1354      (defaults :353-399, state :725-745)
 // Gauss-Newton needs nothing LmBackend does not have: it is solve_augmented(0) (solve_normal_equation) with every step kept.
-// Dog-Leg needs one call more, dogleg_step; TrBackend adds it.  Both backends implement it: the pose-graph one (pg_solver.h) on
-// its sparse Cholesky, the bundle-adjustment one (solver.h) on the Schur solver -- the reference hands a DogLeg configured with
-// SparseSchurComplement a sparse Cholesky of the whole H + mu I (optimizer/mod.rs:681-693), which computes the same step.
+// Dog-Leg needs one call more, dogleg_step; TrBackend adds it.  TileBackend (tile_backend.h) implements it once for both device
+// backends: the pose-graph one (pg_solver.h) solves on its sparse Cholesky, the bundle-adjustment one (solver.h) on the Schur
+// solver -- the reference hands a DogLeg configured with SparseSchurComplement a sparse Cholesky of the whole H + mu I
+// (optimizer/mod.rs:681-693), which computes the same step.
 #pragma once
 #include "lm_loop.h"
 
@@ -61,7 +62,7 @@ struct DoglegStepInfo {
     double reused;                // 1: built from the cache
 };
 
-class TrBackend : public virtual LmBackend {
+class TrBackend : public LmBackend {
    public:
     // compute_optimization_step_generic (dog_leg.rs:963-1089) at radius, then the trial point and its cost, so that step_stats /
     // eval_step / commit_step / discard_step follow as after solve_augmented.

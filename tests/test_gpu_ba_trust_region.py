@@ -287,6 +287,10 @@ def test_reuse_needs_a_cache_that_is_still_valid():
         s.dogleg_step(1.0, 0.5, reuse=True)          # (the cache is there)
         void()
         assert kind_of(s.dogleg_step, 1.0, 0.25, reuse=True) == "InvalidState"
+    s.dogleg_step(1.0, 1.0)
+    s.dogleg_step(1.0, 0.5, reuse=True)
+    s.jv_gram(np.ones(P.n), np.arange(P.n, dtype=np.float64))   # the parity export prices two vectors of its own: the cache stays
+    assert s.dogleg_step(1.0, 0.25, reuse=True)["reused"]
     s.close()
     s = GpuSchurComplementSolver(0).initialize_structure(bt.device_problem(P))
     assert kind_of(s.dogleg_step, 1e-4, 1.0) == "InvalidState" and kind_of(s.jv_gram, np.zeros(P.n), np.zeros(P.n)) == "InvalidState"
@@ -298,12 +302,49 @@ def test_failed_factorisation_is_reported_without_the_ladder():
     mends that with its ladder (last_reg > 0); dogleg_step reports it, and the loop's answer is a larger mu."""
     d, _, delta, _ = bt.golden_data("ba6x40_selfcal")
     P = bt.BaProblem(d, OptimizationType.OnlyLandmarks, bt.huber(delta), bt.gauge(d))
-    s = device(P)
-    assert kind_of(s.dogleg_step, 0.0, 1.0) in ("FactorizationFailed", "SingularMatrix")
-    assert s.info()["last_reg"] == 0.0
-    assert kind_of(s.step_stats) == "InvalidState"
-    s.dogleg_step(1e-4, 1.0)
-    s.close()
+    kinds = []
+    for opts in (None, {"one_wait": 0}):   # the flags read at the solve's one wait, and right behind the factorisation
+        s = device(P, opts)
+        kinds.append(kind_of(s.dogleg_step, 0.0, 1.0))
+        assert kinds[-1] in ("FactorizationFailed", "SingularMatrix")
+        assert s.info()["last_reg"] == 0.0
+        assert kind_of(s.step_stats) == "InvalidState"
+        s.dogleg_step(1e-4, 1.0)
+        s.close()
+    assert kinds[0] == kinds[1]
+
+
+def test_dogleg_step_does_not_depend_on_one_wait():
+    """A fresh blended step and a reused one at half the radius, with the flags waited for where they are raised ("one_wait" 0:
+    Solver::solve_for_dogleg has a branch of its own for it) and with the one wait of the default.  Neither path has an atomic:
+    the step dictionaries, export_step and eval_step are the same bits."""
+    P = gram_problem("golden:ba6x40_selfcal")
+    tr._init_scaling(P, False)
+    H, g = P.normal_equations()
+    mu = bt.mu_for_condition(H)
+    h = tr.solve_damped(H, g, mu)
+    _, p_c = tr.cauchy_point(H, g)
+    hn, pn = np.linalg.norm(h), np.linalg.norm(p_c)
+    assert pn < hn, (pn, hn)
+    radius = 0.5 * (pn + hn)   # inside the Gauss-Newton norm, outside the Cauchy point: the leg is blended
+    runs = []
+    for opts in ({"one_wait": 0}, None):
+        s = device(P, opts)
+        fresh = s.dogleg_step(mu, radius)
+        assert fresh["step_type"] == tr.DOG_LEG and not fresh["reused"]
+        step_f, trial_f = s.export_step(), s.eval_step()
+        s.discard_step()
+        reused = s.dogleg_step(mu, 0.5 * radius, reuse=True)
+        assert reused["reused"]
+        step_r, trial_r = s.export_step(), s.eval_step()
+        s.close()
+        runs.append((fresh, step_f, trial_f, reused, step_r, trial_r))
+    off, on = runs
+    print("one_wait 0", off[0], off[3], "\n   default", on[0], on[3])
+    for i in (0, 2, 3, 5):
+        assert off[i] == on[i], (i, off[i], on[i])
+    for i in (1, 4):
+        assert np.array_equal(off[i][0], on[i][0]) and np.array_equal(off[i][1], on[i][1])
 
 
 # ---- LM is what it was ---------------------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@ import fixed_masks as fm
 import np_ref_trust_region as tr
 import tr_cases as tc
 from apex_solver_amd import capi
+from apex_solver_amd.loss import Loss
 from apex_solver_amd.pose_graph import DogLegConfig, GaussNewtonConfig, GpuSparseCholeskySolver, PoseGraphProblem
 from apex_solver_amd.solver import LevenbergMarquardtConfig
 from apex_solver_amd.synthetic import PoseGraphData
@@ -32,6 +33,12 @@ def solver(prob, poses):
     s = GpuSparseCholeskySolver(0).initialize_structure(prob)
     s.set_parameters(poses)
     return s
+
+
+def kind_of(call, *a, **k):
+    with pytest.raises(capi.LinAlgError) as e:
+        call(*a, **k)
+    return e.value.kind
 
 
 # ---- jv_gram -------------------------------------------------------------------------------------------------------------------
@@ -171,6 +178,85 @@ def test_reuse_after_a_rejected_step(man):
     r2 = s.dogleg_step(mu, 0.25 * radius, reuse=True)
     assert r2["reused"] and r2["gradient_norm"] == r["gradient_norm"]
     s.close()
+
+
+@pytest.mark.parametrize("man", MANIFOLDS)
+def test_reuse_needs_a_cache_that_is_still_valid(man):
+    """What voids the cached solve and what leaves it alone, call by call (the bundle-adjustment test of this name, on a pose graph)."""
+    prob, p0 = tc.problem(man)
+    n = prob.dof * prob.data.n_v
+    s = solver(prob, p0)
+    assert kind_of(s.dogleg_step, 1e-2, 1.0, reuse=True) == "InvalidState"     # before any fresh solve
+    rng = np.random.default_rng(7)
+    a, b = rng.normal(size=n), rng.normal(size=n)
+    voids = (lambda: s.set_parameters(p0), lambda: s.set_loss(Loss(capi.LOSS_HUBER, 1.0)), lambda: s.set_priors(prob.priors),
+             lambda: s.set_information(None), lambda: s.apply_column_scaling(np.full(n, 0.5)), lambda: s.apply_column_scaling(None),
+             lambda: s.solve_augmented_equation(1e-3), lambda: s.get_hessian(0.0), lambda: s.compute_column_norms())
+    for void in voids:
+        s.dogleg_step(1e-2, 1.0)
+        assert s.dogleg_step(1e-2, 0.5, reuse=True)["reused"]          # (the cache is there)
+        void()
+        assert kind_of(s.dogleg_step, 1e-2, 0.25, reuse=True) == "InvalidState"
+    keeps = (lambda: s.jv_gram(a, b), lambda: (s.eval_step(), s.discard_step()), lambda: (s.eval_step(), s.commit_step()))
+    for keep in keeps:
+        s.set_parameters(p0)
+        s.dogleg_step(1e-2, 1.0)
+        assert s.dogleg_step(1e-2, 0.5, reuse=True)["reused"]
+        keep()
+        assert s.dogleg_step(1e-2, 0.25, reuse=True)["reused"]
+    s.close()
+
+
+@pytest.mark.parametrize("man", MANIFOLDS)
+def test_dogleg_step_does_not_depend_on_one_wait(man):
+    """A fresh blended step and a reused one at half the radius, with the flags waited for where they are raised ("one_wait" 0)
+    and with the one wait of the default: SE2 has no atomics on either path and is held to the same bits; SE3 scatters its
+    assembly with fp64 atomics and is held to this file's bounds (step 1e-10, scalars 1e-9).  The pose-graph surface has no
+    export_step: the step is compared as the parameters it leaves behind a commit."""
+    prob, p0 = tc.problem(man)
+    mu = 1.0   # (cond(H + mu I) <= 1e5 in the plain variables, as test_dogleg_step_of_every_type_against_numpy has it)
+    P, H, g, D, h, alpha, p_c = tc.first_linearisation(prob, p0, False, mu)
+    hn, pn = np.linalg.norm(h), np.linalg.norm(p_c)
+    assert np.linalg.cond(H + mu * np.eye(P.n)) <= 1e5 and pn < hn, (pn, hn)
+    radius = 0.5 * (pn + hn)   # inside the Gauss-Newton norm, outside the Cauchy point: the leg is blended
+    runs = []
+    for opts in ({"one_wait": 0}, {}):
+        s = GpuSparseCholeskySolver(0)
+        for k, v in opts.items():
+            s.with_option(k, v)
+        s.initialize_structure(prob)
+        s.set_parameters(p0)
+        fresh = s.dogleg_step(mu, radius)
+        assert fresh["step_type"] == tr.DOG_LEG and not fresh["reused"]
+        stats_f, trial_f = s.step_stats(), s.eval_step()
+        s.commit_step()
+        after_f = s.get_parameters()
+        s.set_parameters(p0)
+        s.dogleg_step(mu, radius)
+        s.eval_step(); s.discard_step()
+        reused = s.dogleg_step(mu, 0.5 * radius, reuse=True)
+        assert reused["reused"]
+        stats_r, trial_r = s.step_stats(), s.eval_step()
+        s.commit_step()
+        after_r = s.get_parameters()
+        s.close()
+        runs.append((fresh, stats_f, trial_f, after_f, reused, stats_r, trial_r, after_r))
+    off, on = runs
+    print(man, "one_wait 0", off[0], off[4], "\n   default", on[0], on[4])
+    if man == "se2":
+        for x, y in zip(off, on):
+            assert np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y, (x, y)
+        return
+    for i in (0, 4):      # the step dictionaries
+        assert off[i]["step_type"] == on[i]["step_type"] and off[i]["reused"] == on[i]["reused"]
+        for k in ("gradient_norm", "step_norm", "predicted_reduction", "alpha", "beta", "scaled_step_norm"):
+            assert off[i][k] == pytest.approx(on[i][k], rel=1e-9), (i, k)
+    for i in (1, 5):      # step_stats
+        assert off[i] == pytest.approx(on[i], rel=1e-9)
+    for i in (2, 6):      # eval_step
+        assert off[i] == pytest.approx(on[i], rel=1e-9)
+    for i in (3, 7):      # the applied step
+        assert rel(tc.applied_step(prob, p0, off[i]), tc.applied_step(prob, p0, on[i])) < 1e-10
 
 
 # ---- histories -----------------------------------------------------------------------------------------------------------------
