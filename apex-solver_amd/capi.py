@@ -45,6 +45,8 @@ SYMBOLS = (
     # SE2 pose graphs: the same handle, two more lifetime calls, the SE2 content of a G2O file
     "apexgpu_pg_create_se2", "apexgpu_pg_manifold", "apexgpu_g2o_raw_se2", "apexgpu_g2o_problem_se2",
     "apexgpu_pose_graph_columns_se2",
+    # SO3 pose graphs (rotation averaging)
+    "apexgpu_pg_create_so3",
     # Gauss-Newton and Dog-Leg on pose graphs
     "apexgpu_pg_jv_gram", "apexgpu_pg_dogleg_step", "apexgpu_pg_gn_optimize", "apexgpu_pg_dogleg_optimize",
     # Dog-Leg on bundle adjustment
@@ -54,7 +56,9 @@ SYMBOLS = (
     # edge information matrices on pose graphs
     "apexgpu_pg_set_information", "apexgpu_pg_get_information", "apexgpu_g2o_problem_information",
 )
-MANIFOLD_SE3, MANIFOLD_SE2 = 0, 1
+MANIFOLD_SE3, MANIFOLD_SE2, MANIFOLD_SO3 = 0, 1, 2
+# (ambient, dof) per APEXGPU_MANIFOLD_*: stored doubles per vertex / measurement / prior, tangent columns per vertex
+MANIFOLD_SIZES = {MANIFOLD_SE3: (7, 6), MANIFOLD_SE2: (3, 3), MANIFOLD_SO3: (4, 3)}
 # APEXGPU_LOSS_* of include/apexgpu.h, in value order
 LOSS_KINDS = ("NONE", "L2", "L1", "HUBER", "CAUCHY", "FAIR", "GEMAN_MCCLURE", "WELSCH", "TUKEY", "ANDREWS", "RAMSAY",
               "TRIMMED_MEAN", "LP_NORM", "BARRON", "T_DISTRIBUTION")
@@ -274,6 +278,7 @@ def load() -> C.CDLL:
     L.apexgpu_g2o_problem.argtypes = [vp] * 8
     L.apexgpu_pose_graph_columns.argtypes = [i64, vp, vp]
     L.apexgpu_pg_create_se2.argtypes = [i64, i64, C.c_int, C.POINTER(vp)]
+    L.apexgpu_pg_create_so3.argtypes = [i64, i64, C.c_int, C.POINTER(vp)]
     L.apexgpu_pg_manifold.argtypes = [vp, C.POINTER(C.c_int * 3)]
     L.apexgpu_g2o_raw_se2.argtypes = [vp] * 7
     L.apexgpu_g2o_problem_se2.argtypes = [vp] * 8
@@ -520,13 +525,16 @@ class PgHandle:
     def __init__(self, n_vertices: int, n_edges: int, device: int = 0, manifold: int = MANIFOLD_SE3):
         self.L = load()
         self.h = C.c_void_p()
-        create = self.L.apexgpu_pg_create_se2 if manifold == MANIFOLD_SE2 else self.L.apexgpu_pg_create
+        if manifold not in MANIFOLD_SIZES:
+            raise ValueError(f"unknown manifold {manifold!r}")
+        create = {MANIFOLD_SE3: self.L.apexgpu_pg_create, MANIFOLD_SE2: self.L.apexgpu_pg_create_se2,
+                  MANIFOLD_SO3: self.L.apexgpu_pg_create_so3}[manifold]
         rc = create(n_vertices, n_edges, device, C.byref(self.h))
         if rc != 0:
             raise LinAlgError(rc, "apexgpu_pg_create failed (no MI355X visible to HIP?)")
         self.n_vertices, self.n_edges = n_vertices, n_edges
         self.manifold = manifold
-        self.ambient, self.dof = (3, 3) if manifold == MANIFOLD_SE2 else (7, 6)
+        self.ambient, self.dof = MANIFOLD_SIZES[manifold]   # SO3: 4-wide poses / measurements / priors, 3-wide steps and masks
 
     def check(self, rc: int):
         if rc != 0:

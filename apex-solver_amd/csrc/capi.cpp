@@ -777,7 +777,7 @@ int apexgpu_debug_invert_blocks(int device, int64_t n, const double* blocks9, do
 }
 
 
-/* ---- pose-graph backend (SE3, SE2) --------------------------------------------------------------------- */
+/* ---- pose-graph backend (SE3, SE2, SO3) --------------------------------------------------------------------- */
 #define PG_OR_FAIL \
     if (!h || !h->s) return APEXGPU_ERR_INVALID_STATE
 
@@ -798,6 +798,9 @@ int apexgpu_pg_create(int64_t n_vertices, int64_t n_edges, int device, apexgpu_p
 }
 int apexgpu_pg_create_se2(int64_t n_vertices, int64_t n_edges, int device, apexgpu_pg_solver** out) {
     return pg_create(n_vertices, n_edges, device, APEXGPU_MANIFOLD_SE2, out);
+}
+int apexgpu_pg_create_so3(int64_t n_vertices, int64_t n_edges, int device, apexgpu_pg_solver** out) {
+    return pg_create(n_vertices, n_edges, device, APEXGPU_MANIFOLD_SO3, out);
 }
 int apexgpu_pg_manifold(const apexgpu_pg_solver* h, int out3[3]) {
     PG_OR_FAIL;

@@ -165,10 +165,10 @@ APEX_HD void between2_linearize(const double* __restrict__ k0, const double* __r
     m3_mul(Jl, C, J1);
 }
 
+// ---- the loss correction of one 3-row block (r, J0, J1 row-major 3 x 3): what every 3-DOF manifold shares once its own
+// linearisation has filled the block (SE2 here, SO3 in pg_so3_device.hpp) ---------------------------------------------------
 // r and both Jacobians scaled by sqrt(rho') of the block's loss (pg_huber_scale; corrector.rs:143-181)
-APEX_HD void between2_corrected(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
-                                double huber_delta, double r[3], double J0[9], double J1[9]) {
-    between2_linearize(k0, k1, m, r, J0, J1);
+APEX_HD void block3_correct(double huber_delta, double r[3], double J0[9], double J1[9]) {
     const double sc = pg_huber_scale(huber_delta, r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
     if (sc != 1.0) {
 #pragma unroll
@@ -182,9 +182,7 @@ APEX_HD void between2_corrected(const double* __restrict__ k0, const double* __r
 // First arm: the lines above with
 // sqrt(rho').  Second arm, literally (corrector.rs:241-253, 292-298): r~ = residual_scaling r, J~ = sqrt(rho') (J - a r r^T J).
 // false: rho' = 0, the edge contributes nothing; r, J0, J1 are zero.
-APEX_HD bool between2_corrected(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
-                                const PgLoss& loss, double r[3], double J0[9], double J1[9]) {
-    between2_linearize(k0, k1, m, r, J0, J1);
+APEX_HD bool block3_correct(const PgLoss& loss, double r[3], double J0[9], double J1[9]) {
     const PgCorrector c = pg_loss_corrector(loss, r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
     const double sc = c.sqrt_rho1;
     if (sc == 0.0) {
@@ -219,6 +217,18 @@ APEX_HD bool between2_corrected(const double* __restrict__ k0, const double* __r
 #pragma unroll
     for (int i = 0; i < 3; ++i) r[i] *= c.residual_scaling;
     return true;
+}
+
+// one SE2 edge, linearised and corrected under either loss form
+APEX_HD void between2_corrected(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                                double huber_delta, double r[3], double J0[9], double J1[9]) {
+    between2_linearize(k0, k1, m, r, J0, J1);
+    block3_correct(huber_delta, r, J0, J1);
+}
+APEX_HD bool between2_corrected(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                                const PgLoss& loss, double r[3], double J0[9], double J1[9]) {
+    between2_linearize(k0, k1, m, r, J0, J1);
+    return block3_correct(loss, r, J0, J1);
 }
 
 // H += A^T B (3 x 3 row-major), g += A^T r
@@ -259,23 +269,25 @@ APEX_HD void se2_plus(const double* __restrict__ v3, const double d[3], double* 
 // self-loop listed once (pg2_lists.h).  Every edge of the list is re-linearised; H_vv and g_v accumulate in registers in
 // list order; for an other endpoint u < v the block J_v^T J_u goes to add_off(u, B) -- blocks (v, u) with u < v are touched
 // by the owner of row v only, so a plain read-add-write there has no race and duplicate edges sum in list order.
-template <typename AddOff, typename LossParam>
-APEX_HD void pg2_assemble_row(uint32_t v, const double* __restrict__ posep, const double* __restrict__ meas,
-                              const uint32_t* __restrict__ e_from, const uint32_t* __restrict__ e_to,
-                              const int* __restrict__ inc_ptr, const uint32_t* __restrict__ inc_edge, const LossParam& loss,
-                              double Hvv[9], double gv[3], AddOff add_off) {
+// M: a manifold with 3 tangent DOF (Se2Manifold below | So3Manifold of pg_so3_device.hpp); what it contributes is
+// M::linearize on prepared poses of M::kStride doubles, everything after that is 3 x 3 blocks.
+template <class M, typename AddOff, typename LossParam>
+APEX_HD void pg_row_assemble(uint32_t v, const double* __restrict__ posep, const double* __restrict__ meas,
+                             const uint32_t* __restrict__ e_from, const uint32_t* __restrict__ e_to,
+                             const int* __restrict__ inc_ptr, const uint32_t* __restrict__ inc_edge, const LossParam& loss,
+                             double Hvv[9], double gv[3], AddOff add_off) {
+    static_assert(M::kDof == 3, "the row-owned assembly is written for 3 x 3 blocks");
 #pragma unroll
     for (int i = 0; i < 9; ++i) Hvv[i] = 0.0;
     gv[0] = gv[1] = gv[2] = 0.0;
     for (int k = inc_ptr[v]; k < inc_ptr[v + 1]; ++k) {
         const uint32_t e = inc_edge[k], a = e_from[e], b = e_to[e];
         double r[3], J0[9], J1[9];
+        M::linearize(posep + M::kStride * (size_t)a, posep + M::kStride * (size_t)b, meas + M::kStride * (size_t)e, r, J0, J1);
         if constexpr (std::is_same<LossParam, PgLoss>::value) {   // (an edge with rho' = 0 is skipped)
-            if (!between2_corrected(posep + kPose2Stride * (size_t)a, posep + kPose2Stride * (size_t)b,
-                                    meas + kPose2Stride * (size_t)e, loss, r, J0, J1)) continue;
+            if (!block3_correct(loss, r, J0, J1)) continue;
         } else {
-            between2_corrected(posep + kPose2Stride * (size_t)a, posep + kPose2Stride * (size_t)b, meas + kPose2Stride * (size_t)e,
-                               loss, r, J0, J1);
+            block3_correct(loss, r, J0, J1);
         }
         if (a == b) {   // self-loop: both Jacobians hit the same columns
 #pragma unroll
@@ -304,9 +316,8 @@ APEX_HD void pg2_assemble_row(uint32_t v, const double* __restrict__ posep, cons
 //     r^ = residual_scaling r,   J^ = sqrt(rho') (J - a r (Omega r)^T J),   s = r^T Omega r
 // so that the whitened block is r~ = U r^, J~ = U J^ and every product closes with Omega: J~_a^T J~_b = J^_a^T Omega J^_b,
 // J~_v^T r~ = J^_v^T Omega r^.  The hot kernels need Omega only.  false: rho' = 0, the edge contributes nothing; r, J0, J1 are zero.
-APEX_HD bool between2_weighted(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
-                               const PgLoss& loss, const double* __restrict__ W, double r[3], double J0[9], double J1[9]) {
-    between2_linearize(k0, k1, m, r, J0, J1);
+// (block3_weight: the correction alone, on a block any 3-DOF manifold has linearised)
+APEX_HD bool block3_weight(const PgLoss& loss, const double* __restrict__ W, double r[3], double J0[9], double J1[9]) {
     double Wr[3];
     info_mv<3>(W, r, Wr);
     const PgCorrector c = pg_loss_corrector(loss, fmax(dotn<3>(r, Wr), 0.0));
@@ -336,6 +347,11 @@ APEX_HD bool between2_weighted(const double* __restrict__ k0, const double* __re
     for (int i = 0; i < 3; ++i) r[i] *= c.residual_scaling;
     return true;
 }
+APEX_HD bool between2_weighted(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                               const PgLoss& loss, const double* __restrict__ W, double r[3], double J0[9], double J1[9]) {
+    between2_linearize(k0, k1, m, r, J0, J1);
+    return block3_weight(loss, W, r, J0, J1);
+}
 
 // M = Omega J (3 x 3 row-major)
 APEX_HD void info_mul3(const double* __restrict__ W, const double* __restrict__ J, double* __restrict__ M) {
@@ -349,11 +365,12 @@ APEX_HD void info_mul3(const double* __restrict__ W, const double* __restrict__ 
 // caller's edge order).  Row-owned like pg2_assemble_row: the same lists, the same order of summation, no atomics.  The block
 // of row v and column u is J^_v^T (Omega J^_u) -- Omega sits between the two Jacobians, so the block of (u, v) is its transpose
 // and not the same product with the roles swapped.
-template <typename AddOff>
-APEX_HD void pg2_assemble_row_info(uint32_t v, const double* __restrict__ posep, const double* __restrict__ meas,
-                                   const uint32_t* __restrict__ e_from, const uint32_t* __restrict__ e_to,
-                                   const int* __restrict__ inc_ptr, const uint32_t* __restrict__ inc_edge,
-                                   const double* __restrict__ info, const PgLoss& loss, double Hvv[9], double gv[3], AddOff add_off) {
+template <class Man, typename AddOff>   // (Man: M is the block Omega J below)
+APEX_HD void pg_row_assemble_info(uint32_t v, const double* __restrict__ posep, const double* __restrict__ meas,
+                                  const uint32_t* __restrict__ e_from, const uint32_t* __restrict__ e_to,
+                                  const int* __restrict__ inc_ptr, const uint32_t* __restrict__ inc_edge,
+                                  const double* __restrict__ info, const PgLoss& loss, double Hvv[9], double gv[3], AddOff add_off) {
+    static_assert(Man::kDof == 3, "the row-owned assembly is written for 3 x 3 blocks");
 #pragma unroll
     for (int i = 0; i < 9; ++i) Hvv[i] = 0.0;
     gv[0] = gv[1] = gv[2] = 0.0;
@@ -361,8 +378,8 @@ APEX_HD void pg2_assemble_row_info(uint32_t v, const double* __restrict__ posep,
         const uint32_t e = inc_edge[k], a = e_from[e], b = e_to[e];
         double W[9], r[3], Wr[3], J0[9], J1[9];
         info_unpack<3>(info + InfoPack<3>::kStride * (size_t)e, W);
-        if (!between2_weighted(posep + kPose2Stride * (size_t)a, posep + kPose2Stride * (size_t)b, meas + kPose2Stride * (size_t)e,
-                               loss, W, r, J0, J1)) continue;
+        Man::linearize(posep + Man::kStride * (size_t)a, posep + Man::kStride * (size_t)b, meas + Man::kStride * (size_t)e, r, J0, J1);
+        if (!block3_weight(loss, W, r, J0, J1)) continue;
         info_mv<3>(W, r, Wr);
         double M[9];
         if (a == b) {   // self-loop: both Jacobians hit the same columns
@@ -390,11 +407,73 @@ APEX_HD void pg2_assemble_row_info(uint32_t v, const double* __restrict__ posep,
     }
 }
 
+// The per-edge members of a 3-DOF manifold trait that need nothing but its linearisation: D::linearize(k0, k1, m, r, J0, J1)
+// fills the uncorrected block, and the loss, the information matrix, the products and the exports are 3 x 3 from there on.
+// Se2Manifold and So3Manifold (pg_so3_device.hpp) derive from it (D is the deriving trait).
+template <class D>
+struct Dof3EdgeOps {
+    // u = J~0 a0 + J~1 a1, w = J~0 b0 + J~1 b1 for the corrected Jacobians of one edge (the linearisation of pg_row_assemble:
+    // D::linearize, then block3_correct); a0 / b0: the three tangent entries of k0's vertex, a1 / b1 of k1's
+    template <typename LossParam>
+    static APEX_HD void edge_jv(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m, const LossParam& loss,
+                                const double a0[3], const double a1[3], const double b0[3], const double b1[3], double u[3], double w[3]) {
+        double r[3], J0[9], J1[9];
+        D::linearize(k0, k1, m, r, J0, J1);
+        (void)block3_correct(loss, r, J0, J1);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            u[i] = (J0[3 * i] * a0[0] + J0[3 * i + 1] * a0[1] + J0[3 * i + 2] * a0[2]) + (J1[3 * i] * a1[0] + J1[3 * i + 1] * a1[1] + J1[3 * i + 2] * a1[2]);
+            w[i] = (J0[3 * i] * b0[0] + J0[3 * i + 1] * b0[1] + J0[3 * i + 2] * b0[2]) + (J1[3 * i] * b1[0] + J1[3 * i + 1] * b1[1] + J1[3 * i + 2] * b1[2]);
+        }
+    }
+    // With Omega (LossWeighted): u = J^0 a0 + J^1 a1, w = J^0 b0 + J^1 b1 for the corrected, not whitened Jacobians of
+    // block3_weight; the caller closes the products with Omega: (J~ a).(J~ b) = u^T Omega w.
+    static APEX_HD void edge_jv_info(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m, const PgLoss& loss,
+                                     const double* __restrict__ W, const double a0[3], const double a1[3], const double b0[3], const double b1[3],
+                                     double u[3], double w[3]) {
+        double r[3], J0[9], J1[9];
+        D::linearize(k0, k1, m, r, J0, J1);
+        (void)block3_weight(loss, W, r, J0, J1);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            u[i] = (J0[3 * i] * a0[0] + J0[3 * i + 1] * a0[1] + J0[3 * i + 2] * a0[2]) + (J1[3 * i] * a1[0] + J1[3 * i + 1] * a1[1] + J1[3 * i + 2] * a1[2]);
+            w[i] = (J0[3 * i] * b0[0] + J0[3 * i + 1] * b0[1] + J0[3 * i + 2] * b0[2]) + (J1[3 * i] * b1[0] + J1[3 * i + 1] * b1[1] + J1[3 * i + 2] * b1[2]);
+        }
+    }
+    // the literal whitened, corrected residual [3] and Jacobian [3][6] of one edge (info_export_block: factors Omega here)
+    static APEX_HD void export_edge_info(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                                         const PgLoss& loss, const double* __restrict__ W, double* __restrict__ r_out, double* __restrict__ j_out) {
+        double r[3], J0[9], J1[9], Jd[18];
+        D::linearize(k0, k1, m, r, J0, J1);
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) { Jd[6 * i + j] = J0[3 * i + j]; Jd[6 * i + 3 + j] = J1[3 * i + j]; }
+        info_export_block<3>(W, loss, r, Jd, r_out, j_out);
+    }
+    // corrected residual [3] and Jacobian [3][6] = [dr/dk0 | dr/dk1] of one edge (either may be null); sqrt(rho') is
+    // applied inside block3_correct
+    template <typename LossParam>
+    static APEX_HD void export_edge(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                                    const LossParam& loss, double* __restrict__ r_out, double* __restrict__ j_out) {
+        double r[3], J0[9], J1[9];
+        D::linearize(k0, k1, m, r, J0, J1);
+        (void)block3_correct(loss, r, J0, J1);
+        if (r_out)
+            for (int i = 0; i < 3; ++i) r_out[i] = r[i];
+        if (j_out)
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    j_out[6 * i + j] = J0[3 * i + j];
+                    j_out[6 * i + 3 + j] = J1[3 * i + j];
+                }
+    }
+};
+
 // The SE2 side of the trait pg_device.hpp describes at Se3Manifold.
-struct Se2Manifold {
+struct Se2Manifold : Dof3EdgeOps<Se2Manifold> {
     static constexpr int kDof = 3;                 // tangent columns per vertex
     static constexpr int kAmb = 3;                 // stored doubles per vertex / measurement / prior: x y theta
-    static constexpr int kStride = kPose2Stride;   // doubles per prepared pose / measurement (x y cos sin) / prior block
+    static constexpr int kStride = kPose2Stride;   // doubles per prepared pose / measurement (x y cos sin)
+    static constexpr int kPriorStride = kStride;   // doubles per prior block: data (kAmb) | the block's Huber delta
     static constexpr bool kPriorOnPrepared = false;   // the prior sees [x, y, theta] itself
 
     static APEX_HD void prepare(const double* __restrict__ v, double* __restrict__ o) { se2_prepare(v, o); }
@@ -409,57 +488,26 @@ struct Se2Manifold {
     static APEX_HD double cost_add_prior(double acc, const double r[3]) {   // the block's squared norm first, then one add
         return acc + (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
     }
-    // u = J~0 a0 + J~1 a1, w = J~0 b0 + J~1 b1 for the corrected Jacobians of one edge (the linearisation of pg2_assemble_row:
-    // between2_corrected); a0 / b0: the three tangent entries of k0's vertex, a1 / b1 of k1's
-    template <typename LossParam>
-    static APEX_HD void edge_jv(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m, const LossParam& loss,
-                                const double a0[3], const double a1[3], const double b0[3], const double b1[3], double u[3], double w[3]) {
-        double r[3], J0[9], J1[9];
-        (void)between2_corrected(k0, k1, m, loss, r, J0, J1);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            u[i] = (J0[3 * i] * a0[0] + J0[3 * i + 1] * a0[1] + J0[3 * i + 2] * a0[2]) + (J1[3 * i] * a1[0] + J1[3 * i + 1] * a1[1] + J1[3 * i + 2] * a1[2]);
-            w[i] = (J0[3 * i] * b0[0] + J0[3 * i + 1] * b0[1] + J0[3 * i + 2] * b0[2]) + (J1[3 * i] * b1[0] + J1[3 * i + 1] * b1[1] + J1[3 * i + 2] * b1[2]);
-        }
-    }
-    // With Omega (LossWeighted): u = J^0 a0 + J^1 a1, w = J^0 b0 + J^1 b1 for the corrected, not whitened Jacobians of
-    // between2_weighted; the caller closes the products with Omega: (J~ a).(J~ b) = u^T Omega w.
-    static APEX_HD void edge_jv_info(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m, const PgLoss& loss,
-                                     const double* __restrict__ W, const double a0[3], const double a1[3], const double b0[3], const double b1[3],
-                                     double u[3], double w[3]) {
-        double r[3], J0[9], J1[9];
-        (void)between2_weighted(k0, k1, m, loss, W, r, J0, J1);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            u[i] = (J0[3 * i] * a0[0] + J0[3 * i + 1] * a0[1] + J0[3 * i + 2] * a0[2]) + (J1[3 * i] * a1[0] + J1[3 * i + 1] * a1[1] + J1[3 * i + 2] * a1[2]);
-            w[i] = (J0[3 * i] * b0[0] + J0[3 * i + 1] * b0[1] + J0[3 * i + 2] * b0[2]) + (J1[3 * i] * b1[0] + J1[3 * i + 1] * b1[1] + J1[3 * i + 2] * b1[2]);
-        }
-    }
-    // the literal whitened, corrected residual [3] and Jacobian [3][6] of one edge (info_export_block: factors Omega here)
-    static APEX_HD void export_edge_info(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
-                                         const PgLoss& loss, const double* __restrict__ W, double* __restrict__ r_out, double* __restrict__ j_out) {
-        double r[3], J0[9], J1[9], Jd[18];
+    static APEX_HD void linearize(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
+                                  double r[3], double J0[9], double J1[9]) {
         between2_linearize(k0, k1, m, r, J0, J1);
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) { Jd[6 * i + j] = J0[3 * i + j]; Jd[6 * i + 3 + j] = J1[3 * i + j]; }
-        info_export_block<3>(W, loss, r, Jd, r_out, j_out);
-    }
-    // corrected residual [3] and Jacobian [3][6] = [dr/dk0 | dr/dk1] of one edge (either may be null); sqrt(rho') is
-    // applied inside between2_corrected
-    template <typename LossParam>
-    static APEX_HD void export_edge(const double* __restrict__ k0, const double* __restrict__ k1, const double* __restrict__ m,
-                                    const LossParam& loss, double* __restrict__ r_out, double* __restrict__ j_out) {
-        double r[3], J0[9], J1[9];
-        (void)between2_corrected(k0, k1, m, loss, r, J0, J1);
-        if (r_out)
-            for (int i = 0; i < 3; ++i) r_out[i] = r[i];
-        if (j_out)
-            for (int i = 0; i < 3; ++i)
-                for (int j = 0; j < 3; ++j) {
-                    j_out[6 * i + j] = J0[3 * i + j];
-                    j_out[6 * i + 3 + j] = J1[3 * i + j];
-                }
     }
 };
+
+// The SE2 instantiations under the names they have always had (tests/host_harness_se2.cpp, host_harness_loss.cpp, host_harness_info.cpp)
+template <typename AddOff, typename LossParam>
+APEX_HD void pg2_assemble_row(uint32_t v, const double* __restrict__ posep, const double* __restrict__ meas,
+                              const uint32_t* __restrict__ e_from, const uint32_t* __restrict__ e_to,
+                              const int* __restrict__ inc_ptr, const uint32_t* __restrict__ inc_edge, const LossParam& loss,
+                              double Hvv[9], double gv[3], AddOff add_off) {
+    pg_row_assemble<Se2Manifold>(v, posep, meas, e_from, e_to, inc_ptr, inc_edge, loss, Hvv, gv, add_off);
+}
+template <typename AddOff>
+APEX_HD void pg2_assemble_row_info(uint32_t v, const double* __restrict__ posep, const double* __restrict__ meas,
+                                   const uint32_t* __restrict__ e_from, const uint32_t* __restrict__ e_to,
+                                   const int* __restrict__ inc_ptr, const uint32_t* __restrict__ inc_edge,
+                                   const double* __restrict__ info, const PgLoss& loss, double Hvv[9], double gv[3], AddOff add_off) {
+    pg_row_assemble_info<Se2Manifold>(v, posep, meas, e_from, e_to, inc_ptr, inc_edge, info, loss, Hvv, gv, add_off);
+}
 
 }  // namespace apex

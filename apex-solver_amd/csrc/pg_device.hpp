@@ -57,15 +57,19 @@ APEX_HD void hat_mul(const double t[3], const double* R, double* C) {
 
 // pose as the kernels hold it: translation + unit quaternion [w,x,y,z] (k_pg_prepare normalises twice,
 // like SE3::from(DVector), se3.rs:107-113, 200-206)
-APEX_HD void pose_normalise(const double* __restrict__ v7, double* __restrict__ o7) {
-    o7[0] = v7[0]; o7[1] = v7[1]; o7[2] = v7[2];
-    double w = v7[3], x = v7[4], y = v7[5], z = v7[6];
+// (the quaternion's two passes stand alone so that an SO3 vertex with the same quaternion prepares to the same bits, pg_so3_device.hpp)
+APEX_HD void quat_normalise_twice(const double* __restrict__ q4, double* __restrict__ o4) {
+    double w = q4[0], x = q4[1], y = q4[2], z = q4[3];
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
         const double n = sqrt(w * w + x * x + y * y + z * z);
         w /= n; x /= n; y /= n; z /= n;
     }
-    o7[3] = w; o7[4] = x; o7[5] = y; o7[6] = z;
+    o4[0] = w; o4[1] = x; o4[2] = y; o4[3] = z;
+}
+APEX_HD void pose_normalise(const double* __restrict__ v7, double* __restrict__ o7) {
+    o7[0] = v7[0]; o7[1] = v7[1]; o7[2] = v7[2];
+    quat_normalise_twice(v7 + 3, o7 + 3);
 }
 
 // a^-1 for a = (t, q)
@@ -445,12 +449,13 @@ APEX_HD double prior_eval(const double* __restrict__ x7, const double* __restric
 }
 
 // What the manifold-generic kernels of pg_kernels.hip know about a vertex type: three sizes and forwarders to the math
-// above.  Se2Manifold (pg2_device.hpp) is the other one.  Each manifold keeps its own order of operations behind these
+// above.  Se2Manifold (pg2_device.hpp) and So3Manifold (pg_so3_device.hpp) are the others.  Each manifold keeps its own order of operations behind these
 // names -- where the Huber factor is applied, how a prior's squares are added -- because the bits depend on it.
 struct Se3Manifold {
     static constexpr int kDof = 6;      // tangent columns per vertex
     static constexpr int kAmb = 7;      // stored doubles per vertex / measurement / prior: t(3) q(4)
-    static constexpr int kStride = 8;   // doubles per prepared pose / measurement / prior block: t(3) q(4) pad
+    static constexpr int kStride = 8;   // doubles per prepared pose / measurement: t(3) q(4) pad
+    static constexpr int kPriorStride = kStride;   // doubles per prior block: data (kAmb) | the block's Huber delta
     static constexpr bool kPriorOnPrepared = true;   // the prior sees the normalised pose
 
     static APEX_HD void prepare(const double* __restrict__ v, double* __restrict__ o) { pose_normalise(v, o); }

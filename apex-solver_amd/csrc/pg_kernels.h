@@ -1,5 +1,5 @@
 // pg_kernels.h -- launchers of the pose-graph kernels (pg_kernels.hip; BASELINE.json configs[1]).  Every launcher that
-// depends on what a vertex is takes the manifold and picks the instantiation (Se3Manifold | Se2Manifold) itself.
+// depends on what a vertex is takes the manifold and picks the instantiation (Se3Manifold | Se2Manifold | So3Manifold) itself.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,24 +9,29 @@
 
 namespace apex {
 
-enum PgManifold { kManifoldSE3 = 0, kManifoldSE2 = 1 };
+enum PgManifold { kManifoldSE3 = 0, kManifoldSE2 = 1, kManifoldSO3 = 2 };
+// The 3-DOF manifolds (48 vertices per tile) are assembled row-owned over the incident-edge lists of pg2_lists.h, with their
+// prior blocks sorted by vertex; SE3 is assembled edge-major with atomics.
+inline bool pg_row_owned(int manifold) { return manifold == kManifoldSE2 || manifold == kManifoldSO3; }
 
-// Read-only view of one parameter set + the edge list (internal vertex numbering).  Sizes per manifold (SE3 | SE2):
-// amb = 7 | 3 stored doubles per vertex, stride = 8 | 4 doubles per prepared pose, measurement and prior block.
+// Read-only view of one parameter set + the edge list (internal vertex numbering).  Sizes per manifold (SE3 | SE2 | SO3):
+// amb = 7 | 3 | 4 stored doubles per vertex, stride = 8 | 4 | 4 doubles per prepared pose and measurement, prior stride =
+// 8 | 4 | 6 doubles per prior block.
 struct PGView {
     int64_t n_v, n_e;
-    const double* posep;     // [n_v][stride] prepared poses: t, unit quaternion, pad | x y cos sin
+    const double* posep;     // [n_v][stride] prepared poses: t, unit quaternion, pad | x y cos sin | unit quaternion
     const uint32_t* e_from;  // [n_e] k0 of BetweenFactor
     const uint32_t* e_to;    // [n_e] k1
     const double* meas;      // [n_e][stride] prepared measurements
     double huber_delta;      // <= 0: no loss function
     // PriorFactor blocks (prior_factor.rs:96-108): r = to_vector(x_v) - data, amb rows.  SE3: the caller's order, x_v the
-    // prepared pose, J = the first six columns of I7.  SE2: sorted by vertex (stable), x_v = [x, y, theta], J = I3.
+    // prepared pose, J = the first six columns of I7.  SE2: sorted by vertex (stable), x_v = [x, y, theta], J = I3.  SO3: sorted
+    // by vertex (stable), x_v the prepared quaternion, J = the first three columns of I4.
     int n_prior = 0;
     const uint32_t* prior_v = nullptr;    // [n_prior] vertex (device order)
-    const double* prior_data = nullptr;   // [n_prior][stride]: data (amb) | the block's Huber delta (<= 0: none)
-    // SE2 only (null for SE3)
-    const double* poses = nullptr;        // [n_v][3] x y theta (what the prior sees)
+    const double* prior_data = nullptr;   // [n_prior][prior stride]: data (amb) | the block's Huber delta (<= 0: none)
+    // the row-owned manifolds only (null for SE3)
+    const double* poses = nullptr;        // [n_v][amb] the stored vertices (what an SE2 prior sees: x y theta)
     const int* inc_ptr = nullptr;         // [n_v + 1] incident-edge CSR of the row-owned assembly (pg2_lists.h)
     const uint32_t* inc_edge = nullptr;
     const int* prior_slot = nullptr;      // [n_prior] the caller's index of the block (export order)
@@ -49,7 +54,7 @@ void launch_pg_prepare(int manifold, int64_t n, const double* poses, double* pos
 // H (tiles, lower triangle) += J^T J, g += J^T r over the edges, then the prior blocks' J^T J (sc^2 on the diagonal entries
 // of the vertex) and J^T r; tiles and g zeroed by the caller.  Two launches, and two algorithms:
 //   SE3  k_pg_edges + k_pg_priors      edge-major, fp64 atomics, priors in the caller's order
-//   SE2  k_pg2_assemble + k_pg2_priors row-owned, no atomics, a fixed order of summation per destination
+//   SE2, SO3  k_pg2_assemble + k_pg2_priors row-owned, no atomics, a fixed order of summation per destination
 void launch_pg_assemble(int manifold, const PGView& v, const TileMap& tm, double* g, hipStream_t s);
 // corrected prior residuals [n_prior][amb], the caller's order
 void launch_pg_prior_export(int manifold, const PGView& v, double* r_out, hipStream_t s);

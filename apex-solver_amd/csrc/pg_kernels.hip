@@ -1,7 +1,7 @@
 // pg_kernels.hip -- pose-graph kernels: BetweenFactor linearisation fused with the block-sparse J^T J / J^T r assembly,
 // trial cost, retraction, parity exports.
 //
-// Generic over the manifold M (Se3Manifold of pg_device.hpp | Se2Manifold of pg2_device.hpp):
+// Generic over the manifold M (Se3Manifold of pg_device.hpp | Se2Manifold of pg2_device.hpp | So3Manifold of pg_so3_device.hpp):
 //   k_pg_prepare<M>       vertex-major  prepared poses of a parameter set (SE3::from(DVector) | SE2::from(DVector))
 //   k_pg_cost_partial<M>  edge-major    1/2 |r~|^2 at a (trial) parameter set
 //   k_pg_retract<M>       vertex-major  x (+) d with the fixed-DOF mask (src/core/problem.rs:185-197)
@@ -9,18 +9,18 @@
 //   k_pg_jv_gram<M>       edge-major    |J a|^2, (J a).(J b), |J b|^2 matrix-free: the products with H = J^T J the Dog-Leg step needs
 //                                       (dog_leg.rs:776-803, 948-960) once the tiles hold L instead of H; the rest of a Dog-Leg
 //                                       step runs on plain vectors and lives in dogleg_kernels.hip
-// The assembly is one algorithm per manifold:
+// The assembly is one algorithm per block size -- SE3 (6 x 6) edge-major, the 3-DOF manifolds SE2 and SO3 row-owned:
 //   k_pg_edges      SE3  edge-major    r, dr/dk0, dr/dk1 per edge in registers (never written to memory), loss correction,
 //                                      then H_aa += Ja^T Ja, H_bb += Jb^T Jb, H_(hi,lo) += J_hi^T J_lo, g_a += Ja^T r,
 //                                      g_b += Jb^T r with fp64 atomics (SparseCholeskySolver's J^T J and J^T r,
 //                                      src/linalg/sparse/cholesky.rs:166-181)
 //   k_pg_priors     SE3  one lane per prior block, atomics
-//   k_pg2_assemble  SE2  vertex-major  lane v walks the edges incident to v (pg2_assemble_row): H_vv and g_v in registers,
+//   k_pg2_assemble<M>  SE2, SO3  vertex-major  lane v walks the edges incident to v (pg_row_assemble<M>): H_vv and g_v in registers,
 //                                      blocks (v, u), u < v, by plain read-add-write -- row v of the lower triangle has
 //                                      one writer, so there are no atomics and every sum has a fixed order: two
 //                                      assemblies of one state are bit-identical.  An edge is linearised by both of its
 //                                      endpoints (a few dozen flops) instead of scattering 24-byte segments atomically.
-//   k_pg2_priors    SE2  one lane per run of prior blocks on one vertex (the blocks arrive sorted by vertex)
+//   k_pg2_priors<M>    SE2, SO3  one lane per run of prior blocks on one vertex (the blocks arrive sorted by vertex)
 // Every kernel that linearises edges is instantiated per loss policy (pg_device.hpp): LossLegacy (huber_delta), LossGeneral
 // (PgLoss), LossWeighted (PgLoss and the edge information matrices of PGView::info).
 //
@@ -32,18 +32,25 @@
 #include "pg2_device.hpp"
 #include "pg_device.hpp"
 #include "pg_kernels.h"
+#include "pg_so3_device.hpp"
 
 namespace apex {
 
-// one prepared pose / measurement / prior block: M::kStride doubles by 16-byte loads
-template <class M>
-__device__ __forceinline__ void load_pose(const double* __restrict__ base, int64_t i, double p[M::kStride]) {
-    const double2* q = reinterpret_cast<const double2*>(base + M::kStride * i);
+// block i of N doubles (N even) by 16-byte loads
+template <int N>
+__device__ __forceinline__ void load_block(const double* __restrict__ base, int64_t i, double p[N]) {
+    static_assert(N % 2 == 0, "16-byte loads");
+    const double2* q = reinterpret_cast<const double2*>(base + N * i);
 #pragma unroll
-    for (int a = 0; a < M::kStride / 2; ++a) {
+    for (int a = 0; a < N / 2; ++a) {
         const double2 t = q[a];
         p[2 * a] = t.x; p[2 * a + 1] = t.y;
     }
+}
+// one prepared pose / measurement: M::kStride doubles
+template <class M>
+__device__ __forceinline__ void load_pose(const double* __restrict__ base, int64_t i, double p[M::kStride]) {
+    load_block<M::kStride>(base, i, p);
 }
 
 // DOF x DOF block (row vertex vr, column vertex vc, vr >= vc) of the lower-triangular tile matrix
@@ -93,14 +100,15 @@ __device__ __forceinline__ void load_info(const double* __restrict__ base, int64
 template <class M>
 __device__ __forceinline__ double prior_at(const PGView& v, int k, double r[M::kAmb]) {
     const uint32_t a = v.prior_v[k];
-    double x[M::kStride], d[M::kStride];
+    static_assert(M::kPriorStride > M::kAmb, "a prior block holds its Huber delta behind the datum");
+    double x[M::kStride], d[M::kPriorStride];
     if constexpr (M::kPriorOnPrepared) {
         load_pose<M>(v.posep, a, x);
     } else {
 #pragma unroll
         for (int i = 0; i < M::kAmb; ++i) x[i] = v.poses[M::kAmb * (size_t)a + i];
     }
-    load_pose<M>(v.prior_data, k, d);   // data (kAmb) | the block's Huber delta
+    load_block<M::kPriorStride>(v.prior_data, k, d);   // data (kAmb) | the block's Huber delta
     return M::prior_residual(x, d, d[M::kAmb], r);
 }
 
@@ -269,8 +277,8 @@ __global__ __launch_bounds__(64) void k_pg_priors(PGView v, TileMap tm, double* 
     }
 }
 
-// ---- SE2 assembly: row-owned ---------------------------------------------------------------------------------------
-template <class LP>
+// ---- the 3-DOF manifolds' assembly (SE2, SO3): row-owned -----------------------------------------------------------
+template <class M, class LP>
 __global__ __launch_bounds__(256) void k_pg2_assemble(PGView v, TileMap tm, double* __restrict__ g) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= v.n_v) return;
@@ -284,9 +292,9 @@ __global__ __launch_bounds__(256) void k_pg2_assemble(PGView v, TileMap tm, doub
             for (int b = 0; b < 3; ++b) blk[a * kNB + b] += B[3 * a + b];
     };
     if constexpr (kWeighted<LP>)
-        pg2_assemble_row_info(row, v.posep, v.meas, v.e_from, v.e_to, v.inc_ptr, v.inc_edge, v.info, v.loss, H, gv, add_off);
+        pg_row_assemble_info<M>(row, v.posep, v.meas, v.e_from, v.e_to, v.inc_ptr, v.inc_edge, v.info, v.loss, H, gv, add_off);
     else
-        pg2_assemble_row(row, v.posep, v.meas, v.e_from, v.e_to, v.inc_ptr, v.inc_edge, loss_param<LP>(v), H, gv, add_off);
+        pg_row_assemble<M>(row, v.posep, v.meas, v.e_from, v.e_to, v.inc_ptr, v.inc_edge, loss_param<LP>(v), H, gv, add_off);
     double* blk = h_block_ptr<3>(tm, row, row);   // (on top of the damping add_diag has put there)
 #pragma unroll
     for (int a = 0; a < 3; ++a)
@@ -296,6 +304,9 @@ __global__ __launch_bounds__(256) void k_pg2_assemble(PGView v, TileMap tm, doub
     for (int a = 0; a < 3; ++a) g[3 * (size_t)row + a] = gv[a];
 }
 
+// (a prior block has M::kAmb rows over the vertex's three columns: J~ = sc times the first three columns of I, so rows past
+// the third -- SO3's fourth -- count in the cost only)
+template <class M>
 __global__ __launch_bounds__(64) void k_pg2_priors(PGView v, TileMap tm, double* __restrict__ g) {
     const int k = blockIdx.x * 64 + threadIdx.x;
     if (k >= v.n_prior) return;
@@ -303,8 +314,8 @@ __global__ __launch_bounds__(64) void k_pg2_priors(PGView v, TileMap tm, double*
     if (k > 0 && v.prior_v[k - 1] == a) return;   // the first block of a vertex sums the whole run, in order
     double h = 0.0, gv[3] = {0.0, 0.0, 0.0};
     for (int j = k; j < v.n_prior && v.prior_v[j] == a; ++j) {
-        double r[3];
-        const double sc = prior_at<Se2Manifold>(v, j, r);   // J~ = sc I3: J~^T J~ = sc^2 I3, J~^T r~ = sc r~
+        double r[M::kAmb];
+        const double sc = prior_at<M>(v, j, r);   // J~ = sc I3: J~^T J~ = sc^2 I3, J~^T r~ = sc r~
         h += sc * sc;
 #pragma unroll
         for (int i = 0; i < 3; ++i) gv[i] += sc * r[i];
@@ -462,10 +473,11 @@ __global__ __launch_bounds__(256) void k_pg_jv_gram(PGView v, const double* __re
 // ---- launchers -----------------------------------------------------------------------------------------------------
 static inline int grid256(int64_t n) { return (int)((n + 255) / 256); }
 
-// the one place a manifold id becomes a type: f is called with an Se3Manifold or an Se2Manifold
+// the one place a manifold id becomes a type: f is called with an Se3Manifold, an Se2Manifold or an So3Manifold
 template <class F>
 static inline void with_manifold(int manifold, F f) {
     if (manifold == kManifoldSE2) f(Se2Manifold{});
+    else if (manifold == kManifoldSO3) f(So3Manifold{});
     else f(Se3Manifold{});
 }
 // the one place a view's loss becomes a policy type: the weighted instantiation when the view carries information matrices,
@@ -485,12 +497,17 @@ void launch_pg_prepare(int manifold, int64_t n, const double* poses, double* pos
 }
 void launch_pg_assemble(int manifold, const PGView& v, const TileMap& tm, double* g, hipStream_t s) {
     const dim3 prior_grid((v.n_prior + 63) / 64);
-    if (manifold == kManifoldSE2) {
-        if (v.n_v > 0)
-            with_loss(v, [&](auto LP) {
-                hipLaunchKernelGGL(k_pg2_assemble<decltype(LP)>, dim3(grid256(v.n_v)), dim3(256), 0, s, v, tm, g);
-            });
-        if (v.n_prior > 0) hipLaunchKernelGGL(k_pg2_priors, prior_grid, dim3(64), 0, s, v, tm, g);
+    if (pg_row_owned(manifold)) {
+        with_manifold(manifold, [&](auto M) {
+            using Man = decltype(M);
+            if constexpr (Man::kDof == 3) {   // (the row-owned kernels exist for the 3-DOF manifolds only: SE3 never gets here)
+                if (v.n_v > 0)
+                    with_loss(v, [&](auto LP) {
+                        hipLaunchKernelGGL((k_pg2_assemble<Man, decltype(LP)>), dim3(grid256(v.n_v)), dim3(256), 0, s, v, tm, g);
+                    });
+                if (v.n_prior > 0) hipLaunchKernelGGL(k_pg2_priors<Man>, prior_grid, dim3(64), 0, s, v, tm, g);
+            }
+        });
     } else {
         if (v.n_e > 0)
             with_loss(v, [&](auto LP) {

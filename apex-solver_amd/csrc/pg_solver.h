@@ -1,4 +1,4 @@
-// pg_solver.h -- host side of the MI355X pose-graph backend (BASELINE.json configs[1]): SE3 and SE2 vertices.
+// pg_solver.h -- host side of the MI355X pose-graph backend (BASELINE.json configs[1]): SE3, SE2 and SO3 vertices.
 //
 // Mirrors SparseCholeskySolver (src/linalg/sparse/cholesky.rs:159-230) driven by the LM loop
 // (src/optimizer/levenberg_marquardt.rs:823-1031) on a problem of BetweenFactor<SE3> blocks
@@ -6,12 +6,13 @@
 // H = J^T J is assembled block-sparse (6x6 blocks) straight from the edges into 144x144 tiles,
 // H + lambda I is factorised by the level-scheduled tile Cholesky of TilePlan -- no Schur complement.
 //
-// One class, two manifolds.  The orchestration (speculative factor, one wait per iteration, eager step evaluation,
+// One class, three manifolds.  The orchestration (speculative factor, one wait per iteration, eager step evaluation,
 // scaling, covariance, exports) does not care what a vertex is: it sees dof_ tangent columns and amb_ stored doubles per
 // vertex, kNB / dof_ vertices per tile.  Only prepare / assemble / priors / cost / retract / exports differ, and the
-// launchers of pg_kernels.h take manifold_ for that: the same kernels instantiated for Se3Manifold (6, 7) or Se2Manifold
-// (3, 3), and one assembly each -- SE3 the atomic edge scatter, SE2 the row-owned assembly over the incident-edge lists
-// of pg2_lists.h, which live with the SE2 structure only.
+// launchers of pg_kernels.h take manifold_ for that: the same kernels instantiated for Se3Manifold (6, 7), Se2Manifold
+// (3, 3) or So3Manifold (3, 4), and one assembly per block size -- SE3 the atomic edge scatter, the 3-DOF manifolds SE2 and
+// SO3 (rotation averaging, BetweenFactor<SO3>: between_factor.rs:13,55) the row-owned assembly over the incident-edge lists
+// of pg2_lists.h, which live with the structure of the row-owned manifolds only (pg_row_owned).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -76,8 +77,8 @@ class PoseGraphSolver : public TileBackend {
 
     int64_t n_vertices() const { return n_v_; }
     int manifold() const { return manifold_; }
-    int dof() const { return dof_; }           // tangent columns per vertex: 6 | 3
-    int ambient() const { return amb_; }       // stored doubles per vertex / measurement / prior: 7 | 3
+    int dof() const { return dof_; }           // tangent columns per vertex: 6 | 3 | 3
+    int ambient() const { return amb_; }       // stored doubles per vertex / measurement / prior: 7 | 3 | 4
     int n_tile_rows() const { return tp_.nt(); }
     int64_t tile_count() const { return tp_.n_slots(); }
     int64_t touched_tiles() const { return tp_.n_touched_slots(); }
@@ -93,6 +94,9 @@ class PoseGraphSolver : public TileBackend {
     int enqueue_step_stats() override;
     int enqueue_trial_point(double* sumsq_out) override;
     int enqueue_retract(int from, double sign, int to) override;   // retraction + the prepared poses of the result
+    // SO3: a rejected trial step restores the parameters bit for bit (tile_backend.h).  SE3 and SE2 keep the reference's
+    // apply_negative_parameter_step, trial (+) (-step), and the bits their tests pin.
+    bool keeps_current_on_discard() const override { return manifold_ == kManifoldSO3; }
     // scal_: [1..3] the step's sums, [4] the trial point's sum of squares -- read here only
     double* step_sums(int* n) override { *n = 3; return scal_ + 1; }
     StepAnswers answers_from_sums(const double* h) const override { return {sqrt(h[0]), sqrt(h[1]), 0.5 * h[2], h[3]}; }
@@ -105,7 +109,7 @@ class PoseGraphSolver : public TileBackend {
     int solve_for_dogleg(double mu) override { return solve_damped(mu, nullptr, nullptr); }
 
     int64_t n_v_, n_e_;
-    int manifold_, dof_, amb_, stride_, vpt_;   // vpt_: vertices per tile = kNB / dof_
+    int manifold_, dof_, amb_, stride_, prior_stride_, vpt_;   // vpt_: vertices per tile = kNB / dof_
     int64_t n_ = 0, n_pad_ = 0;
     double huber_delta_ = 0.0;
     bool loss_set_ = false;   // set_loss has replaced huber_delta_ (until the next set_structure)
@@ -117,7 +121,7 @@ class PoseGraphSolver : public TileBackend {
     DeviceBuffer<uint32_t> e_from_, e_to_;
     int n_prior_ = 0;
     DeviceBuffer<uint32_t> prior_v_;
-    DeviceBuffer<int> inc_ptr_, prior_slot_;   // SE2 only: incident-edge CSR, the caller's index of each sorted prior
+    DeviceBuffer<int> inc_ptr_, prior_slot_;   // the row-owned manifolds only: incident-edge CSR, the caller's index of each sorted prior
     DeviceBuffer<uint32_t> inc_edge_;
     DeviceBuffer<double> prior_data_;
     DeviceBuffer<double> prior_res_;   // staging of get_prior_residual

@@ -10,21 +10,34 @@
 #include "pg2_device.hpp"
 #include "pg2_lists.h"
 #include "pg_device.hpp"
+#include "pg_so3_device.hpp"
 
 namespace apex {
 
+namespace {
+// the sizes of a manifold trait as values: {dof, amb, stride, prior stride}
+struct ManifoldSizes { int dof, amb, stride, prior_stride; };
+template <class M>
+constexpr ManifoldSizes sizes_of() { return {M::kDof, M::kAmb, M::kStride, M::kPriorStride}; }
+ManifoldSizes manifold_sizes(int manifold) {
+    if (manifold == kManifoldSE2) return sizes_of<Se2Manifold>();
+    if (manifold == kManifoldSO3) return sizes_of<So3Manifold>();
+    return sizes_of<Se3Manifold>();
+}
+int known_manifold(int manifold) { return manifold == kManifoldSE2 || manifold == kManifoldSO3 ? manifold : kManifoldSE3; }
+}  // namespace
+
 PoseGraphSolver::PoseGraphSolver(int64_t n_v, int64_t n_e, int device, int manifold)
-    : TileBackend(device, kPgNumStages, /*nd_leaf=*/2, kPgStats, /*n_partial=*/256), n_v_(n_v), n_e_(n_e), manifold_(manifold == kManifoldSE2 ? kManifoldSE2 : kManifoldSE3),
-      dof_(manifold_ == kManifoldSE2 ? Se2Manifold::kDof : Se3Manifold::kDof),
-      amb_(manifold_ == kManifoldSE2 ? Se2Manifold::kAmb : Se3Manifold::kAmb),
-      stride_(manifold_ == kManifoldSE2 ? Se2Manifold::kStride : Se3Manifold::kStride), vpt_(kNB / dof_) {}
+    : TileBackend(device, kPgNumStages, /*nd_leaf=*/2, kPgStats, /*n_partial=*/256), n_v_(n_v), n_e_(n_e), manifold_(known_manifold(manifold)),
+      dof_(manifold_sizes(manifold_).dof), amb_(manifold_sizes(manifold_).amb), stride_(manifold_sizes(manifold_).stride),
+      prior_stride_(manifold_sizes(manifold_).prior_stride), vpt_(kNB / dof_) {}
 
 PoseGraphSolver::~PoseGraphSolver() {
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);   // before any buffer is freed; stream_last_ destroys the stream after them
 }
 
-// (the SE2-only members are empty buffers, so null, on an SE3 graph)
+// (the members of the row-owned manifolds are empty buffers, so null, on an SE3 graph)
 PGView PoseGraphSolver::view(int which) const {
     PGView v;
     v.n_v = n_v_; v.n_e = n_e_;
@@ -44,7 +57,7 @@ PGView PoseGraphSolver::view(int which) const {
         else if (huber_delta_ > 0.0) (void)pg_loss_make(kLossHuber, huber_delta_, 0.0, &v.loss);
     }
     v.n_prior = n_prior_; v.prior_v = prior_v_; v.prior_data = prior_data_;
-    if (manifold_ == kManifoldSE2) {
+    if (pg_row_owned(manifold_)) {
         v.poses = poses_[which]; v.inc_ptr = inc_ptr_; v.inc_edge = inc_edge_; v.prior_slot = prior_slot_;
     }
     return v;
@@ -81,20 +94,20 @@ int PoseGraphSolver::set_priors(int64_t n, const uint32_t* vertex, const double*
     };
     if (n == 0) return install();
     std::vector<uint32_t> hv((size_t)n);
-    std::vector<double> hd((size_t)n * stride_, 0.0);
-    // SE2: the blocks go to the device sorted by vertex (stable), so that one lane sums the run of a vertex in a fixed
+    std::vector<double> hd((size_t)n * prior_stride_, 0.0);
+    // SE2, SO3: the blocks go to the device sorted by vertex (stable), so that one lane sums the run of a vertex in a fixed
     // order (k_pg2_priors); prior_slot_ keeps the caller's index for the export.  SE3: the caller's order, as ever.
     std::vector<int> order((size_t)n);
     std::iota(order.begin(), order.end(), 0);
-    if (manifold_ == kManifoldSE2)
+    if (pg_row_owned(manifold_))
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return vmap_[vertex[a]] < vmap_[vertex[b]]; });
     for (int64_t k = 0; k < n; ++k) {
         const int src = order[k];
         hv[k] = (uint32_t)vmap_[vertex[src]];
-        memcpy(hd.data() + (size_t)k * stride_, data7 + (size_t)amb_ * src, amb_ * sizeof(double));
-        hd[(size_t)k * stride_ + amb_] = huber_delta ? huber_delta[src] : -1.0;
+        memcpy(hd.data() + (size_t)k * prior_stride_, data7 + (size_t)amb_ * src, amb_ * sizeof(double));
+        hd[(size_t)k * prior_stride_ + amb_] = huber_delta ? huber_delta[src] : -1.0;
     }
-    if (manifold_ == kManifoldSE2) HIP_TRY(new_slot.upload(order));
+    if (pg_row_owned(manifold_)) HIP_TRY(new_slot.upload(order));
     HIP_TRY(new_v.upload(hv));
     HIP_TRY(new_data.upload(hd));
     return install();
@@ -235,14 +248,16 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
     }
     // measurements are constants: normalise once (SE3::from_translation_quaternion, se3.rs:107-113)
     // (SE2: BetweenFactor::new keeps SE2::from_xy_angle of the measurement, se2.rs:106-110)
+    // (SO3: the measurement is an SO3 built from its quaternion, so3.rs:225-229 -- the vertex's own preparation)
     std::vector<double> mp((size_t)n_e_ * stride_, 0.0);
     for (int64_t e = 0; e < n_e_; ++e) {
         if (manifold_ == kManifoldSE2) se2_prepare(meas7 + 3 * e, mp.data() + (size_t)stride_ * e);
+        else if (manifold_ == kManifoldSO3) So3Manifold::prepare(meas7 + 4 * e, mp.data() + (size_t)stride_ * e);
         else pose_normalise(meas7 + 7 * e, mp.data() + (size_t)stride_ * e);
     }
     std::vector<uint8_t> fx((size_t)dof_ * n_v_, 0);
     if (fix6) blocks_to_internal(vmap_, dof_, fix6, fx.data());
-    if (manifold_ == kManifoldSE2) {   // the row-owned assembly walks each vertex's incident edges
+    if (pg_row_owned(manifold_)) {   // the row-owned assembly walks each vertex's incident edges
         IncidentLists inc;
         if (!build_incident_lists(n_v_, n_e_, ef.data(), et.data(), &inc)) return fail(kInvalidInput, "incident-edge lists: out of range");
         HIP_TRY(inc_ptr_.upload(inc.ptr));

@@ -63,7 +63,7 @@ class TileBackend : public TrBackend {
     int step_stats(double out3[3]) final;       // |g|, |step|, predicted reduction
     int eval_step(double* trial_cost) final;    // x (+) step into the trial set, its cost
     int commit_step() final;
-    int discard_step() final;                   // reference semantics: trial (+) (-step), not a snapshot
+    int discard_step() final;                   // reference semantics: trial (+) (-step), not a snapshot -- unless keeps_current_on_discard()
     // The Dog-Leg step (tr_loop.h), to ONE host wait, fresh or reused.  Fresh: solve_for_dogleg with dl_mode_ on, whose finish_step
     // runs enqueue_dogleg_tail behind the step: the inner products, the Gram pass, the combine (one lane), the blended step into
     // the step vector, the trial point and its cost, one copy of DoglegScalars -- posted as the solve's answers, so step_stats /
@@ -111,6 +111,10 @@ class TileBackend : public TrBackend {
     virtual int enqueue_step_stats() = 0;                                 // the step's sums into step_sums()
     virtual int enqueue_trial_point(double* sumsq_out) = 0;               // current (+) step into the trial set, the sum of squares there
     virtual int enqueue_retract(int from, double sign, int to) = 0;       // set `to` = set `from` (+) sign * step, ready to be evaluated
+    // true: discard_step leaves the current parameter set as it is (it still holds x: the trial point is in the other set) instead of
+    // retracting the trial point by -step.  The parameters then come back bit for bit, and differ from the reference solver's, which
+    // applies the negative step, by the rounding of x (+) d (+) (-d).  Only an SO3 pose graph answers true.
+    virtual bool keeps_current_on_discard() const { return false; }
     virtual double* step_sums(int* n) = 0;                                // device: the *n sums of enqueue_step_stats, the trial point's slot behind them
     virtual StepAnswers answers_from_sums(const double* h) const = 0;     // a host copy of those *n + 1 doubles as named answers
     virtual void params_moved() {}                                        // the current parameters are other ones now (commit, discard)

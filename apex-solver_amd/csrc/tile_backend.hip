@@ -155,12 +155,16 @@ int TileBackend::commit_step() {
     return kOk;
 }
 // apply_negative_parameter_step (optimizer/mod.rs:343-356): the rejected trial point is moved back by the inverse retraction,
-// it is NOT restored from a snapshot.
+// it is NOT restored from a snapshot.  The one exception is a backend that answers keeps_current_on_discard(): the trial point
+// lives in the other parameter set (enqueue_trial_point writes st_.cur ^ 1 only), so the current set still holds x with its bits
+// and nothing is enqueued -- an SO3 pose graph (pg_solver.h).
 int TileBackend::discard_step() {
     if (const Status rc = st_.begin_discard()) return fail(rc, st_.refusal);
     HIP_TRY(hipSetDevice(device_));
-    const int rc = enqueue_retract(st_.cur ^ 1, -1.0, st_.cur);
-    if (rc != kOk) return rc;
+    if (!keeps_current_on_discard()) {
+        const int rc = enqueue_retract(st_.cur ^ 1, -1.0, st_.cur);
+        if (rc != kOk) return rc;
+    }
     HIP_TRY(hipStreamSynchronize(stream_));
     (void)st_.finish_discard();
     params_moved();

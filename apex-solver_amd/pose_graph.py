@@ -1,11 +1,14 @@
-"""Pose-graph path, SE3 and SE2 (BASELINE.json configs[1]): Python mirror of what bin/pose_graph_g2o.rs drives --
+"""Pose-graph path, SE3, SE2 and SO3 (BASELINE.json configs[1]): Python mirror of what bin/pose_graph_g2o.rs drives --
 `G2oLoader` (crates/apex-io/src/g2o.rs) over the library's C++ reader, the `Problem` of BetweenFactor<SE3>
 blocks with the first vertex fixed, and the `SparseCholesky` linear solver on the device
 (`GpuSparseCholeskySolver`, src/linalg/sparse/cholesky.rs:159-230).  Every numeric path calls
 libapexgpu.so; there is no CPU fallback.
 
 SE2 (the 2D half of bin/pose_graph_g2o.rs, :314-700): the same classes on 3-wide data -- pose / measurement / prior data
-= [x, y, theta], three tangent columns per vertex.  The manifold is picked from the width of `data.poses`."""
+= [x, y, theta], three tangent columns per vertex.  The manifold is picked from the width of `data.poses`.
+
+SO3 (rotation averaging, BetweenFactor<SO3>: src/factors/between_factor.rs:13,55): the same classes on 4-wide data -- vertex /
+measurement / prior data = [qw, qx, qy, qz], three tangent columns per vertex; `PoseGraphProblem(data, manifold="so3")`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -60,12 +63,21 @@ class G2oGraph:
         return int(self.edge_from.shape[0]) + self.n_edges_se2
 
     def to_problem_data(self, name: str = "g2o", manifold: str | None = None, use_information: bool = False) -> PoseGraphData:
-        """manifold "se3" | "se2"; None: "se2" for a file with SE2 content only, else "se3".  use_information: the file's edge
-        information matrices go along as `information`, in the problem's edge order (default: None, they are not used)."""
+        """manifold "se3" | "se2" | "so3"; None: "se2" for a file with SE2 content only, else "se3".  use_information: the file's
+        edge information matrices go along as `information`, in the problem's edge order (default: None, they are not used).
+        "so3": the rotation part of the file's SE3 content -- the quaternions [qw, qx, qy, qz] of the vertices and of the edges'
+        measurements, and with use_information the rotational 3 x 3 block of every 6 x 6 matrix (tangent order [rho; theta])."""
         if manifold is None:
             manifold = "se2" if (self.vertex_ids.shape[0] == 0 and self.n_vertices_se2 > 0) else "se3"
-        if manifold not in ("se3", "se2"):
+        if manifold not in ("se3", "se2", "so3"):
             raise ValueError(manifold)
+        if manifold == "so3":
+            p = self._problem
+            if p is None or p.n_v == 0:
+                raise ValueError("to_problem_data(manifold=\"so3\"): the file holds no SE3 content to take rotations from")
+            info = None if (not use_information or p.information is None) else np.ascontiguousarray(p.information[:, 3:6, 3:6])
+            return PoseGraphData(ids=p.ids.copy(), poses=np.ascontiguousarray(p.poses[:, 3:7]), e_from=p.e_from.copy(),
+                                 e_to=p.e_to.copy(), meas=np.ascontiguousarray(p.meas[:, 3:7]), name=name, information=info)
         if manifold == "se2" and self._problem_se2_error is not None:
             # (e.g. an EDGE_SE2 that names a vertex the file does not hold: the file still loads, as it did when SE2 lines
             # were only counted; the error belongs to whoever asks for the SE2 problem)
@@ -149,7 +161,8 @@ def write_g2o(path, data: PoseGraphData, information: np.ndarray | None = None):
 
 
 def pose_graph_columns(ids: np.ndarray, dof: int = 6) -> np.ndarray:
-    """First global column of `x{id}` in sorted-name order (src/optimizer/mod.rs:530-536); dof 6 (SE3) | 3 (SE2)."""
+    """First global column of `x{id}` in sorted-name order (src/optimizer/mod.rs:530-536); dof 6 (SE3) | 3 (SE2, SO3: the
+    3-column layout is the same, apexgpu_pose_graph_columns_se2 serves both)."""
     L = capi.load()
     ids = np.ascontiguousarray(ids, dtype=np.int64)
     out = np.zeros(ids.shape[0], np.int64)
@@ -179,6 +192,18 @@ def se2_as_vector(pose3) -> np.ndarray:
     return p
 
 
+def so3_as_vector(quat4) -> np.ndarray:
+    """SO3::from(DVector) -> DVector: [w, i, j, k] normalised (so3.rs:225-235), with the two passes an SE3 pose's quaternion gets."""
+    q = np.asarray(quat4, dtype=np.float64).reshape(4).copy()
+    q = q / np.sqrt(np.dot(q, q))
+    q = q / np.sqrt(np.dot(q, q))
+    return q
+
+
+_MANIFOLD_SIZES = {"se3": (6, 7), "se2": (3, 3), "so3": (3, 4)}   # (dof, ambient)
+_MANIFOLD_IDS = {"se3": capi.MANIFOLD_SE3, "se2": capi.MANIFOLD_SE2, "so3": capi.MANIFOLD_SO3}
+
+
 @dataclass
 class PoseGraphProblem:
     """The factor graph bin/pose_graph_g2o.rs:748-830 builds: variables `x{id}` (SE3), one
@@ -190,12 +215,18 @@ class PoseGraphProblem:
     priors: list = field(default_factory=list)   # (vertex index, data[7], huber delta or None) per PriorFactor block
     loss: Loss | None = None   # the loss of every BetweenFactor block; mutually exclusive with huber_delta
     information: np.ndarray | None = None   # (n_e, dof, dof) edge information matrices; None: data.information (None: not used)
+    manifold: str | None = None   # "se3" | "se2" | "so3"; None: from the width of data.poses (7 | 3 | 4)
 
     def __post_init__(self):
         if self.loss is not None and self.huber_delta is not None:
             raise ValueError("PoseGraphProblem: give either loss or huber_delta, not both")
-        self.manifold = self.data.manifold
-        self.dof, self.ambient = (3, 3) if self.manifold == "se2" else (6, 7)
+        if self.manifold is None:
+            self.manifold = self.data.manifold
+        if self.manifold not in _MANIFOLD_SIZES:
+            raise ValueError(f"PoseGraphProblem: unknown manifold {self.manifold!r}")
+        self.dof, self.ambient = _MANIFOLD_SIZES[self.manifold]
+        if self.data.poses.shape[1] != self.ambient or self.data.meas.shape[1] != self.ambient:
+            raise ValueError(f"PoseGraphProblem: a {self.manifold} graph has {self.ambient}-wide poses and measurements")
         if self.information is None:
             self.information = self.data.information
         if self.information is not None:
@@ -219,6 +250,8 @@ class PoseGraphProblem:
         v = int(hit[0])
         if self.manifold == "se2":   # r = [x, y, theta] - data, three rows, Jacobian I3 (integration_tests.rs:213-231)
             x = se2_as_vector(self.data.poses[v]) if data is None else np.asarray(data, dtype=np.float64).reshape(3)
+        elif self.manifold == "so3":   # r = [w, i, j, k] - data, four rows; the linearizer keeps three columns of I4 (sparse.rs:201-204)
+            x = so3_as_vector(self.data.poses[v]) if data is None else np.asarray(data, dtype=np.float64).reshape(4)
         else:
             x = se3_as_vector(self.data.poses[v]) if data is None else np.asarray(data, dtype=np.float64).reshape(7)
         self.priors.append((v, x, huber_delta))
@@ -325,7 +358,7 @@ class GpuSparseCholeskySolver:
     def initialize_structure(self, problem: PoseGraphProblem):
         d = problem.data
         self.close()
-        h = capi.PgHandle(d.n_v, d.n_e, self.device, capi.MANIFOLD_SE2 if problem.manifold == "se2" else capi.MANIFOLD_SE3)
+        h = capi.PgHandle(d.n_v, d.n_e, self.device, _MANIFOLD_IDS[problem.manifold])
         for k, v in self._opts.items():
             h.check(h.L.apexgpu_pg_set_option(h.h, k.encode(), v))
         ef = np.ascontiguousarray(d.e_from, dtype=np.uint32); et = np.ascontiguousarray(d.e_to, dtype=np.uint32)

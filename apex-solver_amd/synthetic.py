@@ -365,6 +365,7 @@ class PoseGraphData:
     truth: np.ndarray | None = None
     name: str = "pose-graph"
     information: np.ndarray | None = None   # (n_e, D, D) edge information matrices, D = 6 | 3; None: not used
+    # (SO3 graphs, make_rotation_graph: 4-wide rows, vertex / meas = [qw, qx, qy, qz], D = 3)
 
     @property
     def n_v(self) -> int:
@@ -376,7 +377,7 @@ class PoseGraphData:
 
     @property
     def manifold(self) -> str:
-        return "se2" if self.poses.shape[1] == 3 else "se3"
+        return {3: "se2", 4: "so3"}.get(self.poses.shape[1], "se3")
 
 
 def se3_exp(tau: np.ndarray) -> np.ndarray:
@@ -515,3 +516,46 @@ def make_manhattan(n: int = 3500, noise: float = 0.02, rot_noise: float = 0.01, 
         init[k + 1] = se2_mul(init[k:k + 1], meas[k:k + 1])[0]
     ids = np.arange(n, dtype=np.int64) * id_stride
     return PoseGraphData(ids=ids, poses=init, e_from=ef, e_to=et, meas=meas, truth=truth, name=f"manhattan-{n}")
+
+
+# ---------------------------------------------------------------------------------------------------
+# SO3 pose graphs: rotation averaging (BetweenFactor<SO3>, src/factors/between_factor.rs:13,55).  PoseGraphData with
+# 4-wide rows: vertex / measurement = [qw, qx, qy, qz].
+# ---------------------------------------------------------------------------------------------------
+def make_rotation_graph(n_v: int, degree: float = 4.0, sigma: float = 0.05, seed: int = 0, window: int | None = None,
+                        id_stride: int = 1) -> PoseGraphData:
+    """Rotation-averaging graph: n_v random orientations (uniform on SO3), the chain i -> i + 1 (so the graph is connected)
+    and random chords i -> j, j >= i + 2, up to round(n_v * degree / 2) edges in all -- mean vertex degree `degree`, never
+    fewer than the chain.  A chord spans at most `window` vertices (None: any two vertices; a view graph of a capture
+    sequence is mostly local).  Measurements are the true relative rotations truth[from]^-1 truth[to] times
+    Exp(N(0, sigma^2 I)): at sigma = 0 the truth has zero cost and is the optimum.  Initial values are the chain of
+    measurements from the true first orientation (drifting; the truth itself at sigma = 0).  Edges: the n_v - 1 chain edges
+    first, then the chords in draw order (a pair may be drawn twice: parallel edges are legal input)."""
+    if n_v < 1:
+        raise ValueError("make_rotation_graph: n_v must be positive")
+    rng = SplitMix(SEED_BASE + 9000 + seed)
+    q = np.stack([rng.normal(10 + 2 * a, n_v) for a in range(4)], axis=-1)
+    truth = q / np.linalg.norm(q, axis=-1, keepdims=True)
+    n_chain = n_v - 1
+    n_chord = max(int(round(n_v * degree / 2.0)) - n_chain, 0) if n_v >= 3 else 0
+    span = n_v - 1 if window is None else max(2, min(int(window), n_v - 1))
+    off = 2 + np.floor(rng.uniform(20, n_chord) * (span - 1)).astype(np.int64)        # 2 .. span
+    ci = np.floor(rng.uniform(21, n_chord) * (n_v - off)).astype(np.int64)            # 0 .. n_v - off - 1
+    ef = np.concatenate([np.arange(n_chain, dtype=np.int64), ci]).astype(np.uint32)
+    et = np.concatenate([np.arange(1, n_v, dtype=np.int64), ci + off]).astype(np.uint32)
+    m = ef.shape[0]
+    conj = np.array([1.0, -1.0, -1.0, -1.0])
+    rel = quat_mul(truth[ef] * conj, truth[et])
+    tau = sigma * np.stack([rng.normal(30 + 2 * a, m) for a in range(3)], axis=-1)
+    meas = quat_mul(rel, quat_exp(tau)) if sigma != 0.0 else rel
+    meas = meas / np.linalg.norm(meas, axis=-1, keepdims=True)
+    init = np.empty_like(truth)
+    init[0] = truth[0]
+    for k in range(n_chain):   # chain edges are the first n_v - 1, edge k is k -> k + 1
+        init[k + 1] = quat_mul(init[k], meas[k])
+    init /= np.linalg.norm(init, axis=-1, keepdims=True)
+    if sigma == 0.0:
+        init = truth.copy()
+    ids = np.arange(n_v, dtype=np.int64) * id_stride
+    return PoseGraphData(ids=ids, poses=np.ascontiguousarray(init), e_from=ef, e_to=et, meas=np.ascontiguousarray(meas),
+                         truth=truth, name=f"rotations-{n_v}-deg{degree:g}")

@@ -156,7 +156,7 @@ int apexgpu_eval_step(apexgpu_solver* h, double* trial_cost);
 /* accept: the trial copy becomes current (levenberg_marquardt.rs:797-801) */
 int apexgpu_commit_step(apexgpu_solver* h);
 /* reject: apply_negative_parameter_step (src/optimizer/mod.rs:343-356) -- the inverse retraction of
- * the trial point, not a snapshot restore */
+ * the trial point, not a snapshot restore (the one exception: apexgpu_pg_discard_step on an SO3 handle, see there) */
 int apexgpu_discard_step(apexgpu_solver* h);
 /* compute_parameter_norm (src/optimizer/mod.rs:458-467) */
 int apexgpu_parameter_norm(apexgpu_solver* h, double* out);
@@ -564,7 +564,7 @@ int apexgpu_bal_variables(const apexgpu_bal* b, double* poses7, double* intr3);
 int apexgpu_reference_columns(int64_t n_cam, int64_t n_pt, int64_t* intr_col, int64_t* pose_col, int64_t* pt_col);
 
 /* =================================================================================================
- * Pose-graph backend, SE3 and SE2 (BASELINE.json configs[1]: block-sparse J^T J assembly + Cholesky, no Schur)
+ * Pose-graph backend, SE3, SE2 and SO3 (BASELINE.json configs[1]: block-sparse J^T J assembly + Cholesky, no Schur)
  *
  * Replaces, for problems made of BetweenFactor<SE3> residual blocks (bin/pose_graph_g2o.rs:748-830):
  *   BetweenFactor<SE3>::linearize                         src/factors/between_factor.rs:268-322
@@ -586,13 +586,26 @@ typedef struct apexgpu_pg_solver apexgpu_pg_solver;
  * se2.rs:252-284, 468-613), the retraction is the right-plus x * Exp(d).  Wherever an entry below says 7 (ambient size)
  * or 6 (tangent dof) an SE2 handle reads and writes 3; each entry repeats its SE2 shape.  H is assembled without
  * atomics (one owner per block row): two assemblies of one state, and two LM runs from one start, are bit-identical. */
+/* SO3 pose graphs -- rotation averaging: absolute orientations from relative rotations, BetweenFactor<SO3> blocks
+ * (src/factors/between_factor.rs:13,55; src/core/problem.rs:119-128) -- use the SAME handle type and entry points too.  A handle
+ * made by apexgpu_pg_create_so3 holds SO3 variables (unit quaternion, crates/apex-manifolds/src/so3.rs): the parameter vector of
+ * a vertex, a measurement and a prior's data are [qw, qx, qy, qz] (SO3::from(DVector) / coeffs(), so3.rs:225-229, 210-213;
+ * normalised on the way in like an SE3 pose's quaternion), the tangent is [theta_x, theta_y, theta_z]
+ * (BetweenFactor<SO3>::linearize, between_factor.rs:268-322; log with its cos < 0 arm, so3.rs:313-357; Jr^-1 = (Jl^-1)^T,
+ * so3.rs:618-644; thresholds on the square against 1e-10, lib.rs:61), the retraction is the right-plus x * Exp(d)
+ * (lib.rs:269-283, so3.rs:558-577), stored as the product gives it.  Wherever an entry below says 7 (ambient size) an SO3
+ * handle reads and writes 4, where it says 6 (tangent dof) 3; each entry repeats its SO3 shape.  Assembled like SE2: no
+ * atomics, two assemblies of one state and two runs from one start are bit-identical. */
 #define APEXGPU_MANIFOLD_SE3 0
 #define APEXGPU_MANIFOLD_SE2 1
+#define APEXGPU_MANIFOLD_SO3 2
 
 /* SparseCholeskySolver::new (cholesky.rs:60-70) + per-optimize state */
 int apexgpu_pg_create(int64_t n_vertices, int64_t n_edges, int device, apexgpu_pg_solver** out);
 int apexgpu_pg_create_se2(int64_t n_vertices, int64_t n_edges, int device, apexgpu_pg_solver** out);
-/* out3 = { APEXGPU_MANIFOLD_*, ambient size (7 | 3), tangent dof (6 | 3) } */
+int apexgpu_pg_create_so3(int64_t n_vertices, int64_t n_edges, int device, apexgpu_pg_solver** out);
+/* out3 = { APEXGPU_MANIFOLD_*, ambient size (7 | 3 | 4), tangent dof (6 | 3 | 3) }: an SO3 handle answers {2, 4, 3} -- the id, then
+ * the ambient size, then the dof, the order the SE3 {0, 7, 6} and SE2 {1, 3, 3} answers have always had */
 int apexgpu_pg_manifold(const apexgpu_pg_solver* h, int out3[3]);
 void apexgpu_pg_destroy(apexgpu_pg_solver* h);
 const char* apexgpu_pg_last_error(const apexgpu_pg_solver* h);
@@ -603,7 +616,10 @@ const char* apexgpu_pg_last_error(const apexgpu_pg_solver* h);
  * vertex v (Problem::fix_variable, src/core/problem.rs:185-197), huber_delta <= 0: no loss function,
  * > 0: HuberLoss(delta) on every block.
  * SE2 handle: meas7 is [n_e][3] = x y theta (SE2::from_xy_angle, se2.rs:106-110), fix6 is [n_v][3], pose_col counts 3
- * columns per variable (apexgpu_pose_graph_columns_se2). */
+ * columns per variable (apexgpu_pose_graph_columns_se2).
+ * SO3 handle: meas7 is [n_e][4] = qw qx qy qz of the measured k0->k1 rotation (so3.rs:225-229), fix6 is [n_v][3]
+ * (problem.rs:185-197), pose_col counts 3 columns per variable: apexgpu_pose_graph_columns_se2 computes any 3-column layout
+ * and serves SO3 as it is. */
 int apexgpu_pg_set_structure(apexgpu_pg_solver* h, const uint32_t* e_from, const uint32_t* e_to, const double* meas7,
                              const int64_t* pose_col, const uint8_t* fix6, double huber_delta);
 /* Problem::initialize_variables (src/core/problem.rs:686-808): poses7[v] = [t, qw,qx,qy,qz] */
@@ -615,7 +631,12 @@ int apexgpu_pg_set_structure(apexgpu_pg_solver* h, const uint32_t* e_from, const
  * SE2 handle (run_se2_optimization(.., use_prior = true), tests/integration_tests.rs:213-231): data7 is [n][3], r = [x, y, theta]
  * - data (prior_factor.rs:96-108), Jacobian the 3 x 3 identity, residuals [n][3].
  * apexgpu_pg_set_params / get_params on an SE2 handle: poses7 is [n_v][3] = x y theta; get_params returns theta in (-pi, pi]
- * (SE2 -> DVector, se2.rs:55-63: UnitComplex::angle). */
+ * (SE2 -> DVector, se2.rs:55-63: UnitComplex::angle).
+ * SO3 handle: data7 is [n][4], r = coeffs(x) - data over the four stored doubles of the normalised quaternion
+ * (prior_factor.rs:96-108), the Jacobian the 4 x 4 identity of which the linearizer keeps the three tangent columns
+ * (sparse.rs:201-204): H_vv += rho' diag(1, 1, 1), g_v += r[0:3], all four rows count in the cost; residuals [n][4].
+ * apexgpu_pg_set_params / get_params on an SO3 handle: poses7 is [n_v][4] = qw qx qy qz; get_params returns the stored
+ * quaternion (after a step: the product x * Exp(d), not re-normalised, lib.rs:269-283). */
 int apexgpu_pg_set_priors(apexgpu_pg_solver* h, int64_t n, const uint32_t* vertex, const double* data7, const double* huber_delta);
 int apexgpu_pg_get_prior_residual(apexgpu_pg_solver* h, double* r7_out);
 
@@ -649,8 +670,8 @@ int apexgpu_pg_set_loss(apexgpu_pg_solver* h, int kind, double p0, double p1);
 /* what the edges carry: the loss of set_loss, else HUBER with set_structure's delta, else NONE; out2 = {p0, p1} */
 int apexgpu_pg_get_loss(const apexgpu_pg_solver* h, int* kind, double out2[2]);
 /* ---- edge information matrices -------------------------------------------------------------------------------------------
- * info[e] is the symmetric positive-definite D x D matrix Omega_e of BetweenFactor e (D = 6 | 3), row-major, in the tangent
- * order of the residual ([rho; theta] | [x, y, theta] -- the order of a G2O file), the caller's edge order; NULL: none, the
+ * info[e] is the symmetric positive-definite D x D matrix Omega_e of BetweenFactor e (D = 6 | 3 | SO3: 3), row-major, in the tangent
+ * order of the residual ([rho; theta] | [x, y, theta] -- the order of a G2O file | SO3: [theta_x, theta_y, theta_z]), the caller's edge order; NULL: none, the
  * handle is again what it was before the first call.  With Omega = U^T U (U upper-triangular) the block is the reference's
  * block whitened, r_w = U r, J_w = U J, and the loss (huber_delta or apexgpu_pg_set_loss) acts on (r_w, J_w,
  * s = r^T Omega r) through the same corrector: whiten, then robustify.  The cost is 1/2 sum rho(r^T Omega r), H = J^T Omega J
@@ -659,7 +680,8 @@ int apexgpu_pg_get_loss(const apexgpu_pg_solver* h, int* kind, double out2[2]);
  * the first offending edge named in apexgpu_pg_last_error and the handle unchanged, when an entry is not finite, when
  * |Omega_ij - Omega_ji| > 1e-12 max|Omega|, or when the Cholesky factorisation meets a pivot <= 0.  The upper triangle is what
  * is stored.  Invalidates a pending step and a cached Dog-Leg solve like apexgpu_pg_set_loss.
- * apexgpu_pg_get_information: *present = 1 when matrices are held; info_out (may be NULL) receives them, full and symmetric. */
+ * apexgpu_pg_get_information: *present = 1 when matrices are held; info_out (may be NULL) receives them, full and symmetric.
+ * SO3 handle: info and info_out are [n_e][3][3] in the order [theta_x, theta_y, theta_z] of the residual (between_factor.rs:268-322). */
 int apexgpu_pg_set_information(apexgpu_pg_solver* h, const double* info);
 int apexgpu_pg_get_information(apexgpu_pg_solver* h, int* present, double* info_out);
 /* host only, no device: out6 = { rho, rho', rho'', sqrt_rho1, residual_scaling, alpha_sq_norm } at squared norm s */
@@ -673,18 +695,24 @@ int apexgpu_pg_cost(apexgpu_pg_solver* h, double* cost);
  * (J^T J + lambda I) dx = -J^T r.  step_out / grad_out (= +J^T r, get_gradient) have 6 n_vertices entries in
  * the global column order and may be NULL.  A non-positive pivot returns APEXGPU_ERR_SINGULAR_MATRIX
  * ("Cholesky factorization failed (matrix may be singular)", cholesky.rs:213-219).
- * SE2 handle: 3 n_vertices entries. */
+ * SE2 handle: 3 n_vertices entries.  SO3 handle: 3 n_vertices entries (the step is applied by so3.rs:558-577). */
 int apexgpu_pg_solve_augmented(apexgpu_pg_solver* h, double lambda, double* step_out, double* grad_out);
-/* out3 = { |g|, |step|, predicted reduction } (levenberg_marquardt.rs:721-746) */
+/* out3 = { |g|, |step|, predicted reduction } (levenberg_marquardt.rs:721-746); SO3 handle: over the 3 n_vertices tangent entries */
 int apexgpu_pg_step_stats(apexgpu_pg_solver* h, double out3[3]);
 /* apply_parameter_step into a trial set + its cost; commit = accept; discard = apply_negative_parameter_step
- * (src/optimizer/mod.rs:309-356) */
+ * (src/optimizer/mod.rs:309-356): trial (+) (-step), not a snapshot restore.
+ * SO3 handle: the step is the 3-wide tangent per vertex applied by x * Exp(d) (lib.rs:269-283, so3.rs:558-577) with the
+ * fixed-DOF mask zeroing entries first (problem.rs:185-197).  apexgpu_pg_discard_step on an SO3 handle is the exception to
+ * the line above: it restores the 4-wide parameters BIT FOR BIT (the trial point lives in a second parameter set, the current
+ * one is left as it is) where the reference's negative step would return them an ulp away; SE3 and SE2 handles do not. */
 int apexgpu_pg_eval_step(apexgpu_pg_solver* h, double* trial_cost);
 int apexgpu_pg_commit_step(apexgpu_pg_solver* h);
 int apexgpu_pg_discard_step(apexgpu_pg_solver* h);
+/* SO3 handle: the norm over the 4 n_vertices stored quaternion entries (optimizer/mod.rs:358-361) */
 int apexgpu_pg_parameter_norm(apexgpu_pg_solver* h, double* out);
 /* optimize_with_mode (levenberg_marquardt.rs:823-1031), device-resident; cfg->variant must be 0 */
-/* Jacobi column scaling, as apexgpu_column_norms / apexgpu_set_column_scaling */
+/* Jacobi column scaling, as apexgpu_column_norms / apexgpu_set_column_scaling; SO3 handle: norms_out and scaling have
+ * 3 n_vertices entries in the global column order (optimizer/mod.rs:749-763) */
 int apexgpu_pg_column_norms(apexgpu_pg_solver* h, double* norms_out);
 int apexgpu_pg_set_column_scaling(apexgpu_pg_solver* h, const double* scaling);
 int apexgpu_pg_lm_optimize(apexgpu_pg_solver* h, apexgpu_lm_config* cfg, apexgpu_lm_result* result,
@@ -733,7 +761,8 @@ typedef struct {
 } apexgpu_dl_iter;
 
 /* out3 = { |J a|^2, (J a).(J b), |J b|^2 } = { a.Ha, a.Hb, b.Hb } for H = J^T J at the current parameters, in one pass over the
- * edges and priors (no matrix is built).  a, b: total-dof entries in the global column order, taken as given (no scaling). */
+ * edges and priors (no matrix is built).  a, b: total-dof entries in the global column order, taken as given (no scaling);
+ * SO3 handle: 3 n_vertices entries each (dog_leg.rs:776-803). */
 int apexgpu_pg_jv_gram(apexgpu_pg_solver* h, const double* a, const double* b, double out3[3]);
 /* One Dog-Leg step at the current parameters (compute_optimization_step_generic, dog_leg.rs:963-1089) and its trial point:
  * apexgpu_pg_step_stats / eval_step / commit_step / discard_step follow as after apexgpu_pg_solve_augmented.
@@ -742,7 +771,9 @@ int apexgpu_pg_jv_gram(apexgpu_pg_solver* h, const double* a, const double* b, d
  * APEXGPU_ERR_INVALID_STATE when there is none (or parameters, priors, scaling were set, or another solve / export ran, since).
  * out8 = { |g|, |step| (unscaled), predicted reduction, step type, alpha, beta, |step| in the scaled variables, reused }. */
 int apexgpu_pg_dogleg_step(apexgpu_pg_solver* h, double mu, double radius, int reuse, double out8[8]);
-/* history rows: apexgpu_lm_iter with damping = 0, rho = 0, accepted = 1.  result->jacobian_evaluations counts iterations. */
+/* history rows: apexgpu_lm_iter with damping = 0, rho = 0, accepted = 1.  result->jacobian_evaluations counts iterations.
+ * SO3 handle (here, apexgpu_pg_lm_optimize and apexgpu_pg_dogleg_step / _optimize): the loops see 3 tangent columns per vertex
+ * and 4 stored doubles; nothing else differs (gauss_newton.rs:559-720, dog_leg.rs:1143-1354, levenberg_marquardt.rs:823-1031). */
 int apexgpu_pg_gn_optimize(apexgpu_pg_solver* h, apexgpu_gn_config* cfg, apexgpu_lm_result* result, apexgpu_lm_iter* history,
                            int history_capacity);
 int apexgpu_pg_dogleg_optimize(apexgpu_pg_solver* h, apexgpu_dl_config* cfg, apexgpu_lm_result* result, apexgpu_dl_iter* history,
@@ -778,7 +809,8 @@ int apexgpu_dogleg_optimize(apexgpu_solver* h, apexgpu_dl_config* cfg, apexgpu_l
 
 /* parity / debug exports: loss-corrected residuals [n_edges][6], Jacobians [n_edges][6][12] = [dr/dk0 | dr/dk1]
  * in residual-block order; dense H = J^T J + lambda I ([6 n_v]^2 row-major) and g = J^T r in the global column order.
- * SE2 handle: residuals [n_edges][3], Jacobians [n_edges][3][6], H (3 n_v)^2, g 3 n_v. */
+ * SE2 handle: residuals [n_edges][3], Jacobians [n_edges][3][6], H (3 n_v)^2, g 3 n_v.
+ * SO3 handle: the same shapes as SE2's (between_factor.rs:268-322 with dof = 3). */
 int apexgpu_pg_get_residual(apexgpu_pg_solver* h, double* r_out);
 int apexgpu_pg_get_jacobian_blocks(apexgpu_pg_solver* h, double* j_out);
 int apexgpu_pg_get_hessian(apexgpu_pg_solver* h, double lambda, double* H_out, double* g_out);
@@ -787,8 +819,8 @@ int apexgpu_pg_get_hessian(apexgpu_pg_solver* h, double lambda, double* H_out, d
  * that point and lambda, scaled variables under Jacobi scaling: what apexgpu_pg_get_hessian(lambda) returns there), from the
  * tile factor by selected inversion.  cov_out[n_v][6][6], caller's vertex order, columns as apexgpu_pg_get_hessian's.
  * APEXGPU_ERR_INVALID_STATE: no valid factor (no solve yet, or an assembly / export since).
- * SE2 handle: cov_out[n_v][3][3]. */
-int apexgpu_pg_covariance(apexgpu_pg_solver* h, double* cov_out /* n_v*36 | n_v*9 */);
+ * SE2 handle: cov_out[n_v][3][3].  SO3 handle: cov_out[n_v][3][3] (core/problem.rs:1128-1147 with dof = 3). */
+int apexgpu_pg_covariance(apexgpu_pg_solver* h, double* cov_out /* n_v*36 | n_v*9 | n_v*9 */);
 int apexgpu_pg_covariance_stats(apexgpu_pg_solver* h, double out[6], double* group_ms, int group_cap);   /* as apexgpu_covariance_stats */
 
 /* name: "graphs" (hipGraph replay of factor / solves), "update_overlap" (second stream for trailing updates),
@@ -839,6 +871,7 @@ int apexgpu_g2o_raw_se2(const apexgpu_g2o* g, int64_t* ids, double* poses3, int6
                         double* info9);
 int apexgpu_g2o_problem_se2(const apexgpu_g2o* g, int64_t* sorted_ids, double* poses3, uint32_t* e_from, uint32_t* e_to,
                             double* meas3, int64_t* pose_col, uint8_t* fix3);
+/* (3 columns per variable: the layout of an SO3 graph too, src/optimizer/mod.rs:530-536) */
 int apexgpu_pose_graph_columns_se2(int64_t n_vertices, const int64_t* ids, int64_t* pose_col);
 /* host only: the file's edge information matrices in the edge order of apexgpu_g2o_problem (manifold APEXGPU_MANIFOLD_SE3:
  * info_out [n_e][36]) or apexgpu_g2o_problem_se2 (APEXGPU_MANIFOLD_SE2: [n_e][9]), row-major, full and symmetric */
