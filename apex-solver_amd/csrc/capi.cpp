@@ -945,6 +945,8 @@ int apexgpu_pg_covariance_stats(apexgpu_pg_solver* h, double out[6], double* gro
 int apexgpu_pg_set_option(apexgpu_pg_solver* h, const char* name, int value) {
     PG_OR_FAIL;
     const std::string n = name ? name : "";
+    if (n == "row_owned_assembly")   /* read by the next set_structure; SE2 and SO3 have no other assembly and refuse 0 */
+        return (value == 0 || value == 1) && h->s->set_row_owned_option(value == 1) ? APEXGPU_OK : APEXGPU_ERR_INVALID_INPUT;
     return shared_option(h->s, n, value) ? APEXGPU_OK : APEXGPU_ERR_INVALID_INPUT;
 }
 int apexgpu_pg_enable_stage_timing(apexgpu_pg_solver* h, int on) {

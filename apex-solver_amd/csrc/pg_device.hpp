@@ -18,6 +18,10 @@
 // so a Jacobian travels as the pair (P, T): 18 doubles instead of 36, and J_a^T J_b needs three
 // 3x3 products instead of a 6x6x6 one.
 #pragma once
+#include <stddef.h>
+
+#include <type_traits>
+
 #include "ba_device.hpp"
 #include "pg_loss.hpp"
 
@@ -633,5 +637,114 @@ struct Se3Manifold {
                     }
     }
 };
+
+// ---- the row-owned SE3 assembly (apexgpu_pg_set_option "row_owned_assembly") ---------------------------------
+// One block-row of H and of g, owned by vertex v: the loop of k_pg6_assemble, host-compilable so that
+// tests/host_harness_se3_row.cpp replays it.  The 6-DOF sibling of pg_row_assemble<M> (pg2_device.hpp) over the same lists
+// (pg2_lists.h: CSR of the edges incident to each vertex, ascending edge index, a self-loop listed once).  Every edge of the
+// list is re-linearised; H_vv and g_v accumulate in registers in list order; for an other endpoint u < v the full block of
+// (v, u) goes to add_off(u, B) -- row v of the lower triangle has one writer, so a plain read-add-write there has no race and
+// parallel edges sum in list order.
+// Every product is formed by the operations of k_pg_edges / pg_edge_weighted (pg_kernels.hip) under the same policy LP --
+// between_linearize scaled by pg_huber_scale, jtj and jtr | between_linearize_general, jtj, EdgeNormal6 |
+// between_linearize_weighted, info_mul_jac, jt_mul, EdgeNormal6 -- and only the order in which the products of different edges
+// are summed differs from the atomic scatter.  Hvv is filled in full; a caller that reads its lower triangle only lets the
+// compiler drop the rest.  info: the packed Omega of every edge (InfoPack<6>), read by LossWeighted only.
+template <class LP, typename AddOff>
+APEX_HD void pg_row_assemble6(uint32_t v, const double* __restrict__ posep, const double* __restrict__ meas,
+                              const uint32_t* __restrict__ e_from, const uint32_t* __restrict__ e_to,
+                              const int* __restrict__ inc_ptr, const uint32_t* __restrict__ inc_edge,
+                              const double* __restrict__ info, const typename LP::Param& loss, double Hvv[36], double gv[6],
+                              AddOff add_off) {
+    constexpr bool weighted = std::is_same<LP, LossWeighted>::value;
+#pragma unroll
+    for (int i = 0; i < 36; ++i) Hvv[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) gv[i] = 0.0;
+    for (int k = inc_ptr[v]; k < inc_ptr[v + 1]; ++k) {
+        const uint32_t e = inc_edge[k], a = e_from[e], b = e_to[e];
+        const double* k0 = posep + 8 * (size_t)a;
+        const double* k1 = posep + 8 * (size_t)b;
+        const double* m = meas + 8 * (size_t)e;
+        double r[6];
+        Jac6 J0, J1;
+        [[maybe_unused]] EdgeNormal6 nf;
+        [[maybe_unused]] double W[36];
+        if constexpr (weighted) {
+            info_unpack<6>(info + InfoPack<6>::kStride * (size_t)e, W);
+            if (!between_linearize_weighted(k0, k1, m, loss, W, r, J0, J1, nf)) continue;   // (rho' = 0: nothing)
+        } else if constexpr (LP::kGeneral) {
+            if (!between_linearize_general(k0, k1, m, loss, r, J0, J1, nf)) continue;
+        } else {
+            between_linearize(k0, k1, m, r, J0, J1);
+            const double sc = pg_huber_scale(loss, r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+            if (sc != 1.0) {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) r[i] *= sc;
+#pragma unroll
+                for (int i = 0; i < 9; ++i) { J0.P[i] *= sc; J0.T[i] *= sc; J1.P[i] *= sc; J1.T[i] *= sc; }
+            }
+        }
+        // G = A^T B (A^T Omega B under LossWeighted), corrected: the block of row A's vertex and column B's vertex
+        const auto block = [&](const Jac6& A, const double* wa, const Jac6& B, const double* wb, double G[36]) {
+            if constexpr (weighted) {
+                double M[36];
+                info_mul_jac(W, B, M);
+                jt_mul(A, M, G);
+            } else {
+                jtj(A, B, G);
+            }
+            if constexpr (LP::kGeneral) nf.correct(G, wa, wb);
+        };
+        const auto gradient = [&](const Jac6& A, const double* wa, double gt[6]) {
+            if constexpr (LP::kGeneral) nf.grad(wa, gt);
+            else jtr(A, r, gt);
+        };
+        double G[36], gt[6];
+        if (a == b) {   // self-loop: G_00 + G_11 + G_01 + G_01^T on the diagonal block, both gradient segments on g_v
+            block(J0, nf.w0, J0, nf.w0, G);
+#pragma unroll
+            for (int i = 0; i < 36; ++i) Hvv[i] += G[i];
+            block(J1, nf.w1, J1, nf.w1, G);
+#pragma unroll
+            for (int i = 0; i < 36; ++i) Hvv[i] += G[i];
+            block(J0, nf.w0, J1, nf.w1, G);
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+#pragma unroll
+                for (int j = 0; j < 6; ++j) Hvv[6 * i + j] += G[6 * i + j] + G[6 * j + i];
+            gradient(J0, nf.w0, gt);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) gv[i] += gt[i];
+            gradient(J1, nf.w1, gt);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) gv[i] += gt[i];
+            continue;
+        }
+        const bool first = a == v;   // (selects, not pointers into the register arrays: no scratch)
+        const uint32_t u = first ? b : a;
+        Jac6 Jv, Ju;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            Jv.P[i] = first ? J0.P[i] : J1.P[i]; Jv.T[i] = first ? J0.T[i] : J1.T[i];
+            Ju.P[i] = first ? J1.P[i] : J0.P[i]; Ju.T[i] = first ? J1.T[i] : J0.T[i];
+        }
+        [[maybe_unused]] double wv[6], wu[6];
+        if constexpr (LP::kGeneral) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) { wv[i] = first ? nf.w0[i] : nf.w1[i]; wu[i] = first ? nf.w1[i] : nf.w0[i]; }
+        }
+        block(Jv, wv, Jv, wv, G);
+#pragma unroll
+        for (int i = 0; i < 36; ++i) Hvv[i] += G[i];
+        gradient(Jv, wv, gt);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) gv[i] += gt[i];
+        if (u < v) {   // row v, column u: J_v^T (Omega) J_u -- the transposed Jacobian is the row vertex's
+            block(Jv, wv, Ju, wu, G);
+            add_off(u, G);
+        }
+    }
+}
 
 }  // namespace apex

@@ -10,8 +10,10 @@
 namespace apex {
 
 enum PgManifold { kManifoldSE3 = 0, kManifoldSE2 = 1, kManifoldSO3 = 2 };
-// The 3-DOF manifolds (48 vertices per tile) are assembled row-owned over the incident-edge lists of pg2_lists.h, with their
-// prior blocks sorted by vertex; SE3 is assembled edge-major with atomics.
+// The 3-DOF manifolds (48 vertices per tile) are always assembled row-owned over the incident-edge lists of pg2_lists.h, with
+// their prior blocks sorted by vertex; SE3 is assembled edge-major with atomics unless its handle was given the option
+// "row_owned_assembly" (PoseGraphSolver::row_owned_: the property of the handle that the lists, the views, the prior order
+// and launch_pg_assemble follow -- this function answers for the manifold alone).
 inline bool pg_row_owned(int manifold) { return manifold == kManifoldSE2 || manifold == kManifoldSO3; }
 
 // Read-only view of one parameter set + the edge list (internal vertex numbering).  Sizes per manifold (SE3 | SE2 | SO3):
@@ -24,13 +26,13 @@ struct PGView {
     const uint32_t* e_to;    // [n_e] k1
     const double* meas;      // [n_e][stride] prepared measurements
     double huber_delta;      // <= 0: no loss function
-    // PriorFactor blocks (prior_factor.rs:96-108): r = to_vector(x_v) - data, amb rows.  SE3: the caller's order, x_v the
-    // prepared pose, J = the first six columns of I7.  SE2: sorted by vertex (stable), x_v = [x, y, theta], J = I3.  SO3: sorted
+    // PriorFactor blocks (prior_factor.rs:96-108): r = to_vector(x_v) - data, amb rows.  SE3: the caller's order (row-owned
+    // handle: sorted by vertex, stable), x_v the prepared pose, J = the first six columns of I7.  SE2: sorted by vertex (stable), x_v = [x, y, theta], J = I3.  SO3: sorted
     // by vertex (stable), x_v the prepared quaternion, J = the first three columns of I4.
     int n_prior = 0;
     const uint32_t* prior_v = nullptr;    // [n_prior] vertex (device order)
     const double* prior_data = nullptr;   // [n_prior][prior stride]: data (amb) | the block's Huber delta (<= 0: none)
-    // the row-owned manifolds only (null for SE3)
+    // row-owned handles only (null on an SE3 handle without the option "row_owned_assembly")
     const double* poses = nullptr;        // [n_v][amb] the stored vertices (what an SE2 prior sees: x y theta)
     const int* inc_ptr = nullptr;         // [n_v + 1] incident-edge CSR of the row-owned assembly (pg2_lists.h)
     const uint32_t* inc_edge = nullptr;
@@ -53,9 +55,11 @@ struct PGView {
 void launch_pg_prepare(int manifold, int64_t n, const double* poses, double* posep, hipStream_t s);
 // H (tiles, lower triangle) += J^T J, g += J^T r over the edges, then the prior blocks' J^T J (sc^2 on the diagonal entries
 // of the vertex) and J^T r; tiles and g zeroed by the caller.  Two launches, and two algorithms:
-//   SE3  k_pg_edges + k_pg_priors      edge-major, fp64 atomics, priors in the caller's order
-//   SE2, SO3  k_pg2_assemble + k_pg2_priors row-owned, no atomics, a fixed order of summation per destination
-void launch_pg_assemble(int manifold, const PGView& v, const TileMap& tm, double* g, hipStream_t s);
+//   row_owned false (SE3 only)  k_pg_edges + k_pg_priors   edge-major, fp64 atomics, priors in the caller's order
+//   row_owned true   SE2, SO3   k_pg2_assemble + k_pg2_priors   no atomics, a fixed order of summation per destination
+//                    SE3        k_pg6_assemble + k_pg2_priors   the same over 6 x 6 blocks
+// row_owned is the handle's property: the view must carry inc_ptr / inc_edge and priors sorted by vertex when it is true.
+void launch_pg_assemble(int manifold, bool row_owned, const PGView& v, const TileMap& tm, double* g, hipStream_t s);
 // corrected prior residuals [n_prior][amb], the caller's order
 void launch_pg_prior_export(int manifold, const PGView& v, double* r_out, hipStream_t s);
 void launch_pg_cost(int manifold, const PGView& v, double* partial, int n_partial, double* out_sumsq, hipStream_t s);

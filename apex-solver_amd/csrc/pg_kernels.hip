@@ -9,7 +9,8 @@
 //   k_pg_jv_gram<M>       edge-major    |J a|^2, (J a).(J b), |J b|^2 matrix-free: the products with H = J^T J the Dog-Leg step needs
 //                                       (dog_leg.rs:776-803, 948-960) once the tiles hold L instead of H; the rest of a Dog-Leg
 //                                       step runs on plain vectors and lives in dogleg_kernels.hip
-// The assembly is one algorithm per block size -- SE3 (6 x 6) edge-major, the 3-DOF manifolds SE2 and SO3 row-owned:
+// Two assemblies.  The 3-DOF manifolds SE2 and SO3 are always row-owned; SE3 (6 x 6) is edge-major by default and row-owned
+// on a handle given the option "row_owned_assembly" (launch_pg_assemble takes the handle's flag):
 //   k_pg_edges      SE3  edge-major    r, dr/dk0, dr/dk1 per edge in registers (never written to memory), loss correction,
 //                                      then H_aa += Ja^T Ja, H_bb += Jb^T Jb, H_(hi,lo) += J_hi^T J_lo, g_a += Ja^T r,
 //                                      g_b += Jb^T r with fp64 atomics (SparseCholeskySolver's J^T J and J^T r,
@@ -20,7 +21,9 @@
 //                                      one writer, so there are no atomics and every sum has a fixed order: two
 //                                      assemblies of one state are bit-identical.  An edge is linearised by both of its
 //                                      endpoints (a few dozen flops) instead of scattering 24-byte segments atomically.
-//   k_pg2_priors<M>    SE2, SO3  one lane per run of prior blocks on one vertex (the blocks arrive sorted by vertex)
+//   k_pg6_assemble<LP> SE3 under the option  vertex-major  the same over 6 x 6 blocks (pg_row_assemble6): every product formed as
+//                                      k_pg_edges forms it, summed in list order instead of by atomics
+//   k_pg2_priors<M>    every row-owned handle  one lane per run of prior blocks on one vertex (the blocks arrive sorted by vertex)
 // Every kernel that linearises edges is instantiated per loss policy (pg_device.hpp): LossLegacy (huber_delta), LossGeneral
 // (PgLoss), LossWeighted (PgLoss and the edge information matrices of PGView::info).
 //
@@ -304,29 +307,60 @@ __global__ __launch_bounds__(256) void k_pg2_assemble(PGView v, TileMap tm, doub
     for (int a = 0; a < 3; ++a) g[3 * (size_t)row + a] = gv[a];
 }
 
-// (a prior block has M::kAmb rows over the vertex's three columns: J~ = sc times the first three columns of I, so rows past
-// the third -- SO3's fourth -- count in the cost only)
+// (a prior block has M::kAmb rows over the vertex's M::kDof columns: J~ = sc times the first kDof columns of I, so rows past
+// them -- SO3's fourth, SE3's seventh -- count in the cost only)
 template <class M>
 __global__ __launch_bounds__(64) void k_pg2_priors(PGView v, TileMap tm, double* __restrict__ g) {
+    constexpr int D = M::kDof;
     const int k = blockIdx.x * 64 + threadIdx.x;
     if (k >= v.n_prior) return;
     const uint32_t a = v.prior_v[k];
     if (k > 0 && v.prior_v[k - 1] == a) return;   // the first block of a vertex sums the whole run, in order
-    double h = 0.0, gv[3] = {0.0, 0.0, 0.0};
+    double h = 0.0, gv[D] = {};
     for (int j = k; j < v.n_prior && v.prior_v[j] == a; ++j) {
         double r[M::kAmb];
-        const double sc = prior_at<M>(v, j, r);   // J~ = sc I3: J~^T J~ = sc^2 I3, J~^T r~ = sc r~
+        const double sc = prior_at<M>(v, j, r);   // J~ = sc [I_D; 0]: J~^T J~ = sc^2 I_D, J~^T r~ = sc r~[0..D)
         h += sc * sc;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) gv[i] += sc * r[i];
+        for (int i = 0; i < D; ++i) gv[i] += sc * r[i];
     }
-    double* blk = h_block_ptr<3>(tm, a, a);
+    double* blk = h_block_ptr<D>(tm, a, a);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < D; ++i) {
         blk[i * kNB + i] += h;
-        g[3 * (size_t)a + i] += gv[i];
+        g[D * (size_t)a + i] += gv[i];
     }
 }
+
+// ---- SE3 assembly, row-owned (option "row_owned_assembly") -------------------------------------------------------
+// Lane v walks the edges incident to v (pg_row_assemble6, pg_device.hpp): the diagonal block's lower triangle by plain
+// read-add-write on top of the damping, the blocks (v, u), u < v, in full by plain read-add-write, g_v by a plain store.  kB:
+// the workgroup size the instantiation is launched with (kRowBlock below); the per-lane state of a 6 x 6 row is what sets it.
+template <class LP, int kB>
+__global__ __launch_bounds__(kB) void k_pg6_assemble(PGView v, TileMap tm, double* __restrict__ g) {
+    const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
+    if (i >= v.n_v) return;
+    const uint32_t row = (uint32_t)i;
+    double H[36], gv[6];
+    const auto add_off = [&](uint32_t u, const double* B) {
+        double* blk = h_block_ptr<6>(tm, row, u);
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = 0; b < 6; ++b) blk[a * kNB + b] += B[6 * a + b];
+    };
+    pg_row_assemble6<LP>(row, v.posep, v.meas, v.e_from, v.e_to, v.inc_ptr, v.inc_edge, v.info, loss_param<LP>(v), H, gv, add_off);
+    double* blk = h_block_ptr<6>(tm, row, row);   // (on top of the damping add_diag has put there)
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = 0; b <= a; ++b) blk[a * kNB + b] += H[6 * a + b];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) g[6 * (size_t)row + a] = gv[a];
+}
+// lanes per workgroup of k_pg6_assemble<LP>: the largest at which the instantiation keeps its row in registers (no scratch)
+template <class LP>
+constexpr int kRowBlock = 256;
 
 // ---- the kernels both manifolds share ------------------------------------------------------------------------------
 template <class M>
@@ -495,20 +529,24 @@ void launch_pg_prepare(int manifold, int64_t n, const double* poses, double* pos
         hipLaunchKernelGGL(k_pg_prepare<decltype(M)>, dim3(grid256(n)), dim3(256), 0, s, n, poses, posep);
     });
 }
-void launch_pg_assemble(int manifold, const PGView& v, const TileMap& tm, double* g, hipStream_t s) {
+void launch_pg_assemble(int manifold, bool row_owned, const PGView& v, const TileMap& tm, double* g, hipStream_t s) {
     const dim3 prior_grid((v.n_prior + 63) / 64);
-    if (pg_row_owned(manifold)) {
+    if (row_owned) {
         with_manifold(manifold, [&](auto M) {
             using Man = decltype(M);
-            if constexpr (Man::kDof == 3) {   // (the row-owned kernels exist for the 3-DOF manifolds only: SE3 never gets here)
-                if (v.n_v > 0)
-                    with_loss(v, [&](auto LP) {
-                        hipLaunchKernelGGL((k_pg2_assemble<Man, decltype(LP)>), dim3(grid256(v.n_v)), dim3(256), 0, s, v, tm, g);
-                    });
-                if (v.n_prior > 0) hipLaunchKernelGGL(k_pg2_priors<Man>, prior_grid, dim3(64), 0, s, v, tm, g);
-            }
+            if (v.n_v > 0)
+                with_loss(v, [&](auto LP) {
+                    using L = decltype(LP);
+                    if constexpr (Man::kDof == 3) {
+                        hipLaunchKernelGGL((k_pg2_assemble<Man, L>), dim3(grid256(v.n_v)), dim3(256), 0, s, v, tm, g);
+                    } else {
+                        constexpr int B = kRowBlock<L>;
+                        hipLaunchKernelGGL((k_pg6_assemble<L, B>), dim3((unsigned)((v.n_v + B - 1) / B)), dim3(B), 0, s, v, tm, g);
+                    }
+                });
+            if (v.n_prior > 0) hipLaunchKernelGGL(k_pg2_priors<Man>, prior_grid, dim3(64), 0, s, v, tm, g);
         });
-    } else {
+    } else {   // (SE3 only: pg_row_owned(manifold) handles are never assembled here)
         if (v.n_e > 0)
             with_loss(v, [&](auto LP) {
                 hipLaunchKernelGGL(k_pg_edges<decltype(LP)>, dim3(grid256(v.n_e)), dim3(256), 0, s, v, tm, g);

@@ -10,9 +10,11 @@
 // scaling, covariance, exports) does not care what a vertex is: it sees dof_ tangent columns and amb_ stored doubles per
 // vertex, kNB / dof_ vertices per tile.  Only prepare / assemble / priors / cost / retract / exports differ, and the
 // launchers of pg_kernels.h take manifold_ for that: the same kernels instantiated for Se3Manifold (6, 7), Se2Manifold
-// (3, 3) or So3Manifold (3, 4), and one assembly per block size -- SE3 the atomic edge scatter, the 3-DOF manifolds SE2 and
-// SO3 (rotation averaging, BetweenFactor<SO3>: between_factor.rs:13,55) the row-owned assembly over the incident-edge lists
-// of pg2_lists.h, which live with the structure of the row-owned manifolds only (pg_row_owned).
+// (3, 3) or So3Manifold (3, 4), and two assemblies -- the 3-DOF manifolds SE2 and SO3 (rotation averaging,
+// BetweenFactor<SO3>: between_factor.rs:13,55) always the row-owned assembly over the incident-edge lists of pg2_lists.h, SE3
+// the atomic edge scatter by default and the row-owned assembly (bit-reproducible runs) under the option
+// "row_owned_assembly".  Row-owned is a property of the handle (row_owned_), fixed by set_structure: the lists, the sorted
+// priors and their slots live with the structure of row-owned handles only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -75,6 +77,14 @@ class PoseGraphSolver : public TileBackend {
     // no valid factor is held (no solve yet, or an export / assembly since).
     int covariance(double* out);
 
+    // "row_owned_assembly": read by the next set_structure.  false on a manifold that has the row-owned assembly only.
+    bool set_row_owned_option(bool on) {
+        if (!on && pg_row_owned(manifold_)) return false;
+        opt_row_owned_ = on;
+        return true;
+    }
+    bool row_owned() const { return row_owned_; }
+
     int64_t n_vertices() const { return n_v_; }
     int manifold() const { return manifold_; }
     int dof() const { return dof_; }           // tangent columns per vertex: 6 | 3 | 3
@@ -115,13 +125,15 @@ class PoseGraphSolver : public TileBackend {
     bool loss_set_ = false;   // set_loss has replaced huber_delta_ (until the next set_structure)
     PgLoss loss_;             // kLossNone unless loss_set_
     bool have_structure_ = false, have_params_ = false;
+    bool opt_row_owned_ = false;   // the option as last set; becomes row_owned_ at set_structure
+    bool row_owned_;               // this structure is assembled row-owned: the manifold is (pg_row_owned) or the option was set
     std::vector<int> vmap_;  // caller's vertex -> internal vertex
     ColumnMap map_;          // ... and per tangent column: the caller's pose_col against the internal order (column_map.h)
     DeviceBuffer<double> poses_[2], posep_[2];
     DeviceBuffer<uint32_t> e_from_, e_to_;
     int n_prior_ = 0;
     DeviceBuffer<uint32_t> prior_v_;
-    DeviceBuffer<int> inc_ptr_, prior_slot_;   // the row-owned manifolds only: incident-edge CSR, the caller's index of each sorted prior
+    DeviceBuffer<int> inc_ptr_, prior_slot_;   // row-owned handles only: incident-edge CSR, the caller's index of each sorted prior
     DeviceBuffer<uint32_t> inc_edge_;
     DeviceBuffer<double> prior_data_;
     DeviceBuffer<double> prior_res_;   // staging of get_prior_residual

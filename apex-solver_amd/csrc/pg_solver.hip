@@ -30,14 +30,14 @@ int known_manifold(int manifold) { return manifold == kManifoldSE2 || manifold =
 PoseGraphSolver::PoseGraphSolver(int64_t n_v, int64_t n_e, int device, int manifold)
     : TileBackend(device, kPgNumStages, /*nd_leaf=*/2, kPgStats, /*n_partial=*/256), n_v_(n_v), n_e_(n_e), manifold_(known_manifold(manifold)),
       dof_(manifold_sizes(manifold_).dof), amb_(manifold_sizes(manifold_).amb), stride_(manifold_sizes(manifold_).stride),
-      prior_stride_(manifold_sizes(manifold_).prior_stride), vpt_(kNB / dof_) {}
+      prior_stride_(manifold_sizes(manifold_).prior_stride), vpt_(kNB / dof_), row_owned_(pg_row_owned(manifold_)) {}
 
 PoseGraphSolver::~PoseGraphSolver() {
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);   // before any buffer is freed; stream_last_ destroys the stream after them
 }
 
-// (the members of the row-owned manifolds are empty buffers, so null, on an SE3 graph)
+// (the members of a row-owned handle are empty buffers, so null, on an SE3 graph assembled with atomics)
 PGView PoseGraphSolver::view(int which) const {
     PGView v;
     v.n_v = n_v_; v.n_e = n_e_;
@@ -57,7 +57,7 @@ PGView PoseGraphSolver::view(int which) const {
         else if (huber_delta_ > 0.0) (void)pg_loss_make(kLossHuber, huber_delta_, 0.0, &v.loss);
     }
     v.n_prior = n_prior_; v.prior_v = prior_v_; v.prior_data = prior_data_;
-    if (pg_row_owned(manifold_)) {
+    if (row_owned_) {
         v.poses = poses_[which]; v.inc_ptr = inc_ptr_; v.inc_edge = inc_edge_; v.prior_slot = prior_slot_;
     }
     return v;
@@ -95,11 +95,11 @@ int PoseGraphSolver::set_priors(int64_t n, const uint32_t* vertex, const double*
     if (n == 0) return install();
     std::vector<uint32_t> hv((size_t)n);
     std::vector<double> hd((size_t)n * prior_stride_, 0.0);
-    // SE2, SO3: the blocks go to the device sorted by vertex (stable), so that one lane sums the run of a vertex in a fixed
-    // order (k_pg2_priors); prior_slot_ keeps the caller's index for the export.  SE3: the caller's order, as ever.
+    // Row-owned handles: the blocks go to the device sorted by vertex (stable), so that one lane sums the run of a vertex in a
+    // fixed order (k_pg2_priors); prior_slot_ keeps the caller's index for the export.  SE3 with atomics: the caller's order, as ever.
     std::vector<int> order((size_t)n);
     std::iota(order.begin(), order.end(), 0);
-    if (pg_row_owned(manifold_))
+    if (row_owned_)
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return vmap_[vertex[a]] < vmap_[vertex[b]]; });
     for (int64_t k = 0; k < n; ++k) {
         const int src = order[k];
@@ -107,7 +107,7 @@ int PoseGraphSolver::set_priors(int64_t n, const uint32_t* vertex, const double*
         memcpy(hd.data() + (size_t)k * prior_stride_, data7 + (size_t)amb_ * src, amb_ * sizeof(double));
         hd[(size_t)k * prior_stride_ + amb_] = huber_delta ? huber_delta[src] : -1.0;
     }
-    if (pg_row_owned(manifold_)) HIP_TRY(new_slot.upload(order));
+    if (row_owned_) HIP_TRY(new_slot.upload(order));
     HIP_TRY(new_v.upload(hv));
     HIP_TRY(new_data.upload(hd));
     return install();
@@ -257,7 +257,16 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
     }
     std::vector<uint8_t> fx((size_t)dof_ * n_v_, 0);
     if (fix6) blocks_to_internal(vmap_, dof_, fix6, fx.data());
-    if (pg_row_owned(manifold_)) {   // the row-owned assembly walks each vertex's incident edges
+    // Row-owned from here on: the manifold's only assembly, or the option as it stands now.  Prior blocks are stored in the
+    // order of the assembly they were given for, so a structure that changes the assembly starts without them.
+    const bool row_owned = pg_row_owned(manifold_) || opt_row_owned_;
+    if (row_owned != row_owned_) {
+        prior_v_.reset(); prior_data_.reset(); prior_slot_.reset(); prior_res_.reset();
+        n_prior_ = 0;
+    }
+    row_owned_ = row_owned;
+    inc_ptr_.reset(); inc_edge_.reset();
+    if (row_owned_) {   // the row-owned assembly walks each vertex's incident edges
         IncidentLists inc;
         if (!build_incident_lists(n_v_, n_e_, ef.data(), et.data(), &inc)) return fail(kInvalidInput, "incident-edge lists: out of range");
         HIP_TRY(inc_ptr_.upload(inc.ptr));
@@ -331,7 +340,7 @@ int PoseGraphSolver::assemble(double lambda) {
     HIP_TRY(tp_.zero_tiles());
     HIP_TRY(hipMemsetAsync(g_, 0, n_pad_ * sizeof(double), stream_));
     tp_.add_diag((int)n_, scaled_ ? 0.0 : lambda, 1.0);  // lambda on the real rows, identity on the padding rows
-    launch_pg_assemble(manifold_, view(st_.cur), tp_.tilemap(), g_, stream_);
+    launch_pg_assemble(manifold_, row_owned_, view(st_.cur), tp_.tilemap(), g_, stream_);
     if (scaled_) {  // Jacobi scaling: H := D H D, then the damping of the scaled system
         tp_.scale_sym(scale_.dev);
         tp_.add_diag((int)n_, lambda, 1.0);

@@ -824,7 +824,14 @@ int apexgpu_pg_covariance(apexgpu_pg_solver* h, double* cov_out /* n_v*36 | n_v*
 int apexgpu_pg_covariance_stats(apexgpu_pg_solver* h, double out[6], double* group_ms, int group_cap);   /* as apexgpu_covariance_stats */
 
 /* name: "graphs" (hipGraph replay of factor / solves), "update_overlap" (second stream for trailing updates),
- * "tri_dataflow" (triangular sweeps as one dataflow launch each), "nested_dissection" (0 off, 1 on, > 1 leaf size; before apexgpu_pg_set_structure) */
+ * "tri_dataflow" (triangular sweeps as one dataflow launch each), "nested_dissection" (0 off, 1 on, > 1 leaf size; before apexgpu_pg_set_structure),
+ * "row_owned_assembly" (0 | 1, default 0; read by the next apexgpu_pg_set_structure, a later change waits for the one after):
+ *   1 on an SE3 handle assembles H and g row-owned -- one lane per vertex walks its incident edges, no atomics, every sum in a
+ *   fixed order -- so two assemblies of one state, and two runs of one problem, are bit-identical.  Every product is formed as
+ *   the default assembly forms it; only the order of the sums differs, so results agree with the default to rounding, not to
+ *   the bit.  0 is the atomic edge scatter, whose sums change order from launch to launch.  SE2 and SO3 handles are always
+ *   row-owned: they accept 1 (nothing changes) and refuse 0 with APEXGPU_ERR_INVALID_INPUT, as any value but 0 and 1 is.
+ *   A structure set under a different value than the one before it drops the prior blocks (they are stored in the assembly's order). */
 int apexgpu_pg_set_option(apexgpu_pg_solver* h, const char* name, int value);
 #define APEXGPU_PG_NUM_STAGES 6 /* assemble, factor, tri_solve, step_stats, retract, cost */
 int apexgpu_pg_enable_stage_timing(apexgpu_pg_solver* h, int on);
