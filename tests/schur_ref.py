@@ -91,9 +91,10 @@ def _n2(a):
 
 
 class SchurRef:
-    """The Schur system of one linearisation in `dtype`.  dense=False leaves out S (S4, M, P): vectors and matvec only."""
+    """The Schur system of one linearisation in `dtype`.  dense=False leaves out S (S4, M, P): vectors and matvec only.
+    hinv_given = {landmark: 3 x 3}: H_ll^-1 of these landmarks is taken as given, not computed."""
 
-    def __init__(self, n_cam, n_pt, cam_idx, pt_idx, jc, jl, r, lam, dtype=LD, dense=True, chunk=20000):
+    def __init__(self, n_cam, n_pt, cam_idx, pt_idx, jc, jl, r, lam, dtype=LD, dense=True, chunk=20000, hinv_given=None):
         T = self.T = dtype
         self.n_cam, self.n_pt, self.lam = int(n_cam), int(n_pt), float(lam)
         ci = self.ci = np.asarray(cam_idx, dtype=np.int64); li = self.li = np.asarray(pt_idx, dtype=np.int64)
@@ -105,6 +106,8 @@ class SchurRef:
         self.Hll = _scatter(n_pt, li, np.einsum("kra,krb->kab", Jl, Jl), T) + T(lam) * eye_l
         self.gl = _scatter(n_pt, li, np.einsum("kra,kr->ka", Jl, rr), T)
         self.Hinv = inv3(self.Hll)
+        for l, h in (hinv_given or {}).items():       # a block inverse taken as given (landmark_cov_ref.py: a gated landmark)
+            self.Hinv[l] = np.asarray(h, dtype=T)
         W = self.W = np.einsum("kra,krb->kab", Jc, Jl)                         # (n_obs, dc, 3)
         self.TW = np.einsum("kab,kbc->kac", W, self.Hinv[li])                  # W_k Hll^-1
         self.gred = -self.gc + _scatter(n_cam, ci, np.einsum("kab,kb->ka", self.TW, self.gl[li]), T)
