@@ -55,6 +55,8 @@ SYMBOLS = (
     "apexgpu_pg_set_loss", "apexgpu_pg_get_loss", "apexgpu_loss_evaluate", "apexgpu_set_loss", "apexgpu_get_loss",
     # edge information matrices on pose graphs
     "apexgpu_pg_set_information", "apexgpu_pg_get_information", "apexgpu_g2o_problem_information",
+    # prior factors on camera poses and intrinsics in bundle adjustment
+    "apexgpu_set_pose_priors", "apexgpu_set_intrinsic_priors", "apexgpu_get_prior_residual",
 )
 MANIFOLD_SE3, MANIFOLD_SE2, MANIFOLD_SO3 = 0, 1, 2
 # (ambient, dof) per APEXGPU_MANIFOLD_*: stored doubles per vertex / measurement / prior, tangent columns per vertex
@@ -237,6 +239,9 @@ def load() -> C.CDLL:
     L.apexgpu_pg_get_prior_residual.argtypes = [vp, vp]
     L.apexgpu_pg_set_loss.argtypes = [vp, C.c_int, dbl, dbl]
     L.apexgpu_set_loss.argtypes = [vp, C.c_int, dbl, dbl]
+    L.apexgpu_set_pose_priors.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
+    L.apexgpu_set_intrinsic_priors.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
+    L.apexgpu_get_prior_residual.argtypes = [vp, vp, vp]
     L.apexgpu_get_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(dbl * 2)]
     L.apexgpu_pg_get_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(dbl * 2)]
     L.apexgpu_loss_evaluate.argtypes = [C.c_int, dbl, dbl, dbl, C.POINTER(dbl * 6)]

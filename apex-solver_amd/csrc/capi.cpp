@@ -182,6 +182,18 @@ int apexgpu_get_loss(const apexgpu_solver* h, int* kind, double out2[2]) {
     h->s->get_loss(kind, out2);
     return APEXGPU_OK;
 }
+int apexgpu_set_pose_priors(apexgpu_solver* h, int64_t n, const uint32_t* cam, const double* data7, const double* huber_delta, const double* weight) {
+    H_OR_FAIL;
+    return guarded([&] { return h->s->set_priors(false, n, cam, data7, huber_delta, weight); });
+}
+int apexgpu_set_intrinsic_priors(apexgpu_solver* h, int64_t n, const uint32_t* cam, const double* data3, const double* huber_delta, const double* weight) {
+    H_OR_FAIL;
+    return guarded([&] { return h->s->set_priors(true, n, cam, data3, huber_delta, weight); });
+}
+int apexgpu_get_prior_residual(apexgpu_solver* h, double* pose_r7_out, double* intr_r3_out) {
+    H_OR_FAIL;
+    return guarded([&] { return h->s->get_prior_residual(pose_r7_out, intr_r3_out); });
+}
 int apexgpu_get_params(apexgpu_solver* h, double* poses, double* intr, double* points) {
     H_OR_FAIL;
     if (!poses || !intr || !points) return APEXGPU_ERR_INVALID_INPUT;

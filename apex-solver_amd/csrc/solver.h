@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "ba_kernels.h"
+#include "ba_prior_kernels.h"
 #include "chol_kernels.h"
 #include "pcg_kernels.h"
 #include "pcg_readback.h"
@@ -42,6 +43,16 @@ class Solver : public TileBackend {
     // the landmark covariance's linearisation, as set_params does.
     int set_loss(int kind, double p0, double p1);
     void get_loss(int* kind, double out2[2]) const;
+    // PriorFactor blocks on camera poses (intr false: data [tx,ty,tz,qw,qx,qy,qz], seven rows over the six pose columns) or on
+    // camera intrinsics (intr true: data [f,k1,k2]; nine-column handles only), beside the projection factors (DESIGN.md §17;
+    // prior_factor.rs:93-105 as PoseGraphSolver::set_priors restates it, plus a scalar weight w per block: r <- w r, J <- w J).
+    // huber_delta / weight may be NULL (none / 1).  Replaces the set of its kind, n = 0 clears it; set_structure clears both.
+    // Voids a pending trial step, the Dog-Leg cache and the factor the covariance calls read.  kInvalidInput (nothing changes): a
+    // camera that does not exist, a NaN, a weight that is not finite and positive, intrinsics priors on a six-column handle.
+    // kInvalidState: before set_structure, and on a sharded handle (multi-rank priors are not built).
+    int set_priors(bool intr, int64_t n, const uint32_t* cam, const double* data, const double* huber_delta, const double* weight);
+    int get_prior_residual(double* pose_r7_out, double* intr_r3_out);   // corrected, the caller's order; either may be NULL
+    int64_t n_priors(bool intr) const { return intr ? intr_pri_.n : pose_pri_.n; }
     int set_params(const double* poses, const double* intr, const double* points);
     int get_params(double* poses, double* intr, double* points);
     void set_cg_params(int max_iter, double tol) { cg_max_iter_ = max_iter; cg_tol_ = tol; }
@@ -188,6 +199,11 @@ class Solver : public TileBackend {
     int assemble_implicit(double lambda);
     int implicit_pcg_solve(double lambda, int max_iter, double tol);
     int implicit_matvec(const double* x, double lam_local, double* y, bool reduce);
+    // the prior add-ons (ba_prior_kernels.h), each enqueued behind the kernel it extends and only when a set is non-empty
+    bool have_priors() const { return pose_pri_.n > 0 || intr_pri_.n > 0; }
+    BaPriorView prior_view() const;
+    void enqueue_prior_eval(int which, bool cost_only);            // -> pri_diag_, pri_g_ (unless cost_only), pri_cost_ of parameter set `which`
+    void enqueue_prior_cost(int which, double* sumsq);             // *sumsq += the prior rows' squares at set `which`
     int column_norms_sq_device();   // -> n2 in cam_scale_.dev / pt_scale_.dev (camera part all-reduced over the shards)
     int factor_with_ladder(double lambda);
     int ladder(double lambda);
@@ -323,6 +339,15 @@ class Solver : public TileBackend {
     DeviceBuffer<uint8_t> lam_mask_;  // tree sharding: cameras whose diagonal block gets lambda on this rank
     DeviceBuffer<double> pcg_buf_;                 // 7 vectors of n_c_pad
     DeviceBuffer<double> lmu_, sd_, minv_;  // matrix-free variant: {pt, u_l} records, diag blocks of S, their inverses
+    // PriorFactor blocks on the cameras: each set sorted by internal camera (stable) with a CSR over the cameras; the vectors of
+    // the last evaluation -- diag(P) and P's gradient over the camera columns [n_c_pad], the cost per camera [n_cam]
+    struct PriorSet {
+        int n = 0;
+        DeviceBuffer<int> ptr, slot, cam;
+        DeviceBuffer<double> data;
+    };
+    PriorSet pose_pri_, intr_pri_;
+    DeviceBuffer<double> pri_diag_, pri_g_, pri_cost_, pri_res_;
     JacobiScaling cam_scale_, pt_scale_;   // Jacobi scaling, internal order ([n_c_pad] with 1 on the padding, [3 n_pt]); on: TileBackend::scaled_
     bool use_graphs_ = true;
     double setup_s_[6] = {0, 0, 0, 0, 0, 0};  // set_structure by phase: order + tile structure, landmark / camera lists, tile plan, Schur lists, uploads, total

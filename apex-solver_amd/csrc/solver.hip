@@ -100,6 +100,7 @@ void Solver::stage_begin(int st) { timer_.begin(st, stream_); }
 void Solver::stage_end(int st) { timer_.end(st, stream_); }
 
 int Solver::set_shard(int rank, int world) {
+    if (have_priors()) return fail(kInvalidState, "set_shard: the handle holds camera priors, which are single-rank only");
     if (have_structure_) return fail(kInvalidState, "set_shard must precede set_structure");
     if (world < 1 || rank < 0 || rank >= world) return fail(kInvalidInput, "bad rank/world");
     rank_ = rank; world_ = world;
@@ -485,6 +486,8 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     if (n_cam_ <= 0 || n_pt_ <= 0) return fail(kInvalidInput, n_cam_ <= 0 ? "No camera variables found" : "No landmark variables found");
     if (n_obs_ < 0 || n_obs_ > 2000000000LL) return fail(kInvalidInput, "observation count out of range");
     lc_release();   // (the landmark covariance lists belong to the old structure)
+    pose_pri_ = PriorSet{}; intr_pri_ = PriorSet{};   // (and so do the priors: camera indices of the old problem)
+    pri_diag_.reset(); pri_g_.reset(); pri_cost_.reset(); pri_res_.reset();
     Setup su;   // (its destructor releases and joins whatever thread is still out, on every return below)
     su.cam_idx = cam_idx; su.pt_idx = pt_idx; su.obs_uv = obs_uv;
     su.intr_col = intr_col; su.pose_col = pose_col; su.pt_col = pt_col;
@@ -624,6 +627,98 @@ void Solver::get_loss(int* kind, double out2[2]) const {
     else *kind = kLossNone;
 }
 
+// ---------------------------------------------------------------------------------------------
+// PriorFactor blocks on the cameras
+// ---------------------------------------------------------------------------------------------
+int Solver::set_priors(bool intr, int64_t n, const uint32_t* cam, const double* data, const double* huber_delta, const double* weight) {
+    const char* what = intr ? "set_intrinsic_priors" : "set_pose_priors";
+    if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
+    if (world_ > 1 || tp_.distributed()) return fail(kInvalidState, std::string(what) + ": camera priors are single-rank only (this handle is sharded)");
+    if (n < 0 || n > (1 << 24)) return fail(kInvalidInput, std::string(what) + ": prior count out of range");
+    if (n > 0 && (!cam || !data)) return fail(kInvalidInput, std::string(what) + ": cam / data are NULL");
+    if (intr && n > 0 && dc_ != 9)
+        return fail(kInvalidInput, "set_intrinsic_priors: this handle optimises six columns per camera; the intrinsics have no columns on the device");
+    const int amb = intr ? 3 : 7, stride = intr ? kIntrPriorStride : kPosePriorStride;
+    for (int64_t k = 0; k < n; ++k) {
+        if ((int64_t)cam[k] >= n_cam_) return fail(kInvalidInput, std::string(what) + ": prior " + std::to_string(k) + " is on a camera that does not exist");
+        for (int a = 0; a < amb; ++a)
+            if (std::isnan(data[amb * k + a])) return fail(kInvalidInput, std::string(what) + ": prior " + std::to_string(k) + " has NaN data");
+        if (huber_delta && std::isnan(huber_delta[k])) return fail(kInvalidInput, std::string(what) + ": prior " + std::to_string(k) + " has a NaN Huber delta");
+        if (weight && !(std::isfinite(weight[k]) && weight[k] > 0.0))
+            return fail(kInvalidInput, std::string(what) + ": the weight of prior " + std::to_string(k) + " must be finite and positive");
+    }
+    HIP_TRY(hipSetDevice(device_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    // The new set goes up into a local and replaces the member only when every upload has succeeded (as PoseGraphSolver::set_priors)
+    PriorSet ns;
+    if (n > 0) {
+        // sorted by internal camera (stable): one lane sums a camera's run in the caller's order; slot keeps the caller's index
+        std::vector<int> order((size_t)n), hc((size_t)n), ptr((size_t)n_cam_ + 1, 0);
+        std::iota(order.begin(), order.end(), 0);
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cmap_[cam[a]] < cmap_[cam[b]]; });
+        std::vector<double> hd((size_t)n * stride, 0.0);
+        for (int64_t k = 0; k < n; ++k) {
+            const int src = order[k];
+            hc[k] = cmap_[cam[src]];
+            ptr[hc[k] + 1]++;
+            double* d = hd.data() + (size_t)k * stride;
+            memcpy(d, data + (size_t)amb * src, amb * sizeof(double));
+            d[amb] = huber_delta ? huber_delta[src] : -1.0;
+            d[amb + 1] = weight ? weight[src] : 1.0;
+        }
+        for (int64_t c = 0; c < n_cam_; ++c) ptr[c + 1] += ptr[c];
+        HIP_TRY(ns.ptr.upload(ptr));
+        HIP_TRY(ns.slot.upload(order));
+        HIP_TRY(ns.cam.upload(hc));
+        HIP_TRY(ns.data.upload(hd));
+        ns.n = (int)n;
+        if (!pri_diag_) {
+            HIP_TRY(pri_diag_.alloc_zero(n_c_pad_));
+            HIP_TRY(pri_g_.alloc_zero(n_c_pad_));
+            HIP_TRY(pri_cost_.alloc_zero(n_cam_));
+            HIP_TRY(hipDeviceSynchronize());   // (null-stream memsets ahead of the work on stream_)
+        }
+    }
+    (intr ? intr_pri_ : pose_pri_) = std::move(ns);
+    pri_res_.reset();   // (sized by the old counts)
+    st_.invalidate();
+    drop_dogleg_cache();
+    tp_.set_factor_valid(false);   // (the factor is of a system without these rows)
+    factor_lin_ = -1;
+    return kOk;
+}
+
+BaPriorView Solver::prior_view() const {
+    BaPriorView pv;
+    pv.n_pose = pose_pri_.n; pv.pose_ptr = pose_pri_.ptr; pv.pose_data = pose_pri_.data; pv.pose_slot = pose_pri_.slot; pv.pose_cam = pose_pri_.cam;
+    pv.n_intr = intr_pri_.n; pv.intr_ptr = intr_pri_.ptr; pv.intr_data = intr_pri_.data; pv.intr_slot = intr_pri_.slot; pv.intr_cam = intr_pri_.cam;
+    return pv;
+}
+
+void Solver::enqueue_prior_eval(int which, bool cost_only) {
+    launch_ba_prior_eval(dc_, n_cam_, camp_[which] + (size_t)kCamStride * n_cam_, prior_view(), cost_only ? nullptr : pri_diag_.get(),
+                         cost_only ? nullptr : pri_g_.get(), pri_cost_, stream_);
+}
+
+void Solver::enqueue_prior_cost(int which, double* sumsq) {
+    enqueue_prior_eval(which, true);
+    launch_ba_prior_cost_add(n_cam_, pri_cost_, sumsq, stream_);
+}
+
+int Solver::get_prior_residual(double* pose_r7_out, double* intr_r3_out) {
+    if (!have_params_) return fail(kInvalidState, "no parameters set");
+    if (!have_priors()) return kOk;
+    HIP_TRY(hipSetDevice(device_));
+    const size_t np = 7 * (size_t)pose_pri_.n, ni = 3 * (size_t)intr_pri_.n;
+    if (!pri_res_) HIP_TRY(pri_res_.alloc(std::max<size_t>(np + ni, 1)));   // kept with the priors (set_priors frees it)
+    launch_ba_prior_export(camp_[st_.cur] + (size_t)kCamStride * n_cam_, prior_view(), pri_res_, pri_res_ + np, stream_);
+    HIP_TRY(hipGetLastError());
+    if (pose_r7_out && np) HIP_TRY(hipMemcpyAsync(pose_r7_out, pri_res_, np * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    if (intr_r3_out && ni) HIP_TRY(hipMemcpyAsync(intr_r3_out, pri_res_ + np, ni * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    return kOk;
+}
+
 int Solver::get_params(double* poses, double* intr, double* points) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
@@ -667,6 +762,7 @@ int Solver::cost(double* out) {
     launch_cost(view(st_.cur), partial_, n_partial_, scal_, stream_, general_loss());
     if (comm_ && world_ > 1)
         COMM_TRY(comm_->all_reduce_sum(scal_, 1, stream_));
+    if (have_priors()) enqueue_prior_cost(st_.cur, scal_);
     stage_end(kStCost);
     HIP_TRY(hipGetLastError());
     double ss = 0.0;
@@ -730,6 +826,10 @@ int Solver::assemble_local(double lambda, double diag_extra, bool for_factor) {
     stage_begin(kStAssembleCam);
     launch_cam_reduce(dc_, v, tm, cam_ptr_, cam_obs_, lambda + diag_extra, rank_ == 0 ? 1 : 0, hinv_, g_l_, 1,
                       g_c_, g_red_, stream_, general_loss());
+    if (have_priors()) {   // the prior rows of the Jacobian: block-diagonal in H_cc, so S and g_red take them as they are (before any rescaling)
+        enqueue_prior_eval(st_.cur, false);
+        launch_ba_prior_add_system(n_c_, pri_diag_, pri_g_, tm, g_c_, g_red_, stream_);
+    }
     stage_end(kStAssembleCam);
     stage_begin(kStScatter);
     launch_schur_pairs(dc_, v, tp_.tiles(), ptasks_, n_ptasks_, pchunks_, pblocks_, precs_, hinv_, stream_, orec_, pqdesc_);
@@ -846,6 +946,10 @@ int Solver::assemble_implicit(double lambda) {
     stage_begin(kStAssembleCam);
     launch_cam_reduce(dc_, v, tilemap(), cam_ptr_, cam_obs_, lambda, rank_ == 0 ? 1 : 0, hinv_, g_l_, 1, g_c_, g_red_, stream_, general_loss());
     launch_extract_diag_blocks(dc_, n_cam_, tilemap(), sd_, stream_);
+    if (have_priors()) {   // (single rank: nothing below sums these twice)
+        enqueue_prior_eval(st_.cur, false);
+        launch_ba_prior_add_blocks(dc_, n_cam_, pri_diag_, pri_g_, sd_, g_c_, g_red_, stream_);
+    }
     stage_end(kStAssembleCam);
     if (comm_ && world_ > 1) {
         stage_begin(kStAllReduce);
@@ -877,6 +981,7 @@ int Solver::implicit_matvec(const double* x, double lam_local, double* y, bool r
         xin = t;
     }
     launch_implicit_matvec(dc_, view(st_.cur), cam_ptr_, hinv_, lmu_, xin, lam_local, y, stream_, backsub_records(), general_loss());
+    if (have_priors()) launch_ba_prior_matvec(n_c_, pri_diag_, xin, y, stream_);   // (diag(P) of assemble_implicit's evaluation, in the unscaled variables)
     if (reduce && comm_ && world_ > 1)
         COMM_TRY(comm_->all_reduce_sum(y, (size_t)n_c_, stream_));
     if (scaled_) launch_vec_mul(n_c_, y, cam_scale_.dev, y, stream_);
@@ -1123,6 +1228,7 @@ int Solver::enqueue_trial_point(double* sumsq_out) {
     launch_cost(view(t), partial_, n_partial_, sumsq_out, stream_, general_loss());
     if (comm_ && world_ > 1)
         COMM_TRY(comm_->all_reduce_sum(sumsq_out, 1, stream_));
+    if (have_priors()) enqueue_prior_cost(t, sumsq_out);
     stage_end(kStCost);
     return kOk;
 }
@@ -1157,6 +1263,10 @@ int Solver::column_norms_sq_device() {
     HIP_TRY(hipMemsetAsync(cam_scale_.dev, 0, n_c_pad_ * sizeof(double), stream_));
     HIP_TRY(hipMemsetAsync(pt_scale_.dev, 0, std::max<int64_t>(3 * n_pt_, 1) * sizeof(double), stream_));
     launch_column_norms_sq(dc_, v, cam_scale_.dev, pt_scale_.dev, stream_, general_loss());
+    if (have_priors()) {   // a prior row has one entry per column: its square is diag(P)
+        enqueue_prior_eval(st_.cur, false);
+        launch_vec_add(n_c_, cam_scale_.dev, pri_diag_, cam_scale_.dev, stream_);
+    }
     if (comm_ && world_ > 1)  // every rank sees all cameras but only its own landmarks
         COMM_TRY(comm_->all_reduce_sum(cam_scale_.dev, (size_t)n_c_, stream_));
     return kOk;
@@ -1246,6 +1356,10 @@ int Solver::dogleg_segments(DlSegment out[2]) {
 void Solver::enqueue_jv_gram(const double* const a[2], const double* const b[2], double* out3) {
     static_assert(sizeof(PgLoss) % sizeof(double) == 0, "k_ba_jv_gram keeps the loss in doubles of LDS");
     launch_ba_jv_gram(dc_, view(st_.cur), a[0], a[1], b[0], b[1], partial_, n_partial_, out3, stream_, general_loss());
+    if (have_priors()) {
+        enqueue_prior_eval(st_.cur, false);
+        launch_ba_prior_gram_add(n_c_, pri_diag_, a[0], b[0], out3, stream_);
+    }
 }
 
 // solve_augmented(mu, 0) on a single rank, with dl_mode_ on: finish_step runs the tail, recover_factor leaves the ladder out
@@ -1404,6 +1518,16 @@ int Solver::get_hessian_csc(int64_t* nnz_out, int64_t* colptr, int64_t* rowidx, 
         cam_seen[cam_idx_h_[i]] = 1; pt_seen[pt_idx_h_[i]] = 1;
         if (k == 0 || pt_idx_h_[i] != pt_idx_h_[order[k - 1]] || cam_idx_h_[i] != cam_idx_h_[order[k - 1]]) ++n_cl;
     }
+    std::vector<double> pd;   // diag(P) of the camera priors, internal order: their cameras carry a diagonal block even when unobserved
+    if (have_priors()) {
+        enqueue_prior_eval(st_.cur, false);
+        pd.resize(n_c_);
+        HIP_TRY(hipMemcpyAsync(pd.data(), pri_diag_, n_c_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
+        HIP_TRY(hipStreamSynchronize(stream_));
+        for (int64_t c = 0; c < n_cam_; ++c)
+            for (int a = 0; a < dc_; ++a)
+                if (pd[(size_t)cmap_[c] * dc_ + a] != 0.0) cam_seen[c] = 1;
+    }
     int64_t nnz = 2 * n_cl * dc_ * 3;
     for (int64_t c = 0; c < n_cam_; ++c) if (cam_seen[c]) nnz += dc_ * dc_;
     for (int64_t l = 0; l < n_pt_; ++l) if (pt_seen[l]) nnz += 9;
@@ -1426,6 +1550,9 @@ int Solver::get_hessian_csc(int64_t* nnz_out, int64_t* colptr, int64_t* rowidx, 
             for (int a = 0; a < dc_; ++a)
                 for (int b = 0; b < dc_; ++b) H[a * dc_ + b] += J[a] * J[b] + J[dc_ + a] * J[dc_ + b];
         }
+        if (!pd.empty())
+            for (int64_t c = 0; c < n_cam_; ++c)
+                for (int a = 0; a < dc_; ++a) hcc[(size_t)c * dc_ * dc_ + a * dc_ + a] += pd[(size_t)cmap_[c] * dc_ + a];
         for (int64_t c = 0; c < n_cam_; ++c)
             if (cam_seen[c])
                 for (int a = 0; a < dc_; ++a)

@@ -156,6 +156,22 @@ class LevenbergMarquardtConfig:
             1 if self.use_jacobi_scaling else 0)
 
 
+def _prior_rows(cams, data, amb, huber_delta, weight):
+    cams = np.asarray(cams, dtype=np.int64).reshape(-1)
+    data = np.asarray(data, dtype=np.float64).reshape(len(cams), amb)
+    dl = np.broadcast_to(np.nan if huber_delta is None else np.asarray(huber_delta, dtype=np.float64), cams.shape)
+    w = np.broadcast_to(1.0 if weight is None else np.asarray(weight, dtype=np.float64), cams.shape)
+    return [(int(c), data[k].copy(), None if np.isnan(dl[k]) else float(dl[k]), float(w[k])) for k, c in enumerate(cams)]
+
+
+def _prior_arrays(priors, amb):
+    cam = np.ascontiguousarray([q[0] for q in priors], dtype=np.uint32)
+    data = np.ascontiguousarray([q[1] for q in priors], dtype=np.float64).reshape(-1, amb)
+    dl = np.ascontiguousarray([-1.0 if q[2] is None else float(q[2]) for q in priors], dtype=np.float64)
+    w = np.ascontiguousarray([q[3] for q in priors], dtype=np.float64)
+    return cam, data, dl, w
+
+
 @dataclass
 class Problem:
     """The factor graph bin/bundle_adjustment.rs builds: variables `pose_{i:04}` (SE3),
@@ -169,6 +185,10 @@ class Problem:
     fix_intr: np.ndarray = field(default=None)
     fix_pt: np.ndarray = field(default=None)
     loss: Loss | None = None   # the loss of every ProjectionFactor block; takes precedence over huber_delta
+    # PriorFactor blocks beside the projection factors: (camera index, data, huber delta or None, weight) each; data is
+    # [tx,ty,tz,qw,qx,qy,qz] for a pose prior and [f,k1,k2] for an intrinsics prior (SelfCalibration-like modes only)
+    pose_priors: list = field(default_factory=list)
+    intr_priors: list = field(default_factory=list)
 
     def __post_init__(self):
         d = self.data
@@ -203,6 +223,26 @@ class Problem:
         else:
             raise KeyError(name)
 
+    def add_pose_prior(self, cam: int, data7, huber_delta: float | None = None, weight: float = 1.0):
+        """PriorFactor on pose_{cam}: r = w (to_vector(pose) - data7), seven rows over the pose's six tangent columns; the
+        weight is a scalar square-root information (1: the reference's factor).  Several priors on one camera sum."""
+        self.pose_priors.append((int(cam), np.asarray(data7, dtype=np.float64).reshape(7), huber_delta, float(weight)))
+        return self
+
+    def add_intrinsic_prior(self, cam: int, data3, huber_delta: float | None = None, weight: float = 1.0):
+        """PriorFactor on intr_{cam}: r = w (intr - data3), J = w I3."""
+        self.intr_priors.append((int(cam), np.asarray(data3, dtype=np.float64).reshape(3), huber_delta, float(weight)))
+        return self
+
+    def add_pose_priors(self, cams, data7, huber_delta=None, weight=None):
+        """Bulk form: cams [n], data7 [n][7], huber_delta / weight scalars, arrays [n] or None."""
+        self.pose_priors.extend(_prior_rows(cams, data7, 7, huber_delta, weight))
+        return self
+
+    def add_intrinsic_priors(self, cams, data3, huber_delta=None, weight=None):
+        self.intr_priors.extend(_prior_rows(cams, data3, 3, huber_delta, weight))
+        return self
+
     @property
     def total_dof(self) -> int:
         return self.layout.total_dof
@@ -230,6 +270,7 @@ class GpuSchurComplementSolver:
         self._shard = None
         self._comm = None
         self._pre_options = {}
+        self._n_pose_priors = self._n_intr_priors = 0
 
     # builder methods (explicit_schur.rs:219-238)
     def with_variant(self, v: SchurVariant): self.variant = v; return self
@@ -281,6 +322,9 @@ class GpuSchurComplementSolver:
         self._problem = problem
         if problem.loss is not None:
             self.set_loss(problem.loss)
+        self._n_pose_priors = self._n_intr_priors = 0   # (set_structure cleared both sets)
+        if problem.pose_priors or problem.intr_priors:
+            self.set_priors(problem.pose_priors, problem.intr_priors)
         # wall time of this call by piece (seconds): handle + communicator, host-side argument arrays, apexgpu_set_structure
         self.setup_wall = dict(create_handle=t1 - t0, host_arrays=t2 - t1, set_structure=t3 - t2)
         return self
@@ -303,6 +347,9 @@ class GpuSchurComplementSolver:
         self._problem = problem
         if problem.loss is not None:
             self.set_loss(problem.loss)
+        self._n_pose_priors = self._n_intr_priors = 0   # (set_structure cleared both sets)
+        if problem.pose_priors or problem.intr_priors:
+            self.set_priors(problem.pose_priors, problem.intr_priors)
         return self
 
     def set_loss(self, loss: Loss | None):
@@ -319,6 +366,28 @@ class GpuSchurComplementSolver:
         k = C.c_int(); p = (C.c_double * 2)()
         h.check(h.L.apexgpu_get_loss(h.h, C.byref(k), C.byref(p)))
         return Loss(k.value, p[0], p[1])
+
+    def set_priors(self, pose_priors=None, intr_priors=None):
+        """PriorFactor blocks on the cameras, as Problem.add_pose_prior / add_intrinsic_prior list them: (camera, data, huber
+        delta or None, weight) each.  A list replaces the set of its kind ([] clears it); None leaves that set as it is.
+        initialize_structure applies the problem's lists; this call re-applies or changes them on the built handle."""
+        h = self._need()
+        if pose_priors is not None:
+            cam, data, dl, w = _prior_arrays(pose_priors, 7)
+            h.check(h.L.apexgpu_set_pose_priors(h.h, len(cam), capi.ptr(cam), capi.ptr(data), capi.ptr(dl), capi.ptr(w)))
+            self._n_pose_priors = len(cam)
+        if intr_priors is not None:
+            cam, data, dl, w = _prior_arrays(intr_priors, 3)
+            h.check(h.L.apexgpu_set_intrinsic_priors(h.h, len(cam), capi.ptr(cam), capi.ptr(data), capi.ptr(dl), capi.ptr(w)))
+            self._n_intr_priors = len(cam)
+
+    def prior_residuals(self):
+        """Corrected residuals of the prior blocks at the current parameters: ([n_pose][7], [n_intr][3]), the caller's order."""
+        h = self._need()
+        rp = np.zeros((getattr(self, "_n_pose_priors", 0), 7)); ri = np.zeros((getattr(self, "_n_intr_priors", 0), 3))
+        if len(rp) or len(ri):
+            h.check(h.L.apexgpu_get_prior_residual(h.h, capi.ptr(rp) if len(rp) else None, capi.ptr(ri) if len(ri) else None))
+        return rp, ri
 
     def _need(self) -> capi.Handle:
         if self._h is None:

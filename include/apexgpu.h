@@ -124,6 +124,35 @@ int apexgpu_set_params(apexgpu_solver* h, const double* poses, const double* int
 int apexgpu_set_loss(apexgpu_solver* h, int kind, double p0, double p1);
 /* what the observations carry: the loss of set_loss, else HUBER with set_structure's delta, else NONE; out2 = {p0, p1} */
 int apexgpu_get_loss(const apexgpu_solver* h, int* kind, double out2[2]);
+/* PriorFactor blocks on camera poses and camera intrinsics, beside the projection factors (Problem::add_residual_block with a
+ * PriorFactor, src/factors/prior_factor.rs:93-105; the semantics apexgpu_pg_set_priors has on an SE3 vertex):
+ *   pose prior on camera cam[k], data7 = [tx,ty,tz,qw,qx,qy,qz]: r = to_vector(pose) - data over the normalised pose, seven rows;
+ *     the identity Jacobian is truncated to the pose's six tangent columns (src/linearizer/cpu/sparse.rs:201-204), so the camera's
+ *     pose block of H gains rho' w^2 I6, its gradient rho' w^2 r[0:6], and all seven rows count in the cost;
+ *   intrinsics prior on camera cam[k], data3 = [f,k1,k2]: r = intr - data, J = I3, on the three intrinsic columns.  Only on a
+ *     handle whose mode optimises the intrinsics (nine columns per camera): elsewhere those columns do not exist on the device
+ *     and the call answers APEXGPU_ERR_INVALID_INPUT (apexgpu_last_error says why).
+ * huber_delta[k] (NULL or <= 0: none) is the block's own Huber loss, applied as the corrector's first arm with s = |w r|^2 over
+ * all rows of the block; apexgpu_set_loss does not touch prior blocks.  weight[k] (NULL: 1) is a scalar square-root information:
+ * r <- w r, J <- w J.  The reference's factor has no weight -- this is an addition, and w = 1 is the reference's factor.
+ * Several priors on one camera sum; priors on a camera whose DOFs are fixed by mask still enter H and the gradient
+ * (problem.rs:185-197).  Every variant, the LM and Dog-Leg loops, Jacobi scaling, the covariances, apexgpu_get_schur,
+ * apexgpu_get_hessian_csc, apexgpu_schur_matvec and the gradient see them; apexgpu_get_residual / _get_jacobian_blocks stay per
+ * observation.  Assembly stays free of atomics: with the same inputs a handle computes the same bits, whatever the order of
+ * priors on DIFFERENT cameras (priors on one camera are summed in the caller's order).
+ * Each call replaces the set of its kind (n = 0 clears it); apexgpu_set_structure clears both.  A call voids a pending trial
+ * step, a cached Dog-Leg solve and the factor the covariance calls read.
+ * APEXGPU_ERR_INVALID_STATE before set_structure and on a sharded handle (apexgpu_set_shard / a communicator of several
+ * ranks: multi-rank priors are not built; apexgpu_set_shard on a handle that holds priors is refused likewise);
+ * APEXGPU_ERR_INVALID_INPUT for cam[k] >= n_cam, a NaN in data, huber_delta or weight, a weight that is not finite and > 0.
+ * A refused call leaves the handle as it was.
+ * apexgpu_get_prior_residual: the corrected residuals at the current parameters in the caller's order, [n_pose][7] and
+ * [n_intr][3]; either pointer may be NULL. */
+int apexgpu_set_pose_priors(apexgpu_solver* h, int64_t n, const uint32_t* cam, const double* data7, const double* huber_delta,
+                            const double* weight);
+int apexgpu_set_intrinsic_priors(apexgpu_solver* h, int64_t n, const uint32_t* cam, const double* data3, const double* huber_delta,
+                                 const double* weight);
+int apexgpu_get_prior_residual(apexgpu_solver* h, double* pose_r7_out, double* intr_r3_out);
 int apexgpu_get_params(apexgpu_solver* h, double* poses, double* intr, double* points);
 
 /* ---- hot path --------------------------------------------------------------------------------*/

@@ -61,6 +61,13 @@ extern "C" {
     /// `InvalidInput` for the kinds whose corrector can take its second arm (Andrews, Lp with p > 2, Barron with alpha > 2)
     pub fn apexgpu_set_loss(h: *mut ApexGpuSolver, kind: c_int, p0: f64, p1: f64) -> c_int;
     pub fn apexgpu_get_loss(h: *const ApexGpuSolver, kind: *mut c_int, out2: *mut f64) -> c_int;
+    /// `PriorFactor` blocks on camera poses (`data7` = `to_vector()`: t, qw qx qy qz) and on camera intrinsics (`data3` = f, k1, k2;
+    /// nine-column handles only), after `apexgpu_set_structure`, each call replacing the set of its kind (n = 0 clears it).
+    /// `huber_delta` / `weight` may be null (no loss / 1); the weight is a scalar square-root information the reference's
+    /// factor does not have (1 = that factor).  `InvalidState` on a sharded handle.
+    pub fn apexgpu_set_pose_priors(h: *mut ApexGpuSolver, n: i64, cam: *const u32, data7: *const f64, huber_delta: *const f64, weight: *const f64) -> c_int;
+    pub fn apexgpu_set_intrinsic_priors(h: *mut ApexGpuSolver, n: i64, cam: *const u32, data3: *const f64, huber_delta: *const f64, weight: *const f64) -> c_int;
+    pub fn apexgpu_get_prior_residual(h: *mut ApexGpuSolver, pose_r7_out: *mut f64, intr_r3_out: *mut f64) -> c_int;
     pub fn apexgpu_solve_augmented(h: *mut ApexGpuSolver, lambda: f64, variant: c_int, step_out: *mut f64, grad_out: *mut f64) -> c_int;
     pub fn apexgpu_column_norms(h: *mut ApexGpuSolver, norms_out: *mut f64) -> c_int;
     pub fn apexgpu_set_column_scaling(h: *mut ApexGpuSolver, scaling: *const f64) -> c_int;
