@@ -92,9 +92,14 @@ def _n2(a):
 
 class SchurRef:
     """The Schur system of one linearisation in `dtype`.  dense=False leaves out S (S4, M, P): vectors and matvec only.
-    hinv_given = {landmark: 3 x 3}: H_ll^-1 of these landmarks is taken as given, not computed."""
+    hinv_given = {landmark: 3 x 3}: H_ll^-1 of these landmarks is taken as given, not computed.
+    mags = (M_Jc, M_Jl, M_r): entrywise magnitudes >= |Jc|, |Jl|, |r| of blocks that are themselves on trial (projection_ref.py);
+    every magnitude below is then formed from the norms of these instead of the blocks' own (|W| <= |M_Jc| |M_Jl|), and
+    H_ll^-1 on its own gets, beside cond(H_ll), the relative magnitude of H_ll = sum_k Jl_k^T Jl_k + lambda I itself,
+    kap_l = max(1, (sum_k (2 |M_Jl_k| |Jl_k| - |Jl_k|^2) + lambda) / |H_ll|) in spectral norms (the magnitude of a square is
+    2 M |x| - x^2 to first order): cond eps |H^-1| with eps the relative uncertainty of H_ll."""
 
-    def __init__(self, n_cam, n_pt, cam_idx, pt_idx, jc, jl, r, lam, dtype=LD, dense=True, chunk=20000, hinv_given=None):
+    def __init__(self, n_cam, n_pt, cam_idx, pt_idx, jc, jl, r, lam, dtype=LD, dense=True, chunk=20000, hinv_given=None, mags=None):
         T = self.T = dtype
         self.n_cam, self.n_pt, self.lam = int(n_cam), int(n_pt), float(lam)
         ci = self.ci = np.asarray(cam_idx, dtype=np.int64); li = self.li = np.asarray(pt_idx, dtype=np.int64)
@@ -116,6 +121,13 @@ class SchurRef:
         self.wn, self.hn = _n2(W), _n2(self.Hinv)
         self.jcn, self.jln = _n2(Jc), _n2(Jl)
         self.rn = np.linalg.norm(np.asarray(rr, dtype=np.float64), axis=1)
+        self.kap = np.ones(n_pt)
+        if mags is not None:
+            mjl = _n2(mags[1])
+            mag_h = _scatter(n_pt, li, 2.0 * mjl * self.jln - self.jln ** 2, np.float64) + abs(lam)
+            self.jcn, self.jln = _n2(mags[0]), mjl
+            self.rn = np.linalg.norm(np.asarray(mags[2], dtype=np.float64).reshape(-1, 2), axis=1)
+            self.wn = self.jcn * self.jln
         self.hcc_mag = _scatter(n_cam, ci, self.jcn ** 2, np.float64) + abs(lam)
         self.gl_mag = _scatter(n_pt, li, self.jln * self.rn, np.float64)
         self.gred_mag = _scatter(n_cam, ci, self.jcn * self.rn + self.wn * self.hn[li] * self.gl_mag[li], np.float64)
@@ -123,7 +135,9 @@ class SchurRef:
         self.gred_terms = self.n_i + kmax_i
         ev = np.linalg.eigvalsh(np.asarray(self.Hll, dtype=np.float64))
         self.cond = ev[:, 2] / ev[:, 0]
-        self.hinv_mag = self.cond * self.hn
+        if mags is not None:
+            self.kap = np.maximum(1.0, mag_h / ev[:, 2])
+        self.hinv_mag = self.cond * self.hn * self.kap
         self.dense = dense
         if not dense:
             return
