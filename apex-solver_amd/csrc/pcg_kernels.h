@@ -1,5 +1,5 @@
 // pcg_kernels.h -- the device scalars and the launchers of the two Jacobi-PCG loops (pcg_kernels.hip): the explicit one on a
-// plan's unfactored tiles (TilePcg, tile_pcg.h) and the matrix-free one (Solver::implicit_pcg_solve).
+// plan's unfactored tiles (TilePcg, tile_pcg.h) and the one over an abstract operator (SchurJacobiPcg, schur_jacobi_pcg.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

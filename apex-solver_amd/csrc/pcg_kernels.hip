@@ -1,6 +1,6 @@
 // pcg_kernels.hip -- the kernels of the two Jacobi-preconditioned conjugate-gradient loops (pcg_kernels.h): the symmetric tile
 // product of the explicit loop (TilePcg, tile_pcg.h), its fused vector updates, and the vector updates of the matrix-free loop
-// (Solver::implicit_pcg_solve).  Every scalar of an iteration stays on the device; the layouts are pcg_kernels.h's.
+// (SchurJacobiPcg, schur_jacobi_pcg.h).  Every scalar of an iteration stays on the device; the layouts are pcg_kernels.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void k_dot(int n, const double* __restrict__ a
     if (threadIdx.x == 0) out[0] = (sc[0] + sc[1]) + (sc[2] + sc[3]);
 }
 
-// ---- the matrix-free PCG with its scalars on the device (Solver::implicit_pcg_solve reads them one iteration behind) ----------
+// ---- the matrix-free PCG with its scalars on the device (SchurJacobiPcg::solve reads them one iteration behind) ----------
 // sc: ImplicitPcgScalars (pcg_kernels.h)
 __global__ void k_pcg_implicit_begin(double* __restrict__ sc) { sc[4] = sc[0]; sc[5] = 0.0; sc[6] = 0.0; }   // (sc[0] = r.z of the start)
 __global__ __launch_bounds__(256) void k_pcg_update_xr_sc(int n, const double* __restrict__ sc, const double* __restrict__ p,

@@ -2,7 +2,7 @@
 // Iteration k + 1 is enqueued on speculation before the host waits for the scalars of iteration k, so the device never idles
 // through a host round trip; the termination tests are also made on the device, so an iteration enqueued behind a met test
 // changes nothing, and x, the iteration count and every scalar are those of the loop that waited every time -- whatever the cap.
-// No HIP here: TilePcg::solve (tile_pcg.hip) and Solver::implicit_pcg_solve (solver.hip) give the device work as callables over
+// No HIP here: TilePcg::solve (tile_pcg.hip) and SchurJacobiPcg::solve (schur_jacobi_pcg.h) give the device work as callables over
 // a PcgReadback (pcg_readback.h), tests/host_harness_pcg_loop.cpp walks the loop on the host.
 #pragma once
 

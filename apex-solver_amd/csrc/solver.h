@@ -14,9 +14,9 @@
 
 #include "ba_kernels.h"
 #include "ba_prior_kernels.h"
+#include "ba_scalars.h"
 #include "chol_kernels.h"
-#include "pcg_kernels.h"
-#include "pcg_readback.h"
+#include "schur_jacobi_pcg.h"
 #include "schur_pairs.h"
 #include "comm.h"
 #include "tile_backend.h"
@@ -184,8 +184,8 @@ class Solver : public TileBackend {
     int enqueue_step_stats() override;
     int enqueue_trial_point(double* sumsq_out) override;
     int enqueue_retract(int from, double sign, int to) override { retract_sets(from, sign, to, n_pt_); return kOk; }
-    // scal_: [0..5] the camera and the landmark half of the step's sums, [6] the trial point's sum of squares -- read here only
-    double* step_sums(int* n) override { *n = 6; return scal_; }
+    // BaScalars::step, the camera and the landmark half of the step's sums, and trial_sumsq behind them -- read here only
+    double* step_sums(int* n) override { *n = 6; return scal_.get()->step; }
     StepAnswers answers_from_sums(const double* h) const override { return {sqrt(h[0] + h[3]), sqrt(h[1] + h[4]), 0.5 * (h[2] + h[5]), h[6]}; }
     void params_moved() override { orec_fresh_ = false; }
     void retract_sets(int from, double sign, int to, int64_t n_pt);
@@ -282,7 +282,6 @@ class Solver : public TileBackend {
     bool matrix_free_only_opt_ = false;   // the caller's option ("matrix_free_only")
     bool matrix_free_only_ = false;       // the effective state of the structure that is built: the option, or the automatic selection
     bool trial_pts_written_ = false;   // the back-substitution of this solve has written the trial points (enqueue_trial_point skips them)
-    PcgReadback<ImplicitPcgScalars> pcg_readback_;   // the matrix-free PCG's scalars, read one iteration behind
     bool device_pair_recs_ = true;   // queued layout: the pair records are written by the device (k_build_pair_recs_q), not built on the host and copied
     bool auto_variant_ = true, auto_fallback_ = false;   // see set_auto_variant
     int variant_cost_permille_ = 1000, variant_choice_ = 0;
@@ -319,7 +318,8 @@ class Solver : public TileBackend {
     DeviceBuffer<int> o_orig_, pt_ptr_, cam_ptr_, cam_obs_;
     DeviceBuffer<uint8_t> fix_pose_, fix_intr_, fix_pt_;
     DeviceBuffer<double> g_c_, g_red_, dcam_, hinv_, g_l_, dl_;
-    DeviceBuffer<double> scal_;            // scalar outputs (the reduction scratch partial_ is TileBackend's)
+    DeviceBuffer<BaScalars> scal_;         // scalar outputs, by field: a device address, never read through on the host (the reduction scratch partial_ is TileBackend's)
+    DeviceBuffer<int64_t> lm_ranges_;      // [world_][2] every rank's landmark range, gathered by get_params (several ranks: adopt_comm)
     DeviceBuffer<int> flags_;              // [0] landmark inversion error
     std::vector<int> cmap_, cinv_;   // external camera -> internal camera and back
     bool hubs_last_ = true;     // order cameras covisible with > max(16, 10 sqrt(n_cam)) others last (ba_structure.h)
@@ -337,8 +337,10 @@ class Solver : public TileBackend {
     // (an in-place all-gather, a debug import) breaks what export_step, step_stats and retract read.
     ColumnMap cam_map_, pt_map_;
     DeviceBuffer<uint8_t> lam_mask_;  // tree sharding: cameras whose diagonal block gets lambda on this rank
-    DeviceBuffer<double> pcg_buf_;                 // 7 vectors of n_c_pad
-    DeviceBuffer<double> lmu_, sd_, minv_;  // matrix-free variant: {pt, u_l} records, diag blocks of S, their inverses
+    DeviceBuffer<double> tile_work_;   // 6 n_c_pad: what tp_.pcg asks for (tile_plan.h; tp_.solve / solve_phase: 2 n_pad); ladder() reads the diagonal into it
+    // matrix-free variant: the {pt, u_l} records and the scaled x of the operator (implicit_matvec); the loop and its preconditioner
+    DeviceBuffer<double> lmu_, mf_xs_;
+    SchurJacobiPcg sj_pcg_;
     // PriorFactor blocks on the cameras: each set sorted by internal camera (stable) with a CSR over the cameras; the vectors of
     // the last evaluation -- diag(P) and P's gradient over the camera columns [n_c_pad], the cost per camera [n_cam]
     struct PriorSet {

@@ -2,7 +2,6 @@
 #include "solver.h"
 #include "ba_device.hpp"
 #include "ba_structure.h"
-#include "pcg_loop.h"
 
 #include <math.h>
 #include <string.h>
@@ -116,6 +115,7 @@ int Solver::adopt_comm(std::unique_ptr<Communicator> c, const std::string& err) 
     tc.sum = [cp, note](double* buf, size_t n, hipStream_t st) { return note(cp->all_reduce_sum(buf, n, st)); };
     tc.max_int = [cp, note](int* buf, size_t n, hipStream_t st) { return note(cp->all_reduce_max(buf, n, st)); };
     tp_.set_comm(std::move(tc));
+    HIP_TRY(lm_ranges_.alloc(2 * (size_t)world_));
     return kOk;
 }
 
@@ -424,11 +424,11 @@ int Solver::alloc_work_arrays(std::string* err) {
     HIP_TRY(g_l_.alloc_zero(3 * n_pt_), err);
     HIP_TRY(dl_.alloc_zero(3 * n_pt_), err);
     HIP_TRY(partial_.alloc_zero(3 * (size_t)n_partial_), err);
-    HIP_TRY(scal_.alloc_zero(32), err);
-    HIP_TRY(pcg_buf_.alloc_zero(7 * (size_t)n_c_pad_), err);
+    HIP_TRY(scal_.alloc_zero(1), err);
+    HIP_TRY(tile_work_.alloc_zero(6 * (size_t)n_c_pad_), err);   // tp_.pcg: "work: 6*n_pad doubles" (tile_plan.h), the largest of its users
     HIP_TRY(lmu_.alloc_zero((size_t)kLmuStride * n_pt_), err);
-    HIP_TRY(sd_.alloc_zero((size_t)n_cam_ * dc_ * dc_), err);
-    HIP_TRY(minv_.alloc_zero((size_t)n_cam_ * dc_ * dc_), err);
+    HIP_TRY(mf_xs_.alloc_zero(n_c_pad_), err);
+    HIP_TRY(sj_pcg_.setup(n_cam_, dc_, n_c_, n_c_pad_, stream_, partial_, n_partial_), err);
     HIP_TRY(flags_.alloc_zero(4), err);
     for (int b = 0; b < 2; ++b) {   // the pinned chunks of upload_staged: mapped here, not in the caller's first set_params
         if (!pin_[b]) HIP_TRY(pin_[b].alloc((size_t)16 << 20), err);
@@ -729,7 +729,7 @@ int Solver::get_params(double* poses, double* intr, double* points) {
         // all ranks compute identical cuts from the replicated structure: re-derive from pt_ptr is not
         // possible without the full lists, so exchange the range starts.
         int64_t mine[2] = {lm_lo_, lm_hi_};
-        int64_t* d_rng = reinterpret_cast<int64_t*>(scal_ + 8);
+        int64_t* d_rng = lm_ranges_;
         HIP_TRY(hipMemcpyAsync(d_rng + 2 * rank_, mine, sizeof mine, hipMemcpyHostToDevice, stream_));
         COMM_TRY(comm_->all_gather(d_rng + 2 * rank_, d_rng, 2 * sizeof(int64_t), stream_));
         std::vector<int64_t> rng(2 * world_);
@@ -759,14 +759,15 @@ int Solver::cost(double* out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
     stage_begin(kStCost);
-    launch_cost(view(st_.cur), partial_, n_partial_, scal_, stream_, general_loss());
+    double* sumsq = &scal_.get()->cost_sumsq;
+    launch_cost(view(st_.cur), partial_, n_partial_, sumsq, stream_, general_loss());
     if (comm_ && world_ > 1)
-        COMM_TRY(comm_->all_reduce_sum(scal_, 1, stream_));
-    if (have_priors()) enqueue_prior_cost(st_.cur, scal_);
+        COMM_TRY(comm_->all_reduce_sum(sumsq, 1, stream_));
+    if (have_priors()) enqueue_prior_cost(st_.cur, sumsq);
     stage_end(kStCost);
     HIP_TRY(hipGetLastError());
     double ss = 0.0;
-    HIP_TRY(hipMemcpyAsync(&ss, scal_, sizeof(double), hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(&ss, sumsq, sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     *out = cost_from_sumsq(ss);
     return kOk;
@@ -860,7 +861,7 @@ int Solver::factor_now(int* failed_at, bool defer_flags) {
 
 int Solver::enqueue_sweeps() {
     stage_begin(kStTriSolve);
-    const hipError_t se = tp_.solve(g_red_, dcam_, pcg_buf_);
+    const hipError_t se = tp_.solve(g_red_, dcam_, tile_work_);
     if (se != hipSuccess && !comm_err_.empty()) return fail(kDeviceError, comm_err_);
     HIP_TRY(se);
     stage_end(kStTriSolve);
@@ -895,7 +896,7 @@ int Solver::ladder(double lambda) {
     int failed = 0;
     int rc = assemble(lambda, 0.0);
     if (rc != kOk) return rc;
-    double* diag = pcg_buf_;
+    double* diag = tile_work_;
     tp_.diag(diag);
     std::vector<double> hd(n_c_);
     HIP_TRY(hipMemcpyAsync(hd.data(), diag, n_c_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
@@ -921,7 +922,7 @@ int Solver::ladder(double lambda) {
 // solve_with_pcg (explicit_schur.rs:639-756): Jacobi-preconditioned CG on the explicit S.
 int Solver::pcg_solve() {
     stage_begin(kStFactor);
-    HIP_TRY(tp_.pcg(g_red_, dcam_, pcg_buf_, cg_max_iter_, cg_tol_, &last_pcg_iters_));
+    HIP_TRY(tp_.pcg(g_red_, dcam_, tile_work_, cg_max_iter_, cg_tol_, &last_pcg_iters_));
     stage_end(kStFactor);
     return kOk;
 }
@@ -930,8 +931,8 @@ int Solver::pcg_solve() {
 // A18: IterativeSchurSolver (src/linalg/sparse/implicit_schur.rs) -- S is never formed.
 //   assemble_implicit : Hll^-1 / g_l (k_landmark_reduce), g_c and g_red plus the DIAGONAL blocks of S
 //                       (k_cam_reduce with its self terms), Schur-Jacobi blocks inverted per variable
-//   implicit_pcg_solve: solve_pcg_block (:577-679); every S p is two passes over the observations
-//                       (landmark-major, then camera-major), nothing but 64 bytes per landmark in between
+//   implicit_pcg_solve: solve_pcg_block (:577-679), the loop SchurJacobiPcg's (schur_jacobi_pcg.h); every S p (implicit_matvec) is two
+//                       passes over the observations (landmark-major, then camera-major), nothing but 64 bytes per landmark in between
 // Sharded: g_red, g_c and the diagonal blocks are all-reduced once, every S p once per iteration.
 // ---------------------------------------------------------------------------------------------
 int Solver::assemble_implicit(double lambda) {
@@ -945,16 +946,16 @@ int Solver::assemble_implicit(double lambda) {
     stage_end(kStAssembleLm);
     stage_begin(kStAssembleCam);
     launch_cam_reduce(dc_, v, tilemap(), cam_ptr_, cam_obs_, lambda, rank_ == 0 ? 1 : 0, hinv_, g_l_, 1, g_c_, g_red_, stream_, general_loss());
-    launch_extract_diag_blocks(dc_, n_cam_, tilemap(), sd_, stream_);
+    launch_extract_diag_blocks(dc_, n_cam_, tilemap(), sj_pcg_.diag_blocks(), stream_);
     if (have_priors()) {   // (single rank: nothing below sums these twice)
         enqueue_prior_eval(st_.cur, false);
-        launch_ba_prior_add_blocks(dc_, n_cam_, pri_diag_, pri_g_, sd_, g_c_, g_red_, stream_);
+        launch_ba_prior_add_blocks(dc_, n_cam_, pri_diag_, pri_g_, sj_pcg_.diag_blocks(), g_c_, g_red_, stream_);
     }
     stage_end(kStAssembleCam);
     if (comm_ && world_ > 1) {
         stage_begin(kStAllReduce);
         COMM_TRY(comm_->group_start());
-        COMM_TRY(comm_->all_reduce_sum(sd_, (size_t)n_cam_ * dc_ * dc_, stream_));
+        COMM_TRY(comm_->all_reduce_sum(sj_pcg_.diag_blocks(), (size_t)n_cam_ * dc_ * dc_, stream_));
         COMM_TRY(comm_->all_reduce_sum(g_red_, (size_t)n_c_pad_, stream_));
         COMM_TRY(comm_->all_reduce_sum(g_c_, (size_t)n_c_pad_, stream_));
         COMM_TRY(comm_->all_reduce_max(flags_, 1, stream_));  // a singular landmark block anywhere fails the solve on every rank
@@ -962,11 +963,8 @@ int Solver::assemble_implicit(double lambda) {
         stage_end(kStAllReduce);
     }
     stage_begin(kStAssembleCam);
-    if (scaled_) {
-        launch_scale_diag_blocks(dc_, n_cam_, cam_scale_.dev, sd_, stream_);
-        launch_vec_mul(n_c_pad_, g_red_, cam_scale_.dev, g_red_, stream_);
-    }
-    launch_precond_blocks(dc_, n_cam_, sd_, minv_, stream_);
+    if (scaled_) launch_vec_mul(n_c_pad_, g_red_, cam_scale_.dev, g_red_, stream_);
+    sj_pcg_.build_preconditioner(scaled_ ? cam_scale_.dev.get() : nullptr);
     stage_end(kStAssembleCam);
     return kOk;
 }
@@ -976,9 +974,8 @@ int Solver::assemble_implicit(double lambda) {
 int Solver::implicit_matvec(const double* x, double lam_local, double* y, bool reduce) {
     const double* xin = x;
     if (scaled_) {
-        double* t = pcg_buf_ + 4 * n_c_pad_;
-        launch_vec_mul(n_c_, x, cam_scale_.dev, t, stream_);
-        xin = t;
+        launch_vec_mul(n_c_, x, cam_scale_.dev, mf_xs_, stream_);
+        xin = mf_xs_;
     }
     launch_implicit_matvec(dc_, view(st_.cur), cam_ptr_, hinv_, lmu_, xin, lam_local, y, stream_, backsub_records(), general_loss());
     if (have_priors()) launch_ba_prior_matvec(n_c_, pri_diag_, xin, y, stream_);   // (diag(P) of assemble_implicit's evaluation, in the unscaled variables)
@@ -990,46 +987,11 @@ int Solver::implicit_matvec(const double* x, double lam_local, double* y, bool r
 
 int Solver::implicit_pcg_solve(double lambda, int max_iter, double tol) {
     stage_begin(kStFactor);
-    const int n = (int)n_c_;
-    double *x = dcam_, *r = pcg_buf_, *z = pcg_buf_ + n_c_pad_, *p = pcg_buf_ + 2 * n_c_pad_, *ap = pcg_buf_ + 3 * n_c_pad_;
-    double* sc = scal_ + 16;   // ImplicitPcgScalars (pcg_kernels.h)
-    HIP_TRY(pcg_readback_.ensure());
-    HIP_TRY(hipMemsetAsync(x, 0, n_c_pad_ * sizeof(double), stream_));
-    HIP_TRY(hipMemcpyAsync(r, g_red_, n_c_pad_ * sizeof(double), hipMemcpyDeviceToDevice, stream_));
-    launch_precond_apply(dc_, n_cam_, minv_, r, z, stream_);
-    HIP_TRY(hipMemcpyAsync(p, z, n_c_pad_ * sizeof(double), hipMemcpyDeviceToDevice, stream_));
-    launch_dot2(n, r, z, r, r, partial_, n_partial_, sc, stream_);
-    launch_pcg_implicit_begin(sc, stream_);   // rz_old := r.z, not frozen
-    HIP_TRY(hipMemcpyAsync(&pcg_readback_.host(0), sc, 2 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    ImplicitPcgStart start;
-    memcpy(&start, &pcg_readback_.host(0), sizeof start);
-    const double abs_tol = tol * std::max(sqrt(start.rr), 1.0);
     const double lam_local = (rank_ == 0) ? lambda : 0.0;  // the all-reduce sums the ranks' partial S p
-    // Every scalar of the iteration stays on the device (alpha, beta, the reference's three termination tests:
-    // k_pcg_implicit_close), and the host reads {r.r, r.z, p.Ap, frozen} one iteration behind (pcg_loop.h).  (Sharded: every rank
-    // reads the same scalars and enqueues the same iterations.)
-    auto enqueue_iteration = [&](int slot) -> int {
-        const int mrc = implicit_matvec(p, lam_local, ap, true);
-        if (mrc != kOk) return mrc;
-        launch_dot2(n, p, ap, p, ap, partial_, n_partial_, sc + 2, stream_);
-        launch_pcg_update_xr_sc(n, sc, p, ap, x, r, stream_);        // alpha = rz_old / p.Ap; nothing when |p.Ap| < 1e-20 (:610-613)
-        launch_precond_apply(dc_, n_cam_, minv_, r, z, stream_);
-        launch_dot2(n, r, r, r, z, partial_, n_partial_, sc, stream_);
-        launch_pcg_implicit_close(sc, abs_tol, stream_);               // :634-641, :652-654, else beta and rz_old
-        launch_pcg_update_p_sc(n, sc, z, p, stream_);
-        return check_hip(pcg_readback_.post(slot, sc, 6, stream_), "pcg_readback_.post");
-    };
-    const PcgLoopResult res = pcg_loop_one_behind(
-        max_iter, enqueue_iteration, [&](int slot) -> int { return check_hip(pcg_readback_.wait(slot), "pcg_readback_.wait"); },
-        [&](int slot) {
-            const ImplicitPcgScalars& h = pcg_readback_.host(slot);
-            if (fabs(h.p_ap) < 1e-20) return PcgVerdict::kStopUncounted;               // :610-613 (x, r untouched)
-            return h.frozen != 0.0 ? PcgVerdict::kStopCounted : PcgVerdict::kGoOn;   // the device's verdict: |r| < tol (:634-641) or rz_old ~ 0 (:652-654)
-        });
-    if (res.status != kOk) return res.status;   // (a failed collective of the matvec included: its status, its text in err_)
-    HIP_TRY(hipStreamSynchronize(stream_));      // (the speculative iteration, if any, has drained)
-    last_pcg_iters_ = res.iterations;
+    // (a failed collective of the matvec ends the loop with its status, its text in err_)
+    const int rc = sj_pcg_.solve(g_red_, dcam_, max_iter, tol, [&](const double* p, double* ap) { return implicit_matvec(p, lam_local, ap, true); },
+                                 &last_pcg_iters_, &err_);
+    if (rc != kOk) return rc;
     stage_end(kStFactor);
     return kOk;
 }
@@ -1145,17 +1107,17 @@ int Solver::dist_phase(int phase, double lambda) {
             if (f[1]) return fail(kSingularMatrix, "Landmark block is singular");
             if (f[0]) return fail(kFactorizationFailed, "non-positive pivot in tile column " + std::to_string(f[0] - 1));
             stage_begin(kStTriSolve);
-            tp_.solve_phase(0, g_red_, dcam_, pcg_buf_);
+            tp_.solve_phase(0, g_red_, dcam_, tile_work_);
             stage_end(kStTriSolve);
             return kOk;
         }
         case 4:
             stage_begin(kStTriSolve);
-            tp_.solve_phase(1, g_red_, dcam_, pcg_buf_);
+            tp_.solve_phase(1, g_red_, dcam_, tile_work_);
             stage_end(kStTriSolve);
             return kOk;
         case 5:
-            tp_.solve_phase(2, g_red_, dcam_, pcg_buf_);
+            tp_.solve_phase(2, g_red_, dcam_, tile_work_);
             if (scaled_) launch_vec_mul(n_c_, dcam_, cam_scale_.dev, dcam_, stream_);
             launch_back_substitute(dc_, view(st_.cur), hinv_, g_l_, dcam_, dl_, stream_, backsub_records(), nullptr, nullptr, general_loss());
             HIP_TRY(hipStreamSynchronize(stream_));
@@ -1204,10 +1166,11 @@ int Solver::assemble_only(double lambda) {
 
 int Solver::enqueue_step_stats() {
     stage_begin(kStStats);
-    launch_step_stats(n_c_, g_c_, dcam_, last_lambda_, scaled_ ? cam_scale_.dev.get() : nullptr, partial_, n_partial_, scal_, stream_);
-    launch_step_stats(3 * n_pt_, g_l_, dl_, last_lambda_, scaled_ ? pt_scale_.dev.get() : nullptr, partial_, n_partial_, scal_ + 3, stream_);
+    double* step = scal_.get()->step;   // [0..2] the camera half, [3..5] the landmark half
+    launch_step_stats(n_c_, g_c_, dcam_, last_lambda_, scaled_ ? cam_scale_.dev.get() : nullptr, partial_, n_partial_, step, stream_);
+    launch_step_stats(3 * n_pt_, g_l_, dl_, last_lambda_, scaled_ ? pt_scale_.dev.get() : nullptr, partial_, n_partial_, &step[3], stream_);
     if (comm_ && world_ > 1)  // landmark part is sharded, camera part replicated
-        COMM_TRY(comm_->all_reduce_sum(scal_ + 3, 3, stream_));
+        COMM_TRY(comm_->all_reduce_sum(&step[3], 3, stream_));
     stage_end(kStStats);
     return kOk;
 }
@@ -1236,14 +1199,15 @@ int Solver::enqueue_trial_point(double* sumsq_out) {
 int Solver::parameter_norm(double* out) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    launch_sumsq(7 * n_cam_, poses_[st_.cur], partial_, n_partial_, scal_ + 9, stream_);
-    launch_sumsq(3 * n_cam_, intr_[st_.cur], partial_, n_partial_, scal_ + 10, stream_);
+    double* sumsq = scal_.get()->param_sumsq;
+    launch_sumsq(7 * n_cam_, poses_[st_.cur], partial_, n_partial_, &sumsq[0], stream_);
+    launch_sumsq(3 * n_cam_, intr_[st_.cur], partial_, n_partial_, &sumsq[1], stream_);
     // points: in a sharded run only the owned range is current on this rank
-    launch_sumsq(3 * (lm_hi_ - lm_lo_), pts_[st_.cur] + 3 * lm_lo_, partial_, n_partial_, scal_ + 11, stream_);
+    launch_sumsq(3 * (lm_hi_ - lm_lo_), pts_[st_.cur] + 3 * lm_lo_, partial_, n_partial_, &sumsq[2], stream_);
     if (comm_ && world_ > 1)
-        COMM_TRY(comm_->all_reduce_sum(scal_ + 11, 1, stream_));
+        COMM_TRY(comm_->all_reduce_sum(&sumsq[2], 1, stream_));
     double h[3];
-    HIP_TRY(hipMemcpyAsync(h, scal_ + 9, sizeof h, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(h, sumsq, sizeof h, hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     *out = sqrt(h[0] + h[1] + h[2]);
     return kOk;
@@ -1459,7 +1423,9 @@ int Solver::schur_matvec(double lambda, const double* x_in, double* y_explicit, 
     const int64_t nref = 9 * n_cam_;
     std::vector<double> h(n_c_pad_, 0.0);
     cam_map_.gather(x_in, h.data());
-    double *xd = pcg_buf_, *yd = pcg_buf_ + n_c_pad_;
+    DeviceBuffer<double> xd, yd;   // (a parity export: allocated in the call)
+    HIP_TRY(xd.alloc(n_c_pad_));
+    HIP_TRY(yd.alloc(n_c_pad_));
     HIP_TRY(hipMemcpyAsync(xd, h.data(), n_c_pad_ * sizeof(double), hipMemcpyHostToDevice, stream_));
     for (int pass = 0; pass < 2; ++pass) {
         double* out = pass == 0 ? y_explicit : y_implicit;
