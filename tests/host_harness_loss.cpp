@@ -117,6 +117,20 @@ int hl_jv(int manifold, const double* k0, const double* k1, const double* m, int
     return 0;
 }
 
+// |r~|^2 = residual_scaling^2 s as k_pg_cost_partial<M, LossGeneral> forms it: M::residual, s summed left to right
+int hl_cost(int manifold, const double* k0, const double* k1, const double* m, int kind, double lp0, double lp1, double* out) {
+    PgLoss l;
+    if (!pg_loss_make(kind, lp0, lp1, &l)) return -1;
+    double p0[8], p1[8], pm[8], r[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (manifold == 1) { prepare3<Se2Manifold>(k0, k1, m, p0, p1, pm); Se2Manifold::residual(p0, p1, pm, r); }
+    else { prepare3<Se3Manifold>(k0, k1, m, p0, p1, pm); Se3Manifold::residual(p0, p1, pm, r); }
+    double s = 0.0;
+    for (int i = 0; i < (manifold == 1 ? 3 : 6); ++i) s += r[i] * r[i];
+    const double sc = pg_loss_corrector(l, s).residual_scaling;
+    *out = (sc * sc) * s;
+    return 0;
+}
+
 }  // extern "C"
 
 #ifdef HL_MAIN

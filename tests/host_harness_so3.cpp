@@ -91,6 +91,48 @@ int hs3_assemble_dense(int64_t n_v, int64_t n_e, const double* poses4, const uin
     return 0;
 }
 
+// The per-edge forms under a loss of pg_loss.hpp, with Omega (info9: full, row-major) or without (null), as the kernels call them:
+//   hs3_edge  k_pg_export     the literal corrected (whitened) residual [3] and Jacobian [3][6]
+//   hs3_jv    k_pg_jv_gram    out3 = {(J~ a).(J~ a), (J~ a).(J~ b), (J~ b).(J~ b)}, closed with Omega where there is one
+//   hs3_cost  k_pg_cost_partial  |r~|^2 = residual_scaling^2 s
+// 0, or -1 where the loss is refused.
+int hs3_edge(const double* k0, const double* k1, const double* m, int kind, double lp0, double lp1, const double* info9, double* r, double* J) {
+    PgLoss l;
+    if (!pg_loss_make(kind, lp0, lp1, &l)) return -1;
+    double p0[4], p1[4], pm[4];
+    So3Manifold::prepare(k0, p0); So3Manifold::prepare(k1, p1); So3Manifold::prepare(m, pm);
+    if (info9) So3Manifold::export_edge_info(p0, p1, pm, l, info9, r, J);
+    else So3Manifold::export_edge(p0, p1, pm, l, r, J);
+    return 0;
+}
+int hs3_jv(const double* k0, const double* k1, const double* m, int kind, double lp0, double lp1, const double* info9, const double* a0,
+           const double* a1, const double* b0, const double* b1, double* out3) {
+    PgLoss l;
+    if (!pg_loss_make(kind, lp0, lp1, &l)) return -1;
+    double p0[4], p1[4], pm[4], u[3], w[3], Wu[3], Ww[3];
+    So3Manifold::prepare(k0, p0); So3Manifold::prepare(k1, p1); So3Manifold::prepare(m, pm);
+    if (info9) {
+        So3Manifold::edge_jv_info(p0, p1, pm, l, info9, a0, a1, b0, b1, u, w);
+        info_mv<3>(info9, u, Wu); info_mv<3>(info9, w, Ww);
+    } else {
+        So3Manifold::edge_jv(p0, p1, pm, l, a0, a1, b0, b1, u, w);
+        for (int i = 0; i < 3; ++i) { Wu[i] = u[i]; Ww[i] = w[i]; }
+    }
+    out3[0] = dotn<3>(u, Wu); out3[1] = dotn<3>(u, Ww); out3[2] = dotn<3>(w, Ww);
+    return 0;
+}
+int hs3_cost(const double* k0, const double* k1, const double* m, int kind, double lp0, double lp1, const double* info9, double* out) {
+    PgLoss l;
+    if (!pg_loss_make(kind, lp0, lp1, &l)) return -1;
+    double p0[4], p1[4], pm[4], r[3];
+    So3Manifold::prepare(k0, p0); So3Manifold::prepare(k1, p1); So3Manifold::prepare(m, pm);
+    So3Manifold::residual(p0, p1, pm, r);
+    const double s = info9 ? info_sqnorm<3>(info9, r) : (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+    const double sc = pg_loss_corrector(l, s).residual_scaling;
+    *out = (sc * sc) * s;
+    return 0;
+}
+
 // the incident list of vertex v (ascending edge index, a self-loop once): the order in which its diagonal block is summed
 int64_t hs3_incident(int64_t n_v, int64_t n_e, const uint32_t* ef, const uint32_t* et, int64_t v, uint32_t* out) {
     IncidentLists inc;

@@ -53,10 +53,14 @@ def thresholds(loss):
     return []
 
 
-def evaluate(loss, s):
-    """[rho, rho', rho''] at the fp64 squared norm s"""
+def evaluate(loss, s, dtype=LD):
+    """[rho, rho', rho''] at the fp64 squared norm s.  dtype: the arithmetic behind the branches -- np.longdouble (the reference), or
+    np.float64: the same statements as an fp64 evaluation of them, whose distance from the reference is what fp64 code may be off by
+    (as tile_ref.selected_inverse takes a dtype)"""
+    LD = dtype
     s64 = float(s)
     s = LD(s64)
+    F64_MIN, PI = LD(-np.finfo(np.float64).max), LD(np.pi)
     k = loss.kind
     p0, p1 = LD(loss.p0), LD(loss.p1)
     l2 = np.array([s, LD(1), LD(0)], dtype=LD)
@@ -145,13 +149,14 @@ def evaluate(loss, s):
     raise ValueError(f"unknown loss kind {k}")
 
 
-def corrector(loss, s):
+def corrector(loss, s, dtype=LD):
     """(sqrt_rho1, residual_scaling, alpha_sq_norm, arm) -- arm 1 | 2"""
-    return corrector_of(evaluate(loss, s), s)
+    return corrector_of(evaluate(loss, s, dtype), s, dtype)
 
 
-def corrector_of(rho, s):
-    """Corrector::new on a given (rho, rho', rho'')"""
+def corrector_of(rho, s, dtype=LD):
+    """Corrector::new on a given (rho, rho', rho''), in the arithmetic of dtype"""
+    LD = dtype
     rho = np.asarray(rho, dtype=LD)
     with np.errstate(invalid="ignore"):
         sq = np.sqrt(rho[1])
@@ -168,14 +173,15 @@ def six(loss, s):
     return np.concatenate([evaluate(loss, s), np.array(c[:3], dtype=LD)])
 
 
-def correct(r, J, loss):
+def correct(r, J, loss, dtype=LD):
     """(r~, the literal J~, arm) of one residual block: r (m,), J (m, n), uncorrected, fp64.  s is the fp64 squared norm the
-    device forms (left to right)."""
+    device forms (left to right).  dtype: the arithmetic of the correction (evaluate)."""
+    LD = dtype
     r64 = np.asarray(r, dtype=np.float64)
     s = np.float64(0.0)
     for x in r64:
         s = s + x * x
-    sq, rs, a, arm = corrector(loss, float(s))
+    sq, rs, a, arm = corrector(loss, float(s), dtype)
     rl, Jl = r64.astype(LD), np.asarray(J, dtype=np.float64).astype(LD)
     if arm == 1:
         return rl * rs, Jl * sq, 1, float(s)
