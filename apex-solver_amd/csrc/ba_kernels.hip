@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "ba_device.hpp"
+#include "ba_dispatch.h"
 #include "ba_kernels.h"
 #include "device_reduce.hpp"
 
@@ -965,89 +966,87 @@ void launch_cam_reduce(int dc, const BAView& v, const TileMap& tm, const int* ca
                        double lambda, int add_lambda, const double* hinv, const double* g_l, int with_self, double* g_c,
                        double* g_red, hipStream_t s, const PgLoss* loss) {
     if (v.n_cam == 0) return;
-    const bool masked = !(v.mask_code == 7 || (dc == 6 && v.mask_code == 6));   // (the masked form costs a wave per SIMD at d_c = 9)
-#define CAM_REDUCE(DCV, MK, WS)                                                                                                                            \
-    do {                                                                                                                                                   \
-        if (loss) hipLaunchKernelGGL((k_cam_reduce<DCV, MK, WS, PgLoss>), dim3((unsigned)v.n_cam), dim3(kCamThreads), 0, s, v, *loss, tm, cam_ptr, cam_obs, lambda, add_lambda, hinv, g_l, g_c, g_red); \
-        else hipLaunchKernelGGL((k_cam_reduce<DCV, MK, WS>), dim3((unsigned)v.n_cam), dim3(kCamThreads), 0, s, v, tm, cam_ptr, cam_obs, lambda, add_lambda, hinv, g_l, g_c, g_red);                    \
-    } while (0)
-    if (with_self) {
-        if (dc == 9 && !masked) CAM_REDUCE(9, false, true); else if (dc == 9) CAM_REDUCE(9, true, true);
-        else if (!masked) CAM_REDUCE(6, false, true); else CAM_REDUCE(6, true, true);
-    } else {
-        if (dc == 9 && !masked) CAM_REDUCE(9, false, false); else if (dc == 9) CAM_REDUCE(9, true, false);
-        else if (!masked) CAM_REDUCE(6, false, false); else CAM_REDUCE(6, true, false);
-    }
-#undef CAM_REDUCE
+    const bool masked = !all_columns_free(dc, v.mask_code);   // (the masked form costs a wave per SIMD at d_c = 9)
+    with_dc(dc, [&](auto DC) {
+        with_bool(masked, [&](auto MK) {
+            with_bool(with_self != 0, [&](auto WS) {
+                with_ba_loss(loss, [&](auto... l) {
+                    hipLaunchKernelGGL((k_cam_reduce<DC(), MK(), WS(), decltype(l)...>), dim3((unsigned)v.n_cam),
+                                       dim3(kCamThreads), 0, s, v, l..., tm, cam_ptr, cam_obs, lambda, add_lambda, hinv, g_l, g_c, g_red);
+                });
+            });
+        });
+    });
 }
 
 void launch_landmark_reduce(int dc, const BAView& v, double lambda, double* hinv, double* g_l, int* err_flag, double* lmu,
                             hipStream_t s, double* orec, const PgLoss* loss) {
     if (v.n_pt == 0) return;
-    const int grid = lm_grid(v);
-    if (loss) {
-        if (dc == 9) hipLaunchKernelGGL((k_landmark_reduce<9, PgLoss>), dim3(grid), dim3(kLmWg * kLmLanes), 0, s, v, *loss, lambda, hinv, g_l, err_flag, lmu, orec);
-        else hipLaunchKernelGGL((k_landmark_reduce<6, PgLoss>), dim3(grid), dim3(kLmWg * kLmLanes), 0, s, v, *loss, lambda, hinv, g_l, err_flag, lmu, orec);
-        return;
-    }
-    if (dc == 9) hipLaunchKernelGGL(k_landmark_reduce<9>, dim3(grid), dim3(kLmWg * kLmLanes), 0, s, v, lambda, hinv, g_l, err_flag, lmu, orec);
-    else hipLaunchKernelGGL(k_landmark_reduce<6>, dim3(grid), dim3(kLmWg * kLmLanes), 0, s, v, lambda, hinv, g_l, err_flag, lmu, orec);
+    with_dc(dc, [&](auto DC) {
+        with_ba_loss(loss, [&](auto... l) {
+            hipLaunchKernelGGL((k_landmark_reduce<DC(), decltype(l)...>), dim3(lm_grid(v)), dim3(kLmWg * kLmLanes), 0, s, v, l..., lambda, hinv,
+                               g_l, err_flag, lmu, orec);
+        });
+    });
 }
 
 void launch_prepare_cams(int64_t n_cam, const double* poses, const double* intr, double* camp, int mask_code, hipStream_t s) {
     if (n_cam > 0) hipLaunchKernelGGL(k_prepare_cams, dim3(grid_for(n_cam, 256, 0)), dim3(256), 0, s, n_cam, poses, intr, camp, mask_code);
 }
 
-
 // orec != nullptr: the record form (the records of THIS linearisation, k_landmark_reduce); ignored in the masked modes
-static bool rec_form_ok(int dc, const BAView& v, const double* orec) { return orec != nullptr && v.mask_code == (dc == 9 ? 7 : 6); }
+static bool rec_form_ok(int dc, const BAView& v, const double* orec) { return orec != nullptr && all_columns_free(dc, v.mask_code); }
+// the one place k_back_substitute is launched (back-substitution, and MATVEC: the landmark half of the matrix-free operator) and
+// its form chosen: the record form first, without a loss whatever `loss` is (the record carries sqrt(rho') of whichever loss
+// wrote it: one form for every loss); else the general loss; else v.huber_delta
+template <bool MATVEC>
+static void launch_bs_form(int dc, const BAView& v, const double* hinv, const double* g_l, const double* dcam, double* dl, hipStream_t s,
+                           const double* orec, const uint8_t* fix_pt, double* pts_trial, const PgLoss* loss) {
+    const bool rec = rec_form_ok(dc, v, orec);
+    with_dc(dc, [&](auto DC) {
+        with_bool(rec, [&](auto REC) {
+            auto launch = [&](auto... l) {
+                hipLaunchKernelGGL((k_back_substitute<DC(), MATVEC, REC(), kBsLanes, decltype(l)...>), dim3(lm_grid(v)),
+                                   dim3(kLmWg * kBsLanes), 0, s, v, l..., hinv, g_l, dcam, dl, REC() ? orec : nullptr, fix_pt, pts_trial);
+            };
+            if constexpr (REC()) launch();
+            else with_ba_loss(loss, launch);
+        });
+    });
+}
 void launch_back_substitute(int dc, const BAView& v, const double* hinv, const double* g_l, const double* dcam,
                             double* dl, hipStream_t s, const double* orec, const uint8_t* fix_pt, double* pts_trial, const PgLoss* loss) {
     if (v.n_pt == 0) return;
-    const int grid = lm_grid(v);
-    if (rec_form_ok(dc, v, orec)) {   // (the record carries sqrt(rho') of whichever loss wrote it: one form for every loss)
-        if (dc == 9) hipLaunchKernelGGL((k_back_substitute<9, false, true>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, g_l, dcam, dl, orec, fix_pt, pts_trial);
-        else hipLaunchKernelGGL((k_back_substitute<6, false, true>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, g_l, dcam, dl, orec, fix_pt, pts_trial);
-        return;
-    }
-    if (loss) {
-        if (dc == 9) hipLaunchKernelGGL((k_back_substitute<9, false, false, kBsLanes, PgLoss>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, *loss, hinv, g_l, dcam, dl, nullptr, fix_pt, pts_trial);
-        else hipLaunchKernelGGL((k_back_substitute<6, false, false, kBsLanes, PgLoss>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, *loss, hinv, g_l, dcam, dl, nullptr, fix_pt, pts_trial);
-        return;
-    }
-    if (dc == 9) hipLaunchKernelGGL((k_back_substitute<9, false, false>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, g_l, dcam, dl, nullptr, fix_pt, pts_trial);
-    else hipLaunchKernelGGL((k_back_substitute<6, false, false>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, g_l, dcam, dl, nullptr, fix_pt, pts_trial);
+    launch_bs_form<false>(dc, v, hinv, g_l, dcam, dl, s, orec, fix_pt, pts_trial, loss);
 }
 
 void launch_retract(int dc, int64_t n_cam, int64_t n_pt, const double* poses, const double* intr, const double* pts,
                     const double* dcam, const double* dl, double sign, const uint8_t* fix_pose,
                     const uint8_t* fix_intr, const uint8_t* fix_pt, double* poses_out, double* intr_out,
                     double* pts_out, hipStream_t s) {
-    if (n_cam > 0) {
-        const int grid = grid_for(n_cam, 256, 0);
-        if (dc == 9) hipLaunchKernelGGL(k_retract_cams<9>, dim3(grid), dim3(256), 0, s, n_cam, poses, intr, dcam, sign, fix_pose, fix_intr, poses_out, intr_out);
-        else hipLaunchKernelGGL(k_retract_cams<6>, dim3(grid), dim3(256), 0, s, n_cam, poses, intr, dcam, sign, fix_pose, fix_intr, poses_out, intr_out);
-    }
+    if (n_cam > 0)
+        with_dc(dc, [&](auto DC) {
+            hipLaunchKernelGGL(k_retract_cams<DC()>, dim3(grid_for(n_cam, 256, 0)), dim3(256), 0, s, n_cam, poses, intr, dcam, sign, fix_pose,
+                               fix_intr, poses_out, intr_out);
+        });
     if (n_pt > 0)
         hipLaunchKernelGGL(k_retract_points, dim3(grid_for(3 * n_pt, 256, 0)), dim3(256), 0, s, 3 * n_pt, pts, dl, sign, fix_pt, pts_out);
 }
 
 void launch_cost(const BAView& v, double* partial, int n_partial, double* out_sumsq, hipStream_t s, const PgLoss* loss) {
-    if (loss) hipLaunchKernelGGL(k_cost_partial<PgLoss>, dim3(n_partial), dim3(256), 0, s, v, *loss, partial);
-    else hipLaunchKernelGGL(k_cost_partial<>, dim3(n_partial), dim3(256), 0, s, v, partial);
+    with_ba_loss(loss, [&](auto... l) {
+        hipLaunchKernelGGL(k_cost_partial<decltype(l)...>, dim3(n_partial), dim3(256), 0, s, v, l..., partial);
+    });
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, partial, n_partial, 1, out_sumsq);
 }
 
 void launch_ba_jv_gram(int dc, const BAView& v, const double* a_cam, const double* a_pt, const double* b_cam, const double* b_pt,
                        double* partial, int n_partial, double* out3, hipStream_t s, const PgLoss* loss) {
-    const dim3 grid(n_partial), block(256);
-    if (loss) {
-        if (dc == 9) hipLaunchKernelGGL((k_ba_jv_gram<9, PgLoss>), grid, block, 0, s, v, *loss, a_cam, a_pt, b_cam, b_pt, partial);
-        else hipLaunchKernelGGL((k_ba_jv_gram<6, PgLoss>), grid, block, 0, s, v, *loss, a_cam, a_pt, b_cam, b_pt, partial);
-    } else {
-        if (dc == 9) hipLaunchKernelGGL(k_ba_jv_gram<9>, grid, block, 0, s, v, a_cam, a_pt, b_cam, b_pt, partial);
-        else hipLaunchKernelGGL(k_ba_jv_gram<6>, grid, block, 0, s, v, a_cam, a_pt, b_cam, b_pt, partial);
-    }
+    with_dc(dc, [&](auto DC) {
+        with_ba_loss(loss, [&](auto... l) {
+            hipLaunchKernelGGL((k_ba_jv_gram<DC(), decltype(l)...>), dim3(n_partial), dim3(256), 0, s, v, l..., a_cam, a_pt, b_cam, b_pt, partial);
+        });
+    });
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, partial, n_partial, 3, out3);
 }
 
@@ -1059,14 +1058,11 @@ void launch_step_stats(int64_t n, const double* g, const double* d, double lambd
 
 void launch_column_norms_sq(int dc, const BAView& v, double* n2_cam, double* n2_pt, hipStream_t s, const PgLoss* loss) {
     if (v.n_obs == 0) return;
-    const unsigned grid = (unsigned)((v.n_obs + 255) / 256);
-    if (loss) {
-        if (dc == 9) hipLaunchKernelGGL((k_column_norms_sq<9, PgLoss>), dim3(grid), dim3(256), 0, s, v, *loss, n2_cam, n2_pt);
-        else hipLaunchKernelGGL((k_column_norms_sq<6, PgLoss>), dim3(grid), dim3(256), 0, s, v, *loss, n2_cam, n2_pt);
-        return;
-    }
-    if (dc == 9) hipLaunchKernelGGL(k_column_norms_sq<9>, dim3(grid), dim3(256), 0, s, v, n2_cam, n2_pt);
-    else hipLaunchKernelGGL(k_column_norms_sq<6>, dim3(grid), dim3(256), 0, s, v, n2_cam, n2_pt);
+    with_dc(dc, [&](auto DC) {
+        with_ba_loss(loss, [&](auto... l) {
+            hipLaunchKernelGGL((k_column_norms_sq<DC(), decltype(l)...>), dim3((unsigned)((v.n_obs + 255) / 256)), dim3(256), 0, s, v, l..., n2_cam, n2_pt);
+        });
+    });
 }
 void launch_scaling_from_norms_sq(int64_t n, const double* n2, double* scale, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_scaling_from_norms_sq, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, n2, scale);
@@ -1080,8 +1076,9 @@ void launch_vec_add(int64_t n, const double* a, const double* b, double* out, hi
 void launch_scale_diag_blocks(int dc, int64_t n_cam, const double* scale, double* sd, hipStream_t s) {
     const int64_t n = n_cam * dc * dc;
     if (n == 0) return;
-    if (dc == 9) hipLaunchKernelGGL(k_scale_diag_blocks<9>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_cam, scale, sd);
-    else hipLaunchKernelGGL(k_scale_diag_blocks<6>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_cam, scale, sd);
+    with_dc(dc, [&](auto DC) {
+        hipLaunchKernelGGL(k_scale_diag_blocks<DC()>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_cam, scale, sd);
+    });
 }
 
 void launch_sumsq(int64_t n, const double* x, double* partial, int n_partial, double* out, hipStream_t s) {
@@ -1116,41 +1113,30 @@ void launch_gather_u32(int64_t n, const int* idx, const uint32_t* src, uint32_t*
 // y = S x without S: landmark half (u_l into lmu), then camera half
 void launch_implicit_matvec(int dc, const BAView& v, const int* cam_ptr, const double* hinv, double* lmu, const double* x,
                             double lambda, double* y, hipStream_t s, const double* orec, const PgLoss* loss) {
-    if (v.n_pt > 0) {
-        const int grid = lm_grid(v);
-        if (rec_form_ok(dc, v, orec)) {
-            if (dc == 9) hipLaunchKernelGGL((k_back_substitute<9, true, true>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, nullptr, x, lmu, orec, nullptr, nullptr);
-            else hipLaunchKernelGGL((k_back_substitute<6, true, true>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, nullptr, x, lmu, orec, nullptr, nullptr);
-        } else if (loss) {
-            if (dc == 9) hipLaunchKernelGGL((k_back_substitute<9, true, false, kBsLanes, PgLoss>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, *loss, hinv, nullptr, x, lmu, nullptr, nullptr, nullptr);
-            else hipLaunchKernelGGL((k_back_substitute<6, true, false, kBsLanes, PgLoss>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, *loss, hinv, nullptr, x, lmu, nullptr, nullptr, nullptr);
-        } else {
-            if (dc == 9) hipLaunchKernelGGL((k_back_substitute<9, true, false>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, nullptr, x, lmu, nullptr, nullptr, nullptr);
-            else hipLaunchKernelGGL((k_back_substitute<6, true, false>), dim3(grid), dim3(kLmWg * kBsLanes), 0, s, v, hinv, nullptr, x, lmu, nullptr, nullptr, nullptr);
-        }
-    }
-    if (loss) {
-        if (dc == 9) hipLaunchKernelGGL((k_implicit_cam<9, PgLoss>), dim3((unsigned)v.n_cam), dim3(64), 0, s, v, *loss, cam_ptr, lmu, x, lambda, y);
-        else hipLaunchKernelGGL((k_implicit_cam<6, PgLoss>), dim3((unsigned)v.n_cam), dim3(64), 0, s, v, *loss, cam_ptr, lmu, x, lambda, y);
-        return;
-    }
-    if (dc == 9) hipLaunchKernelGGL(k_implicit_cam<9>, dim3((unsigned)v.n_cam), dim3(64), 0, s, v, cam_ptr, lmu, x, lambda, y);
-    else hipLaunchKernelGGL(k_implicit_cam<6>, dim3((unsigned)v.n_cam), dim3(64), 0, s, v, cam_ptr, lmu, x, lambda, y);
+    if (v.n_pt > 0) launch_bs_form<true>(dc, v, hinv, nullptr, x, lmu, s, orec, nullptr, nullptr, loss);
+    with_dc(dc, [&](auto DC) {
+        with_ba_loss(loss, [&](auto... l) {
+            hipLaunchKernelGGL((k_implicit_cam<DC(), decltype(l)...>), dim3((unsigned)v.n_cam), dim3(64), 0, s, v, l..., cam_ptr, lmu, x, lambda, y);
+        });
+    });
 }
 void launch_extract_diag_blocks(int dc, int64_t n_cam, const TileMap& tm, double* sd, hipStream_t s) {
     const int64_t n = n_cam * dc * dc;
-    if (dc == 9) hipLaunchKernelGGL(k_extract_diag_blocks<9>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_cam, tm, sd);
-    else hipLaunchKernelGGL(k_extract_diag_blocks<6>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_cam, tm, sd);
+    with_dc(dc, [&](auto DC) {
+        hipLaunchKernelGGL(k_extract_diag_blocks<DC()>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_cam, tm, sd);
+    });
 }
 void launch_precond_blocks(int dc, int64_t n_cam, const double* sd, double* minv, hipStream_t s) {
     const unsigned grid = (unsigned)((2 * n_cam + 63) / 64);
-    if (dc == 9) hipLaunchKernelGGL(k_precond_blocks<9>, dim3(grid), dim3(64), 0, s, n_cam, sd, minv);
-    else hipLaunchKernelGGL(k_precond_blocks<6>, dim3(grid), dim3(64), 0, s, n_cam, sd, minv);
+    with_dc(dc, [&](auto DC) {
+        hipLaunchKernelGGL(k_precond_blocks<DC()>, dim3(grid), dim3(64), 0, s, n_cam, sd, minv);
+    });
 }
 void launch_precond_apply(int dc, int64_t n_cam, const double* minv, const double* r, double* z, hipStream_t s) {
     const int64_t n = n_cam * dc;
-    if (dc == 9) hipLaunchKernelGGL(k_precond_apply<9>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, minv, r, z);
-    else hipLaunchKernelGGL(k_precond_apply<6>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, minv, r, z);
+    with_dc(dc, [&](auto DC) {
+        hipLaunchKernelGGL(k_precond_apply<DC()>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, minv, r, z);
+    });
 }
 
 // two dot products in one pass: partial[b] = {sum a1 b1, sum a2 b2}
@@ -1201,14 +1187,12 @@ void launch_debug_invert_blocks(int64_t n, const double* in, double* out, int* o
 void launch_export_linearization(int dc, const BAView& v, const int* o_orig, double* r_out, double* jc_out,
                                  double* jl_out, hipStream_t s, const PgLoss* loss) {
     if (v.n_obs == 0) return;
-    const int grid = grid_for(v.n_obs, 256, 0);
-    if (loss) {
-        if (dc == 9) hipLaunchKernelGGL((k_export_linearization<9, PgLoss>), dim3(grid), dim3(256), 0, s, v, *loss, o_orig, r_out, jc_out, jl_out);
-        else hipLaunchKernelGGL((k_export_linearization<6, PgLoss>), dim3(grid), dim3(256), 0, s, v, *loss, o_orig, r_out, jc_out, jl_out);
-        return;
-    }
-    if (dc == 9) hipLaunchKernelGGL(k_export_linearization<9>, dim3(grid), dim3(256), 0, s, v, o_orig, r_out, jc_out, jl_out);
-    else hipLaunchKernelGGL(k_export_linearization<6>, dim3(grid), dim3(256), 0, s, v, o_orig, r_out, jc_out, jl_out);
+    with_dc(dc, [&](auto DC) {
+        with_ba_loss(loss, [&](auto... l) {
+            hipLaunchKernelGGL((k_export_linearization<DC(), decltype(l)...>), dim3(grid_for(v.n_obs, 256, 0)), dim3(256), 0, s, v, l..., o_orig, r_out,
+                               jc_out, jl_out);
+        });
+    });
 }
 
 // (set-up: the first launch of a kernel of this translation unit loads its code object -- tens of milliseconds for the big

@@ -15,6 +15,7 @@
 #include "ba_prior_kernels.h"
 
 #include "ba_device.hpp"
+#include "ba_dispatch.h"
 #include "device_reduce.hpp"
 #include "pg_device.hpp"
 
@@ -161,16 +162,18 @@ __global__ __launch_bounds__(64) void k_ba_prior_export(const double* __restrict
 static unsigned grid_of(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
 void launch_ba_prior_eval(int dc, int64_t n_cam, const double* camq, const BaPriorView& pv, double* pdiag, double* pg, double* pcost, hipStream_t s) {
-    if (dc == 9) hipLaunchKernelGGL(k_ba_prior_eval<9>, dim3(grid_of(n_cam, 64)), dim3(64), 0, s, n_cam, camq, pv, pdiag, pg, pcost);
-    else hipLaunchKernelGGL(k_ba_prior_eval<6>, dim3(grid_of(n_cam, 64)), dim3(64), 0, s, n_cam, camq, pv, pdiag, pg, pcost);
+    with_dc(dc, [&](auto DC) {
+        hipLaunchKernelGGL(k_ba_prior_eval<DC()>, dim3(grid_of(n_cam, 64)), dim3(64), 0, s, n_cam, camq, pv, pdiag, pg, pcost);
+    });
 }
 void launch_ba_prior_add_system(int64_t n_c, const double* pdiag, const double* pg, const TileMap& tm, double* g_c, double* g_red, hipStream_t s) {
     hipLaunchKernelGGL(k_ba_prior_add_system, dim3(grid_of(n_c, 256)), dim3(256), 0, s, n_c, pdiag, pg, tm, g_c, g_red);
 }
 void launch_ba_prior_add_blocks(int dc, int64_t n_cam, const double* pdiag, const double* pg, double* sd, double* g_c, double* g_red, hipStream_t s) {
     const int64_t n_c = n_cam * dc;
-    if (dc == 9) hipLaunchKernelGGL(k_ba_prior_add_blocks<9>, dim3(grid_of(n_c, 256)), dim3(256), 0, s, n_c, pdiag, pg, sd, g_c, g_red);
-    else hipLaunchKernelGGL(k_ba_prior_add_blocks<6>, dim3(grid_of(n_c, 256)), dim3(256), 0, s, n_c, pdiag, pg, sd, g_c, g_red);
+    with_dc(dc, [&](auto DC) {
+        hipLaunchKernelGGL(k_ba_prior_add_blocks<DC()>, dim3(grid_of(n_c, 256)), dim3(256), 0, s, n_c, pdiag, pg, sd, g_c, g_red);
+    });
 }
 void launch_ba_prior_matvec(int64_t n_c, const double* pdiag, const double* x, double* y, hipStream_t s) {
     hipLaunchKernelGGL(k_ba_prior_matvec, dim3(grid_of(n_c, 256)), dim3(256), 0, s, n_c, pdiag, x, y);

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "ba_device.hpp"
+#include "ba_dispatch.h"
 #include "ba_kernels.h"
 
 namespace apex {
@@ -165,27 +166,15 @@ void launch_landmark_cov(int dc, const BAView& v, const double* hinv, const Tile
                          const int* large_list, int n_large, double* out, int* err, hipStream_t s, const PgLoss* loss) {
     constexpr int NT = 128, G = 8;
     static_assert(kLcSmallK <= G, "a small landmark is one chunk of its group");
-    if (loss) {
-        if (n_large > 0) {
-            if (dc == 9) hipLaunchKernelGGL((k_landmark_cov<9, 64, 64, kLcChunk, PgLoss>), dim3(n_large), dim3(64), 0, s, v, *loss, hinv, z, large_list, n_large, out, err);
-            else hipLaunchKernelGGL((k_landmark_cov<6, 64, 64, kLcChunk, PgLoss>), dim3(n_large), dim3(64), 0, s, v, *loss, hinv, z, large_list, n_large, out, err);
-        }
-        if (n_small > 0) {
-            const int grid = (n_small + NT / G - 1) / (NT / G);
-            if (dc == 9) hipLaunchKernelGGL((k_landmark_cov<9, G, NT, kLcSmallK, PgLoss>), dim3(grid), dim3(NT), 0, s, v, *loss, hinv, z, small_list, n_small, out, err);
-            else hipLaunchKernelGGL((k_landmark_cov<6, G, NT, kLcSmallK, PgLoss>), dim3(grid), dim3(NT), 0, s, v, *loss, hinv, z, small_list, n_small, out, err);
-        }
-        return;
-    }
-    if (n_large > 0) {   // first: the long ones start early and the short ones fill in behind them
-        if (dc == 9) hipLaunchKernelGGL((k_landmark_cov<9, 64, 64, kLcChunk>), dim3(n_large), dim3(64), 0, s, v, hinv, z, large_list, n_large, out, err);
-        else hipLaunchKernelGGL((k_landmark_cov<6, 64, 64, kLcChunk>), dim3(n_large), dim3(64), 0, s, v, hinv, z, large_list, n_large, out, err);
-    }
-    if (n_small > 0) {
-        const int grid = (n_small + NT / G - 1) / (NT / G);
-        if (dc == 9) hipLaunchKernelGGL((k_landmark_cov<9, G, NT, kLcSmallK>), dim3(grid), dim3(NT), 0, s, v, hinv, z, small_list, n_small, out, err);
-        else hipLaunchKernelGGL((k_landmark_cov<6, G, NT, kLcSmallK>), dim3(grid), dim3(NT), 0, s, v, hinv, z, small_list, n_small, out, err);
-    }
+    with_dc(dc, [&](auto DC) {
+        with_ba_loss(loss, [&](auto... l) {
+            if (n_large > 0)   // first: the long ones start early and the short ones fill in behind them
+                hipLaunchKernelGGL((k_landmark_cov<DC(), 64, 64, kLcChunk, decltype(l)...>), dim3(n_large), dim3(64), 0, s, v, l..., hinv, z, large_list, n_large, out, err);
+            if (n_small > 0)
+                hipLaunchKernelGGL((k_landmark_cov<DC(), G, NT, kLcSmallK, decltype(l)...>), dim3((n_small + NT / G - 1) / (NT / G)), dim3(NT), 0, s, v, l..., hinv, z,
+                                   small_list, n_small, out, err);
+        });
+    });
 }
 
 }  // namespace apex

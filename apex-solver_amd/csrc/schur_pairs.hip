@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "ba_device.hpp"
+#include "ba_dispatch.h"
 #include "device_buffer.h"
 #include "host_parallel.h"
 
@@ -1050,12 +1051,16 @@ void launch_schur_pairs(int dc, const BAView& v, double* tiles, const PairTask* 
                         const PairQDesc* qdesc) {
     if (n_tasks == 0) return;
     const unsigned grid = (unsigned)((n_tasks + 3) / 4);
-    const bool masked = v.mask_code != (dc == 9 ? 7 : 6);
-#define PAIRS_R(DCV, MK, Q) hipLaunchKernelGGL((k_schur_pairs_r<DCV, MK, Q>), dim3(grid), dim3(256), 0, s, v, tiles, tasks, n_tasks, chunks, blocks, recs, lmrec, orec, qdesc)
-    if (dc == 9 && qdesc) { if (masked) PAIRS_R(9, true, true); else PAIRS_R(9, false, true); }
-    else if (dc == 9) { if (masked) PAIRS_R(9, true, false); else PAIRS_R(9, false, false); }
-    else { if (masked) PAIRS_R(6, true, false); else PAIRS_R(6, false, false); }
-#undef PAIRS_R
+    const bool masked = !all_columns_free(dc, v.mask_code);
+    with_dc(dc, [&](auto DC) {
+        auto launch = [&](auto Q) {
+            with_bool(masked, [&](auto MK) {
+                hipLaunchKernelGGL((k_schur_pairs_r<DC(), MK(), Q()>), dim3(grid), dim3(256), 0, s, v, tiles, tasks, n_tasks, chunks, blocks, recs, lmrec, orec, qdesc);
+            });
+        };
+        if constexpr (DC() == 9) with_bool(qdesc != nullptr, launch);   // (the queued layout exists for nine-column cameras only)
+        else launch(std::false_type{});
+    });
 }
 
 // (set-up: the first launch of a kernel of this translation unit loads its code object -- tens of milliseconds for the big

@@ -17,7 +17,8 @@ from apex_solver_amd.solver import (GpuSchurComplementSolver, LevenbergMarquardt
 
 pytestmark = pytest.mark.gpu
 STEP_FORWARD_BOUND = 1e-7   # (tests/test_gpu_parity.py)
-MODES = {"selfcal": OptimizationType.SelfCalibration, "ba": OptimizationType.BundleAdjustment, "pose_intr": OptimizationType.PoseAndIntrinsics}
+MODES = {"selfcal": OptimizationType.SelfCalibration, "ba": OptimizationType.BundleAdjustment, "pose_intr": OptimizationType.PoseAndIntrinsics,
+         "only_pose": OptimizationType.OnlyPose}
 
 
 def rel(a, b):
@@ -91,6 +92,15 @@ def test_masked_mode_under_cauchy():
     d, losses = sweep_data()
     prob, s = gpu_solver(d, "pose_intr", loss=losses["cauchy"])
     check_assembly_and_steps(d, prob, s, sweep_reference("cauchy", "pose_intr"), 9, "cauchy pose_intr")
+    s.close()
+
+
+def test_six_column_masked_mode_under_cauchy():
+    """OnlyPose: six camera columns and the landmark group masked, so the solve's back-substitution has no record form to take
+    and runs the general-loss instantiation at d_c = 6 (launch_back_substitute), which no other test reaches"""
+    d, losses = sweep_data()
+    prob, s = gpu_solver(d, "only_pose", loss=losses["cauchy"])
+    check_assembly_and_steps(d, prob, s, sweep_reference("cauchy", "only_pose"), 6, "cauchy only_pose")
     s.close()
 
 
