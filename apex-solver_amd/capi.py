@@ -18,46 +18,6 @@ NUM_STAGES = 10
 STAGE_NAMES = ("cam_reduce", "landmark_reduce", "schur_scatter", "all_reduce", "factor", "tri_solve",
                "back_substitute", "step_stats", "retract", "cost")
 
-# every symbol include/apexgpu.h declares (checked by tests/test_capi_symbols.py)
-SYMBOLS = (
-    "apexgpu_create", "apexgpu_destroy", "apexgpu_last_error", "apexgpu_version", "apexgpu_set_structure",
-    "apexgpu_set_cg_params", "apexgpu_set_params", "apexgpu_get_params", "apexgpu_cost", "apexgpu_assemble", "apexgpu_solve_augmented",
-    "apexgpu_step_stats", "apexgpu_eval_step", "apexgpu_commit_step", "apexgpu_discard_step",
-    "apexgpu_parameter_norm", "apexgpu_column_norms", "apexgpu_set_column_scaling", "apexgpu_lm_optimize", "apexgpu_get_residual", "apexgpu_get_jacobian_blocks",
-    "apexgpu_get_schur", "apexgpu_camera_covariance", "apexgpu_covariance_stats", "apexgpu_landmark_covariance", "apexgpu_landmark_covariance_stats", "apexgpu_get_landmark_blocks", "apexgpu_get_hessian_csc", "apexgpu_debug_invert_blocks", "apexgpu_debug_pair_lists", "apexgpu_debug_pair_lists_queued", "apexgpu_debug_pair_lists_queued_dc", "apexgpu_debug_host_structure", "apexgpu_setup_times", "apexgpu_schur_matvec", "apexgpu_set_option", "apexgpu_enable_stage_timing", "apexgpu_reset_stage_times",
-    "apexgpu_stage_times", "apexgpu_info", "apexgpu_variant_info", "apexgpu_variant_costs", "apexgpu_trim_host_cache", "apexgpu_host_cache_bytes", "apexgpu_counters", "apexgpu_debug_get_pair_records", "apexgpu_get_unique_id", "apexgpu_comm_init", "apexgpu_comm_init_shm", "apexgpu_set_shard", "apexgpu_shard_range",
-    "apexgpu_debug_lockstep_solve", "apexgpu_export_step", "apexgpu_owned_landmarks", "apexgpu_debug_partition", "apexgpu_debug_check_schedule",
-    "apexgpu_debug_schedule_ops", "apexgpu_debug_plan_lists", "apexgpu_debug_sinv_lists", "apexgpu_debug_sinv_lists_direct",
-    "apexgpu_debug_tiles_create", "apexgpu_debug_tiles_pattern", "apexgpu_debug_tiles_set", "apexgpu_debug_tiles_factor",
-    "apexgpu_debug_tiles_solve", "apexgpu_debug_tiles_matvec", "apexgpu_debug_tiles_pcg", "apexgpu_debug_tiles_get", "apexgpu_debug_tiles_destroy",
-    "apexgpu_bal_open", "apexgpu_bal_close", "apexgpu_bal_last_error", "apexgpu_bal_sizes", "apexgpu_bal_raw",
-    "apexgpu_bal_variables", "apexgpu_reference_columns",
-    # SE3 pose-graph backend
-    "apexgpu_pg_create", "apexgpu_pg_destroy", "apexgpu_pg_last_error", "apexgpu_pg_set_structure", "apexgpu_pg_set_params",
-    "apexgpu_pg_get_params", "apexgpu_pg_cost", "apexgpu_pg_solve_augmented", "apexgpu_pg_step_stats", "apexgpu_pg_eval_step",
-    "apexgpu_pg_commit_step", "apexgpu_pg_discard_step", "apexgpu_pg_parameter_norm", "apexgpu_pg_column_norms",
-    "apexgpu_pg_set_column_scaling", "apexgpu_pg_lm_optimize",
-    "apexgpu_pg_get_residual", "apexgpu_pg_get_jacobian_blocks", "apexgpu_pg_get_hessian", "apexgpu_pg_covariance", "apexgpu_pg_covariance_stats", "apexgpu_pg_set_option",
-    "apexgpu_pg_enable_stage_timing", "apexgpu_pg_reset_stage_times", "apexgpu_pg_stage_times", "apexgpu_pg_info", "apexgpu_pg_counters",
-    "apexgpu_pg_set_priors", "apexgpu_pg_get_prior_residual",
-    "apexgpu_g2o_open", "apexgpu_g2o_close", "apexgpu_g2o_last_error", "apexgpu_g2o_sizes", "apexgpu_g2o_raw",
-    "apexgpu_g2o_problem", "apexgpu_pose_graph_columns",
-    # SE2 pose graphs: the same handle, two more lifetime calls, the SE2 content of a G2O file
-    "apexgpu_pg_create_se2", "apexgpu_pg_manifold", "apexgpu_g2o_raw_se2", "apexgpu_g2o_problem_se2",
-    "apexgpu_pose_graph_columns_se2",
-    # SO3 pose graphs (rotation averaging)
-    "apexgpu_pg_create_so3",
-    # Gauss-Newton and Dog-Leg on pose graphs
-    "apexgpu_pg_jv_gram", "apexgpu_pg_dogleg_step", "apexgpu_pg_gn_optimize", "apexgpu_pg_dogleg_optimize",
-    # Dog-Leg on bundle adjustment
-    "apexgpu_jv_gram", "apexgpu_dogleg_step", "apexgpu_dogleg_optimize",
-    # the robust loss family on pose graphs
-    "apexgpu_pg_set_loss", "apexgpu_pg_get_loss", "apexgpu_loss_evaluate", "apexgpu_set_loss", "apexgpu_get_loss",
-    # edge information matrices on pose graphs
-    "apexgpu_pg_set_information", "apexgpu_pg_get_information", "apexgpu_g2o_problem_information",
-    # prior factors on camera poses and intrinsics in bundle adjustment
-    "apexgpu_set_pose_priors", "apexgpu_set_intrinsic_priors", "apexgpu_get_prior_residual",
-)
 MANIFOLD_SE3, MANIFOLD_SE2, MANIFOLD_SO3 = 0, 1, 2
 # (ambient, dof) per APEXGPU_MANIFOLD_*: stored doubles per vertex / measurement / prior, tangent columns per vertex
 MANIFOLD_SIZES = {MANIFOLD_SE3: (7, 6), MANIFOLD_SE2: (3, 3), MANIFOLD_SO3: (4, 3)}
@@ -68,8 +28,6 @@ LOSS_KINDS = ("NONE", "L2", "L1", "HUBER", "CAUCHY", "FAIR", "GEMAN_MCCLURE", "W
  LOSS_RAMSAY, LOSS_TRIMMED_MEAN, LOSS_LP_NORM, LOSS_BARRON, LOSS_T_DISTRIBUTION) = range(15)
 PG_NUM_STAGES = 6
 PG_STAGE_NAMES = ("assemble", "factor", "tri_solve", "step_stats", "retract", "cost")
-_NON_INT = ("apexgpu_destroy", "apexgpu_debug_tiles_destroy", "apexgpu_last_error", "apexgpu_version", "apexgpu_host_cache_bytes", "apexgpu_bal_close", "apexgpu_bal_last_error",
-            "apexgpu_pg_destroy", "apexgpu_pg_last_error", "apexgpu_g2o_close", "apexgpu_g2o_last_error")
 
 ERROR_NAMES = {
     -1: "FactorizationFailed", -2: "SingularMatrix", -3: "SparseMatrixCreation", -4: "MatrixConversion",
@@ -133,6 +91,153 @@ class DlIterC(C.Structure):
 
 DL_STEP_TYPES = ("GaussNewton", "SteepestDescent", "DogLeg")   # StepType (dog_leg.rs), the value of step_type
 
+_int, _i64, _dbl, _vp, _str, _P = C.c_int, C.c_int64, C.c_double, C.c_void_p, C.c_char_p, C.POINTER
+_opt = [_P(LmResultC), _vp, _int]   # after the handle and the config of an optimise call: result, history, its capacity
+_pairs = [_vp] * 8                       # apexgpu_debug_pair_lists*: cam_idx, pt_idx, counts[4], then five outputs
+
+# Every function include/apexgpu.h declares, in its order: name -> (restype, argtypes).  load() applies exactly this table;
+# SYMBOLS is its key set (held to the header by tests/test_capi_symbols.py).
+API = {
+    "apexgpu_create": (_int, [_i64, _i64, _i64, _int, _int, _P(_vp)]),
+    "apexgpu_destroy": (None, [_vp]),
+    "apexgpu_last_error": (_str, [_vp]),
+    "apexgpu_version": (_str, []),
+    "apexgpu_trim_host_cache": (_int, [_P(_i64)]),
+    "apexgpu_host_cache_bytes": (_i64, []),
+    "apexgpu_set_structure": (_int, [_vp] + [_vp] * 9 + [_dbl]),
+    "apexgpu_set_cg_params": (_int, [_vp, _int, _dbl]),
+    "apexgpu_set_params": (_int, [_vp, _vp, _vp, _vp]),
+    "apexgpu_set_loss": (_int, [_vp, _int, _dbl, _dbl]),
+    "apexgpu_get_loss": (_int, [_vp, _P(_int), _P(_dbl * 2)]),
+    "apexgpu_set_pose_priors": (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "apexgpu_set_intrinsic_priors": (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "apexgpu_get_prior_residual": (_int, [_vp, _vp, _vp]),
+    "apexgpu_get_params": (_int, [_vp, _vp, _vp, _vp]),
+    "apexgpu_cost": (_int, [_vp, _P(_dbl)]),
+    "apexgpu_solve_augmented": (_int, [_vp, _dbl, _int, _vp, _vp]),
+    "apexgpu_assemble": (_int, [_vp, _dbl]),
+    "apexgpu_step_stats": (_int, [_vp, _P(_dbl * 3)]),
+    "apexgpu_eval_step": (_int, [_vp, _P(_dbl)]),
+    "apexgpu_commit_step": (_int, [_vp]),
+    "apexgpu_discard_step": (_int, [_vp]),
+    "apexgpu_parameter_norm": (_int, [_vp, _P(_dbl)]),
+    "apexgpu_column_norms": (_int, [_vp, _vp]),
+    "apexgpu_set_column_scaling": (_int, [_vp, _vp]),
+    "apexgpu_lm_optimize": (_int, [_vp, _P(LmConfigC)] + _opt),
+    "apexgpu_get_residual": (_int, [_vp, _vp]),
+    "apexgpu_get_jacobian_blocks": (_int, [_vp, _vp, _vp]),
+    "apexgpu_get_schur": (_int, [_vp, _vp, _vp]),
+    "apexgpu_camera_covariance": (_int, [_vp, _vp]),
+    "apexgpu_covariance_stats": (_int, [_vp, _P(_dbl * 6), _vp, _int]),
+    "apexgpu_landmark_covariance": (_int, [_vp, _vp]),
+    "apexgpu_landmark_covariance_stats": (_int, [_vp, _P(_dbl * 4)]),
+    "apexgpu_get_landmark_blocks": (_int, [_vp, _vp, _vp]),
+    "apexgpu_debug_invert_blocks": (_int, [_int, _i64, _vp, _vp, _vp]),
+    "apexgpu_get_hessian_csc": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "apexgpu_schur_matvec": (_int, [_vp, _dbl, _vp, _vp, _vp]),
+    "apexgpu_set_option": (_int, [_vp, _str, _int]),
+    "apexgpu_enable_stage_timing": (_int, [_vp, _int]),
+    "apexgpu_reset_stage_times": (_int, [_vp]),
+    "apexgpu_stage_times": (_int, [_vp, _P(_dbl * NUM_STAGES), _P(_i64 * NUM_STAGES)]),
+    "apexgpu_info": (_int, [_vp, _P(_dbl * 16)]),
+    "apexgpu_variant_info": (_int, [_vp, _int, _P(_int), _str, _int]),
+    "apexgpu_variant_costs": (_int, [_vp, _P(_dbl * 4)]),
+    "apexgpu_counters": (_int, [_vp, _P(_i64 * 4)]),
+    "apexgpu_debug_get_pair_records": (_int, [_vp, _vp, _i64]),
+    "apexgpu_setup_times": (_int, [_vp, _vp, _vp]),
+    "apexgpu_get_unique_id": (_int, [_vp]),
+    "apexgpu_comm_init": (_int, [_vp, _int, _int, _vp]),
+    "apexgpu_comm_init_shm": (_int, [_vp, _int, _int, _str]),
+    "apexgpu_set_shard": (_int, [_vp, _int, _int]),
+    "apexgpu_debug_lockstep_solve": (_int, [_vp, _int, _dbl]),
+    "apexgpu_owned_landmarks": (_int, [_vp, _vp]),
+    "apexgpu_debug_partition": (_int, [_int, _vp, _int, _vp]),
+    "apexgpu_debug_check_schedule": (_int, [_int, _vp, _int, _int, _vp, _vp, _str, _int]),
+    "apexgpu_debug_schedule_ops": (_int, [_int, _vp, _int, _int, _vp, _int, _vp, _int]),
+    "apexgpu_debug_plan_lists": (_int, [_int, _vp, _int, _int, _vp, _int, _vp, _int]),
+    "apexgpu_debug_sinv_lists": (_int, [_int, _vp, _vp, _int, _vp, _vp]),
+    "apexgpu_debug_sinv_lists_direct": (_int, [_int, _vp, _int, _vp, _vp, _vp, _int, _vp, _str, _int]),
+    "apexgpu_debug_tiles_create": (_int, [_int, _int, _vp, _vp, _P(_vp)]),
+    "apexgpu_debug_tiles_pattern": (_int, [_vp, _vp, _vp]),
+    "apexgpu_debug_tiles_set": (_int, [_vp, _vp, _int, _dbl, _int]),
+    "apexgpu_debug_tiles_factor": (_int, [_vp, _P(_int)]),
+    "apexgpu_debug_tiles_solve": (_int, [_vp, _int, _vp, _vp]),
+    "apexgpu_debug_tiles_matvec": (_int, [_vp, _vp, _vp]),
+    "apexgpu_debug_tiles_pcg": (_int, [_vp, _vp, _int, _dbl, _vp, _P(_int), _vp]),
+    "apexgpu_debug_tiles_get": (_int, [_vp, _int, _vp, _P(_int)]),
+    "apexgpu_debug_tiles_destroy": (None, [_vp]),
+    "apexgpu_debug_host_structure": (_int, [_i64, _i64, _i64, _int, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "apexgpu_debug_pair_lists": (_int, [_i64, _i64, _i64, _int] + _pairs),
+    "apexgpu_debug_pair_lists_queued": (_int, [_i64, _i64, _i64] + _pairs + [_vp]),
+    "apexgpu_debug_pair_lists_queued_dc": (_int, [_i64, _i64, _i64, _int] + _pairs + [_vp]),
+    "apexgpu_export_step": (_int, [_vp, _vp, _vp]),
+    "apexgpu_shard_range": (_int, [_i64, _i64, _vp, _int, _int, _P(_i64), _P(_i64)]),
+    "apexgpu_bal_open": (_int, [_str, _P(_vp)]),
+    "apexgpu_bal_close": (None, [_vp]),
+    "apexgpu_bal_last_error": (_str, []),
+    "apexgpu_bal_sizes": (_int, [_vp, _P(_i64), _P(_i64), _P(_i64)]),
+    "apexgpu_bal_raw": (_int, [_vp] * 6),
+    "apexgpu_bal_variables": (_int, [_vp, _vp, _vp]),
+    "apexgpu_reference_columns": (_int, [_i64, _i64, _vp, _vp, _vp]),
+    # pose graphs: SE3, SE2, SO3 on one handle
+    "apexgpu_pg_create": (_int, [_i64, _i64, _int, _P(_vp)]),
+    "apexgpu_pg_create_se2": (_int, [_i64, _i64, _int, _P(_vp)]),
+    "apexgpu_pg_create_so3": (_int, [_i64, _i64, _int, _P(_vp)]),
+    "apexgpu_pg_manifold": (_int, [_vp, _P(_int * 3)]),
+    "apexgpu_pg_destroy": (None, [_vp]),
+    "apexgpu_pg_last_error": (_str, [_vp]),
+    "apexgpu_pg_set_structure": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _dbl]),
+    "apexgpu_pg_set_priors": (_int, [_vp, _i64, _vp, _vp, _vp]),
+    "apexgpu_pg_get_prior_residual": (_int, [_vp, _vp]),
+    "apexgpu_pg_set_loss": (_int, [_vp, _int, _dbl, _dbl]),
+    "apexgpu_pg_get_loss": (_int, [_vp, _P(_int), _P(_dbl * 2)]),
+    "apexgpu_pg_set_information": (_int, [_vp, _vp]),
+    "apexgpu_pg_get_information": (_int, [_vp, _P(_int), _vp]),
+    "apexgpu_loss_evaluate": (_int, [_int, _dbl, _dbl, _dbl, _P(_dbl * 6)]),
+    "apexgpu_pg_set_params": (_int, [_vp, _vp]),
+    "apexgpu_pg_get_params": (_int, [_vp, _vp]),
+    "apexgpu_pg_cost": (_int, [_vp, _P(_dbl)]),
+    "apexgpu_pg_solve_augmented": (_int, [_vp, _dbl, _vp, _vp]),
+    "apexgpu_pg_step_stats": (_int, [_vp, _P(_dbl * 3)]),
+    "apexgpu_pg_eval_step": (_int, [_vp, _P(_dbl)]),
+    "apexgpu_pg_commit_step": (_int, [_vp]),
+    "apexgpu_pg_discard_step": (_int, [_vp]),
+    "apexgpu_pg_parameter_norm": (_int, [_vp, _P(_dbl)]),
+    "apexgpu_pg_column_norms": (_int, [_vp, _vp]),
+    "apexgpu_pg_set_column_scaling": (_int, [_vp, _vp]),
+    "apexgpu_pg_lm_optimize": (_int, [_vp, _P(LmConfigC)] + _opt),
+    "apexgpu_pg_jv_gram": (_int, [_vp, _vp, _vp, _P(_dbl * 3)]),
+    "apexgpu_pg_dogleg_step": (_int, [_vp, _dbl, _dbl, _int, _P(_dbl * 8)]),
+    "apexgpu_pg_gn_optimize": (_int, [_vp, _P(GnConfigC)] + _opt),
+    "apexgpu_pg_dogleg_optimize": (_int, [_vp, _P(DlConfigC)] + _opt),
+    "apexgpu_jv_gram": (_int, [_vp, _vp, _vp, _P(_dbl * 3)]),
+    "apexgpu_dogleg_step": (_int, [_vp, _dbl, _dbl, _int, _P(_dbl * 8)]),
+    "apexgpu_dogleg_optimize": (_int, [_vp, _P(DlConfigC)] + _opt),
+    "apexgpu_pg_get_residual": (_int, [_vp, _vp]),
+    "apexgpu_pg_get_jacobian_blocks": (_int, [_vp, _vp]),
+    "apexgpu_pg_get_hessian": (_int, [_vp, _dbl, _vp, _vp]),
+    "apexgpu_pg_covariance": (_int, [_vp, _vp]),
+    "apexgpu_pg_covariance_stats": (_int, [_vp, _P(_dbl * 6), _vp, _int]),
+    "apexgpu_pg_set_option": (_int, [_vp, _str, _int]),
+    "apexgpu_pg_enable_stage_timing": (_int, [_vp, _int]),
+    "apexgpu_pg_reset_stage_times": (_int, [_vp]),
+    "apexgpu_pg_stage_times": (_int, [_vp, _P(_dbl * PG_NUM_STAGES), _P(_i64 * PG_NUM_STAGES)]),
+    "apexgpu_pg_info": (_int, [_vp, _P(_dbl * 8)]),
+    "apexgpu_pg_counters": (_int, [_vp, _P(_i64 * 4)]),
+    "apexgpu_g2o_open": (_int, [_str, _P(_vp)]),
+    "apexgpu_g2o_close": (None, [_vp]),
+    "apexgpu_g2o_last_error": (_str, []),
+    "apexgpu_g2o_sizes": (_int, [_vp] + [_P(_i64)] * 4),
+    "apexgpu_g2o_raw": (_int, [_vp] * 7),
+    "apexgpu_g2o_problem": (_int, [_vp] * 8),
+    "apexgpu_pose_graph_columns": (_int, [_i64, _vp, _vp]),
+    "apexgpu_g2o_raw_se2": (_int, [_vp] * 7),
+    "apexgpu_g2o_problem_se2": (_int, [_vp] * 8),
+    "apexgpu_pose_graph_columns_se2": (_int, [_i64, _vp, _vp]),
+    "apexgpu_g2o_problem_information": (_int, [_vp, _int, _vp]),
+}
+SYMBOLS = tuple(API)
+
 _lib = None
 
 
@@ -147,154 +252,9 @@ def load() -> C.CDLL:
             " There is no CPU fallback."
         )
     L = C.CDLL(LIB_PATH)
-    vp, i64, dbl = C.c_void_p, C.c_int64, C.c_double
-    L.apexgpu_create.argtypes = [i64, i64, i64, C.c_int, C.c_int, C.POINTER(vp)]
-    L.apexgpu_destroy.argtypes = [vp]
-    L.apexgpu_destroy.restype = None
-    L.apexgpu_last_error.argtypes = [vp]
-    L.apexgpu_last_error.restype = C.c_char_p
-    L.apexgpu_version.restype = C.c_char_p
-    L.apexgpu_set_structure.argtypes = [vp] + [vp] * 9 + [dbl]
-    L.apexgpu_set_cg_params.argtypes = [vp, C.c_int, dbl]
-    L.apexgpu_set_params.argtypes = [vp, vp, vp, vp]
-    L.apexgpu_get_params.argtypes = [vp, vp, vp, vp]
-    L.apexgpu_cost.argtypes = [vp, C.POINTER(dbl)]
-    L.apexgpu_assemble.argtypes = [vp, dbl]
-    L.apexgpu_solve_augmented.argtypes = [vp, dbl, C.c_int, vp, vp]
-    L.apexgpu_step_stats.argtypes = [vp, C.POINTER(dbl * 3)]
-    L.apexgpu_eval_step.argtypes = [vp, C.POINTER(dbl)]
-    L.apexgpu_commit_step.argtypes = [vp]
-    L.apexgpu_discard_step.argtypes = [vp]
-    L.apexgpu_parameter_norm.argtypes = [vp, C.POINTER(dbl)]
-    L.apexgpu_column_norms.argtypes = [vp, vp]
-    L.apexgpu_debug_lockstep_solve.argtypes = [vp, C.c_int, C.c_double]
-    L.apexgpu_export_step.argtypes = [vp, vp, vp]
-    L.apexgpu_owned_landmarks.argtypes = [vp, vp]
-    L.apexgpu_debug_partition.argtypes = [C.c_int, vp, C.c_int, vp]
-    L.apexgpu_debug_check_schedule.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_char_p, C.c_int]
-    L.apexgpu_debug_schedule_ops.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int]
-    L.apexgpu_debug_plan_lists.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int]
-    L.apexgpu_debug_sinv_lists.argtypes = [C.c_int, vp, vp, C.c_int, vp, vp]
-    L.apexgpu_debug_sinv_lists_direct.argtypes = [C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_char_p, C.c_int]
-    L.apexgpu_debug_tiles_create.argtypes = [C.c_int, C.c_int, vp, vp, C.POINTER(vp)]
-    L.apexgpu_debug_tiles_pattern.argtypes = [vp, vp, vp]
-    L.apexgpu_debug_tiles_set.argtypes = [vp, vp, C.c_int, dbl, C.c_int]
-    L.apexgpu_debug_tiles_factor.argtypes = [vp, C.POINTER(C.c_int)]
-    L.apexgpu_debug_tiles_solve.argtypes = [vp, C.c_int, vp, vp]
-    L.apexgpu_debug_tiles_matvec.argtypes = [vp, vp, vp]
-    L.apexgpu_debug_tiles_pcg.argtypes = [vp, vp, C.c_int, dbl, vp, C.POINTER(C.c_int), vp]
-    L.apexgpu_debug_tiles_get.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int)]
-    L.apexgpu_debug_tiles_destroy.argtypes = [vp]
-    L.apexgpu_debug_tiles_destroy.restype = None
-    L.apexgpu_set_column_scaling.argtypes = [vp, vp]
-    L.apexgpu_lm_optimize.argtypes = [vp, C.POINTER(LmConfigC), C.POINTER(LmResultC), vp, C.c_int]
-    L.apexgpu_get_residual.argtypes = [vp, vp]
-    L.apexgpu_get_jacobian_blocks.argtypes = [vp, vp, vp]
-    L.apexgpu_get_schur.argtypes = [vp, vp, vp]
-    L.apexgpu_camera_covariance.argtypes = [vp, vp]
-    L.apexgpu_covariance_stats.argtypes = [vp, C.POINTER(dbl * 6), vp, C.c_int]
-    L.apexgpu_landmark_covariance.argtypes = [vp, vp]
-    L.apexgpu_landmark_covariance_stats.argtypes = [vp, C.POINTER(dbl * 4)]
-    L.apexgpu_get_landmark_blocks.argtypes = [vp, vp, vp]
-    L.apexgpu_schur_matvec.argtypes = [vp, dbl, vp, vp, vp]
-    L.apexgpu_set_option.argtypes = [vp, C.c_char_p, C.c_int]
-    L.apexgpu_get_hessian_csc.argtypes = [vp, vp, vp, vp, vp]
-    L.apexgpu_debug_invert_blocks.argtypes = [C.c_int, C.c_int64, vp, vp, vp]
-    L.apexgpu_debug_host_structure.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-    L.apexgpu_setup_times.argtypes = [vp, vp, vp]
-    L.apexgpu_debug_pair_lists.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.apexgpu_debug_pair_lists_queued.argtypes = [C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.apexgpu_enable_stage_timing.argtypes = [vp, C.c_int]
-    L.apexgpu_reset_stage_times.argtypes = [vp]
-    L.apexgpu_stage_times.argtypes = [vp, C.POINTER(dbl * NUM_STAGES), C.POINTER(i64 * NUM_STAGES)]
-    L.apexgpu_info.argtypes = [vp, C.POINTER(dbl * 16)]
-    L.apexgpu_trim_host_cache.argtypes = [C.POINTER(C.c_int64)]
-    L.apexgpu_host_cache_bytes.argtypes = []
-    L.apexgpu_host_cache_bytes.restype = C.c_int64
-    L.apexgpu_debug_get_pair_records.argtypes = [vp, vp, i64]
-    L.apexgpu_variant_info.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int]
-    L.apexgpu_variant_costs.argtypes = [vp, C.POINTER(dbl * 4)]
-    L.apexgpu_counters.argtypes = [vp, C.POINTER(i64 * 4)]
-    L.apexgpu_get_unique_id.argtypes = [vp]
-    L.apexgpu_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
-    L.apexgpu_comm_init_shm.argtypes = [vp, C.c_int, C.c_int, C.c_char_p]
-    L.apexgpu_set_shard.argtypes = [vp, C.c_int, C.c_int]
-    L.apexgpu_shard_range.argtypes = [i64, i64, vp, C.c_int, C.c_int, C.POINTER(i64), C.POINTER(i64)]
-    L.apexgpu_bal_open.argtypes = [C.c_char_p, C.POINTER(vp)]
-    L.apexgpu_bal_close.argtypes = [vp]
-    L.apexgpu_bal_close.restype = None
-    L.apexgpu_bal_last_error.restype = C.c_char_p
-    L.apexgpu_bal_sizes.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-    L.apexgpu_bal_raw.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.apexgpu_bal_variables.argtypes = [vp, vp, vp]
-    L.apexgpu_reference_columns.argtypes = [i64, i64, vp, vp, vp]
-    L.apexgpu_pg_create.argtypes = [i64, i64, C.c_int, C.POINTER(vp)]
-    L.apexgpu_pg_destroy.argtypes = [vp]
-    L.apexgpu_pg_destroy.restype = None
-    L.apexgpu_pg_last_error.argtypes = [vp]
-    L.apexgpu_pg_last_error.restype = C.c_char_p
-    L.apexgpu_pg_set_structure.argtypes = [vp, vp, vp, vp, vp, vp, dbl]
-    L.apexgpu_pg_set_params.argtypes = [vp, vp]
-    L.apexgpu_pg_set_priors.argtypes = [vp, C.c_int64, vp, vp, vp]
-    L.apexgpu_pg_get_prior_residual.argtypes = [vp, vp]
-    L.apexgpu_pg_set_loss.argtypes = [vp, C.c_int, dbl, dbl]
-    L.apexgpu_set_loss.argtypes = [vp, C.c_int, dbl, dbl]
-    L.apexgpu_set_pose_priors.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
-    L.apexgpu_set_intrinsic_priors.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
-    L.apexgpu_get_prior_residual.argtypes = [vp, vp, vp]
-    L.apexgpu_get_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(dbl * 2)]
-    L.apexgpu_pg_get_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(dbl * 2)]
-    L.apexgpu_loss_evaluate.argtypes = [C.c_int, dbl, dbl, dbl, C.POINTER(dbl * 6)]
-    L.apexgpu_pg_get_params.argtypes = [vp, vp]
-    L.apexgpu_pg_cost.argtypes = [vp, C.POINTER(dbl)]
-    L.apexgpu_pg_solve_augmented.argtypes = [vp, dbl, vp, vp]
-    L.apexgpu_pg_step_stats.argtypes = [vp, C.POINTER(dbl * 3)]
-    L.apexgpu_pg_eval_step.argtypes = [vp, C.POINTER(dbl)]
-    L.apexgpu_pg_commit_step.argtypes = [vp]
-    L.apexgpu_pg_discard_step.argtypes = [vp]
-    L.apexgpu_pg_parameter_norm.argtypes = [vp, C.POINTER(dbl)]
-    L.apexgpu_pg_column_norms.argtypes = [vp, vp]
-    L.apexgpu_pg_set_column_scaling.argtypes = [vp, vp]
-    L.apexgpu_pg_lm_optimize.argtypes = [vp, C.POINTER(LmConfigC), C.POINTER(LmResultC), vp, C.c_int]
-    L.apexgpu_jv_gram.argtypes = [vp, vp, vp, C.POINTER(dbl * 3)]
-    L.apexgpu_dogleg_step.argtypes = [vp, dbl, dbl, C.c_int, C.POINTER(dbl * 8)]
-    L.apexgpu_dogleg_optimize.argtypes = [vp, C.POINTER(DlConfigC), C.POINTER(LmResultC), vp, C.c_int]
-    L.apexgpu_pg_jv_gram.argtypes = [vp, vp, vp, C.POINTER(dbl * 3)]
-    L.apexgpu_pg_dogleg_step.argtypes = [vp, dbl, dbl, C.c_int, C.POINTER(dbl * 8)]
-    L.apexgpu_pg_gn_optimize.argtypes = [vp, C.POINTER(GnConfigC), C.POINTER(LmResultC), vp, C.c_int]
-    L.apexgpu_pg_dogleg_optimize.argtypes = [vp, C.POINTER(DlConfigC), C.POINTER(LmResultC), vp, C.c_int]
-    L.apexgpu_pg_get_residual.argtypes = [vp, vp]
-    L.apexgpu_pg_get_jacobian_blocks.argtypes = [vp, vp]
-    L.apexgpu_pg_get_hessian.argtypes = [vp, dbl, vp, vp]
-    L.apexgpu_pg_covariance.argtypes = [vp, vp]
-    L.apexgpu_pg_covariance_stats.argtypes = [vp, C.POINTER(dbl * 6), vp, C.c_int]
-    L.apexgpu_pg_set_option.argtypes = [vp, C.c_char_p, C.c_int]
-    L.apexgpu_pg_enable_stage_timing.argtypes = [vp, C.c_int]
-    L.apexgpu_pg_reset_stage_times.argtypes = [vp]
-    L.apexgpu_pg_stage_times.argtypes = [vp, C.POINTER(dbl * PG_NUM_STAGES), C.POINTER(i64 * PG_NUM_STAGES)]
-    L.apexgpu_pg_info.argtypes = [vp, C.POINTER(dbl * 8)]
-    L.apexgpu_pg_counters.argtypes = [vp, C.POINTER(i64 * 4)]
-    L.apexgpu_g2o_open.argtypes = [C.c_char_p, C.POINTER(vp)]
-    L.apexgpu_g2o_close.argtypes = [vp]
-    L.apexgpu_g2o_close.restype = None
-    L.apexgpu_g2o_last_error.restype = C.c_char_p
-    L.apexgpu_g2o_sizes.argtypes = [vp] + [C.POINTER(i64)] * 4
-    L.apexgpu_g2o_raw.argtypes = [vp] * 7
-    L.apexgpu_g2o_problem.argtypes = [vp] * 8
-    L.apexgpu_pose_graph_columns.argtypes = [i64, vp, vp]
-    L.apexgpu_pg_create_se2.argtypes = [i64, i64, C.c_int, C.POINTER(vp)]
-    L.apexgpu_pg_create_so3.argtypes = [i64, i64, C.c_int, C.POINTER(vp)]
-    L.apexgpu_pg_manifold.argtypes = [vp, C.POINTER(C.c_int * 3)]
-    L.apexgpu_g2o_raw_se2.argtypes = [vp] * 7
-    L.apexgpu_g2o_problem_se2.argtypes = [vp] * 8
-    L.apexgpu_g2o_problem_information.argtypes = [vp, C.c_int, vp]
-    L.apexgpu_pg_set_information.argtypes = [vp, vp]
-    L.apexgpu_pg_get_information.argtypes = [vp, C.POINTER(C.c_int), vp]
-    L.apexgpu_pose_graph_columns_se2.argtypes = [i64, vp, vp]
-    for name in SYMBOLS:
+    for name, (restype, argtypes) in API.items():
         f = getattr(L, name)
-        if name not in _NON_INT:
-            f.restype = C.c_int
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 

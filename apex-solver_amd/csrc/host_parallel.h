@@ -60,7 +60,7 @@ class HostPool {
     // run job(worker) on `use` workers (including the caller) and wait.  Exception-safe: a throw in ANY participant
     // (the bodies allocate: std::bad_alloc) is caught where it happens, the first one is kept, every worker is still
     // waited for -- `job` and the caller's loop state live on this stack frame -- and the exception is rethrown on the
-    // calling thread, where capi.cpp's guarded() turns it into a status code.  Nothing ever escapes a worker thread
+    // calling thread, where guarded() (capi_guard.h) turns it into a status code.  Nothing ever escapes a worker thread
     // (that would be std::terminate in the host process).
     template <typename J>
     void run(unsigned use, J&& job) {

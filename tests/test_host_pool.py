@@ -1,4 +1,4 @@
-"""apex-solver_amd/csrc/host_parallel.h on the CPU: the C ABI promises that no C++ exception crosses it (capi.cpp,
+"""apex-solver_amd/csrc/host_parallel.h on the CPU: the C ABI promises that no C++ exception crosses it (capi_guard.h,
 guarded()); set_structure runs its list construction on HostPool, so a throw inside a pooled loop body must come back on
 the CALLING thread with the pool intact (round-2 advisor finding: it used to reach std::terminate in a worker)."""
 import ctypes as C
