@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "landmark_cov_lists.h"
 #include "pg_loss.hpp"
 #include "tile_tasks.h"   // kNB
 
@@ -127,8 +128,7 @@ void launch_debug_invert_blocks(int64_t n, const double* in, double* out, int* o
 // Marginal landmark covariances (cov_kernels.hip): out[l][3][3] (internal landmark order) from the landmark records, the cameras
 // of the factorised parameter set (v) and the selected inverse z of S.  small_list: landmarks with at most kLcSmallK observations
 // (8 lanes each), large_list: the others (a 64-lane workgroup each, chunks of kLcChunk observations).  err[0] := 1 if a
-// camera pair fell outside z's tile pattern.
-constexpr int kLcSmallK = 8, kLcChunk = 32;
+// camera pair fell outside z's tile pattern.  (kLcSmallK, kLcChunk: landmark_cov_lists.h, where the host builds the two lists)
 void launch_landmark_cov(int dc, const BAView& v, const double* hinv, const TileMap& z, const int* small_list, int n_small,
                          const int* large_list, int n_large, double* out, int* err, hipStream_t s, const PgLoss* loss = nullptr);
 void launch_export_linearization(int dc, const BAView& v, const int* o_orig, double* r_out, double* jc_out,

@@ -8,11 +8,9 @@
 #include <stdint.h>
 
 #include "ba_kernels.h"
+#include "prior_lists.h"   // kPosePriorStride, kIntrPriorStride: the block layouts, where the host packs them
 
 namespace apex {
-
-constexpr int kPosePriorStride = 10;   // doubles per pose block: data [t, qw qx qy qz] (7) | Huber delta (<= 0: none) | w | pad
-constexpr int kIntrPriorStride = 6;    // doubles per intrinsics block: data [f, k1, k2] (3) | Huber delta | w | pad
 
 // Both sets as the device holds them: sorted by internal camera (stable), with a CSR over the cameras.  An empty set: n = 0.
 struct BaPriorView {

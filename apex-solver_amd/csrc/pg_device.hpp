@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "ba_device.hpp"
+#include "info_pack.h"
 #include "pg_loss.hpp"
 
 namespace apex {
@@ -308,12 +309,7 @@ APEX_HD bool between_linearize_general(const double* __restrict__ k0, const doub
 // PGView::info; no loss, L2 and Huber run through it too (as a PgLoss of that kind) when information is set.
 struct LossWeighted { using Param = PgLoss; static constexpr bool kGeneral = true; };
 
-// Omega travels packed: the upper triangle row-major, D (D + 1) / 2 doubles padded to an even count (16-byte loads)
-template <int D>
-struct InfoPack {
-    static constexpr int kPacked = D * (D + 1) / 2;
-    static constexpr int kStride = (kPacked + 1) & ~1;   // 22 | 6
-};
+// Omega travels packed (InfoPack<D>, info_pack.h: the layout, beside the host code that checks and packs the matrices)
 template <int D>
 APEX_HD void info_unpack(const double* __restrict__ p, double* __restrict__ W) {   // -> full, row-major
     int k = 0;

@@ -110,6 +110,7 @@ class PoseGraphSolver : public TileBackend {
     // scal_: [1..3] the step's sums, [4] the trial point's sum of squares -- read here only
     double* step_sums(int* n) override { *n = 3; return scal_ + 1; }
     StepAnswers answers_from_sums(const double* h) const override { return {sqrt(h[0]), sqrt(h[1]), 0.5 * h[2], h[3]}; }
+    void voided_by(Change why);   // the one place a setter's change voids cached state (pg_solver.hip)
     int assemble(double lambda);
     int solve_damped(double lambda, double* step_out, double* grad_out);   // solve_augmented behind its checks; the fresh Dog-Leg solve
     // the Dog-Leg hooks (tile_backend.h)

@@ -5,12 +5,13 @@
 #include <string.h>
 
 #include <algorithm>
-#include <numeric>
 
+#include "info_pack.h"
 #include "pg2_device.hpp"
 #include "pg2_lists.h"
 #include "pg_device.hpp"
 #include "pg_so3_device.hpp"
+#include "prior_lists.h"
 
 namespace apex {
 
@@ -71,46 +72,52 @@ int PoseGraphSolver::enqueue_retract(int from, double sign, int to) {
     return kOk;
 }
 
+// What a change voids ("What a change voids"): on a pose graph every setter drops the pending step and the Dog-Leg
+// cache, nothing else.  The factor stays valid through all of them: covariance() is by contract of the matrix the LAST solve
+// factorised, whatever was set since (pg_solver.h); the next assembly writes the tiles and voids it there.
+void PoseGraphSolver::voided_by(Change why) {
+    switch (why) {
+        case Change::kStructure:     // (the vectors and the tiles are new)
+        case Change::kParams:        // (the current set is overwritten under the step)
+        case Change::kLoss:          // (the step and the cached gradient are of the system under the old loss,
+        case Change::kPriors:        //  ... without these rows,
+        case Change::kInformation:   //  ... under the old whitening)
+            st_.invalidate();        // the trial point too: its cost was taken under the old factors
+            drop_dogleg_cache();
+            break;
+        case Change::kScalingOff:
+        case Change::kScalingVectors:   // the step is of the system under the old scaling; a trial point already written stays committable
+            st_.invalidate_step();
+            drop_dogleg_cache();       // (the cache holds for the scaling it was taken under)
+            break;
+    }
+}
+
 // PriorFactor blocks (prior_factor.rs:96-108); replaces the set.  data7 in to_vector order [t, w, i, j, k].
 int PoseGraphSolver::set_priors(int64_t n, const uint32_t* vertex, const double* data7, const double* huber_delta) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
-    if (n < 0 || n > (1 << 24)) return fail(kInvalidInput, "prior count out of range");
-    for (int64_t k = 0; k < n; ++k)
-        if ((int64_t)vertex[k] >= n_v_) return fail(kInvalidInput, "prior on a vertex that does not exist");
+    if (!prior_count_in_range(n)) return fail(kInvalidInput, "prior count out of range");
+    { const std::string why = pg_prior_refusal(n, vertex, n_v_); if (!why.empty()) return fail(kInvalidInput, why); }
+    // Row-owned handles: the blocks go to the device sorted by vertex (stable), so that one lane sums the run of a vertex in a
+    // fixed order (k_pg2_priors); prior_slot_ keeps the caller's index for the export.  SE3 with atomics: the caller's order, as ever.
+    const PriorLists pl = build_prior_lists(n, vertex, vmap_, {amb_, prior_stride_, false}, data7, huber_delta, nullptr, row_owned_, 0);
     HIP_TRY(hipSetDevice(device_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    st_.invalidate();
-    drop_dogleg_cache();
+    voided_by(Change::kPriors);   // (ahead of the uploads: a call whose upload fails has voided the step all the same)
     // The new set goes up into locals and replaces the members (and n_prior_) only when every upload has succeeded: a failed
     // call leaves the old priors fully in place, a call with n = 0 none at all.
     DeviceBuffer<uint32_t> new_v;
     DeviceBuffer<double> new_data;
     DeviceBuffer<int> new_slot;
-    auto install = [&] {
-        prior_v_ = std::move(new_v); prior_data_ = std::move(new_data); prior_slot_ = std::move(new_slot);
-        prior_res_.reset();   // (sized by the old count: get_prior_residual allocates it again)
-        n_prior_ = (int)n;
-        return kOk;
-    };
-    if (n == 0) return install();
-    std::vector<uint32_t> hv((size_t)n);
-    std::vector<double> hd((size_t)n * prior_stride_, 0.0);
-    // Row-owned handles: the blocks go to the device sorted by vertex (stable), so that one lane sums the run of a vertex in a
-    // fixed order (k_pg2_priors); prior_slot_ keeps the caller's index for the export.  SE3 with atomics: the caller's order, as ever.
-    std::vector<int> order((size_t)n);
-    std::iota(order.begin(), order.end(), 0);
-    if (row_owned_)
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return vmap_[vertex[a]] < vmap_[vertex[b]]; });
-    for (int64_t k = 0; k < n; ++k) {
-        const int src = order[k];
-        hv[k] = (uint32_t)vmap_[vertex[src]];
-        memcpy(hd.data() + (size_t)k * prior_stride_, data7 + (size_t)amb_ * src, amb_ * sizeof(double));
-        hd[(size_t)k * prior_stride_ + amb_] = huber_delta ? huber_delta[src] : -1.0;
+    if (n > 0) {
+        if (row_owned_) HIP_TRY(new_slot.upload(pl.slot));
+        HIP_TRY(new_v.upload(pl.owner));
+        HIP_TRY(new_data.upload(pl.data));
     }
-    if (row_owned_) HIP_TRY(new_slot.upload(order));
-    HIP_TRY(new_v.upload(hv));
-    HIP_TRY(new_data.upload(hd));
-    return install();
+    prior_v_ = std::move(new_v); prior_data_ = std::move(new_data); prior_slot_ = std::move(new_slot);
+    prior_res_.reset();   // (sized by the old count: get_prior_residual allocates it again)
+    n_prior_ = (int)n;
+    return kOk;
 }
 
 int PoseGraphSolver::set_loss(int kind, double p0, double p1) {
@@ -119,69 +126,31 @@ int PoseGraphSolver::set_loss(int kind, double p0, double p1) {
     if (!pg_loss_make(kind, p0, p1, &l)) return fail(kInvalidInput, "set_loss: unknown loss kind or a parameter its constructor refuses");
     HIP_TRY(hipSetDevice(device_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    st_.invalidate();
-    drop_dogleg_cache();
     loss_ = l;
     loss_set_ = true;
+    voided_by(Change::kLoss);
     return kOk;
 }
 
 int PoseGraphSolver::set_information(const double* info) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
-    const int D = dof_, S = (D * (D + 1) / 2 + 1) & ~1;
     std::vector<double> packed;
-    if (info) {
-        packed.assign((size_t)n_e_ * S, 0.0);
-        for (int64_t e = 0; e < n_e_; ++e) {
-            const double* W = info + (size_t)e * D * D;
-            const std::string who = "set_information: edge " + std::to_string(e);
-            double big = 0.0;
-            for (int i = 0; i < D * D; ++i) {
-                if (!std::isfinite(W[i])) return fail(kInvalidInput, who + " has an entry that is not finite");
-                big = std::max(big, fabs(W[i]));
-            }
-            for (int i = 0; i < D; ++i)
-                for (int j = i + 1; j < D; ++j)
-                    if (fabs(W[D * i + j] - W[D * j + i]) > 1e-12 * big) return fail(kInvalidInput, who + " is not symmetric");
-            double U[36];   // Omega = U^T U from the upper triangle
-            for (int i = 0; i < D; ++i)
-                for (int j = i; j < D; ++j) {
-                    double acc = W[D * i + j];
-                    for (int k = 0; k < i; ++k) acc -= U[D * k + i] * U[D * k + j];
-                    if (i == j) {
-                        if (!(acc > 0.0)) return fail(kInvalidInput, who + " is not positive definite (Cholesky pivot " + std::to_string(i) + " <= 0)");
-                        U[D * i + i] = sqrt(acc);
-                    } else {
-                        U[D * i + j] = acc / U[D * i + i];
-                    }
-                }
-            double* p = packed.data() + (size_t)e * S;
-            for (int i = 0; i < D; ++i)
-                for (int j = i; j < D; ++j) *p++ = W[D * i + j];
-        }
-    }
+    std::string why;
+    if (info && !info_validate_and_pack(dof_, n_e_, info, &packed, &why)) return fail(kInvalidInput, why);
     HIP_TRY(hipSetDevice(device_));
     HIP_TRY(hipStreamSynchronize(stream_));
     DeviceBuffer<double> fresh;   // the members change only when the upload has succeeded
     if (info && n_e_ > 0) HIP_TRY(fresh.upload(packed));
-    st_.invalidate();
-    drop_dogleg_cache();
     info_ = std::move(fresh);
     info_host_ = std::move(packed);
+    voided_by(Change::kInformation);
     return kOk;
 }
 
 int PoseGraphSolver::get_information(int* present, double* info_out) const {
-    const int D = dof_, S = (D * (D + 1) / 2 + 1) & ~1;
     const bool have = !info_host_.empty();
     if (present) *present = have ? 1 : 0;
-    if (!have || !info_out) return kOk;
-    for (int64_t e = 0; e < n_e_; ++e) {
-        const double* p = info_host_.data() + (size_t)e * S;
-        double* W = info_out + (size_t)e * D * D;
-        for (int i = 0; i < D; ++i)
-            for (int j = i; j < D; ++j) { W[D * i + j] = *p; W[D * j + i] = *p; ++p; }
-    }
+    if (have && info_out) info_expand(dof_, n_e_, info_host_.data(), info_out);
     return kOk;
 }
 
@@ -288,8 +257,8 @@ int PoseGraphSolver::set_structure(const uint32_t* e_from, const uint32_t* e_to,
     HIP_TRY(scal_.alloc_zero(16));
     HIP_TRY(hipDeviceSynchronize());
     have_structure_ = true;
-    have_params_ = false; st_.invalidate();
-    drop_dogleg_cache();
+    have_params_ = false;
+    voided_by(Change::kStructure);
     release_dogleg_buffers();
     st_.cur = 0;
     return kOk;
@@ -305,8 +274,8 @@ int PoseGraphSolver::set_params(const double* poses7) {
     HIP_TRY(hipMemcpyAsync(poses_[st_.cur], hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
     launch_pg_prepare(manifold_, n_v_, poses_[st_.cur], posep_[st_.cur], stream_);
     HIP_TRY(hipStreamSynchronize(stream_));
-    have_params_ = true; st_.invalidate();
-    drop_dogleg_cache();
+    have_params_ = true;
+    voided_by(Change::kParams);
     return kOk;
 }
 
@@ -465,9 +434,8 @@ int PoseGraphSolver::column_norms(double* norms_out) {
 int PoseGraphSolver::set_column_scaling(const double* scaling) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built");
     HIP_TRY(hipSetDevice(device_));
-    st_.invalidate_step();
-    drop_dogleg_cache();
-    if (!scaling) { scaled_ = false; return kOk; }
+    if (!scaling) { scaled_ = false; voided_by(Change::kScalingOff); return kOk; }
+    voided_by(Change::kScalingVectors);   // (ahead of the checks: a refused vector has voided the step all the same)
     HIP_TRY(scale_.ensure());
     std::vector<double> staged;
     if (!scale_.accepts(map_, scaling, &staged)) return fail(kInvalidInput, JacobiScaling::kRefused);
@@ -478,7 +446,7 @@ int PoseGraphSolver::set_column_scaling(const double* scaling) {
 }
 
 int PoseGraphSolver::set_jacobi_scaling(bool on) {
-    if (!on) { scaled_ = false; st_.invalidate_step(); drop_dogleg_cache(); return kOk; }
+    if (!on) { scaled_ = false; voided_by(Change::kScalingOff); return kOk; }
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
     HIP_TRY(scale_.ensure());
@@ -488,7 +456,8 @@ int PoseGraphSolver::set_jacobi_scaling(bool on) {
     tp_.diag(work_);
     HIP_TRY(scale_.from_norms_sq(work_, n_, stream_));  // the padding keeps its 1
     HIP_TRY(hipStreamSynchronize(stream_));
-    scaled_ = true; st_.invalidate_step();
+    scaled_ = true;
+    voided_by(Change::kScalingVectors);   // (the assembly above has dropped the Dog-Leg cache already)
     return kOk;
 }
 

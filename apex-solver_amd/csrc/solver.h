@@ -110,7 +110,7 @@ class Solver : public TileBackend {
     int landmark_covariance(double* out);
     // [0] device bytes of the landmark pass, [1] observation pairs sum k (k + 1) / 2, [2] 1 if the last call recomputed Z,
     // [3] ms of the landmark kernels alone in the last call ("covariance_timing" on, else 0)
-    void landmark_covariance_stats(double out[4]) const { out[0] = (double)lc_bytes_; out[1] = (double)lc_pairs_; out[2] = lc_recomputed_ ? 1.0 : 0.0; out[3] = lc_ms_; }
+    void landmark_covariance_stats(double out[4]) const { out[0] = (double)lc_.bytes; out[1] = (double)lc_.pairs; out[2] = lc_.recomputed ? 1.0 : 0.0; out[3] = lc_.ms; }
     int get_landmark_blocks(double* hinv_out, double* gl_out);
     // H = J^T J of the corrected Jacobian at the current parameters as a full symmetric CSC matrix in the global column
     // order (what SparseSchurComplementSolver::get_hessian caches, explicit_schur.rs:1146-1160, 1236-1238).  Two-call
@@ -189,6 +189,7 @@ class Solver : public TileBackend {
     StepAnswers answers_from_sums(const double* h) const override { return {sqrt(h[0] + h[3]), sqrt(h[1] + h[4]), 0.5 * (h[2] + h[5]), h[6]}; }
     void params_moved() override { orec_fresh_ = false; }
     void retract_sets(int from, double sign, int to, int64_t n_pt);
+    void voided_by(Change why);   // the one place a setter's change voids cached state (solver.hip)
     BAView view(int which) const;
     TileMap tilemap() const;
     // for_factor: the result feeds tp_.factor() (a distributed plan then leaves the top tiles to the factorisation's
@@ -291,16 +292,19 @@ class Solver : public TileBackend {
     // scaling was on for it (the scale vectors are kept until new scaling overwrites them)
     int factor_lin_ = -1;
     bool factor_scaled_ = false;
-    // landmark covariance pass (landmark_covariance): built on the first call
+    // landmark covariance pass (landmark_covariance): built on the first call by lc_setup, released by set_structure
+    struct LandmarkCov {
+        DeviceBuffer<int> lists, err;   // [small | large] landmark lists (landmark_cov_lists.h), error word
+        DeviceBuffer<double> out;       // [n_pt][9], internal order
+        int n_small = 0, n_large = 0;
+        int64_t pairs = 0;
+        size_t bytes = 0;
+        bool recomputed = false;        // the last call recomputed Z
+        double ms = 0.0;                // ... and took this long in the landmark kernels ("covariance_timing" on, else 0)
+        void release();
+    };
     int lc_setup();
-    void lc_release();
-    DeviceBuffer<int> lc_lists_, lc_err_;   // [small | large] landmark lists, error word
-    DeviceBuffer<double> lc_out_;           // [n_pt][9], internal order
-    int lc_n_small_ = 0, lc_n_large_ = 0;
-    int64_t lc_pairs_ = 0;
-    size_t lc_bytes_ = 0;
-    bool lc_recomputed_ = false;
-    double lc_ms_ = 0.0;
+    LandmarkCov lc_;
     bool orec_fresh_ = false;   // orec_ holds the records of the current parameters' last linearisation
     const double* backsub_records() const { return orec_fresh_ ? orec_ : nullptr; }   // the projection records of THIS linearisation
     DeviceBuffer<double> orec_;   // [local observations][4] projection records written by k_landmark_reduce (pair kernel, record form)

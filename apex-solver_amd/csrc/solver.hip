@@ -2,6 +2,7 @@
 #include "solver.h"
 #include "ba_device.hpp"
 #include "ba_structure.h"
+#include "hessian_csc.h"
 
 #include <math.h>
 #include <string.h>
@@ -10,7 +11,6 @@
 #include <chrono>
 #include <functional>
 #include <future>
-#include <numeric>
 
 namespace apex {
 
@@ -485,7 +485,7 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
                           double huber_delta) {
     if (n_cam_ <= 0 || n_pt_ <= 0) return fail(kInvalidInput, n_cam_ <= 0 ? "No camera variables found" : "No landmark variables found");
     if (n_obs_ < 0 || n_obs_ > 2000000000LL) return fail(kInvalidInput, "observation count out of range");
-    lc_release();   // (the landmark covariance lists belong to the old structure)
+    lc_.release();   // (the landmark covariance lists belong to the old structure)
     pose_pri_ = PriorSet{}; intr_pri_ = PriorSet{};   // (and so do the priors: camera indices of the old problem)
     pri_diag_.reset(); pri_g_.reset(); pri_cost_.reset(); pri_res_.reset();
     Setup su;   // (its destructor releases and joins whatever thread is still out, on every return below)
@@ -569,11 +569,44 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     su.tr.mark("host lists handed to the free thread");
 
     have_structure_ = true;
-    have_params_ = false; st_.invalidate();
-    drop_dogleg_cache();
+    have_params_ = false;
+    voided_by(Change::kStructure);
     release_dogleg_buffers();
     st_.cur = 0;
     return kOk;
+}
+
+// What a change voids ("What a change voids"): the one place outside the solve path that touches the pending step,
+// the Dog-Leg cache, the projection records, the factor's linearisation point and the factor's validity.
+void Solver::voided_by(Change why) {
+    switch (why) {
+        case Change::kStructure:   // (the new plan holds no valid factor; set_params, which must follow, voids the rest)
+            st_.invalidate();
+            drop_dogleg_cache();
+            break;
+        case Change::kParams:      // the current set is overwritten: the factor's linearisation is no longer known
+        case Change::kLoss:        // the factor was linearised, and the records written, under the old loss
+            st_.invalidate();
+            orec_fresh_ = false;
+            drop_dogleg_cache();
+            factor_lin_ = -1;
+            break;
+        case Change::kPriors:      // (the projection records do not see the priors: they stay)
+            st_.invalidate();
+            drop_dogleg_cache();
+            tp_.set_factor_valid(false);   // the factor is of a system without these rows
+            factor_lin_ = -1;
+            break;
+        case Change::kInformation:   // (pose graphs only)
+            break;
+        case Change::kScalingVectors:
+            if (factor_scaled_) factor_lin_ = -1;   // the factor's scale vectors are overwritten
+            [[fallthrough]];
+        case Change::kScalingOff:    // the step is of the system under the old scaling; a trial point already written stays committable
+            st_.invalidate_step();
+            drop_dogleg_cache();
+            break;
+    }
 }
 
 int Solver::set_params(const double* poses, const double* intr, const double* points) {
@@ -594,9 +627,8 @@ int Solver::set_params(const double* poses, const double* intr, const double* po
     { const int rc = upload_staged(pts_[st_.cur], src_pts, 3 * (size_t)n_pt_ * sizeof(double)); if (rc != kOk) return rc; }
     launch_prepare_cams(n_cam_, poses_[st_.cur], intr_[st_.cur], camp_[st_.cur], mode_mask(mode_), stream_);
     HIP_TRY(hipStreamSynchronize(stream_));
-    have_params_ = true; st_.invalidate(); orec_fresh_ = false;
-    drop_dogleg_cache();
-    factor_lin_ = -1;   // (the current set is overwritten: the factor's linearisation is no longer known)
+    have_params_ = true;
+    voided_by(Change::kParams);
     return kOk;
 }
 
@@ -611,11 +643,9 @@ int Solver::set_loss(int kind, double p0, double p1) {
     }
     HIP_TRY(hipSetDevice(device_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    st_.invalidate(); orec_fresh_ = false;
-    drop_dogleg_cache();
-    factor_lin_ = -1;   // (the factor was linearised under the old loss)
     loss_ = l;
     loss_set_ = true;
+    voided_by(Change::kLoss);
     return kOk;
 }
 
@@ -631,46 +661,26 @@ void Solver::get_loss(int* kind, double out2[2]) const {
 // PriorFactor blocks on the cameras
 // ---------------------------------------------------------------------------------------------
 int Solver::set_priors(bool intr, int64_t n, const uint32_t* cam, const double* data, const double* huber_delta, const double* weight) {
-    const char* what = intr ? "set_intrinsic_priors" : "set_pose_priors";
+    const std::string what = intr ? "set_intrinsic_priors" : "set_pose_priors";
     if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
-    if (world_ > 1 || tp_.distributed()) return fail(kInvalidState, std::string(what) + ": camera priors are single-rank only (this handle is sharded)");
-    if (n < 0 || n > (1 << 24)) return fail(kInvalidInput, std::string(what) + ": prior count out of range");
-    if (n > 0 && (!cam || !data)) return fail(kInvalidInput, std::string(what) + ": cam / data are NULL");
+    if (world_ > 1 || tp_.distributed()) return fail(kInvalidState, what + ": camera priors are single-rank only (this handle is sharded)");
+    if (!prior_count_in_range(n)) return fail(kInvalidInput, what + ": prior count out of range");
+    if (n > 0 && (!cam || !data)) return fail(kInvalidInput, what + ": cam / data are NULL");
     if (intr && n > 0 && dc_ != 9)
         return fail(kInvalidInput, "set_intrinsic_priors: this handle optimises six columns per camera; the intrinsics have no columns on the device");
-    const int amb = intr ? 3 : 7, stride = intr ? kIntrPriorStride : kPosePriorStride;
-    for (int64_t k = 0; k < n; ++k) {
-        if ((int64_t)cam[k] >= n_cam_) return fail(kInvalidInput, std::string(what) + ": prior " + std::to_string(k) + " is on a camera that does not exist");
-        for (int a = 0; a < amb; ++a)
-            if (std::isnan(data[amb * k + a])) return fail(kInvalidInput, std::string(what) + ": prior " + std::to_string(k) + " has NaN data");
-        if (huber_delta && std::isnan(huber_delta[k])) return fail(kInvalidInput, std::string(what) + ": prior " + std::to_string(k) + " has a NaN Huber delta");
-        if (weight && !(std::isfinite(weight[k]) && weight[k] > 0.0))
-            return fail(kInvalidInput, std::string(what) + ": the weight of prior " + std::to_string(k) + " must be finite and positive");
-    }
+    const PriorLayout lay = intr ? PriorLayout{3, kIntrPriorStride, true} : PriorLayout{7, kPosePriorStride, true};
+    { const std::string why = ba_prior_refusal(what, n, cam, n_cam_, lay.amb, data, huber_delta, weight); if (!why.empty()) return fail(kInvalidInput, why); }
     HIP_TRY(hipSetDevice(device_));
     HIP_TRY(hipStreamSynchronize(stream_));
     // The new set goes up into a local and replaces the member only when every upload has succeeded (as PoseGraphSolver::set_priors)
     PriorSet ns;
     if (n > 0) {
         // sorted by internal camera (stable): one lane sums a camera's run in the caller's order; slot keeps the caller's index
-        std::vector<int> order((size_t)n), hc((size_t)n), ptr((size_t)n_cam_ + 1, 0);
-        std::iota(order.begin(), order.end(), 0);
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cmap_[cam[a]] < cmap_[cam[b]]; });
-        std::vector<double> hd((size_t)n * stride, 0.0);
-        for (int64_t k = 0; k < n; ++k) {
-            const int src = order[k];
-            hc[k] = cmap_[cam[src]];
-            ptr[hc[k] + 1]++;
-            double* d = hd.data() + (size_t)k * stride;
-            memcpy(d, data + (size_t)amb * src, amb * sizeof(double));
-            d[amb] = huber_delta ? huber_delta[src] : -1.0;
-            d[amb + 1] = weight ? weight[src] : 1.0;
-        }
-        for (int64_t c = 0; c < n_cam_; ++c) ptr[c + 1] += ptr[c];
-        HIP_TRY(ns.ptr.upload(ptr));
-        HIP_TRY(ns.slot.upload(order));
-        HIP_TRY(ns.cam.upload(hc));
-        HIP_TRY(ns.data.upload(hd));
+        const PriorLists pl = build_prior_lists(n, cam, cmap_, lay, data, huber_delta, weight, true, n_cam_);
+        HIP_TRY(ns.ptr.upload(pl.ptr));
+        HIP_TRY(ns.slot.upload(pl.slot));
+        HIP_TRY(ns.cam.upload(pl.owner));
+        HIP_TRY(ns.data.upload(pl.data));
         ns.n = (int)n;
         if (!pri_diag_) {
             HIP_TRY(pri_diag_.alloc_zero(n_c_pad_));
@@ -681,10 +691,7 @@ int Solver::set_priors(bool intr, int64_t n, const uint32_t* cam, const double* 
     }
     (intr ? intr_pri_ : pose_pri_) = std::move(ns);
     pri_res_.reset();   // (sized by the old counts)
-    st_.invalidate();
-    drop_dogleg_cache();
-    tp_.set_factor_valid(false);   // (the factor is of a system without these rows)
-    factor_lin_ = -1;
+    voided_by(Change::kPriors);
     return kOk;
 }
 
@@ -1260,10 +1267,8 @@ int Solver::column_norms(double* norms_out) {
 int Solver::set_column_scaling(const double* scaling) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built");
     HIP_TRY(hipSetDevice(device_));
-    st_.invalidate_step();
-    drop_dogleg_cache();
-    if (!scaling) { scaled_ = false; return kOk; }
-    if (factor_scaled_) factor_lin_ = -1;   // (the factor's scale vectors are overwritten below)
+    if (!scaling) { scaled_ = false; voided_by(Change::kScalingOff); return kOk; }
+    voided_by(Change::kScalingVectors);   // (ahead of the checks: a refused vector has voided the step all the same)
     HIP_TRY(cam_scale_.ensure());
     HIP_TRY(pt_scale_.ensure());
     std::vector<double> hc, hl;
@@ -1277,17 +1282,16 @@ int Solver::set_column_scaling(const double* scaling) {
 
 // iteration 0 of the reference's loop: norms of the current Jacobian -> s = 1 / (1 + norm), kept for the whole optimize
 int Solver::set_jacobi_scaling(bool on) {
-    drop_dogleg_cache();
-    if (!on) { scaled_ = false; st_.invalidate_step(); return kOk; }
-    if (!have_params_) return fail(kInvalidState, "no parameters set");
+    if (!on) { scaled_ = false; voided_by(Change::kScalingOff); return kOk; }
+    if (!have_params_) return fail(kInvalidState, "no parameters set");   // (no parameters: no step and no Dog-Leg cache to void)
     HIP_TRY(hipSetDevice(device_));
-    if (factor_scaled_) factor_lin_ = -1;   // (the factor's scale vectors are overwritten below)
+    voided_by(Change::kScalingVectors);   // (ahead of the norms, which overwrite the vectors)
     int rc = column_norms_sq_device();
     if (rc != kOk) return rc;
     HIP_TRY(cam_scale_.from_norms_sq(cam_scale_.dev, n_c_pad_, stream_));  // padding: n2 = 0 -> 1
     HIP_TRY(pt_scale_.from_norms_sq(pt_scale_.dev, 3 * n_pt_, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
-    scaled_ = true; st_.invalidate_step();
+    scaled_ = true;
     return kOk;
 }
 
@@ -1447,12 +1451,12 @@ int Solver::schur_matvec(double lambda, const double* x_in, double* y_explicit, 
 // get_hessian (explicit_schur.rs:1236-1238): H = J^T J, undamped, full symmetric, CSC in the global column order.  The
 // device never forms it; this export rebuilds it on the host from the per-factor blocks the device linearises (an
 // observer / DogLeg path, not the hot path): structural entries of every factor are kept even when a block is zero
-// (a point behind its camera), as the reference's sparse product keeps them.
+// (a point behind its camera), as the reference's sparse product keeps them.  The device work is here -- the two copies that
+// rebuild the caller's factor list, the priors' diagonal, the blocks --, the assembly is the host function hessian_csc.
 int Solver::get_hessian_csc(int64_t* nnz_out, int64_t* colptr, int64_t* rowidx, double* values) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     if (world_ > 1) return fail(kInvalidState, "the Hessian export is single-rank");
     if (!nnz_out) return fail(kInvalidInput, "nnz_out is NULL");
-    const int64_t total = 9 * n_cam_ + 3 * n_pt_;
     // the caller's factor list, rebuilt from the device's landmark-major lists (single rank: they hold every observation):
     // observation k of the device is the caller's o_orig[k], its camera / landmark the internal ones mapped back
     std::vector<uint32_t> cam_idx_h_(n_obs_), pt_idx_h_(n_obs_);
@@ -1471,97 +1475,26 @@ int Solver::get_hessian_csc(int64_t* nnz_out, int64_t* colptr, int64_t* rowidx, 
             pt_idx_h_[i] = (uint32_t)linv[op[k]];
         }
     }
-    // unique (camera, landmark) couplings and the variables that carry entries
-    std::vector<int64_t> order(n_obs_);
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-        return pt_idx_h_[a] != pt_idx_h_[b] ? pt_idx_h_[a] < pt_idx_h_[b] : cam_idx_h_[a] < cam_idx_h_[b];
-    });
-    std::vector<uint8_t> cam_seen(n_cam_, 0), pt_seen(n_pt_, 0);
-    int64_t n_cl = 0;
-    for (int64_t k = 0; k < n_obs_; ++k) {
-        const int64_t i = order[k];
-        cam_seen[cam_idx_h_[i]] = 1; pt_seen[pt_idx_h_[i]] = 1;
-        if (k == 0 || pt_idx_h_[i] != pt_idx_h_[order[k - 1]] || cam_idx_h_[i] != cam_idx_h_[order[k - 1]]) ++n_cl;
-    }
+    HessianCscInput in;
+    in.n_cam = n_cam_; in.n_pt = n_pt_; in.n_obs = n_obs_; in.dc = dc_;
+    in.cam_idx = cam_idx_h_.data(); in.pt_idx = pt_idx_h_.data();
+    in.cmap = &cmap_; in.cam_map = &cam_map_; in.pt_map = &pt_map_;
     std::vector<double> pd;   // diag(P) of the camera priors, internal order: their cameras carry a diagonal block even when unobserved
     if (have_priors()) {
         enqueue_prior_eval(st_.cur, false);
         pd.resize(n_c_);
         HIP_TRY(hipMemcpyAsync(pd.data(), pri_diag_, n_c_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
         HIP_TRY(hipStreamSynchronize(stream_));
-        for (int64_t c = 0; c < n_cam_; ++c)
-            for (int a = 0; a < dc_; ++a)
-                if (pd[(size_t)cmap_[c] * dc_ + a] != 0.0) cam_seen[c] = 1;
+        in.prior_diag = &pd;
     }
-    int64_t nnz = 2 * n_cl * dc_ * 3;
-    for (int64_t c = 0; c < n_cam_; ++c) if (cam_seen[c]) nnz += dc_ * dc_;
-    for (int64_t l = 0; l < n_pt_; ++l) if (pt_seen[l]) nnz += 9;
-    *nnz_out = nnz;
+    *nnz_out = hessian_csc(in, nullptr, nullptr, nullptr);   // (no blocks: the count alone)
     if (!colptr) return kOk;
     if (!rowidx || !values) return fail(kInvalidInput, "rowidx / values are NULL");
     std::vector<double> jc((size_t)2 * dc_ * n_obs_), jl((size_t)6 * n_obs_);
     int rc = get_jacobian_blocks(jc.data(), jl.data());
     if (rc != kOk) return rc;
-    // column a of the caller's camera c: cc[cp[c] + a]; column b of its landmark l: pc[pp[l] + b]
-    const std::vector<int64_t>&cc = cam_map_.col, &cp = cam_map_.pos, &pc = pt_map_.col, &pp = pt_map_.pos;
-    struct Trip { int64_t col, row; double v; };
-    std::vector<Trip> t;
-    t.reserve((size_t)nnz);
-    {   // camera blocks
-        std::vector<double> hcc((size_t)n_cam_ * dc_ * dc_, 0.0);
-        for (int64_t i = 0; i < n_obs_; ++i) {
-            const double* J = jc.data() + (size_t)2 * dc_ * i;
-            double* H = hcc.data() + (size_t)cam_idx_h_[i] * dc_ * dc_;
-            for (int a = 0; a < dc_; ++a)
-                for (int b = 0; b < dc_; ++b) H[a * dc_ + b] += J[a] * J[b] + J[dc_ + a] * J[dc_ + b];
-        }
-        if (!pd.empty())
-            for (int64_t c = 0; c < n_cam_; ++c)
-                for (int a = 0; a < dc_; ++a) hcc[(size_t)c * dc_ * dc_ + a * dc_ + a] += pd[(size_t)cmap_[c] * dc_ + a];
-        for (int64_t c = 0; c < n_cam_; ++c)
-            if (cam_seen[c])
-                for (int a = 0; a < dc_; ++a)
-                    for (int b = 0; b < dc_; ++b) t.push_back({cc[cp[c] + b], cc[cp[c] + a], hcc[(size_t)c * dc_ * dc_ + a * dc_ + b]});
-    }
-    {   // landmark blocks
-        std::vector<double> hll((size_t)n_pt_ * 9, 0.0);
-        for (int64_t i = 0; i < n_obs_; ++i) {
-            const double* J = jl.data() + (size_t)6 * i;
-            double* H = hll.data() + (size_t)pt_idx_h_[i] * 9;
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b) H[3 * a + b] += J[a] * J[b] + J[3 + a] * J[3 + b];
-        }
-        for (int64_t l = 0; l < n_pt_; ++l)
-            if (pt_seen[l])
-                for (int a = 0; a < 3; ++a)
-                    for (int b = 0; b < 3; ++b) t.push_back({pc[pp[l] + b], pc[pp[l] + a], hll[(size_t)l * 9 + 3 * a + b]});
-    }
-    {   // couplings, duplicated (camera, landmark) factors merged
-        std::vector<double> w((size_t)dc_ * 3);
-        for (int64_t k = 0; k < n_obs_;) {
-            const int64_t i0 = order[k];
-            const uint32_t c = cam_idx_h_[i0], l = pt_idx_h_[i0];
-            std::fill(w.begin(), w.end(), 0.0);
-            for (; k < n_obs_ && cam_idx_h_[order[k]] == c && pt_idx_h_[order[k]] == l; ++k) {
-                const double* Jc = jc.data() + (size_t)2 * dc_ * order[k];
-                const double* Jl = jl.data() + (size_t)6 * order[k];
-                for (int a = 0; a < dc_; ++a)
-                    for (int b = 0; b < 3; ++b) w[a * 3 + b] += Jc[a] * Jl[b] + Jc[dc_ + a] * Jl[3 + b];
-            }
-            for (int a = 0; a < dc_; ++a)
-                for (int b = 0; b < 3; ++b) {
-                    t.push_back({pc[pp[l] + b], cc[cp[c] + a], w[a * 3 + b]});
-                    t.push_back({cc[cp[c] + a], pc[pp[l] + b], w[a * 3 + b]});
-                }
-        }
-    }
-    if ((int64_t)t.size() != nnz) return fail(kInvalidState, "Hessian export: entry count mismatch");
-    std::sort(t.begin(), t.end(), [](const Trip& a, const Trip& b) { return a.col != b.col ? a.col < b.col : a.row < b.row; });
-    std::fill(colptr, colptr + total + 1, 0);
-    for (const Trip& e : t) colptr[e.col + 1]++;
-    for (int64_t j = 0; j < total; ++j) colptr[j + 1] += colptr[j];
-    for (int64_t k = 0; k < nnz; ++k) { rowidx[k] = t[k].row; values[k] = t[k].v; }
+    in.jc = jc.data(); in.jl = jl.data();
+    if (hessian_csc(in, colptr, rowidx, values) != *nnz_out) return fail(kInvalidState, "Hessian export: entry count mismatch");
     return kOk;
 }
 
@@ -1627,36 +1560,26 @@ int Solver::camera_covariance(double* out) {
     return kOk;
 }
 
-void Solver::lc_release() {
-    lc_lists_.reset(); lc_err_.reset(); lc_out_.reset();   // (null lc_out_: landmark_covariance sets up again)
-    lc_n_small_ = lc_n_large_ = 0;
-    lc_pairs_ = 0; lc_bytes_ = 0;
+void Solver::LandmarkCov::release() {
+    lists.reset(); err.reset(); out.reset();   // (null out: landmark_covariance sets up again)
+    n_small = n_large = 0;
+    pairs = 0; bytes = 0;
 }
 
-// The landmark lists of the covariance pass from the observation pointers: the landmarks with at most kLcSmallK observations
-// in the landmark-major order of the assembly (neighbours share cameras, so their Z blocks meet in L2), then the others by
-// decreasing observation count (one workgroup each, launched first: the longest start earliest).
+// The landmark lists of the covariance pass from the observation pointers (landmark_cov_lists.h), and the pass's buffers
 int Solver::lc_setup() {
     std::vector<int> ptr(n_pt_ + 1);
     HIP_TRY(hipMemcpy(ptr.data(), pt_ptr_, (n_pt_ + 1) * sizeof(int), hipMemcpyDeviceToHost));
-    std::vector<int> small, large;
-    int64_t pairs = 0;
-    for (int64_t l = 0; l < n_pt_; ++l) {
-        const int64_t k = ptr[l + 1] - ptr[l];
-        pairs += k * (k + 1) / 2;
-        (k <= kLcSmallK ? small : large).push_back((int)l);
-    }
-    std::stable_sort(large.begin(), large.end(), [&](int a, int b) { return ptr[a + 1] - ptr[a] > ptr[b + 1] - ptr[b]; });
-    small.insert(small.end(), large.begin(), large.end());
-    const size_t b_lists = std::max<size_t>(small.size(), 1) * sizeof(int), b_out = 9 * (size_t)n_pt_ * sizeof(double);
-    hipError_t e = lc_lists_.upload(small);
-    if (e == hipSuccess) e = lc_err_.alloc(1);
-    if (e == hipSuccess) e = lc_out_.alloc(9 * (size_t)n_pt_);
-    if (e != hipSuccess) { lc_release(); return check_hip(e, "landmark covariance set-up"); }
-    lc_n_large_ = (int)large.size();
-    lc_n_small_ = (int)(small.size() - large.size());
-    lc_pairs_ = pairs;
-    lc_bytes_ = b_lists + sizeof(int) + b_out;
+    const LandmarkCovLists ll = build_landmark_cov_lists(n_pt_, ptr.data(), kLcSmallK);
+    const size_t b_lists = std::max<size_t>(ll.lists.size(), 1) * sizeof(int), b_out = 9 * (size_t)n_pt_ * sizeof(double);
+    hipError_t e = lc_.lists.upload(ll.lists);
+    if (e == hipSuccess) e = lc_.err.alloc(1);
+    if (e == hipSuccess) e = lc_.out.alloc(9 * (size_t)n_pt_);
+    if (e != hipSuccess) { lc_.release(); return check_hip(e, "landmark covariance set-up"); }
+    lc_.n_large = ll.n_large;
+    lc_.n_small = ll.n_small;
+    lc_.pairs = ll.pairs;
+    lc_.bytes = b_lists + sizeof(int) + b_out;
     return kOk;
 }
 
@@ -1675,9 +1598,9 @@ int Solver::landmark_covariance(double* out) {
     int rc = tp_.inverse().ensure(&recomputed, &err);
     if (rc == 1) return fail(kInvalidState, "landmark covariance: " + err + " (the Iterative and matrix-free variants have no factor)");
     if (rc != 0) return fail(kDeviceError, "landmark covariance: " + err);
-    if (!lc_out_ && (rc = lc_setup()) != kOk) return rc;
-    lc_recomputed_ = recomputed;
-    lc_ms_ = 0.0;
+    if (!lc_.out && (rc = lc_setup()) != kOk) return rc;
+    lc_.recomputed = recomputed;
+    lc_.ms = 0.0;
     BAView v = view(factor_lin_);   // the cameras the factor was linearised at; the points come from the landmark records
     v.cam_scale = factor_scaled_ ? cam_scale_.dev.get() : nullptr;
     v.pt_scale = factor_scaled_ ? pt_scale_.dev.get() : nullptr;
@@ -1687,20 +1610,20 @@ int Solver::landmark_covariance(double* out) {
         HIP_TRY(hipEventCreate(&ev[0]));
         HIP_TRY(hipEventCreate(&ev[1]));
     }
-    HIP_TRY(hipMemsetAsync(lc_err_, 0, sizeof(int), stream_));
+    HIP_TRY(hipMemsetAsync(lc_.err, 0, sizeof(int), stream_));
     if (timed) HIP_TRY(hipEventRecord(ev[0], stream_));
-    launch_landmark_cov(dc_, v, hinv_, tp_.inverse().map(), lc_lists_, lc_n_small_, lc_lists_ + lc_n_small_, lc_n_large_, lc_out_, lc_err_, stream_, general_loss());
+    launch_landmark_cov(dc_, v, hinv_, tp_.inverse().map(), lc_.lists, lc_.n_small, lc_.lists + lc_.n_small, lc_.n_large, lc_.out, lc_.err, stream_, general_loss());
     if (timed) HIP_TRY(hipEventRecord(ev[1], stream_));
     hipError_t e = hipGetLastError();
     std::vector<double> blk(9 * (size_t)n_pt_);
     int kerr = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(blk.data(), lc_out_, blk.size() * sizeof(double), hipMemcpyDeviceToHost, stream_);
-    if (e == hipSuccess) e = hipMemcpyAsync(&kerr, lc_err_, sizeof(int), hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk.data(), lc_.out, blk.size() * sizeof(double), hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess) e = hipMemcpyAsync(&kerr, lc_.err, sizeof(int), hipMemcpyDeviceToHost, stream_);
     const hipError_t se = hipStreamSynchronize(stream_);
     if (e == hipSuccess) e = se;
     if (timed) {
         float ms = 0.0f;
-        if (e == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) lc_ms_ = ms;
+        if (e == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) lc_.ms = ms;
         (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
     }
     if (e != hipSuccess) return check_hip(e, "landmark covariance");

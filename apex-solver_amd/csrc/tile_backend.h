@@ -131,6 +131,10 @@ class TileBackend : public TrBackend {
     // maps and zero-padded, to out3.  One wait; booked under the stats stage; the Dog-Leg cache stays.
     int jv_gram_columns(const double* a, const double* b, double out3[3]);
     void drop_dogleg_cache() { have_dl_cache_ = false; }
+    // What a setter did to the handle.  Each solver has ONE function over these, voided_by(), that says which cached state the
+    // change voids (a pending step and trial point, the Dog-Leg cache, and what else the solver keeps): the table of DESIGN.md,
+    // "What a change voids".  The solve path (assemblies, factorisations, exports that assemble) keeps its own direct calls.
+    enum class Change { kStructure, kParams, kLoss, kPriors, kInformation, kScalingOff, kScalingVectors };
     // set_structure: they are sized by the old structure, dogleg_step allocates them again
     void release_dogleg_buffers() { for (int k = 0; k < 2; ++k) { dl_h_[k].reset(); dl_a_[k].reset(); } dls_.reset(); }
 
