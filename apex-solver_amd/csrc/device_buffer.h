@@ -1,7 +1,9 @@
 // device_buffer.h -- the two owners of memory the library allocates through HIP: DeviceBuffer<T> (one hipMalloc block) and
 // PinnedBuffer<T> (one hipHostMalloc block).  Move-only; the destructor frees; alloc / alloc_zero / upload free what was held
 // first and return the HIP status.  Both convert to T*, so a buffer is passed, indexed, offset and null-tested as the
-// pointer it owns.  Every allocation holds at least one element: an empty list still gets an address.
+// pointer it owns.  Every allocation holds at least kMinBytes: an empty list still gets an address, and upload() of an empty
+// list clears it -- the kernels issue their first loads unconditionally on a clamped index (ba_kernels.hip), so entry 0 of a
+// list must exist and be a valid index even on a rank that holds no observation at all.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -9,6 +11,8 @@
 #include <algorithm>
 
 namespace apex {
+
+constexpr size_t kMinBytes = 64;   // (the widest unconditional first load is 32 bytes: two double2 of a projection record)
 
 template <typename T>
 class DeviceBuffer {
@@ -25,19 +29,20 @@ class DeviceBuffer {
 
     hipError_t alloc(size_t n) {   // contents undefined
         reset();
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p_), std::max<size_t>(n, 1) * sizeof(T));
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p_), std::max<size_t>(n * sizeof(T), kMinBytes));
         if (e != hipSuccess) p_ = nullptr;
         return e;
     }
     hipError_t alloc_zero(size_t n) {   // cleared on the NULL stream: the caller synchronises the device before a non-blocking stream reads it
         const hipError_t e = alloc(n);
-        return e != hipSuccess ? e : hipMemset(p_, 0, std::max<size_t>(n, 1) * sizeof(T));
+        return e != hipSuccess ? e : hipMemset(p_, 0, std::max<size_t>(n * sizeof(T), kMinBytes));
     }
     template <typename C>
     hipError_t upload(const C& hv) {   // synchronous copy of anything with data() / size() and T's element size
         static_assert(sizeof(*hv.data()) == sizeof(T), "upload: element size differs");
         const hipError_t e = alloc(hv.size());
-        if (e != hipSuccess || hv.size() == 0) return e;
+        if (e != hipSuccess) return e;
+        if (hv.size() == 0) return hipMemset(p_, 0, kMinBytes);
         return hipMemcpy(p_, hv.data(), hv.size() * sizeof(T), hipMemcpyHostToDevice);
     }
     void reset() {

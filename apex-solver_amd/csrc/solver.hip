@@ -1410,7 +1410,10 @@ int Solver::get_schur(double* S_out, double* gred_out) {
     }
     if (S_out) {
         std::fill(S_out, S_out + nref * nref, 0.0);
-        for (int64_t u : cam_map_.untouched) S_out[u * nref + u] = last_lambda_;   // intrinsic variables exist but no factor touches them: S_ii = lambda
+        // intrinsic variables exist but no factor touches them: S_ii = lambda.  A shard without a communicator exports its
+        // partial S, and the partials sum to the whole: rank 0 alone carries these entries, as in schur_matvec
+        if (rank_ == 0 || comm_)
+            for (int64_t u : cam_map_.untouched) S_out[u * nref + u] = last_lambda_;
         return export_tiles_dense(cam_map_, nref, tp_.n_slots(), S_out);
     }
     return kOk;

@@ -99,14 +99,17 @@ class SchurRef:
     kap_l = max(1, (sum_k (2 |M_Jl_k| |Jl_k| - |Jl_k|^2) + lambda) / |H_ll|) in spectral norms (the magnitude of a square is
     2 M |x| - x^2 to first order): cond eps |H^-1| with eps the relative uncertainty of H_ll."""
 
-    def __init__(self, n_cam, n_pt, cam_idx, pt_idx, jc, jl, r, lam, dtype=LD, dense=True, chunk=20000, hinv_given=None, mags=None):
+    def __init__(self, n_cam, n_pt, cam_idx, pt_idx, jc, jl, r, lam, dtype=LD, dense=True, chunk=20000, hinv_given=None, mags=None,
+                 lam_cams=None):
         T = self.T = dtype
+        # lam_cams (boolean per camera, None: all): the cameras whose H_cc carries lambda -- a shard's partial system (shard_cases.py)
+        lam_c = np.where(np.ones(n_cam, dtype=bool) if lam_cams is None else np.asarray(lam_cams, dtype=bool), T(lam), T(0)).astype(T)
         self.n_cam, self.n_pt, self.lam = int(n_cam), int(n_pt), float(lam)
         ci = self.ci = np.asarray(cam_idx, dtype=np.int64); li = self.li = np.asarray(pt_idx, dtype=np.int64)
         Jc = np.asarray(jc, dtype=T); Jl = np.asarray(jl, dtype=T); rr = np.asarray(r, dtype=T).reshape(-1, 2)
         dc = self.dc = Jc.shape[2]
         eye_c, eye_l = np.eye(dc, dtype=T), np.eye(3, dtype=T)
-        self.Hcc = _scatter(n_cam, ci, np.einsum("kra,krb->kab", Jc, Jc), T) + T(lam) * eye_c
+        self.Hcc = _scatter(n_cam, ci, np.einsum("kra,krb->kab", Jc, Jc), T) + lam_c[:, None, None] * eye_c
         self.gc = _scatter(n_cam, ci, np.einsum("kra,kr->ka", Jc, rr), T)
         self.Hll = _scatter(n_pt, li, np.einsum("kra,krb->kab", Jl, Jl), T) + T(lam) * eye_l
         self.gl = _scatter(n_pt, li, np.einsum("kra,kr->ka", Jl, rr), T)
@@ -128,7 +131,7 @@ class SchurRef:
             self.jcn, self.jln = _n2(mags[0]), mjl
             self.rn = np.linalg.norm(np.asarray(mags[2], dtype=np.float64).reshape(-1, 2), axis=1)
             self.wn = self.jcn * self.jln
-        self.hcc_mag = _scatter(n_cam, ci, self.jcn ** 2, np.float64) + abs(lam)
+        self.hcc_mag = _scatter(n_cam, ci, self.jcn ** 2, np.float64) + np.abs(lam_c.astype(np.float64))
         self.gl_mag = _scatter(n_pt, li, self.jln * self.rn, np.float64)
         self.gred_mag = _scatter(n_cam, ci, self.jcn * self.rn + self.wn * self.hn[li] * self.gl_mag[li], np.float64)
         kmax_i = np.zeros(n_cam, dtype=np.int64); np.maximum.at(kmax_i, ci, self.k_l[li])
@@ -188,10 +191,10 @@ class SchurRef:
         return pmax + self.dc * (np.minimum(partners, self.n_cam) + 1)
 
 
-def pair(n_cam, n_pt, cam_idx, pt_idx, jc, jl, r, lam, dense=True):
+def pair(n_cam, n_pt, cam_idx, pt_idx, jc, jl, r, lam, dense=True, lam_cams=None):
     """(long double reference, fp64 restatement) of one linearisation."""
-    return (SchurRef(n_cam, n_pt, cam_idx, pt_idx, jc, jl, r, lam, LD, dense),
-            SchurRef(n_cam, n_pt, cam_idx, pt_idx, jc, jl, r, lam, np.float64, dense))
+    return (SchurRef(n_cam, n_pt, cam_idx, pt_idx, jc, jl, r, lam, LD, dense, lam_cams=lam_cams),
+            SchurRef(n_cam, n_pt, cam_idx, pt_idx, jc, jl, r, lam, np.float64, dense, lam_cams=lam_cams))
 
 
 # ---- column order ---------------------------------------------------------------------------------------------------------
