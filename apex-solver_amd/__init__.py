@@ -6,6 +6,7 @@ Host-side modules:
   layout     the reference's lexicographic global column layout
   capi       ctypes binding of the C-ABI library (include/apexgpu.h)
   solver     Python mirror of the reference's Problem / LevenbergMarquardt surface
+  handle_solver  the calls GpuSchurComplementSolver and GpuSparseCholeskySolver share, written once against the handle's prefix
   loss       the robust loss family of both front ends: Loss, create_loss_function
   pose_graph SE3 pose-graph path: G2O reader, PoseGraphProblem, GpuSparseCholeskySolver
   datasets   real BAL / G2O files in the reference's data/ layout when present, the synthetic shapes otherwise

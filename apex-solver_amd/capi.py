@@ -457,24 +457,32 @@ def ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-class Handle:
-    """RAII wrapper of an apexgpu_solver*."""
+class _HandleBase:
+    """Owner of one library handle of the kind whose calls start with _PREFIX: L the library, h the handle."""
 
-    def __init__(self, n_cam: int, n_pt: int, n_obs: int, mode: int, device: int = 0):
+    _PREFIX = ""
+
+    def __init__(self):
         self.L = load()
         self.h = C.c_void_p()
-        rc = self.L.apexgpu_create(n_cam, n_pt, n_obs, mode, device, C.byref(self.h))
+
+    def _fn(self, name: str):
+        """The call of this handle's kind by its unprefixed name: apexgpu_cost / apexgpu_pg_cost for "cost"."""
+        return getattr(self.L, self._PREFIX + name)
+
+    def _call(self, name: str, *args):
+        """That call on this handle; raises what it refuses."""
+        rc = getattr(self.L, self._PREFIX + name)(self.h, *args)
         if rc != 0:
-            raise LinAlgError(rc, "apexgpu_create failed (no MI355X visible to HIP?)")
-        self.n_cam, self.n_pt, self.n_obs, self.mode = n_cam, n_pt, n_obs, mode
+            self.check(rc)
 
     def check(self, rc: int):
         if rc != 0:
-            raise LinAlgError(rc, self.L.apexgpu_last_error(self.h).decode())
+            raise LinAlgError(rc, self._fn("last_error")(self.h).decode())
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
-            self.L.apexgpu_destroy(self.h)
+            self._fn("destroy")(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -484,12 +492,26 @@ class Handle:
             pass
 
 
-class PgHandle:
+class Handle(_HandleBase):
+    """RAII wrapper of an apexgpu_solver*."""
+
+    _PREFIX = "apexgpu_"
+
+    def __init__(self, n_cam: int, n_pt: int, n_obs: int, mode: int, device: int = 0):
+        super().__init__()
+        rc = self.L.apexgpu_create(n_cam, n_pt, n_obs, mode, device, C.byref(self.h))
+        if rc != 0:
+            raise LinAlgError(rc, "apexgpu_create failed (no MI355X visible to HIP?)")
+        self.n_cam, self.n_pt, self.n_obs, self.mode = n_cam, n_pt, n_obs, mode
+
+
+class PgHandle(_HandleBase):
     """RAII wrapper of an apexgpu_pg_solver*."""
 
+    _PREFIX = "apexgpu_pg_"
+
     def __init__(self, n_vertices: int, n_edges: int, device: int = 0, manifold: int = MANIFOLD_SE3):
-        self.L = load()
-        self.h = C.c_void_p()
+        super().__init__()
         if manifold not in MANIFOLD_SIZES:
             raise ValueError(f"unknown manifold {manifold!r}")
         create = {MANIFOLD_SE3: self.L.apexgpu_pg_create, MANIFOLD_SE2: self.L.apexgpu_pg_create_se2,
@@ -500,21 +522,6 @@ class PgHandle:
         self.n_vertices, self.n_edges = n_vertices, n_edges
         self.manifold = manifold
         self.ambient, self.dof = MANIFOLD_SIZES[manifold]   # SO3: 4-wide poses / measurements / priors, 3-wide steps and masks
-
-    def check(self, rc: int):
-        if rc != 0:
-            raise LinAlgError(rc, self.L.apexgpu_pg_last_error(self.h).decode())
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h:
-            self.L.apexgpu_pg_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class TileCholesky:

@@ -17,6 +17,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import capi
+from .handle_solver import HandleSolver
 from .loss import Loss, create_loss_function   # (both front ends use them; exported from here as before)
 from .synthetic import PoseGraphData
 
@@ -340,27 +341,32 @@ class DogLegConfig:
                               1 if self.use_jacobi_scaling else 0, 1 if self.enable_step_reuse else 0)
 
 
-class GpuSparseCholeskySolver:
+class GpuSparseCholeskySolver(HandleSolver):
     """Device counterpart of SparseCholeskySolver (src/linalg/sparse/cholesky.rs) for pose graphs:
     `solve_augmented_equation(lambda)` linearises the BetweenFactors, assembles J^T J + lambda I
-    block-sparse and solves by the tile Cholesky.  No Schur complement."""
+    block-sparse and solves by the tile Cholesky.  No Schur complement.  The calls it shares with the bundle-adjustment
+    solver are HandleSolver's."""
+
+    _STAGE_NAMES = capi.PG_STAGE_NAMES
 
     def __init__(self, device: int = 0):
-        self.device = device
-        self._h: capi.PgHandle | None = None
-        self._opts: dict[str, int] = {}
+        super().__init__(device)
         self.problem: PoseGraphProblem | None = None
 
-    def with_option(self, name: str, value: int):
-        self._opts[name] = int(value)
-        return self
+    def _need(self) -> capi.PgHandle:
+        return self._h or self._built(-6)
+
+    def _total_dof(self) -> int:
+        return self._h.dof * self._h.n_vertices
+
+    def _variant(self) -> int:
+        return 0
 
     def initialize_structure(self, problem: PoseGraphProblem):
         d = problem.data
         self.close()
         h = capi.PgHandle(d.n_v, d.n_e, self.device, _MANIFOLD_IDS[problem.manifold])
-        for k, v in self._opts.items():
-            h.check(h.L.apexgpu_pg_set_option(h.h, k.encode(), v))
+        self._apply_options(h)
         ef = np.ascontiguousarray(d.e_from, dtype=np.uint32); et = np.ascontiguousarray(d.e_to, dtype=np.uint32)
         meas = np.ascontiguousarray(d.meas, dtype=np.float64)
         fix = np.ascontiguousarray(problem.fix, dtype=np.uint8)
@@ -396,18 +402,6 @@ class GpuSparseCholeskySolver:
         h.check(h.L.apexgpu_pg_get_information(h.h, C.byref(present), capi.ptr(out)))
         return out if present.value else None
 
-    def set_loss(self, loss: Loss | None):
-        """The loss of every BetweenFactor block from here on (None: no loss); replaces the problem's huber_delta."""
-        h = self._need()
-        loss = Loss(capi.LOSS_NONE) if loss is None else loss
-        h.check(h.L.apexgpu_pg_set_loss(h.h, int(loss.kind), float(loss.p0), float(loss.p1)))
-
-    def get_loss(self) -> Loss:
-        h = self._need()
-        k = C.c_int(); p = (C.c_double * 2)()
-        h.check(h.L.apexgpu_pg_get_loss(h.h, C.byref(k), C.byref(p)))
-        return Loss(k.value, p[0], p[1])
-
     def set_priors(self, priors):
         """PriorFactor blocks: (vertex index, data[7], huber delta or None) each; replaces the set."""
         h = self._need()
@@ -424,11 +418,6 @@ class GpuSparseCholeskySolver:
         if n: h.check(h.L.apexgpu_pg_get_prior_residual(h.h, capi.ptr(r)))
         return r
 
-    def _need(self) -> capi.PgHandle:
-        if self._h is None:
-            raise capi.LinAlgError(-6, "Block structure not built. Call initialize_structure() first.")
-        return self._h
-
     def set_parameters(self, poses):
         h = self._need()
         p = np.ascontiguousarray(poses, dtype=np.float64)
@@ -442,65 +431,13 @@ class GpuSparseCholeskySolver:
         h.check(h.L.apexgpu_pg_get_params(h.h, capi.ptr(p)))
         return p
 
-    def compute_cost(self) -> float:
-        h = self._need()
-        c = C.c_double()
-        h.check(h.L.apexgpu_pg_cost(h.h, C.byref(c)))
-        return c.value
-
     def solve_augmented_equation(self, lam: float, want_step: bool = True):
         h = self._need()
-        n = h.dof * h.n_vertices
+        n = self._total_dof()
         step = np.zeros(n) if want_step else None
-        self._grad = np.zeros(n) if want_step else None
-        h.check(h.L.apexgpu_pg_solve_augmented(h.h, float(lam), capi.ptr(step), capi.ptr(self._grad)))
+        self._gradient = np.zeros(n) if want_step else None
+        h.check(h.L.apexgpu_pg_solve_augmented(h.h, float(lam), capi.ptr(step), capi.ptr(self._gradient)))
         return step
-
-    def solve_normal_equation(self):
-        return self.solve_augmented_equation(0.0)
-
-    def get_gradient(self):
-        return getattr(self, "_grad", None)
-
-    # AssemblyBackend::compute_column_norms / apply_column_scaling / apply_inverse_scaling (linearizer/mod.rs:229-262)
-    def compute_column_norms(self) -> np.ndarray:
-        h = self._need()
-        n = np.zeros(h.dof * h.n_vertices)
-        h.check(h.L.apexgpu_pg_column_norms(h.h, capi.ptr(n)))
-        return n
-
-    def apply_column_scaling(self, scaling):
-        h = self._need()
-        a = None if scaling is None else np.ascontiguousarray(scaling, dtype=np.float64)
-        if a is not None and a.shape != (h.dof * h.n_vertices,):
-            raise ValueError("scaling must have total_dof entries")
-        h.check(h.L.apexgpu_pg_set_column_scaling(h.h, capi.ptr(a)))
-        self._scaling = a
-
-    def apply_inverse_scaling(self, step):
-        s = getattr(self, "_scaling", None)
-        return step if s is None else step * s
-
-    def step_stats(self):
-        h = self._need()
-        o = (C.c_double * 3)()
-        h.check(h.L.apexgpu_pg_step_stats(h.h, C.byref(o)))
-        return o[0], o[1], o[2]
-
-    def eval_step(self) -> float:
-        h = self._need()
-        c = C.c_double()
-        h.check(h.L.apexgpu_pg_eval_step(h.h, C.byref(c)))
-        return c.value
-
-    def commit_step(self): h = self._need(); h.check(h.L.apexgpu_pg_commit_step(h.h))
-    def discard_step(self): h = self._need(); h.check(h.L.apexgpu_pg_discard_step(h.h))
-
-    def parameter_norm(self) -> float:
-        h = self._need()
-        c = C.c_double()
-        h.check(h.L.apexgpu_pg_parameter_norm(h.h, C.byref(c)))
-        return c.value
 
     def get_residual(self) -> np.ndarray:
         h = self._need()
@@ -537,11 +474,6 @@ class GpuSparseCholeskySolver:
         blocks = self.pose_covariance_blocks()
         return {f"x{int(i)}": blocks[k].copy() for k, i in enumerate(self.problem.data.ids)}
 
-    def covariance_stats(self, group_cap: int = 0) -> dict:
-        from .solver import _covariance_stats
-        h = self._need()
-        return _covariance_stats(h, h.L.apexgpu_pg_covariance_stats, group_cap)
-
     def info(self) -> dict:
         h = self._need()
         a = (C.c_double * 8)()
@@ -549,80 +481,7 @@ class GpuSparseCholeskySolver:
         return {"tile_rows": int(a[0]), "tiles": int(a[1]), "touched_tiles": int(a[2]), "etree_levels": int(a[3]),
                 "total_dof": int(a[4]), "n_potrf": int(a[5]), "n_trsm": int(a[6]), "n_update": int(a[7])}
 
-    def set_option(self, name: str, value: int):
-        h = self._need(); h.check(h.L.apexgpu_pg_set_option(h.h, name.encode(), int(value)))
-
-    def counters(self) -> dict:
-        h = self._need(); out = (C.c_int64 * 4)()
-        h.check(h.L.apexgpu_pg_counters(h.h, C.byref(out)))
-        return dict(sweep_timeouts=int(out[0]), tri_dataflow=bool(out[1]), factor_flow_timeouts=int(out[2]), factor_flow_groups=int(out[3]))
-
-    def enable_stage_timing(self, on=True): h = self._need(); h.check(h.L.apexgpu_pg_enable_stage_timing(h.h, int(on)))
-    def reset_stage_times(self): h = self._need(); h.check(h.L.apexgpu_pg_reset_stage_times(h.h))
-
-    def stage_times(self) -> dict:
-        h = self._need()
-        ms = (C.c_double * capi.PG_NUM_STAGES)(); n = (C.c_int64 * capi.PG_NUM_STAGES)()
-        h.check(h.L.apexgpu_pg_stage_times(h.h, C.byref(ms), C.byref(n)))
-        return {name: (ms[i], n[i]) for i, name in enumerate(capi.PG_STAGE_NAMES)}
-
-    def lm_optimize(self, cfg):
-        h = self._need()
-        c = cfg.to_c()
-        c.variant = 0
-        res = capi.LmResultC()
-        cap = cfg.max_iterations + 2
-        hist = (capi.LmIterC * cap)()
-        h.check(h.L.apexgpu_pg_lm_optimize(h.h, C.byref(c), C.byref(res), C.cast(hist, C.c_void_p), cap))
-        n = res.iterations
-        H = np.array([[getattr(hist[i], f) for f, _ in capi.LmIterC._fields_] for i in range(min(n, cap))])
-        return res, H.reshape(-1, 8), c
-
     def gn_optimize(self, cfg: GaussNewtonConfig):
         """GaussNewton::optimize (gauss_newton.rs:559-720) on the device: (result, history (n, 8) in LmIterC's columns with
         damping = rho = 0 and accepted = 1, the config as the loop left it)."""
-        h = self._need()
-        c = cfg.to_c()
-        res = capi.LmResultC()
-        cap = cfg.max_iterations + 2
-        hist = (capi.LmIterC * cap)()
-        h.check(h.L.apexgpu_pg_gn_optimize(h.h, C.byref(c), C.byref(res), C.cast(hist, C.c_void_p), cap))
-        H = np.array([[getattr(hist[i], f) for f, _ in capi.LmIterC._fields_] for i in range(min(res.iterations, cap))])
-        return res, H.reshape(-1, 8), c
-
-    def dogleg_optimize(self, cfg: DogLegConfig):
-        """DogLeg::optimize (dog_leg.rs:1143-1354) on the device: (result, history (n, 12) in DlIterC's columns, the config as
-        the loop left it -- trust_region_radius and mu hold their final values)."""
-        h = self._need()
-        c = cfg.to_c()
-        res = capi.LmResultC()
-        cap = cfg.max_iterations + 2
-        hist = (capi.DlIterC * cap)()
-        h.check(h.L.apexgpu_pg_dogleg_optimize(h.h, C.byref(c), C.byref(res), C.cast(hist, C.c_void_p), cap))
-        H = np.array([[getattr(hist[i], f) for f, _ in capi.DlIterC._fields_] for i in range(min(res.iterations, cap))])
-        return res, H.reshape(-1, 12), c
-
-    def dogleg_step(self, mu: float, radius: float, reuse: bool = False) -> dict:
-        """One Dog-Leg step and its trial point at the current parameters; eval_step / commit_step / discard_step follow.
-        reuse: rebuild the step from the cached solve at the new radius (no assembly, no factorisation)."""
-        h = self._need()
-        o = (C.c_double * 8)()
-        h.check(h.L.apexgpu_pg_dogleg_step(h.h, float(mu), float(radius), 1 if reuse else 0, C.byref(o)))
-        return dict(gradient_norm=o[0], step_norm=o[1], predicted_reduction=o[2], step_type=int(o[3]), alpha=o[4], beta=o[5],
-                    scaled_step_norm=o[6], reused=bool(o[7]))
-
-    def jv_gram(self, a, b):
-        """(|J a|^2, (J a).(J b), |J b|^2) at the current parameters, matrix-free; a, b in the global column order."""
-        h = self._need()
-        n = h.dof * h.n_vertices
-        a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
-        if a.shape != (n,) or b.shape != (n,):
-            raise ValueError("a and b must have total_dof entries")
-        o = (C.c_double * 3)()
-        h.check(h.L.apexgpu_pg_jv_gram(h.h, capi.ptr(a), capi.ptr(b), C.byref(o)))
-        return o[0], o[1], o[2]
-
-    def close(self):
-        if self._h is not None:
-            self._h.close()
-            self._h = None
+        return self._optimize("gn_optimize", cfg, capi.LmIterC)

@@ -24,14 +24,16 @@ from __future__ import annotations
 
 import ctypes as C
 import enum
+import time
 from dataclasses import dataclass, field, replace
 
 import numpy as np
 
 from . import capi
+from .handle_solver import HandleSolver
 from .layout import ColumnLayout, reference_column_layout
 from .loss import Loss, create_loss_function  # noqa: F401
-from .pose_graph import DogLegConfig
+from .pose_graph import DogLegConfig, GpuSparseCholeskySolver, PoseGraphProblem
 from .synthetic import BAProblemData
 
 
@@ -252,25 +254,35 @@ class Problem:
         return self.data.n_obs
 
 
-class GpuSchurComplementSolver:
+class GpuSchurComplementSolver(HandleSolver):
     """Device-resident explicit-Schur solver behind the reference's LinearSolver surface.
 
     Differences from SparseSchurComplementSolver that the boundary hides: the Jacobian is never
     materialised (the solver linearises the factors itself, so `solve_augmented_equation` takes
-    only lambda), and the parameters live on the device between calls."""
+    only lambda), and the parameters live on the device between calls.  The calls it shares with the pose-graph solver
+    are HandleSolver's."""
+
+    _STAGE_NAMES = capi.STAGE_NAMES
 
     def __init__(self, device: int = 0):
-        self.device = device
+        super().__init__(device)
         self.variant = SchurVariant.Sparse
         self.cg_max_iterations = 200
         self.cg_tolerance = 1e-6
-        self._h: capi.Handle | None = None
         self._problem: Problem | None = None
-        self._gradient = None
         self._shard = None
         self._comm = None
-        self._pre_options = {}
         self._n_pose_priors = self._n_intr_priors = 0
+        self.setup_wall = {}   # wall time of the set-up calls by piece (seconds): initialize_structure, set_parameters
+
+    def _need(self) -> capi.Handle:
+        return self._h or self._built(-5)
+
+    def _total_dof(self) -> int:
+        return self._problem.total_dof
+
+    def _variant(self) -> int:
+        return self.variant.value
 
     # builder methods (explicit_schur.rs:219-238)
     def with_variant(self, v: SchurVariant): self.variant = v; return self
@@ -280,10 +292,6 @@ class GpuSchurComplementSolver:
         if self._h is not None:
             self._h.check(self._h.L.apexgpu_set_cg_params(self._h.h, self.cg_max_iterations, self.cg_tolerance))
         return self
-    def with_option(self, name: str, value: int):
-        """An implementation switch that must be set before initialize_structure (e.g. nested_dissection)."""
-        self._pre_options[name] = int(value); return self
-
     def with_shard(self, rank: int, world: int): self._shard = (rank, world); return self
     def with_communicator(self, world: int, rank: int, unique_id: bytes): self._comm = (world, rank, unique_id); return self
     def with_shm_communicator(self, world: int, rank: int, name: str):
@@ -292,7 +300,6 @@ class GpuSchurComplementSolver:
 
     # StructureAware::initialize_structure
     def initialize_structure(self, problem: Problem):
-        import time
         t0 = time.perf_counter()
         d = problem.data
         mode = problem.optimization_type.value
@@ -307,42 +314,36 @@ class GpuSchurComplementSolver:
                 h.check(h.L.apexgpu_comm_init(h.h, world, rank, C.cast(buf, C.c_void_p)))
         elif self._shard is not None:
             h.check(h.L.apexgpu_set_shard(h.h, *self._shard))
-        for k, v in self._pre_options.items():
-            h.check(h.L.apexgpu_set_option(h.h, k.encode(), v))
+        self._apply_options(h)
         t1 = time.perf_counter()
-        lay = problem.layout
-        self._keep = [np.ascontiguousarray(a) for a in (
-            d.cam_idx.astype(np.uint32, copy=False), d.pt_idx.astype(np.uint32, copy=False), d.obs_uv.astype(np.float64, copy=False),
-            lay.intr_col, lay.pose_col, lay.pt_col, problem.fix_pose, problem.fix_intr, problem.fix_pt)]
-        hd = -1.0 if problem.huber_delta is None else float(problem.huber_delta)
-        t2 = time.perf_counter()
-        h.check(h.L.apexgpu_set_structure(h.h, *[capi.ptr(a) for a in self._keep], hd))
-        t3 = time.perf_counter()
-        h.check(h.L.apexgpu_set_cg_params(h.h, self.cg_max_iterations, self.cg_tolerance))
-        self._problem = problem
-        if problem.loss is not None:
-            self.set_loss(problem.loss)
-        self._n_pose_priors = self._n_intr_priors = 0   # (set_structure cleared both sets)
-        if problem.pose_priors or problem.intr_priors:
-            self.set_priors(problem.pose_priors, problem.intr_priors)
+        host_arrays, set_structure = self._set_problem(problem)
         # wall time of this call by piece (seconds): handle + communicator, host-side argument arrays, apexgpu_set_structure
-        self.setup_wall = dict(create_handle=t1 - t0, host_arrays=t2 - t1, set_structure=t3 - t2)
+        self.setup_wall = dict(create_handle=t1 - t0, host_arrays=host_arrays, set_structure=set_structure)
         return self
 
     def reinitialize_structure(self, problem: Problem):
         """A second initialize_structure on the SAME handle (StructureAware::initialize_structure may be called again,
         src/linalg/mod.rs:116-123): the counts are those the handle was created with, the lists and every decision that follows
         from them (tile plan, variant selection) are made afresh.  Options stay as they were set."""
-        h = self._need()
+        self._need()
         d, old = problem.data, self._problem.data
         if (d.n_cam, d.n_pt, d.n_obs) != (old.n_cam, old.n_pt, old.n_obs) or problem.optimization_type != self._problem.optimization_type:
             raise capi.LinAlgError(-5, "reinitialize_structure: the handle was created for other counts")
-        lay = problem.layout
+        self._set_problem(problem)
+        return self
+
+    def _set_problem(self, problem: Problem):
+        """This problem's lists, loss and priors onto the handle; the seconds the host-side argument arrays and
+        apexgpu_set_structure took."""
+        h, d, lay = self._h, problem.data, problem.layout
+        t0 = time.perf_counter()
         self._keep = [np.ascontiguousarray(a) for a in (
             d.cam_idx.astype(np.uint32, copy=False), d.pt_idx.astype(np.uint32, copy=False), d.obs_uv.astype(np.float64, copy=False),
             lay.intr_col, lay.pose_col, lay.pt_col, problem.fix_pose, problem.fix_intr, problem.fix_pt)]
         hd = -1.0 if problem.huber_delta is None else float(problem.huber_delta)
+        t1 = time.perf_counter()
         h.check(h.L.apexgpu_set_structure(h.h, *[capi.ptr(a) for a in self._keep], hd))
+        t2 = time.perf_counter()
         h.check(h.L.apexgpu_set_cg_params(h.h, self.cg_max_iterations, self.cg_tolerance))
         self._problem = problem
         if problem.loss is not None:
@@ -350,22 +351,7 @@ class GpuSchurComplementSolver:
         self._n_pose_priors = self._n_intr_priors = 0   # (set_structure cleared both sets)
         if problem.pose_priors or problem.intr_priors:
             self.set_priors(problem.pose_priors, problem.intr_priors)
-        return self
-
-    def set_loss(self, loss: Loss | None):
-        """The loss of every ProjectionFactor block from here on (None: no loss); replaces the problem's huber_delta until the
-        next initialize_structure.  InvalidInput for the kinds whose corrector needs more than one weight per observation
-        (Andrews, lp with p > 2, Barron with alpha > 2).  With several ranks every rank sets the same loss."""
-        h = self._need()
-        if loss is None:
-            loss = Loss(capi.LOSS_NONE)
-        h.check(h.L.apexgpu_set_loss(h.h, int(loss.kind), float(loss.p0), float(loss.p1)))
-
-    def get_loss(self) -> Loss:
-        h = self._need()
-        k = C.c_int(); p = (C.c_double * 2)()
-        h.check(h.L.apexgpu_get_loss(h.h, C.byref(k), C.byref(p)))
-        return Loss(k.value, p[0], p[1])
+        return t1 - t0, t2 - t1
 
     def set_priors(self, pose_priors=None, intr_priors=None):
         """PriorFactor blocks on the cameras, as Problem.add_pose_prior / add_intrinsic_prior list them: (camera, data, huber
@@ -384,23 +370,17 @@ class GpuSchurComplementSolver:
     def prior_residuals(self):
         """Corrected residuals of the prior blocks at the current parameters: ([n_pose][7], [n_intr][3]), the caller's order."""
         h = self._need()
-        rp = np.zeros((getattr(self, "_n_pose_priors", 0), 7)); ri = np.zeros((getattr(self, "_n_intr_priors", 0), 3))
+        rp = np.zeros((self._n_pose_priors, 7)); ri = np.zeros((self._n_intr_priors, 3))
         if len(rp) or len(ri):
             h.check(h.L.apexgpu_get_prior_residual(h.h, capi.ptr(rp) if len(rp) else None, capi.ptr(ri) if len(ri) else None))
         return rp, ri
 
-    def _need(self) -> capi.Handle:
-        if self._h is None:
-            raise capi.LinAlgError(-5, "Block structure not built. Call initialize_structure() first.")
-        return self._h
-
     def set_parameters(self, poses, intr, points):
-        import time
         t0 = time.perf_counter()
         h = self._need()
         a = [np.ascontiguousarray(x, dtype=np.float64) for x in (poses, intr, points)]
         h.check(h.L.apexgpu_set_params(h.h, *[capi.ptr(x) for x in a]))
-        if hasattr(self, "setup_wall"): self.setup_wall["set_parameters"] = time.perf_counter() - t0
+        self.setup_wall["set_parameters"] = time.perf_counter() - t0
 
     def get_parameters(self):
         h = self._need()
@@ -408,71 +388,20 @@ class GpuSchurComplementSolver:
         h.check(h.L.apexgpu_get_params(h.h, capi.ptr(poses), capi.ptr(intr), capi.ptr(pts)))
         return poses, intr, pts
 
-    def compute_cost(self) -> float:
-        h = self._need(); c = C.c_double()
-        h.check(h.L.apexgpu_cost(h.h, C.byref(c)))
-        return c.value
-
     def assemble(self, lam: float):
         """A1-A11 only: S, g_red, H_ll^-1, g on the device at the current parameters."""
         h = self._need()
         h.check(h.L.apexgpu_assemble(h.h, float(lam)))
 
-    # LinearSolver::solve_augmented_equation / solve_normal_equation
+    # LinearSolver::solve_augmented_equation
     def solve_augmented_equation(self, lam: float, want_step: bool = True):
         h = self._need()
-        n = self._problem.total_dof
+        n = self._total_dof()
         step = np.zeros(n) if want_step else None
         grad = np.zeros(n) if want_step else None
         h.check(h.L.apexgpu_solve_augmented(h.h, float(lam), self.variant.value, capi.ptr(step), capi.ptr(grad)))
         self._gradient = grad
         return step
-
-    def solve_normal_equation(self):
-        return self.solve_augmented_equation(0.0)
-
-    def get_gradient(self):
-        """+J^T r of the last solve (explicit_schur.rs:1240-1242); None before any solve."""
-        return self._gradient
-
-    # AssemblyBackend::compute_column_norms / apply_column_scaling / apply_inverse_scaling (linearizer/mod.rs:229-262)
-    def compute_column_norms(self) -> np.ndarray:
-        h = self._need()
-        n = np.zeros(self._problem.total_dof)
-        h.check(h.L.apexgpu_column_norms(h.h, capi.ptr(n)))
-        return n
-
-    def apply_column_scaling(self, scaling):
-        """J -> J diag(scaling) for the following solves (None: off).  solve_augmented_equation then returns the
-        scaled step and get_gradient the scaled gradient, like the reference's solver fed with the scaled Jacobian."""
-        h = self._need()
-        a = None if scaling is None else np.ascontiguousarray(scaling, dtype=np.float64)
-        if a is not None and a.shape != (self._problem.total_dof,):
-            raise ValueError("scaling must have total_dof entries")
-        h.check(h.L.apexgpu_set_column_scaling(h.h, capi.ptr(a)))
-        self._scaling = a
-
-    def apply_inverse_scaling(self, step):
-        s = getattr(self, "_scaling", None)
-        return step if s is None else step * s
-
-    def step_stats(self):
-        h = self._need(); out = (C.c_double * 3)()
-        h.check(h.L.apexgpu_step_stats(h.h, C.byref(out)))
-        return tuple(out)
-
-    def eval_step(self) -> float:
-        h = self._need(); c = C.c_double()
-        h.check(h.L.apexgpu_eval_step(h.h, C.byref(c)))
-        return c.value
-
-    def commit_step(self): h = self._need(); h.check(h.L.apexgpu_commit_step(h.h))
-    def discard_step(self): h = self._need(); h.check(h.L.apexgpu_discard_step(h.h))
-
-    def parameter_norm(self) -> float:
-        h = self._need(); c = C.c_double()
-        h.check(h.L.apexgpu_parameter_norm(h.h, C.byref(c)))
-        return c.value
 
     # parity / debug
     def get_residual(self):
@@ -544,10 +473,6 @@ class GpuSchurComplementSolver:
             out.update(landmark_covariance_dict(self.landmark_covariance_blocks()))
         return out
 
-    def covariance_stats(self, group_cap: int = 0) -> dict:
-        h = self._need()
-        return _covariance_stats(h, h.L.apexgpu_covariance_stats, group_cap)
-
     def landmark_covariance_stats(self) -> dict:
         h = self._need()
         out = (C.c_double * 4)()
@@ -582,21 +507,12 @@ class GpuSchurComplementSolver:
                     predicted_direct_ms=float(c[0]), predicted_matrix_free_ms=float(c[1]),
                     variant_choice=("direct", "matrix-free by predicted cost", "matrix-free: plan refused", "matrix-free by option")[int(c[2])])
 
-    def counters(self) -> dict:
-        """Events of this handle's life: dataflow triangular sweeps that timed out and were repeated level by level."""
-        h = self._need(); out = (C.c_int64 * 4)()
-        h.check(h.L.apexgpu_counters(h.h, C.byref(out)))
-        return dict(sweep_timeouts=int(out[0]), tri_dataflow=bool(out[1]), factor_flow_timeouts=int(out[2]), factor_flow_groups=int(out[3]))
-
     def setup_times(self) -> dict:
         """Wall time of initialize_structure by phase (seconds) and the counts that go with it."""
         h = self._need(); sec = (C.c_double * 6)(); cnt = (C.c_double * 4)()
         h.check(h.L.apexgpu_setup_times(h.h, C.byref(sec), C.byref(cnt)))
         return dict(order=sec[0], lists=sec[1], tile_plan=sec[2], schur_lists=sec[3], uploads=sec[4], total=sec[5],
                     hub_cameras=int(cnt[0]), pair_blocks=int(cnt[1]), pair_slots=int(cnt[2]), schur_form=int(cnt[3]))
-
-    def set_option(self, name: str, value: int):
-        h = self._need(); h.check(h.L.apexgpu_set_option(h.h, name.encode(), int(value)))
 
     def pair_records(self) -> np.ndarray:
         """Tests: the records of the sorted pair list as they sit on the device, (slots, 4) uint32 = (i, j, landmark, queue)."""
@@ -634,66 +550,8 @@ class GpuSchurComplementSolver:
                     raise capi.LinAlgError(rc, msg.decode())
             raise capi.LinAlgError(rc, "lockstep solve")
 
-    def enable_stage_timing(self, on=True): h = self._need(); h.check(h.L.apexgpu_enable_stage_timing(h.h, int(on)))
-    def reset_stage_times(self): h = self._need(); h.check(h.L.apexgpu_reset_stage_times(h.h))
-
-    def stage_times(self) -> dict:
-        h = self._need()
-        ms = (C.c_double * capi.NUM_STAGES)(); n = (C.c_int64 * capi.NUM_STAGES)()
-        h.check(h.L.apexgpu_stage_times(h.h, C.byref(ms), C.byref(n)))
-        return {name: (ms[i], n[i]) for i, name in enumerate(capi.STAGE_NAMES)}
-
     def lm_optimize(self, cfg: LevenbergMarquardtConfig):
-        h = self._need()
-        c = cfg.to_c()
-        c.variant = self.variant.value
-        res = capi.LmResultC()
-        cap = cfg.max_iterations + 2
-        hist = (capi.LmIterC * cap)()
-        h.check(h.L.apexgpu_lm_optimize(h.h, C.byref(c), C.byref(res), C.cast(hist, C.c_void_p), cap))
-        n = res.iterations
-        H = np.array([[getattr(hist[i], f) for f, _ in capi.LmIterC._fields_] for i in range(min(n, cap))])
-        return res, H.reshape(-1, 8), c
-
-    # ---- Dog-Leg (dog_leg.rs): mirrors of GpuSparseCholeskySolver's three calls ----
-    def dogleg_optimize(self, cfg: DogLegConfig):
-        """DogLeg::optimize (dog_leg.rs:1143-1354) on the device: (result, history (n, 12) in DlIterC's columns, the config as
-        the loop left it -- trust_region_radius and mu hold their final values).  LinAlgError: InvalidInput for cfg.variant != 0,
-        InvalidState on a matrix-free or a sharded handle."""
-        h = self._need()
-        c = cfg.to_c()
-        res = capi.LmResultC()
-        cap = cfg.max_iterations + 2
-        hist = (capi.DlIterC * cap)()
-        h.check(h.L.apexgpu_dogleg_optimize(h.h, C.byref(c), C.byref(res), C.cast(hist, C.c_void_p), cap))
-        H = np.array([[getattr(hist[i], f) for f, _ in capi.DlIterC._fields_] for i in range(min(res.iterations, cap))])
-        return res, H.reshape(-1, 12), c
-
-    def dogleg_step(self, mu: float, radius: float, reuse: bool = False) -> dict:
-        """One Dog-Leg step and its trial point at the current parameters; eval_step / commit_step / discard_step follow.
-        reuse: rebuild the step from the cached solve at the new radius (no assembly, factorisation, sweeps or
-        back-substitution).  A failed factorisation raises FactorizationFailed / SingularMatrix without the ladder."""
-        h = self._need()
-        o = (C.c_double * 8)()
-        h.check(h.L.apexgpu_dogleg_step(h.h, float(mu), float(radius), 1 if reuse else 0, C.byref(o)))
-        return dict(gradient_norm=o[0], step_norm=o[1], predicted_reduction=o[2], step_type=int(o[3]), alpha=o[4], beta=o[5],
-                    scaled_step_norm=o[6], reused=bool(o[7]))
-
-    def jv_gram(self, a, b):
-        """(|J a|^2, (J a).(J b), |J b|^2) at the current parameters, matrix-free; a, b in the global column order."""
-        h = self._need()
-        n = self._problem.total_dof
-        a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
-        if a.shape != (n,) or b.shape != (n,):
-            raise ValueError("a and b must have total_dof entries")
-        o = (C.c_double * 3)()
-        h.check(h.L.apexgpu_jv_gram(h.h, capi.ptr(a), capi.ptr(b), C.byref(o)))
-        return o[0], o[1], o[2]
-
-    def close(self):
-        if self._h is not None:
-            self._h.close()
-            self._h = None
+        return super().lm_optimize(cfg)
 
 
 def camera_covariance_dict(blocks: np.ndarray) -> dict:
@@ -708,14 +566,6 @@ def camera_covariance_dict(blocks: np.ndarray) -> dict:
 def landmark_covariance_dict(blocks: np.ndarray) -> dict:
     """(n_pt, 3, 3) landmark blocks -> {"pt_{l:05}": 3 x 3} (the reference's landmark names)."""
     return {f"pt_{l:05}": b.copy() for l, b in enumerate(blocks)}
-
-
-def _covariance_stats(h, fn, group_cap: int) -> dict:
-    out = (C.c_double * 6)()
-    ms = np.zeros(max(int(group_cap), 1))
-    h.check(fn(h.h, C.byref(out), capi.ptr(ms), int(group_cap)))
-    return dict(extra_bytes=int(out[0]), y_products=int(out[1]), zoff_products=int(out[2]), zdiag_products=int(out[3]),
-                level_groups=int(out[4]), group_ms=ms[:int(out[5])].tolist())
 
 
 def _covariances_or_none(s, landmarks: bool = False):
@@ -752,6 +602,15 @@ class SolverResult:
     covariances: dict | None = None  # mod.rs:265-272: per variable, when config.compute_covariances
 
 
+def _result(cls, res: capi.LmResultC, history: np.ndarray, parameters: tuple, **own):
+    """The SolverResult (cls: or DogLegResult) of one optimiser loop of the library; own: the fields beyond the loop's result."""
+    return cls(status=OptimizationStatus(res.status), iterations=res.iterations, initial_cost=res.initial_cost,
+               final_cost=res.final_cost, parameters=parameters, elapsed_time=res.elapsed_s,
+               final_gradient_norm=res.final_gradient_norm, final_parameter_update_norm=res.final_step_norm,
+               cost_evaluations=res.cost_evaluations, jacobian_evaluations=res.jacobian_evaluations,
+               successful_steps=res.successful_steps, unsuccessful_steps=res.unsuccessful_steps, history=history, **own)
+
+
 class LevenbergMarquardt:
     def __init__(self, config: LevenbergMarquardtConfig | None = None, device: int = 0):
         self.config = config or LevenbergMarquardtConfig()
@@ -768,7 +627,6 @@ class LevenbergMarquardt:
         """LevenbergMarquardt::optimize (:1034-1083): the GpuSchurComplement arm builds the solver,
         initialises its structure, uploads the initial values and runs the loop on the device."""
         t = self.config.linear_solver_type
-        from .pose_graph import GpuSparseCholeskySolver, PoseGraphProblem
         if isinstance(problem, PoseGraphProblem):
             # the SparseCholesky arm (levenberg_marquardt.rs:1055-1062) on the device
             if t not in (LinearSolverType.GpuSparseCholesky, LinearSolverType.SparseCholesky):
@@ -780,13 +638,7 @@ class LevenbergMarquardt:
             self.linear_solver = s
             res, hist, c = s.lm_optimize(self.config)
             cov = _covariances_or_none(s) if self.config.compute_covariances else None
-            return SolverResult(
-                status=OptimizationStatus(res.status), iterations=res.iterations, initial_cost=res.initial_cost,
-                final_cost=res.final_cost, parameters=(s.get_parameters(),), elapsed_time=res.elapsed_s,
-                final_gradient_norm=res.final_gradient_norm, final_parameter_update_norm=res.final_step_norm,
-                cost_evaluations=res.cost_evaluations, jacobian_evaluations=res.jacobian_evaluations,
-                successful_steps=res.successful_steps, unsuccessful_steps=res.unsuccessful_steps, history=hist,
-                final_damping=c.damping, covariances=cov)
+            return _result(SolverResult, res, hist, (s.get_parameters(),), final_damping=c.damping, covariances=cov)
         if t not in (LinearSolverType.GpuSchurComplement, LinearSolverType.SparseSchurComplement):
             raise NotImplementedError(f"{t} is a CPU solver of the reference; this backend provides GpuSchurComplement")
         d = problem.data
@@ -803,13 +655,7 @@ class LevenbergMarquardt:
         res, hist, c = s.lm_optimize(self.config)
         cov = (_covariances_or_none(s, self.config.compute_landmark_covariances) if self.config.compute_covariances
                else None)
-        return SolverResult(
-            status=OptimizationStatus(res.status), iterations=res.iterations, initial_cost=res.initial_cost,
-            final_cost=res.final_cost, parameters=s.get_parameters(), elapsed_time=res.elapsed_s,
-            final_gradient_norm=res.final_gradient_norm, final_parameter_update_norm=res.final_step_norm,
-            cost_evaluations=res.cost_evaluations, jacobian_evaluations=res.jacobian_evaluations,
-            successful_steps=res.successful_steps, unsuccessful_steps=res.unsuccessful_steps, history=hist,
-            final_damping=c.damping, covariances=cov)
+        return _result(SolverResult, res, hist, s.get_parameters(), final_damping=c.damping, covariances=cov)
 
 
 @dataclass
@@ -846,10 +692,4 @@ class DogLeg:
         s.set_parameters(*(initial_values if initial_values is not None else (d.poses, d.intr, d.points)))
         self.linear_solver = s
         res, hist, c = s.dogleg_optimize(self.config)
-        return DogLegResult(
-            status=OptimizationStatus(res.status), iterations=res.iterations, initial_cost=res.initial_cost,
-            final_cost=res.final_cost, parameters=s.get_parameters(), elapsed_time=res.elapsed_s,
-            final_gradient_norm=res.final_gradient_norm, final_parameter_update_norm=res.final_step_norm,
-            cost_evaluations=res.cost_evaluations, jacobian_evaluations=res.jacobian_evaluations,
-            successful_steps=res.successful_steps, unsuccessful_steps=res.unsuccessful_steps, history=hist,
-            final_radius=c.trust_region_radius, final_mu=c.mu)
+        return _result(DogLegResult, res, hist, s.get_parameters(), final_radius=c.trust_region_radius, final_mu=c.mu)
