@@ -139,7 +139,7 @@ API = {
     "apexgpu_enable_stage_timing": (_int, [_vp, _int]),
     "apexgpu_reset_stage_times": (_int, [_vp]),
     "apexgpu_stage_times": (_int, [_vp, _P(_dbl * NUM_STAGES), _P(_i64 * NUM_STAGES)]),
-    "apexgpu_info": (_int, [_vp, _P(_dbl * 16)]),
+    "apexgpu_info": (_int, [_vp, _P(_dbl * 17)]),
     "apexgpu_variant_info": (_int, [_vp, _int, _P(_int), _str, _int]),
     "apexgpu_variant_costs": (_int, [_vp, _P(_dbl * 4)]),
     "apexgpu_counters": (_int, [_vp, _P(_i64 * 4)]),
@@ -222,7 +222,7 @@ API = {
     "apexgpu_pg_enable_stage_timing": (_int, [_vp, _int]),
     "apexgpu_pg_reset_stage_times": (_int, [_vp]),
     "apexgpu_pg_stage_times": (_int, [_vp, _P(_dbl * PG_NUM_STAGES), _P(_i64 * PG_NUM_STAGES)]),
-    "apexgpu_pg_info": (_int, [_vp, _P(_dbl * 8)]),
+    "apexgpu_pg_info": (_int, [_vp, _P(_dbl * 9)]),
     "apexgpu_pg_counters": (_int, [_vp, _P(_i64 * 4)]),
     "apexgpu_g2o_open": (_int, [_str, _P(_vp)]),
     "apexgpu_g2o_close": (None, [_vp]),
@@ -533,7 +533,8 @@ class TileCholesky:
     OPTS = ("graphs", "factor_flow", "factor_flow_rows", "tri_dataflow", "update_overlap", "split_u1", "two_side", "flood_gate")
     DEFAULTS = dict(graphs=1, factor_flow=-1, factor_flow_rows=24, tri_dataflow=1, update_overlap=1, split_u1=4, two_side=1, flood_gate=256)
 
-    def __init__(self, present: np.ndarray, device: int = 0, **opts):
+    def __init__(self, present: np.ndarray, device: int = 0, diag_update_lower: int = 1, **opts):
+        """diag_update_lower 0: the updates of diagonal tiles compute all nine 48 x 48 blocks (bit 1 of opts[0])."""
         unknown = set(opts) - set(self.OPTS)
         if unknown:
             raise ValueError(f"unknown options {sorted(unknown)}")
@@ -543,6 +544,7 @@ class TileCholesky:
         self.nt = int(pr.shape[0])
         o = dict(self.DEFAULTS, **opts)
         ov = np.array([o[k] for k in self.OPTS], dtype=np.int32)
+        ov[0] = (1 if o["graphs"] else 0) | (0 if diag_update_lower else 2)
         rc = self.L.apexgpu_debug_tiles_create(int(device), self.nt, ptr(pr), ptr(ov), C.byref(self.h))
         if rc != 0:
             raise LinAlgError(rc, "apexgpu_debug_tiles_create failed")

@@ -215,7 +215,7 @@ int apexgpu_setup_times(apexgpu_solver* h, double seconds[6], double counts[4]) 
         return APEXGPU_OK;
     });
 }
-int apexgpu_info(apexgpu_solver* h, double info[16]) {
+int apexgpu_info(apexgpu_solver* h, double info[17]) {
     return with_handle(h, [&](auto& s) {
         info[0] = s.n_tile_rows(); info[1] = (double)s.tile_count(); info[2] = s.schur_scatter_pairs();
         info[3] = (double)s.cam_dof_internal(); info[4] = s.last_reg(); info[5] = s.last_pcg_iters();
@@ -227,6 +227,7 @@ int apexgpu_info(apexgpu_solver* h, double info[16]) {
         info[12] = s.dist_top_columns(); info[13] = s.dist_local_fraction();
         info[14] = s.tree_sharded() ? 1.0 : 0.0;
         info[15] = s.schur_form();
+        info[16] = (double)s.plan().n_diag_updates();
         return APEXGPU_OK;
     });
 }

@@ -71,6 +71,7 @@ bool shared_option(S* s, const std::string& n, int value) {
     else if (n == "split_u1") s->set_split_u1(value);
     else if (n == "flood_gate") s->set_gate_min(value);
     else if (n == "two_side") s->set_two_side(value);
+    else if (n == "diag_update_lower") s->set_diag_lower(value != 0);
     else if (n == "eager_step_eval") s->set_eager_step_eval(value != 0);
     else if (n == "one_wait") s->set_one_wait(value != 0);
     else if (n == "factor_flow") s->set_factor_flow(value, 0);          // max columns per level group inside the dataflow launch (0: off)

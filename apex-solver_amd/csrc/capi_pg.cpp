@@ -157,13 +157,14 @@ int apexgpu_pg_stage_times(apexgpu_pg_solver* h, double ms[APEXGPU_PG_NUM_STAGES
     });
 }
 int apexgpu_pg_counters(apexgpu_pg_solver* h, int64_t out[4]) { return with_handle(h, [&](auto& s) { return counters(&s, out); }); }
-int apexgpu_pg_info(apexgpu_pg_solver* h, double info[8]) {
+int apexgpu_pg_info(apexgpu_pg_solver* h, double info[9]) {
     return with_handle(h, [&](auto& s) {
         info[0] = s.n_tile_rows(); info[1] = (double)s.tile_count(); info[2] = (double)s.touched_tiles();
         info[3] = s.n_levels(); info[4] = (double)s.dof() * (double)s.n_vertices();
         int64_t a = 0, b = 0, c = 0;
         s.plan().op_counts(&a, &b, &c);
         info[5] = (double)a; info[6] = (double)b; info[7] = (double)c;
+        info[8] = (double)s.plan().n_diag_updates();
         return APEXGPU_OK;
     });
 }

@@ -12,11 +12,13 @@ void launch_potrf_inv(const PotrfTask* tasks, int n, int* fail, hipStream_t s, i
 void launch_gate(const int* arrived, int expected, int max_micros, hipStream_t s);
 // the dataflow factorisation: one workgroup per unit, dispatched in list order; ver[] must be zero; err: error word (time-out)
 void launch_factor_flow(const FactorUnit* units, int n_units, int* ver, int* fail, int* err, hipStream_t s,
-                        unsigned long long* trace = nullptr);
+                        unsigned long long* trace = nullptr, bool diag_lower = false);
 // batches of <= 56 tasks use the latency kernels, larger ones the four-wave strip kernel (three workgroups per tile)
 // tri_b: every B is a lower-triangular inverse written by launch_potrf_inv (zero 16 x 16 blocks right of the diagonal): the
 // large-batch kernel then skips the 36 of 81 block products that multiply by them.
-void launch_tile_gemm_nt(const GemmTask* tasks, int n, double alpha, double beta, hipStream_t s, bool tri_b = false);
+// diag_lower (the updates, beta != 0): a task with A == B targets a diagonal tile, of which only the lower triangle is read again;
+// its three 48 x 48 blocks right of the diagonal ones are not computed (in k_factor_flow likewise)
+void launch_tile_gemm_nt(const GemmTask* tasks, int n, double alpha, double beta, hipStream_t s, bool tri_b = false, bool diag_lower = false);
 void launch_clear_i32(int* p, int64_t n, hipStream_t s);                   // a small clear as ONE kernel (chol_kernels.hip)
 void launch_post_word(int* word, int* host_word_dev, hipStream_t s);       // *host = *word, *word = 0 when *word != 0
 // poison_block >= 0 (tests only): that block's counter is made unreachable after the flags are cleared, so the task that

@@ -458,8 +458,80 @@ constexpr int kGemmSmallMax = 56;  // batches of at most this many tasks use the
 // {8, 1} {7, 2} {6, 3} {5, 4, 0} = 11 / 11 / 11 / 12 chunk products per block row.  Skipping a product with an exact-zero factor
 // changes no finite value.
 // ------------------------------------------------------------------------------------------
+// DIAGONAL TARGETS ("diag_lower"): C_II -= L_IK L_IK^T, A and B the same tile, C symmetric, and only the lower triangle of a
+// diagonal tile is ever read again (potrf_tile_mf loads the 45 lower 16 x 16 blocks).  The 48 x 48 blocks right of the diagonal
+// 48 x 48 blocks are not computed: strip s needs the block columns 0 .. 3 s + 2 only, 9 / 18 / 27 blocks, and the saving is real
+// only when those are DEALT AGAIN over the four waves -- masking the deal above would leave wave 0 its six blocks in strip 0.
+// Strip 0: 3 / 2 / 2 / 2, strip 1: 5 / 5 / 4 / 4 (block n = 3 * column + row, a wave takes a run of n), strip 2 runs the body
+// above as it is (7 / 7 / 7 / 6): 3 + 5 + 7 = 15 block steps per tile instead of 21.  The A strip is rows 48 s .. 48 s + 47 of
+// the same tile, so ONE image of the rows 0 .. 48 (s + 1) - 1 serves both operands: 48 / 96 staged rows per chunk instead of 192.
+// Every computed element sums the same products in the same order as above: same bits.
+template <int DS>
+__device__ __forceinline__ void gemm_diag_strip(const GemmTask& tg, double alpha, double beta, double* __restrict__ sm) {
+    static_assert(DS == 0 || DS == 1, "strip 2 of a diagonal target is the general body");
+    constexpr int P4 = KC + 2;
+    constexpr int ROWS = STRIP * (DS + 1);   // operand rows of this strip: B rows 0 .. ROWS - 1, the last 48 of them the A strip
+    constexpr int NACC = DS == 0 ? 3 : 5;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lr = lane & 15, lk = lane >> 4;
+    const int start = DS == 0 ? (w == 0 ? 0 : 1 + 2 * w) : (w < 2 ? 5 * w : 2 + 4 * w);
+    const int cnt = DS == 0 ? (w == 0 ? 3 : 2) : (w < 2 ? 5 : 4);
+    constexpr int C2 = KC / 2, RPR = 256 / C2, NRD = (ROWS + RPR - 1) / RPR;   // rounds of 32 rows x 8 double2: two (the second half used) / three
+    const int r0 = tid / C2, c2 = tid % C2;
+    const bool last_on = ROWS % RPR == 0 || r0 < ROWS % RPR;   // (wave-uniform: a wave stages eight rows per round)
+    GlobalCF64 Bg = (GlobalCF64)tg.B;
+    const unsigned offB = r0 * NB + 2 * c2;
+    const int dst0 = r0 * P4 + 2 * c2;
+    f64x2_t rg[NRD];
+    auto gload = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < NRD; ++i)
+            if (i + 1 < NRD || last_on) rg[i] = *reinterpret_cast<GlobalCF64x2>(Bg + (offB + (unsigned)(RPR * i * NB + k0)));
+    };
+    int oa[NACC], ob[NACC], oc[NACC];
+    double4_t acc[NACC];
+#pragma unroll
+    for (int q = 0; q < NACC; ++q) {
+        const int n = start + (q < cnt ? q : cnt - 1), br = n % 3, bc = n / 3;
+        oa[q] = (STRIP * DS + 16 * br + lr) * P4 + lk;
+        ob[q] = (16 * bc + lr) * P4 + lk;
+        oc[q] = (16 * br + lk) * NB + 16 * bc + lr;
+        acc[q] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    }
+    gload(0);
+    for (int k0 = 0; k0 < NB; k0 += KC) {
+        __syncthreads();  // previous chunk fully consumed
+#pragma unroll
+        for (int i = 0; i < NRD; ++i)
+            if (i + 1 < NRD || last_on) { sm[dst0 + RPR * i * P4] = rg[i].x; sm[dst0 + RPR * i * P4 + 1] = rg[i].y; }
+        __syncthreads();
+        if (k0 + KC < NB) gload(k0 + KC);
+#pragma unroll
+        for (int kk = 0; kk < KC; kk += 4) {
+#pragma unroll
+            for (int q = 0; q < NACC; ++q)
+                if (q < cnt) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(sm[oa[q] + kk], sm[ob[q] + kk], acc[q], 0, 0, 0);
+        }
+    }
+    GlobalF64 C = (GlobalF64)tg.C + (size_t)DS * STRIP * NB;
+    double cv[NACC][4];
+#pragma unroll
+    for (int q = 0; q < NACC; ++q)
+        if (q < cnt) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) cv[q][r] = C[oc[q] + 4 * r * NB];
+        }
+#pragma unroll
+    for (int q = 0; q < NACC; ++q)
+        if (q < cnt) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) C[oc[q] + 4 * r * NB] = alpha * acc[q][r] + beta * cv[q][r];
+        }
+}
+
 template <bool TRI>
-__global__ __launch_bounds__(256, 3) void k_tile_gemm_nt(const GemmTask* __restrict__ tasks, int n_units, double alpha, double beta) {
+__global__ __launch_bounds__(256, 3) void k_tile_gemm_nt(const GemmTask* __restrict__ tasks, int n_units, double alpha, double beta,
+                                                          int diag_lower) {
     constexpr int P4 = KC + 2;
     constexpr int IMG = (NB + STRIP) * P4;
     __shared__ double sm[IMG];
@@ -476,6 +548,13 @@ __global__ __launch_bounds__(256, 3) void k_tile_gemm_nt(const GemmTask* __restr
     const bool first = (reinterpret_cast<uintptr_t>(tg.C) & 1) != 0;
     tg.C = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(tg.C) & ~uintptr_t(7));
     const int strip = unit % NSTRIP;
+    if constexpr (!TRI) {   // a diagonal target (gemm_diag_strip above); workgroup-uniform: the task record and the block index
+        if (diag_lower && !first && beta != 0.0 && tg.A == tg.B && strip < 2) {
+            if (strip == 0) gemm_diag_strip<0>(tg, alpha, beta, sm);
+            else gemm_diag_strip<1>(tg, alpha, beta, sm);
+            return;
+        }
+    }
     // The task's pointers are loaded from memory, so the compiler only knows them as generic (flat) addresses; flat loads count
     // on lgkmcnt as well as vmcnt, which makes every wait for an LDS read also wait for the global prefetch of the next chunk.
     // Re-typed as global (address space 1) they become global_load / global_store and the prefetch stays asynchronous.
@@ -608,7 +687,7 @@ __global__ __launch_bounds__(256, 3) void k_tile_gemm_nt(const GemmTask* __restr
 // ~18 us; it moves 1 MB through L2 per task instead of 0.66 MB, which is irrelevant at these batch sizes.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(192) void k_tile_gemm_nt_small(const GemmTask* __restrict__ tasks, int n_units, double alpha,
-                                                              double beta) {
+                                                              double beta, int diag_lower) {
     __shared__ double sA[48 * PS];
     __shared__ double sB[48 * PS];
     const int unit = blockIdx.x;
@@ -618,6 +697,7 @@ __global__ __launch_bounds__(192) void k_tile_gemm_nt_small(const GemmTask* __re
     tg.C = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(tg.C) & ~uintptr_t(7));
     if (first) beta = 0.0;
     const int blk = unit % 9, bi = blk / 3, bj = blk % 3;
+    if (diag_lower && tg.A == tg.B && bj > bi) return;   // a diagonal target's block right of the diagonal: never read again (k_tile_gemm_nt)
     GlobalCF64 Ag = (GlobalCF64)tg.A + (size_t)bi * 48 * NB;
     GlobalCF64 Bg = (GlobalCF64)tg.B + (size_t)bj * 48 * NB;
     GlobalF64 C = (GlobalF64)tg.C + (size_t)bi * 48 * NB + bj * 48;
@@ -1153,7 +1233,8 @@ constexpr int kFlowFactorThreadsC = 768;   // (= kFlowFactorThreads, needed by t
 // 36 MFMAs per wave, summed over k in the order of the level kernels (k ascending, four per instruction): same bits.
 constexpr int kFlowPK = NB + 2;   // LDS pitch of a full-K operand row: 292 dwords = 36 mod 64 -> conflict-free b64 operand reads
 __device__ __forceinline__ void flow_update_unit(const FactorUnit& u, double* __restrict__ sA, double* __restrict__ sB,
-                                                 int* __restrict__ ver, int* __restrict__ err, unsigned long long* __restrict__ trace) {
+                                                 int* __restrict__ ver, int* __restrict__ err, unsigned long long* __restrict__ trace,
+                                                 int diag_lower) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int lr = lane & 15, lk = lane >> 4;
     const int wr = w / 3, wc = w % 3;
@@ -1161,7 +1242,10 @@ __device__ __forceinline__ void flow_update_unit(const FactorUnit& u, double* __
     const __amdgpu_buffer_rsrc_t rC = coh_rsrc(u.C), rA = coh_rsrc(u.A), rB = coh_rsrc(u.B);
     flow_wait_unit(ver, u, tid, err);   // the previous writer of the target is done, both operands are final
     if (trace && tid == 0) trace[1] = wall_clock64();
-    const bool act = tid < 576;   // (the workgroup has 12 waves for the potrf units' sake: nine of them work here)
+    // A block right of the diagonal of a DIAGONAL target (A == B) is never read again (k_tile_gemm_nt, "diag_lower"): the unit keeps
+    // its place in the protocol -- the wait above, the publish below -- and does nothing in between
+    const bool skip = diag_lower && u.A == u.B && bj > bi;
+    const bool act = tid < 576 && !skip;   // (the workgroup has 12 waves for the potrf units' sake: nine of them work here)
     double cv[4] = {0.0, 0.0, 0.0, 0.0};   // the old values of the block: requested with the operands, consumed last
     if (act && !(u.kind & kFlowFirstWriter)) {   // (the first writer of a fill tile: nothing there yet, nothing read)
 #pragma unroll
@@ -1262,14 +1346,26 @@ __device__ __forceinline__ void flow_solve_unit(const FactorUnit& u, double* __r
 // block (k ascending, four per instruction) and the same epilogue expression as the 48 x 48 units and the level kernels: the
 // factor is bit-identical.  Publishes all nine counts of a writer at once.
 __device__ __forceinline__ void flow_update_tile_unit(const FactorUnit& u, double* __restrict__ sA, double* __restrict__ sB,
-                                                      int* __restrict__ ver, int* __restrict__ err, unsigned long long* __restrict__ trace) {
+                                                      int* __restrict__ ver, int* __restrict__ err, unsigned long long* __restrict__ trace,
+                                                      int diag_lower) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int lr = lane & 15, lk = lane >> 4;
     const __amdgpu_buffer_rsrc_t rC = coh_rsrc(u.C), rA = coh_rsrc(u.A), rB = coh_rsrc(u.B);
     flow_wait_unit(ver, u, tid, err);   // the previous writer of the target is done, both operands are final
     if (trace && tid == 0) trace[1] = wall_clock64();
     constexpr int NBW = 7;                                     // blocks per wave (waves 9..11: six)
-    const int nb = w < 9 ? 7 : 6, b0 = w < 9 ? 7 * w : 63 + 6 * (w - 9);
+    // A DIAGONAL target (A == B, "diag_lower": k_tile_gemm_nt): the 54 blocks of the six 48 x 48 blocks on and left of the diagonal
+    // only, numbered row by row (block rows 0..2: 3 columns each, 3..5: 6, 6..8: 9) and dealt 5 / 4 per wave; all nine published
+    const bool diag = diag_lower && u.A == u.B;
+    const int nb = diag ? (w < 6 ? 5 : 4) : (w < 9 ? 7 : 6);
+    const int b0 = diag ? (w < 6 ? 5 * w : 30 + 4 * (w - 6)) : (w < 9 ? 7 * w : 63 + 6 * (w - 9));
+    const int b_last = diag ? 53 : 80;
+    auto block_at = [&](int b, int& br, int& bc) {   // block number -> block row, block column
+        if (!diag) { br = b / 9; bc = b - 9 * br; }
+        else if (b < 9) { br = b / 3; bc = b - 3 * br; }
+        else if (b < 27) { br = 3 + (b - 9) / 6; bc = (b - 9) % 6; }
+        else { br = 6 + (b - 27) / 9; bc = (b - 27) % 9; }
+    };
     constexpr int C2 = KS / 2, NCH = NB / KS;                  // 24 double2 per row and chunk, 3 chunks
     constexpr int NLD = (NB * C2 + kFlowFactorThreadsC - 1) / kFlowFactorThreadsC;   // 3456 double2 per operand and chunk over 768 threads: 5 rounds, the last half empty
     double2 ra[NLD], rb[NLD];
@@ -1303,7 +1399,8 @@ __device__ __forceinline__ void flow_update_tile_unit(const FactorUnit& u, doubl
             const bool first = (u.kind & kFlowFirstWriter) != 0;   // (the first writer of a fill tile: nothing there yet)
 #pragma unroll
             for (int q = 0; q < NBW; ++q) {
-                const int b = min(b0 + q, 80), br = b / 9, bc = b - 9 * br;
+                int br, bc;
+                block_at(min(b0 + q, b_last), br, bc);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) cv[q][r] = first ? 0.0 : coh_ld1(rC, (16 * br + lk + 4 * r) * NB + 16 * bc + lr);
             }
@@ -1312,7 +1409,8 @@ __device__ __forceinline__ void flow_update_tile_unit(const FactorUnit& u, doubl
 #pragma unroll
         for (int q = 0; q < NBW; ++q) {
             if (q < nb) {
-                const int b = b0 + q, br = b / 9, bc = b - 9 * br;
+                int br, bc;
+                block_at(b0 + q, br, bc);
                 const double* pa = sA + (16 * br + lr) * PS + lk;
                 const double* pb = sB + (16 * bc + lr) * PS + lk;
 #pragma unroll
@@ -1323,7 +1421,8 @@ __device__ __forceinline__ void flow_update_tile_unit(const FactorUnit& u, doubl
 #pragma unroll
     for (int q = 0; q < NBW; ++q) {
         if (q < nb) {
-            const int b = b0 + q, br = b / 9, bc = b - 9 * br;
+            int br, bc;
+            block_at(b0 + q, br, bc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) coh_st1(rC, (16 * br + lk + 4 * r) * NB + 16 * bc + lr, -1.0 * acc[q][r] + 1.0 * cv[q][r]);
         }
@@ -1336,7 +1435,7 @@ __device__ __forceinline__ void flow_update_tile_unit(const FactorUnit& u, doubl
 constexpr int kFlowFactorThreads = 768;   // 12 waves: the potrf units' 9 helper waves (+ wave 0 and two idle ones on its SIMD); products use 9
 __global__ __launch_bounds__(kFlowFactorThreads) void k_factor_flow(const FactorUnit* __restrict__ units, int* __restrict__ ver,
                                                                      int* __restrict__ fail, int* __restrict__ err,
-                                                                     unsigned long long* __restrict__ trace) {
+                                                                     unsigned long long* __restrict__ trace, int diag_lower) {
     __shared__ double smem[(NLB + NBK) * BSZ];   // potrf: the tile's 45 lower blocks + 9 inverted diagonal blocks; product: sA | sB
     __shared__ int bad, sync_cnt;
     static_assert((16 + NB) * PS <= (NLB + NBK) * BSZ && 2 * 48 * kFlowPK <= (NLB + NBK) * BSZ && 2 * NB * PS <= (NLB + NBK) * BSZ, "the products' staging areas fit in the potrf's");
@@ -1358,9 +1457,9 @@ __global__ __launch_bounds__(kFlowFactorThreads) void k_factor_flow(const Factor
     } else if (kind == 1) {
         flow_solve_unit(u, smem, smem + 16 * PS, ver, err, trace);
     } else if (kind == 3) {
-        flow_update_tile_unit(u, smem, smem + NB * PS, ver, err, trace);
+        flow_update_tile_unit(u, smem, smem + NB * PS, ver, err, trace, diag_lower);
     } else {
-        flow_update_unit(u, smem, smem + 48 * kFlowPK, ver, err, trace);
+        flow_update_unit(u, smem, smem + 48 * kFlowPK, ver, err, trace, diag_lower);
     }
     if (trace && tid == 0) trace[2] = wall_clock64();
 }
@@ -1424,24 +1523,26 @@ __global__ __launch_bounds__(64) void k_gate(const int* __restrict__ arrived, in
 void launch_gate(const int* arrived, int expected, int max_micros, hipStream_t s) {
     hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, s, arrived, expected, (long long)max_micros * 100);
 }
-void launch_factor_flow(const FactorUnit* units, int n_units, int* ver, int* fail, int* err, hipStream_t s, unsigned long long* trace) {
+void launch_factor_flow(const FactorUnit* units, int n_units, int* ver, int* fail, int* err, hipStream_t s, unsigned long long* trace,
+                        bool diag_lower) {
     if (n_units <= 0) return;
-    hipLaunchKernelGGL(k_factor_flow, dim3(n_units), dim3(kFlowFactorThreads), 0, s, units, ver, fail, err, trace);
+    hipLaunchKernelGGL(k_factor_flow, dim3(n_units), dim3(kFlowFactorThreads), 0, s, units, ver, fail, err, trace, diag_lower ? 1 : 0);
 }
 void launch_potrf_inv(const PotrfTask* tasks, int n, int* fail, hipStream_t s, int* arrived) {
     if (n <= 0) return;
     hipLaunchKernelGGL(k_potrf_inv_mf<12>, dim3(n), dim3(768), 0, s, tasks, fail, arrived);
 }
-void launch_tile_gemm_nt(const GemmTask* tasks, int n, double alpha, double beta, hipStream_t s, bool tri_b) {
+void launch_tile_gemm_nt(const GemmTask* tasks, int n, double alpha, double beta, hipStream_t s, bool tri_b, bool diag_lower) {
     if (n <= 0) return;
+    const int dl = diag_lower && !tri_b && beta != 0.0 ? 1 : 0;   // (the updates only: a panel solve's target is never diagonal)
     if (n <= kGemmSmallMax) {  // latency kernels; the 9-workgroup form never for the in-place panel solves (C aliases A)
-        if (beta != 0.0) hipLaunchKernelGGL(k_tile_gemm_nt_small, dim3(9 * n), dim3(192), 0, s, tasks, 9 * n, alpha, beta);
+        if (beta != 0.0) hipLaunchKernelGGL(k_tile_gemm_nt_small, dim3(9 * n), dim3(192), 0, s, tasks, 9 * n, alpha, beta, dl);
         else hipLaunchKernelGGL(k_tile_gemm_nt_small_strip, dim3(3 * n), dim3(576), 0, s, tasks, 3 * n, alpha, beta);
         return;
     }
     const int units = n * NSTRIP, per_xcd = (units + 7) / 8;
-    if (tri_b) hipLaunchKernelGGL(k_tile_gemm_nt<true>, dim3(8 * per_xcd), dim3(256), 0, s, tasks, units, alpha, beta);
-    else hipLaunchKernelGGL(k_tile_gemm_nt<false>, dim3(8 * per_xcd), dim3(256), 0, s, tasks, units, alpha, beta);
+    if (tri_b) hipLaunchKernelGGL(k_tile_gemm_nt<true>, dim3(8 * per_xcd), dim3(256), 0, s, tasks, units, alpha, beta, 0);
+    else hipLaunchKernelGGL(k_tile_gemm_nt<false>, dim3(8 * per_xcd), dim3(256), 0, s, tasks, units, alpha, beta, dl);
 }
 void launch_tri_step(bool trans, const TriTask* tasks, int n, double* vwork, double* vout, hipStream_t s) {
     if (n <= 0) return;

@@ -801,8 +801,28 @@ std::string build_plan_lists(const PlanStructure& s, const std::vector<uint8_t>&
     // more stream is one more edge per level, 3.1 -> 3.5 ms).
     out->two_side_plan = o.two_side == 2 || (o.two_side == 1 && (int64_t)out->upd.size() >= 256 * (int64_t)s.n_levels());
     const std::string e = flow_regions(s, o.flow_cols, o.flow_rows, tiles, linv, out);
-    if (e.empty()) flag_first_writers(s, tiles, out);
-    return e;
+    if (!e.empty()) return e;
+    flag_first_writers(s, tiles, out);
+    // The updates of diagonal tiles (PlanOptions::diag_lower), counted as they run: the level lists in front of each phase's
+    // dataflow launch, then its units.  A diagonal tile is a tile of S, so none of them may be a first writer.
+    for (int ph = 0; ph < 2; ++ph) {
+        const int g0 = ph == 0 ? 0 : s.n_local_groups;
+        const size_t r0 = (size_t)out->lv[(size_t)g0].upd, r1 = (size_t)out->lv[(size_t)out->flow[ph].g0].upd;
+        for (size_t r = r0; r < r1 && r < out->upd_rounds.size(); ++r)
+            for (int64_t q = out->upd_rounds[r].first; q < out->upd_rounds[r].first + out->upd_rounds[r].second; ++q) {
+                const GemmTask& t = out->upd[(size_t)q];
+                if (t.A != t.B) continue;
+                if (reinterpret_cast<uintptr_t>(t.C) & 1) return "internal error: the first writer of a fill tile targets a diagonal tile";
+                ++out->n_diag_upd[0];
+            }
+    }
+    for (const FactorUnit& u : out->units) {
+        const int kind = u.kind & 15;
+        if ((kind != 2 && kind != 3) || u.A != u.B || (kind == 2 && u.strip != 0)) continue;
+        if (u.kind & kFlowFirstWriter) return "internal error: the first writer of a fill tile targets a diagonal tile";
+        ++out->n_diag_upd[1];
+    }
+    return "";
 }
 
 }  // namespace apex

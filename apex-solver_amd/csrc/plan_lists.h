@@ -29,6 +29,10 @@ struct PlanOptions {
     int flow_cols = -1, flow_rows = 24;   // dataflow launch: trailing groups of at most so many columns / off-diagonal tiles per column; 0 off, < 0 by cost model
     int64_t max_updates = 80000000LL;     // tile products per factorisation a plan may hold (12.7 s at 45 TF/s)
     double cost_limit_ms = 0.0;           // a plan predicted to cost more per solve is refused; <= 0: no limit
+    // Updates of DIAGONAL tiles (A == B) compute the 48 x 48 blocks on and left of the diagonal only (chol_kernels.hip).  Read by
+    // the launches alone (TilePlan::issue): the structure, the lists and the schedule are the same either way
+    // (tests/test_diag_update_lower_host.py)
+    int diag_lower = 1;
 };
 
 using PlanCols = std::vector<std::vector<int>>;
@@ -78,6 +82,9 @@ struct PlanLists {
     // neither cleared before a factorisation nor read by those updates.  first_ok: this plan qualifies (not distributed, has
     // fill tiles, no dataflow launch over shared top groups).
     bool first_ok = false;
+    // updates whose target is a diagonal tile (A == B): [0] in the level lists that run, [1] in the dataflow launches (whole-tile
+    // units once, 48 x 48 units once per tile and writer)
+    int64_t n_diag_upd[2] = {0, 0};
 };
 
 // The switches that shape only the launch sequence: they and a plan's two values make its ScheduleInput.

@@ -41,6 +41,7 @@ class TileBackend : public TrBackend {
     void set_overlap_min(int n) { tp_.set_overlap_min(n); }
     void set_gate_min(int n) { tp_.set_gate_min(n); }
     void set_two_side(int mode) { tp_.set_two_side(mode); }
+    void set_diag_lower(bool on) { tp_.set_diag_lower(on); }
     void set_factor_flow(int max_cols, int max_rows) { tp_.set_factor_flow(max_cols, max_rows); }
     int factor_flow_timeouts() const { return n_factor_flow_timeouts_; }
     // "one_wait": one host wait per direct solve (direct_solve), 0 = the flags are waited for where they are raised.

@@ -37,7 +37,8 @@ int apexgpu_debug_tiles_create(int device, int nt, const uint8_t* present, const
         apex::TileSession& t = *(apex::HandleOwner::solver(h.get()) = new apex::TileSession());
         t.device = device;
         apex::TilePlan& tp = t.plan;
-        tp.enable_graphs(opts[0] != 0);
+        tp.enable_graphs((opts[0] & 1) != 0);
+        tp.set_diag_lower((opts[0] & 2) == 0);
         tp.set_factor_flow(opts[1], opts[2]);
         tp.enable_tri_flow(opts[3] != 0);
         tp.enable_overlap(opts[4] != 0);

@@ -123,6 +123,11 @@ class TilePlan : private TilePlanMemory {
     // level groups inside the dataflow launches THAT RUN: none once a launch has timed out
     int factor_flow_groups() const { return !sw_.flow_on ? 0 : (lists_.flow[0].g1 - lists_.flow[0].g0) + (lists_.flow[1].g1 - lists_.flow[1].g0); }
     int factor_flow_cols() const { return opts_.flow_cols; }
+    // Updates of diagonal tiles compute the 48 x 48 blocks on and left of the diagonal only (default; chol_kernels.hip,
+    // "diag_lower").  Any time: the captured factorisations are dropped.
+    void set_diag_lower(bool on);
+    bool diag_lower() const { return opts_.diag_lower != 0; }
+    int64_t n_diag_updates() const { return lists_.n_diag_upd[0] + (sw_.flow_on ? lists_.n_diag_upd[1] : 0); }   // of the factorisation that runs
     double factor_flow_sim_us() const { return lists_.flow[0].sim_us + lists_.flow[1].sim_us; }
     int factor_flow_units() const { return lists_.flow[0].n + lists_.flow[1].n; }
     // A dataflow factorisation whose waits ran into their spin limit leaves the tiles half updated: factor() reports it here

@@ -163,8 +163,8 @@ void TilePlan::issue(const std::vector<SchedOp>& ops) {
             case kOpLaunch:
                 if (o.list == 0) launch_potrf_inv(potrf_tasks_ + o.first, o.count, flag_, s, o.arrive >= 0 ? gate_cnt_ + o.arrive : nullptr);
                 else if (o.list == 1) launch_tile_gemm_nt(trsm_tasks_ + o.first, o.count, 1.0, 0.0, s, /*tri_b=*/true);
-                else if (o.list == 2) launch_tile_gemm_nt(upd_tasks_ + o.first, o.count, -1.0, 1.0, s);
-                else launch_factor_flow(flow_units_ + o.first, o.count, flow_ver_, flag_, flag_ + 1, s, flow_trace_ ? flow_trace_ + 3 * (size_t)o.first : nullptr);
+                else if (o.list == 2) launch_tile_gemm_nt(upd_tasks_ + o.first, o.count, -1.0, 1.0, s, /*tri_b=*/false, diag_lower());
+                else launch_factor_flow(flow_units_ + o.first, o.count, flow_ver_, flag_, flag_ + 1, s, flow_trace_ ? flow_trace_ + 3 * (size_t)o.first : nullptr, diag_lower());
                 break;
             case kOpRecord: (void)hipEventRecord(ev_[o.event / kLevelEvents][o.event % kLevelEvents], s); break;
             case kOpWait: (void)hipStreamWaitEvent(s, ev_[o.event / kLevelEvents][o.event % kLevelEvents], 0); break;
@@ -269,6 +269,13 @@ void TilePlan::enable_tri_flow(bool on) {
     if (on == tri_flow_) return;
     tri_flow_ = on;
     for (int which : {kGraphSweeps, kGraphDistSolve0, kGraphDistSolve1})   // the captured sweeps change
+        if (graph_exec_[which]) { (void)hipGraphExecDestroy(graph_exec_[which]); graph_exec_[which] = nullptr; }
+}
+
+void TilePlan::set_diag_lower(bool on) {
+    if (on == diag_lower()) return;
+    opts_.diag_lower = on ? 1 : 0;
+    for (int which : {kGraphFactor, kGraphFactorTop})   // the captured launches hold the old value
         if (graph_exec_[which]) { (void)hipGraphExecDestroy(graph_exec_[which]); graph_exec_[which] = nullptr; }
 }
 

@@ -476,10 +476,11 @@ class GpuSparseCholeskySolver(HandleSolver):
 
     def info(self) -> dict:
         h = self._need()
-        a = (C.c_double * 8)()
+        a = (C.c_double * 9)()
         h.check(h.L.apexgpu_pg_info(h.h, C.byref(a)))
         return {"tile_rows": int(a[0]), "tiles": int(a[1]), "touched_tiles": int(a[2]), "etree_levels": int(a[3]),
-                "total_dof": int(a[4]), "n_potrf": int(a[5]), "n_trsm": int(a[6]), "n_update": int(a[7])}
+                "total_dof": int(a[4]), "n_potrf": int(a[5]), "n_trsm": int(a[6]), "n_update": int(a[7]),
+                "n_update_diag": int(a[8])}
 
     def gn_optimize(self, cfg: GaussNewtonConfig):
         """GaussNewton::optimize (gauss_newton.rs:559-720) on the device: (result, history (n, 8) in LmIterC's columns with

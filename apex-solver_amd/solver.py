@@ -486,11 +486,11 @@ class GpuSchurComplementSolver(HandleSolver):
         return hi, gl
 
     def info(self) -> dict:
-        h = self._need(); out = (C.c_double * 16)()
+        h = self._need(); out = (C.c_double * 17)()
         h.check(h.L.apexgpu_info(h.h, C.byref(out)))
         return dict(tile_rows=int(out[0]), tiles=int(out[1]), pair_blocks=float(out[2]), cam_dof=int(out[3]),
                     last_reg=float(out[4]), pcg_iterations=int(out[5]), touched_tiles=int(out[6]), local_obs=int(out[7]), etree_levels=int(out[8]),
-                    n_potrf=int(out[9]), n_trsm=int(out[10]), n_update=int(out[11]),
+                    n_potrf=int(out[9]), n_trsm=int(out[10]), n_update=int(out[11]), n_update_diag=int(out[16]),
                     dist_top_columns=int(out[12]), dist_local_fraction=float(out[13]), tree_sharded=bool(out[14]), schur_form=int(out[15]))
 
     def variant_info(self, asked: "SchurVariant | None" = None) -> dict:

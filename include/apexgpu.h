@@ -320,6 +320,10 @@ int apexgpu_schur_matvec(apexgpu_solver* h, double lambda, const double* x_in, d
  *                     sit on their CUs (a one-lane gate kernel; 0: off)
  *   "two_side" (1)    the bulk updates on two side streams (targets two / three levels up; four and more): 0 off, 1 by plan
  *                     size, 2 always (tests)
+ *   "diag_update_lower" (1)  a trailing update whose target is a DIAGONAL tile (C_II -= L_IK L_IK^T) computes the 48 x 48 blocks
+ *                     on and left of the diagonal only: nothing reads a diagonal tile right of its diagonal 16 x 16 blocks again.
+ *                     The lower triangle of the factor, the step and the cost are bit for bit those of 0 (all nine blocks);
+ *                     may be set at any time (the captured factorisations are dropped)
  *   "matrix_free_only" (0)  the handle will only be asked for variant 2 (IterativeSchurSolver semantics): S is never formed,
  *                     so only its diagonal tiles are allocated and no pair list is built -- set-up and LM iteration are then
  *                     independent of the fill of S; variants 0 / 1 and the exports of S answer APEXGPU_ERR_INVALID_STATE
@@ -390,8 +394,9 @@ int apexgpu_stage_times(apexgpu_solver* h, double ms[APEXGPU_NUM_STAGES], int64_
  * [9..11] = tile operations per factorisation: potrf, panel products, trailing updates (2*144^3 flop each for the last two),
  * [12] = shared top tile columns of a distributed factorisation (0: replicated), [13] = this rank's share of the tile
  * operations below them (1 when not distributed), [14] = 1 when the landmarks are sharded by the elimination tree,
- * [15] = form of the Schur reduction in use ("schur_form") */
-int apexgpu_info(apexgpu_solver* h, double info[16]);
+ * [15] = form of the Schur reduction in use ("schur_form"), [16] = those of the trailing updates whose target is a diagonal
+ * tile (with "diag_update_lower" they compute six of their nine 48 x 48 blocks: 2*48^3*3 flop less each) */
+int apexgpu_info(apexgpu_solver* h, double info[17]);
 /* Which variant a solve asked with `asked_variant` runs on this handle (*used_variant; differs only after the automatic
  * selection of "auto_variant") and why (reason: NUL-terminated, cut to reason_len; empty when nothing was overridden).
  * The reference never needs it: its LM dispatch (src/optimizer/levenberg_marquardt.rs:1039-1082) does not depend on the
@@ -503,7 +508,7 @@ int apexgpu_debug_sinv_lists(int nt, const uint8_t* present, int64_t* rows, int 
 int apexgpu_debug_sinv_lists_direct(int nt, const int32_t* slot, int n_groups, const int32_t* group_ptr, const int32_t* group_cols,
                                     int64_t* rows, int max_rows, int64_t counts[4], char* msg, int msg_len);
 /* Tests only: the single-GPU tile Cholesky (TilePlan) on a matrix the caller chooses, in the caller's tile order (nothing is
- * reordered).  present: lower-triangular nt x nt 0/1 structure (I >= J); opts[8] = {graphs, factor_flow (max columns; 0 off,
+ * reordered).  present: lower-triangular nt x nt 0/1 structure (I >= J); opts[8] = {graphs (bit 1 set: "diag_update_lower" off), factor_flow (max columns; 0 off,
  * < 0 by cost model), factor_flow_rows, tri_dataflow, update_overlap (> 1: minimum batch), split_u1 (0 off, else minimum
  * batch), two_side, flood_gate}.  Without a visible GPU: APEXGPU_ERR_DEVICE. */
 typedef struct apexgpu_tiles apexgpu_tiles;
@@ -867,8 +872,9 @@ int apexgpu_pg_enable_stage_timing(apexgpu_pg_solver* h, int on);
 int apexgpu_pg_reset_stage_times(apexgpu_pg_solver* h);
 int apexgpu_pg_stage_times(apexgpu_pg_solver* h, double ms[APEXGPU_PG_NUM_STAGES], int64_t calls[APEXGPU_PG_NUM_STAGES]);
 /* info[0] tile rows, [1] tiles incl. fill, [2] tiles of H itself, [3] elimination-tree levels, [4] total dof,
- * [5..7] tile operations per factorisation: potrf, panel products, trailing updates */
-int apexgpu_pg_info(apexgpu_pg_solver* h, double info[8]);
+ * [5..7] tile operations per factorisation: potrf, panel products, trailing updates, [8] the updates among them whose target
+ * is a diagonal tile (apexgpu_info[16]) */
+int apexgpu_pg_info(apexgpu_pg_solver* h, double info[9]);
 int apexgpu_pg_counters(apexgpu_pg_solver* h, int64_t out[4]);   /* as apexgpu_counters */
 
 /* ---- input path (host only): G2O files ------------------------------------------------------------
