@@ -27,26 +27,30 @@ static int lockstep_solve_impl(apexgpu_solver** hs, int n, double lambda) {
             if (hipDeviceSynchronize() != hipSuccess) return APEXGPU_ERR_DEVICE;
         }
         if (phase == 5) break;
-        std::vector<std::vector<apex::Solver::DistBuf>> bufs(n);
-        std::vector<int*> flags(n, nullptr);
-        for (int r = 0; r < n; ++r) solver(r)->dist_buffers(phase, &bufs[r], &flags[r]);
-        for (size_t b = 0; b < bufs[0].size(); ++b) {
-            const size_t len = bufs[0][b].n;
-            const int root = bufs[0][b].root;
+        std::vector<apex::ExchangeList> lists(n);   // the lists production issues behind this phase (Solver::exchange)
+        for (int r = 0; r < n; ++r) lists[r] = solver(r)->exchange(phase, true);
+        for (size_t b = 0; b < lists[0].size(); ++b) {
+            const size_t len = lists[0][b].n;
+            const int root = lists[0][b].root, op = lists[0][b].op;
             for (int r = 1; r < n; ++r)
-                if (bufs[r].size() != bufs[0].size() || bufs[r][b].n != len || bufs[r][b].root != root) return APEXGPU_ERR_INVALID_STATE;
+                if (lists[r].size() != lists[0].size() || lists[r][b].op != op || lists[r][b].n != len || lists[r][b].root != root) return APEXGPU_ERR_INVALID_STATE;
             if (len == 0) continue;
+            if (op == apex::ExchangeItem::kMaxInt) {   // the failure flags: max over the ranks, on the host
+                std::vector<int> mx(len, 0), f(len);
+                for (int r = 0; r < n; ++r) {
+                    if (hipMemcpy(f.data(), lists[r][b].dev, len * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return APEXGPU_ERR_DEVICE;
+                    for (size_t i = 0; i < len; ++i) mx[i] = std::max(mx[i], f[i]);
+                }
+                for (int r = 0; r < n; ++r) if (hipMemcpy(lists[r][b].dev, mx.data(), len * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return APEXGPU_ERR_DEVICE;
+                continue;
+            }
+            auto buf = [&](int r) { return static_cast<double*>(lists[r][b].dev); };
             const int dst = root >= 0 ? root : 0;   // ncclReduce(root) / ncclAllReduce: ranks summed in rank order
             for (int r = 0; r < n; ++r)
-                if (r != dst) apex::launch_vec_add((int64_t)len, bufs[dst][b].ptr, bufs[r][b].ptr, bufs[dst][b].ptr, nullptr);
+                if (r != dst) apex::launch_vec_add((int64_t)len, buf(dst), buf(r), buf(dst), nullptr);
             if (root < 0)
                 for (int r = 1; r < n; ++r)
-                    if (hipMemcpyAsync(bufs[r][b].ptr, bufs[0][b].ptr, len * sizeof(double), hipMemcpyDeviceToDevice, nullptr) != hipSuccess) return APEXGPU_ERR_DEVICE;
-        }
-        if (flags[0]) {
-            int mx = 0;
-            for (int r = 0; r < n; ++r) { int f = 0; if (hipMemcpy(&f, flags[r], sizeof f, hipMemcpyDeviceToHost) != hipSuccess) return APEXGPU_ERR_DEVICE; mx = std::max(mx, f); }
-            for (int r = 0; r < n; ++r) if (hipMemcpy(flags[r], &mx, sizeof mx, hipMemcpyHostToDevice) != hipSuccess) return APEXGPU_ERR_DEVICE;
+                    if (hipMemcpyAsync(buf(r), buf(0), len * sizeof(double), hipMemcpyDeviceToDevice, nullptr) != hipSuccess) return APEXGPU_ERR_DEVICE;
         }
         if (hipDeviceSynchronize() != hipSuccess) return APEXGPU_ERR_DEVICE;
     }

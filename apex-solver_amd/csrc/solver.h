@@ -18,7 +18,7 @@
 #include "chol_kernels.h"
 #include "schur_jacobi_pcg.h"
 #include "schur_pairs.h"
-#include "comm.h"
+#include "rank_exchange.h"
 #include "tile_backend.h"
 
 namespace apex {
@@ -83,8 +83,9 @@ class Solver : public TileBackend {
 
     // the phases of the distributed Cholesky solve, for the single-process lockstep test (see solver.hip)
     int dist_phase(int phase, double lambda);
-    struct DistBuf { double* ptr; size_t n; int root; };   // root >= 0: the sum is needed on that rank only; -1: everywhere
-    void dist_buffers(int point, std::vector<DistBuf>* sums, int** max_flag);
+    // What the ranks exchange at point 0 (behind the assembly; for_factor as assemble() takes it) and at the plan's points 1..4
+    // (TilePlan::exchange).  assemble() and the plan issue these lists; the lockstep test plays the same ones.
+    ExchangeList exchange(int point, bool for_factor) const;
     int export_step(double* step_out, double* grad_out);
     double dist_local_fraction() const { return tp_.local_work_fraction(); }
     int dist_top_columns() const { return tp_.n_top_columns(); }
@@ -254,12 +255,11 @@ class Solver : public TileBackend {
     double cg_tol_ = 1e-6;
     int64_t n_pairs_ = 0, n_present_ = 0;
     // shard
-    int rank_ = 0, world_ = 1;
+    RankExchange ranks_;        // rank, world, the communicator and every collective (rank_exchange.h)
     int pad_rank_ = 0;          // rank that writes the identity on the padding rows of the last tile (assemble_local)
-    std::string comm_err_;      // text of the last failed collective inside TilePlan's hooks
     int64_t lm_lo_ = 0, lm_hi_ = 0;  // landmark range owned by this rank
-    std::unique_ptr<Communicator> comm_;
-    int adopt_comm(std::unique_ptr<Communicator> c, const std::string& err);
+    using MakeComm = std::function<std::unique_ptr<Communicator>(std::string* err)>;
+    int adopt_comm(int world, int rank, const MakeComm& make);   // what comm_init and comm_init_shm share
 
     // host copies
     std::vector<int> o_orig_h_;
@@ -323,7 +323,6 @@ class Solver : public TileBackend {
     DeviceBuffer<uint8_t> fix_pose_, fix_intr_, fix_pt_;
     DeviceBuffer<double> g_c_, g_red_, dcam_, hinv_, g_l_, dl_;
     DeviceBuffer<BaScalars> scal_;         // scalar outputs, by field: a device address, never read through on the host (the reduction scratch partial_ is TileBackend's)
-    DeviceBuffer<int64_t> lm_ranges_;      // [world_][2] every rank's landmark range, gathered by get_params (several ranks: adopt_comm)
     DeviceBuffer<int> flags_;              // [0] landmark inversion error
     std::vector<int> cmap_, cinv_;   // external camera -> internal camera and back
     bool hubs_last_ = true;     // order cameras covisible with > max(16, 10 sqrt(n_cam)) others last (ba_structure.h)

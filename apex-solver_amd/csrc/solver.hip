@@ -19,11 +19,8 @@ void warm_schur_pairs(hipStream_t s);
 void warm_chol_kernels(hipStream_t s);
 void warm_pcg_kernels(hipStream_t s);
 
-// every collective's result is surfaced as APEXGPU_ERR_DEVICE with the transport's own text (comm.h)
-#define COMM_TRY(expr)                                                                  \
-    do {                                                                                \
-        if (!(expr)) return fail(kDeviceError, comm_->error());                         \
-    } while (0)
+// a collective that failed is surfaced as APEXGPU_ERR_DEVICE with the transport's own text (rank_exchange.h)
+#define RANK_TRY(expr) do { const int _rc = (expr); if (_rc != kOk) return fail(_rc, ranks_.error()); } while (0)
 
 // OptimizeParams<POSE, LANDMARK, INTRINSIC> of every mode as 4 POSE + 2 LANDMARK + INTRINSIC (src/factors/mod.rs:82-101)
 int mode_mask(int mode) {
@@ -43,7 +40,7 @@ Solver::~Solver() {
     HostBlockCache::get().release();   // the last handle returns the cached blocks to the system
     hipSetDevice(device_);
     if (stream_) hipStreamSynchronize(stream_);   // (and the join above) before any buffer is freed; stream_last_ destroys the stream after them
-    comm_.reset();
+    ranks_.close();
     for (hipEvent_t e : pin_ev_) if (e) (void)hipEventDestroy(e);
 }
 
@@ -86,7 +83,7 @@ BAView Solver::view(int which) const {
     v.pt_scale = scaled_ ? pt_scale_.dev.get() : nullptr;
     v.lam_mask = tree_shard_ ? lam_mask_ : nullptr;
     v.o_slot = o_slot_; v.wg_cam_n = wg_cam_n_; v.wg_cam_list = wg_cam_list_;
-    if (world_ > 1 && lm_hi_ > lm_lo_) {   // the rank's own landmark range, in whole workgroups of kLmWg
+    if (ranks_.world() > 1 && lm_hi_ > lm_lo_) {   // the rank's own landmark range, in whole workgroups of kLmWg
         v.lm_wg0 = (int)(lm_lo_ / kLmWg);
         v.lm_wgn = (int)((lm_hi_ + kLmWg - 1) / kLmWg) - v.lm_wg0;
     }
@@ -101,39 +98,29 @@ void Solver::stage_end(int st) { timer_.end(st, stream_); }
 int Solver::set_shard(int rank, int world) {
     if (have_priors()) return fail(kInvalidState, "set_shard: the handle holds camera priors, which are single-rank only");
     if (have_structure_) return fail(kInvalidState, "set_shard must precede set_structure");
-    if (world < 1 || rank < 0 || rank >= world) return fail(kInvalidInput, "bad rank/world");
-    rank_ = rank; world_ = world;
+    RANK_TRY(ranks_.set_shard(rank, world));
     return kOk;
 }
 
-int Solver::adopt_comm(std::unique_ptr<Communicator> c, const std::string& err) {
-    if (!c) return fail(kDeviceError, err);
-    comm_ = std::move(c);
-    Communicator* cp = comm_.get();
-    TilePlan::Comm tc;
-    auto note = [this, cp](bool ok) { if (!ok) comm_err_ = cp->error(); return ok; };
-    tc.sum = [cp, note](double* buf, size_t n, hipStream_t st) { return note(cp->all_reduce_sum(buf, n, st)); };
-    tc.max_int = [cp, note](int* buf, size_t n, hipStream_t st) { return note(cp->all_reduce_max(buf, n, st)); };
-    tp_.set_comm(std::move(tc));
-    HIP_TRY(lm_ranges_.alloc(2 * (size_t)world_));
+int Solver::adopt_comm(int world, int rank, const MakeComm& make) {
+    const int rc = set_shard(rank, world);
+    if (rc != kOk) return rc;
+    HIP_TRY(hipSetDevice(device_));
+    std::string err;
+    std::unique_ptr<Communicator> c = make(&err);
+    RANK_TRY(ranks_.adopt(std::move(c), err));
+    tp_.set_comm([this](const ExchangeList& l, hipStream_t st) { return ranks_.issue(l, st) == kOk; });
+    HIP_TRY(ranks_.lm_ranges.alloc(2 * (size_t)world));
     return kOk;
 }
 
 int Solver::comm_init(int world, int rank, const void* unique_id128) {
-    int rc = set_shard(rank, world);
-    if (rc != kOk) return rc;
-    HIP_TRY(hipSetDevice(device_));
-    std::string err;
-    return adopt_comm(make_rccl_comm(world, rank, unique_id128, &err), err);
+    return adopt_comm(world, rank, [&](std::string* err) { return make_rccl_comm(world, rank, unique_id128, err); });
 }
 
 // The same multi-rank schedule over the host shared-memory transport (comm.h): ranks = processes of one node.
 int Solver::comm_init_shm(int world, int rank, const char* name) {
-    int rc = set_shard(rank, world);
-    if (rc != kOk) return rc;
-    HIP_TRY(hipSetDevice(device_));
-    std::string err;
-    return adopt_comm(make_shm_comm(world, rank, name, &err), err);
+    return adopt_comm(world, rank, [&](std::string* err) { return make_shm_comm(world, rank, name, err); });
 }
 
 // Landmark range [lo,hi) of `rank`: contiguous, balanced by observation count.  ptr[l] = number of
@@ -290,7 +277,7 @@ void Solver::choose_and_build_plan(Setup& su) {
     // error of the caller's: the reference's LM never fails on the fill of S.  The handle becomes matrix-free only by itself
     // and answers every variant with the matrix-free PCG (set_auto_variant).  The update-list rule is pure host arithmetic
     // on the replicated structure (every rank decides alike); the memory rule depends on the device and is single-rank only.
-    const bool refused_size = tp_.refused_too_large(), refused_mem = tp_.refused_no_memory() && world_ == 1, refused_cost = tp_.refused_by_cost();
+    const bool refused_size = tp_.refused_too_large(), refused_mem = tp_.refused_no_memory() && ranks_.world() == 1, refused_cost = tp_.refused_by_cost();
     if (!e.empty() && auto_variant_ && !matrix_free_only_ && (refused_size || refused_mem || refused_cost)) {
         auto_fallback_ = true; matrix_free_only_ = true;
         variant_choice_ = refused_cost ? 1 : 2;
@@ -492,7 +479,7 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     su.cam_idx = cam_idx; su.pt_idx = pt_idx; su.obs_uv = obs_uv;
     su.intr_col = intr_col; su.pose_col = pose_col; su.pt_col = pt_col;
     su.fix_pose = fix_pose; su.fix_intr = fix_intr; su.fix_pt = fix_pt;
-    su.raw_uv_wanted = world_ == 1;
+    su.raw_uv_wanted = ranks_.world() == 1;
     su.device_thread = std::thread(&Solver::device_thread_body, this, std::ref(su));
     { const int rc = validate_indices(su); if (rc != kOk) return rc; }
     su.release_device_thread(true);
@@ -509,9 +496,9 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     HostBlockCache::get().begin_setup();
     BaStructOptions& so = su.so;
     so.dc = dc_; so.use_nd = use_nd_; so.nd_leaf = nd_leaf_; so.hubs_last = hubs_last_;
-    so.rank = rank_; so.world = world_; so.dist_factor = dist_factor_; so.tree_sharding = tree_sharding_;
+    so.rank = ranks_.rank(); so.world = ranks_.world(); so.dist_factor = dist_factor_; so.tree_sharding = tree_sharding_;
     so.dist_selftest = dist_selftest_; so.schur_form = rows_form_;
-    so.device_gathers = world_ == 1;
+    so.device_gathers = ranks_.world() == 1;
     BaHostStructure& hs = *su.hs;
     // Camera order and tile structure first; then the tile plan (symbolic fill, task lists, 1.4 GB of device allocations: 0.06-
     // 0.1 s, mostly serial) is built on a thread of its own BESIDE the observation lists (0.1 s), which do not need it (round 5).
@@ -520,10 +507,7 @@ int Solver::set_structure(const uint32_t* cam_idx, const uint32_t* pt_idx, const
     tp_.set_partition(hs.part_rank, hs.part_world);
     tp_.set_own_all(hs.part_own_all);
     if (hs.part_own_all) {   // (self-test: one rank plays every owner, the exchanges are no-ops)
-        TilePlan::Comm tc;
-        tc.sum = [](double*, size_t, hipStream_t) { return true; };
-        tc.max_int = [](int*, size_t, hipStream_t) { return true; };
-        tp_.set_comm(std::move(tc));
+        tp_.set_comm([](const ExchangeList&, hipStream_t) { return true; });
     }
     nt_ = hs.nt;
     su.present_plan = hs.present;
@@ -663,7 +647,7 @@ void Solver::get_loss(int* kind, double out2[2]) const {
 int Solver::set_priors(bool intr, int64_t n, const uint32_t* cam, const double* data, const double* huber_delta, const double* weight) {
     const std::string what = intr ? "set_intrinsic_priors" : "set_pose_priors";
     if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
-    if (world_ > 1 || tp_.distributed()) return fail(kInvalidState, what + ": camera priors are single-rank only (this handle is sharded)");
+    if (ranks_.world() > 1 || tp_.distributed()) return fail(kInvalidState, what + ": camera priors are single-rank only (this handle is sharded)");
     if (!prior_count_in_range(n)) return fail(kInvalidInput, what + ": prior count out of range");
     if (n > 0 && (!cam || !data)) return fail(kInvalidInput, what + ": cam / data are NULL");
     if (intr && n > 0 && dc_ != 9)
@@ -729,22 +713,21 @@ int Solver::get_prior_residual(double* pose_r7_out, double* intr_r3_out) {
 int Solver::get_params(double* poses, double* intr, double* points) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
     HIP_TRY(hipSetDevice(device_));
-    if (comm_ && world_ > 1) {
+    if (ranks_.active()) {
         // every rank owns a contiguous landmark range: gather the owners' points everywhere
         // (ranges differ in size, so one broadcast per owner)
-        std::vector<int64_t> lo(world_ + 1);
         // all ranks compute identical cuts from the replicated structure: re-derive from pt_ptr is not
         // possible without the full lists, so exchange the range starts.
         int64_t mine[2] = {lm_lo_, lm_hi_};
-        int64_t* d_rng = lm_ranges_;
-        HIP_TRY(hipMemcpyAsync(d_rng + 2 * rank_, mine, sizeof mine, hipMemcpyHostToDevice, stream_));
-        COMM_TRY(comm_->all_gather(d_rng + 2 * rank_, d_rng, 2 * sizeof(int64_t), stream_));
-        std::vector<int64_t> rng(2 * world_);
+        int64_t* d_rng = ranks_.lm_ranges;
+        HIP_TRY(hipMemcpyAsync(d_rng + 2 * ranks_.rank(), mine, sizeof mine, hipMemcpyHostToDevice, stream_));
+        RANK_TRY(ranks_.all_gather(d_rng + 2 * ranks_.rank(), d_rng, 2 * sizeof(int64_t), stream_));
+        std::vector<int64_t> rng(2 * ranks_.world());
         HIP_TRY(hipMemcpyAsync(rng.data(), d_rng, rng.size() * 8, hipMemcpyDeviceToHost, stream_));
         HIP_TRY(hipStreamSynchronize(stream_));
-        for (int r = 0; r < world_; ++r) {
+        for (int r = 0; r < ranks_.world(); ++r) {
             const int64_t a = rng[2 * r], b = rng[2 * r + 1];
-            if (b > a) COMM_TRY(comm_->broadcast(pts_[st_.cur] + 3 * a, 3 * (b - a), r, stream_));
+            if (b > a) RANK_TRY(ranks_.broadcast(pts_[st_.cur] + 3 * a, 3 * (b - a), r, stream_));
         }
     }
     std::vector<double> hp(7 * n_cam_), hi(3 * n_cam_);
@@ -768,8 +751,7 @@ int Solver::cost(double* out) {
     stage_begin(kStCost);
     double* sumsq = &scal_.get()->cost_sumsq;
     launch_cost(view(st_.cur), partial_, n_partial_, sumsq, stream_, general_loss());
-    if (comm_ && world_ > 1)
-        COMM_TRY(comm_->all_reduce_sum(sumsq, 1, stream_));
+    RANK_TRY(ranks_.sum(sumsq, 1, stream_));
     if (have_priors()) enqueue_prior_cost(st_.cur, sumsq);
     stage_end(kStCost);
     HIP_TRY(hipGetLastError());
@@ -787,30 +769,31 @@ int Solver::assemble(double lambda, double diag_extra, bool for_factor) {
     if (matrix_free_only_) return fail(kInvalidState, "this handle was built matrix-free only (\"matrix_free_only\"): the explicit S does not exist");
     int rc = assemble_local(lambda, diag_extra, for_factor);
     if (rc != kOk) return rc;
-    if (comm_ && world_ > 1) {
+    if (ranks_.active()) {
         stage_begin(kStAllReduce);
-        // A distributed factorisation sums the shared top tiles itself, after the local levels, and a rank's local
-        // levels read its own columns only: every column's tiles are reduced to their owner (tile_plan.h).
-        const size_t te = (size_t)kNB * kNB;
-        COMM_TRY(comm_->group_start());
-        if (for_factor && tp_.distributed() && tree_shard_) {
-            // tree sharding: a rank's landmarks are exactly those that touch its columns -- its tiles are complete
-        } else if (for_factor && tp_.distributed()) {
-            for (int o = 0; o < tp_.part_world(); ++o) {
-                const std::pair<int64_t, int64_t> rg = tp_.owner_slot_range(o);
-                if (rg.second > 0)
-                    COMM_TRY(comm_->reduce_sum(tp_.tiles() + (size_t)rg.first * te, (size_t)rg.second * te, o, stream_));
-            }
-        } else {
-            COMM_TRY(comm_->all_reduce_sum(tp_.tiles(), (size_t)tp_.n_touched_slots() * te, stream_));
-        }
-        COMM_TRY(comm_->all_reduce_sum(g_red_, (size_t)n_c_pad_, stream_));
-        COMM_TRY(comm_->all_reduce_sum(g_c_, (size_t)n_c_pad_, stream_));
-        COMM_TRY(comm_->all_reduce_max(flags_, 1, stream_));  // a singular landmark block anywhere fails the solve on every rank
-        COMM_TRY(comm_->group_end());
+        RANK_TRY(ranks_.issue(exchange(0, for_factor), stream_));
         stage_end(kStAllReduce);
     }
     return assemble_finish();
+}
+
+ExchangeList Solver::exchange(int point, bool for_factor) const {
+    if (point != 0) return tp_.exchange(point);
+    const size_t te = (size_t)kNB * kNB;
+    ExchangeList l;
+    if (for_factor && tp_.distributed()) {
+        // A distributed factorisation sums the shared top tiles itself, after the local levels, and a rank's local
+        // levels read its own columns only: every column's tiles are reduced to their owner (tile_plan.h).
+        // (tree sharding: a rank's landmarks are exactly those that touch its columns -- its tiles are complete)
+        for (int o = 0; o < tp_.part_world() && !tree_shard_; ++o) {
+            const std::pair<int64_t, int64_t> rg = tp_.owner_slot_range(o);
+            l.push_back({ExchangeItem::kSum, tp_.tiles() + (size_t)rg.first * te, (size_t)rg.second * te, o});
+        }
+    } else l.push_back({ExchangeItem::kSum, tp_.tiles(), (size_t)tp_.n_touched_slots() * te, -1});
+    l.push_back({ExchangeItem::kSum, g_red_.get(), (size_t)n_c_pad_, -1});
+    l.push_back({ExchangeItem::kSum, g_c_.get(), (size_t)n_c_pad_, -1});
+    l.push_back({ExchangeItem::kMaxInt, flags_.get(), 1, -1});  // a singular landmark block anywhere fails the solve on every rank
+    return l;
 }
 
 // this rank's part of S, g_red, g_c (its landmarks), before any exchange
@@ -821,18 +804,18 @@ int Solver::assemble_local(double lambda, double diag_extra, bool for_factor) {
     stage_begin(kStAssembleCam);
     // (a tree-sharded rank that assembles for its distributed factorisation adds to its own and the top tiles only; every
     // other use of S -- PCG, exports, the ladder's diagonal -- all-reduces every touched tile and needs them all cleared)
-    HIP_TRY(tp_.zero_tiles(tree_shard_ && for_factor, for_factor && world_ == 1));   // (the fill tiles stay as they are: tile_plan.h, first_ok_)
+    HIP_TRY(tp_.zero_tiles(tree_shard_ && for_factor, for_factor && ranks_.world() == 1));   // (the fill tiles stay as they are: tile_plan.h, first_ok_)
     launch_clear3(g_red_, g_c_, n_c_pad_, flags_, 4, stream_);   // (one launch instead of three fills)
     // identity on the padding rows of the last tile (rank 0 only: the all-reduce sums the ranks)
     // (tree sharding: by the owner of the last tile column, whose tiles are never summed -- pad_rank_)
-    tp_.add_diag((int)n_c_, 0.0, rank_ == pad_rank_ ? 1.0 : 0.0);
+    tp_.add_diag((int)n_c_, 0.0, ranks_.rank() == pad_rank_ ? 1.0 : 0.0);
     stage_end(kStAssembleCam);
     stage_begin(kStAssembleLm);
     launch_landmark_reduce(dc_, v, lambda, hinv_, g_l_, flags_, nullptr, stream_, orec_, general_loss());   // (the pair kernel and the back-substitution read the projection records)
     orec_fresh_ = true;
     stage_end(kStAssembleLm);
     stage_begin(kStAssembleCam);
-    launch_cam_reduce(dc_, v, tm, cam_ptr_, cam_obs_, lambda + diag_extra, rank_ == 0 ? 1 : 0, hinv_, g_l_, 1,
+    launch_cam_reduce(dc_, v, tm, cam_ptr_, cam_obs_, lambda + diag_extra, ranks_.rank() == 0 ? 1 : 0, hinv_, g_l_, 1,
                       g_c_, g_red_, stream_, general_loss());
     if (have_priors()) {   // the prior rows of the Jacobian: block-diagonal in H_cc, so S and g_red take them as they are (before any rescaling)
         enqueue_prior_eval(st_.cur, false);
@@ -860,7 +843,7 @@ int Solver::assemble_finish() {
 int Solver::factor_now(int* failed_at, bool defer_flags) {
     stage_begin(kStFactor);
     const hipError_t fe = tp_.factor(failed_at, defer_flags);
-    if (fe != hipSuccess && !comm_err_.empty()) return fail(kDeviceError, comm_err_);
+    if (fe == hipErrorUnknown && ranks_.active()) return fail(kDeviceError, ranks_.error());   // (a collective of the plan's: tile_plan.h)
     HIP_TRY(fe);
     stage_end(kStFactor);
     return kOk;
@@ -869,7 +852,7 @@ int Solver::factor_now(int* failed_at, bool defer_flags) {
 int Solver::enqueue_sweeps() {
     stage_begin(kStTriSolve);
     const hipError_t se = tp_.solve(g_red_, dcam_, tile_work_);
-    if (se != hipSuccess && !comm_err_.empty()) return fail(kDeviceError, comm_err_);
+    if (se == hipErrorUnknown && ranks_.active()) return fail(kDeviceError, ranks_.error());
     HIP_TRY(se);
     stage_end(kStTriSolve);
     return kOk;
@@ -952,21 +935,20 @@ int Solver::assemble_implicit(double lambda) {
     orec_fresh_ = orec_ != nullptr;
     stage_end(kStAssembleLm);
     stage_begin(kStAssembleCam);
-    launch_cam_reduce(dc_, v, tilemap(), cam_ptr_, cam_obs_, lambda, rank_ == 0 ? 1 : 0, hinv_, g_l_, 1, g_c_, g_red_, stream_, general_loss());
+    launch_cam_reduce(dc_, v, tilemap(), cam_ptr_, cam_obs_, lambda, ranks_.rank() == 0 ? 1 : 0, hinv_, g_l_, 1, g_c_, g_red_, stream_, general_loss());
     launch_extract_diag_blocks(dc_, n_cam_, tilemap(), sj_pcg_.diag_blocks(), stream_);
     if (have_priors()) {   // (single rank: nothing below sums these twice)
         enqueue_prior_eval(st_.cur, false);
         launch_ba_prior_add_blocks(dc_, n_cam_, pri_diag_, pri_g_, sj_pcg_.diag_blocks(), g_c_, g_red_, stream_);
     }
     stage_end(kStAssembleCam);
-    if (comm_ && world_ > 1) {
+    if (ranks_.active()) {
         stage_begin(kStAllReduce);
-        COMM_TRY(comm_->group_start());
-        COMM_TRY(comm_->all_reduce_sum(sj_pcg_.diag_blocks(), (size_t)n_cam_ * dc_ * dc_, stream_));
-        COMM_TRY(comm_->all_reduce_sum(g_red_, (size_t)n_c_pad_, stream_));
-        COMM_TRY(comm_->all_reduce_sum(g_c_, (size_t)n_c_pad_, stream_));
-        COMM_TRY(comm_->all_reduce_max(flags_, 1, stream_));  // a singular landmark block anywhere fails the solve on every rank
-        COMM_TRY(comm_->group_end());
+        RANK_TRY(ranks_.issue({{ExchangeItem::kSum, sj_pcg_.diag_blocks(), (size_t)n_cam_ * dc_ * dc_, -1},
+                               {ExchangeItem::kSum, g_red_.get(), (size_t)n_c_pad_, -1},
+                               {ExchangeItem::kSum, g_c_.get(), (size_t)n_c_pad_, -1},
+                               {ExchangeItem::kMaxInt, flags_.get(), 1, -1}},   // a singular landmark block anywhere fails the solve on every rank
+                              stream_));
         stage_end(kStAllReduce);
     }
     stage_begin(kStAssembleCam);
@@ -986,15 +968,14 @@ int Solver::implicit_matvec(const double* x, double lam_local, double* y, bool r
     }
     launch_implicit_matvec(dc_, view(st_.cur), cam_ptr_, hinv_, lmu_, xin, lam_local, y, stream_, backsub_records(), general_loss());
     if (have_priors()) launch_ba_prior_matvec(n_c_, pri_diag_, xin, y, stream_);   // (diag(P) of assemble_implicit's evaluation, in the unscaled variables)
-    if (reduce && comm_ && world_ > 1)
-        COMM_TRY(comm_->all_reduce_sum(y, (size_t)n_c_, stream_));
+    if (reduce) RANK_TRY(ranks_.sum(y, (size_t)n_c_, stream_));
     if (scaled_) launch_vec_mul(n_c_, y, cam_scale_.dev, y, stream_);
     return check_hip(hipGetLastError(), "implicit_matvec");
 }
 
 int Solver::implicit_pcg_solve(double lambda, int max_iter, double tol) {
     stage_begin(kStFactor);
-    const double lam_local = (rank_ == 0) ? lambda : 0.0;  // the all-reduce sums the ranks' partial S p
+    const double lam_local = (ranks_.rank() == 0) ? lambda : 0.0;  // the all-reduce sums the ranks' partial S p
     // (a failed collective of the matvec ends the loop with its status, its text in err_)
     const int rc = sj_pcg_.solve(g_red_, dcam_, max_iter, tol, [&](const double* p, double* ap) { return implicit_matvec(p, lam_local, ap, true); },
                                  &last_pcg_iters_, &err_);
@@ -1021,7 +1002,7 @@ int Solver::solve_augmented(double lambda, int variant, double* step_out, double
     // ONE host wait per Cholesky solve (TileBackend::direct_solve) on a single rank.  Otherwise the host waits three times inside
     // this call -- for the landmark-inversion flag behind the assembly, for the pivot flag behind the factorisation, for the step
     // at the end -- and the GPU idles through a synchronisation plus a graph launch each time.
-    const bool speculative = one_wait_ && variant == 0 && !(comm_ && world_ > 1) && !tp_.distributed();
+    const bool speculative = one_wait_ && variant == 0 && !ranks_.active() && !tp_.distributed();
     if (speculative) {
         last_reg_ = 0.0;
     } else {
@@ -1043,7 +1024,7 @@ int Solver::finish_step(double* step_out, double* grad_out) {
     // what the LM loop asks next (step statistics, trial cost) rides on this solve's wait (tile_backend.h, eager_eval_; single
     // rank); the trial POINTS are written by the back-substitution itself
     // (a Dog-Leg solve evaluates the BLENDED step behind its tail, not the Gauss-Newton step these sweeps left)
-    const bool eager = eager_eval_ && !(comm_ && world_ > 1) && !dl_mode_;
+    const bool eager = eager_eval_ && !ranks_.active() && !dl_mode_;
     trial_pts_written_ = eager && fix_pt_ != nullptr;
     launch_back_substitute(dc_, view(st_.cur), hinv_, g_l_, dcam_, dl_, stream_, backsub_records(), trial_pts_written_ ? fix_pt_ : nullptr,
                            trial_pts_written_ ? pts_[st_.cur ^ 1] : nullptr, general_loss());
@@ -1064,7 +1045,7 @@ int Solver::finish_step(double* step_out, double* grad_out) {
 
 // camera_covariance() may invert this factor -- single rank only
 void Solver::keep_factor() {
-    if (world_ != 1 || tp_.distributed()) return;
+    if (ranks_.world() != 1 || tp_.distributed()) return;
     tp_.set_factor_valid(true);
     factor_lin_ = st_.cur;   // (commit_step flips st_.cur: the factorised cameras are then in the other set)
     factor_scaled_ = scaled_;
@@ -1081,10 +1062,10 @@ int Solver::export_step(double* step_out, double* grad_out) {
 // ---------------------------------------------------------------------------------------------
 // The distributed Cholesky solve cut into its phases, so that a test can drive the `world` instances of a
 // sharded problem in lockstep inside ONE process and play the communicator itself (capi: apexgpu_debug_lockstep_solve).
-// The production path (solve_augmented with an RCCL communicator) runs exactly these pieces with ncclAllReduce on the
-// same buffers in between.  Exchange point p follows phase p:
-//   0: each rank's column tiles (reduce to the owner), g_red, g_c   1: the top tile ranges   2: the failure flag (max)
-//   3, 4: TilePlan's exchange vector
+// The production path (solve_augmented with a communicator) runs these pieces and issues, in between, the very lists the
+// test plays: exchange(p, true) follows phase p, and it is what assemble(), TilePlan::factor and TilePlan::solve issue.
+//   0: each rank's column tiles (reduce to the owner), g_red, g_c, the landmark flag (max)   1: the top tile ranges
+//   2: the two failure words of the factorisation (max)   3, 4: TilePlan's exchange vector
 // ---------------------------------------------------------------------------------------------
 int Solver::dist_phase(int phase, double lambda) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
@@ -1134,28 +1115,6 @@ int Solver::dist_phase(int phase, double lambda) {
     }
 }
 
-void Solver::dist_buffers(int point, std::vector<DistBuf>* sums, int** max_flag) {
-    const size_t te = (size_t)kNB * kNB;
-    sums->clear(); *max_flag = nullptr;
-    if (point == 0) {
-        for (int o = 0; o < tp_.part_world() && !tree_shard_; ++o) {   // every column's tiles are reduced to their owner
-            const std::pair<int64_t, int64_t> rg = tp_.owner_slot_range(o);
-            sums->push_back({tp_.tiles() + (size_t)rg.first * te, (size_t)rg.second * te, o});
-        }
-        sums->push_back({g_red_, (size_t)n_c_pad_, -1});
-        sums->push_back({g_c_, (size_t)n_c_pad_, -1});
-    } else if (point == 1) {
-        std::pair<int64_t, int64_t> rg[2];
-        tp_.top_slot_ranges(rg);
-        for (int i = 0; i < 2; ++i)
-            if (rg[i].second > 0) sums->push_back({tp_.tiles() + (size_t)rg[i].first * te, (size_t)rg[i].second * te, -1});
-    } else if (point == 2) {
-        *max_flag = tp_.flag_dev();
-    } else if (point == 3 || point == 4) {
-        sums->push_back({tp_.exch_buffer(), (size_t)tp_.n_pad(), -1});
-    }
-}
-
 int Solver::assemble_only(double lambda) {
     if (!have_params_) return fail(kInvalidState, "Block structure not built or parameters not set");
     HIP_TRY(hipSetDevice(device_));
@@ -1176,8 +1135,7 @@ int Solver::enqueue_step_stats() {
     double* step = scal_.get()->step;   // [0..2] the camera half, [3..5] the landmark half
     launch_step_stats(n_c_, g_c_, dcam_, last_lambda_, scaled_ ? cam_scale_.dev.get() : nullptr, partial_, n_partial_, step, stream_);
     launch_step_stats(3 * n_pt_, g_l_, dl_, last_lambda_, scaled_ ? pt_scale_.dev.get() : nullptr, partial_, n_partial_, &step[3], stream_);
-    if (comm_ && world_ > 1)  // landmark part is sharded, camera part replicated
-        COMM_TRY(comm_->all_reduce_sum(&step[3], 3, stream_));
+    RANK_TRY(ranks_.sum(&step[3], 3, stream_));   // landmark part is sharded, camera part replicated
     stage_end(kStStats);
     return kOk;
 }
@@ -1196,8 +1154,7 @@ int Solver::enqueue_trial_point(double* sumsq_out) {
     trial_pts_written_ = false;
     stage_begin(kStCost);
     launch_cost(view(t), partial_, n_partial_, sumsq_out, stream_, general_loss());
-    if (comm_ && world_ > 1)
-        COMM_TRY(comm_->all_reduce_sum(sumsq_out, 1, stream_));
+    RANK_TRY(ranks_.sum(sumsq_out, 1, stream_));
     if (have_priors()) enqueue_prior_cost(t, sumsq_out);
     stage_end(kStCost);
     return kOk;
@@ -1211,8 +1168,7 @@ int Solver::parameter_norm(double* out) {
     launch_sumsq(3 * n_cam_, intr_[st_.cur], partial_, n_partial_, &sumsq[1], stream_);
     // points: in a sharded run only the owned range is current on this rank
     launch_sumsq(3 * (lm_hi_ - lm_lo_), pts_[st_.cur] + 3 * lm_lo_, partial_, n_partial_, &sumsq[2], stream_);
-    if (comm_ && world_ > 1)
-        COMM_TRY(comm_->all_reduce_sum(&sumsq[2], 1, stream_));
+    RANK_TRY(ranks_.sum(&sumsq[2], 1, stream_));
     double h[3];
     HIP_TRY(hipMemcpyAsync(h, sumsq, sizeof h, hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
@@ -1238,8 +1194,7 @@ int Solver::column_norms_sq_device() {
         enqueue_prior_eval(st_.cur, false);
         launch_vec_add(n_c_, cam_scale_.dev, pri_diag_, cam_scale_.dev, stream_);
     }
-    if (comm_ && world_ > 1)  // every rank sees all cameras but only its own landmarks
-        COMM_TRY(comm_->all_reduce_sum(cam_scale_.dev, (size_t)n_c_, stream_));
+    RANK_TRY(ranks_.sum(cam_scale_.dev, (size_t)n_c_, stream_));   // every rank sees all cameras but only its own landmarks
     return kOk;
 }
 
@@ -1311,7 +1266,7 @@ int Solver::dogleg_refusal() {
     if (!have_params_) return fail(kInvalidState, "Block structure not built or parameters not set");
     if (matrix_free_only_ || auto_fallback_)
         return fail(kInvalidState, "Dog-Leg needs the direct solve: this handle is matrix-free only (the PCG step is inexact and S is never factorised)");
-    if (world_ > 1 || tp_.distributed()) return fail(kInvalidState, "Dog-Leg: single rank only");
+    if (ranks_.world() > 1 || tp_.distributed()) return fail(kInvalidState, "Dog-Leg: single rank only");
     return kOk;
 }
 
@@ -1360,7 +1315,7 @@ int Solver::dogleg_optimize(DlConfig* cfg, LmResult* res, DlIterRecord* hist, in
 
 int Solver::jv_gram(const double* a, const double* b, double out3[3]) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
-    if (world_ > 1) return fail(kInvalidState, "jv_gram: single rank only");
+    if (ranks_.world() > 1) return fail(kInvalidState, "jv_gram: single rank only");
     return jv_gram_columns(a, b, out3);
 }
 
@@ -1412,7 +1367,7 @@ int Solver::get_schur(double* S_out, double* gred_out) {
         std::fill(S_out, S_out + nref * nref, 0.0);
         // intrinsic variables exist but no factor touches them: S_ii = lambda.  A shard without a communicator exports its
         // partial S, and the partials sum to the whole: rank 0 alone carries these entries, as in schur_matvec
-        if (rank_ == 0 || comm_)
+        if (ranks_.rank() == 0 || ranks_.has_comm())
             for (int64_t u : cam_map_.untouched) S_out[u * nref + u] = last_lambda_;
         return export_tiles_dense(cam_map_, nref, tp_.n_slots(), S_out);
     }
@@ -1440,12 +1395,12 @@ int Solver::schur_matvec(double lambda, const double* x_in, double* y_explicit, 
         int rc = pass == 0 ? assemble(lambda, 0.0) : assemble_implicit(lambda);
         if (rc != kOk) return rc;
         if (pass == 0) tp_.sym_matvec(xd, yd);
-        else implicit_matvec(xd, rank_ == 0 ? lambda : 0.0, yd, false);  // a shard's partial
+        else implicit_matvec(xd, ranks_.rank() == 0 ? lambda : 0.0, yd, false);  // a shard's partial
         HIP_TRY(hipMemcpyAsync(h.data(), yd, n_c_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
         HIP_TRY(hipStreamSynchronize(stream_));
         std::fill(out, out + nref, 0.0);
         cam_map_.scatter(h.data(), out, 0.0);
-        if (rank_ == 0)  // intrinsic variables exist but no factor touches them: S_ii = lambda
+        if (ranks_.rank() == 0)  // intrinsic variables exist but no factor touches them: S_ii = lambda
             for (int64_t u : cam_map_.untouched) out[u] = lambda * x_in[u];
     }
     return kOk;
@@ -1458,7 +1413,7 @@ int Solver::schur_matvec(double lambda, const double* x_in, double* y_explicit, 
 // rebuild the caller's factor list, the priors' diagonal, the blocks --, the assembly is the host function hessian_csc.
 int Solver::get_hessian_csc(int64_t* nnz_out, int64_t* colptr, int64_t* rowidx, double* values) {
     if (!have_params_) return fail(kInvalidState, "no parameters set");
-    if (world_ > 1) return fail(kInvalidState, "the Hessian export is single-rank");
+    if (ranks_.world() > 1) return fail(kInvalidState, "the Hessian export is single-rank");
     if (!nnz_out) return fail(kInvalidInput, "nnz_out is NULL");
     // the caller's factor list, rebuilt from the device's landmark-major lists (single rank: they hold every observation):
     // observation k of the device is the caller's o_orig[k], its camera / landmark the internal ones mapped back
@@ -1542,7 +1497,7 @@ int Solver::get_landmark_blocks(double* hinv_out, double* gl_out) {
 int Solver::camera_covariance(double* out) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
     if (!out) return fail(kInvalidInput, "cov_out is NULL");
-    if (world_ > 1 || tp_.distributed()) return fail(kInvalidState, "covariance: multi-rank handles are not supported (single rank only)");
+    if (ranks_.world() > 1 || tp_.distributed()) return fail(kInvalidState, "covariance: multi-rank handles are not supported (single rank only)");
     if (matrix_free_only_)
         return fail(kInvalidState, auto_fallback_ ? "covariance: the automatic variant selection chose the matrix-free PCG for this handle: there is no factor to invert"
                                                   : "covariance: this handle was built matrix-free only: there is no factor to invert");
@@ -1589,7 +1544,7 @@ int Solver::lc_setup() {
 int Solver::landmark_covariance(double* out) {
     if (!have_structure_) return fail(kInvalidState, "Block structure not built. Call set_structure() first.");
     if (!out) return fail(kInvalidInput, "cov_out is NULL");
-    if (world_ > 1 || tp_.distributed()) return fail(kInvalidState, "landmark covariance: multi-rank handles are not supported (single rank only)");
+    if (ranks_.world() > 1 || tp_.distributed()) return fail(kInvalidState, "landmark covariance: multi-rank handles are not supported (single rank only)");
     if (matrix_free_only_)
         return fail(kInvalidState, auto_fallback_ ? "landmark covariance: the automatic variant selection chose the matrix-free PCG for this handle: there is no factor to invert"
                                                   : "landmark covariance: this handle was built matrix-free only: there is no factor to invert");

@@ -15,8 +15,8 @@
 // columns -- latency-bound, a small fraction of the flops -- are factorised redundantly by every rank.  The
 // triangular solves follow the same pattern: local forward sweep, one n_pad-vector exchange for the top blocks,
 // replicated top sweeps, local backward sweep, one n_pad-vector exchange that assembles x on every rank.
-// factor()/solve() run the phases and call the communicator hooks in between; factor_phase()/solve_phase() expose the
-// same phases so that several instances can be driven in lockstep inside one process (tests).
+// factor()/solve() run the phases and issue the exchange lists (exchange()) through the communicator hook in between;
+// factor_phase()/solve_phase() expose the same phases so that several instances can be driven in lockstep inside one process (tests).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,6 +31,7 @@
 #include "device_buffer.h"
 #include "factor_schedule.h"
 #include "plan_lists.h"
+#include "rank_exchange.h"
 #include "tile_pcg.h"
 #include "tile_sinv.h"
 
@@ -69,10 +70,8 @@ class TilePlan : private TilePlanMemory {
     std::string build(int nt, const std::vector<uint8_t>& present, hipStream_t stream);
 
     // ---- distributed factorisation ----
-    struct Comm {  // in-place reductions over the ranks, enqueued on `stream`; false = the collective failed
-        std::function<bool(double* buf, size_t n, hipStream_t stream)> sum;
-        std::function<bool(int* buf, size_t n, hipStream_t stream)> max_int;
-    };
+    // one exchange over the ranks, in place, enqueued on `stream`; false = a collective failed (its text is with the hook's owner)
+    using Comm = std::function<bool(const ExchangeList& list, hipStream_t stream)>;
     void set_partition(int rank, int world) { opts_.rank = rank; opts_.world = world; }  // before build()
     // self-test: cut the tree for `world` ranks but let THIS rank own every subtree -- the distributed schedule
     // (local levels, top levels, phased sweeps) then runs complete on one rank with no-op exchanges
@@ -81,21 +80,19 @@ class TilePlan : private TilePlanMemory {
     bool distributed() const { return structure_.distributed(); }
     int n_top_columns() const { return structure_.n_top_cols; }
     double local_work_fraction() const { return structure_.local_frac; }  // this rank's share of the tile operations below the top
-    // tiles every rank owns a copy of after the matrix all-reduce: [0, n_reduce_slots()); in a distributed plan the
-    // top tiles are left out (they are summed after the local factorisation instead), otherwise = n_touched_slots()
-    int64_t n_reduce_slots() const { return distributed() ? structure_.n_t_nt : structure_.n_touched; }
-    // ... and inside that range the tiles of rank o's columns are contiguous: [first, first + count).  The local phase
-    // of rank o reads no other rank's columns, so a reduce to their owner (half the traffic of an all-reduce) is enough.
+    // below the top tiles (summed after the local factorisation) the tiles of rank o's columns are contiguous: [first, first + count).
+    // The local phase of rank o reads no other rank's columns, so a reduce to their owner (half the traffic of an all-reduce) is enough.
     int part_world() const { return opts_.world; }
     std::pair<int64_t, int64_t> owner_slot_range(int o) const { return structure_.own_range[o]; }
-    // the slot ranges [first, count) summed after the local phase (touched top tiles, fill top tiles)
-    void top_slot_ranges(std::pair<int64_t, int64_t> out[2]) const;
+    // What the ranks exchange at the plan's points, each following one phase below: 1 (behind factor_phase(0)) the sums of the
+    // top tiles, touched and fill; 2 (behind factor_phase(1)) the max of the factorisation's two failure words; 3, 4 (behind
+    // solve_phase(0), (1)) the sum of the exchange vector.  factor() and solve() issue these lists through the hook.
+    ExchangeList exchange(int point) const;
     void factor_phase(int phase);                  // 0: local levels, 1: top levels (after the top tiles were summed)
-    int* flag_dev() const { return flag_; }       // first failed tile column + 1 (max over the ranks after the factorisation)
-    // 0: local forward sweep, top blocks of the right-hand side packed into exch_buffer() [sum it over the ranks];
-    // 1: top sweeps + local backward sweep, this rank's blocks of x packed into exch_buffer() [sum it]; 2: x := buffer
+    int* flag_dev() const { return flag_; }       // [0] first failed tile column + 1, [1] the dataflow factorisation's error word
+    // 0: local forward sweep, top blocks of the right-hand side packed into the exchange vector [summed over the ranks];
+    // 1: top sweeps + local backward sweep, this rank's blocks of x packed into the vector [summed]; 2: x := the vector
     void solve_phase(int phase, const double* rhs, double* x, double* work);
-    double* exch_buffer() const { return exch_; }
 
     int nt() const { return structure_.nt; }
     int64_t n_pad() const { return (int64_t)structure_.nt * kNB; }

@@ -298,9 +298,15 @@ hipError_t TilePlan::read_flow_trace(std::vector<FactorUnit>* units, std::vector
     return hipMemcpy(stamps->data(), flow_trace_, 3 * n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
 }
 
-void TilePlan::top_slot_ranges(std::pair<int64_t, int64_t> out[2]) const {
-    out[0] = {structure_.n_t_nt, structure_.n_touched - structure_.n_t_nt};
-    out[1] = {structure_.n_f_nt, structure_.n_slots - structure_.n_f_nt};
+ExchangeList TilePlan::exchange(int point) const {
+    const size_t te = (size_t)kNB * kNB;
+    const auto tiles = [&](int64_t first, int64_t end) { return ExchangeItem{ExchangeItem::kSum, tiles_ + (size_t)first * te, (size_t)(end - first) * te, -1}; };
+    switch (point) {
+        case 1: return {tiles(structure_.n_t_nt, structure_.n_touched), tiles(structure_.n_f_nt, structure_.n_slots)};
+        case 2: return {{ExchangeItem::kMaxInt, flag_.get(), 2, -1}};  // a failed pivot (or a dataflow time-out) anywhere fails the factorisation everywhere
+        case 3: case 4: return {{ExchangeItem::kSum, exch_.get(), (size_t)n_pad(), -1}};
+        default: return {};
+    }
 }
 
 void TilePlan::factor_phase(int phase) {
@@ -316,15 +322,11 @@ void TilePlan::solve_phase(int phase, const double* rhs, double* x, double* work
 hipError_t TilePlan::factor(int* failed_at, bool defer_flags) {
     tiles_written();
     if (distributed()) {
-        if (!comm_.sum || !comm_.max_int) return hipErrorNotInitialized;  // a distributed plan needs its communicator
+        if (!comm_) return hipErrorNotInitialized;  // a distributed plan needs its communicator
         factor_phase(0);
-        std::pair<int64_t, int64_t> rg[2];
-        top_slot_ranges(rg);
-        const size_t te = (size_t)kNB * kNB;
-        for (int i = 0; i < 2; ++i)
-            if (rg[i].second > 0 && !comm_.sum(tiles_ + (size_t)rg[i].first * te, (size_t)rg[i].second * te, stream_)) return hipErrorUnknown;
+        if (!comm_(exchange(1), stream_)) return hipErrorUnknown;
         factor_phase(1);
-        if (!comm_.max_int(flag_, 2, stream_)) return hipErrorUnknown;  // a failed pivot (or a dataflow time-out) anywhere fails the factorisation everywhere
+        if (!comm_(exchange(2), stream_)) return hipErrorUnknown;
         return read_flags(failed_at);
     }
     if (poison_factor_) {   // (tests: the poisoned launch is not part of the captured graphs)
@@ -361,7 +363,7 @@ hipError_t TilePlan::read_flags(int* failed_at) {
 bool TilePlan::post_sweep_status(bool reduce) {
     if (!flow_flags_ || !flow_err_host_) return true;
     int* err = flow_flags_ + 2 * (size_t)structure_.nt;
-    if (reduce && comm_.max_int && !comm_.max_int(err, 1, stream_)) return false;   // (the communicator keeps its message)
+    if (reduce && comm_ && !comm_({{ExchangeItem::kMaxInt, err, 1, -1}}, stream_)) return false;   // (the hook's owner keeps the message)
     if (!reduce && flow_err_host_dev_) { launch_post_word(err, flow_err_host_dev_, stream_); return true; }   // (one launch, no copy engine)
     (void)hipMemcpyAsync(flow_err_host_, err, sizeof(int), hipMemcpyDeviceToHost, stream_);
     (void)hipMemsetAsync(err, 0, sizeof(int), stream_);
@@ -389,11 +391,11 @@ hipError_t TilePlan::debug_occupy_cus(int n_cus, int micros) {
 
 hipError_t TilePlan::solve(const double* rhs, double* x, double* work) {
     if (distributed()) {
-        if (!comm_.sum) return hipErrorNotInitialized;
+        if (!comm_) return hipErrorNotInitialized;
         solve_phase(0, rhs, x, work);
-        if (!comm_.sum(exch_, (size_t)n_pad(), stream_)) return hipErrorUnknown;
+        if (!comm_(exchange(3), stream_)) return hipErrorUnknown;
         solve_phase(1, rhs, x, work);
-        if (!comm_.sum(exch_, (size_t)n_pad(), stream_)) return hipErrorUnknown;
+        if (!comm_(exchange(4), stream_)) return hipErrorUnknown;
         solve_phase(2, rhs, x, work);
         // (the collective is entered by every rank or by none: tri_flow_ is a plan-wide setting, and a distributed plan has
         // dataflow tasks on every rank -- at least the fold tasks of the shared top columns)
